@@ -1,11 +1,20 @@
 #!/usr/bin/env python3
 """bench.py — SpMM GFLOP/s (= 2*nnz*N/t) and achieved HBM GB/s against the roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE launch of the hot path (C = A @ B, valued CSR x dense fp32) over one resident batch of
 synthetic input — what the reference's driver times 200x per width (spmm_test.cu:754-762).
+
+A plain run does what the headline figure needs and nothing else: it generates the seeded operands, makes the
+plan once, warms up (the 200 launches of the full run's per-launch statistic run untimed, then the W warm-up
+steps, so that both modes start the timed region alike), times the K steps and prints the line (`value`, `ms_per_step` and the roofline priced with
+the timed region). `--full` adds every side measurement and check described below: the median of per-launch
+event pairs, the plan timed three times, the copy-rate yardstick and the ceilings it prices, the sampled-row
+check against the CPU oracle, the other widths, graphs and configurations, the driver and reference-kernel legs,
+and the CPU baselines (`--no-extra` / `--no-cpu-baseline` trim a `--full` run). `--dump-outputs DIR` writes, after
+the timed steps, what the last step handed its caller (C, or a fixed seeded sample of its rows) as .npy files.
 
 One GPU (the BENCH line): BASELINE.json configs[1], the com-Amazon-shaped graph (M = K = 334 863,
 nnz = 1 851 744) at feature width 128 as a seeded synthetic stand-in (no network: SURVEY.md §8 d4) — since round 3
@@ -54,6 +63,7 @@ STEADY_STATE = 1000000    # expected_launches of a plan whose analysis always pa
 COPY_RATE_GUIDE_GBS = 6290.0  # MI355X_MICROARCH.md:35 — measured copy rate of the chip; the sanity bound for the rate measured in the run
 LINE_LIMIT = 4096  # the final stdout line stays below this; everything else goes to EXTRA_FILE (and to stderr)
 EXTRA_FILE = os.path.join("profiles", "bench_extra_last.json")
+DUMP_BYTES = 60 * 1000 * 1000  # --dump-outputs writes at most this much (C whole, or a seeded sample of its rows)
 
 
 def self_launch_argv(n, argv):
@@ -65,6 +75,22 @@ def self_launch_argv(n, argv):
         port = sk.getsockname()[1]
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
             "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
+
+
+def dump_outputs(dirname, C, seed=0):
+    """--dump-outputs: the (M, N) fp32 product the timed path handed its caller in its last step, as DIR/C_sample.npy, and the
+    rows it holds as DIR/C_sample_rows.npy (float64). All of C when it fits in DUMP_BYTES, else a fixed seeded sample of rows in
+    ascending order — the same rows for the same arguments, so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+
+    M, N = int(C.shape[0]), int(C.shape[1])
+    keep = max(1, DUMP_BYTES // (4 * N + 8))
+    rows = np.arange(M) if M <= keep else np.sort(np.random.RandomState(seed).choice(M, keep, replace=False))
+    sample = C[torch.from_numpy(rows.astype(np.int64)).to(C.device)].cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "C_sample.npy"), sample)
+    np.save(os.path.join(dirname, "C_sample_rows.npy"), rows.astype(np.float64))
 
 
 def _r(x, nd=4):
@@ -265,12 +291,16 @@ class BenchEnv:
         return float(t.item())
 
     def timed_region(self, fn, steps, warmup):
-        for _ in range(warmup):
-            fn()
-        self.sync_all()
         ev = None
         if self.cuda:  # one pair of HIP events around the K timed steps, on the launch stream (torch's current stream)
             ev = (self.torch.cuda.Event(enable_timing=True), self.torch.cuda.Event(enable_timing=True))
+            # torch makes a HIP event at its first record: here, not inside the timed window (a process that has timed nothing
+            # before paid ~50 us for it inside the window: +2.5 us per step at --steps 20)
+            ev[0].record()
+            ev[1].record()
+        for _ in range(warmup):
+            fn()
+        self.sync_all()
         t0 = time.perf_counter()
         if ev:
             ev[0].record()
@@ -330,13 +360,31 @@ def main():
     ap.add_argument("--variant", type=int, default=-1)
     ap.add_argument("--locality", type=float, default=0.0, help="fraction of id-local edges in the stand-in")
     ap.add_argument("--no-plan", action="store_true", help="time the plain entry point as the headline")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (per-launch statistics, plan timing, copy rate and ceilings, "
+                         "oracle check, other widths / graphs / configurations, driver and reference legs, CPU baselines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/*.npy (at most 64 MB)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--panel-cols", type=int, default=128, help="column panel of the exchange/compute pipeline")
     ap.add_argument("--expected-launches", type=int, default=0,
                     help="expected_launches of the headline plan (0 = the library's default, 200 = the reference's protocol)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the several-GPU run (nccl = RCCL on ROCm)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # `python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run ... bench.py --gpus N ...` as a child
+        # (one process per GPU; rendezvous on 127.0.0.1, a free port) — the line the ranks print is the same either way. This
+        # process has not touched the device (nothing above imports torch or the library).
+        import subprocess
+
+        raise SystemExit(subprocess.call(self_launch_argv(args.gpus, sys.argv[1:])))
 
     import torch
     import torch.distributed as dist
@@ -348,13 +396,6 @@ def main():
     # default keeps 1 GiB; a multi-GB hipMalloc was seen to take seconds now and then: profiles/r03/plan_repeat.log)
     _lib.set_cached_memory_limit(16 << 30)
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become `python -m torch.distributed.run ... bench.py --gpus N ...`
-        # (one process per GPU; rendezvous on 127.0.0.1, a free port) — the line the ranks print is the same either way
-        os.execv(sys.executable, self_launch_argv(args.gpus, sys.argv[1:]))
     if world != args.gpus:
         raise SystemExit("bench.py --gpus %d under a launcher with WORLD_SIZE=%d" % (args.gpus, world))
     if not torch.cuda.is_available():
@@ -382,10 +423,11 @@ def main():
     env = BenchEnv(torch, dist, dev, world, rank, use_dist, variant=args.variant)
     sync_all, make_B, kernel_times_us, timed_region, verify = env.sync_all, env.make_B, env.kernel_times_us, env.timed_region, env.verify
 
-    def measure_graph(g, val, N, valued=True, use_plan=True, samples=MIN_KERNEL_SAMPLES, keep=False, expected_launches=0):
+    def measure_graph(g, val, N, valued=True, use_plan=True, samples=MIN_KERNEL_SAMPLES, keep=False, expected_launches=0, plan_reps=3):
         """Median kernel time of one (graph, width) through a plan (or the plain entry point). `expected_launches` goes to the plan:
         0 = the library's default, 200 (the reference's protocol) — an AUTO plan then skips an analysis that 200 launches would
-        not pay for; STEADY_STATE = the kernel a long-running caller gets (what `widths` reports)."""
+        not pay for; STEADY_STATE = the kernel a long-running caller gets (what `widths` reports). The plain run's headline asks
+        for samples = 0 and plan_reps = 1: operands, one plan and the step, nothing measured beside them."""
         M, K, nnz = g["M"], g["K"], g["nnz"]
         B = make_B(K, N)
         C = torch.empty((M, N), dtype=torch.float32, device=dev)
@@ -396,14 +438,14 @@ def main():
             # the analysis stage (on the device): timed three times — the first creation in a process also pays for
             # loading the analysis kernels and growing the library's memory pool; `plan_ms` is the best of the other two
             times = []
-            for _ in range(3):
+            for _ in range(plan_reps):
                 plan = None
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 plan = spmm.SpmmPlan(g["rowptr"], g["colind"], K, N, variant=args.variant, values=v, expected_launches=expected_launches)
                 torch.cuda.synchronize()
                 times.append((time.perf_counter() - t0) * 1e3)
-            plan_first_ms, plan_ms = times[0], min(times[1:])
+            plan_first_ms, plan_ms = times[0], (min(times[1:]) if len(times) > 1 else None)
             what = plan.describe()
 
         def step():
@@ -414,6 +456,9 @@ def main():
 
         for _ in range(5):
             step()
+        if samples == 0:
+            out = {"plan_ms_first_creation": plan_first_ms, "plan": what} if use_plan else {}
+            return (out, step, B, C, plan) if keep else out
         us = kernel_times_us(step, samples)
         ab = algorithmic_bytes(M, K, N, nnz, valued)
         med = statistics.median(us)
@@ -458,7 +503,7 @@ def main():
                     "measured_GBs": gbs}
         return {"GBs": gbs, "how": how, "measured_GBs": gbs}
 
-    copy_rate = None if strong else measure_copy_rate()  # (the several-GPU mode prices no ceiling)
+    copy_rate = measure_copy_rate() if args.full and not strong else None  # (the several-GPU mode prices no ceiling)
 
     def ceiling_for(gx, n, frac):
         """Where the planted structure of a stand-in caps `frac`: inside a planted unit (perfect reuse inside, none across: the edges that
@@ -528,7 +573,7 @@ def main():
 
     # =============================================================================================== several GPUs
     if strong:
-        out = run_rmat(args, env, N)
+        out = run_rmat(args, env, N, full=args.full)
         if rank == 0:
             emit(out)
         if use_dist:
@@ -543,16 +588,24 @@ def main():
     gen.manual_seed(7 + rank)
     val = torch.rand(nnz, generator=gen, device=dev) - 0.5
 
-    head, step, B, C, plan = measure_graph(g, val, N, True, use_plan=not args.no_plan, keep=True, expected_launches=args.expected_launches)
+    head, step, B, C, plan = measure_graph(g, val, N, True, use_plan=not args.no_plan, keep=True, expected_launches=args.expected_launches,
+                                           samples=MIN_KERNEL_SAMPLES if args.full else 0, plan_reps=3 if args.full else 1)
+    if not args.full:
+        # the launches of the per-launch statistic a --full run takes here, untimed, so that both modes start the timed region from the
+        # same device state (without them a region of 200 steps read 0.7 % slower, 0.0822 against 0.0815 ms per step; 5000 steps did not)
+        for _ in range(MIN_KERNEL_SAMPLES):
+            step()
     wall = timed_region(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, C)
     flop_per_step = 2.0 * nnz * N * world  # weak scaling: every rank owns one graph of this size
     value = flop_per_step * args.steps / wall / 1e9
     ms_per_step = wall / args.steps * 1e3
-    verified = verify(g["rowptr"], g["colind"], val, B, C) if rank == 0 else None
+    verified = verify(g["rowptr"], g["colind"], val, B, C) if rank == 0 and args.full else None
     abytes = algorithmic_bytes(M, K, N, nnz, True)
     # the line's roofline is priced with the average launch duration over the timed region (HIP events around the K steps); the median
     # of per-launch event pairs (what the other entries of this record use: they are not timed as a region) stays beside it
-    head["kernel_us_median_of_pairs"] = head["kernel_us"]
+    head["kernel_us_median_of_pairs"] = head.get("kernel_us")
     head["kernel_us"] = env.region_event_us
     head["achieved_GBs"] = abytes / head["kernel_us"] / 1e3
     head["frac"] = head["achieved_GBs"] / HBM_PEAK_GBS
@@ -566,7 +619,7 @@ def main():
     widths = {}   # the metric's other widths on the headline graph
     reference_kernel = None
     stateless = None
-    if not args.no_extra and world == 1:
+    if args.full and not args.no_extra and world == 1:
         # the plain entry point on the same operands (what a caller without a plan gets; r01's headline)
         def plain():
             spmm.csr_spmm(g["rowptr"], g["colind"], val, B, variant=args.variant, out=C)
@@ -817,7 +870,7 @@ def main():
             free_b, _ = torch.cuda.mem_get_info()
             rscale = 26 if free_b > (170 << 30) else 24
             rargs = argparse.Namespace(**vars(args))
-            rargs.rmat_scale, rargs.steps, rargs.warmup = rscale, 5, 2
+            rargs.rmat_scale, rargs.steps, rargs.warmup, rargs.dump_outputs = rscale, 5, 2, None
             rline = run_rmat(rargs, BenchEnv(torch, dist, dev, 1, 0, False, variant=args.variant), 256,
                              with_cpu_baseline=not args.no_cpu_baseline)
             extra["rmat-%d_N256_valued" % rscale] = {
@@ -892,7 +945,7 @@ def main():
             extra["reference_kernels_on_this_gpu_N%d" % N] = {"skipped": "%s: %s" % (type(ex).__name__, str(ex)[:200])}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baselines(graphs, torch, g, val, N, graph, quick=args.no_extra)
 
     if rank == 0:
@@ -936,12 +989,12 @@ def main():
                 "l2_hit_rate": l2_hit,
                 "algorithmic_bytes_per_launch": abytes,
                 "kernel_us": head["kernel_us"],
-                "launches": head["launches"],
+                "launches": head.get("launches"),
                 "kernel_us_stat": "average over the %d launches of the timed region, one HIP event pair around the region" % args.steps,
                 "kernel_us_median_of_pairs": head["kernel_us_median_of_pairs"],
-                "kernel_us_mean": head["kernel_us_mean"],
-                "kernel_us_min": head["kernel_us_min"],
-                "roof_gflops": head["roof_gflops"],
+                "kernel_us_mean": head.get("kernel_us_mean"),
+                "kernel_us_min": head.get("kernel_us_min"),
+                "roof_gflops": roof_gflops(M, K, N, nnz, True),
                 "gflops_kernel": head["gflops"],
                 # diagnostic: B-row gathers without reuse, 4*nnz*N bytes, and their rate
                 "gather_bytes_per_launch": 4 * nnz * N,
@@ -1159,9 +1212,11 @@ def rmat_cpu_baseline(torch, g, N):
                       (len(rows), 100.0 * len(rows) / M, fl / 1e9, len(cols_u))}
 
 
-def run_rmat(args, env, N, with_cpu_baseline=False):
+def run_rmat(args, env, N, with_cpu_baseline=False, full=True):
     """ONE RMAT graph, nnz-balanced contiguous row shards, B replicated by all-gather: the north_star experiment.
-    `env` (BenchEnv) carries the device, the process group and the product — see its docstring."""
+    `env` (BenchEnv) carries the device, the process group and the product — see its docstring. `full` = False (a plain
+    `bench.py` run) times the kernel-only loop and nothing beside it: no per-launch event pairs (their launches run untimed; the
+    roofline is priced with the timed region, as the one-GPU line is), no sampled-row check, no end-to-end panel pipeline."""
     from gespmm_amd import dist as gdist
     from gespmm_amd import graphs
 
@@ -1200,11 +1255,18 @@ def run_rmat(args, env, N, with_cpu_baseline=False):
 
     for _ in range(max(args.warmup, 1)):
         step()
-    us = env.kernel_times_us(step, max(args.steps, 5))
+    if full:
+        us = env.kernel_times_us(step, max(args.steps, 5))
+    else:  # the same launches untimed: both modes start the timed region from the same device state (see main())
+        us = None
+        for _ in range(max(args.steps, 5)):
+            step()
     wall = env.timed_region(step, args.steps, 0)
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, C)
     value = 2.0 * nnz_total * N * args.steps / wall / 1e9
-    med = statistics.median(us)
-    verified = env.verify(rowptr, colind, val, B, C, nrows=256, tolerant=True) if rank == 0 else None
+    med = statistics.median(us) if full else env.region_event_us
+    verified = env.verify(rowptr, colind, val, B, C, nrows=256, tolerant=True) if rank == 0 and full else None
     if env.on_local_product is not None:  # (the CPU suite gathers the shards' rows and compares them with the unsharded product)
         env.on_local_product(g, val, B, C)
     abytes = algorithmic_bytes(M, K, N, nnz, True)
@@ -1216,9 +1278,9 @@ def run_rmat(args, env, N, with_cpu_baseline=False):
     e2e = None
     pc = max(4, min(args.panel_cols, N))
     need = 4.0 * ((k1 - k0) * N + 2 * K * pc + M * N) * 1.02  # panel copies of the shard, two panel buffers, C panels
-    if use_dist and need > env.free_bytes() + 4.0 * K * N:
+    if full and use_dist and need > env.free_bytes() + 4.0 * K * N:
         e2e = {"skipped": "panel buffers exceed free HBM at this scale on %d GPU(s)" % world}
-    elif use_dist:
+    elif full and use_dist:
         def end_to_end():
             nonlocal B, plan
             del B, plan
@@ -1285,7 +1347,8 @@ def run_rmat(args, env, N, with_cpu_baseline=False):
         "roofline": {
             "bound": "hbm", "achieved": abytes / med / 1e3, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": abytes / med / 1e3 / HBM_PEAK_GBS,
             "traffic": None, "algorithmic_bytes_per_launch": abytes, "kernel_us": med,
-            "kernel_us_stat": "median of %d event pairs around %d launch(es) each (rank 0)" % (len(us), env.launches_per_event_pair),
+            "kernel_us_stat": ("median of %d event pairs around %d launch(es) each (rank 0)" % (len(us), env.launches_per_event_pair) if full
+                               else "average over the %d launches of the timed region, one HIP event pair around the region (rank 0)" % args.steps),
             "gather_bytes_per_launch": 4 * nnz * N, "gather_GBs": 4.0 * nnz * N / med / 1e3,
         },
         "exchange": {

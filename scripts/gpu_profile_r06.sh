@@ -33,9 +33,9 @@ sed -i "s#gpurun_out/pmc_#profiles/r06/pmc_#g" profiles/hbm_traffic.json; cp pro
 for t in bench_sbm_plan bench_sbm_plain bench_like_plan bench_like_plain bench_sbm_plan_N32 bench_sbm_plan_N64 bench_sbm_plan_N512 bench_sbm_plan_N100 bench_sbm_plan_N200 products_sbm_staged products_sbm_staged_N512 reddit_sbm_plan rmat24_plain_N256; do
   echo "== $t"; grep -E "FETCH_SIZE|WRITE_SIZE|TCC_HIT_sum|TCC_MISS_sum|TCC_EA0_RDREQ_sum" gpurun_out/pmc_$t/summary.csv | cut -d, -f1,6- | cut -c1-200; grep -E "spmm_" gpurun_out/pmc_$t/kernel_stats.csv | cut -c1-200; done > $O/pmc_digest.log 2>&1
 P=/tmp/prof_bench; rm -rf $P; mkdir -p $P
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P -o b -- python bench.py > $O/bench_under_profiler.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P -o b -- python bench.py --full > $O/bench_under_profiler.log 2>&1
 f=$(find $P -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_default_kernel_stats.csv
-( time python bench.py > $O/bench_round6.log 2> $O/bench_round6.err ) 2> $O/bench_round6.time
+( time python bench.py --full > $O/bench_round6.log 2> $O/bench_round6.err ) 2> $O/bench_round6.time
 cp profiles/bench_extra_last.json $O/bench_extra_round6.json
 ( time python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --graph rmat --rmat-scale 24 --steps 5 --warmup 2 ) > $O/bench_rmat24_torchrun1.log 2>&1
 timeout 600 python scripts/plan_ms.py com-amazon-sbm com-amazon-like pubmed-like products-sbm 2>&1 | grep -v amdgpu | cut -c1-400 > $O/plan_ms.log

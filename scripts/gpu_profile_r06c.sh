@@ -27,9 +27,9 @@ python scripts/update_traffic_json.py \
   > $O/update_traffic.log 2>&1
 sed -i "s#gpurun_out/pmc_#profiles/r06/pmc_#g" profiles/hbm_traffic.json; cp profiles/hbm_traffic.json $O/hbm_traffic.json
 P=/tmp/prof_bench; rm -rf $P; mkdir -p $P
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P -o b -- python bench.py > $O/bench_under_profiler.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $P -o b -- python bench.py --full > $O/bench_under_profiler.log 2>&1
 f=$(find $P -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_default_kernel_stats.csv
-( time python bench.py > $O/bench_round6.log 2> $O/bench_round6.err ) 2> $O/bench_round6.time
+( time python bench.py --full > $O/bench_round6.log 2> $O/bench_round6.err ) 2> $O/bench_round6.time
 cp profiles/bench_extra_last.json $O/bench_extra_round6.json
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 timeout 2400 python -m pytest tests -m gpu -q -rs > $O/pytest_gpu_final.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu_final.log

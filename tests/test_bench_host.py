@@ -92,3 +92,63 @@ def test_self_launch_command_line():
     assert argv[argv.index("--nproc-per-node") + 1] == "8" and argv[argv.index("--master-addr") + 1] == "127.0.0.1"
     assert 1024 < int(argv[argv.index("--master-port") + 1]) < 65536
     assert argv[-5] == os.path.join(ROOT, "bench.py") and argv[-4:] == ["--gpus", "8", "--steps", "5"]
+
+
+def test_bench_options_full_and_dump_outputs():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+    assert not any(line.startswith("{") for line in r.stdout.splitlines())
+
+
+def test_plain_run_rmat_and_dump_outputs(tmp_path, pkg, oracle):
+    """A plain run's several-GPU mode with one rank on the host (the checker injected as the product, as in
+    tests/test_graphs_and_dist.py): the kernel-only loop and its line, nothing measured beside it; `--dump-outputs` writes the
+    product of the last step — all of C when it fits, a fixed seeded sample of rows when it does not — as float32 / float64."""
+    import argparse
+
+    import numpy as np
+
+    bench = _load_bench()
+    calls = []
+
+    def host_product(rowptr_, colind_, val_, B_, out):
+        calls.append(1)
+        out.copy_(torch.from_numpy(oracle.spmm(rowptr_.numpy(), colind_.numpy(), val_.numpy(), B_.contiguous().numpy(), "fma")))
+        return out
+
+    seen = {}
+
+    def on_local_product(g, val, B, C):
+        seen["C"] = C.numpy().copy()
+
+    env = bench.BenchEnv(torch, None, "cpu", 1, 0, False, product=host_product, on_local_product=on_local_product)
+    args = argparse.Namespace(rmat_scale=10, edge_factor=8, steps=3, warmup=2, panel_cols=8, variant=-1,
+                              dump_outputs=str(tmp_path / "whole"))
+    out = bench.run_rmat(args, env, 16, full=False)
+    # the untimed launches of the --full run's per-launch statistic (same device state before the region), warm-up, timed steps
+    assert len(calls) == max(args.steps, 5) + args.warmup + args.steps, "a plain run launches the step and nothing else"
+    line = json.loads(bench.compact_line(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3
+    assert out["verified_vs_oracle"] is None and out["exchange"]["end_to_end"] is None
+    C = np.load(tmp_path / "whole" / "C_sample.npy")
+    rows = np.load(tmp_path / "whole" / "C_sample_rows.npy")
+    assert C.dtype == np.float32 and rows.dtype == np.float64
+    assert np.array_equal(rows, np.arange(1 << 10)) and np.array_equal(C.view(np.uint32), seen["C"].view(np.uint32))
+
+    # a product larger than the limit: the same seeded rows every time, ascending, within the limit
+    big = torch.arange(4000 * 3, dtype=torch.float32).reshape(4000, 3)
+    limit = bench.DUMP_BYTES
+    try:
+        bench.DUMP_BYTES = 1000 * (4 * 3 + 8)
+        for d in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / d), big)
+    finally:
+        bench.DUMP_BYTES = limit
+    ra, rb = np.load(tmp_path / "a" / "C_sample_rows.npy"), np.load(tmp_path / "b" / "C_sample_rows.npy")
+    assert ra.shape == (1000,) and np.array_equal(ra, rb) and np.all(np.diff(ra) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "C_sample.npy"), big.numpy()[ra.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64 * 1000 * 1000
