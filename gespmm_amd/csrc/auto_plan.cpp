@@ -5,7 +5,9 @@
 // hold a gespmm_plan, so on a graph with structure it stays at the plain kernels' rate (0.30 of the roofline on the headline graph
 // against 0.50 through a plan). gespmm_set_auto_plan(k) lets the library keep the plan instead:
 //
-//   * a small cache keyed on what the caller passes — device, the rowptr / colind pointers, M, K, N, valued?, variant, reducer;
+//   * a small cache keyed on what the caller passes — device, STREAM, the rowptr / colind pointers, M, K, N, valued?, variant, reducer
+//     (the stream: each stream's calls have a plan, a device-side check state and a record of their own, so nothing of one entry is
+//     touched by two streams — see "streams and in-place changes" below);
 //   * pointer identity is not pattern identity, so every call that would use a cached plan first runs a FINGERPRINT of the arrays on
 //     the device (one kernel: position-mixed 64-bit sums over ALL of rowptr and colind, separately over the values; rowptr[M]; the
 //     largest column) and reads 32 bytes back — one stream synchronisation, which the DGL entry points perform anyway to learn nnz.
@@ -17,6 +19,18 @@
 //     the plain path, nothing else).
 //
 // A plan changes the ORDER rows are processed in, not the sums: the bits are the plain call's (tests/test_gpu_auto_plan.py).
+//
+// Streams and in-place changes (round 7; tests/test_gpu_auto_plan_streams.py). The contract is the plain call's bits for the operands as
+// they are at that point in STREAM order, whatever the host has or has not waited for:
+//   * an entry belongs to one stream (the stream is part of the key). Everything the cached plan's value tables, the guard word, the
+//     check's partial sums and ticket, and the record are changed by is enqueued on that stream, so stream order alone orders them with
+//     the caller's own work. Two streams on one graph hold two plans (two entries of the eight);
+//   * the value tables are only ever re-permuted right after a synchronous fingerprint, and the fingerprint the device compares against
+//     is the one just taken. A record that reports changed values is NOT adopted (the values it saw may have changed again since — by
+//     work that is already queued): the call that reads it takes the synchronous path;
+//   * the check state is zeroed on the stream whenever a plan is made;
+//   * the record is a seqlock: the device stores an odd sequence word before the fields and the even one after them; the host accepts a
+//     record only when it reads the same even word before and after the fields.
 
 #include <hip/hip_runtime.h>
 
@@ -41,6 +55,7 @@ constexpr int kAutoDevices = 16;
 struct AutoEntry {
     bool used = false;
     int device = 0;
+    void* stream = nullptr;  // the one stream this entry's plan, check state and record are used on
     const int32_t* rowptr = nullptr;
     const int32_t* colind = nullptr;
     int64_t M = 0, K = 0, N = 0;
@@ -56,7 +71,8 @@ struct AutoEntry {
     // asynchronous mode (below): the plan's launch and the plain launch are one kernel each, so both can sit behind a device-side guard
     bool async_ok = false;
     int32_t* guard_word = nullptr;              // device: 1 = the arrays still have the plan's fingerprint (written by k_fingerprint_check)
-    unsigned long long* rec = nullptr;          // pinned + mapped host record {seq, pattern, values, nnz, match} of the latest finished check
+    unsigned long long* rec = nullptr;          // pinned + mapped host record {2 seq, pattern, values, nnz, match} of the latest finished check
+                                                // (rec[0] = 2 seq - 1 while check seq stores the fields: a seqlock)
     unsigned long long* rec_dev = nullptr;
     unsigned long long seq_launched = 0, seq_seen = 0;
 };
@@ -250,29 +266,33 @@ __global__ void __launch_bounds__(256) k_fingerprint_check(const int32_t* __rest
             slots[4 * kFpCheckSlots] = 0;
             const bool match = a0 == want_pattern && nnz == want_nnz && (!val || a1 == want_values);
             *guard_word = match ? 1 : 0;
+            __hip_atomic_store(&rec[0], 2 * seq - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);  // odd: the fields are being written
+            __threadfence_system();
             rec[1] = a0;
             rec[2] = a1;
             rec[3] = (unsigned long long)nnz;
             rec[4] = match ? 1ull : 0ull;
             __threadfence_system();
-            __hip_atomic_store(&rec[0], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&rec[0], 2 * seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
 
-hipError_t async_setup(AutoEntry& en, int dev) {
+hipError_t async_setup(AutoEntry& en, int dev, hipStream_t st) {
     if (dev < 0 || dev >= kAutoDevices) return hipErrorInvalidDevice;
-    // per ENTRY: guard word + the check's partial sums and ticket (zero between launches: the last workgroup clears them) — two keys on
-    // two streams may have their checks in flight together
+    // per ENTRY (= per stream): guard word + the check's partial sums and ticket (zero between launches: the last workgroup clears them)
     constexpr size_t kBytes = kGuardBytes + ((size_t)kFpCheckSlots * 4 + 1) * 8;
     if (!en.guard_word) {
         hipError_t e = hipMalloc(reinterpret_cast<void**>(&en.guard_word), kBytes);
-        if (e == hipSuccess) e = hipMemset(en.guard_word, 0, kBytes);
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&en.rec), 64, hipHostMallocMapped);
         if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&en.rec_dev), en.rec, 0);
         if (e != hipSuccess) return e;
         std::memset(en.rec, 0, 64);
     }
+    // zeroed for every plan, on the entry's stream (in front of the plan's first check), not only at the allocation: whatever an earlier
+    // plan's checks left behind is not inherited
+    hipError_t e = hipMemsetAsync(en.guard_word, 0, kBytes, st);
+    if (e != hipSuccess) return e;
     // records of checks launched for an earlier plan of this key are history (drop_plan has waited for them): sequence numbers go on
     en.seq_seen = en.seq_launched;
     return hipSuccess;
@@ -315,7 +335,7 @@ bool auto_plan_try(const int32_t* rowptr, const int32_t* colind, const float* va
     AutoEntry* en = nullptr;
     AutoEntry* victim = &g_entries[0];
     for (AutoEntry& e : g_entries) {
-        if (e.used && e.device == dev && e.rowptr == rowptr && e.colind == colind && e.M == M && e.K == K && e.N == N &&
+        if (e.used && e.device == dev && e.stream == stream && e.rowptr == rowptr && e.colind == colind && e.M == M && e.K == K && e.N == N &&
             e.valued == (val != nullptr) && e.variant == variant && e.reduce == reduce) {
             en = &e;
             break;
@@ -328,6 +348,7 @@ bool auto_plan_try(const int32_t* rowptr, const int32_t* colind, const float* va
         *victim = AutoEntry();
         victim->used = true;
         victim->device = dev;
+        victim->stream = stream;
         victim->rowptr = rowptr;
         victim->colind = colind;
         victim->M = M;
@@ -348,31 +369,30 @@ bool auto_plan_try(const int32_t* rowptr, const int32_t* colind, const float* va
 
     // ---- asynchronous mode: nothing comes back to the host before the launch (see k_fingerprint_check)
     if (en->plan && en->async_ok && val == en->val_seen) {
-        // what the checks of earlier calls found (whatever has landed; seqlock: seq, fields, seq again)
+        // what the checks of earlier calls found (whatever has landed; seqlock: an even word, the fields, the same word again)
+        bool values_changed = false;
         const unsigned long long done = __atomic_load_n(&en->rec[0], __ATOMIC_ACQUIRE);
-        if (done > en->seq_seen) {
-            const unsigned long long r_pat = en->rec[1], r_val = en->rec[2], r_nnz = en->rec[3], r_match = en->rec[4];
-            if (__atomic_load_n(&en->rec[0], __ATOMIC_ACQUIRE) == done) {
-                en->seq_seen = done;
+        if ((done & 1) == 0 && done / 2 > en->seq_seen) {
+            const unsigned long long r_pat = __atomic_load_n(&en->rec[1], __ATOMIC_RELAXED), r_nnz = __atomic_load_n(&en->rec[3], __ATOMIC_RELAXED),
+                                     r_match = __atomic_load_n(&en->rec[4], __ATOMIC_RELAXED);
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            if (__atomic_load_n(&en->rec[0], __ATOMIC_RELAXED) == done) {
+                en->seq_seen = done / 2;
                 if (!r_match) {
                     if (r_pat != en->fp_pattern || (int64_t)r_nnz != en->nnz) {
                         drop_plan(*en);  // the pattern changed under the same pointers (the calls since then ran the plain kernel)
                         en->count = 1;
                         g_stats.invalidated += 1;
                         if (en->count < k) return false;
-                    } else if (val) {
-                        if (gespmm_plan_set_values(en->plan, val, stream) != 0) {
-                            drop_plan(*en);
-                            en->count = 0;
-                            return false;
-                        }
-                        en->fp_values = r_val;
-                        g_stats.values_refreshed += 1;
+                    } else {
+                        // the values changed. What that check saw may have changed again by now, by work already queued: this call
+                        // re-permutes from a fingerprint of its own (the synchronous path below), never from the record's
+                        values_changed = true;
                     }
                 }
             }
         }
-        if (en->plan && en->async_ok) {
+        if (en->plan && en->async_ok && !values_changed) {
             const unsigned long long seq = ++en->seq_launched;
             hipLaunchKernelGGL(k_fingerprint_check, dim3(kFpCheckBlocks), dim3(256), 0, st, rowptr, colind, val, (long long)M,
                                reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(en->guard_word) + kGuardBytes), en->fp_pattern, en->fp_values, (long long)en->nnz, en->guard_word, en->rec_dev, seq);
@@ -404,6 +424,7 @@ bool auto_plan_try(const int32_t* rowptr, const int32_t* colind, const float* va
         return false;
     }
     g_stats.fingerprints += 1;
+    en->seq_seen = en->seq_launched;  // (the stream has drained: every check launched so far has landed, and this fingerprint is newer)
     const int64_t nnz = (int64_t)fp[2];
     if (nnz_arg >= 0 && nnz_arg != nnz) {  // the caller's nnz contradicts rowptr[M]: let the plain path report what it reports
         drop_plan(*en);
@@ -452,7 +473,7 @@ bool auto_plan_try(const int32_t* rowptr, const int32_t* colind, const float* va
         en->async_ok = g_auto_async.load(std::memory_order_relaxed) && plan_spmm_guarded(p, B, C, N, reduce, empty, stream, &dry) == 0 &&
                        run_spmm(rowptr, colind, val, B, C, M, dgl ? M : K, N, nnz, variant, &fallback_cfg, reduce, empty, stream, nullptr, 0, nullptr,
                                 &dry) == 0 &&
-                       async_setup(*en, dev) == hipSuccess;
+                       async_setup(*en, dev, st) == hipSuccess;
         (void)hipGetLastError();
     } else if (val && (fp[1] != en->fp_values || val != en->val_seen)) {
         const int src = gespmm_plan_set_values(en->plan, val, stream);

@@ -250,7 +250,10 @@ int gespmm_csr_spmm_f32_ws(const int32_t* rowptr, const int32_t* colind, const f
                            int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, const gespmm_launch_cfg* cfg,
                            void* workspace, int64_t workspace_bytes, void* stream) {
     if (workspace_bytes < 0 || (workspace_bytes > 0 && workspace == nullptr)) return GESPMM_EINVAL;
-    if (cfg == nullptr && gespmm::auto_plan_enabled()) {  // (no launch knobs: the stateless call with the caller's scratch — what the torch op makes)
+    // no launch knobs (no cfg, or every field 0 — what the torch op passes): the stateless call with the caller's scratch
+    const bool no_knobs = cfg == nullptr || (cfg->vec == 0 && cfg->strips == 0 && cfg->group == 0 && cfg->rows_per_wave == 0 &&
+                                             cfg->slab_rows == 0 && cfg->flags == 0);
+    if (no_knobs && gespmm::auto_plan_enabled()) {
         int rc = 0;
         if (check_common(rowptr, colind, val, B, C, M, K, N, nnz) == 0 && variant >= GESPMM_VARIANT_AUTO && variant < GESPMM_NUM_VARIANTS &&
             variant != GESPMM_VARIANT_NAIVE && variant != GESPMM_VARIANT_PARREDUCE &&

@@ -381,7 +381,7 @@ int gespmm_plan_wants_warmup(int64_t M, int64_t K, int64_t nnz, int64_t N, int32
  * Plan reuse behind the STATELESS entry points (since 0.3; off by default). The reference's callers keep no state between products
  * (spmmWrapper spmm_test.cu:456-492, spmm_cuda spmm_kernel.cu:425-458, DGL's CustomCsrmm binary_reduce_sum.cu:338-360), so they cannot
  * hold a gespmm_plan. gespmm_set_auto_plan(k), k >= 1: gespmm_csr_spmm_f32, gespmm_csr_spmm_max_f32 and gespmm_dgl_csrmm_{sum,max}_f32
- * keep a small cache (8 entries, least recently used) keyed on (device, rowptr, colind, M, K, N, valued, variant, reducer); the k-th
+ * keep a small cache (8 entries, least recently used) keyed on (device, stream, rowptr, colind, M, K, N, valued, variant, reducer); the k-th
  * call with one key builds a plan (synchronously), later calls run through it. Pointer identity is not pattern identity: every call
  * that uses a cached plan first fingerprints ALL of rowptr / colind / val on the device (one small kernel + a 32-byte read-back = one
  * stream synchronisation per call — the price of the switch: ~25 us on a com-Amazon-sized graph, where the plan saves ~60). A pattern
@@ -389,7 +389,12 @@ int gespmm_plan_wants_warmup(int64_t M, int64_t K, int64_t nnz, int64_t N, int32
  * long-row pass, no cache blocking) the calls after the plan's creation do not synchronise at all: the fingerprint is compared ON THE
  * DEVICE, the plan's kernel and the plain kernel are both enqueued behind the result (one of them runs, the other's workgroups leave at
  * once), and the host learns of a change from a record the check leaves in pinned memory, at the next call. Never on a capturing stream. Matrices whose analysis keeps the
- * storage order run the plain path without fingerprint from then on. Results: the plain call's bits.
+ * storage order run the plain path without fingerprint from then on. Results: the plain call's bits for the operands as they are at
+ * that point in STREAM order, on any number of streams, whether or not the host waited for in-place changes that are ordered on the
+ * stream. The stream is part of the key, so each stream keeps its own plan and device-side check state (a plan per stream
+ * and graph: two streams on one graph take two of the 8 entries and twice the plan memory); a record of changed values is never
+ * adopted — the call that reads it re-fingerprints synchronously and re-permutes from that; the check state is zeroed whenever a plan
+ * is made; the record is a seqlock (round-6 advisor findings 1-3).
  * k = 0 switches it off and frees the cached plans; gespmm_auto_plan_clear frees them and keeps the switch.
  */
 typedef struct gespmm_auto_plan_stats {
