@@ -2,8 +2,7 @@
 //
 // The reference launches its kernels straight on the caller's CSR (spmmWrapper, spmm_test.cu:456-492;
 // spmm_cuda, pytorch-custom/spmm_kernel.cu:425-458) and has no such stage; vendor libraries do
-// (rocsparse_spmm_stage_preprocess). A plan looks at the matrix ONCE — on the host, one synchronisation —
-// and keeps what every later launch can reuse:
+// (rocsparse_spmm_stage_preprocess). A plan looks at the matrix ONCE and keeps what every later launch can reuse:
 //
 //   * the longest row (decides the long-row pass exactly instead of guessing from nnz and the mean degree);
 //   * for dense graphs: the workspace with the per-row split points of the cache-blocked path;
@@ -11,10 +10,19 @@
 //     table with an equal non-zero budget per wavefront. Rows that share neighbours are processed next to
 //     each other, so the B rows they share are gathered from the XCD's L2 instead of crossing the fabric
 //     again. Only the processing order changes: every row is still summed by one lane group in its own CSR
-//     order and written to its own C row (through perm[]), so the result has the same bits as the plain call.
+//     order and written to its own C row (through perm[]), so the result has the same bits as the plain call;
+//   * tables of the staged-rows, column-slab and padded-record kernels for the plan's width, where the policy keeps them.
 //
-// The plan owns its device memory (permuted rowptr / colind / val, perm, tasks, workspace) and refers to the
-// caller's arrays only while it is created (and in gespmm_plan_set_values).
+// How the file is laid out:
+//   * WHICH KERNEL a launch takes is one pure function, plan_route (plan_policy.cpp). plan_run switches on its answer,
+//     gespmm_plan_describe prints it, gespmm_plan_tune asks it which candidates exist: they cannot disagree.
+//   * OWNERSHIP: every device allocation has one owning member of gespmm_plan, released by its destructor; pointers into an
+//     allocation are views. Creation holds the plan in a unique_ptr, so every early exit is a plain return.
+//   * CREATION is a sequence of stages (plan_create_impl): facts -> order (device or host analysis) -> task tables and
+//     values -> staged / slab tables -> launch scratch -> record tables.
+//
+// The plan refers to the caller's arrays only while it is created (and in gespmm_plan_set_values) — unless it keeps the
+// storage order, in which case it launches on them.
 
 #include <hip/hip_runtime.h>
 
@@ -24,6 +32,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -34,6 +43,7 @@
 #include "plan_policy.h"
 #include "reorder.h"
 #include "select.h"
+#include "spmm_device.h"
 #include "spmm_kernels.h"
 
 struct gespmm_plan {
@@ -48,19 +58,21 @@ struct gespmm_plan {
     int32_t max_degree = 0;
     bool reordered = false;
     bool identity_order = false;  // reordered, but the plan's copy is in the caller's order (a matrix that arrived clustered: the staged-rows kernel needs the plan's tables)
-    void* d_block = nullptr;  // device analysis: perm / rowptr / colind / src_begin (/ val) are parts of this ONE allocation
-    bool val_in_block = false;
-    int32_t* d_rowptr = nullptr;
+    // ---- device memory: OWNERS (released by the destructor) and views into them (never freed)
+    void* d_block = nullptr;          // owner: the plan's permuted copy — perm / rowptr / colind / src_begin (/ val) are parts of this ONE allocation
+    int32_t* d_rowptr = nullptr;      // views (alloc_plan_copy)
     int32_t* d_colind = nullptr;
-    float* d_val = nullptr;
     int32_t* d_perm = nullptr;
     int32_t* d_src_begin = nullptr;
-    int32_t* d_tasks = nullptr;
+    float* d_val = nullptr;           // view: into d_block when the plan was created with values, else d_val_late
+    float* d_val_late = nullptr;      // owner: gespmm_plan_set_values gave values to a plan created without (the block has no room for them)
+    int32_t* d_tasks = nullptr;       // owner: the block of both task tables
     int32_t ntasks = 0;
-    int32_t* d_gtasks = nullptr;  // lane-group tasks of the segmented-stream kernel
+    int32_t* d_gtasks = nullptr;      // view: lane-group tasks of the segmented-stream kernel
     int32_t ngtasks = 0;
-    bool gtasks_shared = false;   // d_gtasks points into the block of d_tasks (device analysis)
-    // SDDMM through the plan (built on first use): edges in clustered order as COO with the ORIGINAL row ids, the
+    void* ws = nullptr;               // owner: scratch of the launches
+    int64_t ws_bytes = 0;
+    // owners, SDDMM through the plan (built on first use): edges in clustered order as COO with the ORIGINAL row ids, the
     // position of every edge in the caller's CSR, and a buffer for the results in clustered order
     int32_t* d_coo_row = nullptr;
     int32_t* d_coo_row_storage = nullptr;  // storage-order plans: row id of every edge (the COO form skips the row search)
@@ -74,8 +86,6 @@ struct gespmm_plan {
     double est_gain_us = 0.0, est_cost_us = 0.0;
     int analysis = 0;                // GESPMM_PLAN_ANALYSIS_*
     double model_seconds = 0.0;
-    void* ws = nullptr;
-    int64_t ws_bytes = 0;
     bool split_ready = false;
     int split_vec = 0;               // vector width (operand alignment) the kept split points were computed for
     gespmm::ClusterStats stats;
@@ -100,26 +110,28 @@ struct gespmm_plan {
     bool staging_kept_by_policy = false;  // keep_staged_tables() said yes at creation (else the tables exist only while tune measures them / if they won)
     double tune_us[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};  // batch-stream, segmented-stream, staged-rows, batch-stream with 4 floats per lane (N <= 64), padded records
     bool records_kept_by_policy = false;  // want_record_tables() / keep_record_tables() said yes at creation (else the tables exist only while tune measures them / if they won)
+
+    gespmm_plan() = default;
+    gespmm_plan(const gespmm_plan&) = delete;
+    gespmm_plan& operator=(const gespmm_plan&) = delete;
+    ~gespmm_plan() {
+        gespmm::free_staging(&stg);
+        gespmm::free_staging(&slab);
+        gespmm::free_slab_view(&slab_view, false);
+        gespmm::free_records(&rec);
+        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp})
+            if (q) (void)hipFree(q);
+    }
 };
 
 namespace {
-
-__global__ void iota_kernel(int32_t* __restrict__ out, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = i;
-}
 
 __global__ void permute_values_kernel(const int32_t* __restrict__ rowptr_p, const int32_t* __restrict__ src_begin,
                                       const float* __restrict__ val, float* __restrict__ val_p, int M, int nnz) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
-    int lo = 0, hi = M;  // rowptr_p[lo] <= p < rowptr_p[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (rowptr_p[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    val_p[p] = val[src_begin[lo] + (p - rowptr_p[lo])];
+    const int r = gespmm::row_of_entry(rowptr_p, M, p);
+    val_p[p] = val[src_begin[r] + (p - rowptr_p[r])];
 }
 
 __global__ void plan_edge_maps_kernel(const int32_t* __restrict__ rowptr_p, const int32_t* __restrict__ src_begin,
@@ -127,26 +139,14 @@ __global__ void plan_edge_maps_kernel(const int32_t* __restrict__ rowptr_p, cons
                                       int32_t* __restrict__ edge_dst, int M, int nnz) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
-    int lo = 0, hi = M;  // rowptr_p[lo] <= p < rowptr_p[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (rowptr_p[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    coo_row[p] = perm[lo];
-    edge_dst[p] = src_begin[lo] + (p - rowptr_p[lo]);
+    const int r = gespmm::row_of_entry(rowptr_p, M, p);
+    coo_row[p] = perm[r];
+    edge_dst[p] = src_begin[r] + (p - rowptr_p[r]);
 }
 
 __global__ void expand_rows_kernel(const int32_t* __restrict__ rowptr, int32_t* __restrict__ coo_row, int M, int nnz) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= nnz) return;
-    int lo = 0, hi = M;  // rowptr[lo] <= p < rowptr[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (rowptr[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    coo_row[p] = lo;
+    if (p < nnz) coo_row[p] = gespmm::row_of_entry(rowptr, M, p);
 }
 
 __global__ void scatter_by_index_kernel(const float* __restrict__ src, const int32_t* __restrict__ dst_index,
@@ -155,29 +155,47 @@ __global__ void scatter_by_index_kernel(const float* __restrict__ src, const int
     if (i < n) dst[dst_index[i]] = src[i];
 }
 
-void free_device(gespmm_plan* p) {
-    gespmm::free_staging(&p->stg);
-    gespmm::free_staging(&p->slab);
-    gespmm::free_slab_view(&p->slab_view, false);
-    gespmm::free_records(&p->rec);
-    if (p->gtasks_shared) p->d_gtasks = nullptr;
-    if (p->d_block) {  // the permuted copy is one block
-        (void)hipFree(p->d_block);
-        p->d_block = nullptr;
-        p->d_rowptr = p->d_colind = p->d_perm = p->d_src_begin = nullptr;
-        if (p->val_in_block) p->d_val = nullptr;
-        p->val_in_block = false;
-    }
-    void* ptrs[] = {p->d_rowptr, p->d_colind, p->d_val, p->d_perm, p->d_src_begin, p->d_tasks, p->ws, p->d_gtasks, p->d_coo_row, p->d_edge_dst, p->d_sddmm_tmp, p->d_coo_row_storage};
-    for (void* q : ptrs)
-        if (q) (void)hipFree(q);
-    p->d_rowptr = p->d_colind = p->d_perm = p->d_src_begin = p->d_tasks = p->d_gtasks = p->d_coo_row = p->d_edge_dst = nullptr;
-    p->d_sddmm_tmp = nullptr;
-    p->d_coo_row_storage = nullptr;
-    p->d_val = nullptr;
-    p->ws = nullptr;
+inline bool aligned16(const float* B, const float* C) {  // what the staged-rows and padded-record kernels ask of their operands
+    return ((reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(C)) & 15) == 0;
 }
 
+struct Stopwatch {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+};
+
+// The plan's permuted copy of the matrix as ONE allocation (a hipMalloc costs ~0.1 ms: five of them were 7 % of the device analysis).
+hipError_t alloc_plan_copy(gespmm_plan* p) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t entries = (size_t)(p->nnz > 0 ? p->nnz : 1);
+    const size_t b_perm = up((size_t)p->M * 4), b_rp = up(((size_t)p->M + 1) * 4), b_ci = up(entries * 4), b_src = up((size_t)p->M * 4),
+                 b_val = p->valued ? up(entries * 4) : 0;
+    const hipError_t e = hipMalloc(&p->d_block, b_perm + b_rp + b_ci + b_src + b_val);
+    if (e != hipSuccess) return e;
+    char* base = reinterpret_cast<char*>(p->d_block);
+    p->d_perm = reinterpret_cast<int32_t*>(base);
+    p->d_rowptr = reinterpret_cast<int32_t*>(base + b_perm);
+    p->d_colind = reinterpret_cast<int32_t*>(base + b_perm + b_rp);
+    p->d_src_begin = reinterpret_cast<int32_t*>(base + b_perm + b_rp + b_ci);
+    if (p->valued) p->d_val = reinterpret_cast<float*>(base + b_perm + b_rp + b_ci + b_src);
+    return hipSuccess;
+}
+
+// ... and gone again, with the task tables cut from it: the plan launches on the caller's arrays (nothing is paid per launch)
+void drop_plan_copy(gespmm_plan* p) {
+    if (p->d_block) (void)hipFree(p->d_block);
+    if (p->d_tasks) (void)hipFree(p->d_tasks);
+    p->d_block = nullptr;
+    p->d_perm = p->d_rowptr = p->d_colind = p->d_src_begin = p->d_tasks = p->d_gtasks = nullptr;
+    p->d_val = nullptr;
+    p->ntasks = p->ngtasks = 0;
+}
+
+hipError_t permute_values(const gespmm_plan* p, const float* val, hipStream_t st) {  // d_val = val in the plan's entry order
+    hipLaunchKernelGGL(permute_values_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->d_rowptr, p->d_src_begin, val,
+                       p->d_val, (int)p->M, (int)p->nnz);
+    return hipGetLastError();
+}
 
 // Experiment knobs (scripts/plan_time.py): GESPMM_CLUSTER_LEVELS / _SWEEPS / _STOP / _CAP override the clustering defaults.
 gespmm::ClusterOptions cluster_options_from_env() {
@@ -189,13 +207,44 @@ gespmm::ClusterOptions cluster_options_from_env() {
     return o;
 }
 
-template <typename T>
-hipError_t upload(T** dst, const std::vector<T>& src, hipStream_t st) {
-    const size_t bytes = (src.empty() ? 1 : src.size()) * sizeof(T);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), bytes);
-    if (e != hipSuccess) return e;
-    if (!src.empty()) e = hipMemcpyAsync(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st);
-    return e;
+// ... for a plan: what the environment leaves open, the policy fills in
+gespmm::ClusterOptions cluster_options_for(const gespmm::PlanFacts& f, int threads) {
+    gespmm::ClusterOptions o = cluster_options_from_env();
+    if (o.max_levels <= 0) o.max_levels = gespmm::cluster_levels_for(f);
+    if (o.sweeps <= 0) o.sweeps = gespmm::cluster_sweeps_for(f);
+    o.threads = threads;
+    return o;
+}
+
+// GESPMM_PLAN_TIMING: the time since the previous lap of this thread, device work included (what == NULL: start)
+void lap(hipStream_t st, const char* what) {
+    static const bool timing = getenv("GESPMM_PLAN_TIMING") != nullptr;
+    if (!timing) return;
+    (void)hipStreamSynchronize(st);
+    static thread_local std::chrono::steady_clock::time_point last;
+    const auto now = std::chrono::steady_clock::now();
+    if (what) fprintf(stderr, "[plan] %-22s %8.3f ms\n", what, std::chrono::duration<double>(now - last).count() * 1e3);
+    last = now;
+}
+
+// What a launch of width N does (plan_policy.cpp: plan_route) — the plan's state as that function reads it.
+gespmm::RouteAnswer route_of(const gespmm_plan* p, int64_t N, int reduce, bool operands_aligned16) {
+    gespmm::RouteState s;
+    s.reordered = p->reordered;
+    s.has_staged = p->stg.ev != nullptr;
+    s.has_slabs = p->slab.ev != nullptr;
+    s.has_records = p->rec.batches != nullptr;
+    s.has_gtasks = p->d_gtasks != nullptr;
+    s.staging_kept_by_policy = p->staging_kept_by_policy;
+    s.tuned = p->tuned;
+    s.tuned_kernel = p->tuned_kernel;
+    s.tuned_vec = p->tuned_vec;
+    s.kernel_choice = p->kernel_choice;
+    s.hits_after = p->hits_after;
+    s.stg_waves = p->stg.waves;
+    s.stg_slots = p->stg.slots;
+    s.stg_nlong = p->stg.nlong;
+    return gespmm::plan_route(p->facts, s, N, reduce, operands_aligned16);
 }
 
 }  // namespace
@@ -319,7 +368,7 @@ int gespmm_plan_debug_tasks(const gespmm_plan* p, int32_t which, int32_t* out_ho
 // alone) are taken out: the staged kernel sees them empty, the streaming kernel's long-row pass gets them as one-row tasks
 // (plan_run). Leaves p->stg empty when there is nothing but hub rows.
 static hipError_t build_staging_tables(gespmm_plan* p, hipStream_t st) {
-    const auto ts = std::chrono::steady_clock::now();
+    const Stopwatch sw;
     const int64_t M = p->M, K = p->K, nnz = p->nnz, N = p->N;
     gespmm::StagedShape shape = gespmm::staged_shape_any(N);  // (the block shape of whichever staged kernel serves the width)
     if (!getenv("GESPMM_STAGED_ROWS")) shape.rows = gespmm::staged_rows_for(p->facts, shape.rows, shape.waves);  // (by mean degree: plan_policy.cpp)
@@ -343,7 +392,7 @@ static hipError_t build_staging_tables(gespmm_plan* p, hipStream_t st) {
     if (ci_tmp) (void)hipFree(ci_tmp);
     if (val_tmp) (void)hipFree(val_tmp);
     if (e == hipSuccess && !p->stg.ev) gespmm::free_staging(&p->stg);  // (nothing but hub rows)
-    p->staging_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+    p->staging_seconds = sw.seconds();
     return e;
 }
 
@@ -351,7 +400,7 @@ static hipError_t build_staging_tables(gespmm_plan* p, hipStream_t st) {
 // (block of rows, slab). Leaves p->slab empty when the matrix does not qualify (a row with descending columns: slab order would not be
 // CSR order; a slab of some row beyond the staged kernel's row limit) — the plan's other kernels stay.
 static hipError_t build_slab_tables(gespmm_plan* p, int P, hipStream_t st) {
-    const auto ts = std::chrono::steady_clock::now();
+    const Stopwatch sw;
     const int64_t M = p->M, K = p->K, nnz = p->nnz, N = p->N;
     gespmm::StagedShape shape = gespmm::staged_shape(N);
     static const int rows_env = getenv("GESPMM_SLAB_ROWS") ? atoi(getenv("GESPMM_SLAB_ROWS")) : 0;  // experiments
@@ -372,7 +421,7 @@ static hipError_t build_slab_tables(gespmm_plan* p, int P, hipStream_t st) {
                                          shape.rows, shape.slots, shape.waves, shape.waves, &p->slab, st, M, true);
     gespmm::free_slab_view(&p->slab_view, e == hipSuccess);  // (the view's column indices / values / row map are in the tables now)
     if (e != hipSuccess) gespmm::free_staging(&p->slab);
-    p->slab_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+    p->slab_seconds = sw.seconds();
     return e;
 }
 
@@ -384,14 +433,306 @@ static double record_slot_fill(const gespmm_plan* p) {  // share of the entry sl
 // Tables of the padded-record kernel (spmm_records.hip) for the plan's width: the matrix in the order the plan processes it (its
 // clustered copy, or the caller's arrays when the storage order was kept).
 static hipError_t build_record_tables(gespmm_plan* p, hipStream_t st) {
-    const auto ts = std::chrono::steady_clock::now();
+    const Stopwatch sw;
     static const int env_rows = getenv("GESPMM_REC_BATCHES") ? atoi(getenv("GESPMM_REC_BATCHES")) : 0;  // experiments
     const int rows = env_rows > 0 ? env_rows : gespmm::records_batches_per_task(p->facts);
     const hipError_t e = gespmm::device_build_records(p->M, p->reordered ? p->d_rowptr : p->rowptr, p->reordered ? p->d_colind : p->colind,
                                                       p->valued ? (p->reordered ? p->d_val : p->val) : nullptr,
                                                       p->reordered ? p->d_perm : nullptr, rows, p->N, &p->rec, st);
-    p->records_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+    p->records_seconds = sw.seconds();
     return e;
+}
+
+// ------------------------------------------------------------------------------------------------ creation, stage by stage
+// Every stage returns 0 or an error code (GESPMM_E* or a hipError_t); what the plan owns by then goes with the plan.
+
+struct Creation {  // what the stages hand on
+    hipStream_t st = nullptr;
+    bool on_host = false;
+    int threads = 0;                           // gespmm_plan_options.threads (host clustering)
+    gespmm::AnalysisDecision ad;
+    std::vector<int32_t> h_rowptr, h_colind;   // host analysis: the caller's matrix
+    std::vector<int32_t> rp, ci, src;          // host analysis: its row-permuted copy ...
+    std::vector<int32_t> tasks, gtasks;        // ... and task tables, alive until the uploads are synchronised (make_task_tables)
+};
+
+static int check_create_args(const int32_t* rowptr, const int32_t* colind, int64_t M, int64_t K, int64_t nnz, int64_t N, int variant,
+                             const gespmm_plan_options* opt) {
+    if (M < 0 || K < 0 || N < 0 || nnz < 0) return GESPMM_EINVAL;
+    if (M > 0x7fffffffLL - 64 || K > 0x7fffffffLL || N > 0x7fffffffLL / 4 || nnz > 0x7fffffffLL - 4096) return GESPMM_ERANGE;
+    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    if (M > 0 && !rowptr) return GESPMM_EINVAL;
+    if (nnz > 0 && !colind) return GESPMM_EINVAL;
+    if (!opt) return 0;
+    if (opt->reorder < 0 || opt->reorder > 2) return GESPMM_EINVAL;
+    const int k = opt->kernel;
+    if (k != GESPMM_PLAN_KERNEL_AUTO && k != GESPMM_PLAN_KERNEL_STREAM && k != GESPMM_PLAN_KERNEL_SEG_STREAM && k != GESPMM_PLAN_KERNEL_STAGED &&
+        k != GESPMM_PLAN_KERNEL_RECORDS && k != GESPMM_PLAN_KERNEL_STAGED_SLABS)
+        return GESPMM_EINVAL;
+    if (opt->expected_launches < 0) return GESPMM_EINVAL;
+    if (opt->analysis != GESPMM_PLAN_ANALYSIS_DEVICE && opt->analysis != GESPMM_PLAN_ANALYSIS_HOST) return GESPMM_EINVAL;
+    return 0;
+}
+
+// One pass over the matrix on the device — rowptr monotone and consistent with nnz, every column index inside [0, K) (the kernels
+// trust them), the longest row — then the facts the policy is asked with (plan_policy.h) and its decision about the analysis.
+static int validate_and_decide(gespmm_plan* p, Creation& cx, const gespmm_plan_options* opt) {
+    const int64_t M = p->M, K = p->K, nnz = p->nnz, N = p->N;
+    const int reorder_mode = opt ? opt->reorder : GESPMM_PLAN_REORDER_AUTO;
+    int32_t max_deg = 0, bad = 0;
+    double wedge_probe = -1.0;
+    hipError_t e = gespmm::device_validate_csr(p->rowptr, p->colind, M, K, nnz, &max_deg, &bad,
+                                               (reorder_mode == GESPMM_PLAN_REORDER_AUTO && !cx.on_host) ? &wedge_probe : nullptr, cx.st);
+    if (e != hipSuccess) return (int)e;
+    if (bad) return GESPMM_EINVAL;  // rowptr does not describe nnz entries, or a column index is outside [0, K)
+    if (cx.on_host) {  // the matrix comes to the host once
+        cx.h_rowptr.assign((size_t)M + 1, 0);
+        cx.h_colind.resize((size_t)nnz);
+        if (M > 0) e = hipMemcpyAsync(cx.h_rowptr.data(), p->rowptr, ((size_t)M + 1) * 4, hipMemcpyDeviceToHost, cx.st);
+        if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(cx.h_colind.data(), p->colind, (size_t)nnz * 4, hipMemcpyDeviceToHost, cx.st);
+        if (e == hipSuccess) e = hipStreamSynchronize(cx.st);
+        if (e != hipSuccess) return (int)e;
+    }
+    p->max_degree = max_deg;
+    // what a plain call would launch, the longest row, the options
+    gespmm::PlanFacts& f = p->facts;
+    f.M = M;
+    f.K = K;
+    f.nnz = nnz;
+    f.N = N;
+    f.variant = p->variant;
+    f.max_degree = max_deg;
+    f.reorder_mode = reorder_mode;
+    f.kernel_choice = p->kernel_choice = opt ? opt->kernel : GESPMM_PLAN_KERNEL_AUTO;
+    f.host_analysis = cx.on_host;
+    f.user_flags = opt ? opt->flags : 0;
+    f.opt_task_entries = opt ? opt->task_entries : 0;
+    f.opt_row_floor = opt ? opt->row_floor : 0;
+    f.expected_launches = opt ? opt->expected_launches : 0;
+    f.wedge_probe = wedge_probe;
+    f.cold_start = !gespmm::analysis_is_warm();
+    gespmm::Selection sel;
+    int max_vec = 4;
+    while (max_vec > 1 && (N % max_vec) != 0) max_vec >>= 1;
+    const int lr_flags = gespmm::long_row_flags(M, nnz, max_deg, f.user_flags);
+    if (gespmm::resolve_geometry(M, K, N > 0 ? N : 1, nnz, p->variant, max_vec, 0, 0, 0, 0, 0, lr_flags, &sel) != 0) return GESPMM_EINVAL;
+    f.sel_variant = sel.variant;
+    f.slab_blocked = sel.geo.slab_blocked;
+    f.tile_cols = (int64_t)sel.geo.group * sel.geo.vec * sel.geo.strips;
+    cx.ad = gespmm::decide_analysis(f);
+    p->launch_flags = cx.ad.launch_flags;
+    p->cost_skipped = cx.ad.cost_skipped;
+    p->est_gain_us = cx.ad.cost.gain_us;
+    p->est_cost_us = cx.ad.cost.cost_us;
+    return 0;
+}
+
+// Analysis on the device: cluster, copy the matrix in the new order, model the L2s on both orders. *clustered: the plan holds a
+// permuted copy (in the clustered order — or in the caller's, identity_order) and goes on to its task tables; else it holds nothing.
+static int order_on_device(gespmm_plan* p, const Creation& cx, bool* clustered) {
+    const int64_t M = p->M, K = p->K, nnz = p->nnz;
+    const gespmm::PlanFacts& f = p->facts;
+    hipStream_t st = cx.st;
+    lap(st, nullptr);
+    const Stopwatch tc;
+    hipError_t e = alloc_plan_copy(p);
+    const gespmm::ClusterOptions copt = cluster_options_for(f, 0);
+    if (e == hipSuccess) e = gespmm::device_cluster_rows(M, K, nnz, p->rowptr, p->colind, copt, p->d_perm, &p->stats, st);
+    p->cluster_seconds = tc.seconds();
+    lap(st, "cluster");
+    if (e == hipSuccess) e = gespmm::device_permute_csr(M, nnz, p->rowptr, p->colind, p->d_perm, p->d_rowptr, p->d_colind, p->d_src_begin, st);
+    lap(st, "permute");
+    const Stopwatch tm;
+    // (the storage order is only judged against the clustered one — "already local, or hit by hubs: keep it" shows anywhere in a
+    //  slice — so on matrices of >= 2^20 entries the first QUARTER of every slice is modelled: a quarter of the sort)
+    const int64_t model_sample = cx.ad.model_sample;
+    const int64_t before_sample = nnz >= (1 << 20) ? std::max<int64_t>(nnz / 32, 1 << 15) : model_sample;
+    const int model_points = gespmm::model_points_for(f);  // sampled accesses per slice
+    if (e == hipSuccess)
+        e = gespmm::device_l2_model(M, K, nnz, p->rowptr, p->colind, 8, cx.ad.model_window,
+                                    model_sample > 0 ? std::min<int64_t>(model_sample, before_sample) : before_sample, model_points,
+                                    &p->hits_before, st);
+    if (e == hipSuccess)
+        e = gespmm::device_l2_model(M, K, nnz, p->d_rowptr, p->d_colind, 8, cx.ad.model_window, model_sample, model_points, &p->hits_after, st);
+    p->model_seconds = tm.seconds();
+    lap(st, "l2 model x2");
+    if (e != hipSuccess) return (int)e;
+    if (gespmm::keep_clustered_order(f, cx.ad, p->hits_before, p->hits_after)) {
+        if (cx.ad.dense_try) p->launch_flags |= GESPMM_FLAG_NO_SLAB_BLOCKED;  // a clustered dense graph runs the streaming kernels
+    } else if (!cx.ad.dense_try && gespmm::storage_order_wants_plan_copy(f, p->hits_before)) {
+        // The matrix ARRIVED in an order as good as the clustering's (a caller who keeps the graph by community): the staged-rows
+        // kernel still needs the plan's own tables, so the plan copies the matrix in the IDENTITY order and goes on as if it had
+        // clustered it (dropped again in build_device_tables if the tables are not kept: then nothing is paid per launch, as before)
+        e = gespmm::device_identity_copy(M, nnz, p->rowptr, p->colind, p->d_perm, p->d_rowptr, p->d_colind, p->d_src_begin, st);
+        if (e != hipSuccess) return (int)e;
+        p->hits_after = p->hits_before;
+        p->identity_order = true;
+    } else {
+        drop_plan_copy(p);  // the storage order (or the cache-blocked path) is as good: keep it and pay nothing per launch
+        return 0;
+    }
+    *clustered = true;
+    return 0;
+}
+
+// Analysis on the host (GESPMM_PLAN_ANALYSIS_HOST): the same clustering and a model of the XCD L2s that says whether the new order is
+// worth having (graphs whose storage order is already local, or that have no structure to find, keep their order and pay nothing per
+// launch). *clustered: cx.rp / ci / src hold the row-permuted copy for upload_host_copy.
+static int order_on_host(gespmm_plan* p, Creation& cx, bool* clustered) {
+    const int64_t M = p->M, K = p->K, nnz = p->nnz;
+    const Stopwatch tc;
+    p->perm_host.resize((size_t)M);
+    const gespmm::ClusterOptions copt = cluster_options_for(p->facts, cx.threads);
+    if (gespmm::cluster_rows(M, K, cx.h_rowptr.data(), cx.h_colind.data(), copt, p->perm_host.data(), &p->stats) != 0) return GESPMM_EINVAL;
+    // (Moving the heavy rows to the front of each XCD slice, so that no long sequential chain starts late, was
+    // measured: no effect on the community graph, 151 vs 137 us on the structureless one — hubs stay where the
+    // clustering puts them, next to the rows that share their neighbours. profiles/r02/plan_hubs_first.log)
+    p->cluster_seconds = tc.seconds();
+    p->hits_before = gespmm::simulate_l2_hits(M, K, cx.h_rowptr.data(), cx.h_colind.data(), nullptr, 8, cx.ad.model_window, cx.ad.model_sample);
+    p->hits_after = gespmm::simulate_l2_hits(M, K, cx.h_rowptr.data(), cx.h_colind.data(), p->perm_host.data(), 8, cx.ad.model_window, cx.ad.model_sample);
+    if (!gespmm::keep_clustered_order(p->facts, cx.ad, p->hits_before, p->hits_after)) return 0;
+    cx.rp.resize((size_t)M + 1);
+    cx.ci.resize((size_t)nnz);
+    cx.src.resize((size_t)M);
+    cx.rp[0] = 0;
+    for (int64_t i = 0; i < M; ++i) {
+        const int32_t r = p->perm_host[i];
+        const int32_t b = cx.h_rowptr[r], d = cx.h_rowptr[r + 1] - b;
+        cx.src[i] = b;
+        std::memcpy(cx.ci.data() + cx.rp[i], cx.h_colind.data() + b, (size_t)d * 4);
+        cx.rp[i + 1] = cx.rp[i] + d;
+    }
+    *clustered = true;
+    return 0;
+}
+
+// Host analysis: the task tables cut on the host (the greedy cut of device_cut_tasks), then the copy and the tables to the device.
+static hipError_t upload_host_copy(gespmm_plan* p, Creation& cx, const gespmm::PlanKernelDecision& kd) {
+    const int64_t M = p->M, nnz = p->nnz;
+    const std::vector<int32_t>& rp = cx.rp;
+    // batch-stream kernel: a task per WAVEFRONT, a row counting as at least row_floor entries; segmented-stream kernel: a task per
+    // lane GROUP (its time is proportional to the entries it streams, so its tasks are cut by non-zeros alone, half the budget)
+    auto cut_tasks = [&](int64_t budget, int64_t row_floor, std::vector<int32_t>& out) {
+        out.reserve((size_t)(nnz / (budget > 0 ? budget : 1) + M / gespmm::kMaxRowsPerWave + 16) * 4);
+        auto cost = [&](int64_t r) { return std::max<int64_t>(rp[r + 1] - rp[r], row_floor); };
+        int64_t i = 0;
+        while (i < M) {
+            const int64_t first = i;
+            int64_t acc = cost(i);
+            ++i;
+            while (i < M && i - first < gespmm::kMaxRowsPerWave && acc + cost(i) <= budget) {
+                acc += cost(i);
+                ++i;
+            }
+            out.push_back((int32_t)first);
+            out.push_back((int32_t)(i - first));
+            out.push_back(rp[first]);
+            out.push_back(rp[i]);
+        }
+    };
+    std::vector<int32_t>&tasks = cx.tasks, &gtasks = cx.gtasks;
+    cut_tasks(kd.task_entries, kd.row_floor, tasks);
+    cut_tasks(kd.group_task_entries, 0, gtasks);
+    p->ntasks = (int32_t)(tasks.size() / 4);
+    p->ngtasks = (int32_t)(gtasks.size() / 4);
+    auto put = [&](void* dst, const std::vector<int32_t>& v) {
+        return v.empty() ? hipSuccess : hipMemcpyAsync(dst, v.data(), v.size() * 4, hipMemcpyHostToDevice, cx.st);
+    };
+    hipError_t e = alloc_plan_copy(p);
+    if (e == hipSuccess) e = put(p->d_rowptr, rp);
+    if (e == hipSuccess) e = put(p->d_colind, cx.ci);
+    if (e == hipSuccess) e = put(p->d_perm, p->perm_host);
+    if (e == hipSuccess) e = put(p->d_src_begin, cx.src);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&p->d_tasks), (tasks.size() + gtasks.size()) * 4 + 16);  // (one block, as device_cut_tasks makes)
+    if (e != hipSuccess) return e;
+    p->d_gtasks = p->d_tasks + tasks.size();
+    e = put(p->d_tasks, tasks);
+    if (e == hipSuccess) e = put(p->d_gtasks, gtasks);
+    return e;
+}
+
+// The plan holds its order: task tables for the two streaming kernels, the values in the plan's entry order.
+static int make_task_tables(gespmm_plan* p, Creation& cx, const gespmm::PlanKernelDecision& kd) {
+    hipError_t e;
+    p->task_entries = kd.task_entries;
+    if (cx.on_host) {
+        e = upload_host_copy(p, cx, kd);
+    } else {
+        const int64_t budgets[2] = {kd.task_entries, kd.group_task_entries}, floors[2] = {kd.row_floor, 0};
+        int32_t* tables[2] = {nullptr, nullptr};
+        int32_t counts[2] = {0, 0};
+        e = gespmm::device_cut_tasks(p->M, p->d_rowptr, budgets, floors, tables, counts, cx.st);
+        p->d_tasks = tables[0];  // (one block holds both tables)
+        p->d_gtasks = tables[1];
+        p->ntasks = counts[0];
+        p->ngtasks = counts[1];
+        lap(cx.st, "tasks x2");
+    }
+    if (e == hipSuccess && p->valued && p->nnz > 0) e = permute_values(p, p->val, cx.st);
+    // the caller's `val` is not read after the call returns, and the host analysis' vectors go out of scope
+    if (e == hipSuccess) e = hipStreamSynchronize(cx.st);
+    if (!cx.on_host) lap(cx.st, "values");
+    return (int)e;
+}
+
+// Device analysis only: the tables of the staged-rows kernel (choose_plan_kernel says when: built, and kept when enough entries find
+// their B row staged) and the column-slab tables (dense clustered matrices at N = 128: plan_policy.cpp slab_count_for / keep_slab_tables).
+// *clustered turns false when an identity-order copy loses its reason to exist.
+static int build_device_tables(gespmm_plan* p, const Creation& cx, const gespmm::PlanKernelDecision& kd, bool* clustered) {
+    hipError_t e = hipSuccess;
+    if (kd.build_staged) {
+        e = build_staging_tables(p, cx.st);
+        if (e == hipSuccess && p->stg.ev && !gespmm::keep_staged_tables(p->facts, p->stg.staged_fraction))
+            gespmm::free_staging(&p->stg);  // not enough reuse inside the blocks: the streaming kernels stay
+        p->staging_kept_by_policy = p->stg.ev != nullptr;
+        lap(cx.st, "staging tables");
+    }
+    const int P = p->identity_order ? 0 : gespmm::slab_count_for(p->facts);
+    if (e == hipSuccess && P >= 2) {
+        e = build_slab_tables(p, P, cx.st);
+        if (e == hipSuccess && p->slab.ev && !gespmm::keep_slab_tables(p->facts, p->slab.staged_fraction)) {
+            gespmm::free_staging(&p->slab);
+            gespmm::free_slab_view(&p->slab_view, false);
+        }
+        lap(cx.st, "slab tables");
+    }
+    if (e != hipSuccess) return (int)e;
+    if (p->identity_order && !p->staging_kept_by_policy) {
+        // the copy in storage order was made for the staged-rows kernel alone: without its tables the caller's arrays serve
+        gespmm::free_staging(&p->stg);
+        drop_plan_copy(p);
+        p->identity_order = false;
+        *clustered = false;
+    }
+    return 0;
+}
+
+// Scratch of the launches (split points / long-row partials), owned by the plan.
+static int alloc_launch_scratch(gespmm_plan* p) {
+    gespmm_launch_cfg cfg = {0, 0, 0, 0, 0, p->launch_flags};
+    const int64_t need = gespmm_csr_spmm_workspace_bytes(p->M, p->K, p->N, p->nnz, p->variant, &cfg);
+    if (need <= 0) return 0;
+    const hipError_t e = hipMalloc(&p->ws, (size_t)need);
+    if (e == hipSuccess) p->ws_bytes = need;
+    return (int)e;
+}
+
+// Padded-record kernel (narrow widths, short rows): when asked for, or when the policy says so (plan_policy.cpp) — not beside staged
+// tables that were kept.
+static int build_policy_records(gespmm_plan* p, hipStream_t st) {
+    if (!(gespmm::records_serves(p->M, p->K, p->N, p->max_degree) && p->nnz > 0 &&
+          gespmm::want_record_tables(p->facts, p->reordered ? p->hits_after : p->hits_before) && !(p->stg.ev && p->staging_kept_by_policy)))
+        return 0;
+    hipError_t e = build_record_tables(p, st);
+    if (e == hipErrorOutOfMemory) {  // (padding beyond the cap, or no memory: the other kernels serve the plan)
+        gespmm::free_records(&p->rec);
+        (void)hipGetLastError();
+        e = hipSuccess;
+    }
+    if (e == hipSuccess && p->rec.batches && !gespmm::keep_record_tables(p->facts, record_slot_fill(p)))
+        gespmm::free_records(&p->rec);  // too much padding (rows of very different lengths share tasks): the other kernels stay
+    p->records_kept_by_policy = p->rec.batches != nullptr;
+    return (int)e;
 }
 
 // gespmm_plan_create_v2: `opt_bytes` = sizeof(gespmm_plan_options) as the CALLER was compiled with; fields beyond it take
@@ -400,22 +741,11 @@ static int plan_create_impl(gespmm_plan** out, const int32_t* rowptr, const int3
                             int64_t K, int64_t nnz, int64_t N, int variant, const gespmm_plan_options* opt, void* stream) {
     if (!out) return GESPMM_EINVAL;
     *out = nullptr;
-    if (M < 0 || K < 0 || N < 0 || nnz < 0) return GESPMM_EINVAL;
-    if (M > 0x7fffffffLL - 64 || K > 0x7fffffffLL || N > 0x7fffffffLL / 4 || nnz > 0x7fffffffLL - 4096) return GESPMM_ERANGE;
-    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
-    if (M > 0 && !rowptr) return GESPMM_EINVAL;
-    if (nnz > 0 && !colind) return GESPMM_EINVAL;
-    const int reorder_mode = opt ? opt->reorder : GESPMM_PLAN_REORDER_AUTO;
-    if (reorder_mode < 0 || reorder_mode > 2) return GESPMM_EINVAL;
-    const int kernel_mode = opt ? opt->kernel : GESPMM_PLAN_KERNEL_AUTO;
-    if (kernel_mode != GESPMM_PLAN_KERNEL_AUTO && kernel_mode != GESPMM_PLAN_KERNEL_STREAM && kernel_mode != GESPMM_PLAN_KERNEL_SEG_STREAM &&
-        kernel_mode != GESPMM_PLAN_KERNEL_STAGED && kernel_mode != GESPMM_PLAN_KERNEL_RECORDS && kernel_mode != GESPMM_PLAN_KERNEL_STAGED_SLABS)
-        return GESPMM_EINVAL;
-    if (opt && opt->expected_launches < 0) return GESPMM_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const auto t_start = std::chrono::steady_clock::now();
-
-    gespmm_plan* p = new (std::nothrow) gespmm_plan;
+    int rc = check_create_args(rowptr, colind, M, K, nnz, N, variant, opt);
+    if (rc != 0) return rc;
+    const Stopwatch total;
+    std::unique_ptr<gespmm_plan> plan(new (std::nothrow) gespmm_plan);
+    gespmm_plan* p = plan.get();
     if (!p) return GESPMM_ENOMEM;
     p->M = M;
     p->K = K;
@@ -426,368 +756,32 @@ static int plan_create_impl(gespmm_plan** out, const int32_t* rowptr, const int3
     p->colind = colind;
     p->val = val;
     p->valued = val != nullptr;
-    hipError_t e = hipGetDevice(&p->device);
-    if (e != hipSuccess) {
-        delete p;
-        return (int)e;
-    }
-    const int user_flags = opt ? opt->flags : 0;
-
-    const int analysis = opt ? opt->analysis : GESPMM_PLAN_ANALYSIS_DEVICE;
-    if (analysis != GESPMM_PLAN_ANALYSIS_DEVICE && analysis != GESPMM_PLAN_ANALYSIS_HOST) {
-        delete p;
-        return GESPMM_EINVAL;
-    }
-    p->analysis = analysis;
-    const bool on_host = analysis == GESPMM_PLAN_ANALYSIS_HOST;
-
+    p->analysis = opt ? opt->analysis : GESPMM_PLAN_ANALYSIS_DEVICE;
+    if (const hipError_t e = hipGetDevice(&p->device)) return (int)e;
     try {
-        // ---- one pass over the matrix on the device: rowptr monotone and consistent with nnz, every column index
-        //      inside [0, K) (the kernels trust them), the longest row
-        int32_t max_deg = 0, bad = 0;
-        double wedge_probe = -1.0;
-        const int reorder_auto = reorder_mode == GESPMM_PLAN_REORDER_AUTO;
-        e = gespmm::device_validate_csr(rowptr, colind, M, K, nnz, &max_deg, &bad, (reorder_auto && !on_host) ? &wedge_probe : nullptr, st);
-        if (e != hipSuccess) {
-            delete p;
-            return (int)e;
+        Creation cx;
+        cx.st = reinterpret_cast<hipStream_t>(stream);
+        cx.on_host = p->analysis == GESPMM_PLAN_ANALYSIS_HOST;
+        cx.threads = opt ? opt->threads : 0;
+        if ((rc = validate_and_decide(p, cx, opt)) != 0) return rc;
+        bool clustered = false;
+        if (cx.ad.analyse && (rc = cx.on_host ? order_on_host(p, cx, &clustered) : order_on_device(p, cx, &clustered)) != 0) return rc;
+        if (clustered) {
+            const gespmm::PlanKernelDecision kd = gespmm::choose_plan_kernel(p->facts, p->hits_after);
+            if ((rc = make_task_tables(p, cx, kd)) != 0) return rc;
+            if (!cx.on_host && (rc = build_device_tables(p, cx, kd, &clustered)) != 0) return rc;
+            if (clustered && kd.shallow_unroll) p->launch_flags |= GESPMM_FLAG_SHALLOW_UNROLL;
         }
-        if (bad) {
-            delete p;
-            return GESPMM_EINVAL;  // rowptr does not describe nnz entries, or a column index is outside [0, K)
-        }
-        // ---- host analysis only (GESPMM_PLAN_ANALYSIS_HOST): the matrix comes to the host once
-        std::vector<int32_t> h_rowptr, h_colind;
-        if (on_host) {
-            h_rowptr.assign((size_t)M + 1, 0);
-            h_colind.resize((size_t)nnz);
-            if (M > 0) e = hipMemcpyAsync(h_rowptr.data(), rowptr, ((size_t)M + 1) * 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && nnz > 0) e = hipMemcpyAsync(h_colind.data(), colind, (size_t)nnz * 4, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                delete p;
-                return (int)e;
-            }
-        }
-        p->max_degree = max_deg;
-        // ---- the facts the policy is asked with (plan_policy.h): what a plain call would launch, the longest row, the options
-        gespmm::PlanFacts& f = p->facts;
-        f.M = M;
-        f.K = K;
-        f.nnz = nnz;
-        f.N = N;
-        f.variant = variant;
-        f.max_degree = max_deg;
-        f.reorder_mode = reorder_mode;
-        f.kernel_choice = p->kernel_choice = opt ? opt->kernel : GESPMM_PLAN_KERNEL_AUTO;
-        f.host_analysis = on_host;
-        f.user_flags = user_flags;
-        f.opt_task_entries = opt ? opt->task_entries : 0;
-        f.opt_row_floor = opt ? opt->row_floor : 0;
-        f.expected_launches = opt ? opt->expected_launches : 0;
-        f.wedge_probe = wedge_probe;
-        f.cold_start = !gespmm::analysis_is_warm();
-        {
-            gespmm::Selection sel;
-            int max_vec = 4;
-            while (max_vec > 1 && (N % max_vec) != 0) max_vec >>= 1;
-            const int lr_flags = gespmm::long_row_flags(M, nnz, max_deg, user_flags);
-            if (gespmm::resolve_geometry(M, K, N > 0 ? N : 1, nnz, variant, max_vec, 0, 0, 0, 0, 0, lr_flags, &sel) != 0) {
-                delete p;
-                return GESPMM_EINVAL;
-            }
-            f.sel_variant = sel.variant;
-            f.slab_blocked = sel.geo.slab_blocked;
-            f.tile_cols = (int64_t)sel.geo.group * sel.geo.vec * sel.geo.strips;
-        }
-        const gespmm::AnalysisDecision ad = gespmm::decide_analysis(f);
-        p->launch_flags = ad.launch_flags;
-        bool reorder = ad.analyse;
-        p->cost_skipped = ad.cost_skipped;
-        p->est_gain_us = ad.cost.gain_us;
-        p->est_cost_us = ad.cost.cost_us;
-        const bool dense_try = ad.dense_try;
-        const int64_t model_window = ad.model_window, model_sample = ad.model_sample;
-
-        static const bool timing = getenv("GESPMM_PLAN_TIMING") != nullptr;
-        auto lap = [&](const char* what) {
-            if (!timing) return;
-            (void)hipStreamSynchronize(st);
-            static thread_local std::chrono::steady_clock::time_point last;
-            const auto now = std::chrono::steady_clock::now();
-            if (what) fprintf(stderr, "[plan] %-22s %8.3f ms\n", what, std::chrono::duration<double>(now - last).count() * 1e3);
-            last = now;
-        };
-        if (reorder && !on_host) {
-            // ==================================================================== analysis on the device
-            lap(nullptr);
-            const auto tc = std::chrono::steady_clock::now();
-            {   // one allocation for the plan's permuted copy of the matrix (a hipMalloc costs ~0.1 ms: five of them were 7 % of the analysis)
-                auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-                const size_t b_perm = up((size_t)M * 4), b_rp = up(((size_t)M + 1) * 4), b_ci = up((size_t)(nnz > 0 ? nnz : 1) * 4),
-                             b_src = up((size_t)M * 4), b_val = p->valued ? up((size_t)(nnz > 0 ? nnz : 1) * 4) : 0;
-                e = hipMalloc(&p->d_block, b_perm + b_rp + b_ci + b_src + b_val);
-                if (e == hipSuccess) {
-                    char* base = reinterpret_cast<char*>(p->d_block);
-                    p->d_perm = reinterpret_cast<int32_t*>(base);
-                    p->d_rowptr = reinterpret_cast<int32_t*>(base + b_perm);
-                    p->d_colind = reinterpret_cast<int32_t*>(base + b_perm + b_rp);
-                    p->d_src_begin = reinterpret_cast<int32_t*>(base + b_perm + b_rp + b_ci);
-                    if (p->valued) {
-                        p->d_val = reinterpret_cast<float*>(base + b_perm + b_rp + b_ci + b_src);
-                        p->val_in_block = true;
-                    }
-                }
-            }
-            gespmm::ClusterOptions copt = cluster_options_from_env();
-            if (copt.max_levels <= 0) copt.max_levels = gespmm::cluster_levels_for(f);
-            if (copt.sweeps <= 0) copt.sweeps = gespmm::cluster_sweeps_for(f);
-            if (e == hipSuccess) e = gespmm::device_cluster_rows(M, K, nnz, rowptr, colind, copt, p->d_perm, &p->stats, st);
-            p->cluster_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tc).count();
-            lap("cluster");
-            if (e == hipSuccess)
-                e = gespmm::device_permute_csr(M, nnz, rowptr, colind, p->d_perm, p->d_rowptr, p->d_colind, p->d_src_begin, st);
-            lap("permute");
-            const auto tm = std::chrono::steady_clock::now();
-            // (the storage order is only judged against the clustered one — "already local, or hit by hubs: keep it" shows anywhere in a
-            //  slice — so on matrices of >= 2^20 entries the first QUARTER of every slice is modelled: a quarter of the sort)
-            const int64_t before_sample = nnz >= (1 << 20) ? std::max<int64_t>(nnz / 32, 1 << 15) : model_sample;
-            const int model_points = gespmm::model_points_for(f);  // sampled accesses per slice
-            if (e == hipSuccess)
-                e = gespmm::device_l2_model(M, K, nnz, rowptr, colind, 8, model_window,
-                                            model_sample > 0 ? std::min<int64_t>(model_sample, before_sample) : before_sample, model_points,
-                                            &p->hits_before, st);
-            if (e == hipSuccess)
-                e = gespmm::device_l2_model(M, K, nnz, p->d_rowptr, p->d_colind, 8, model_window, model_sample, model_points,
-                                            &p->hits_after, st);
-            p->model_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tm).count();
-            lap("l2 model x2");
-            if (e != hipSuccess) {
-                free_device(p);
-                delete p;
-                return (int)e;
-            }
-            if (!gespmm::keep_clustered_order(f, ad, p->hits_before, p->hits_after) && !dense_try && gespmm::storage_order_wants_plan_copy(f, p->hits_before)) {
-                // The matrix ARRIVED in an order as good as the clustering's (a caller who keeps the graph by community): the staged-rows
-                // kernel still needs the plan's own tables, so the plan copies the matrix in the IDENTITY order and goes on as if it had
-                // clustered it (dropped again below if the tables are not kept: then nothing is paid per launch, as before)
-                hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, p->d_perm, (int)M);
-                e = hipGetLastError();
-                if (e == hipSuccess)
-                    e = gespmm::device_permute_csr(M, nnz, rowptr, colind, p->d_perm, p->d_rowptr, p->d_colind, p->d_src_begin, st);
-                if (e != hipSuccess) {
-                    free_device(p);
-                    delete p;
-                    return (int)e;
-                }
-                p->hits_after = p->hits_before;
-                p->identity_order = true;
-            } else if (!gespmm::keep_clustered_order(f, ad, p->hits_before, p->hits_after)) {
-                reorder = false;  // the storage order (or the cache-blocked path) is as good: keep it and pay nothing per launch
-                (void)hipFree(p->d_block);
-                p->d_block = nullptr;
-                p->d_perm = p->d_rowptr = p->d_colind = p->d_src_begin = nullptr;
-                p->d_val = nullptr;
-                p->val_in_block = false;
-            }
-        }
-        if (reorder && !on_host) {
-            if (dense_try) p->launch_flags |= GESPMM_FLAG_NO_SLAB_BLOCKED;  // a clustered dense graph runs the streaming kernels
-            // ---- task tables (same greedy cut as the host path), values
-            const gespmm::PlanKernelDecision kd = gespmm::choose_plan_kernel(f, p->hits_after);
-            const int budget = kd.task_entries, gbudget = kd.group_task_entries;
-            const int64_t row_floor = kd.row_floor;
-            p->task_entries = budget;
-            {
-                const int64_t budgets[2] = {budget, gbudget}, floors[2] = {row_floor, 0};
-                int32_t* tables[2] = {nullptr, nullptr};
-                int32_t counts[2] = {0, 0};
-                e = gespmm::device_cut_tasks(M, p->d_rowptr, budgets, floors, tables, counts, st);
-                p->d_tasks = tables[0];
-                p->d_gtasks = tables[1];
-                p->ntasks = counts[0];
-                p->ngtasks = counts[1];
-                p->gtasks_shared = true;  // one block holds both tables: free d_tasks only
-            }
-            lap("tasks x2");
-            if (e == hipSuccess && p->valued && nnz > 0) {  // (d_val is part of the plan's block)
-                hipLaunchKernelGGL(permute_values_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, p->d_rowptr,
-                                   p->d_src_begin, val, p->d_val, (int)M, (int)nnz);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the caller's `val` is not read after the call returns)
-            lap("values");
-            // ---- staged-rows kernel (choose_plan_kernel says when): the tables are built, and kept when enough entries find
-            //      their B row staged
-            if (e == hipSuccess && kd.build_staged) {
-                e = build_staging_tables(p, st);
-                if (e == hipSuccess && p->stg.ev && !gespmm::keep_staged_tables(f, p->stg.staged_fraction))
-                    gespmm::free_staging(&p->stg);  // not enough reuse inside the blocks: the streaming kernels stay
-                p->staging_kept_by_policy = p->stg.ev != nullptr;
-                lap("staging tables");
-            }
-            // ---- column-slab tables (dense clustered matrices at N = 128: plan_policy.cpp slab_count_for / keep_slab_tables)
-            if (e == hipSuccess && !p->identity_order) {
-                const int P = gespmm::slab_count_for(f);
-                if (P >= 2) {
-                    e = build_slab_tables(p, P, st);
-                    if (e == hipSuccess && p->slab.ev && !gespmm::keep_slab_tables(f, p->slab.staged_fraction)) {
-                        gespmm::free_staging(&p->slab);
-                        gespmm::free_slab_view(&p->slab_view, false);
-                    }
-                    lap("slab tables");
-                }
-            }
-            if (e != hipSuccess) {
-                free_device(p);
-                delete p;
-                return (int)e;
-            }
-            if (p->identity_order && !p->staging_kept_by_policy) {
-                // the copy in storage order was made for the staged-rows kernel alone: without its tables the caller's arrays serve
-                gespmm::free_staging(&p->stg);
-                if (p->d_tasks) (void)hipFree(p->d_tasks);
-                p->d_tasks = p->d_gtasks = nullptr;
-                p->ntasks = p->ngtasks = 0;
-                p->gtasks_shared = false;
-                (void)hipFree(p->d_block);
-                p->d_block = nullptr;
-                p->d_perm = p->d_rowptr = p->d_colind = p->d_src_begin = nullptr;
-                p->d_val = nullptr;
-                p->val_in_block = false;
-                p->identity_order = false;
-            } else {
-                p->reordered = true;
-                if (kd.shallow_unroll) p->launch_flags |= GESPMM_FLAG_SHALLOW_UNROLL;
-            }
-            reorder = false;  // done: skip the host branch
-        }
-
-        if (reorder) {
-            const auto tc = std::chrono::steady_clock::now();
-            p->perm_host.resize((size_t)M);
-            gespmm::ClusterOptions copt = cluster_options_from_env();
-            if (copt.max_levels <= 0) copt.max_levels = gespmm::cluster_levels_for(f);
-            if (copt.sweeps <= 0) copt.sweeps = gespmm::cluster_sweeps_for(f);
-            copt.threads = opt ? opt->threads : 0;
-            if (gespmm::cluster_rows(M, K, h_rowptr.data(), h_colind.data(), copt, p->perm_host.data(), &p->stats) != 0) {
-                delete p;
-                return GESPMM_EINVAL;
-            }
-            // (Moving the heavy rows to the front of each XCD slice, so that no long sequential chain starts late, was
-            // measured: no effect on the community graph, 151 vs 137 us on the structureless one — hubs stay where the
-            // clustering puts them, next to the rows that share their neighbours. profiles/r02/plan_hubs_first.log)
-            p->cluster_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tc).count();
-            // A model of the XCD L2s says whether the new order is worth having (graphs whose storage order is
-            // already local, or that have no structure to find, keep their order and pay nothing per launch).
-            {
-                p->hits_before = gespmm::simulate_l2_hits(M, K, h_rowptr.data(), h_colind.data(), nullptr, 8, model_window, model_sample);
-                p->hits_after = gespmm::simulate_l2_hits(M, K, h_rowptr.data(), h_colind.data(), p->perm_host.data(), 8, model_window, model_sample);
-                if (!gespmm::keep_clustered_order(f, ad, p->hits_before, p->hits_after)) reorder = false;
-            }
-        }
-        if (reorder) {
-            // ---- row-permuted copy + task table
-            std::vector<int32_t> rp((size_t)M + 1), ci((size_t)nnz), src((size_t)M);
-            rp[0] = 0;
-            for (int64_t i = 0; i < M; ++i) {
-                const int32_t r = p->perm_host[i];
-                const int32_t b = h_rowptr[r], d = h_rowptr[r + 1] - b;
-                src[i] = b;
-                std::memcpy(ci.data() + rp[i], h_colind.data() + b, (size_t)d * 4);
-                rp[i + 1] = rp[i] + d;
-            }
-            const gespmm::PlanKernelDecision kd = gespmm::choose_plan_kernel(f, p->hits_after);
-            const int budget = kd.task_entries, gbudget = kd.group_task_entries;
-            const int64_t row_floor = kd.row_floor;
-            p->task_entries = budget;
-            auto cost = [&](int64_t i2) { const int64_t d = rp[i2 + 1] - rp[i2]; return d > row_floor ? d : row_floor; };
-            // batch-stream kernel: a task per WAVEFRONT; segmented-stream kernel: a task per lane GROUP (its time is
-            // proportional to the entries it streams, so its tasks are cut by non-zeros alone, half the budget)
-            auto cut_tasks = [&](int64_t budget_, bool floor_rows, std::vector<int32_t>& out_) {
-                out_.reserve((size_t)(nnz / (budget_ > 0 ? budget_ : 1) + M / gespmm::kMaxRowsPerWave + 16) * 4);
-                int64_t i2 = 0;
-                while (i2 < M) {
-                    const int64_t first = i2;
-                    auto c2 = [&](int64_t r) { return floor_rows ? cost(r) : (int64_t)(rp[r + 1] - rp[r]); };
-                    int64_t acc = c2(i2);
-                    ++i2;
-                    while (i2 < M && i2 - first < gespmm::kMaxRowsPerWave && acc + c2(i2) <= budget_) {
-                        acc += c2(i2);
-                        ++i2;
-                    }
-                    out_.push_back((int32_t)first);
-                    out_.push_back((int32_t)(i2 - first));
-                    out_.push_back(rp[first]);
-                    out_.push_back(rp[i2]);
-                }
-            };
-            std::vector<int32_t> tasks, gtasks;
-            cut_tasks(budget, true, tasks);
-            cut_tasks(gbudget, false, gtasks);
-            p->ngtasks = (int32_t)(gtasks.size() / 4);
-            p->ntasks = (int32_t)(tasks.size() / 4);
-            e = upload(&p->d_rowptr, rp, st);
-            if (e == hipSuccess) e = upload(&p->d_colind, ci, st);
-            if (e == hipSuccess) e = upload(&p->d_perm, p->perm_host, st);
-            if (e == hipSuccess) e = upload(&p->d_src_begin, src, st);
-            if (e == hipSuccess) e = upload(&p->d_tasks, tasks, st);
-            if (e == hipSuccess) e = upload(&p->d_gtasks, gtasks, st);
-            if (e == hipSuccess && p->valued) e = hipMalloc(reinterpret_cast<void**>(&p->d_val), (size_t)(nnz > 0 ? nnz : 1) * 4);
-            if (e == hipSuccess && p->valued && nnz > 0) {
-                hipLaunchKernelGGL(permute_values_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, p->d_rowptr,
-                                   p->d_src_begin, val, p->d_val, (int)M, (int)nnz);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(st);  // the host vectors go out of scope
-            if (e != hipSuccess) {
-                free_device(p);
-                delete p;
-                return (int)e;
-            }
-            p->reordered = true;
-            if (kd.shallow_unroll) p->launch_flags |= GESPMM_FLAG_SHALLOW_UNROLL;
-        } else {
-            p->perm_host.clear();
-        }
-        // ---- scratch of the launches (split points / long-row partials), owned by the plan
-        gespmm_launch_cfg cfg = {0, 0, 0, 0, 0, p->launch_flags};
-        const int64_t need = gespmm_csr_spmm_workspace_bytes(M, K, N, nnz, variant, &cfg);
-        if (need > 0) {
-            e = hipMalloc(&p->ws, (size_t)need);
-            if (e != hipSuccess) {
-                free_device(p);
-                delete p;
-                return (int)e;
-            }
-            p->ws_bytes = need;
-        }
+        p->reordered = clustered;
+        if (!clustered) p->perm_host.clear();
+        if ((rc = alloc_launch_scratch(p)) != 0) return rc;
+        if ((rc = build_policy_records(p, cx.st)) != 0) return rc;
     } catch (const std::bad_alloc&) {
-        free_device(p);
-        delete p;
         return GESPMM_ENOMEM;
     }
-    // ---- padded-record kernel (narrow widths, short rows): when asked for, or when the policy says so (plan_policy.cpp)
-    if (gespmm::records_serves(M, K, N, p->max_degree) && nnz > 0 && gespmm::want_record_tables(p->facts, p->reordered ? p->hits_after : p->hits_before) &&
-        !(p->stg.ev && p->staging_kept_by_policy)) {
-        e = build_record_tables(p, st);
-        if (e == hipErrorOutOfMemory) {  // (padding beyond the cap, or no memory: the other kernels serve the plan)
-            gespmm::free_records(&p->rec);
-            (void)hipGetLastError();
-            e = hipSuccess;
-        }
-        if (e == hipSuccess && p->rec.batches && !gespmm::keep_record_tables(p->facts, record_slot_fill(p)))
-            gespmm::free_records(&p->rec);  // too much padding (rows of very different lengths share tasks): the other kernels stay
-        p->records_kept_by_policy = p->rec.batches != nullptr;
-        if (e != hipSuccess) {
-            free_device(p);
-            delete p;
-            return (int)e;
-        }
-    }
-    p->analysis_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    p->analysis_seconds = total.seconds();
     if (p->reordered || p->hits_after >= 0.0) gespmm::mark_analysis_warm();  // (the analysis passes ran: their kernels are loaded now)
-    *out = p;
+    *out = plan.release();
     return 0;
 }
 
@@ -811,6 +805,7 @@ int gespmm_plan_create_v2(gespmm_plan** out, const int32_t* rowptr, const int32_
 
 static int plan_run(gespmm_plan* p, const float* B, float* C, int64_t N, int reduce, float empty, void* stream,
                     const gespmm::LaunchGuard* guard = nullptr) {
+    using gespmm::PlanRoute;
     if (!p || N < 0) return GESPMM_EINVAL;
     if (reduce == gespmm::kReduceMax && p->valued) return GESPMM_EINVAL;
     gespmm_launch_cfg cfg = {0, 0, 0, 0, 0, p->launch_flags};
@@ -823,83 +818,60 @@ static int plan_run(gespmm_plan* p, const float* B, float* C, int64_t N, int red
                            (reinterpret_cast<uintptr_t>(C) % (4u * vec_now)) != 0))
         vec_now >>= 1;
     if (ws && p->split_ready && p->split_vec == vec_now) cfg.flags |= GESPMM_FLAG_REUSE_SPLIT;
-    int rc;
-    const bool variant_v4 = p->variant == GESPMM_VARIANT_AUTO || p->variant == GESPMM_VARIANT_CRC_CWM4 ||
-                            p->variant == GESPMM_VARIANT_CRC_CWM8;
-    // which kernel: the creator's choice (AUTO = the rules of plan_policy.cpp, per launch width) — or, at the plan's own width,
-    // what gespmm_plan_tune measured
-    const bool use_tuned = p->tuned && N == p->N;
-    const int kchoice = use_tuned ? p->tuned_kernel : p->kernel_choice;
-    gespmm::PlanFacts facts = p->facts;
-    facts.kernel_choice = kchoice;
-    // staged-rows kernels: the tables exist (the plan decided at creation), same width, 16-byte operands. Which kernel walks them follows
-    // from the width and the reducer (spmm_kernels.h: staged_kernel_class): lane groups at N = 16 / 32 / 64, the tuned shapes at N = 128 and
-    // 256 * 2^t, the general kernel at every other width and for the max reducer (round 6)
-    const int sclass = gespmm::staged_kernel_class(p->M, p->K, N, reduce);
-    const bool shape_ok = sclass != gespmm::kStagedGeneral ||
-                          (p->stg.waves == gespmm::staged_gen_shape(N).waves && p->stg.slots == gespmm::staged_gen_shape(N).slots);
-    const bool staged = p->reordered && p->stg.ev && N == p->N && sclass != gespmm::kStagedNone && shape_ok && variant_v4 &&
-                        (use_tuned ? kchoice == GESPMM_PLAN_KERNEL_STAGED
-                                   : ((kchoice == GESPMM_PLAN_KERNEL_AUTO && p->staging_kept_by_policy) || kchoice == GESPMM_PLAN_KERNEL_STAGED)) &&
-                        (reinterpret_cast<uintptr_t>(B) & 15) == 0 &&
-                        (reinterpret_cast<uintptr_t>(C) & 15) == 0;
-    // padded-record kernel: the tables exist (plan's width), sum reducer, 16-byte operands
-    if (p->rec.batches && N == p->N && reduce == gespmm::kReduceSum && variant_v4 && !(use_tuned && kchoice != GESPMM_PLAN_KERNEL_RECORDS) &&
-        (reinterpret_cast<uintptr_t>(B) & 15) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && !(staged && kchoice == GESPMM_PLAN_KERNEL_STAGED)) {
+    hipStream_t hst = reinterpret_cast<hipStream_t>(stream);
+    const float* pval = p->valued ? p->d_val : nullptr;
+    const gespmm::RouteAnswer ra = route_of(p, N, reduce, aligned16(B, C));
+    if (ra.route == PlanRoute::Records || ra.route == PlanRoute::StagedSlabs || ra.staged()) {  // the kernels that walk the plan's tables
         if (!B || !C) return GESPMM_EINVAL;
-        if (guard && guard->word == nullptr) return 0;  // (dry run: one kernel, guardable)
-        return (int)gespmm::launch_spmm_records(p->rec, B, C, N, p->launch_flags, guard, reinterpret_cast<hipStream_t>(stream));
+        if (guard && !ra.guardable()) return gespmm::kNotGuardable;  // (several launches)
+        if (guard && guard->word == nullptr) return 0;               // (dry run: one kernel, guardable)
     }
-    // column-slab tables: one launch of the staged-rows kernel per slab, the second and later ones continuing from C (sum reducer, the
-    // plan's width, 16-byte operands; an explicit other kernel or a tuned plan keeps its choice)
-    if (p->reordered && p->slab.ev && N == p->N && reduce == gespmm::kReduceSum && variant_v4 && !use_tuned &&
-        (kchoice == GESPMM_PLAN_KERNEL_AUTO || kchoice == GESPMM_PLAN_KERNEL_STAGED_SLABS) && (reinterpret_cast<uintptr_t>(B) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(C) & 15) == 0) {
-        if (!B || !C) return GESPMM_EINVAL;
-        if (guard) return gespmm::kNotGuardable;  // (several launches)
-        hipStream_t hst = reinterpret_cast<hipStream_t>(stream);
+    int rc = 0;
+    switch (ra.route) {
+    case PlanRoute::Records:
+        return (int)gespmm::launch_spmm_records(p->rec, B, C, N, p->launch_flags, guard, hst);
+    case PlanRoute::StagedSlabs: {
+        // one launch of the staged-rows kernel per slab, the second and later ones continuing from C
         const int P = p->slab_view.slabs, nb = p->slab.nblocks / P;
-        for (int s = 0; s < P; ++s) {
+        for (int s = 0; s < P && rc == 0; ++s) {
             gespmm::StagedArgs sa = {p->slab_view.rowptr_v, p->slab.ev, nullptr, p->slab.tasks, p->slab.hot_cols, p->slab.nhot, B, C, nb,
                                      p->slab.waves, p->slab.slots, 0, nullptr, 0, 0, 0.0f, nullptr, 0, s * nb, s > 0 ? 1 : 0};
             rc = (int)gespmm::launch_spmm_staged(sa, p->M, p->K, N, hst);
-            if (rc != 0) return rc;
         }
-        return 0;
+        return rc;
     }
-    if (staged) {
-        if (!B || !C) return GESPMM_EINVAL;
+    case PlanRoute::StagedTuned:
+    case PlanRoute::StagedNarrow:
+    case PlanRoute::StagedGeneral: {
         gespmm::StagedArgs sa = {p->stg.rowptr_s ? p->stg.rowptr_s : p->d_rowptr, p->stg.ev, p->d_perm, p->stg.tasks, p->stg.hot_cols,
                                  p->stg.nhot, B, C, p->stg.nblocks, p->stg.waves, p->stg.slots, 0, nullptr, 0, 0, 0.0f,
                                  guard ? guard->word : nullptr, guard ? guard->want : 0};
-        if (guard && p->stg.nlong > 0) return gespmm::kNotGuardable;  // (hub rows take a second launch and the long-row pass)
-        if (guard && guard->word == nullptr) return 0;                 // (dry run: one kernel, guardable)
-        hipStream_t hst = reinterpret_cast<hipStream_t>(stream);
-        if (sclass == gespmm::kStagedTuned) rc = (int)gespmm::launch_spmm_staged(sa, p->M, p->K, N, hst);
-        else if (sclass == gespmm::kStagedNarrow) rc = (int)gespmm::launch_spmm_staged_narrow(sa, p->M, p->K, N, hst);
+        if (ra.route == PlanRoute::StagedTuned) rc = (int)gespmm::launch_spmm_staged(sa, p->M, p->K, N, hst);
+        else if (ra.route == PlanRoute::StagedNarrow) rc = (int)gespmm::launch_spmm_staged_narrow(sa, p->M, p->K, N, hst);
         else rc = (int)gespmm::launch_spmm_staged_gen(sa, p->M, p->K, N, reduce, empty, hst);
-        if (rc == 0 && p->stg.nlong > 0) {
+        if (rc == 0 && ra.hub_pass) {
             // hub rows (written as empty rows above): one-row tasks through the batch-stream kernel, whose long-row pass splits
             // them — under GESPMM_FLAG_STRICT_ORDER each is one lane group's chain instead, as everywhere else
             gespmm::PlanLaunch pl = {p->stg.ltasks, p->stg.nlong, p->d_perm, nullptr, 0, false};
             gespmm_launch_cfg lcfg = cfg;
             lcfg.flags = (lcfg.flags | GESPMM_FLAG_BATCH_STREAM | GESPMM_FLAG_NO_SLAB_BLOCKED) & ~GESPMM_FLAG_REUSE_SPLIT;
             if (!(lcfg.flags & GESPMM_FLAG_STRICT_ORDER)) lcfg.flags |= GESPMM_FLAG_SPLIT_LONG_ROWS;
-            rc = gespmm::run_spmm(p->d_rowptr, p->d_colind, p->valued ? p->d_val : nullptr, B, C, p->M, p->K, N, p->nnz, p->variant,
-                                  &lcfg, reduce, empty, stream, ws, ws_bytes, &pl);
+            rc = gespmm::run_spmm(p->d_rowptr, p->d_colind, pval, B, C, p->M, p->K, N, p->nnz, p->variant, &lcfg, reduce, empty, stream, ws,
+                                  ws_bytes, &pl);
         }
         return rc;
     }
-    if (p->reordered) {
+    case PlanRoute::PlanStream: {
         // (which streaming kernel: prefer_segmented; which lane geometry at narrow widths: narrow_vec4 — plan_policy.cpp)
-        const bool seg = gespmm::prefer_segmented(facts, p->hits_after, N);
-        const bool vec4 = use_tuned ? p->tuned_vec == 1 : gespmm::narrow_vec4(facts, p->hits_after, N);
-        gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, seg && !vec4};
-        rc = gespmm::run_spmm(p->d_rowptr, p->d_colind, p->valued ? p->d_val : nullptr, B, C, p->M, p->K, N, p->nnz,
-                              vec4 ? GESPMM_VARIANT_CRC_CWM4 : p->variant, &cfg, reduce, empty, stream, ws, ws_bytes, &pl, guard);
-    } else {
-        rc = gespmm::run_spmm(p->rowptr, p->colind, p->valued ? p->val : nullptr, B, C, p->M, p->K, N, p->nnz, p->variant,
-                              &cfg, reduce, empty, stream, ws, ws_bytes, nullptr, guard);
+        gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, ra.segmented};
+        rc = gespmm::run_spmm(p->d_rowptr, p->d_colind, pval, B, C, p->M, p->K, N, p->nnz, ra.vec4 ? GESPMM_VARIANT_CRC_CWM4 : p->variant, &cfg,
+                              reduce, empty, stream, ws, ws_bytes, &pl, guard);
+        break;
+    }
+    case PlanRoute::StorageOrder:
+        rc = gespmm::run_spmm(p->rowptr, p->colind, p->valued ? p->val : nullptr, B, C, p->M, p->K, N, p->nnz, p->variant, &cfg, reduce, empty,
+                              stream, ws, ws_bytes, nullptr, guard);
+        break;
     }
     if (rc == 0 && ws) {
         p->split_ready = true;
@@ -921,7 +893,40 @@ int gespmm_plan_spmm_max_f32(gespmm_plan* plan, const float* B, float* C, int64_
 // candidate produces the same bits, so C holds the product afterwards whatever wins. The static rules of plan_policy.cpp
 // stay the default; this is for callers that would rather pay a few launches than trust a threshold (the hold-out audit,
 // profiles/r04/holdout_audit.log, is where the rules and the measurement are compared).
+namespace {
+// gespmm_plan_tune's bookkeeping, settled in ONE place when the call ends: unless a winner was set, the plan leaves as it came —
+// and tables do not stay behind (~16 bytes per entry, and an AUTO launch would otherwise take the staged-rows kernel against the
+// policy). After a win only the winner's tables survive: launches at p->N take the winner, other widths never use the tables, and a
+// later tune rebuilds them if it is asked again. After a failure only what the policy kept, or what the previous winner uses.
+struct TuneScope {
+    gespmm_plan* p;
+    const bool was_tuned = p->tuned;
+    const int was_kernel = p->tuned_kernel, was_vec = p->tuned_vec;
+    bool won = false;
+    explicit TuneScope(gespmm_plan* plan) : p(plan) {}
+    ~TuneScope() {
+        if (!won) {
+            p->tuned = was_tuned;
+            p->tuned_kernel = was_kernel;
+            p->tuned_vec = was_vec;
+        }
+        auto stays = [&](int kernel, bool kept_by_policy) {
+            return won ? p->tuned_kernel == kernel : (kept_by_policy || (was_tuned && was_kernel == kernel));
+        };
+        if (!stays(GESPMM_PLAN_KERNEL_STAGED, p->staging_kept_by_policy)) {
+            gespmm::free_staging(&p->stg);
+            p->staging_kept_by_policy = false;
+        }
+        if (!stays(GESPMM_PLAN_KERNEL_RECORDS, p->records_kept_by_policy)) {
+            gespmm::free_records(&p->rec);
+            p->records_kept_by_policy = false;
+        }
+    }
+};
+}  // namespace
+
 int gespmm_plan_tune(gespmm_plan* p, const float* B, float* C, int64_t N, int32_t reps, void* stream) {
+    using gespmm::PlanRoute;
     if (!p || N <= 0 || !B || !C) return GESPMM_EINVAL;
     if (N != p->N) return GESPMM_EINVAL;  // the tables are made for one width
     // a storage-order plan has one launch path, and the caller's explicit choice stands: nothing to measure, but C = A * B as promised
@@ -935,46 +940,40 @@ int gespmm_plan_tune(gespmm_plan* p, const float* B, float* C, int64_t N, int32_
     (void)hipGetLastError();
     if (reps <= 0) reps = 3;
     if (reps > 50) reps = 50;
-    hipError_t e = hipSuccess;
-    const bool v4 = p->variant == GESPMM_VARIANT_AUTO || p->variant == GESPMM_VARIANT_CRC_CWM4 || p->variant == GESPMM_VARIANT_CRC_CWM8;
-    if (!p->stg.ev && p->analysis == GESPMM_PLAN_ANALYSIS_DEVICE && v4 && p->nnz > 0 && gespmm::staged_serves_any(p->M, p->K, p->N) && gespmm::staged_stream_fits(p->M, p->nnz)) {
-        e = build_staging_tables(p, st);  // (built for the occasion: kept only if the staged-rows kernel wins)
-        if (e != hipSuccess) {
-            gespmm::free_staging(&p->stg);
-            return (int)e;
-        }
+    TuneScope scope(p);
+    // tables built for the occasion: kept only if their kernel wins
+    const bool v4 = gespmm::variant_takes_vec4(p->variant);
+    if (!p->stg.ev && p->analysis == GESPMM_PLAN_ANALYSIS_DEVICE && v4 && p->nnz > 0 && gespmm::staged_serves_any(p->M, p->K, p->N) &&
+        gespmm::staged_stream_fits(p->M, p->nnz)) {
+        const hipError_t e = build_staging_tables(p, st);
+        if (e != hipSuccess) return (int)e;
     }
-    if (!p->rec.batches && v4 && p->nnz > 0 && gespmm::records_serves(p->M, p->K, p->N, p->max_degree)) {
-        e = build_record_tables(p, st);  // (built for the occasion too)
-        if (e != hipSuccess) {
-            gespmm::free_records(&p->rec);
-            (void)hipGetLastError();
-            e = hipSuccess;
-        }
+    if (!p->rec.batches && v4 && p->nnz > 0 && gespmm::records_serves(p->M, p->K, p->N, p->max_degree) && build_record_tables(p, st) != hipSuccess) {
+        gespmm::free_records(&p->rec);  // (the other candidates are measured without)
+        (void)hipGetLastError();
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
-        if (!p->staging_kept_by_policy) gespmm::free_staging(&p->stg);
-        if (!p->records_kept_by_policy) gespmm::free_records(&p->rec);
-        return (int)e;
-    }
+    int rc = (int)hipEventCreate(&e0);
+    if (rc == 0) rc = (int)hipEventCreate(&e1);
     const int cand[5] = {GESPMM_PLAN_KERNEL_STREAM, GESPMM_PLAN_KERNEL_SEG_STREAM, GESPMM_PLAN_KERNEL_STAGED, GESPMM_PLAN_KERNEL_STREAM,
                          GESPMM_PLAN_KERNEL_RECORDS};
-    const bool was_tuned = p->tuned;
-    const int was_kernel = p->tuned_kernel, was_vec = p->tuned_vec;
-    int best = -1, rc = 0;
+    int best = -1;
     p->tuned = true;  // (plan_run below launches the candidate through the tuned path)
     for (int c = 0; c < 5 && rc == 0; ++c) {
         p->tune_us[c] = -1.0;
-        if (c == 1 && !p->d_gtasks) continue;
-        if (c == 4 && !(p->rec.batches && (reinterpret_cast<uintptr_t>(B) & 15) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0)) continue;
-        if (c == 2 && !(p->stg.ev && (reinterpret_cast<uintptr_t>(B) & 15) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 && v4)) continue;
-        if (c == 3 && !(p->variant == GESPMM_VARIANT_AUTO && N <= 64 && N % 4 == 0)) continue;
         p->tuned_kernel = cand[c];
         p->tuned_vec = c == 3 ? 1 : 0;
+        // is the candidate what a launch would take? (plan_route takes the tuned lane geometry as given: whether four floats per lane
+        // exist at this width is asked here.) Asking the route is stricter than asking whether the tables exist: tables that no kernel
+        // would walk at this width, block shape or variant are skipped instead of timing the streaming kernel under their name — the
+        // table builders make no such tables, so no plan they can produce is measured differently.
+        const gespmm::RouteAnswer ra = route_of(p, N, gespmm::kReduceSum, aligned16(B, C));
+        const bool available = c == 1   ? ra.route == PlanRoute::PlanStream && ra.segmented
+                               : c == 2 ? ra.staged()
+                               : c == 3 ? p->variant == GESPMM_VARIANT_AUTO && N <= 64 && N % 4 == 0
+                               : c == 4 ? ra.route == PlanRoute::Records
+                                        : true;
+        if (!available) continue;
         rc = plan_run(p, B, C, N, gespmm::kReduceSum, 0.0f, stream);  // warm: code objects, split points, L2 state
         if (rc == 0) rc = (int)hipEventRecord(e0, st);
         for (int r = 0; r < reps && rc == 0; ++r) rc = plan_run(p, B, C, N, gespmm::kReduceSum, 0.0f, stream);
@@ -986,30 +985,12 @@ int gespmm_plan_tune(gespmm_plan* p, const float* B, float* C, int64_t N, int32_
         p->tune_us[c] = (double)ms * 1e3 / reps;
         if (best < 0 || p->tune_us[c] < p->tune_us[best]) best = c;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != 0 || best < 0) {
-        // a candidate failed: the plan is what it was before the call — and tables the policy had not kept do not stay behind
-        // (~16 bytes per entry, and an AUTO launch would otherwise take the staged-rows kernel against the policy)
-        p->tuned = was_tuned;
-        p->tuned_kernel = was_kernel;
-        p->tuned_vec = was_vec;
-        if (!p->staging_kept_by_policy && !(was_tuned && was_kernel == GESPMM_PLAN_KERNEL_STAGED)) gespmm::free_staging(&p->stg);
-        if (!p->records_kept_by_policy && !(was_tuned && was_kernel == GESPMM_PLAN_KERNEL_RECORDS)) gespmm::free_records(&p->rec);
-        return rc;
-    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (rc != 0 || best < 0) return rc;  // a candidate failed: the plan is what it was before the call (TuneScope)
     p->tuned_kernel = cand[best];
     p->tuned_vec = best == 3 ? 1 : 0;
-    // tables of a kernel that lost are not kept (~16 bytes per entry): launches at p->N take the winner, other widths never use the
-    // staged-rows kernel, and a later tune rebuilds them (above) if it is asked again
-    if (best != 2 && p->stg.ev) {
-        gespmm::free_staging(&p->stg);
-        p->staging_kept_by_policy = false;
-    }
-    if (best != 4 && p->rec.batches) {
-        gespmm::free_records(&p->rec);
-        p->records_kept_by_policy = false;
-    }
+    scope.won = true;
     if (best != 2) rc = plan_run(p, B, C, N, gespmm::kReduceSum, 0.0f, stream);  // (C is the winner's product either way: same bits)
     return rc;
 }
@@ -1098,14 +1079,15 @@ int gespmm_plan_set_values(gespmm_plan* p, const float* val, void* stream) {
         if (p->stg.ev) return (int)gespmm::device_staging_set_values(p->stg, nullptr, p->d_rowptr, p->M, p->nnz, st);  // the stream carries 1.0f
         return 0;
     }
-    if (!p->d_val) {
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_val), (size_t)(p->nnz > 0 ? p->nnz : 1) * 4);
+    if (!p->d_val) {  // (created without values: the plan's block has no room for them)
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_val_late), (size_t)(p->nnz > 0 ? p->nnz : 1) * 4);
         if (e != hipSuccess) return (int)e;
+        p->d_val = p->d_val_late;
     }
     p->valued = true;
     if (p->nnz == 0) return 0;
-    hipLaunchKernelGGL(permute_values_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->d_rowptr,
-                       p->d_src_begin, val, p->d_val, (int)p->M, (int)p->nnz);
+    const hipError_t ep = permute_values(p, val, st);
+    if (ep != hipSuccess) return (int)ep;
     if (p->stg.ev) {
         const hipError_t es = gespmm::device_staging_set_values(p->stg, p->d_val, p->d_rowptr, p->M, p->nnz, st);
         if (es != hipSuccess) return (int)es;
@@ -1132,37 +1114,30 @@ int gespmm_plan_get_order(const gespmm_plan* p, int32_t* perm_host) {
 }
 
 int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
+    using gespmm::PlanRoute;
     if (!p || !out || capacity <= 0) return GESPMM_EINVAL;
-    char what[256] = "";
-    gespmm::PlanFacts facts = p->facts;  // (what a launch at the plan's own width does: the tuned choice, if there is one)
-    if (p->tuned) facts.kernel_choice = p->tuned_kernel;
-    const bool vec4d = p->reordered && (p->tuned ? p->tuned_vec == 1 : gespmm::narrow_vec4(facts, p->hits_after, p->N));
-    const bool seg = p->reordered && p->d_gtasks && !vec4d && gespmm::prefer_segmented(facts, p->hits_after, p->N);
-    const bool staged_d = p->stg.ev && (p->tuned ? p->tuned_kernel == GESPMM_PLAN_KERNEL_STAGED
-                                                 : (p->kernel_choice == GESPMM_PLAN_KERNEL_STAGED ||
-                                                    (p->kernel_choice == GESPMM_PLAN_KERNEL_AUTO && p->staging_kept_by_policy)));
-    gespmm_launch_cfg cfg = {0, 0, 0, 0, 0, p->launch_flags | (p->reordered ? ((seg ? GESPMM_FLAG_SEG_STREAM : GESPMM_FLAG_BATCH_STREAM) | GESPMM_FLAG_NO_SLAB_BLOCKED) : 0)};
-    gespmm_describe_launch(p->M, p->K, p->N, p->nnz, vec4d ? GESPMM_VARIANT_CRC_CWM4 : p->variant, &cfg, what, sizeof what);
+    // what a sum launch at the plan's own width does on 16-byte operands: the answer plan_run acts on
+    const gespmm::RouteAnswer ra = route_of(p, p->N, gespmm::kReduceSum, true);
+    char what[256] = "";  // the streaming launch (of that width too: what the max reducer and unaligned operands get)
+    gespmm_launch_cfg cfg = {0, 0, 0, 0, 0, p->launch_flags | (p->reordered ? ((ra.segmented ? GESPMM_FLAG_SEG_STREAM : GESPMM_FLAG_BATCH_STREAM) | GESPMM_FLAG_NO_SLAB_BLOCKED) : 0)};
+    gespmm_describe_launch(p->M, p->K, p->N, p->nnz, ra.vec4 ? GESPMM_VARIANT_CRC_CWM4 : p->variant, &cfg, what, sizeof what);
+    char kern[420];
+    if (ra.route == PlanRoute::Records)
+        snprintf(kern, sizeof kern, "kernel=padded-records tasks=%d batches_per_task>=%d batches=%d slot_fill=%.3f tables=%.4fs (max / other widths: %s)",
+                 p->rec.ntasks, p->rec.target_batches, p->rec.nbatches, record_slot_fill(p), p->records_seconds, what);
+    else if (ra.route == PlanRoute::StagedSlabs)
+        snprintf(kern, sizeof kern, "kernel=staged-slabs slabs=%d blocks=%d rows_in_lds<=%d staged_entries=%.3f tables=%.4fs (max / other widths: %s)",
+                 p->slab_view.slabs, p->slab.nblocks, p->slab.slots, p->slab.staged_fraction, p->slab_seconds, what);
+    else if (ra.staged())
+        snprintf(kern, sizeof kern, "kernel=staged-rows blocks=%d rows_in_lds<=%d staged_entries=%.3f hub_rows=%d tables=%.4fs (max / other widths: %s)",
+                 p->stg.nblocks, gespmm::staged_shape_any(p->N).slots, p->stg.staged_fraction, p->stg.nlong, p->staging_seconds, what);
+    else snprintf(kern, sizeof kern, "%s", what);
     int n;
     if (p->reordered) {
         char lv[128] = "";
         int off = 0;
         for (int i = 0; i < p->stats.levels && i < 16 && off < 100; ++i)
             off += snprintf(lv + off, sizeof lv - (size_t)off, "%s%d", i ? ">" : "", p->stats.clusters[i]);
-        char kern[420];
-        const bool slab_d = p->slab.ev && !p->tuned && (p->kernel_choice == GESPMM_PLAN_KERNEL_AUTO || p->kernel_choice == GESPMM_PLAN_KERNEL_STAGED_SLABS) &&
-                            (p->variant == GESPMM_VARIANT_AUTO || p->variant >= GESPMM_VARIANT_CRC_CWM4);
-        if (slab_d)
-            snprintf(kern, sizeof kern, "kernel=staged-slabs slabs=%d blocks=%d rows_in_lds<=%d staged_entries=%.3f tables=%.4fs (max / other widths: %s)",
-                     p->slab_view.slabs, p->slab.nblocks, p->slab.slots, p->slab.staged_fraction, p->slab_seconds, what);
-        else if (staged_d && (p->variant == GESPMM_VARIANT_AUTO || p->variant >= GESPMM_VARIANT_CRC_CWM4))
-            snprintf(kern, sizeof kern, "kernel=staged-rows blocks=%d rows_in_lds<=%d staged_entries=%.3f hub_rows=%d tables=%.4fs (max / other widths: %s)",
-                     p->stg.nblocks, gespmm::staged_shape_any(p->N).slots, p->stg.staged_fraction, p->stg.nlong, p->staging_seconds, what);
-        else snprintf(kern, sizeof kern, "%s", what);
-        if (p->rec.batches && !(p->tuned && p->tuned_kernel != GESPMM_PLAN_KERNEL_RECORDS) && !(staged_d && p->kernel_choice == GESPMM_PLAN_KERNEL_STAGED))
-            snprintf(kern, sizeof kern, "kernel=padded-records tasks=%d batches_per_task>=%d batches=%d slot_fill=%.3f tables=%.4fs (max / other widths: %s)",
-                     p->rec.ntasks, p->rec.target_batches, p->rec.nbatches,
-                     record_slot_fill(p), p->records_seconds, what);
         char tuned[200] = "";
         if (p->tuned)
             snprintf(tuned, sizeof tuned, " tuned[us: batch-stream=%.1f segmented-stream=%.1f staged-rows=%.1f batch-stream-V4=%.1f padded-records=%.1f]",
@@ -1179,11 +1154,6 @@ int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
             snprintf(why, sizeof why, " (analysis skipped: est. gain %.1f us x %d launches < est. cost %.0f us; wedge probe %.4f)", p->est_gain_us,
                      p->facts.expected_launches > 0 ? p->facts.expected_launches : gespmm::kDefaultExpectedLaunches, p->est_cost_us,
                      p->facts.wedge_probe);
-        char kern[420];
-        if (p->rec.batches)
-            snprintf(kern, sizeof kern, "kernel=padded-records tasks=%d batches_per_task>=%d batches=%d slot_fill=%.3f tables=%.4fs (max / other widths: %s)", p->rec.ntasks,
-                     p->rec.target_batches, p->rec.nbatches, record_slot_fill(p), p->records_seconds, what);
-        else snprintf(kern, sizeof kern, "%s", what);
         n = snprintf(out, (size_t)capacity, "order=storage max_degree=%d l2_model=%.3f->%.3f analysis=%.4fs%s | %s",
                      p->max_degree, p->hits_before, p->hits_after, p->analysis_seconds, why, kern);
     }
@@ -1195,11 +1165,7 @@ void gespmm_release_cached_memory(void) { gespmm::release_cached_arena(); }
 
 void gespmm_set_cached_memory_limit(int64_t bytes) { gespmm::set_arena_cache_limit((long long)bytes); }
 
-void gespmm_plan_destroy(gespmm_plan* p) {
-    if (!p) return;
-    free_device(p);
-    delete p;
-}
+void gespmm_plan_destroy(gespmm_plan* p) { delete p; }
 
 }  // extern "C"
 

@@ -26,6 +26,10 @@ hipError_t device_cluster_rows(int64_t M, int64_t K, int64_t nnz, const int32_t*
 hipError_t device_permute_csr(int64_t M, int64_t nnz, const int32_t* rowptr, const int32_t* colind, const int32_t* perm,
                               int32_t* rowptr_p, int32_t* colind_p, int32_t* src_begin, hipStream_t st);
 
+// ... the same copy in the caller's own order: perm = 0, 1, .., M - 1 (written here).
+hipError_t device_identity_copy(int64_t M, int64_t nnz, const int32_t* rowptr, const int32_t* colind, int32_t* perm, int32_t* rowptr_p,
+                                int32_t* colind_p, int32_t* src_begin, hipStream_t st);
+
 // The L2 model of simulate_l2_hits() (rows of `rowptr`/`colind` in storage order — pass the permuted copy to
 // judge an order): `slices` parts of equal non-zero count, an LRU of `window` B rows each; an unbiased estimate
 // from `samples_per_slice` stratified accesses per slice whose LRU stack distance is computed exactly

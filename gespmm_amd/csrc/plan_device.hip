@@ -45,6 +45,7 @@
 
 #include "auto_plan.h"
 #include "plan_device.h"
+#include "spmm_device.h"
 #include "spmm_kernels.h"
 #include "workspace.h"
 
@@ -254,17 +255,6 @@ __device__ inline uint32_t mix32(uint32_t x) {  // == reorder.cpp
 
 __device__ inline int lane_id() { return (int)(threadIdx.x & 63); }
 
-// row owning CSR position p: ptr[lo] <= p < ptr[lo + 1]
-__device__ inline int owner_of(const int32_t* __restrict__ ptr, int n, int p) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // ------------------------------------------------------------------------------------------------ validation
 
 __global__ void k_validate(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colind, int64_t M, int64_t K,
@@ -378,8 +368,8 @@ __global__ void k_lower_bound_ptr(const int32_t* __restrict__ keys, int n, int n
 __global__ void __launch_bounds__(256) k_rows_of_entries(const int32_t* __restrict__ ptr, int n, int64_t E, int32_t* __restrict__ out) {
     __shared__ int s_lo, s_hi;
     const int64_t e0 = (int64_t)blockIdx.x * 256;
-    if (threadIdx.x == 0) s_lo = owner_of(ptr, n, (int)e0);
-    if (threadIdx.x == 64) s_hi = owner_of(ptr, n, (int)(e0 + 255 < E ? e0 + 255 : E - 1));
+    if (threadIdx.x == 0) s_lo = row_of_entry(ptr, n, (int)e0);
+    if (threadIdx.x == 64) s_hi = row_of_entry(ptr, n, (int)(e0 + 255 < E ? e0 + 255 : E - 1));
     __syncthreads();
     const int64_t e = e0 + threadIdx.x;
     if (e >= E) return;
@@ -802,7 +792,7 @@ __global__ void k_emit_edges(DAdj rows, int R, int E, const int32_t* __restrict_
                              int32_t* __restrict__ vals) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= E) return;
-    const int r = owner_of(rows.ptr, R, e);
+    const int r = row_of_entry(rows.ptr, R, e);
     const int cl = clab[rows.idx[e]];
     unsigned long long key = (unsigned long long)R2 << shift;
     if (cl >= 0) {
@@ -916,7 +906,7 @@ __global__ void k_copy_entries(const int32_t* __restrict__ rowptr_p, const int32
                                const int32_t* __restrict__ colind, int M, int nnz, int32_t* __restrict__ colind_p) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
-    const int lo = owner_of(rowptr_p, M, p);
+    const int lo = row_of_entry(rowptr_p, M, p);
     colind_p[p] = colind[src_begin[lo] + (p - rowptr_p[lo])];
 }
 
@@ -1633,6 +1623,14 @@ hipError_t device_permute_csr(int64_t M, int64_t nnz, const int32_t* rowptr, con
     return hipGetLastError();
 }
 
+hipError_t device_identity_copy(int64_t M, int64_t nnz, const int32_t* rowptr, const int32_t* colind, int32_t* perm, int32_t* rowptr_p,
+                                int32_t* colind_p, int32_t* src_begin, hipStream_t st) {
+    if (M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_iota, dim3(grid_for(M)), dim3(256), 0, st, perm, M);
+    GESPMM_TRY(hipGetLastError());
+    return device_permute_csr(M, nnz, rowptr, colind, perm, rowptr_p, colind_p, src_begin, st);
+}
+
 hipError_t device_l2_model(int64_t M, int64_t K, int64_t nnz, const int32_t* rowptr, const int32_t* colind, int slices,
                            int64_t window, int64_t max_entries_per_slice, int samples_per_slice, double* hits_host,
                            hipStream_t st) {
@@ -1769,11 +1767,6 @@ __global__ void k_stage_offsets(const int32_t* __restrict__ rowptr_p, int64_t M,
     blkoff[i] = rowptr_p[stage_block_begin(i, R, seg_rows, nb_seg, M)];
 }
 
-__global__ void k_stage_iota(int32_t* __restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (int32_t)i;
-}
-
 __global__ __launch_bounds__(256) void k_stage_select(const int32_t* __restrict__ blkoff, const int32_t* __restrict__ keys,
                                                        const int32_t* __restrict__ idx, int H, int32_t* __restrict__ code,
                                                        int32_t* __restrict__ hot_cols, int32_t* __restrict__ nhot,
@@ -1898,16 +1891,6 @@ __global__ void k_stage_tasks(const int32_t* __restrict__ rowptr_p, int64_t M, i
     // (word 0 — not read by the kernels since the stream carries the rows — holds the C row of the task's first row in column-slab tables)
     const int w0 = first_crow ? first_crow[r0 < M ? r0 : (int)M - 1] : r0;
     reinterpret_cast<int4*>(tasks)[i] = make_int4(w0, r1 - r0, rowptr_p[r0] + r0, rowptr_p[r1] + r1);
-}
-
-__device__ __forceinline__ int row_of_entry(const int32_t* __restrict__ rowptr, int M, int q) {
-    int lo = 0, hi = M;  // rowptr[lo] <= q < rowptr[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (rowptr[mid] <= q) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // The record stream: entry p of row r -> record p + r = {code, value bits}
@@ -2076,7 +2059,7 @@ hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t
     auto body = [&]() -> hipError_t {
         GESPMM_TRY(hipMemsetAsync(staged, 0, 8 * kStageCounters, st));
         hipLaunchKernelGGL(k_stage_offsets, dim3(grid_for(nblk + 1)), dim3(256), 0, st, rowptr_p, M, nblk, R, seg_rows, nb_seg, blkoff);
-        hipLaunchKernelGGL(k_stage_iota, dim3(grid_for(nnz)), dim3(256), 0, st, idx_in, nnz);
+        hipLaunchKernelGGL(k_iota, dim3(grid_for(nnz)), dim3(256), 0, st, idx_in, nnz);
         GESPMM_TRY(rocprim::segmented_radix_sort_pairs(tmp, sort_bytes, colind_p, keys, (const int32_t*)idx_in, idx_out, (size_t)nnz,
                                                        (unsigned)nblk, (const int32_t*)blkoff, (const int32_t*)blkoff + 1, 0u,
                                                        (unsigned)bits, st));

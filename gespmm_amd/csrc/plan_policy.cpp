@@ -212,7 +212,7 @@ PlanKernelDecision choose_plan_kernel(const PlanFacts& f, double hits_after) {
     // degree 8: 239 vs 236 us) and a mean degree of 12 was asked there; with round 5's walk (row ends in the stream, packed
     // multiply-adds) they win at both widths: com-Amazon-shaped 92.7 vs 107 us (N = 128), 175 vs 216 us (N = 256); mean degree 6 / 8:
     // x1.06 / x1.14 at N = 128 (profiles/r05/staged_degree_sweep.log, kernel_ab_record_stream.log). Device analysis only.
-    const bool v4 = f.variant == GESPMM_VARIANT_AUTO || f.variant == GESPMM_VARIANT_CRC_CWM4 || f.variant == GESPMM_VARIANT_CRC_CWM8;
+    const bool v4 = variant_takes_vec4(f.variant);
     const int sclass = staged_kernel_class(f.M, f.K, f.N);
     const bool fits = f.nnz > 0 && sclass != kStagedNone && staged_stream_fits(f.M, f.nnz);
     const bool narrow = sclass == kStagedNarrow;  // N = 16 / 32 / 64: the lane-group form of the kernel (spmm_staged_narrow.hip)
@@ -400,6 +400,41 @@ bool prefer_segmented(const PlanFacts& f, double hits_after, int64_t N) {
 bool narrow_vec4(const PlanFacts& f, double hits_after, int64_t N) {
     return f.variant == GESPMM_VARIANT_AUTO && N <= 64 && N >= 16 && N % 4 == 0 && hits_after >= 0.40 && f.mean_ceil() <= 8 &&
            f.nnz >= (1 << 20);
+}
+
+// Which kernel a launch takes: the creator's choice (AUTO = the rules above, per launch width) — or, at the plan's own width, what
+// gespmm_plan_tune measured. The tables serve the plan's width and 16-byte operands only; which staged kernel walks them follows
+// from the width and the reducer (spmm_kernels.h: staged_kernel_class): lane groups at N = 16 / 32 / 64, the tuned shapes at N = 128
+// and 256 * 2^t, the general kernel at every other width and for the max reducer — whose block shape the tables must have.
+RouteAnswer plan_route(const PlanFacts& f, const RouteState& s, int64_t N, int reduce, bool aligned16) {
+    RouteAnswer a;
+    const bool own_width = N == f.N, v4 = variant_takes_vec4(f.variant), sum = reduce == kReduceSum;
+    const bool use_tuned = s.tuned && own_width;
+    const int kchoice = use_tuned ? s.tuned_kernel : s.kernel_choice;
+    const int sclass = staged_kernel_class(f.M, f.K, N, reduce);
+    const bool shape_ok = sclass != kStagedGeneral || (s.stg_waves == staged_gen_shape(N).waves && s.stg_slots == staged_gen_shape(N).slots);
+    const bool staged = s.reordered && s.has_staged && own_width && sclass != kStagedNone && shape_ok && v4 && aligned16 &&
+                        (kchoice == GESPMM_PLAN_KERNEL_STAGED || (!use_tuned && kchoice == GESPMM_PLAN_KERNEL_AUTO && s.staging_kept_by_policy));
+    if (s.reordered) {  // the streaming launch of this width (what the table routes fall back to for the max reducer or unaligned operands)
+        PlanFacts fl = f;
+        fl.kernel_choice = kchoice;
+        a.vec4 = use_tuned ? s.tuned_vec == 1 : narrow_vec4(fl, s.hits_after, N);
+        // (has_gtasks: the gate run_spmm applies to PlanLaunch::prefer_segmented — no lane-group tasks, no segmented-stream launch)
+        a.segmented = s.has_gtasks && !a.vec4 && prefer_segmented(fl, s.hits_after, N);
+    }
+    if (s.has_records && own_width && sum && v4 && aligned16 && !(use_tuned && kchoice != GESPMM_PLAN_KERNEL_RECORDS) &&
+        !(staged && kchoice == GESPMM_PLAN_KERNEL_STAGED)) {
+        a.route = PlanRoute::Records;
+    } else if (s.reordered && s.has_slabs && own_width && sum && v4 && aligned16 && !use_tuned &&
+               (kchoice == GESPMM_PLAN_KERNEL_AUTO || kchoice == GESPMM_PLAN_KERNEL_STAGED_SLABS)) {
+        a.route = PlanRoute::StagedSlabs;  // (an explicit other kernel or a tuned plan keeps its choice)
+    } else if (staged) {
+        a.route = sclass == kStagedTuned ? PlanRoute::StagedTuned : sclass == kStagedNarrow ? PlanRoute::StagedNarrow : PlanRoute::StagedGeneral;
+        a.hub_pass = s.stg_nlong > 0;
+    } else if (s.reordered) {
+        a.route = PlanRoute::PlanStream;
+    }
+    return a;
 }
 
 // The clustered edge walk pays a scatter pass at the end: worth it where the order is modelled to hit L2 for >= 40 % of the

@@ -6,6 +6,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/gespmm.h"
 #include "spmm_kernels.h"
 
 namespace gespmm {
@@ -109,6 +110,37 @@ bool prefer_segmented(const PlanFacts& f, double hits_after, int64_t N_launch);
 // ---- per launch at N_launch <= 64: four floats per lane (8 lanes per 32 columns = 8 rows per gather instruction) instead of the
 //      one-lane-per-column geometry AUTO takes at narrow widths
 bool narrow_vec4(const PlanFacts& f, double hits_after, int64_t N_launch);
+
+// ---- per launch: WHICH kernel a launch of a plan takes. One answer for gespmm_plan's launch (plan.cpp: plan_run), for the `kernel=...` text
+//      of gespmm_plan_describe and for the candidates of gespmm_plan_tune. A pure function of the plan's state and of the launch.
+inline bool variant_takes_vec4(int variant) {  // the variants whose launches may take the kernels with four floats per lane
+    return variant == GESPMM_VARIANT_AUTO || variant == GESPMM_VARIANT_CRC_CWM4 || variant == GESPMM_VARIANT_CRC_CWM8;
+}
+enum class PlanRoute { Records, StagedSlabs, StagedNarrow, StagedTuned, StagedGeneral, PlanStream, StorageOrder };
+struct RouteState {  // what the routing reads of a plan besides its facts
+    bool reordered = false;
+    bool has_staged = false, has_slabs = false, has_records = false, has_gtasks = false;  // which tables exist
+    bool staging_kept_by_policy = false;
+    bool tuned = false;
+    int tuned_kernel = 0, tuned_vec = 0;
+    int kernel_choice = 0;            // the creator's GESPMM_PLAN_KERNEL_*
+    double hits_after = -1.0;
+    int stg_waves = 0, stg_slots = 0, stg_nlong = 0;
+};
+struct RouteAnswer {
+    PlanRoute route = PlanRoute::StorageOrder;
+    // the streaming launch of a clustered plan at this width — the route itself when it is PlanStream, else what the same plan does
+    // where its tables do not serve (gespmm_plan_describe prints it beside them)
+    bool segmented = false;  // the segmented-stream kernel (else batch-stream)
+    bool vec4 = false;       // four floats per lane at a narrow width
+    bool hub_pass = false;   // Staged*: hub rows follow through the batch-stream kernel's long-row pass (a second launch)
+    bool staged() const { return route == PlanRoute::StagedNarrow || route == PlanRoute::StagedTuned || route == PlanRoute::StagedGeneral; }
+    // one kernel, so a launch guard can cover it (slabs: one launch per slab; hub rows: a second launch) — the streaming
+    // routes are judged by run_spmm, which knows their geometry
+    bool guardable() const { return route != PlanRoute::StagedSlabs && !hub_pass; }
+};
+// f: the plan's facts (f.N = the width its tables are made for); N, reduce, aligned16: the launch (operands on 16-byte boundaries)
+RouteAnswer plan_route(const PlanFacts& f, const RouteState& s, int64_t N, int reduce, bool aligned16);
 
 // ---- SDDMM through the plan: 0 = CSR form on the caller's arrays, 1 = COO form on expanded row ids (storage order),
 //      2 = the plan's clustered edge order + scatter

@@ -81,6 +81,17 @@ __device__ __forceinline__ int xcd_contiguous(int bid, int n) {
     return base + idx;
 }
 
+// Row that owns CSR position q: rowptr[r] <= q < rowptr[r + 1] (behind a run of equal pointers — empty rows — the last of them)
+__device__ __forceinline__ int row_of_entry(const int32_t* __restrict__ rowptr, int M, int q) {
+    int lo = 0, hi = M;  // rowptr[lo] <= q < rowptr[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rowptr[mid] <= q) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // Ordering of a wavefront's own LDS traffic (write by lane i, read by lane j of
 // the same wavefront). DS operations of one wavefront execute in issue order, so
 // no hardware barrier is needed — only the compiler must keep the order.

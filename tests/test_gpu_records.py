@@ -132,6 +132,28 @@ def test_rows_beyond_the_limit_and_unaligned_operands_fall_back(pkg, oracle):
     assert np.array_equal(bits(got), bits(oracle.spmm(rowptr, colind, val_h, B_h, "fma")))
 
 
+@pytest.mark.parametrize("reorder", (True, False))
+@pytest.mark.parametrize("variant", ("VARIANT_CRC", "VARIANT_CRC_CWM2"))
+def test_describe_names_the_streaming_kernel_when_the_variant_rules_the_records_out(pkg, oracle, bundled, variant, reorder):
+    """kernel="records" builds the tables on request, but a launch takes them only under a variant that admits the four-float kernels
+    (AUTO, CWM4, CWM8: plan_route). Under any other variant the streaming kernel of that variant ships the bits, and describe() — the
+    same routing answer — must say so instead of naming tables nothing walks."""
+    from gespmm_amd import _lib, spmm
+
+    g = bundled["cora"]
+    N = 32
+    var = getattr(_lib, variant)
+    rp, ci = _dev(g["rowptr"]), _dev(g["colind"])
+    val_h = oracle.hash_val(g["nnz"], seed=7)
+    B_h = oracle.hash_B(g["K"], N, seed=N)
+    val, B = _dev(val_h), _dev(B_h)
+    plan = spmm.SpmmPlan(rp, ci, g["K"], N, variant=var, values=val, reorder=reorder, kernel="records")
+    assert "kernel=padded-records" not in plan.describe(), plan.describe()
+    got = spmm.csr_spmm(rp, ci, val, B, variant=var, plan=plan).cpu().numpy()
+    assert np.array_equal(bits(got), bits(spmm.csr_spmm(rp, ci, val, B, variant=var).cpu().numpy())), plan.describe()
+    assert np.array_equal(bits(got), bits(oracle.spmm(g["rowptr"], g["colind"], val_h, B_h, "fma"))), plan.describe()
+
+
 def test_reduced_soak_of_the_record_kernel(pkg):
     """120 seeds of scripts/records_soak.py (random shapes, widths 4 .. 64, both orders, rows at and beyond the 1024-entry limit,
     valued / unweighted / new values) against the plain call's strict-order bits."""
