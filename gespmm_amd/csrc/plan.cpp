@@ -370,8 +370,8 @@ int gespmm_plan_debug_tasks(const gespmm_plan* p, int32_t which, int32_t* out_ho
 static hipError_t build_staging_tables(gespmm_plan* p, hipStream_t st) {
     const Stopwatch sw;
     const int64_t M = p->M, K = p->K, nnz = p->nnz, N = p->N;
-    gespmm::StagedShape shape = gespmm::staged_shape_any(N);  // (the block shape of whichever staged kernel serves the width)
-    if (!getenv("GESPMM_STAGED_ROWS")) shape.rows = gespmm::staged_rows_for(p->facts, shape.rows, shape.waves);  // (by mean degree: plan_policy.cpp)
+    gespmm::StagedShape shape = gespmm::staged_block_shape(N);  // (the block shape of whichever staged kernel serves the width)
+    shape.rows = gespmm::staged_rows_for(p->facts, shape);     // (by mean degree: plan_policy.cpp)
     hipError_t e = hipSuccess;
     const int32_t* rp_s = p->d_rowptr;
     const int32_t* ci_s = p->d_colind;
@@ -388,7 +388,7 @@ static hipError_t build_staging_tables(gespmm_plan* p, hipStream_t st) {
     }
     if (e == hipSuccess && nnz_s > 0)
         e = gespmm::device_build_staging(M, K, nnz_s, rp_s, ci_s, val_s, p->d_perm, shape.rows, shape.slots, shape.waves,
-                                         gespmm::staged_tasks_per_block(N), &p->stg, st);
+                                         shape.tasks_per_block, &p->stg, st);
     if (ci_tmp) (void)hipFree(ci_tmp);
     if (val_tmp) (void)hipFree(val_tmp);
     if (e == hipSuccess && !p->stg.ev) gespmm::free_staging(&p->stg);  // (nothing but hub rows)
@@ -402,12 +402,10 @@ static hipError_t build_staging_tables(gespmm_plan* p, hipStream_t st) {
 static hipError_t build_slab_tables(gespmm_plan* p, int P, hipStream_t st) {
     const Stopwatch sw;
     const int64_t M = p->M, K = p->K, nnz = p->nnz, N = p->N;
-    gespmm::StagedShape shape = gespmm::staged_shape(N);
+    gespmm::StagedShape shape = gespmm::staged_block_shape(N);
     static const int rows_env = getenv("GESPMM_SLAB_ROWS") ? atoi(getenv("GESPMM_SLAB_ROWS")) : 0;  // experiments
     if (rows_env > 0) shape.rows = rows_env;
-    static const int lds_env = getenv("GESPMM_SLAB_LDS_KB") ? atoi(getenv("GESPMM_SLAB_LDS_KB")) : 0;  // experiments: 3 = three 48 KB blocks per CU
-    if (N == 128 && shape.waves == 16 && shape.slots == 160 && lds_env == 3) shape.slots = 96;
-    if (N != 128 || shape.waves != 16 || (shape.slots != 160 && shape.slots != 96) || P < 2 || nnz <= 0 || !gespmm::staged_serves(M, K, N) ||
+    if (N != 128 || shape.waves != 16 || shape.slots != 160 || P < 2 || nnz <= 0 || !gespmm::staged_serves(M, K, N) ||
         !gespmm::staged_stream_fits(M * P, nnz) || M * P >= (1ll << 30))
         return hipSuccess;
     hipError_t e = gespmm::device_build_slab_view(M, K, nnz, p->d_rowptr, p->d_colind, p->valued ? p->d_val : nullptr, p->d_perm, P,
@@ -803,6 +801,22 @@ int gespmm_plan_create_v2(gespmm_plan** out, const int32_t* rowptr, const int32_
     return plan_create_impl(out, rowptr, colind, val, M, K, nnz, N, variant, opt ? &o : nullptr, stream);
 }
 
+// The launch arguments of a set of staging tables, field by field (width, tiles and `empty` are the general kernel's launcher's to fill).
+static gespmm::StagedArgs staged_args(const gespmm::StagingTables& t, const float* B, float* C, const gespmm::LaunchGuard* guard) {
+    gespmm::StagedArgs a = {};
+    a.ev = t.ev;
+    a.tasks = t.tasks;
+    a.hot_cols = t.hot_cols;
+    a.B = B;
+    a.C = C;
+    a.nblocks = t.nblocks;
+    a.waves = t.waves;
+    a.slots = t.slots;
+    a.guard = guard ? guard->word : nullptr;
+    a.guard_want = guard ? guard->want : 0;
+    return a;
+}
+
 static int plan_run(gespmm_plan* p, const float* B, float* C, int64_t N, int reduce, float empty, void* stream,
                     const gespmm::LaunchGuard* guard = nullptr) {
     using gespmm::PlanRoute;
@@ -834,8 +848,10 @@ static int plan_run(gespmm_plan* p, const float* B, float* C, int64_t N, int red
         // one launch of the staged-rows kernel per slab, the second and later ones continuing from C
         const int P = p->slab_view.slabs, nb = p->slab.nblocks / P;
         for (int s = 0; s < P && rc == 0; ++s) {
-            gespmm::StagedArgs sa = {p->slab_view.rowptr_v, p->slab.ev, nullptr, p->slab.tasks, p->slab.hot_cols, p->slab.nhot, B, C, nb,
-                                     p->slab.waves, p->slab.slots, 0, nullptr, 0, 0, 0.0f, nullptr, 0, s * nb, s > 0 ? 1 : 0};
+            gespmm::StagedArgs sa = staged_args(p->slab, B, C, nullptr);
+            sa.nblocks = nb;  // (this slab's blocks of the tables; the second and later ones continue from C)
+            sa.blk0 = s * nb;
+            sa.acc = s > 0 ? 1 : 0;
             rc = (int)gespmm::launch_spmm_staged(sa, p->M, p->K, N, hst);
         }
         return rc;
@@ -843,9 +859,7 @@ static int plan_run(gespmm_plan* p, const float* B, float* C, int64_t N, int red
     case PlanRoute::StagedTuned:
     case PlanRoute::StagedNarrow:
     case PlanRoute::StagedGeneral: {
-        gespmm::StagedArgs sa = {p->stg.rowptr_s ? p->stg.rowptr_s : p->d_rowptr, p->stg.ev, p->d_perm, p->stg.tasks, p->stg.hot_cols,
-                                 p->stg.nhot, B, C, p->stg.nblocks, p->stg.waves, p->stg.slots, 0, nullptr, 0, 0, 0.0f,
-                                 guard ? guard->word : nullptr, guard ? guard->want : 0};
+        const gespmm::StagedArgs sa = staged_args(p->stg, B, C, guard);
         if (ra.route == PlanRoute::StagedTuned) rc = (int)gespmm::launch_spmm_staged(sa, p->M, p->K, N, hst);
         else if (ra.route == PlanRoute::StagedNarrow) rc = (int)gespmm::launch_spmm_staged_narrow(sa, p->M, p->K, N, hst);
         else rc = (int)gespmm::launch_spmm_staged_gen(sa, p->M, p->K, N, reduce, empty, hst);
@@ -1130,7 +1144,7 @@ int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
                  p->slab_view.slabs, p->slab.nblocks, p->slab.slots, p->slab.staged_fraction, p->slab_seconds, what);
     else if (ra.staged())
         snprintf(kern, sizeof kern, "kernel=staged-rows blocks=%d rows_in_lds<=%d staged_entries=%.3f hub_rows=%d tables=%.4fs (max / other widths: %s)",
-                 p->stg.nblocks, gespmm::staged_shape_any(p->N).slots, p->stg.staged_fraction, p->stg.nlong, p->staging_seconds, what);
+                 p->stg.nblocks, gespmm::staged_block_shape(p->N).slots, p->stg.staged_fraction, p->stg.nlong, p->staging_seconds, what);
     else snprintf(kern, sizeof kern, "%s", what);
     int n;
     if (p->reordered) {

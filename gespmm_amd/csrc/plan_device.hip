@@ -1740,7 +1740,7 @@ hipError_t device_cut_tasks(int64_t M, const int32_t* rowptr_p, const int64_t bu
 
 // ------------------------------------------------------------------------------------------------ staging tables (spmm_staged.hip)
 //
-// Blocks of R consecutive rows of the clustered matrix (R = staged_block_rows(N)). Per block: the block's column indices sorted (one segment of
+// Blocks of R consecutive rows of the clustered matrix (R = the block shape's rows). Per block: the block's column indices sorted (one segment of
 // a segmented radix sort, payload = position of the entry), runs of equal columns = how often the block uses a B row; the H
 // most used ones (>= 2 uses; ties taken in column order, so the tables are the same on every build) get LDS slots.
 

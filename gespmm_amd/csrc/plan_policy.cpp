@@ -354,14 +354,63 @@ int records_batches_per_task(const PlanFacts& f) {
     return t < 3 ? 3 : (t > 24 ? 24 : t);
 }
 
-int staged_rows_for(const PlanFacts& f, int shape_rows, int shape_waves) {
+// The block shape of the staged-rows kernels at width N — the one table of these numbers (spmm_kernels.h: StagedShape).
+//   Every kernel: 16 wavefronts and 5 KB of staged B rows per wavefront — two blocks of 80 KB fill the CU's 160 KB exactly
+//     (profiles/r05/staged_lds5.log, 4 -> 5 KB at N = 128 / 256: geometric 202.6 -> 187.6 / 341.6 -> 326.3 us, small-world 350 -> 329 /
+//     618 -> 559, LFR 170 -> 168 / 338 -> 327, products-shaped 2.81 -> 2.77 / 5.27 -> 5.10 ms, com-Amazon-shaped level). 8 KB — ONE block
+//     per CU — lost 20-40 % (staged_lds_per_wave.log); blocks of 8 and 4 wavefronts lost as well (staged_block_shapes.log; at N = 32 / 64:
+//     narrow_shapes.log, narrow_lds5_interleaved.log). None of those kernels is built any more.
+//   Tuned widths (N = 128, 256 * 2^t), rows per block, measured on the products-shaped community graph (us at N = 128 / 256): 64 rows
+//     3286 / 5584, 80: 3122 / 5596, 96: 3012 / 5834, 112: 3120 / 6264, 128: 3065 / 6440 — about as many rows as LDS holds staged rows for
+//     the width's row size (profiles/r03/staged_rows.log): 6 rows per wavefront at 128-column tiles, 4 at 256; staged_rows_for below
+//     refines them by mean degree.
+//   Narrow widths (N = 16 / 32 / 64: W = N / 4 lanes per row, 64 / W lane groups = tasks per wavefront): as many rows per block as 64 KB
+//     of rows (N = 32: 384 / 512 / 640 / 768 / 1024 rows -> geometric 80.7 / 76.4 / 77.9 / 89.0 / 94.7 us, products-shaped 1214 / 1185 /
+//     1157 / 1188 / 1269; N = 64: 192 / 256 / 384 / 512 -> 127.6 / 124.5 / 132.1 / 139.9 us: profiles/r05/narrow_shapes.log).
+//   Every other width (the general kernel, staged_gen_vec(N) floats per lane): the rows of the tile width's tuned kernel (96 at
+//     128-column tiles, 64 at 256); 64-column tiles (odd widths) by the same rule "about as many rows as staged slots / 1.7".
+// The rows-per-block knobs of the recorded sweeps (profiles/r05, profiles/r06/scripts/rows_sweep.sh) are read here and nowhere else.
+StagedShape staged_block_shape(int64_t N) {
+    static const char* const rows_env = getenv("GESPMM_STAGED_ROWS");
+    static const int rows_tuned = rows_env ? atoi(rows_env) : 0;
+    static const int rows_narrow = getenv("GESPMM_STAGED_NARROW_ROWS") ? atoi(getenv("GESPMM_STAGED_NARROW_ROWS")) : 0;
+    static const int rows_gen = getenv("GESPMM_STAGED_GEN_ROWS") ? atoi(getenv("GESPMM_STAGED_GEN_ROWS")) : 0;
+    StagedShape sh = {};  // (cls = kStagedNone, waves = 0: width not served)
+    sh.rows_pinned = rows_env != nullptr;
+    const int v = staged_gen_vec(N);
+    if (!v) return sh;
+    constexpr int kLdsBytes = kStagedMaxWaves * kStagedLdsKb * 1024;
+    sh.waves = sh.tasks_per_block = kStagedMaxWaves;
+    sh.lds_kb = kStagedLdsKb;
+    sh.tile_cols = 64 * v;
+    int knob = rows_gen;
+    if (N == 16 || N == 32 || N == 64) {
+        sh.cls = kStagedNarrow;
+        sh.slots = kLdsBytes / (int)(N * 4);
+        sh.rows = kStagedMaxWaves * 4096 / (int)(N * 4);  // (512 / 256 rows at N = 32 / 64: what the sweep found)
+        sh.tasks_per_block = kStagedMaxWaves * (64 / (int)(N / 4));
+        knob = rows_narrow;
+    } else if (N == 128 || N == 256 || N == 512 || N == 1024) {
+        sh.cls = kStagedTuned;
+        sh.slots = kLdsBytes / (sh.tile_cols * 4);
+        sh.rows = (sh.tile_cols == 128 ? 6 : 4) * kStagedMaxWaves;
+        knob = rows_tuned;
+    } else {
+        sh.cls = kStagedGeneral;
+        sh.slots = kLdsBytes / (sh.tile_cols * 4);
+        sh.rows = v == 1 ? 192 : (v == 2 ? 96 : 64);
+    }
+    if (knob > 0) sh.rows = knob;
+    return sh;
+}
+
+int staged_rows_for(const PlanFacts& f, const StagedShape& shape) {
     const int sclass = staged_kernel_class(f.M, f.K, f.N);
-    if (shape_waves != kStagedMaxWaves || (sclass != kStagedTuned && sclass != kStagedGeneral)) return shape_rows;  // (narrow widths, experiment shapes)
+    if (shape.rows_pinned || (sclass != kStagedTuned && sclass != kStagedGeneral)) return shape.rows;  // (a sweep's rows; narrow widths)
     const int64_t mean = f.mean_ceil();
-    const int tc = staged_tile_class(f.N);
-    if (tc == 128) return mean <= 24 ? 112 : shape_rows;
-    if (tc == 256) return mean > 32 ? 48 : shape_rows;
-    return shape_rows;  // (64-column tiles: the general kernel's default)
+    if (shape.tile_cols == 128) return mean <= 24 ? 112 : shape.rows;
+    if (shape.tile_cols == 256) return mean > 32 ? 48 : shape.rows;
+    return shape.rows;  // (64-column tiles: the general kernel's default)
 }
 
 // Which streaming kernel a clustered plan launches (AUTO rule + the caller's choice).
@@ -412,7 +461,8 @@ RouteAnswer plan_route(const PlanFacts& f, const RouteState& s, int64_t N, int r
     const bool use_tuned = s.tuned && own_width;
     const int kchoice = use_tuned ? s.tuned_kernel : s.kernel_choice;
     const int sclass = staged_kernel_class(f.M, f.K, N, reduce);
-    const bool shape_ok = sclass != kStagedGeneral || (s.stg_waves == staged_gen_shape(N).waves && s.stg_slots == staged_gen_shape(N).slots);
+    const StagedShape shape = staged_block_shape(N);
+    const bool shape_ok = sclass != kStagedGeneral || (s.stg_waves == shape.waves && s.stg_slots == shape.slots);
     const bool staged = s.reordered && s.has_staged && own_width && sclass != kStagedNone && shape_ok && v4 && aligned16 &&
                         (kchoice == GESPMM_PLAN_KERNEL_STAGED || (!use_tuned && kchoice == GESPMM_PLAN_KERNEL_AUTO && s.staging_kept_by_policy));
     if (s.reordered) {  // the streaming launch of this width (what the table routes fall back to for the max reducer or unaligned operands)
@@ -549,8 +599,8 @@ extern "C" int gespmm_plan_policy_v2(const gespmm_plan_policy_query* q_in, int64
     a->cluster_levels = ad.analyse ? gespmm::cluster_levels_for(f) : 0;
     a->cluster_sweeps = ad.analyse ? gespmm::cluster_sweeps_for(f) : 0;
     {
-        const gespmm::StagedShape sh = gespmm::staged_shape_any(q->N);
-        a->staged_rows = sh.waves ? gespmm::staged_rows_for(f, sh.rows, sh.waves) : 0;
+        const gespmm::StagedShape sh = gespmm::staged_block_shape(q->N);
+        a->staged_rows = sh.waves ? gespmm::staged_rows_for(f, sh) : 0;
     }
     // the padded-record kernel (plan.cpp builds its tables after the staged ones: not beside tables that were kept)
     a->build_records = gespmm::records_serves(q->M, q->K, q->N, q->max_degree) && q->nnz > 0 && gespmm::want_record_tables(f, !ad.analyse ? -1.0 : (keep ? q->hits_after : q->hits_before)) &&

@@ -74,7 +74,7 @@ bool analysis_could_pay(int64_t M, int64_t K, int64_t nnz, int64_t N, int expect
 int cluster_levels_for(const PlanFacts& f);
 int cluster_sweeps_for(const PlanFacts& f);  // label-propagation sweeps per level (0 = the clustering's own default)
 int model_points_for(const PlanFacts& f);    // sampled accesses per slice in the L2 model
-int staged_rows_for(const PlanFacts& f, int shape_rows, int shape_waves);  // rows per block of the staged-rows kernel
+int staged_rows_for(const PlanFacts& f, const StagedShape& shape);  // rows per block of the staged-rows kernel
 
 // ---- after the model: is the clustered order worth its per-launch indirection?
 bool keep_clustered_order(const PlanFacts& f, const AnalysisDecision& a, double hits_before, double hits_after);

@@ -114,33 +114,35 @@ hipError_t launch_spmm_parreduce(const SpmmArgs& a, const Geometry& geo, hipStre
 
 // spmm_staged.hip — scalar-stream kernel with a block's most used B rows staged in LDS (clustered plans, N = 128 / 256 and, as
 // 256-column tiles bound to XCDs, 512 / 1024; sum).
-// plan_device.hip (device_build_staging) writes the tables: blocks of staged_block_rows(N) consecutive rows of the clustered matrix,
+// plan_device.hip (device_build_staging) writes the tables: blocks of staged_block_shape(N).rows consecutive rows of the clustered matrix,
 // `waves` tasks per block (int4 {first row, #rows, stream begin, stream end}), per block the staged columns, and the record stream
 // `ev`: per row its entries {code, value bits} (bit 31 of the code clear: column; set: staged slot in its low bits) followed by ONE
 // row-end record {kStagedRowEnd, C row of that row} — also for rows without entries — so a wavefront needs nothing but its stream
 // range: no row pointers, no row ids, no position compares on the walk (round 5). Record position of entry p of row r: p + r; the
 // stream is padded by kStagedPad records.
-constexpr int kStagedMaxWaves = 16;      // wavefronts per block: 4, 8 or 16 (StagedShape)
-constexpr int kStagedLdsPerWave = 4096;  // bytes of staged B rows per wavefront of the block (16 wavefronts: 64 KB); GESPMM_STAGED_LDS_KB=8: 8192
+constexpr int kStagedMaxWaves = 16;      // wavefronts per block
+constexpr int kStagedLdsKb = 5;          // KB of staged B rows per wavefront of the block: two 80 KB blocks fill the CU's 160 KB
 constexpr int kStagedPad = 64;
 constexpr int kStagedRowEnd = 0x40000000;  // code of a row-end record (both address shifts of the kernel drop the bit: slot 0 / column 0)
 constexpr int kStagedMaxRow = 2048;  // longer rows are walked by the streaming kernel's long-row pass, not by one wavefront
 inline bool staged_stream_fits(int64_t M, int64_t nnz) { return nnz + M + kStagedPad < (1ll << 31) - 64; }  // 32-bit stream positions
+// (rowptr, perm, nhot, debug and dbg_clk are read by no kernel and filled by no caller. They keep their places: without them the
+//  compiler merges the kernels' argument loads differently (two s_load_dwordx4 become an x2 and an x8, registers renumber) in all 16
+//  kernels, and that change wants a timing comparison of its own.)
 struct StagedArgs {
-    const int32_t* rowptr;    // clustered matrix (not read by the kernel since round 5: the stream carries the row ends)
+    const int32_t* rowptr;    // unused
     const int32_t* ev;        // 2 * (nnz + M + kStagedPad) words
-    const int32_t* perm;      // C row of clustered row i (not read by the kernel since round 5: the row-end records carry it)
+    const int32_t* perm;      // unused
     const int32_t* tasks;     // nblocks * waves int4
-    const int32_t* hot_cols;  // nblocks * H (H = staged_shape(N).slots)
-    const int32_t* nhot;      // nblocks
+    const int32_t* hot_cols;  // nblocks * H (H = staged_block_shape(N).slots)
+    const int32_t* nhot;      // unused
     const float* B;
     float* C;
     int32_t nblocks;
     int32_t waves;            // wavefronts (= tasks) per block the tables were built for
-    int32_t slots;            // staged rows per block the tables were built for (H: decides the LDS per wavefront, 4 or 8 KB)
-    int32_t debug;            // experiments only (GESPMM_STAGED_DEBUG): 1 = skip the staging copy, 2 = every gather from LDS — WRONG results;
-                              // 4 = phase clocks summed into dbg_clk
-    unsigned long long* dbg_clk;
+    int32_t slots;            // staged rows per block the tables were built for (H: kStagedLdsKb KB of LDS per wavefront, else the launch is refused)
+    int32_t debug;            // unused
+    unsigned long long* dbg_clk;  // unused
     // spmm_staged_gen.hip (filled in by its launcher): width, column tiles of 64 * VEC columns, value of rows without entries (max reducer)
     int32_t n;
     int32_t ntiles;
@@ -152,20 +154,24 @@ struct StagedArgs {
     int32_t blk0;
     int32_t acc;
 };
-// Shape of a block at width N: `waves` wavefronts (0 = width not served) own `rows` consecutive rows of the clustered matrix and
-// stage up to `slots` B rows (waves x 4 KB of LDS). GESPMM_STAGED_WAVES / GESPMM_STAGED_ROWS override it for experiments.
+// Which of the three kernels walks a plan's tables at width N: 1 = lane groups (N = 16 / 32 / 64, sum), 2 = spmm_staged.hip's tuned shapes
+// (N = 128, 256 * 2^t, sum), 3 = the general kernel (every other width; the max reducer at every width but 16 / 32 / 64), 0 = none.
+enum { kStagedNone = 0, kStagedNarrow = 1, kStagedTuned = 2, kStagedGeneral = 3 };
+// Shape of a block at width N, for whichever kernel serves the width (plan_policy.cpp: the ONE table of these numbers, and the one
+// place the rows-per-block knobs are read): `waves` wavefronts (0 = width not served) own `rows` consecutive rows of the clustered
+// matrix, stage up to `slots` B rows (waves x lds_kb KB of LDS) and walk `tasks_per_block` ranges of the record stream. At the tuned
+// widths the general kernel (max reducer) has the tuned kernel's waves and slots: one set of tables serves both.
 struct StagedShape {
-    int waves, rows, slots;
+    int cls;         // kStagedNarrow / kStagedTuned / kStagedGeneral by WIDTH alone (sum reducer; staged_kernel_class adds reducer and sizes)
+    int waves, rows, slots, tasks_per_block, lds_kb;
+    int tile_cols;   // columns of one tile of the wide kernels (128 / 256: the tile classes the policy's thresholds are measured for; 64: odd widths)
+    bool rows_pinned;  // GESPMM_STAGED_ROWS is set: the rule by mean degree (staged_rows_for) stays out
 };
-StagedShape staged_shape(int64_t N);
-inline int staged_rows_per_block_lds(int64_t N) { return staged_shape(N).slots; }  // H for this width; 0 = width not served
-inline int staged_block_rows(int64_t N) { return staged_shape(N).rows; }
+StagedShape staged_block_shape(int64_t N);
 bool staged_serves(int64_t M, int64_t K, int64_t N);  // width served, B and C addressable (32-bit offsets; two 4 GB halves for the tiled widths)
 hipError_t launch_spmm_staged(const StagedArgs& a, int64_t M, int64_t K, int64_t N, hipStream_t st);
 // spmm_staged_narrow.hip — the same tables at N = 16 / 32 / 64: a wavefront is G = 64 / (N / 4) lane groups, each walking its own range
 // of the record stream (`waves` x G tasks per block); staged rows from LDS and memory rows under complementary EXEC masks.
-StagedShape staged_narrow_shape(int64_t N);  // waves = 0: width not served
-int staged_narrow_groups(int64_t N);         // lane groups (tasks) per wavefront
 bool staged_narrow_serves(int64_t M, int64_t K, int64_t N);
 hipError_t launch_spmm_staged_narrow(const StagedArgs& a, int64_t M, int64_t K, int64_t N, hipStream_t st);
 // spmm_staged_gen.hip — the same kernel for ANY width and for the max reducer (round 6): VEC = staged_gen_vec(N) floats per lane, column
@@ -173,33 +179,15 @@ hipError_t launch_spmm_staged_narrow(const StagedArgs& a, int64_t M, int64_t K, 
 // 80 KB / (256 * VEC) slots (for N = 128 and 256 * 2^t the shapes of spmm_staged.hip: one set of tables serves its sum kernel and this
 // file's max kernel).
 int staged_gen_vec(int64_t N);  // 1, 2 or 4 (0: N < 1)
-StagedShape staged_gen_shape(int64_t N);
 bool staged_gen_serves(int64_t M, int64_t K, int64_t N);
 hipError_t launch_spmm_staged_gen(const StagedArgs& a, int64_t M, int64_t K, int64_t N, int reduce, float empty, hipStream_t st);
-// Which of the three kernels walks a plan's tables at width N: 1 = lane groups (N = 16 / 32 / 64, sum), 2 = spmm_staged.hip's tuned shapes
-// (N = 128, 256 * 2^t, sum), 3 = the general kernel (every other width; the max reducer at every width but 16 / 32 / 64), 0 = none.
-enum { kStagedNone = 0, kStagedNarrow = 1, kStagedTuned = 2, kStagedGeneral = 3 };
 inline int staged_kernel_class(int64_t M, int64_t K, int64_t N, int reduce = kReduceSum) {
-    if (staged_narrow_shape(N).waves) return (reduce == kReduceSum && staged_narrow_serves(M, K, N)) ? kStagedNarrow : kStagedNone;
-    if (reduce == kReduceSum && staged_serves(M, K, N)) return kStagedTuned;
+    const int cls = staged_block_shape(N).cls;
+    if (cls == kStagedNarrow) return (reduce == kReduceSum && staged_narrow_serves(M, K, N)) ? kStagedNarrow : kStagedNone;
+    if (cls == kStagedTuned && reduce == kReduceSum && staged_serves(M, K, N)) return kStagedTuned;
     return staged_gen_serves(M, K, N) ? kStagedGeneral : kStagedNone;
 }
-// Columns of one tile of the wide kernels at width N (128 / 256: the tile classes the policy's thresholds are measured for; 64: odd widths)
-inline int staged_tile_class(int64_t N) { return 64 * staged_gen_vec(N); }
-// any kernel: the block shape of width N (waves = 0: none serves it) and the tasks per block
-inline StagedShape staged_shape_any(int64_t N) {
-    const StagedShape w = staged_shape(N);
-    if (w.waves) return w;
-    const StagedShape nw = staged_narrow_shape(N);
-    return nw.waves ? nw : staged_gen_shape(N);
-}
-inline int staged_tasks_per_block(int64_t N) {
-    const StagedShape w = staged_shape(N);
-    if (w.waves) return w.waves;
-    const StagedShape nw = staged_narrow_shape(N);
-    if (nw.waves) return nw.waves * staged_narrow_groups(N);
-    return staged_gen_shape(N).waves;
-}
+inline int staged_tile_class(int64_t N) { return staged_block_shape(N).tile_cols; }
 inline bool staged_serves_any(int64_t M, int64_t K, int64_t N) { return staged_kernel_class(M, K, N) != kStagedNone; }
 
 // spmm_records.hip — the padded-record kernel (round 6): narrow widths (4 <= N <= 64), short rows, sum reducer, plans only. A row
@@ -232,10 +220,6 @@ struct RecordArgs {
     int32_t n;
     const int32_t* guard;  // launch guard, as in SpmmArgs (NULL: no check)
     int32_t guard_want;
-    // column-slab tables (plan.cpp: build_slab_tables; spmm_staged.hip only): the launch covers blocks blk0 .. blk0 + nblocks - 1 of the
-    // tables; acc != 0: rows continue from the partial sums in C (task word 0 = C row of the task's first row, row-end codes carry the next)
-    int32_t blk0;
-    int32_t acc;
 };
 int records_group(int64_t N);  // lanes per chain at width N (0: width not served)
 bool records_serves(int64_t M, int64_t K, int64_t N, int32_t max_degree);

@@ -11,9 +11,10 @@
 //     same for the 64 lanes — a record's code and value — is read out of the wavefront's window of the stream into SGPR pairs;
 //     "is this entry's B row staged?" is a SCALAR branch around one of {ds_read, global_load}: a staged entry issues no
 //     vector memory instruction at all;
-//   * a workgroup of 16 wavefronts owns a BLOCK of 96 (N = 128) / 64 (N = 256) consecutive rows of the plan's clustered matrix; the analysis
+//   * a workgroup of 16 wavefronts owns a BLOCK of consecutive rows of the plan's clustered matrix (96 / 64 at 128 / 256-column tiles,
+//     refined by mean degree: plan_policy.cpp, staged_block_shape and staged_rows_for); the analysis
 //     (plan_device.hip: device_build_staging) lists per block the <= H columns used most often inside it (>= 2 uses; H rows =
-//     64 KB) and rewrites the block's entries: bit 31 of the code clear = column, set = slot of the staged row. The workgroup copies
+//     80 KB: two blocks fill a CU's LDS) and rewrites the block's entries: bit 31 of the code clear = column, set = slot of the staged row. The workgroup copies
 //     the listed rows into LDS once, coalesced, then each wavefront walks its share of the block's rows as one stream;
 //   * THE RECORD STREAM (round 5): per row its entries {code, value} and then ONE row-end record {kStagedRowEnd, C row} — rows
 //     without entries have theirs too. A wavefront needs nothing but a range of that stream: no row pointers, no row ids, no
@@ -40,8 +41,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -51,12 +50,6 @@
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 // (80 KB of static LDS per workgroup — gfx942 stops at 64 KB — and inline assembly that spells sc1 / nt modifiers and SGPR-base global loads)
 #error "spmm_staged.hip is written for gfx950: its LDS shapes and inline assembly do not build elsewhere"
-#endif
-
-// Experiments only: -DGESPMM_STAGED_INSTRUMENT=1 compiles the GESPMM_STAGED_DEBUG knobs in (1 = no staging copy, 2 = every gather from
-// LDS — both give WRONG results, they time the skeleton; 4 = per-wavefront phase clocks printed by the launcher). Off: they fold away.
-#ifndef GESPMM_STAGED_INSTRUMENT
-#define GESPMM_STAGED_INSTRUMENT 0
 #endif
 
 namespace gespmm {
@@ -96,7 +89,7 @@ template <int VEC, int U, int TSHIFT, bool PAGE2, int WAVES, int LK, bool ACC = 
 __global__ __launch_bounds__(WAVES * 64) void spmm_staged_kernel(StagedArgs a) {
     static_assert(!ACC || (VEC == 2 && TSHIFT == 0 && !PAGE2), "the continuing form exists for the 128-column shape");
     constexpr int kStagedWaves = WAVES;
-    constexpr int kStagedLdsBytes = WAVES * LK * 1024;  // LK KB of staged B rows per wavefront of the block (4: two blocks per CU; 8: one)
+    constexpr int kStagedLdsBytes = WAVES * LK * 1024;  // LK KB of staged B rows per wavefront of the block (built: 16 x 5 KB, two blocks per CU)
     constexpr int P = LK;                                // 16-byte pieces of the staging copy per thread
     using vec_t = typename LaneVec<VEC>::type;
     constexpr int kRowBytes = 256 * VEC;          // bytes of a row inside one tile
@@ -124,8 +117,6 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_staged_kernel(StagedArgs a) {
         const int q = a.nblocks / NX, r = a.nblocks % NX;
         blk = ((x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q) + idx;
     }
-    const int dbg = GESPMM_STAGED_INSTRUMENT ? a.debug : 0;
-    const uint64_t t_start = (dbg & 4) ? __builtin_readcyclecounter() : 0;
     const int task = blk * kStagedWaves + wave;
     // Round trip 1 — everything whose address follows from the block id alone: the wavefront's task (scalar) and the block's staged
     // columns (vector; thread t copies the 16-byte pieces t, t + T, ... (P of them) of the H x row-bytes array, T = threads per block).
@@ -134,7 +125,7 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_staged_kernel(StagedArgs a) {
     static_assert(H * kRowF4 == P * kStagedWaves * 64, "P pieces per thread");
     int hcol[P];
 #pragma unroll
-    for (int u = 0; u < P; ++u) hcol[u] = (dbg & 1) ? -1 : hc[(u * kStagedWaves * 64 + tid) / kRowF4];
+    for (int u = 0; u < P; ++u) hcol[u] = hc[(u * kStagedWaves * 64 + tid) / kRowF4];
     const int wb = tk[2], we = tk[3];  // the wavefront's range of the record stream (entries + one row-end record per row)
     const int crow0 = ACC ? tk[0] : 0;  // (slab tables: C row of the task's first row)
     const float* Bp = a.B + (size_t)tile * (64 * VEC);
@@ -166,11 +157,6 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_staged_kernel(StagedArgs a) {
         if (hcol[u] >= 0) s_hot[u * kStagedWaves * 64 + tid] = stage[u];
     __syncthreads();
     __builtin_amdgcn_s_waitcnt(0);  // the compiler's scoreboard is clean when the assembly gathers start
-    uint64_t t_staged = 0;
-    if (dbg & 4) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        t_staged = __builtin_readcyclecounter();
-    }
     if (we <= wb) return;  // (a task without rows)
     // one offset serves both paths (LDS address of a staged row / byte offset into B): the staging array must sit at LDS address 0
     // (it is the kernel's only LDS object; a compile-time constant — the check folds away)
@@ -369,7 +355,7 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_staged_kernel(StagedArgs a) {
         // themselves wait for the vector memory counter, and those wait for their own (younger) loads anyway
         i2v nxt = win;
         if (kw + kWin < we) nxt = __builtin_nontemporal_load(evv + (kw - wb) + kWin + lane);
-        const uint64_t gmask = (dbg & 2) ? 0ull : __ballot((uint32_t)win.x < (uint32_t)kStagedRowEnd);  // B row from memory
+        const uint64_t gmask = __ballot((uint32_t)win.x < (uint32_t)kStagedRowEnd);                  // B row from memory
         uint64_t lmask = __ballot((win.x & kStagedRowEnd) != 0 && win.x >= 0);                          // row-end records ...
         if (we - kw < kWin) lmask &= (1ull << (we - kw)) - 1ull;                                          // ... of THIS task
 #pragma unroll 1
@@ -405,18 +391,6 @@ __global__ __launch_bounds__(WAVES * 64) void spmm_staged_kernel(StagedArgs a) {
         }
         win = nxt;
     }
-    if (dbg & 4) {
-        const uint64_t t_walk = __builtin_readcyclecounter();
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        const uint64_t t_end = __builtin_readcyclecounter();
-        if (lane == 0) {  // one record per wavefront (atomics on four words would serialise the whole launch)
-            unsigned long long* rec = a.dbg_clk + (size_t)task * 4;
-            rec[0] = t_staged - t_start;
-            rec[1] = t_walk - t_staged;
-            rec[2] = t_end - t_walk;
-            rec[3] = t_start;
-        }
-    }
 }
 
 }  // namespace
@@ -431,29 +405,6 @@ static int staged_tile_cols(int64_t N, int* tshift) {
     return 0;
 }
 
-StagedShape staged_shape(int64_t N) {
-    // rows per block, measured on the products-shaped community graph with 16 wavefronts (us at N = 128 / 256): 64 rows 3286 / 5584,
-    // 80: 3122 / 5596, 96: 3012 / 5834, 112: 3120 / 6264, 128: 3065 / 6440 — about as many rows as LDS holds staged rows for the
-    // width's row size (profiles/r03/staged_rows.log): 6 rows per wavefront at 128-column tiles, 4 at 256
-    static const int waves_env = getenv("GESPMM_STAGED_WAVES") ? atoi(getenv("GESPMM_STAGED_WAVES")) : 0;
-    static const int rows_env = getenv("GESPMM_STAGED_ROWS") ? atoi(getenv("GESPMM_STAGED_ROWS")) : 0;
-    int t;
-    const int tc = staged_tile_cols(N, &t);
-    StagedShape sh = {0, 0, 0};
-    if (!tc) return sh;
-    sh.waves = (waves_env == 4 || waves_env == 8 || waves_env == 16) ? waves_env : kStagedMaxWaves;
-    // LDS per wavefront: 5 KB — two 16-wavefront blocks of 80 KB fill the CU's 160 KB exactly, 160 / 80 staged rows per block instead of
-    // 128 / 64 (profiles/r05/staged_lds5.log, 4 -> 5 KB at N = 128 / 256: geometric 202.6 -> 187.6 / 341.6 -> 326.3 us, small-world 350 ->
-    // 329 / 618 -> 559, LFR 170 -> 168 / 338 -> 327, products-shaped 2.81 -> 2.77 / 5.27 -> 5.10 ms, com-Amazon-shaped level). 8 KB — ONE
-    // block per CU — lost 20-40 % (staged_lds_per_wave.log). GESPMM_STAGED_LDS_KB=4 brings the 64 KB blocks back; smaller blocks keep 4.
-    static const int lds_env = getenv("GESPMM_STAGED_LDS_KB") ? atoi(getenv("GESPMM_STAGED_LDS_KB")) : 0;
-    const int lds_kb = (sh.waves == 16 && lds_env != 4) ? 5 : 4;
-    sh.rows = (tc == 128 ? 6 : 4) * sh.waves;
-    if (rows_env > 0) sh.rows = rows_env;
-    sh.slots = sh.waves * lds_kb * 1024 / (tc * 4);
-    return sh;
-}
-
 // B and C rows are addressed by a 32-bit lane offset from an SGPR base: the larger of the two matrices must stay below 4 GB — or, for the
 // tiled widths, below 8 GB (two 4 GB halves, the base chosen by one bit of the row index).
 bool staged_serves(int64_t M, int64_t K, int64_t N) {
@@ -463,89 +414,38 @@ bool staged_serves(int64_t M, int64_t K, int64_t N) {
     return bytes < 0xFFFF0000ull || (t >= 1 && bytes < 0x1FFFF0000ull);
 }
 
-hipError_t launch_spmm_staged(const StagedArgs& a_in, int64_t M, int64_t K, int64_t N, hipStream_t st) {
-    StagedArgs a = a_in;
-    static const int dbg_env = (GESPMM_STAGED_INSTRUMENT && getenv("GESPMM_STAGED_DEBUG")) ? atoi(getenv("GESPMM_STAGED_DEBUG")) : 0;
-    a.debug = dbg_env;
-    static unsigned long long* dbg_buf = nullptr;
-    static size_t dbg_cap = 0;
-    const size_t dbg_need = (size_t)a.nblocks * (size_t)a.waves * 4;
-    if ((dbg_env & 4) && dbg_cap < dbg_need) {
-        if (dbg_buf) (void)hipFree(dbg_buf);
-        if (hipMalloc(reinterpret_cast<void**>(&dbg_buf), dbg_need * 8) != hipSuccess) return hipErrorOutOfMemory;
-        dbg_cap = dbg_need;
-    }
-    if (dbg_env & 4) (void)hipMemsetAsync(dbg_buf, 0, dbg_need * 8, st);
-    a.dbg_clk = dbg_buf;
+hipError_t launch_spmm_staged(const StagedArgs& a, int64_t M, int64_t K, int64_t N, hipStream_t st) {
     if (a.nblocks <= 0) return hipSuccess;
     if (!staged_serves(M, K, N)) return hipErrorInvalidValue;
     int t;
     const int tc = staged_tile_cols(N, &t);
     const bool paged = (uint64_t)(M > K ? M : K) * (uint64_t)N * 4ull >= 0xFFFF0000ull;
     const dim3 grid((unsigned)a.nblocks << (t > 0 ? t : 0)), block((unsigned)a.waves * 64);
-    static const int u_env = getenv("GESPMM_STAGED_U") ? atoi(getenv("GESPMM_STAGED_U")) : 0;  // experiment knob: entries in flight per wavefront
-    const int lds_kb = a.slots > 0 ? (int)((int64_t)a.slots * tc * 4 / ((int64_t)a.waves * 1024)) : 4;  // what the tables were built for
-    // (8 KB per wavefront — one 16-wavefront block per CU with twice the staged rows — was built and measured: 20-40 % slower on every
-    //  graph, products-shaped 3.92 vs 2.79 ms, geometric 240 vs 193 us: two blocks per CU hide each other's staging round trips, one does
-    //  not. profiles/r05/staged_lds_per_wave.log; the kernel stays generic in LK, only 4 is instantiated)
-    if (lds_kb != 4 && !(lds_kb == 5 && a.waves == 16) && !(lds_kb == 3 && a.waves == 16)) return hipErrorInvalidValue;
-    if (lds_kb == 3) {  // (column-slab tables built for THREE 48 KB blocks per CU: 96 staged rows, 8 gathers per chunk — 33 VGPRs)
-        if (!(tc == 128 && a.waves == 16)) return hipErrorInvalidValue;
-        if (a.acc) hipLaunchKernelGGL((spmm_staged_kernel<2, 8, 0, false, 16, 3, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((spmm_staged_kernel<2, 8, 0, false, 16, 3, false>), grid, block, 0, st, a);
-        return hipGetLastError();
-    }
-    if (a.acc) {  // (column-slab tables, second and later slabs: the 128-column shape only)
-        if (!(tc == 128 && a.waves == 16 && lds_kb == 5)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((spmm_staged_kernel<2, 16, 0, false, 16, 5, true>), grid, block, 0, st, a);
-        return hipGetLastError();
-    }
-#define GESPMM_STAGED_LAUNCH(VEC, U, TS, PG)                                                                                   \
-    do {                                                                                                                       \
-        if (a.waves == 16 && lds_kb == 5) hipLaunchKernelGGL((spmm_staged_kernel<VEC, U, TS, PG, 16, 5>), grid, block, 0, st, a);   \
-        else if (a.waves == 16) hipLaunchKernelGGL((spmm_staged_kernel<VEC, U, TS, PG, 16, 4>), grid, block, 0, st, a);   \
-        else if (a.waves == 8) hipLaunchKernelGGL((spmm_staged_kernel<VEC, U, TS, PG, 8, 4>), grid, block, 0, st, a);          \
-        else if (a.waves == 4) hipLaunchKernelGGL((spmm_staged_kernel<VEC, U, TS, PG, 4, 4>), grid, block, 0, st, a);          \
-        else return hipErrorInvalidValue;                                                                                      \
-    } while (0)
+    // One block shape is built (plan_policy.cpp: staged_block_shape, with the measurements behind it): 16 wavefronts, 5 KB of staged rows
+    // each. (8 KB per wavefront — one 16-wavefront block per CU with twice the staged rows — was built and measured: 20-40 % slower on
+    //  every graph, products-shaped 3.92 vs 2.79 ms, geometric 240 vs 193 us: two blocks per CU hide each other's staging round trips, one
+    //  does not. profiles/r05/staged_lds_per_wave.log. Column-slab tables built for THREE 48 KB blocks per CU — 96 staged rows, 8 gathers
+    //  per chunk, 33 VGPRs — ran 2.62-2.91 ms where the 80 KB blocks run 2.43: profiles/r06/slabs/slab_sweep2.log.)
+    const StagedShape shape = staged_block_shape(N);
+    if (a.waves != shape.waves || a.slots != shape.slots) return hipErrorInvalidValue;  // tables of another block shape
+    if (a.acc && tc != 128) return hipErrorInvalidValue;  // (column-slab tables, second and later slabs: the 128-column shape only)
+#define GESPMM_STAGED_LAUNCH(VEC, U, TS, PG, ACC) \
+    hipLaunchKernelGGL((spmm_staged_kernel<VEC, U, TS, PG, kStagedMaxWaves, kStagedLdsKb, ACC>), grid, block, 0, st, a)
     // 128 columns: 16 gathers per chunk (57 registers: still eight wavefronts per SIMD). With the retuned blocks, interleaved three times
     // (profiles/r05/staged_u16_lds5.log, 8 -> 16): products-shaped 2.80 -> 2.69 ms, LFR 169 -> 164 us, com-Amazon-shaped 91.2 -> 89.4,
     // small-world 336 -> 330, geometric 188 -> 190; with round 5's first blocks it was level (staged_gathers_per_chunk.log). The
-    // 256-column tiles hold four registers per gathered row: 16 rows would not fit 64 registers.
-    if (tc == 128 && u_env != 8) GESPMM_STAGED_LAUNCH(2, 16, 0, false);
-    else if (tc == 128) GESPMM_STAGED_LAUNCH(2, 8, 0, false);
-    else if (tc == 256 && t == 0) GESPMM_STAGED_LAUNCH(4, 8, 0, false);
-    else if (tc == 256 && t == 1 && !paged) GESPMM_STAGED_LAUNCH(4, 8, 1, false);
-    else if (tc == 256 && t == 1 && paged) GESPMM_STAGED_LAUNCH(4, 8, 1, true);
-    else if (tc == 256 && t == 2 && !paged) GESPMM_STAGED_LAUNCH(4, 8, 2, false);
-    else if (tc == 256 && t == 2 && paged) GESPMM_STAGED_LAUNCH(4, 8, 2, true);
+    // 256-column tiles hold four registers per gathered row: 16 rows would not fit 64 registers. (The U = 8 form of the 128-column shape
+    // is no longer built: the figures above are its comparison.)
+    if (tc == 128 && a.acc) GESPMM_STAGED_LAUNCH(2, 16, 0, false, true);
+    else if (tc == 128) GESPMM_STAGED_LAUNCH(2, 16, 0, false, false);
+    else if (tc == 256 && t == 0) GESPMM_STAGED_LAUNCH(4, 8, 0, false, false);
+    else if (tc == 256 && t == 1 && !paged) GESPMM_STAGED_LAUNCH(4, 8, 1, false, false);
+    else if (tc == 256 && t == 1 && paged) GESPMM_STAGED_LAUNCH(4, 8, 1, true, false);
+    else if (tc == 256 && t == 2 && !paged) GESPMM_STAGED_LAUNCH(4, 8, 2, false, false);
+    else if (tc == 256 && t == 2 && paged) GESPMM_STAGED_LAUNCH(4, 8, 2, true, false);
     else
         return hipErrorInvalidValue;
 #undef GESPMM_STAGED_LAUNCH
-    if (dbg_env & 4) {
-        static int printed = 0;
-        (void)hipStreamSynchronize(st);
-        if (printed++ < 6 && t <= 0) {
-            const size_t nw = (size_t)a.nblocks * (size_t)a.waves;
-            unsigned long long* h = (unsigned long long*)malloc(nw * 32);
-            (void)hipMemcpy(h, dbg_buf, nw * 32, hipMemcpyDeviceToHost);
-            double sum[3] = {0, 0, 0};
-            unsigned long long t0 = ~0ull, t1 = 0;
-            size_t n = 0;
-            for (size_t i = 0; i < nw; ++i) {
-                if (!h[4 * i + 3]) continue;
-                ++n;
-                for (int q = 0; q < 3; ++q) sum[q] += (double)h[4 * i + q];
-                if (h[4 * i + 3] < t0) t0 = h[4 * i + 3];
-                const unsigned long long e = h[4 * i + 3] + h[4 * i] + h[4 * i + 1] + h[4 * i + 2];
-                if (e > t1) t1 = e;
-            }
-            if (n)
-                fprintf(stderr, "[staged clk] %zu wavefronts: to-staged %.0f walk %.0f drain %.0f cycles per wavefront; first start to last end %llu cycles\n",
-                        n, sum[0] / n, sum[1] / n, sum[2] / n, t1 - t0);
-            free(h);
-        }
-    }
     return hipGetLastError();
 }
 

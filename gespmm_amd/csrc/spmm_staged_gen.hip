@@ -25,7 +25,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -59,7 +58,7 @@ template <> struct GenVec<2> { using type = v2f; };
 template <> struct GenVec<4> { using type = f4v; };
 
 constexpr int kGenWaves = kStagedMaxWaves;  // 16 wavefronts per block
-constexpr int kGenLdsKb = 5;                // 5 KB of staged rows per wavefront: two blocks fill the CU's 160 KB (spmm_staged.hip)
+constexpr int kGenLdsKb = kStagedLdsKb;     // 5 KB of staged rows per wavefront: two blocks fill the CU's 160 KB
 
 template <int VEC, int RED>
 __global__ __launch_bounds__(kGenWaves * 64, 8) void spmm_staged_gen_kernel(StagedArgs a) {  // (8 wavefronts per SIMD = two blocks per CU: <= 64 VGPRs)
@@ -359,19 +358,6 @@ int staged_gen_vec(int64_t N) {
     return best;
 }
 
-StagedShape staged_gen_shape(int64_t N) {
-    StagedShape sh = {0, 0, 0};
-    const int v = staged_gen_vec(N);
-    if (!v) return sh;
-    static const int rows_env = getenv("GESPMM_STAGED_GEN_ROWS") ? atoi(getenv("GESPMM_STAGED_GEN_ROWS")) : 0;
-    sh.waves = kGenWaves;
-    sh.slots = kGenWaves * kGenLdsKb * 1024 / (256 * v);
-    // rows per block: those of the tile width's tuned kernel (96 at 128-column tiles, 64 at 256: spmm_staged.hip, plan_policy.cpp
-    // staged_rows_for refines them by mean degree); 64-column tiles (odd widths) by the same rule "about as many rows as staged slots / 1.7"
-    sh.rows = rows_env > 0 ? rows_env : (v == 1 ? 192 : (v == 2 ? 96 : 64));
-    return sh;
-}
-
 bool staged_gen_serves(int64_t M, int64_t K, int64_t N) {
     if (N < 1 || N > (1 << 20)) return false;
     return (uint64_t)(M > K ? M : K) * (uint64_t)N * 4ull < 0xFFFF0000ull;
@@ -379,9 +365,11 @@ bool staged_gen_serves(int64_t M, int64_t K, int64_t N) {
 
 hipError_t launch_spmm_staged_gen(const StagedArgs& a_in, int64_t M, int64_t K, int64_t N, int reduce, float empty, hipStream_t st) {
     if (a_in.nblocks <= 0) return hipSuccess;
-    if (!staged_gen_serves(M, K, N) || a_in.waves != kGenWaves) return hipErrorInvalidValue;
+    if (!staged_gen_serves(M, K, N)) return hipErrorInvalidValue;
     const int v = staged_gen_vec(N);
-    if (a_in.slots != kGenWaves * kGenLdsKb * 1024 / (256 * v)) return hipErrorInvalidValue;  // tables of another tile width
+    const StagedShape shape = staged_block_shape(N);
+    static_assert(kGenWaves == kStagedMaxWaves && kGenLdsKb == kStagedLdsKb, "the kernel's block is the one staged_block_shape describes");
+    if (a_in.waves != shape.waves || a_in.slots != shape.slots) return hipErrorInvalidValue;  // tables of another block shape
     if ((reinterpret_cast<uintptr_t>(a_in.B) | reinterpret_cast<uintptr_t>(a_in.C)) & (uintptr_t)(4 * v - 1)) return hipErrorInvalidValue;
     StagedArgs a = a_in;
     a.n = (int32_t)N;

@@ -3,7 +3,7 @@
 // 7/8 of every instruction empty. Here a wavefront is G = 64 / W LANE GROUPS of W = N / 4 lanes (4 floats per lane), and every group walks
 // ITS OWN range of the plan's record stream (spmm_kernels.h: entries {code, value} + one row-end record {kStagedRowEnd, C row} per row):
 //
-//   * the block's most used B rows are staged in LDS exactly as in spmm_staged.hip (same tables, H = 64 KB / row bytes = 1024 / 512 / 256
+//   * the block's most used B rows are staged in LDS exactly as in spmm_staged.hip (same tables, H = 80 KB / row bytes = 1280 / 640 / 320
 //     slots), so three entries out of four of a clustered graph are one `ds_read_b128` per lane — and ONE LDS instruction serves G rows;
 //   * records live in VGPRs (every lane of a group loads its group's next 8 records itself: eight lanes, one cache line), so "staged or
 //     memory", "entry or row end" are per-lane predicates: the gather of a step is one LDS read for the lanes whose row is staged and one
@@ -19,7 +19,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -221,27 +220,6 @@ __global__ __launch_bounds__(WAVES * 64, 8) void spmm_staged_narrow_kernel(Stage
 // Widths this kernel serves (0 = not served) and the lanes per row.
 static int narrow_lanes(int64_t N) { return N == 16 ? 4 : (N == 32 ? 8 : (N == 64 ? 16 : 0)); }
 
-StagedShape staged_narrow_shape(int64_t N) {
-    static const int rows_env = getenv("GESPMM_STAGED_NARROW_ROWS") ? atoi(getenv("GESPMM_STAGED_NARROW_ROWS")) : 0;
-    StagedShape sh = {0, 0, 0};
-    const int W = narrow_lanes(N);
-    if (!W) return sh;
-    static const int waves_env = getenv("GESPMM_STAGED_NARROW_WAVES") ? atoi(getenv("GESPMM_STAGED_NARROW_WAVES")) : 0;
-    sh.waves = waves_env == 8 ? 8 : kStagedMaxWaves;
-    static const int lds_env = getenv("GESPMM_STAGED_LDS_KB") ? atoi(getenv("GESPMM_STAGED_LDS_KB")) : 0;
-    const int lkb = (sh.waves == kStagedMaxWaves && lds_env != 4) ? 5 : 4;  // (as for the wide kernel: spmm_staged.hip, staged_shape)
-    sh.slots = sh.waves * lkb * 1024 / (W * 16);
-    // as many rows per block as staged slots (N = 32: 384 / 512 / 640 / 768 / 1024 rows -> geometric 80.7 / 76.4 / 77.9 / 89.0 / 94.7 us,
-    // products-shaped 1214 / 1185 / 1157 / 1188 / 1269; N = 64: 192 / 256 / 384 / 512 -> 127.6 / 124.5 / 132.1 / 139.9 us: profiles/r05/narrow_shapes.log)
-    sh.rows = rows_env > 0 ? rows_env : sh.waves * 4096 / (W * 16);  // (512 / 256 rows at N = 32 / 64: what the sweep above found)
-    return sh;
-}
-
-int staged_narrow_groups(int64_t N) {
-    const int W = narrow_lanes(N);
-    return W ? 64 / W : 0;
-}
-
 bool staged_narrow_serves(int64_t M, int64_t K, int64_t N) {
     if (!narrow_lanes(N)) return false;
     return (uint64_t)(M > K ? M : K) * (uint64_t)N * 4ull < 0xFFFF0000ull;
@@ -249,33 +227,16 @@ bool staged_narrow_serves(int64_t M, int64_t K, int64_t N) {
 
 hipError_t launch_spmm_staged_narrow(const StagedArgs& a, int64_t M, int64_t K, int64_t N, hipStream_t st) {
     if (a.nblocks <= 0) return hipSuccess;
-    if (!staged_narrow_serves(M, K, N) || (a.waves != kStagedMaxWaves && a.waves != 8)) return hipErrorInvalidValue;
+    if (!staged_narrow_serves(M, K, N)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)a.nblocks), block((unsigned)a.waves * 64);
     const int W = narrow_lanes(N);
-    const int lkb = a.slots > 0 ? (int)((int64_t)a.slots * W * 16 / ((int64_t)a.waves * 1024)) : 4;  // what the tables were built for
-    if (a.waves == 8) {  // (experiments: half-size blocks, GESPMM_STAGED_NARROW_WAVES=8)
-        if (lkb != 4) return hipErrorInvalidValue;
-        if (W == 8) hipLaunchKernelGGL((spmm_staged_narrow_kernel<8, 8, 4>), grid, block, 0, st, a);
-        else if (W == 16) hipLaunchKernelGGL((spmm_staged_narrow_kernel<16, 8, 4>), grid, block, 0, st, a);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
-    }
-    if (lkb == 5) {
-        switch (W) {
-            case 4: hipLaunchKernelGGL((spmm_staged_narrow_kernel<4, kStagedMaxWaves, 5>), grid, block, 0, st, a); break;
-            case 8: hipLaunchKernelGGL((spmm_staged_narrow_kernel<8, kStagedMaxWaves, 5>), grid, block, 0, st, a); break;
-            case 16: hipLaunchKernelGGL((spmm_staged_narrow_kernel<16, kStagedMaxWaves, 5>), grid, block, 0, st, a); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else if (lkb == 4) {
-        switch (W) {
-            case 4: hipLaunchKernelGGL((spmm_staged_narrow_kernel<4, kStagedMaxWaves, 4>), grid, block, 0, st, a); break;
-            case 8: hipLaunchKernelGGL((spmm_staged_narrow_kernel<8, kStagedMaxWaves, 4>), grid, block, 0, st, a); break;
-            case 16: hipLaunchKernelGGL((spmm_staged_narrow_kernel<16, kStagedMaxWaves, 4>), grid, block, 0, st, a); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        return hipErrorInvalidValue;
+    const StagedShape shape = staged_block_shape(N);
+    if (a.waves != shape.waves || a.slots != shape.slots) return hipErrorInvalidValue;  // tables of another block shape
+    switch (W) {
+        case 4: hipLaunchKernelGGL((spmm_staged_narrow_kernel<4, kStagedMaxWaves, kStagedLdsKb>), grid, block, 0, st, a); break;
+        case 8: hipLaunchKernelGGL((spmm_staged_narrow_kernel<8, kStagedMaxWaves, kStagedLdsKb>), grid, block, 0, st, a); break;
+        case 16: hipLaunchKernelGGL((spmm_staged_narrow_kernel<16, kStagedMaxWaves, kStagedLdsKb>), grid, block, 0, st, a); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

@@ -4,7 +4,7 @@
     python scripts/kernel_ab.py --graphs geometric nws-k10 com-amazon-sbm --widths 128 --kernels stream staged [--auto]
 
 Graph names: the repository's stand-ins (gespmm_amd/graphs.py) or <name>.npz under $GESPMM_HOLDOUT_DIR (default profiles/r05/holdout;
-written by scripts/holdout_graphs.py). Bits are compared with the plain call. Env knobs of the library (GESPMM_STAGED_U ...) are read once per
+written by scripts/holdout_graphs.py). Bits are compared with the plain call. Env knobs of the library (GESPMM_STAGED_ROWS ...) are read once per
 process: run the script once per setting."""
 import argparse
 import os
