@@ -79,11 +79,11 @@ def proc(edge_index, n_v, device, add_self_loop=True):
 
 
 class Net(torch.nn.Module):
-    def __init__(self, n_in, n_hidden, n_out, convs, weighted, cached=True):
+    def __init__(self, n_in, n_hidden, n_out, convs, weighted, cached=True, fused=False):
         super().__init__()
         dims = [n_in] + [n_hidden] * (convs - 1) + [n_out]
         self.convs = torch.nn.ModuleList(
-            [GCNConv(dims[i], dims[i + 1], cached=cached, normalize=True) for i in range(convs)])
+            [GCNConv(dims[i], dims[i + 1], cached=cached, normalize=True, fused=fused) for i in range(convs)])
         self.weighted = weighted
         self.reg_params = self.convs[0].parameters()
         self.non_reg_params = [p for c in self.convs[1:] for p in c.parameters()]
@@ -109,6 +109,7 @@ def main():
     ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--no-plans", action="store_true", help="GCNConv(cached=False): every SpMM is a plain call (no analysis stage)")
+    ap.add_argument("--fused", action="store_true", help="GCNConv(fused=True): degree scalings and bias inside the SpMM (same output bits)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device (the op has no CPU path)")
@@ -129,7 +130,7 @@ def main():
         masks[name] = m.to(device)
 
     weighted = not args.no_edge_weight and args.convs == 2
-    model = Net(n_feat, args.n_hidden, n_cls, args.convs, weighted, cached=not args.no_plans).to(device)
+    model = Net(n_feat, args.n_hidden, n_cls, args.convs, weighted, cached=not args.no_plans, fused=args.fused).to(device)
     optimizer = torch.optim.Adam([dict(params=model.reg_params, weight_decay=5e-4),
                                   dict(params=model.non_reg_params, weight_decay=0)], lr=0.01,
                                  capturable=args.graph_capture)

@@ -84,6 +84,9 @@ EXPORTS = [
     "gespmm_auto_plan_get_stats",
     "gespmm_cluster_rows_study",
     "gespmm_plan_wants_warmup",
+    "gespmm_csr_spmm_fused_f32",
+    "gespmm_plan_spmm_fused_f32",
+    "gespmm_plan_fused_route",
 ]
 
 PLAN_REORDER_AUTO = 0
@@ -212,6 +215,12 @@ def _load():
     lib.gespmm_set_cached_memory_limit.argtypes = [c_int64]
     lib.gespmm_plan_spmm_f32.restype = c_int
     lib.gespmm_plan_spmm_f32.argtypes = [p, p, p, c_int64, p]
+    lib.gespmm_csr_spmm_fused_f32.restype = c_int
+    lib.gespmm_csr_spmm_fused_f32.argtypes = [p, p, p, p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_int, p]
+    lib.gespmm_plan_spmm_fused_f32.restype = c_int
+    lib.gespmm_plan_spmm_fused_f32.argtypes = [p, p, p, p, p, p, c_int64, p]
+    lib.gespmm_plan_fused_route.restype = c_int
+    lib.gespmm_plan_fused_route.argtypes = [p, c_int64, c_int, c_int, c_int]
     lib.gespmm_plan_spmm_max_f32.restype = c_int
     lib.gespmm_plan_spmm_max_f32.argtypes = [p, p, p, c_int64, c_float, p]
     lib.gespmm_plan_sddmm_f32.restype = c_int

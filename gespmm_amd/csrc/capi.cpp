@@ -17,6 +17,7 @@
 #include "auto_plan.h"
 #include "plan.h"
 #include "spmm_kernels.h"
+#include "workspace.h"
 
 namespace {
 
@@ -160,6 +161,72 @@ int run_spmm(const int32_t* rowptr, const int32_t* colind, const float* val, con
     return (int)e;
 }
 
+int check_fused_args(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const FusedVectors& fx, const float* C,
+                     int64_t M, int64_t K, int64_t N, int64_t nnz) {
+    const int rc = check_common(rowptr, colind, val, B, C, M, K, N, nnz);
+    if (rc != 0) return rc;
+    if (!aligned_to(fx.col_scale, 4) || !aligned_to(fx.row_scale, 4) || !aligned_to(fx.bias, 4)) return GESPMM_EALIGN;
+    return 0;
+}
+
+int refuse_allocation_under_capture(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return (int)hipErrorStreamCaptureUnsupported;
+    (void)hipGetLastError();
+    return 0;
+}
+
+// The fused counterpart of run_spmm: the same selection (a plan's task tables included), then ONE fused streaming kernel or nothing.
+int run_spmm_fused(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const FusedVectors& fx, float* C,
+                   int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, int flags, void* stream, const PlanLaunch* pl, bool dry_run,
+                   int* kind) {
+    *kind = 0;
+    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    if (M <= 0 || N <= 0) return kFusedUnavailable;
+    // Vector width: what B, C and the bias slice can be addressed with (the bits do not depend on it).
+    int max_vec = 4;
+    while (max_vec > 1 && ((N % max_vec) != 0 || (!dry_run && (!aligned_to(B, 4u * max_vec) || !aligned_to(C, 4u * max_vec) ||
+                                                               !aligned_to(fx.bias, 4u * max_vec)))))
+        max_vec >>= 1;
+    if (pl) {  // (as run_spmm: task tables exist for the two streaming kernels only)
+        flags |= kFlagNoSlabBlocked;
+        flags &= ~(kFlagSlabBlocked | kFlagSegStream | kFlagBatchStream);
+        flags |= (pl->prefer_segmented && pl->gtasks) ? kFlagSegStream : kFlagBatchStream;
+        flags &= ~kFlagAllowReassoc;
+    }
+    Selection sel;
+    if (resolve_geometry(M, K, N, nnz, variant, max_vec, 0, 0, 0, 0, 0, flags, &sel) != 0) return GESPMM_EINVAL;
+    sel.geo.reduce = kReduceSum;
+    if (sel.variant == GESPMM_VARIANT_NAIVE || sel.variant == GESPMM_VARIANT_PARREDUCE) return kFusedUnavailable;
+    bool seg = sel.geo.segmented;
+    if (flags & kFlagBatchStream) seg = false;
+    if ((flags & kFlagSegStream) && !sel.geo.split_long_rows) seg = true;
+    if (seg && pl && sel.geo.strips == 2 && sel.geo.vec < 4) seg = false;
+    if (!fused_geometry_served(sel.geo, seg, pl != nullptr)) return kFusedUnavailable;  // (long-row pass, cache blocking, 64-bit offsets too)
+    *kind = seg ? 2 : 1;
+    if (dry_run) return 0;
+
+    FusedSpmmArgs a = {};
+    a.rowptr = rowptr;
+    a.colind = colind;
+    a.val = val;
+    a.B = B;
+    a.C = C;
+    a.M = (int32_t)M;
+    a.N = (int32_t)N;
+    a.flags = flags;
+    a.rpw = seg ? sel.geo.rows_per_group : sel.geo.rows_per_wave;
+    a.tasks = pl ? pl->tasks : nullptr;
+    a.perm = pl ? pl->perm : nullptr;
+    a.ntasks = pl ? pl->ntasks : 0;
+    a.gtasks = pl ? pl->gtasks : nullptr;
+    a.ngtasks = pl ? pl->ngtasks : 0;
+    a.col_scale = fx.col_scale;
+    a.row_scale = fx.row_scale;
+    a.bias = fx.bias;
+    return (int)launch_spmm_fused(a, sel.geo, seg, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace gespmm
 
 namespace {
@@ -203,6 +270,42 @@ int gespmm_csr_spmm_f32(const int32_t* rowptr, const int32_t* colind, const floa
             return rc;
     }
     return run_spmm(rowptr, colind, val, B, C, M, K, N, nnz, variant, nullptr, gespmm::kReduceSum, 0.0f, stream);
+}
+
+// The fused product (gespmm.h): one fused streaming kernel where the unfused call would be one streaming kernel, else the
+// composition — prescale into a stream-ordered temporary, the unfused call, the in-place epilogue. Same bits either way.
+int gespmm_csr_spmm_fused_f32(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const float* col_scale,
+                              const float* row_scale, const float* bias, float* C, int64_t M, int64_t K, int64_t N, int64_t nnz,
+                              int variant, void* stream) {
+    const gespmm::FusedVectors fx = {col_scale, row_scale, bias};
+    const int rc0 = gespmm::check_fused_args(rowptr, colind, val, B, fx, C, M, K, N, nnz);
+    if (rc0 != 0) return rc0;
+    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    if (M == 0 || N == 0) return 0;
+    if (!fx.any()) return gespmm_csr_spmm_f32(rowptr, colind, val, B, C, M, K, N, nnz, variant, stream);
+    int kind = 0;
+    int rc = gespmm::run_spmm_fused(rowptr, colind, val, B, fx, C, M, K, N, nnz, variant, 0, stream, nullptr, false, &kind);
+    if (rc != gespmm::kFusedUnavailable) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    void* scratch = nullptr;
+    const float* Bin = B;
+    if (col_scale && K > 0 && nnz != 0) {
+        if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;
+        hipError_t e = gespmm::workspace_alloc(&scratch, (size_t)K * (size_t)N * 4, st);
+        if (e == hipSuccess) e = gespmm::launch_scale_rows(B, col_scale, static_cast<float*>(scratch), K, N, st);
+        if (e != hipSuccess) {
+            if (scratch) (void)gespmm::workspace_free(scratch, st);
+            return (int)e;
+        }
+        Bin = static_cast<const float*>(scratch);
+    }
+    rc = run_spmm(rowptr, colind, val, Bin, C, M, K, N, nnz, variant, nullptr, gespmm::kReduceSum, 0.0f, stream);
+    if (rc == 0) rc = (int)gespmm::launch_scale_bias_inplace(C, row_scale, bias, M, N, st);
+    if (scratch) {
+        const hipError_t e = gespmm::workspace_free(scratch, st);
+        if (rc == 0) rc = (int)e;
+    }
+    return rc;
 }
 
 int gespmm_csr_spmm_f32_cfg(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B,

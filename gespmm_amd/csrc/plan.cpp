@@ -109,6 +109,9 @@ struct gespmm_plan {
     int tuned_vec = 0;     // 1: the winner is the batch-stream kernel with 4 floats per lane (N <= 64)
     bool staging_kept_by_policy = false;  // keep_staged_tables() said yes at creation (else the tables exist only while tune measures them / if they won)
     double tune_us[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};  // batch-stream, segmented-stream, staged-rows, batch-stream with 4 floats per lane (N <= 64), padded records
+    // the fused product's composition route (gespmm_plan_spmm_fused_f32): K x N floats for col_scale . B, made by the first call that needs them
+    float* d_fused_scratch = nullptr;  // owner
+    int64_t fused_scratch_bytes = 0;
     bool records_kept_by_policy = false;  // want_record_tables() / keep_record_tables() said yes at creation (else the tables exist only while tune measures them / if they won)
 
     gespmm_plan() = default;
@@ -119,7 +122,7 @@ struct gespmm_plan {
         gespmm::free_staging(&slab);
         gespmm::free_slab_view(&slab_view, false);
         gespmm::free_records(&rec);
-        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp})
+        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp, (void*)d_fused_scratch})
             if (q) (void)hipFree(q);
     }
 };
@@ -900,6 +903,76 @@ int gespmm_plan_spmm_f32(gespmm_plan* plan, const float* B, float* C, int64_t N,
 
 int gespmm_plan_spmm_max_f32(gespmm_plan* plan, const float* B, float* C, int64_t N, float empty_value, void* stream) {
     return plan_run(plan, B, C, N, gespmm::kReduceMax, empty_value, stream);
+}
+
+// The fused product through a plan. Two executions with the same bits (plan_policy.cpp: fused_route chooses):
+//   * ONE fused streaming kernel — on the caller's arrays (storage order) or on the plan's stream task tables, which every clustered
+//     plan owns whatever its unfused route is (staged rows, records, slabs);
+//   * the composition: col_scale . B into the plan's scratch, the plan's unfused route unchanged (plan_run), the in-place epilogue.
+// `dry`: the answer only (gespmm_plan_fused_route) — operands count as 16-byte aligned, nothing is launched or allocated.
+static int plan_run_fused(gespmm_plan* p, const float* B, const gespmm::FusedVectors& fx, float* C, int64_t N, void* stream, bool dry,
+                          int* route_out) {
+    *route_out = 0;
+    const gespmm::RouteAnswer ra = route_of(p, N, gespmm::kReduceSum, dry ? true : aligned16(B, C));
+    const float* pval = p->valued ? (p->reordered ? p->d_val : p->val) : nullptr;
+    const gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, ra.segmented};
+    const int32_t* rp = p->reordered ? p->d_rowptr : p->rowptr;
+    const int32_t* ci = p->reordered ? p->d_colind : p->colind;
+    const int variant = (p->reordered && ra.vec4) ? GESPMM_VARIANT_CRC_CWM4 : p->variant;
+    int kind = 0;
+    int rc = gespmm::run_spmm_fused(rp, ci, pval, B, fx, C, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
+                                    p->reordered ? &pl : nullptr, true, &kind);
+    if (rc != 0 && rc != gespmm::kFusedUnavailable) return rc;
+    const int route = gespmm::fused_route(p->facts, ra, kind, N, fx.col_scale != nullptr, fx.row_scale != nullptr, fx.bias != nullptr);
+    *route_out = route;
+    if (dry) return 0;
+    if (route != 0)
+        return gespmm::run_spmm_fused(rp, ci, pval, B, fx, C, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
+                                      p->reordered ? &pl : nullptr, false, &kind);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const float* Bin = B;
+    if (fx.col_scale && p->nnz > 0 && p->K > 0) {
+        const int64_t need = p->K * N * 4;
+        if (p->fused_scratch_bytes < need) {
+            if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
+            if (p->d_fused_scratch) (void)hipFree(p->d_fused_scratch);  // (synchronises: no earlier launch still reads it)
+            p->d_fused_scratch = nullptr;
+            p->fused_scratch_bytes = 0;
+            const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_fused_scratch), (size_t)need);
+            if (e != hipSuccess) return (int)e;
+            p->fused_scratch_bytes = need;
+        }
+        const hipError_t e = gespmm::launch_scale_rows(B, fx.col_scale, p->d_fused_scratch, p->K, N, st);
+        if (e != hipSuccess) return (int)e;
+        Bin = p->d_fused_scratch;
+    }
+    rc = plan_run(p, Bin, C, N, gespmm::kReduceSum, 0.0f, stream);
+    if (rc == 0) rc = (int)gespmm::launch_scale_bias_inplace(C, fx.row_scale, fx.bias, p->M, N, st);
+    return rc;
+}
+
+int gespmm_plan_spmm_fused_f32(gespmm_plan* plan, const float* B, const float* col_scale, const float* row_scale, const float* bias,
+                               float* C, int64_t N, void* stream) {
+    if (!plan || N < 0) return GESPMM_EINVAL;
+    const gespmm::FusedVectors fx = {col_scale, row_scale, bias};
+    if (N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    if (plan->M > 0 && N > 0 && (!C || (plan->nnz != 0 && !B))) return GESPMM_EINVAL;
+    for (const void* q : {(const void*)B, (const void*)C, (const void*)col_scale, (const void*)row_scale, (const void*)bias})
+        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
+    if (plan->M == 0 || N == 0) return 0;
+    if (!fx.any()) return plan_run(plan, B, C, N, gespmm::kReduceSum, 0.0f, stream);
+    int route = 0;
+    return plan_run_fused(plan, B, fx, C, N, stream, false, &route);
+}
+
+int gespmm_plan_fused_route(const gespmm_plan* plan, int64_t N, int has_col_scale, int has_row_scale, int has_bias) {
+    if (!plan || N < 0) return GESPMM_EINVAL;
+    if (plan->M == 0 || N == 0 || !(has_col_scale || has_row_scale || has_bias)) return 0;
+    static const float present = 0.0f;  // (a dry run looks at which vectors are given, never at them)
+    const gespmm::FusedVectors fx = {has_col_scale ? &present : nullptr, has_row_scale ? &present : nullptr, has_bias ? &present : nullptr};
+    int route = 0;
+    const int rc = plan_run_fused(const_cast<gespmm_plan*>(plan), nullptr, fx, nullptr, N, nullptr, true, &route);
+    return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
 }
 
 // Which kernel, MEASURED: the candidates of a clustered plan — batch-stream, segmented-stream and (at the plan's width) staged-rows —

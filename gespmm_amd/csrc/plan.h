@@ -19,6 +19,27 @@ struct PlanLaunch {
 int run_spmm(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, float* C, int64_t M,
              int64_t K, int64_t N, int64_t nnz, int variant, const gespmm_launch_cfg* cfg, int reduce, float empty,
              void* stream, void* ws, int64_t ws_bytes, const PlanLaunch* pl, const LaunchGuard* guard = nullptr);
+// The fused product (gespmm_csr_spmm_fused_f32 / gespmm_plan_spmm_fused_f32) as ONE launch of a fused streaming kernel, where the unfused
+// launch of the same arguments would be one streaming kernel (no long-row pass, no cache blocking, 32-bit offsets, a geometry the fused
+// kernels are built for — spmm_fused.h). *kind: 1 batch-stream, 2 segmented-stream, 0 not available (kFusedUnavailable is returned and
+// nothing is launched: the caller composes the product from the unfused launch). dry_run: answer only — pointers are not looked at,
+// operands count as 16-byte aligned. `flags`: GESPMM_FLAG_* as in gespmm_launch_cfg.flags (a plan's launch_flags).
+struct FusedVectors {
+    const float* col_scale;
+    const float* row_scale;
+    const float* bias;
+    bool any() const { return col_scale || row_scale || bias; }
+};
+constexpr int kFusedUnavailable = -101;  // internal
+int run_spmm_fused(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const FusedVectors& fx, float* C,
+                   int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, int flags, void* stream, const PlanLaunch* pl, bool dry_run,
+                   int* kind);
+// argument checks of the fused entry points (no device work): sizes, NULLs, 4-byte alignment of every pointer
+int check_fused_args(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const FusedVectors& fx, const float* C,
+                     int64_t M, int64_t K, int64_t N, int64_t nnz);
+// hipErrorStreamCaptureUnsupported when `st` is capturing (a composition that would have to allocate launches nothing), else 0
+int refuse_allocation_under_capture(hipStream_t st);
+
 // A plan's product behind a launch guard (auto_plan.cpp): kNotGuardable — and nothing launched — when the plan's launch is more than
 // one kernel (hub rows handed to the long-row pass, the cache-blocked path).
 int plan_spmm_guarded(gespmm_plan* plan, const float* B, float* C, int64_t N, int reduce, float empty, void* stream, const LaunchGuard* guard);

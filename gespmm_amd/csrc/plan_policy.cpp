@@ -487,6 +487,31 @@ RouteAnswer plan_route(const PlanFacts& f, const RouteState& s, int64_t N, int r
     return a;
 }
 
+// The fused product: the fused streaming kernel or the composition around the plan's unfused route. Where the unfused route is a
+// streaming kernel anyway, the fused kernel is that kernel plus a few multiplies: taken whenever it exists. Where the unfused route is
+// one of the table kernels (staged rows, slabs, records), the fused kernel gives up that kernel's advantage over the streaming kernels
+// to save three passes over an M x N matrix. The passes cost the same per ROW whatever the matrix (3 x 2 x 4N bytes), the table
+// kernel's advantage grows with the ENTRIES of the row (~a third of 4N gathered bytes each): break-even near 16 entries per row.
+// Measured at N = 128, all three vectors, us (profiles/r07/fused/route_audit.log; unfused = three torch passes + the plan's product):
+//   com-amazon-sbm (mean degree 5.5, staged rows)   kernel 118.6   composition 227.3   unfused 278
+//   products-sbm   (mean degree 50, staged rows)    kernel 4285    composition 3469    unfused 3740
+//   reddit-sbm     (mean degree 492, column slabs)  kernel 3330    composition 2329    unfused 2386
+//   pubmed         (storage order, batch-stream)    kernel 20.0    composition 30.0    unfused 38.1
+// each far beyond the run-to-run spread (0.2-11 us). Hence: a table-kernel route with rows of 16+ entries on average keeps its kernel
+// and composes; everything else takes the fused kernel. (Nothing between 5.5 and 50 was measured: 16 is the estimate above.)
+// GESPMM_FUSED_ROUTE=composition|kernel pins the answer (scripts/fused_timing.py --route-audit runs both).
+int fused_route(const PlanFacts& f, const RouteAnswer& unfused, int fused_kind, int64_t N, bool has_col_scale, bool has_row_scale,
+                bool has_bias) {
+    (void)N;
+    static const char* const env = getenv("GESPMM_FUSED_ROUTE");
+    if (fused_kind == 0 || !(has_col_scale || has_row_scale || has_bias)) return 0;
+    if (env && !strcmp(env, "composition")) return 0;
+    if (env && !strcmp(env, "kernel")) return fused_kind;
+    const bool table_kernel = unfused.staged() || unfused.route == PlanRoute::StagedSlabs || unfused.route == PlanRoute::Records;
+    if (table_kernel && f.mean_ceil() >= 16) return 0;
+    return fused_kind;
+}
+
 // The clustered edge walk pays a scatter pass at the end: worth it where the order is modelled to hit L2 for >= 40 % of the
 // gathers and the rows are >= 256 bytes (com-Amazon-shaped communities, N = 128: 114 vs 151 us COO / 167 us CSR; on the
 // structureless graph or at N = 41 it is equal or slower — profiles/r02/sddmm_plan.log). Otherwise short rows take the COO

@@ -142,6 +142,12 @@ struct RouteAnswer {
 // f: the plan's facts (f.N = the width its tables are made for); N, reduce, aligned16: the launch (operands on 16-byte boundaries)
 RouteAnswer plan_route(const PlanFacts& f, const RouteState& s, int64_t N, int reduce, bool aligned16);
 
+// ---- the fused product through a plan (gespmm_plan_spmm_fused_f32): 0 = composition (prescale, the unfused route `unfused`, epilogue),
+//      else `fused_kind` (1 batch-stream, 2 segmented-stream: the ONE fused streaming kernel this launch could be; 0 = there is none).
+//      Consulted by the fused launch only; plan_route and every unfused route are not touched by it.
+int fused_route(const PlanFacts& f, const RouteAnswer& unfused, int fused_kind, int64_t N, bool has_col_scale, bool has_row_scale,
+                bool has_bias);
+
 // ---- SDDMM through the plan: 0 = CSR form on the caller's arrays, 1 = COO form on expanded row ids (storage order),
 //      2 = the plan's clustered edge order + scatter
 int sddmm_route(const PlanFacts& f, bool reordered, double hits_after, int64_t N_launch);

@@ -71,6 +71,17 @@ struct SpmmArgs {
     int32_t guard_want;
 };
 
+// The fused product (gespmm_csr_spmm_fused_f32): C = ((A (col_scale . B)) . row_scale) + bias, each a separate fp32 rounding. A type of
+// its own — not three more fields of SpmmArgs — so that the unfused kernels keep their argument block (and with it their
+// instruction streams): the streaming kernels of spmm_stream.h select the fused form by the TYPE of their argument.
+struct FusedSpmmArgs : SpmmArgs {
+    const float* col_scale;  // [K] or NULL (= 1)
+    const float* row_scale;  // [M] or NULL (= 1), indexed by the C row
+    const float* bias;       // [N] or NULL (no add)
+};
+template <class ARGS> struct is_fused_args { static constexpr bool value = false; };
+template <> struct is_fused_args<FusedSpmmArgs> { static constexpr bool value = true; };
+
 // A device word + the value a guarded launch runs for (run_spmm / the plan's launch: only paths that are ONE kernel take a guard).
 struct LaunchGuard {
     const int32_t* word;
@@ -102,6 +113,15 @@ hipError_t launch_spmm_segstream(const SpmmArgs& a, const Geometry& geo, hipStre
 // spmm_stream_plan.hip: the same two kernels on a plan's task table (a.tasks / a.gtasks + a.perm)
 hipError_t launch_spmm_stream_planned(const SpmmArgs& a, const Geometry& geo, hipStream_t st);
 hipError_t launch_spmm_segstream_planned(const SpmmArgs& a, const Geometry& geo, hipStream_t st);
+// spmm_fused.hip / spmm_fused_plan.hip: the fused forms of the two streaming kernels (sum reducer, 32-bit offsets, the geometries
+// select.cpp chooses: fused_geometry_served). `segmented`: the segmented-stream kernel. hipErrorInvalidValue where not served.
+bool fused_geometry_served(const Geometry& geo, bool segmented, bool planned);
+hipError_t launch_spmm_fused(const FusedSpmmArgs& a, const Geometry& geo, bool segmented, hipStream_t st);
+hipError_t launch_spmm_fused_planned(const FusedSpmmArgs& a, const Geometry& geo, bool segmented, hipStream_t st);
+// ... and the two elementwise passes of the composition route: Bs[k, :] = B[k, :] * col_scale[k];  C[r, :] = C[r, :] * row_scale[r] + bias
+// in place (either vector may be NULL), a separate multiply and add each.
+hipError_t launch_scale_rows(const float* B, const float* col_scale, float* Bs, int64_t K, int64_t N, hipStream_t st);
+hipError_t launch_scale_bias_inplace(float* C, const float* row_scale, const float* bias, int64_t M, int64_t N, hipStream_t st);
 // The two paths below need a temporary: the caller's (ext_ws, 16-byte aligned, >= *_workspace_bytes) or,
 // when that is absent or too small, a stream-ordered block from the library's pool (workspace.h).
 size_t longrows_workspace_bytes(int64_t nnz, int64_t N, int long_row);

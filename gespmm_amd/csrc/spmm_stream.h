@@ -34,13 +34,42 @@ namespace gespmm {
 // loop around the body cost the plain call 6-22 %: com-Amazon-shaped N = 128 150 -> 160 us, N = 32 48 -> 55 us, RMAT-22
 // N = 128 4.77 -> 5.83 ms; profiles/r02/plain_path_regression.log).
 
-template <int V, int S, int W, bool VALUED, bool IDX64, int RED, int U, bool PLANNED>
-__global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
+//
+// ARGS (spmm_kernels.h: FusedSpmmArgs; spmm_fused.hip, spmm_fused_plan.hip): the fused product C = ((A (col_scale . B)) . row_scale) + bias.
+// Selected by the TYPE of the kernel's argument, at compile time: with ARGS = SpmmArgs (the default) every `if constexpr (FUSED)`
+// below is discarded and the kernel is the unfused one instruction for instruction. The fused form
+//   * keeps a third array beside s_off / s_val in the CSR tile: the scale of each staged entry's column. col_scale[colind[p]] depends on
+//     the tile's colind load, so the tile stream is prefetched TWO deep: colind of tile t+2 is in flight while the values and the
+//     scales of tile t+1 (whose colind landed a tile ago) are — two more registers per lane, no exposed round trip per tile
+//     (GESPMM_FUSED_NAIVE_PROLOGUE builds the one-deep form, scale loaded when the tile is published: profiles/r07/fused/timing.log);
+//   * multiplies every gathered float by that scale (one rounding, then the unchanged fma / add chain);
+//   * at the row-end store multiplies by row_scale[C row] (loaded when the row starts) and adds the lane's slice of bias (loaded once).
+// Each of the three is a separate round-to-nearest operation (__fmul_rn / __fadd_rn): the bits of torch mul -> SpMM -> torch mul, add.
+// NULL col_scale / row_scale read as 1.0f (x * 1.0f keeps every bit pattern the chain can tell apart); NULL bias skips the add
+// (x + 0.0f would turn -0.0 into +0.0).
+
+template <bool FUSED>
+__device__ __forceinline__ float prescale(float b, float scale) {
+    if constexpr (FUSED) return __fmul_rn(b, scale);
+    else return b;
+}
+
+#ifdef GESPMM_FUSED_NAIVE_PROLOGUE
+constexpr bool kFusedDeepPrefetch = false;
+#else
+constexpr bool kFusedDeepPrefetch = true;
+#endif
+
+template <int V, int S, int W, bool VALUED, bool IDX64, int RED, int U, bool PLANNED, class ARGS = SpmmArgs>
+__global__ __launch_bounds__(kThreads) void spmm_stream_kernel(ARGS a) {
     constexpr int G = 64 / W;
+    constexpr bool FUSED = is_fused_args<ARGS>::value;
+    static_assert(!FUSED || RED == kReduceSum, "the fused product is a sum");
     using off_t = typename std::conditional<IDX64, uint64_t, uint32_t>::type;
 
     __shared__ off_t s_off[kWaves][kTile];
     __shared__ float s_val[VALUED ? kWaves : 1][VALUED ? kTile : 1];
+    __shared__ float s_scl[FUSED ? kWaves : 1][FUSED ? kTile : 1];  // fused: col_scale of each staged entry's column
     __shared__ int s_ptr[kWaves][kMaxRowsPerWave + 1];
     __shared__ int s_perm[PLANNED ? kWaves : 1][PLANNED ? kMaxRowsPerWave : 1];
 
@@ -72,10 +101,23 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
     const char* Bbase = reinterpret_cast<const char*>(a.B);
     const off_t rowbytes = (off_t)a.N * 4u;
     const float init = (RED == kReduceMax) ? a.empty : 0.0f;
+    float bias_r[S][V];  // fused: the lane's slice of bias
+    bool has_bias = false;
+    if constexpr (FUSED) {
+        has_bias = a.bias != nullptr;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) bias_r[s][i] = 0.0f;
+            if (has_bias && colok[s]) load_vec<V>(bias_r[s], reinterpret_cast<const char*>(a.bias + col0 + s * W * V));
+        }
+    }
 
     // Tile stream state: `t0` = CSR position of the tile resident in LDS.
     int pc = 0;
     float pv = 0.0f;
+    int pc2 = 0;      // fused: colind of the tile after the prefetched one
+    float ps = 1.0f;  // fused: col_scale[pc]
     auto fetch_tile_regs = [&](int base) {
         const int p = base + lane;
         if (p < we) {
@@ -86,6 +128,31 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
     auto publish_tile = [&]() {
         s_off[wave][lane] = (off_t)(uint32_t)pc * rowbytes;
         if constexpr (VALUED) s_val[wave][lane] = pv;
+        if constexpr (FUSED) {
+            if constexpr (!kFusedDeepPrefetch) ps = (a.col_scale != nullptr) ? a.col_scale[pc] : 1.0f;  // (exposed: waits here)
+            s_scl[wave][lane] = ps;
+        }
+    };
+    // fused, two-deep: `pc` holds the columns of the tile at `base` (loaded a tile ago) — its values and scales start now
+    auto fetch_tile_scaled = [&](int base) {
+        if constexpr (FUSED) {
+            const int p = base + lane;
+            if (p < we) {
+                if constexpr (VALUED) pv = load_csr(a.val + p);
+                ps = (a.col_scale != nullptr) ? a.col_scale[pc] : 1.0f;
+            }
+        }
+    };
+    auto fetch_tile_cols = [&](int base) {  // ... and the columns of the tile after it
+        const int p = base + lane;
+        if (p < we) pc2 = load_csr(a.colind + p);
+    };
+    // (the unfused kernel calls fetch_tile_regs itself, as it always did: routed through this lambda its register
+    //  initialisation came out in another order)
+    auto prefetch_next = [&](int t0_) {  // fused, after a publish: the registers move on by one tile
+        pc = pc2;
+        fetch_tile_scaled(t0_ + kTile);
+        fetch_tile_cols(t0_ + 2 * kTile);
     };
 
     if constexpr (PLANNED) {
@@ -111,7 +178,14 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
         wb = __builtin_amdgcn_readfirstlane(rp);
         we = __builtin_amdgcn_readlane(rp, nrows);
     }
-    fetch_tile_regs(wb);
+    if constexpr (FUSED && kFusedDeepPrefetch) {
+        fetch_tile_cols(wb);
+        pc = pc2;
+        fetch_tile_cols(wb + kTile);
+        fetch_tile_scaled(wb);  // (the one dependent load of the task that nothing hides)
+    } else {
+        fetch_tile_regs(wb);
+    }
     {
         int t0 = wb;
         if constexpr (PLANNED) {  // (after the tile loads are on their way: the three loads of a planned task overlap)
@@ -119,7 +193,8 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
             if (lane < kMaxRowsPerWave) s_perm[wave][lane] = pm_plan;
         }
         publish_tile();
-        fetch_tile_regs(t0 + kTile);
+        if constexpr (FUSED && kFusedDeepPrefetch) prefetch_next(t0);
+        else fetch_tile_regs(t0 + kTile);
         wave_lds_sync();
 
         for (int b = 0; b < nrows; b += G) {
@@ -156,6 +231,14 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
             for (int s = 0; s < S; ++s)
     #pragma unroll
                 for (int i = 0; i < V; ++i) acc[s][i] = init;
+            float rscale = 1.0f;  // fused: row_scale of this lane group's C row, on its way while the row is summed
+            if constexpr (FUSED) {
+                if (rowok2 && a.row_scale != nullptr) {
+                    int crow = row_first + r;
+                    if constexpr (PLANNED) crow = s_perm[wave][r];
+                    rscale = a.row_scale[crow];
+                }
+            }
 
             for (;;) {
                 const int tend = t0 + kTile;
@@ -165,12 +248,15 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
                 for (; k + U <= ke; k += U) {
                     off_t off[U];
                     float v[U];
+                    float sc[U];
                     float bv[U][S][V];
     #pragma unroll
                     for (int j = 0; j < U; ++j) {
                         off[j] = s_off[wave][k + j];
                         if constexpr (VALUED) v[j] = s_val[wave][k + j];
                         else v[j] = 1.0f;
+                        if constexpr (FUSED) sc[j] = s_scl[wave][k + j];
+                        else sc[j] = 1.0f;
                     }
     #pragma unroll
                     for (int j = 0; j < U; ++j)
@@ -181,7 +267,8 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
     #pragma unroll
                         for (int s = 0; s < S; ++s)
     #pragma unroll
-                            for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], bv[j][s][i]);
+                            for (int i = 0; i < V; ++i)
+                                acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
                 }
                 // Tail (1..U-1 entries): ONE predicated group, so a short row is a single round
                 // trip. It is not inside a loop, so there is no loop-carried register hazard and
@@ -190,6 +277,7 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
                 if (rem > 0) {
                     off_t off[U - 1];
                     float v[U - 1];
+                    float sc[U - 1];
                     float bv[U - 1][S][V];
                     // LDS reads first, all of them (clamped slot: always inside the tile), THEN the
                     // predicated gathers: with the read inside the predicate every gather waited for
@@ -200,6 +288,8 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
                         off[j] = s_off[wave][kj];
                         if constexpr (VALUED) v[j] = s_val[wave][kj];
                         else v[j] = 1.0f;
+                        if constexpr (FUSED) sc[j] = s_scl[wave][kj];
+                        else sc[j] = 1.0f;
                     }
     #pragma unroll
                     for (int j = 0; j < U - 1; ++j) {
@@ -215,7 +305,7 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
                             for (int s = 0; s < S; ++s)
     #pragma unroll
                                 for (int i = 0; i < V; ++i)
-                                    acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], bv[j][s][i]);
+                                    acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
                         }
                     }
                 }
@@ -223,7 +313,8 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
                 wave_lds_sync();        // all reads of the old tile are issued before it is overwritten
                 t0 = tend;
                 publish_tile();
-                fetch_tile_regs(t0 + kTile);
+                if constexpr (FUSED && kFusedDeepPrefetch) prefetch_next(t0);
+                else fetch_tile_regs(t0 + kTile);
                 wave_lds_sync();
             }
 
@@ -233,6 +324,15 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
                 float* Crow = a.C + (size_t)crow * (size_t)a.N + col0;
                 const bool nts = (a.flags & kFlagNtStore) != 0;
                 const bool sc1 = (a.flags & kFlagSc1Store) != 0;
+                if constexpr (FUSED) {
+    #pragma unroll
+                    for (int s = 0; s < S; ++s)
+    #pragma unroll
+                        for (int i = 0; i < V; ++i) {
+                            const float t = __fmul_rn(acc[s][i], rscale);
+                            acc[s][i] = has_bias ? __fadd_rn(t, bias_r[s][i]) : t;
+                        }
+                }
     #pragma unroll
                 for (int s = 0; s < S; ++s)
                     if (colok[s]) {
@@ -260,9 +360,15 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(SpmmArgs a) {
 // CRC staging is per group: the group's lanes load T = max(W, 32) entries per refill
 // (E = T/W consecutive entries per lane), next tile prefetched in registers.
 
-template <int V, int S, int W, bool VALUED, bool IDX64, int RED, int U, bool PLANNED>
-__global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
+//
+// ARGS = FusedSpmmArgs: the fused product, as in the batch-stream kernel above (per-group scale tile, two-deep prefetch, row_scale
+// of the current row loaded when the previous row is flushed).
+
+template <int V, int S, int W, bool VALUED, bool IDX64, int RED, int U, bool PLANNED, class ARGS = SpmmArgs>
+__global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(ARGS a) {
     constexpr int G = 64 / W;
+    constexpr bool FUSED = is_fused_args<ARGS>::value;
+    static_assert(!FUSED || RED == kReduceSum, "the fused product is a sum");
     constexpr int T = (W > 32) ? W : 32;  // entries per group tile
     constexpr int E = T / W;              // entries each lane stages per refill
     static_assert(T % U == 0, "tile must hold whole steps");
@@ -270,6 +376,7 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
 
     __shared__ off_t s_off[kWaves][G][T];
     __shared__ float s_val[VALUED ? kWaves : 1][VALUED ? G : 1][VALUED ? T : 1];
+    __shared__ float s_scl[FUSED ? kWaves : 1][FUSED ? G : 1][FUSED ? T : 1];  // fused: col_scale of each staged entry's column
     __shared__ int s_ptr[kWaves][G][kMaxRowsPerWave + 1];
     __shared__ int s_perm[PLANNED ? kWaves : 1][PLANNED ? G : 1][PLANNED ? kMaxRowsPerWave : 1];
 
@@ -328,14 +435,29 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
     const float init = (RED == kReduceMax) ? a.empty : 0.0f;
     const bool nts = (a.flags & kFlagNtStore) != 0;
     const bool sc1 = (a.flags & kFlagSc1Store) != 0;
+    float bias_r[S][V];  // fused: the lane's slice of bias
+    bool has_bias = false;
+    if constexpr (FUSED) {
+        has_bias = a.bias != nullptr;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) bias_r[s][i] = 0.0f;
+            if (has_bias && colok[s]) load_vec<V>(bias_r[s], reinterpret_cast<const char*>(a.bias + col0 + s * W * V));
+        }
+    }
 
     // Per-group tile stream.
     int pc[E];
     float pv[E];
+    int pc2[E];   // fused: colind of the tile after the prefetched one
+    float ps[E];  // fused: col_scale[pc]
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         pc[e] = 0;
         pv[e] = 0.0f;
+        pc2[e] = 0;
+        ps[e] = 1.0f;
     }
     auto fetch_tile_regs = [&](int base) {
 #pragma unroll
@@ -352,11 +474,48 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
         for (int e = 0; e < E; ++e) {
             s_off[wave][g][l * E + e] = (off_t)(uint32_t)pc[e] * rowbytes;
             if constexpr (VALUED) s_val[wave][g][l * E + e] = pv[e];
+            if constexpr (FUSED) {
+                if constexpr (!kFusedDeepPrefetch) ps[e] = (a.col_scale != nullptr) ? a.col_scale[pc[e]] : 1.0f;
+                s_scl[wave][g][l * E + e] = ps[e];
+            }
         }
+    };
+    auto fetch_tile_scaled = [&](int base) {  // fused, two-deep: values and scales of the tile whose columns are in pc
+        if constexpr (FUSED) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const int p = base + l * E + e;
+                if (p < ge) {
+                    if constexpr (VALUED) pv[e] = load_csr(a.val + p);
+                    ps[e] = (a.col_scale != nullptr) ? a.col_scale[pc[e]] : 1.0f;
+                }
+            }
+        }
+    };
+    auto fetch_tile_cols = [&](int base) {  // ... and the columns of the tile after it
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int p = base + l * E + e;
+            if (p < ge) pc2[e] = load_csr(a.colind + p);
+        }
+    };
+    auto prefetch_next = [&](int tbase_) {  // fused, after a publish: the registers move on by one tile
+#pragma unroll
+        for (int e = 0; e < E; ++e) pc[e] = pc2[e];
+        fetch_tile_scaled(tbase_ + T);
+        fetch_tile_cols(tbase_ + 2 * T);
     };
 
     int tbase = gb;  // CSR position of the group's resident tile
-    fetch_tile_regs(tbase);
+    if constexpr (FUSED && kFusedDeepPrefetch) {
+        fetch_tile_cols(tbase);
+#pragma unroll
+        for (int e = 0; e < E; ++e) pc[e] = pc2[e];
+        fetch_tile_cols(tbase + T);
+        fetch_tile_scaled(tbase);
+    } else {
+        fetch_tile_regs(tbase);
+    }
     if constexpr (PLANNED) {
         if (nrows > 0) {
             for (int i = l; i <= nrows; i += W) s_ptr[wave][g][i] = a.rowptr[task_first + i];
@@ -364,7 +523,8 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
         }
     }
     publish_tile();
-    fetch_tile_regs(tbase + T);
+    if constexpr (FUSED && kFusedDeepPrefetch) prefetch_next(tbase);
+    else fetch_tile_regs(tbase + T);
     wave_lds_sync();
 
     float acc[S][V];
@@ -374,10 +534,31 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
         for (int i = 0; i < V; ++i) acc[s][i] = init;
     int cur = 0;                                       // current row of the task
     int rend = (nrows > 0) ? s_ptr[wave][g][1] : 0;    // CSR end of the current row
+    float rscale = 1.0f;  // fused: row_scale of the current row's C row (loaded a row ahead of its use)
+    auto load_rscale = [&]() {
+        if constexpr (FUSED) {
+            rscale = 1.0f;
+            if (cur < nrows && a.row_scale != nullptr) {
+                int crow = task_first + cur;
+                if constexpr (PLANNED) crow = s_perm[wave][g][cur];
+                rscale = a.row_scale[crow];
+            }
+        }
+    };
+    load_rscale();
     auto flush_row = [&]() {
         int crow = task_first + cur;
         if constexpr (PLANNED) crow = s_perm[wave][g][cur];
         float* Crow = a.C + (size_t)crow * (size_t)a.N + col0;
+        if constexpr (FUSED) {
+#pragma unroll
+            for (int s = 0; s < S; ++s)
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const float t = __fmul_rn(acc[s][i], rscale);
+                    acc[s][i] = has_bias ? __fadd_rn(t, bias_r[s][i]) : t;
+                }
+        }
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (colok[s]) {
@@ -390,19 +571,22 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
         }
         ++cur;
         rend = s_ptr[wave][g][(cur + 1 <= nrows) ? cur + 1 : nrows];
+        load_rscale();
     };
 
     for (int k = gb; k < ge; k += U) {
         if (k >= tbase + T) {  // group-uniform: the step crosses into the next tile
             tbase += T;
             publish_tile();
-            fetch_tile_regs(tbase + T);
+            if constexpr (FUSED && kFusedDeepPrefetch) prefetch_next(tbase);
+            else fetch_tile_regs(tbase + T);
             wave_lds_sync();
         }
         const int cnt = ge - k;
         const int t = k - tbase;  // a multiple of U: tiles hold whole steps
         off_t off[U];
         float v[U];
+        float sc[U];
         float bv[U][S][V];
         if (cnt >= U) {
             // Full step: the U tile slots are read with constant offsets (no per-slot clamping: ~4 instead of ~9 VALU
@@ -412,6 +596,8 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
                 off[j] = s_off[wave][g][t + j];
                 if constexpr (VALUED) v[j] = s_val[wave][g][t + j];
                 else v[j] = 1.0f;
+                if constexpr (FUSED) sc[j] = s_scl[wave][g][t + j];
+                else sc[j] = 1.0f;
             }
 #pragma unroll
             for (int j = 0; j < U; ++j)
@@ -425,7 +611,7 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
 #pragma unroll
                     for (int s = 0; s < S; ++s)
 #pragma unroll
-                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], bv[j][s][i]);
+                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
             } else {
 #pragma unroll
                 for (int j = 0; j < U; ++j) {
@@ -433,7 +619,7 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
 #pragma unroll
                     for (int s = 0; s < S; ++s)
 #pragma unroll
-                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], bv[j][s][i]);
+                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
                 }
             }
         } else {
@@ -447,6 +633,8 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
                 off[j] = s_off[wave][g][tj];
                 if constexpr (VALUED) v[j] = s_val[wave][g][tj];
                 else v[j] = 1.0f;
+                if constexpr (FUSED) sc[j] = s_scl[wave][g][tj];
+                else sc[j] = 1.0f;
 #pragma unroll
                 for (int s = 0; s < S; ++s) load_vec<V>(bv[j][s], Bbase + (off_t)(off[j] + cbytes[s]));
             }
@@ -457,7 +645,7 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
 #pragma unroll
                     for (int s = 0; s < S; ++s)
 #pragma unroll
-                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], bv[j][s][i]);
+                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
                 }
             }
         }
@@ -469,10 +657,10 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(SpmmArgs a) {
 
 // ----------------------------------------------------------------------------- launch tables
 
-template <int V, int S, int W, bool VALUED, bool IDX64, int RED, bool PLANNED>
-static hipError_t launch_stream(const SpmmArgs& a, int rpw, hipStream_t st) {
+template <int V, int S, int W, bool VALUED, bool IDX64, int RED, bool PLANNED, class ARGS>
+static hipError_t launch_stream(const ARGS& a, int rpw, hipStream_t st) {
     constexpr int G = 64 / W;
-    SpmmArgs args = a;
+    ARGS args = a;
     if (rpw < G) rpw = G;
     if (rpw > kMaxRowsPerWave) rpw = kMaxRowsPerWave;
     rpw = rpw / G * G;
@@ -494,14 +682,14 @@ static hipError_t launch_stream(const SpmmArgs& a, int rpw, hipStream_t st) {
     // Gather depth U: 8 B-row loads in flight per lane group unless the accumulators are
     // already wide (CF = 8) or the caller asks for the shallow form.
     if constexpr (V * S >= 8) {
-        hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED>), dim3((unsigned)nitems),
+        hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                            dim3(kThreads), 0, st, args);
     } else {
         if (a.flags & kFlagShallowUnroll)
-            hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED>), dim3((unsigned)nitems),
+            hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                                dim3(kThreads), 0, st, args);
         else
-            hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 8, PLANNED>), dim3((unsigned)nitems),
+            hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 8, PLANNED, ARGS>), dim3((unsigned)nitems),
                                dim3(kThreads), 0, st, args);
     }
     return hipGetLastError();
@@ -547,10 +735,10 @@ static hipError_t launch_spmm_stream_impl(const SpmmArgs& a, const Geometry& geo
     return geo.idx64 ? stream_vs<false, true, kReduceSum, PLANNED>(a, geo, st) : stream_vs<false, false, kReduceSum, PLANNED>(a, geo, st);
 }
 
-template <int V, int S, int W, bool VALUED, bool IDX64, int RED, bool PLANNED>
-static hipError_t launch_segstream(const SpmmArgs& a, int rpg, hipStream_t st) {
+template <int V, int S, int W, bool VALUED, bool IDX64, int RED, bool PLANNED, class ARGS>
+static hipError_t launch_segstream(const ARGS& a, int rpg, hipStream_t st) {
     constexpr int G = 64 / W;
-    SpmmArgs args = a;
+    ARGS args = a;
     if (rpg < 1) rpg = 1;
     if (rpg > kMaxRowsPerWave) rpg = kMaxRowsPerWave;
     args.rpw = rpg;
@@ -561,14 +749,14 @@ static hipError_t launch_segstream(const SpmmArgs& a, int rpg, hipStream_t st) {
     if (nitems <= 0) return hipSuccess;
     if (nitems > kMaxGridBlocks) return hipErrorInvalidConfiguration;
     if constexpr (V * S >= 8) {
-        hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED>), dim3((unsigned)nitems),
+        hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                            dim3(kThreads), 0, st, args);
     } else {
         if (a.flags & kFlagShallowUnroll)
-            hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED>), dim3((unsigned)nitems),
+            hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                                dim3(kThreads), 0, st, args);
         else
-            hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 8, PLANNED>), dim3((unsigned)nitems),
+            hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 8, PLANNED, ARGS>), dim3((unsigned)nitems),
                                dim3(kThreads), 0, st, args);
     }
     return hipGetLastError();

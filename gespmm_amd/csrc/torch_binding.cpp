@@ -198,6 +198,39 @@ torch::Tensor plan_spmm(int64_t handle, const torch::Tensor& dense, const c10::o
     return out;
 }
 
+// ... and its fused form (gespmm_plan_spmm_fused_f32): the three optional vectors arrive checked and flattened (spmm.py: _fused_vectors)
+torch::Tensor plan_spmm_fused(int64_t handle, const torch::Tensor& dense, const c10::optional<torch::Tensor>& col_scale,
+                              const c10::optional<torch::Tensor>& row_scale, const c10::optional<torch::Tensor>& bias,
+                              const c10::optional<torch::Tensor>& out_opt, int64_t M) {
+    need(dense, "dense", torch::kFloat32, 2);
+    const int64_t N = dense.size(1);
+    auto vec = [&](const c10::optional<torch::Tensor>& t, const char* name) -> const float* {
+        if (!t.has_value() || !t->defined()) return nullptr;
+        need(*t, name, torch::kFloat32, 1);
+        same_device(dense, *t);
+        return t->data_ptr<float>();
+    };
+    const float* cs = vec(col_scale, "col_scale");
+    const float* rs = vec(row_scale, "row_scale");
+    const float* bs = vec(bias, "bias");
+    TORCH_CHECK_VALUE(!cs || col_scale->numel() == dense.size(0), "col_scale must have K entries");
+    TORCH_CHECK_VALUE(!rs || row_scale->numel() == M, "row_scale must have M entries");
+    TORCH_CHECK_VALUE(!bs || bias->numel() == N, "bias must have N entries");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dense.device());
+    torch::Tensor out;
+    if (out_opt.has_value()) {
+        out = *out_opt;
+        need(out, "out", torch::kFloat32, 2);
+        TORCH_CHECK_VALUE(out.size(0) == M && out.size(1) == N && out.device() == dense.device(), "out must be f32[M, N] on the same device");
+    } else {
+        out = torch::empty({M, N}, dense.options());
+    }
+    check_rc(gespmm_plan_spmm_fused_f32(reinterpret_cast<gespmm_plan*>(handle), dense.data_ptr<float>(), cs, rs, bs, out.data_ptr<float>(), N,
+                                        current_stream(dense)),
+             "gespmm_plan_spmm_fused_f32");
+    return out;
+}
+
 torch::Tensor plan_sddmm(int64_t handle, const torch::Tensor& D1, const torch::Tensor& D2, int64_t nnz) {
     need(D1, "D1", torch::kFloat32, 2);
     need(D2, "D2", torch::kFloat32, 2);
@@ -228,6 +261,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("coo_sddmm", &coo_sddmm, "COO SDDMM");
     m.def("csr_sddmm", &csr_sddmm, "CSR SDDMM");
     m.def("plan_spmm", &plan_spmm, "SpMM through a gespmm_plan handle", py::arg("handle"), py::arg("dense"),
+          py::arg("out") = py::none(), py::arg("M") = 0);
+    m.def("plan_spmm_fused", &plan_spmm_fused, "fused SpMM (column scale, row scale, bias) through a gespmm_plan handle", py::arg("handle"),
+          py::arg("dense"), py::arg("col_scale") = py::none(), py::arg("row_scale") = py::none(), py::arg("bias") = py::none(),
           py::arg("out") = py::none(), py::arg("M") = 0);
     m.def("plan_sddmm", &plan_sddmm, "SDDMM through a gespmm_plan handle");
 }

@@ -29,6 +29,9 @@ also keeps one SpmmPlan per direction (the analysis stage: sparse graphs are row
 task table, dense graphs keep the split points of the cache-blocked path; results keep their bits).
 ``GCNConv(..., cached=True, tune_plans=True)`` (extension, off by default) additionally lets each plan pick its kernel by MEASUREMENT on the
 first forward's operands (``SpmmPlan.tune``: a few extra launches once per direction; not under stream capture — run one eager step first).
+``GCNConv(..., fused=True)`` (extension, off by default) runs the two scalings and the bias INSIDE the product
+(``FusedGCNFunction`` on ``spmm.csr_spmm_fused``): three elementwise passes over an M x N matrix less in forward, two less in
+backward, and the same output bits. It works with ``cached=True`` (plans) and without.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -82,6 +85,50 @@ class SPMMFunction(torch.autograd.Function):
         return None, None, None, None, grad_feat, grad_edge_weight, None, None, None
 
 
+class FusedGCNFunction(torch.autograd.Function):
+    """out = ((A @ (out_scale * feat)) * in_scale) + bias as ONE product (``spmm.csr_spmm_fused``), and its backward
+    grad_feat = (A^T @ (in_scale * grad_out)) * out_scale as one product on the CSC arrays; grad_bias = grad_out.sum(0).
+
+        FusedGCNFunction.apply(rowptr, colind, colptr, rowind, feat, out_scale, in_scale, bias,
+                               edge_weight_csr=None, edge_weight_csc=None, plans=None)
+
+    ``out_scale`` ([K] or [K, 1]: scales the rows of ``feat``), ``in_scale`` ([M] or [M, 1]: scales the rows of the result) and ``bias``
+    ([N]) may each be None. The rules are SPMMFunction's: ``edge_weight_csc`` is required in backward when the product is weighted,
+    index tensors and the two scales get no gradient, edge weights are treated as constants. Forward and the gradient with respect
+    to ``feat`` have the bits of the unfused chain (mul, SPMMFunction, mul, add)."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, feat, out_scale, in_scale, bias, edge_weight_csr=None, edge_weight_csc=None,
+                plans=None):
+        fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
+        out = _spmm.csr_spmm_fused(rowptr, colind, edge_weight_csr, feat.contiguous(), col_scale=out_scale, row_scale=in_scale,
+                                   bias=bias, plan=fwd_plan)
+        ctx.backward_csc = (colptr, rowind, out_scale, in_scale, edge_weight_csr, edge_weight_csc)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        global _warned_no_grad
+        colptr, rowind, out_scale, in_scale, edge_weight_csr, edge_weight_csc = ctx.backward_csc
+        grad_out = grad_out.contiguous()
+        if edge_weight_csr is not None:
+            if edge_weight_csc is None:
+                raise RuntimeError(
+                    "Backward of SPMM require edge values in both src-first and dst-first order, "
+                    "and do not support gradients for edge values. Call with SPMMFunction.apply("
+                    "rowptr, colind, colptr, rowind, in_feat, edge_value_row_first, edge_value_col_first")
+            if not _warned_no_grad:
+                print("[I] Treat edge weight as no_grad.")
+                _warned_no_grad = True
+        grad_feat = None
+        if ctx.needs_input_grad[4]:
+            grad_feat = _spmm.csr_spmm_fused(colptr, rowind, edge_weight_csc, grad_out, col_scale=in_scale, row_scale=out_scale,
+                                             plan=ctx.bwd_plan)
+        grad_bias = grad_out.sum(0) if (ctx.has_bias and ctx.needs_input_grad[7]) else None
+        return None, None, None, None, grad_feat, None, None, grad_bias, None, None, None
+
+
 def glorot(tensor):
     """torch_geometric.nn.inits.glorot: U(-a, a), a = sqrt(6 / (fan_in + fan_out))."""
     if tensor is not None:
@@ -109,6 +156,7 @@ class GCNConv(torch.nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self.improved, self.cached, self.normalize = improved, cached, normalize
         self.tune_plans = bool(kwargs.pop("tune_plans", False))
+        self.fused = bool(kwargs.pop("fused", False))  # extension: scalings and bias inside the product (FusedGCNFunction)
         # extension: products each cached plan is expected to serve (0 = 200: the reference trains 200 epochs, gcn_custom.py:134, one
         # forward and one backward product per layer and epoch) — the plans weigh their analysis against it (SpmmPlan)
         self.expected_launches = int(kwargs.pop("expected_launches", 0))
@@ -148,7 +196,7 @@ class GCNConv(torch.nn.Module):
     def forward(self, x, rowptr, colind, colptr, rowind, edge_weight_csr=None, edge_weight_csc=None):
         h = x @ self.weight
         in_scale, out_scale = self._scalings(h, rowptr, colptr)
-        if self.normalize:
+        if self.normalize and not self.fused:
             h = h * out_scale
         plans = None
         if self.cached:  # `cached` is the caller's promise of a static graph: keep the SpMM scratch as well
@@ -168,11 +216,14 @@ class GCNConv(torch.nn.Module):
                         fwd, bwd = self.cached_plans[1]
                         if edge_weight_csr is not None:
                             fwd._sync_inputs(rowptr, colind, edge_weight_csr, h.detach(), fwd.shape[4])
-                        out0 = fwd.tune(h.detach().contiguous())
+                        out0 = fwd.tune((h.detach() * out_scale).contiguous() if (self.fused and self.normalize) else h.detach().contiguous())
                         if edge_weight_csc is not None:
                             bwd._sync_inputs(colptr, rowind, edge_weight_csc, out0, bwd.shape[4])
                         bwd.tune(out0)
             plans = self.cached_plans[1]
+        if self.fused:
+            return FusedGCNFunction.apply(rowptr, colind, colptr, rowind, h, out_scale if self.normalize else None,
+                                          in_scale if self.normalize else None, self.bias, edge_weight_csr, edge_weight_csc, plans)
         h = SPMMFunction.apply(rowptr, colind, colptr, rowind, h, edge_weight_csr, edge_weight_csc, False, plans)
         if self.normalize:
             h = h * in_scale

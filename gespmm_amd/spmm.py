@@ -207,6 +207,105 @@ class SpmmPlan:
         check(rc, "gespmm_plan_spmm_f32")
         return out
 
+    def run_fused(self, values, dense, col_scale, row_scale, bias, out=None, reduce_max=None):
+        """The fused product through the plan (gespmm_plan_spmm_fused_f32): ``((A @ (col_scale * dense)) * row_scale) + bias`` with the
+        bits of the four separate passes; each vector may be None. ``values`` is what ``run`` takes (the plan already holds them)."""
+        _need(dense, "dense", torch.float32, 2)
+        M, K, _, _, _ = self.shape
+        N = dense.shape[1]
+        col_scale, row_scale, bias = _fused_vectors(dense, M, col_scale, row_scale, bias)
+        if reduce_max is not None:
+            if col_scale is not None or row_scale is not None or bias is not None:
+                raise _lib.GespmmError(-1, "gespmm_plan_spmm_fused_f32 (the fused product supports the sum reducer only)")
+            return self.run(values, dense, out, reduce_max=reduce_max)
+        if _ext is not None and hasattr(_ext, "plan_spmm_fused"):
+            return _ext.plan_spmm_fused(self._handle.value, dense, col_scale, row_scale, bias, out, M)
+        if out is None:
+            out = torch.empty((M, N), dtype=torch.float32, device=self.device)
+        with _on_device(self.device):
+            rc = lib.gespmm_plan_spmm_fused_f32(self._handle, _ptr(dense), _optr(col_scale), _optr(row_scale), _optr(bias), _ptr(out), N,
+                                                _stream(self.device))
+        check(rc, "gespmm_plan_spmm_fused_f32")
+        return out
+
+    def fused_route(self, N=None, col_scale=True, row_scale=True, bias=True):
+        """What ``run_fused`` does at width N (default: the plan's) with these vectors present (gespmm_plan_fused_route, host only):
+        0 the composition around the unfused launch, 1 the fused batch-stream kernel, 2 the fused segmented-stream kernel."""
+        rc = lib.gespmm_plan_fused_route(self._handle, int(self.shape[2] if N is None else N), int(bool(col_scale)), int(bool(row_scale)),
+                                         int(bool(bias)))
+        if rc < 0:
+            check(rc, "gespmm_plan_fused_route")
+        return rc
+
+
+def _optr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _fused_vectors(dense, M, col_scale, row_scale, bias):
+    """The three optional vectors of the fused product as contiguous 1-D tensors: scales are accepted as [n] or [n, 1] (GCNConv keeps
+    them as columns), bias as [N]."""
+    K, N = dense.shape
+
+    def one(t, name, n, column_ok):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor or None" % name)
+        if column_ok and t.dim() == 2 and t.shape[1] == 1:
+            t = t.reshape(-1)
+        _need(t, name, torch.float32, 1)
+        if t.numel() != n:
+            raise ValueError("%s must have %d entries, got %d" % (name, n, t.numel()))
+        if t.device != dense.device:
+            raise RuntimeError("all tensors must live on the same device")
+        return t
+
+    return one(col_scale, "col_scale", K, True), one(row_scale, "row_scale", M, True), one(bias, "bias", N, False)
+
+
+def csr_spmm_fused(rowptr, colind, values, dense, col_scale=None, row_scale=None, bias=None, out=None, plan=None,
+                   variant=_lib.VARIANT_AUTO, reduce_max=None):
+    """``C = ((A @ (col_scale[:, None] * dense)) * row_scale[:, None]) + bias`` in ONE product (gespmm_csr_spmm_fused_f32 /
+    gespmm_plan_spmm_fused_f32) — the normalisation of a graph convolution without its three elementwise passes. ``values`` None: A == 1.
+    Every vector is optional; the result has the bits of torch ``mul``, ``csr_spmm``, ``mul``, ``add`` as separate steps (with no
+    vector at all the call IS the plain product). Sum reducer only: ``reduce_max`` together with a vector raises GESPMM_EINVAL."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    _need(dense, "dense", torch.float32, 2)
+    if values is not None:
+        _need(values, "values", torch.float32, 1)
+        if values.numel() != colind.numel():
+            raise ValueError("values and colind must have the same length")
+        dev = _same_device(dense, rowptr, colind, values)
+    else:
+        dev = _same_device(dense, rowptr, colind)
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have M+1 >= 1 entries")
+    M = rowptr.numel() - 1
+    K, N = dense.shape
+    if out is not None:
+        _need(out, "out", torch.float32, 2)
+        if tuple(out.shape) != (M, N) or out.device != dev:
+            raise ValueError("out must be f32[M, N] on the same device")
+    if plan is not None:
+        plan._sync_inputs(rowptr, colind, values, dense, variant)
+        return plan.run_fused(values, dense, col_scale, row_scale, bias, out, reduce_max=reduce_max)
+    col_scale, row_scale, bias = _fused_vectors(dense, M, col_scale, row_scale, bias)
+    if reduce_max is not None:
+        if col_scale is not None or row_scale is not None or bias is not None:
+            raise _lib.GespmmError(-1, "gespmm_csr_spmm_fused_f32 (the fused product supports the sum reducer only)")
+        if values is not None:
+            raise _lib.GespmmError(-1, "gespmm_csr_spmm_max_f32 (the max reducer is unweighted)")
+        return csr_spmm_max(rowptr, colind, dense, float(reduce_max), variant)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib.gespmm_csr_spmm_fused_f32(_ptr(rowptr), _ptr(colind), _optr(values), _ptr(dense), _optr(col_scale), _optr(row_scale),
+                                           _optr(bias), _ptr(out), M, K, N, colind.numel(), int(variant), _stream(dev))
+    check(rc, "gespmm_csr_spmm_fused_f32")
+    return out
+
 
 def _spmm(rowptr, colind, values, dense, variant, cfg, out, plan=None):
     _need(rowptr, "rowptr", torch.int32, 1)

@@ -59,7 +59,7 @@ extern "C" {
 #endif
 
 #define GESPMM_VERSION_MAJOR 0
-#define GESPMM_VERSION_MINOR 3
+#define GESPMM_VERSION_MINOR 4
 
 /* Negative return codes (positive values are hipError_t). */
 #define GESPMM_EINVAL   (-1)  /* bad argument (null pointer, negative size, unknown variant) */
@@ -334,6 +334,38 @@ int gespmm_plan_create_v2(gespmm_plan** plan, const int32_t* rowptr, const int32
                           int64_t opt_bytes /* sizeof(gespmm_plan_options) in the caller */, void* stream);
 /* C[M x N] = A * B through the plan; any N is legal (scratch and task size are tuned for the plan's N). */
 int gespmm_plan_spmm_f32(gespmm_plan* plan, const float* B, float* C, int64_t N, void* stream);
+/*
+ * The fused product (since 0.4): C = D_r (A (D_c B)) + 1 bias^T with three optional DEVICE vectors col_scale[K], row_scale[M],
+ * bias[N] — the normalisation a graph convolution wraps around its SpMM (pytorch-custom/op.py:141-147), without the three
+ * elementwise passes over an M x N matrix:
+ *
+ *     b'(k,c)  = fl32( B[k,c] * col_scale[k] )                 (col_scale == NULL: b' = B)
+ *     acc(r,c) = fma(val[p], b'(colind[p],c), acc) over the row's entries in CSR order, acc0 = 0   (val == NULL: acc + b')
+ *     t(r,c)   = fl32( acc(r,c) * row_scale[r] )               (row_scale == NULL: t = acc)
+ *     C[r,c]   = fl32( t(r,c) + bias[c] )                      (bias == NULL: C = t)
+ *
+ * Every fl32 is one round-to-nearest operation: the multiply and the add are never contracted and a scale is never folded into
+ * `val`. That is the arithmetic of `mul`, gespmm_csr_spmm_f32, `mul`, `add` as separate passes, so the result has THE SAME BITS as
+ * that composition — rows without entries (0 * row_scale + bias) and infinite scales (0 * inf = NaN) included. With all three
+ * vectors NULL the calls are gespmm_csr_spmm_f32 / gespmm_plan_spmm_f32. Sum reducer only.
+ *
+ * Two executions, same bits: ONE fused streaming kernel where the unfused launch would be one streaming kernel (batch-stream or
+ * segmented-stream, on the caller's arrays or on a clustered plan's task tables; 32-bit offsets, no long-row pass, no cache
+ * blocking), else the composition — col_scale . B into a temporary, the unfused launch unchanged, an in-place epilogue. The
+ * stateless call takes the K x N temporary stream-ordered from the library's pool; a plan owns it (allocated by the first fused
+ * call that needs it, freed with the plan). On a capturing stream a composition that would have to allocate returns
+ * hipErrorStreamCaptureUnsupported and launches nothing; a plan whose temporary exists captures fine.
+ * Conventions as everywhere in this header: device pointers, asynchronous on `stream`, GESPMM_EINVAL / GESPMM_EALIGN checked
+ * before any device work.
+ */
+int gespmm_csr_spmm_fused_f32(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B,
+                              const float* col_scale, const float* row_scale, const float* bias, float* C,
+                              int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, void* stream);
+int gespmm_plan_spmm_fused_f32(gespmm_plan* plan, const float* B, const float* col_scale, const float* row_scale,
+                               const float* bias, float* C, int64_t N, void* stream);
+/* host only: what the call above would do at width N with these vectors present (operands on 16-byte boundaries).
+   0 composition, 1 fused batch-stream, 2 fused segmented-stream */
+int gespmm_plan_fused_route(const gespmm_plan* plan, int64_t N, int has_col_scale, int has_row_scale, int has_bias);
 /*
  * Kernel choice by MEASUREMENT instead of by rule: runs the candidates of a clustered plan (batch-stream, segmented-stream,
  * staged-rows where the width is served, and at N <= 64 the batch-stream kernel with 4 floats per lane) `reps` (0 = 3) times each on these operands, synchronously, and fixes the plan
