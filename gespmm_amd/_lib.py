@@ -87,6 +87,8 @@ EXPORTS = [
     "gespmm_csr_spmm_fused_f32",
     "gespmm_plan_spmm_fused_f32",
     "gespmm_plan_fused_route",
+    "gespmm_describe_sddmm",
+    "gespmm_plan_sddmm_route",
 ]
 
 PLAN_REORDER_AUTO = 0
@@ -225,6 +227,10 @@ def _load():
     lib.gespmm_plan_spmm_max_f32.argtypes = [p, p, p, c_int64, c_float, p]
     lib.gespmm_plan_sddmm_f32.restype = c_int
     lib.gespmm_plan_sddmm_f32.argtypes = [p, p, p, p, c_int64, p]
+    lib.gespmm_plan_sddmm_route.restype = c_int
+    lib.gespmm_plan_sddmm_route.argtypes = [p, c_int64]
+    lib.gespmm_describe_sddmm.restype = c_int
+    lib.gespmm_describe_sddmm.argtypes = [c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_plan_set_values.restype = c_int
     lib.gespmm_plan_set_values.argtypes = [p, p, p]
     lib.gespmm_plan_get_order.restype = c_int
@@ -281,6 +287,17 @@ def plan_policy(M, K, nnz, N, max_degree, hits_before=0.0, hits_after=0.0, stage
     a = PlanPolicyAnswer()
     check(lib.gespmm_plan_policy_v2(ctypes.byref(q), ctypes.sizeof(q), ctypes.byref(a), ctypes.sizeof(a)), "gespmm_plan_policy_v2")
     return {n: getattr(a, n) for n, _ in PlanPolicyAnswer._fields_ if not n.startswith("reserved")}
+
+
+def describe_sddmm(csr, M, nnz, N, d1_align=16, d2_align=16, capturing=False):
+    """What gespmm_sddmm_{coo,csr}_f32 would launch for these arguments (gespmm_describe_sddmm: host only) — a dict with
+    "form" ("coo-edge", "csr-edge", "row-walk", "blocked" or "none") and the integers the form has: V, W, epw / nslab, slab_rows."""
+    buf = ctypes.create_string_buffer(128)
+    n = lib.gespmm_describe_sddmm(1 if csr else 0, int(M), int(nnz), int(N), int(d1_align), int(d2_align), 1 if capturing else 0, buf, 128)
+    if n < 0:
+        raise GespmmError(n, "gespmm_describe_sddmm")
+    out = dict(kv.split("=") for kv in buf.value.decode().split())
+    return {k: (v if k == "form" else int(v)) for k, v in out.items()}
 
 
 def init(rows_hint=0, nnz_hint=0, stream=None):

@@ -463,27 +463,51 @@ int gespmm_dgl_csrmm_max_f32(int m, int n, const int32_t* indptr, const int32_t*
 int gespmm_sddmm_coo_f32(const int32_t* rowind, const int32_t* colind, const float* D1, const float* D2, float* out,
                          int64_t nnz, int64_t N, void* stream) {
     if (nnz < 0 || N < 0) return GESPMM_EINVAL;
-    if (nnz > 0x7fffffffLL || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    if (nnz > gespmm::kSddmmMaxNnz || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
     if (nnz == 0) return 0;
     if (!rowind || !colind || !out || (N > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
     if (!aligned_to(rowind, 4) || !aligned_to(colind, 4) || !aligned_to(D1, 4) || !aligned_to(D2, 4) ||
         !aligned_to(out, 4))
         return GESPMM_EALIGN;
-    return (int)gespmm::launch_sddmm(rowind, false, colind, D1, D2, out, 0, nnz, N, 0,
+    return (int)gespmm::launch_sddmm(rowind, false, colind, D1, D2, out, 0, nnz, N,
                                      reinterpret_cast<hipStream_t>(stream));
 }
 
 int gespmm_sddmm_csr_f32(const int32_t* rowptr, const int32_t* colind, const float* D1, const float* D2, float* out,
                          int64_t M, int64_t nnz, int64_t N, void* stream) {
     if (M < 0 || nnz < 0 || N < 0) return GESPMM_EINVAL;
-    if (M > 0x7fffffffLL - 1 || nnz > 0x7fffffffLL || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    if (M > 0x7fffffffLL - 1 || nnz > gespmm::kSddmmMaxNnz || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
     if (nnz == 0) return 0;
     if (!rowptr || !colind || !out || (N > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
     if (!aligned_to(rowptr, 4) || !aligned_to(colind, 4) || !aligned_to(D1, 4) || !aligned_to(D2, 4) ||
         !aligned_to(out, 4))
         return GESPMM_EALIGN;
-    return (int)gespmm::launch_sddmm(rowptr, true, colind, D1, D2, out, M, nnz, N, 0,
+    return (int)gespmm::launch_sddmm(rowptr, true, colind, D1, D2, out, M, nnz, N,
                                      reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing, char* out,
+                          int64_t capacity) {
+    if (!out || capacity <= 0 || M < 0 || nnz < 0 || N < 0) return GESPMM_EINVAL;
+    if (d1_align < 4 || d2_align < 4 || (d1_align & (d1_align - 1)) != 0 || (d2_align & (d2_align - 1)) != 0) return GESPMM_EINVAL;
+    if (M > 0x7fffffffLL - 1 || nnz > gespmm::kSddmmMaxNnz || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    int n;
+    if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else {
+        const gespmm::SddmmLaunch r = gespmm::resolve_sddmm(csr != 0, M, nnz, N, d1_align > 16 ? 16 : d1_align,
+                                                           d2_align > 16 ? 16 : d2_align, capturing != 0);
+        if (r.form == gespmm::kSddmmBlocked)
+            n = snprintf(out, (size_t)capacity, "form=blocked V=%d W=%d nslab=%lld slab_rows=%lld", r.V, r.W, (long long)r.nslab,
+                         (long long)r.slab_rows);
+        else if (r.form == gespmm::kSddmmRowWalk)
+            n = snprintf(out, (size_t)capacity, "form=row-walk V=%d W=%d", r.V, r.W);
+        else
+            n = snprintf(out, (size_t)capacity, "form=%s V=%d W=%d epw=%d", r.form == gespmm::kSddmmCsrEdge ? "csr-edge" : "coo-edge",
+                         r.V, r.W, r.epw);
+    }
+    if (n < 0) return GESPMM_EINVAL;
+    return n < capacity ? n : (int)capacity - 1;
 }
 
 int gespmm_baseline_atomic_scatter_f32(const int32_t* rowptr, const int32_t* colind, const float* in, float* out,

@@ -1087,9 +1087,14 @@ int gespmm_plan_tune(gespmm_plan* p, const float* B, float* C, int64_t N, int32_
 // are then found in L2, as in the SpMM — and scatters the results back; each dot product is the same lane butterfly as in
 // gespmm_sddmm_{coo,csr}_f32, so the bits are the same.
 int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, float* out, int64_t N, void* stream) {
+    // the checks of gespmm_sddmm_{coo,csr}_f32, in their order (routes 1 and 2 launch without passing through them)
     if (!p || N < 0) return GESPMM_EINVAL;
+    if (N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    if (p->nnz > gespmm::kSddmmMaxNnz) return GESPMM_ERANGE;
     if (p->nnz == 0) return 0;
     if (!out || (N > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
+    for (const void* q : {(const void*)D1, (const void*)D2, (const void*)out})
+        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // which form: sddmm_route (plan_policy.cpp) — 0 CSR call, 1 COO on row ids expanded ONCE (same lane butterfly per edge, same
     // bits), 2 the plan's clustered edge order + scatter
@@ -1110,7 +1115,7 @@ int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, floa
                 }
                 p->d_coo_row_storage = rows;
             }
-            return (int)gespmm::launch_sddmm(p->d_coo_row_storage, false, p->colind, D1, D2, out, p->M, p->nnz, N, 0, st);
+            return (int)gespmm::launch_sddmm(p->d_coo_row_storage, false, p->colind, D1, D2, out, p->M, p->nnz, N, st);
         }
         return gespmm_sddmm_csr_f32(p->rowptr, p->colind, D1, D2, out, p->M, p->nnz, N, stream);
     }
@@ -1137,11 +1142,16 @@ int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, floa
         p->d_edge_dst = dst;
         p->d_sddmm_tmp = tmp;
     }
-    e = gespmm::launch_sddmm(p->d_coo_row, false, p->d_colind, D1, D2, p->d_sddmm_tmp, p->M, p->nnz, N, 0, st);
+    e = gespmm::launch_sddmm(p->d_coo_row, false, p->d_colind, D1, D2, p->d_sddmm_tmp, p->M, p->nnz, N, st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(scatter_by_index_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->d_sddmm_tmp,
                        p->d_edge_dst, out, (int)p->nnz);
     return (int)hipGetLastError();
+}
+
+int gespmm_plan_sddmm_route(const gespmm_plan* p, int64_t N) {
+    if (!p || N < 0) return GESPMM_EINVAL;
+    return gespmm::sddmm_route(p->facts, p->reordered, p->hits_after, N);
 }
 
 int gespmm_plan_set_values(gespmm_plan* p, const float* val, void* stream) {

@@ -14,12 +14,15 @@
 // coalesce. In CSR form, long rows (mean degree >= 64) are walked a row per wavefront with the D1
 // slice in registers (sddmm_slab_kernel), one launch per ~6 MB column slab of D2 when the pattern
 // is dense enough for cache blocking, one launch otherwise. Summation order is not sequential (neither is the
-// reference's shuffle tree): parity for SDDMM is tolerance-based; COO, CSR and the
-// cache-blocked form agree with each other bit for bit.
+// reference's shuffle tree) but it is FIXED by (V, W) alone: lane l of the W runs one fmaf chain over the elements
+// j = l*V + i + t*W*V (t ascending, i < V ascending), then log2(W) xor-butterfly adds (masks W/2 .. 1), lane 0 stores.
+// All three branches on N and all four launch forms keep that order, so COO, CSR, row-walking and the cache-blocked
+// form agree bit for bit, and the test suite compares them with a host restatement of the formula.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "select.h"
 #include "spmm_kernels.h"
 #include "workspace.h"
 
@@ -312,11 +315,6 @@ __global__ __launch_bounds__(kThreads) void sddmm_slab_kernel(const int32_t* __r
     }
 }
 
-// Row-walking (one wavefront per row) is skew-sensitive — a hub row is walked by one wavefront — and only pays
-// for long rows: parity with the edge-parallel form at degree 32-48, up to 2x at degree >= 64 on patterns too
-// small to block (profiles/r01/sddmm_heuristic_audit.log).
-constexpr int64_t kSddmmRowWalkMinDegree = 64;
-
 template <int V>
 static hipError_t sddmm_slab_w(int W, const int32_t* rb, const int32_t* re, const int32_t* colind, const float* D1,
                                const float* D2, float* out, int M, int N, hipStream_t st) {
@@ -340,19 +338,13 @@ static hipError_t sddmm_slab_w(int W, const int32_t* rb, const int32_t* re, cons
 
 template <int V, bool CSR>
 static hipError_t sddmm_w(int W, const int32_t* rows, const int32_t* colind, const float* D1, const float* D2,
-                          float* out, int M, int nnz, int N, hipStream_t st) {
+                          float* out, int M, int nnz, int N, int per_wave, hipStream_t st) {
+    const int nblk = (int)(((int64_t)nnz + kWaves * per_wave - 1) / (kWaves * per_wave));
 #define GESPMM_SD(WW)                                                                                         \
-    case WW: {                                                                                                 \
-        constexpr int G = 64 / WW;                                                                             \
-        /* edges per wavefront: COO G * UE (UE = 4); CSR 256 — one row search per 256 edges — unless that leaves \
-           the chip short of wavefronts (small patterns: pubmed-sized N = 128 ran 18.4 us against COO's 9.8) */   \
-        int per_wave = G * 4;                                                                                  \
-        if (CSR) per_wave = (nnz >= 256 * 16384) ? 256 : (nnz >= 64 * 16384) ? 64 : (G * 4 > 16 ? G * 4 : 16); \
-        const int nblk = (int)(((int64_t)nnz + kWaves * per_wave - 1) / (kWaves * per_wave));                  \
+    case WW:                                                                                                   \
         hipLaunchKernelGGL((sddmm_kernel<V, WW, CSR>), dim3(nblk), dim3(kThreads), 0, st, rows, colind, D1, D2, \
                            out, M, nnz, N, per_wave);                                                          \
-        return hipGetLastError();                                                                              \
-    }
+        return hipGetLastError();
     switch (W) {
         GESPMM_SD(4)
         GESPMM_SD(8)
@@ -364,70 +356,53 @@ static hipError_t sddmm_w(int W, const int32_t* rows, const int32_t* colind, con
     return hipErrorInvalidValue;
 }
 
+static int address_alignment(const void* p) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    return (a % 16 == 0) ? 16 : (a % 8 == 0) ? 8 : 4;
+}
+
+// Which form, vector width, lanes per edge and edges per wavefront: resolve_sddmm (select.cpp) — the one place that decides,
+// also behind gespmm_describe_sddmm. This function only asks whether the stream is capturing and launches what it answers.
 hipError_t launch_sddmm(const int32_t* rows, bool csr, const int32_t* colind, const float* D1, const float* D2,
-                        float* out, int64_t M, int64_t nnz, int64_t N, int flags, hipStream_t st) {
+                        float* out, int64_t M, int64_t nnz, int64_t N, hipStream_t st) {
     if (nnz == 0) return hipSuccess;
-    int V = 4;
-    while (V > 1 && ((N % V) != 0 || (reinterpret_cast<uintptr_t>(D1) % (4u * V)) != 0 ||
-                     (reinterpret_cast<uintptr_t>(D2) % (4u * V)) != 0))
-        V >>= 1;
-    // Lanes per edge: a lane walks ~2 dwordx4 vectors (8 scalars when the rows allow no vector loads)
-    // of both rows, so a wavefront has 64/W edges in flight and the butterfly is log2(W) steps.
-    // Measured against "just enough lanes to cover N" (profiles/r01/sddmm_group_width.log):
-    // N=41 2.4-2.8x, N=64 1.35x, N=128 1.2x faster on reddit-like, equal or better on com-Amazon-like.
-    // Both forms use the same width, so COO and CSR results agree bit for bit.
-    const int64_t per_lane = (V == 4) ? 2 : (V == 2) ? 4 : 8;
-    int W = 4;
-    while (W < 64 && (int64_t)W * V * per_lane < N) W <<= 1;
-    const int m = (int)M, z = (int)nnz, n = (int)N;
-    if (csr && M > 0 && (flags & kSddmmNoSlab) == 0) {
-        // Dense pattern (mean degree >= 64, >= 4.5 KB gathered per row and slab): cache-blocked form, ~6 MB
-        // slabs of D2. The number of D2 rows is not part of the call: the pattern is taken as square for
-        // the slab count (columns past M land in the last slab — fewer hits, same result). Needs a
-        // stream-ordered temporary for the split points, so not on a stream under capture.
-        const int64_t avg_deg = nnz / M;
-        int64_t slab_rows = (6 << 20) / (N * 4 > 0 ? N * 4 : 4);  // 3..6 MB measured best (sddmm_slab.log)
-        if (slab_rows < 64) slab_rows = 64;
-        const int64_t nslab = (M + slab_rows - 1) / slab_rows;
+    bool capturing = false;
+    if (csr && M > 0) {  // (only the cache-blocked CSR form allocates)
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-        // (the edges of a row that fall into one slab must still gather >= ~4.5 KB of D2: with less the per-row
-        // overhead of 'nslab' launches outweighs the L2 hits —
-        // profiles/r01/sddmm_heuristic_audit.log; M = 10^6, degree 100, 41 slabs was 4.5x slower than streaming)
-        if (!capturing && N * 4 >= 256 && nslab >= 4 && nslab <= 4096 && avg_deg >= 64 &&
-            avg_deg * N * 4 >= 4608 * nslab) {
-            int32_t* split = nullptr;
-            hipError_t e = workspace_alloc(reinterpret_cast<void**>(&split), (size_t)(nslab + 1) * (size_t)M * 4, st);
-            if (e != hipSuccess) return e;
-            e = launch_slabplan(rows, colind, split, m, (int)nslab, (int)slab_rows, st);
-            for (int64_t sl = 0; sl < nslab && e == hipSuccess; ++sl) {
-                const int32_t* rb = split + (size_t)sl * M;
-                const int32_t* re = split + (size_t)(sl + 1) * M;
-                if (V == 4) e = sddmm_slab_w<4>(W, rb, re, colind, D1, D2, out, m, n, st);
-                else if (V == 2) e = sddmm_slab_w<2>(W, rb, re, colind, D1, D2, out, m, n, st);
-                else e = sddmm_slab_w<1>(W, rb, re, colind, D1, D2, out, m, n, st);
-            }
-            const hipError_t ef = workspace_free(split, st);
-            return e != hipSuccess ? e : ef;
-        }
+        capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
         (void)hipGetLastError();
-        // Long rows but not worth blocking: the same row-walking kernel over the whole row ([rowptr[r], rowptr[r+1])
-        // is "one slab") — D1 slice in registers, four edges in flight, no per-edge row search. The edge-parallel
-        // form below stays for short rows, where a row per wavefront would leave lanes idle.
-        if (avg_deg >= kSddmmRowWalkMinDegree) {
-            if (V == 4) return sddmm_slab_w<4>(W, rows, rows + 1, colind, D1, D2, out, m, n, st);
-            if (V == 2) return sddmm_slab_w<2>(W, rows, rows + 1, colind, D1, D2, out, m, n, st);
-            return sddmm_slab_w<1>(W, rows, rows + 1, colind, D1, D2, out, m, n, st);
+    }
+    const SddmmLaunch r = resolve_sddmm(csr, M, nnz, N, address_alignment(D1), address_alignment(D2), capturing);
+    const int V = r.V, W = r.W;
+    const int m = (int)M, z = (int)nnz, n = (int)N;
+    if (r.form == kSddmmBlocked) {
+        int32_t* split = nullptr;
+        hipError_t e = workspace_alloc(reinterpret_cast<void**>(&split), (size_t)(r.nslab + 1) * (size_t)M * 4, st);
+        if (e != hipSuccess) return e;
+        e = launch_slabplan(rows, colind, split, m, (int)r.nslab, (int)r.slab_rows, st);
+        for (int64_t sl = 0; sl < r.nslab && e == hipSuccess; ++sl) {
+            const int32_t* rb = split + (size_t)sl * M;
+            const int32_t* re = split + (size_t)(sl + 1) * M;
+            if (V == 4) e = sddmm_slab_w<4>(W, rb, re, colind, D1, D2, out, m, n, st);
+            else if (V == 2) e = sddmm_slab_w<2>(W, rb, re, colind, D1, D2, out, m, n, st);
+            else e = sddmm_slab_w<1>(W, rb, re, colind, D1, D2, out, m, n, st);
         }
+        const hipError_t ef = workspace_free(split, st);
+        return e != hipSuccess ? e : ef;
     }
-    if (csr) {
-        if (V == 4) return sddmm_w<4, true>(W, rows, colind, D1, D2, out, m, z, n, st);
-        if (V == 2) return sddmm_w<2, true>(W, rows, colind, D1, D2, out, m, z, n, st);
-        return sddmm_w<1, true>(W, rows, colind, D1, D2, out, m, z, n, st);
+    if (r.form == kSddmmRowWalk) {
+        if (V == 4) return sddmm_slab_w<4>(W, rows, rows + 1, colind, D1, D2, out, m, n, st);
+        if (V == 2) return sddmm_slab_w<2>(W, rows, rows + 1, colind, D1, D2, out, m, n, st);
+        return sddmm_slab_w<1>(W, rows, rows + 1, colind, D1, D2, out, m, n, st);
     }
-    if (V == 4) return sddmm_w<4, false>(W, rows, colind, D1, D2, out, m, z, n, st);
-    if (V == 2) return sddmm_w<2, false>(W, rows, colind, D1, D2, out, m, z, n, st);
-    return sddmm_w<1, false>(W, rows, colind, D1, D2, out, m, z, n, st);
+    if (r.form == kSddmmCsrEdge) {
+        if (V == 4) return sddmm_w<4, true>(W, rows, colind, D1, D2, out, m, z, n, r.epw, st);
+        if (V == 2) return sddmm_w<2, true>(W, rows, colind, D1, D2, out, m, z, n, r.epw, st);
+        return sddmm_w<1, true>(W, rows, colind, D1, D2, out, m, z, n, r.epw, st);
+    }
+    if (V == 4) return sddmm_w<4, false>(W, rows, colind, D1, D2, out, m, z, n, r.epw, st);
+    if (V == 2) return sddmm_w<2, false>(W, rows, colind, D1, D2, out, m, z, n, r.epw, st);
+    return sddmm_w<1, false>(W, rows, colind, D1, D2, out, m, z, n, r.epw, st);
 }
 
 }  // namespace gespmm

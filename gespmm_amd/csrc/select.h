@@ -21,4 +21,21 @@ int resolve_geometry(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, 
                      int cfg_vec, int cfg_strips, int cfg_group, int cfg_rows_per_wave, int cfg_slab_rows, int flags,
                      Selection* out);
 
+// ---- SDDMM: which of its four launch forms a call takes (launch_sddmm runs exactly this; gespmm_describe_sddmm prints it).
+enum SddmmForm {
+    kSddmmCooEdge = 0,  // edge-parallel kernel on the caller's row ids
+    kSddmmCsrEdge = 1,  // edge-parallel kernel, rows found through an LDS window of row pointers (epw edges per wavefront)
+    kSddmmRowWalk = 2,  // a row per wavefront over the whole row (mean degree >= 64)
+    kSddmmBlocked = 3,  // the row-walking kernel once per ~6 MB column slab of D2 (allocates: never while capturing)
+};
+struct SddmmLaunch {
+    int form;           // SddmmForm
+    int V, W;           // floats per load, lanes per edge: these two fix the summation order
+    int epw;            // edges per wavefront of the edge-parallel forms (0 for the row-walking ones)
+    int64_t nslab;      // blocked form: launches; else 0
+    int64_t slab_rows;  // blocked form: D2 rows per slab; else 0
+};
+// d1_align / d2_align: largest power of two (bytes) that divides the operand's address, 16 is as good as more.
+SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, bool capturing);
+
 }  // namespace gespmm

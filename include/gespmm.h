@@ -59,7 +59,7 @@ extern "C" {
 #endif
 
 #define GESPMM_VERSION_MAJOR 0
-#define GESPMM_VERSION_MINOR 4
+#define GESPMM_VERSION_MINOR 5
 
 /* Negative return codes (positive values are hipError_t). */
 #define GESPMM_EINVAL   (-1)  /* bad argument (null pointer, negative size, unknown variant) */
@@ -227,7 +227,13 @@ int gespmm_dgl_csrmm_max_f32(int m, int n, const int32_t* indptr, const int32_t*
 /*
  * SDDMM: out[e] = sum_j D1[row(e), j] * D2[col(e), j], e in pattern order.
  * COO: row(e) = rowind[e].  CSR: row(e) = the row whose [rowptr[r], rowptr[r+1]) holds e.
- * D1 is M x N, D2 is K x N, row-major; out has nnz floats.
+ * D1 is M x N, D2 is K x N, row-major; out has nnz floats (N == 0: zeros).
+ * nnz <= 2^31 - 1 - 4096 (GESPMM_ERANGE beyond: the kernels count edges in 32 bits, a wavefront's span past the end included).
+ * Summation order: W lanes share an edge, each loads V floats at a time. Lane l runs ONE fmaf chain, from 0, over the elements
+ * j = l*V + t*W*V + i (t ascending; i = 0..V-1 ascending; j < N); then for m = W/2, W/4, .. 1 every lane adds the partial sum
+ * of lane l ^ m to its own; lane 0's sum is out[e]. V is the widest of 4, 2, 1 that divides N and whose 4*V bytes divide both
+ * operand addresses; W the smallest power of two in 4..64 with W * V * (2, 4, 8 for V = 4, 2, 1) >= N (64 beyond). The order
+ * depends on nothing else — not on the form (COO, CSR, a plan), the pattern, or the launch the library picks.
  */
 int gespmm_sddmm_coo_f32(const int32_t* rowind, const int32_t* colind,
                          const float* D1, const float* D2, float* out,
@@ -235,6 +241,17 @@ int gespmm_sddmm_coo_f32(const int32_t* rowind, const int32_t* colind,
 int gespmm_sddmm_csr_f32(const int32_t* rowptr, const int32_t* colind,
                          const float* D1, const float* D2, float* out,
                          int64_t M, int64_t nnz, int64_t N, void* stream);
+
+/*
+ * What an SDDMM call with these arguments would launch, as one line of text (since 0.5; host-only, no device work), in the
+ * manner of gespmm_describe_launch: "form=coo-edge V=4 W=32 epw=8", "form=csr-edge V=1 W=64 epw=256" (epw: edges per
+ * wavefront), "form=row-walk V=4 W=32" (a row per wavefront, mean degree >= 64), "form=blocked V=1 W=64 nslab=5
+ * slab_rows=3066" (the row walk once per ~6 MB column slab of D2; allocates, so never with capturing != 0), "form=none"
+ * (nnz == 0). csr: 0 = gespmm_sddmm_coo_f32 (M is ignored), else gespmm_sddmm_csr_f32. d1_align / d2_align: a power of
+ * two >= 4 that divides the operand's address (16 = as good as it gets). Returns the length written or a negative code.
+ */
+int gespmm_describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing,
+                          char* out, int64_t capacity);
 
 /*
  * CSR (M x K) -> CSC on the device: fills colptr[K+1], rowind[nnz] and, when
@@ -380,6 +397,9 @@ int gespmm_plan_spmm_max_f32(gespmm_plan* plan, const float* B, float* C, int64_
  * plan whose order is modelled to hit L2 walks the edges in its own order (shared rows of D2 come from L2) and scatters the
  * results back; otherwise the call is gespmm_sddmm_csr_f32 on the arrays the plan was made from (keep them alive). */
 int gespmm_plan_sddmm_f32(gespmm_plan* plan, const float* D1, const float* D2, float* out, int64_t N, void* stream);
+/* host only (since 0.5): which way the call above goes at width N. 0 gespmm_sddmm_csr_f32 on the caller's arrays, 1 the COO form on row
+ * ids the plan expands once, 2 the plan's clustered edge order + a scatter into the caller's order. */
+int gespmm_plan_sddmm_route(const gespmm_plan* plan, int64_t N);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */

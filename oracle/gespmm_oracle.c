@@ -382,6 +382,38 @@ void oracle_sddmm(int is_csr, int M, int nnz, int N, const int* rows, const int*
     }
 }
 
+/*
+ * The summation order of this project's SDDMM kernels, pinned (include/gespmm.h states it): W lanes share an edge, a lane
+ * loads V consecutive floats at a time.
+ *   lane l < W:  acc = 0;  for j = l*V; j < N; j += W*V:  for i < V with j + i < N:  acc = fmaf(x[j+i], y[j+i], acc)
+ *   then for m = W/2, W/4, .. 1:  every lane at once  part[l] += part[l ^ m]
+ *   out[e] = part[0]
+ * Written from that formula. fmaf is the C library's correctly rounded fused multiply-add; -ffp-contract=off and the absence
+ * of -ffast-math (oracle/Makefile) keep the compiler from fusing or reassociating anything else, as for oracle_spmm_fma.
+ * rows[e] / colind[e] are the row of D1 / D2 (COO form; callers expand a CSR rowptr themselves). V in {1,2,4}, W a power
+ * of two <= 64.
+ */
+void oracle_sddmm_lanes(int V, int W, int nnz, int N, const int* rows, const int* colind, const float* D1, const float* D2,
+                        float* out) {
+#pragma omp parallel for schedule(static) /* edges are independent: the threads change nothing about any edge's order */
+    for (int e = 0; e < nnz; e++) {
+        const float* x = D1 + (size_t)rows[e] * (size_t)N;
+        const float* y = D2 + (size_t)colind[e] * (size_t)N;
+        float part[64], next[64];
+        for (int l = 0; l < W; l++) {
+            float acc = 0.0f;
+            for (int j = l * V; j < N; j += W * V)
+                for (int i = 0; i < V && j + i < N; i++) acc = fmaf(x[j + i], y[j + i], acc);
+            part[l] = acc;
+        }
+        for (int m = W / 2; m >= 1; m /= 2) {
+            for (int l = 0; l < W; l++) next[l] = part[l] + part[l ^ m];
+            for (int l = 0; l < W; l++) part[l] = next[l];
+        }
+        out[e] = part[0];
+    }
+}
+
 /* ------------------------------------------------------------------ CSR -> CSC */
 
 /* What cusparseCsr2cscEx2 (spmm_kernel.cu:381-423) is asked to produce: the CSC

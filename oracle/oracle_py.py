@@ -39,6 +39,8 @@ def _load():
     lib.oracle_free.argtypes = [c_void_p]
     lib.oracle_sddmm.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p]
+    lib.oracle_sddmm_lanes.argtypes = [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.oracle_sddmm_lanes.restype = None
     lib.oracle_csr2csc.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.oracle_num_threads.restype = c_int
     return lib
@@ -170,6 +172,20 @@ def sddmm(rows, colind, D1, D2, csr=False):
     scale = np.empty(max(nnz, 1), dtype=np.float64)
     lib.oracle_sddmm(1 if csr else 0, M, nnz, N, _p(rows), _p(colind), _p(D1), _p(D2), _p(out), _p(scale))
     return out[:nnz], scale[:nnz]
+
+
+def sddmm_lanes(V, W, rows, colind, D1, D2):
+    """The SDDMM kernels' summation order at (V, W) — W lane-strided fmaf chains, then an xor butterfly — on the host, to be
+    compared bit for bit. rows / colind: row of D1 / D2 per edge (COO form)."""
+    if V not in (1, 2, 4) or W not in (1, 2, 4, 8, 16, 32, 64):
+        raise ValueError("V in {1, 2, 4}, W a power of two <= 64")
+    rows, colind, D1, D2 = _i32(rows), _i32(colind), _f32(D1), _f32(D2)
+    nnz, N = colind.shape[0], D1.shape[1]
+    if rows.shape[0] != nnz or D2.shape[1] != N:
+        raise ValueError("rows / colind and D1 / D2 must match")
+    out = np.empty(max(nnz, 1), dtype=np.float32)
+    lib.oracle_sddmm_lanes(int(V), int(W), nnz, N, _p(rows), _p(colind), _p(D1), _p(D2), _p(out))
+    return out[:nnz]
 
 
 def csr2csc(M, K, rowptr, colind, val=None):

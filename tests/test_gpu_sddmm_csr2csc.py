@@ -87,9 +87,11 @@ def test_csr2csc_round_trip_and_backward_operand(pkg, oracle, bundled):
 
 
 def test_sddmm_cache_blocked_form_matches_streaming_forms(pkg, oracle):
-    """Dense patterns (mean degree >= 64, D2 several slabs large) take the cache-blocked CSR kernel:
-    one launch per column slab. Same per-edge arithmetic, so CSR == COO bit for bit, sorted or not."""
-    from gespmm_amd import sddmm
+    """Dense patterns (mean degree >= 64) take the row-walking CSR kernel, and where D2 is at least four ~6 MB slabs large the
+    cache-blocked form of it: one launch per column slab. Same per-edge arithmetic, so CSR == COO bit for bit, sorted or not.
+    With 30 000 rows only N = 256 has four slabs (6144 rows each); 128, 100 and 65 have 3, 2 and 2 and walk whole rows — which
+    form ran is asserted per N (every blocked V and W: tests/test_gpu_sddmm_forms.py::test_cache_blocked_form)."""
+    from gespmm_amd import _lib, sddmm
 
     rng = np.random.RandomState(3)
     M = 30000
@@ -107,6 +109,11 @@ def test_sddmm_cache_blocked_form_matches_streaming_forms(pkg, oracle):
     for N in (128, 100, 65, 256):
         D1 = torch.rand(M, N, device="cuda") - 0.5
         D2 = torch.rand(M, N, device="cuda") - 0.5
+        assert D1.data_ptr() % 16 == 0 and D2.data_ptr() % 16 == 0
+        form = _lib.describe_sddmm(True, M, nnz, N)
+        want = {128: {"form": "row-walk", "V": 4, "W": 16}, 100: {"form": "row-walk", "V": 4, "W": 16},
+                65: {"form": "row-walk", "V": 1, "W": 16}, 256: {"form": "blocked", "V": 4, "W": 32, "nslab": 5, "slab_rows": 6144}}[N]
+        assert form == want, (N, form)
         o_csr = sddmm.csr_sddmm(rp, ci, D1, D2)
         o_coo = sddmm.coo_sddmm(ri, ci, D1, D2)
         assert torch.equal(o_csr, o_coo), N
