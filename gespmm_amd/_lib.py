@@ -89,7 +89,14 @@ EXPORTS = [
     "gespmm_plan_fused_route",
     "gespmm_describe_sddmm",
     "gespmm_plan_sddmm_route",
+    "gespmm_csr_spmm_x16",
+    "gespmm_plan_spmm_x16",
+    "gespmm_x16_route",
+    "gespmm_plan_x16_route",
 ]
+
+X16_F16 = 1
+X16_BF16 = 2
 
 PLAN_REORDER_AUTO = 0
 PLAN_REORDER = 1
@@ -221,6 +228,14 @@ def _load():
     lib.gespmm_csr_spmm_fused_f32.argtypes = [p, p, p, p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_int, p]
     lib.gespmm_plan_spmm_fused_f32.restype = c_int
     lib.gespmm_plan_spmm_fused_f32.argtypes = [p, p, p, p, p, p, c_int64, p]
+    lib.gespmm_csr_spmm_x16.restype = c_int
+    lib.gespmm_csr_spmm_x16.argtypes = [p, p, p, p, p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, p]
+    lib.gespmm_plan_spmm_x16.restype = c_int
+    lib.gespmm_plan_spmm_x16.argtypes = [p, p, p, c_int, c_int64, p]
+    lib.gespmm_x16_route.restype = c_int
+    lib.gespmm_x16_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int]
+    lib.gespmm_plan_x16_route.restype = c_int
+    lib.gespmm_plan_x16_route.argtypes = [p, c_int64, c_int, c_int]
     lib.gespmm_plan_fused_route.restype = c_int
     lib.gespmm_plan_fused_route.argtypes = [p, c_int64, c_int, c_int, c_int]
     lib.gespmm_plan_spmm_max_f32.restype = c_int

@@ -227,6 +227,84 @@ int run_spmm_fused(const int32_t* rowptr, const int32_t* colind, const float* va
     return (int)launch_spmm_fused(a, sel.geo, seg, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- 16-bit dense operands (gespmm.h: gespmm_csr_spmm_x16). The argument checks of both entry points, no device work.
+int check_x16_args(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, const void* C, int dtype, int64_t M,
+                   int64_t K, int64_t N, int64_t nnz) {
+    if (dtype != GESPMM_X16_F16 && dtype != GESPMM_X16_BF16) return GESPMM_EINVAL;
+    if (M < 0 || K < 0 || N < 0 || nnz < -1) return GESPMM_EINVAL;
+    if (M > 0x7fffffffLL - 64 || K > 0x7fffffffLL || N > 0x7fffffffLL / 4 || nnz > 0x7fffffffLL - 4096) return GESPMM_ERANGE;
+    if (M == 0 || N == 0) return 0;
+    if (!rowptr || !C) return GESPMM_EINVAL;
+    if ((nnz != 0) && (!colind || !B)) return GESPMM_EINVAL;
+    if (!aligned_to(rowptr, 4) || !aligned_to(colind, 4) || !aligned_to(val, 4) || !aligned_to(B, 2) || !aligned_to(C, 2)) return GESPMM_EALIGN;
+    return 0;
+}
+
+int pointer_alignment(const void* p) {  // largest power of two (<= 16) that divides the address
+    int a = 16;
+    while (a > 1 && reinterpret_cast<uintptr_t>(p) % (uintptr_t)a != 0) a >>= 1;
+    return a;
+}
+
+// The 16-bit counterpart of run_spmm_fused: ONE 16-bit streaming kernel or nothing (kX16Unavailable: the caller composes widen, the fp32
+// route, narrow). The kernels work in 32-bit words, so the geometry is the one the selector resolves for the byte-equivalent fp32 width
+// N / 2 — every rule of select.cpp is about bytes and lanes per row — with V limited by what B and C can be addressed with, in words.
+// b_align / c_align: powers of two dividing the operands' addresses (>= 16 is as good as 16); dry_run: the answer only.
+int run_spmm_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, void* C, int dtype, int64_t M, int64_t K,
+                 int64_t N, int64_t nnz, int variant, int flags, void* stream, const PlanLaunch* pl, int b_align, int c_align, bool dry_run,
+                 int* kind, Geometry* geo_out) {
+    *kind = 0;
+    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    if (M <= 0 || N <= 0 || N % 2 != 0 || b_align < 4 || c_align < 4) return kX16Unavailable;
+    const int64_t Nw = N / 2;  // words per row
+    int max_vec = 4;
+    while (max_vec > 1 && ((Nw % max_vec) != 0 || b_align < 4 * max_vec || c_align < 4 * max_vec)) max_vec >>= 1;
+    if (!dry_run) {  // (as run_spmm: a capturing stream takes the streaming kernels, which allocate nothing)
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(reinterpret_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) {
+            flags |= kFlagNoSlabBlocked | kFlagStrictOrder;
+            flags &= ~(kFlagSlabBlocked | kFlagSplitLongRows);
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    if (pl) {  // (as run_spmm: task tables exist for the two streaming kernels only)
+        flags |= kFlagNoSlabBlocked;
+        flags &= ~(kFlagSlabBlocked | kFlagSegStream | kFlagBatchStream);
+        flags |= (pl->prefer_segmented && pl->gtasks) ? kFlagSegStream : kFlagBatchStream;
+        flags &= ~kFlagAllowReassoc;
+    }
+    Selection sel;
+    if (resolve_geometry(M, K, Nw, nnz, variant, max_vec, 0, 0, 0, 0, 0, flags, &sel) != 0) return GESPMM_EINVAL;
+    sel.geo.reduce = kReduceSum;
+    if (sel.variant == GESPMM_VARIANT_NAIVE || sel.variant == GESPMM_VARIANT_PARREDUCE) return kX16Unavailable;
+    bool seg = sel.geo.segmented;
+    if (flags & kFlagBatchStream) seg = false;
+    if ((flags & kFlagSegStream) && !sel.geo.split_long_rows) seg = true;
+    if (seg && pl && sel.geo.strips == 2 && sel.geo.vec < 4) seg = false;
+    if (!x16_geometry_served(sel.geo, seg, pl != nullptr)) return kX16Unavailable;  // (long-row pass, cache blocking, 64-bit offsets too)
+    *kind = seg ? 2 : 1;
+    if (geo_out) *geo_out = sel.geo;
+    if (dry_run) return 0;
+
+    SpmmArgs a = {};
+    a.rowptr = rowptr;
+    a.colind = colind;
+    a.val = val;
+    a.B = static_cast<const float*>(B);  // (arrays of words: spmm_kernels.h, HalfSpmmArgs)
+    a.C = static_cast<float*>(C);
+    a.M = (int32_t)M;
+    a.N = (int32_t)Nw;
+    a.flags = flags;
+    a.rpw = seg ? sel.geo.rows_per_group : sel.geo.rows_per_wave;
+    a.tasks = pl ? pl->tasks : nullptr;
+    a.perm = pl ? pl->perm : nullptr;
+    a.ntasks = pl ? pl->ntasks : 0;
+    a.gtasks = pl ? pl->gtasks : nullptr;
+    a.ngtasks = pl ? pl->ngtasks : 0;
+    return (int)launch_spmm_x16(a, dtype, sel.geo, seg, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace gespmm
 
 namespace {
@@ -306,6 +384,46 @@ int gespmm_csr_spmm_fused_f32(const int32_t* rowptr, const int32_t* colind, cons
         if (rc == 0) rc = (int)e;
     }
     return rc;
+}
+
+// 16-bit dense operands (gespmm.h): one 16-bit streaming kernel where the byte-equivalent fp32 call would be one streaming kernel, else
+// the composition — widen B into a stream-ordered temporary, the fp32 call unchanged into a second one, narrow into C. Same bits:
+// widening is exact and either way the fp32 sum is rounded once.
+int gespmm_csr_spmm_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, void* C, int dtype, int64_t M,
+                        int64_t K, int64_t N, int64_t nnz, int variant, void* stream) {
+    const int rc0 = gespmm::check_x16_args(rowptr, colind, val, B, C, dtype, M, K, N, nnz);
+    if (rc0 != 0) return rc0;
+    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    if (M == 0 || N == 0) return 0;
+    int kind = 0;
+    int rc = gespmm::run_spmm_x16(rowptr, colind, val, B, C, dtype, M, K, N, nnz, variant, 0, stream, nullptr, gespmm::pointer_alignment(B),
+                                  gespmm::pointer_alignment(C), false, &kind);
+    if (rc != gespmm::kX16Unavailable) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
+    const size_t b_bytes = (((size_t)K * (size_t)N * 4) + 255) & ~(size_t)255, c_bytes = (size_t)M * (size_t)N * 4;
+    void* scratch = nullptr;
+    hipError_t e = gespmm::workspace_alloc(&scratch, b_bytes + c_bytes, st);
+    if (e != hipSuccess) return (int)e;
+    float* Bf = static_cast<float*>(scratch);
+    float* Cf = reinterpret_cast<float*>(static_cast<char*>(scratch) + b_bytes);
+    if (B && nnz != 0) e = gespmm::launch_widen_x16(B, Bf, dtype, K * N, st);
+    rc = (int)e;
+    if (rc == 0) rc = run_spmm(rowptr, colind, val, Bf, Cf, M, K, N, nnz, variant, nullptr, gespmm::kReduceSum, 0.0f, stream);
+    if (rc == 0) rc = (int)gespmm::launch_narrow_x16(Cf, C, dtype, M * N, st);
+    e = gespmm::workspace_free(scratch, st);
+    if (rc == 0) rc = (int)e;
+    return rc;
+}
+
+int gespmm_x16_route(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, int b_align, int c_align) {
+    if (M < 0 || K < 0 || N < 0 || nnz < -1 || b_align < 1 || c_align < 1) return GESPMM_EINVAL;
+    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    int kind = 0;
+    const int rc = gespmm::run_spmm_x16(nullptr, nullptr, nullptr, nullptr, nullptr, GESPMM_X16_BF16, M, K, N, nnz, variant, 0, nullptr, nullptr,
+                                        b_align, c_align, true, &kind);
+    if (rc != 0 && rc != gespmm::kX16Unavailable) return rc < 0 ? rc : GESPMM_EINVAL;
+    return kind;
 }
 
 int gespmm_csr_spmm_f32_cfg(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B,

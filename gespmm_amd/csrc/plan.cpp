@@ -112,6 +112,15 @@ struct gespmm_plan {
     // the fused product's composition route (gespmm_plan_spmm_fused_f32): K x N floats for col_scale . B, made by the first call that needs them
     float* d_fused_scratch = nullptr;  // owner
     int64_t fused_scratch_bytes = 0;
+    // 16-bit operands, composition route (gespmm_plan_spmm_x16): K x N floats for widen(B), M x N for the fp32 product; made by the first call
+    // that needs them (and again by a wider one)
+    float* d_x16_b = nullptr;  // owners
+    float* d_x16_c = nullptr;
+    int64_t x16_b_bytes = 0, x16_c_bytes = 0;
+    int x16_last_route = -1;   // what the last 16-bit call RAN (-1: none yet), its width, element type and lane geometry: gespmm_plan_describe
+    gespmm::Geometry x16_last_geo = {};
+    int64_t x16_last_N = 0;
+    int x16_last_dtype = 0;
     bool records_kept_by_policy = false;  // want_record_tables() / keep_record_tables() said yes at creation (else the tables exist only while tune measures them / if they won)
 
     gespmm_plan() = default;
@@ -122,7 +131,7 @@ struct gespmm_plan {
         gespmm::free_staging(&slab);
         gespmm::free_slab_view(&slab_view, false);
         gespmm::free_records(&rec);
-        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp, (void*)d_fused_scratch})
+        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp, (void*)d_fused_scratch, (void*)d_x16_b, (void*)d_x16_c})
             if (q) (void)hipFree(q);
     }
 };
@@ -975,6 +984,88 @@ int gespmm_plan_fused_route(const gespmm_plan* plan, int64_t N, int has_col_scal
     return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
 }
 
+// 16-bit dense operands through a plan. Two executions with the same bits (plan_policy.cpp: x16_route chooses):
+//   * ONE 16-bit streaming kernel — on the caller's arrays (storage order) or on the plan's stream task tables, which every clustered
+//     plan owns whatever its fp32 route is (staged rows, records, slabs);
+//   * the composition: widen(B) into the plan's temporary, the plan's fp32 route unchanged (plan_run) into a second one, narrow into C.
+// `dry`: the answer only (gespmm_plan_x16_route) — nothing is launched or allocated.
+static int plan_run_x16(gespmm_plan* p, const void* B, void* C, int dtype, int64_t N, void* stream, bool dry, int b_align, int c_align,
+                        int* route_out) {
+    *route_out = 0;
+    const gespmm::RouteAnswer ra = route_of(p, N, gespmm::kReduceSum, true);  // the fp32 route of the composition (its temporaries are aligned)
+    // the streaming launch on the task tables is chosen at the byte-equivalent fp32 width, like the lane geometry
+    const gespmm::RouteAnswer rw = (N % 2 == 0 && N > 0) ? route_of(p, N / 2, gespmm::kReduceSum, true) : ra;
+    const float* pval = p->valued ? (p->reordered ? p->d_val : p->val) : nullptr;
+    const gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, rw.segmented};
+    const int32_t* rp = p->reordered ? p->d_rowptr : p->rowptr;
+    const int32_t* ci = p->reordered ? p->d_colind : p->colind;
+    const int variant = (p->reordered && rw.vec4) ? GESPMM_VARIANT_CRC_CWM4 : p->variant;
+    int kind = 0;
+    int rc = gespmm::run_spmm_x16(rp, ci, pval, B, C, dtype, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
+                                  p->reordered ? &pl : nullptr, b_align, c_align, true, &kind);
+    if (rc != 0 && rc != gespmm::kX16Unavailable) return rc;
+    const int route = gespmm::x16_route(kind);
+    *route_out = route;
+    if (dry) return 0;
+    p->x16_last_N = N;
+    p->x16_last_dtype = dtype;
+    if (route != 0) {
+        // the launch itself looks at the stream: while it is capturing the selection drops the multi-kernel routes, so the kernel that
+        // runs may be the other streaming kernel than the dry answer — what ran is what describe reports — and should the geometry
+        // come out unserved the call falls through to the composition
+        rc = gespmm::run_spmm_x16(rp, ci, pval, B, C, dtype, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
+                                  p->reordered ? &pl : nullptr, b_align, c_align, false, &kind, &p->x16_last_geo);
+        if (rc != gespmm::kX16Unavailable) {
+            p->x16_last_route = kind;
+            return rc;
+        }
+    }
+    p->x16_last_route = 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t need_b = (p->nnz != 0 && p->K > 0) ? p->K * N * 4 : 0, need_c = p->M * N * 4;
+    if (p->x16_b_bytes < need_b || p->x16_c_bytes < need_c) {
+        if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
+        auto grow = [](float** q, int64_t* have, int64_t need) -> hipError_t {
+            if (*have >= need) return hipSuccess;
+            if (*q) (void)hipFree(*q);  // (synchronises: no earlier launch still uses it)
+            *q = nullptr;
+            *have = 0;
+            const hipError_t e = hipMalloc(reinterpret_cast<void**>(q), (size_t)need);
+            if (e == hipSuccess) *have = need;
+            return e;
+        };
+        hipError_t e = grow(&p->d_x16_b, &p->x16_b_bytes, need_b);
+        if (e == hipSuccess) e = grow(&p->d_x16_c, &p->x16_c_bytes, need_c);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (need_b > 0) {
+        const hipError_t e = gespmm::launch_widen_x16(B, p->d_x16_b, dtype, p->K * N, st);
+        if (e != hipSuccess) return (int)e;
+    }
+    rc = plan_run(p, p->d_x16_b, p->d_x16_c, N, gespmm::kReduceSum, 0.0f, stream);
+    if (rc == 0) rc = (int)gespmm::launch_narrow_x16(p->d_x16_c, C, dtype, p->M * N, st);
+    return rc;
+}
+
+int gespmm_plan_spmm_x16(gespmm_plan* plan, const void* B, void* C, int dtype, int64_t N, void* stream) {
+    if (!plan || N < 0) return GESPMM_EINVAL;
+    if (dtype != GESPMM_X16_F16 && dtype != GESPMM_X16_BF16) return GESPMM_EINVAL;
+    if (N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    if (plan->M > 0 && N > 0 && (!C || (plan->nnz != 0 && !B))) return GESPMM_EINVAL;
+    if (reinterpret_cast<uintptr_t>(B) % 2 != 0 || reinterpret_cast<uintptr_t>(C) % 2 != 0) return GESPMM_EALIGN;
+    if (plan->M == 0 || N == 0) return 0;
+    int route = 0;
+    return plan_run_x16(plan, B, C, dtype, N, stream, false, gespmm::pointer_alignment(B), gespmm::pointer_alignment(C), &route);
+}
+
+int gespmm_plan_x16_route(const gespmm_plan* plan, int64_t N, int b_align, int c_align) {
+    if (!plan || N < 0 || b_align < 1 || c_align < 1) return GESPMM_EINVAL;
+    if (plan->M == 0 || N == 0) return 0;
+    int route = 0;
+    const int rc = plan_run_x16(const_cast<gespmm_plan*>(plan), nullptr, nullptr, GESPMM_X16_BF16, N, nullptr, true, b_align, c_align, &route);
+    return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
+}
+
 // Which kernel, MEASURED: the candidates of a clustered plan — batch-stream, segmented-stream and (at the plan's width) staged-rows —
 // run on the caller's operands, `reps` launches each between a pair of events; the fastest becomes the plan's kernel. Every
 // candidate produces the same bits, so C holds the product afterwards whatever wins. The static rules of plan_policy.cpp
@@ -1218,7 +1309,7 @@ int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
     char what[256] = "";  // the streaming launch (of that width too: what the max reducer and unaligned operands get)
     gespmm_launch_cfg cfg = {0, 0, 0, 0, 0, p->launch_flags | (p->reordered ? ((ra.segmented ? GESPMM_FLAG_SEG_STREAM : GESPMM_FLAG_BATCH_STREAM) | GESPMM_FLAG_NO_SLAB_BLOCKED) : 0)};
     gespmm_describe_launch(p->M, p->K, p->N, p->nnz, ra.vec4 ? GESPMM_VARIANT_CRC_CWM4 : p->variant, &cfg, what, sizeof what);
-    char kern[420];
+    char kern[520];
     if (ra.route == PlanRoute::Records)
         snprintf(kern, sizeof kern, "kernel=padded-records tasks=%d batches_per_task>=%d batches=%d slot_fill=%.3f tables=%.4fs (max / other widths: %s)",
                  p->rec.ntasks, p->rec.target_batches, p->rec.nbatches, record_slot_fill(p), p->records_seconds, what);
@@ -1229,6 +1320,16 @@ int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
         snprintf(kern, sizeof kern, "kernel=staged-rows blocks=%d rows_in_lds<=%d staged_entries=%.3f hub_rows=%d tables=%.4fs (max / other widths: %s)",
                  p->stg.nblocks, gespmm::staged_block_shape(p->N).slots, p->stg.staged_fraction, p->stg.nlong, p->staging_seconds, what);
     else snprintf(kern, sizeof kern, "%s", what);
+    if (p->x16_last_route >= 0) {  // the last 16-bit call (gespmm_plan_spmm_x16)
+        const size_t used = strlen(kern);
+        char geo[64] = "";
+        if (p->x16_last_route != 0)
+            snprintf(geo, sizeof geo, " V=%d S=%d W=%d", p->x16_last_geo.vec, p->x16_last_geo.strips, p->x16_last_geo.group);
+        snprintf(kern + used, sizeof kern - used, " | x16 %s N=%lld route=%d (%s%s)", p->x16_last_dtype == GESPMM_X16_F16 ? "f16" : "bf16",
+                 (long long)p->x16_last_N, p->x16_last_route,
+                 p->x16_last_route == 1 ? "16-bit batch-stream" : p->x16_last_route == 2 ? "16-bit segmented-stream" : "widen, fp32 route, narrow",
+                 geo);
+    }
     int n;
     if (p->reordered) {
         char lv[128] = "";

@@ -40,6 +40,19 @@ int check_fused_args(const int32_t* rowptr, const int32_t* colind, const float* 
 // hipErrorStreamCaptureUnsupported when `st` is capturing (a composition that would have to allocate launches nothing), else 0
 int refuse_allocation_under_capture(hipStream_t st);
 
+// 16-bit dense operands (gespmm_csr_spmm_x16 / gespmm_plan_spmm_x16) as ONE launch of a 16-bit streaming kernel, where the fp32 launch of
+// the byte-equivalent width N / 2 would be one streaming kernel in a geometry the 16-bit kernels are built for (spmm_x16.h), N is even
+// and B and C are 4-byte aligned. *kind: 1 batch-stream, 2 segmented-stream, 0 not available (kX16Unavailable is returned and nothing is
+// launched: the caller composes widen, the fp32 route, narrow). b_align / c_align: powers of two that divide the operands' addresses;
+// dry_run: answer only — pointers are not looked at, and whether the stream is capturing is not asked.
+constexpr int kX16Unavailable = -102;  // internal
+int run_spmm_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, void* C, int dtype, int64_t M, int64_t K,
+                 int64_t N, int64_t nnz, int variant, int flags, void* stream, const PlanLaunch* pl, int b_align, int c_align, bool dry_run,
+                 int* kind, Geometry* geo_out = nullptr);  // geo_out: the lane geometry (in words) of the kernel *kind names
+int check_x16_args(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, const void* C, int dtype, int64_t M,
+                   int64_t K, int64_t N, int64_t nnz);
+int pointer_alignment(const void* p);  // largest power of two (<= 16) that divides the address
+
 // A plan's product behind a launch guard (auto_plan.cpp): kNotGuardable — and nothing launched — when the plan's launch is more than
 // one kernel (hub rows handed to the long-row pass, the cache-blocked path).
 int plan_spmm_guarded(gespmm_plan* plan, const float* B, float* C, int64_t N, int reduce, float empty, void* stream, const LaunchGuard* guard);

@@ -512,6 +512,30 @@ int fused_route(const PlanFacts& f, const RouteAnswer& unfused, int fused_kind, 
     return fused_kind;
 }
 
+// 16-bit operands: the 16-bit streaming kernel (on the caller's arrays or on the plan's stream task tables) or the composition around
+// the plan's fp32 route. Where the fp32 route is a streaming kernel, the 16-bit kernel is that kernel on half the bytes. Where the fp32
+// route is a table kernel (staged rows, records) both candidates exist: the 16-bit streaming kernel gathers half the bytes without the
+// table kernel's LDS reuse, the composition keeps the table kernel and pays 6 (K + M) N bytes of widen and narrow passes around it.
+// Measured, bf16, default plans, us, median of three runs (scripts/x16_timing.py -> profiles/r07/x16/timing.log):
+//   graph, N (the plan's fp32 route)                  16-bit kernel   composition   fp32 plan
+//   com-amazon-sbm  128 (staged rows, mean degree 5.5)      75.6          173.9         83.2
+//   com-amazon-sbm  256 (staged rows)                      126.6          350.8        162.3
+//   com-amazon-sbm   64 (padded records)                    47.6           97.1         45.4
+//   com-amazon-sbm   32 (batch-stream)                      38.2           69.2         46.3
+//   products-sbm    128 (staged rows, mean degree 50)     1936.1         3240.2       2536.5
+//   com-amazon-like 128 (storage order)                     82.3          239.6        154.3
+//   pubmed          128 (storage order)                     14.6           30.0         16.1
+// The composition loses on every row by x1.7-2.9, against a spread of 0.1-26 us across runs: the kernel is taken wherever it exists,
+// whatever the plan's facts and fp32 route are (so this function is not given them). On the records row the 16-bit kernel is 5 % behind
+// the FP32 plan — the record kernel has no 16-bit form — and still twice as fast as composing around it.
+// GESPMM_X16_ROUTE=composition|kernel pins the answer (read per call: the timing script and the tests run both in one process).
+int x16_route(int x16_kind) {
+    if (x16_kind == 0) return 0;
+    const char* const env = getenv("GESPMM_X16_ROUTE");
+    if (env && !strcmp(env, "composition")) return 0;
+    return x16_kind;
+}
+
 // The clustered edge walk pays a scatter pass at the end: worth it where the order is modelled to hit L2 for >= 40 % of the
 // gathers and the rows are >= 256 bytes (com-Amazon-shaped communities, N = 128: 114 vs 151 us COO / 167 us CSR; on the
 // structureless graph or at N = 41 it is equal or slower — profiles/r02/sddmm_plan.log). Otherwise short rows take the COO

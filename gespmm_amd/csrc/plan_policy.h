@@ -148,6 +148,11 @@ RouteAnswer plan_route(const PlanFacts& f, const RouteState& s, int64_t N, int r
 int fused_route(const PlanFacts& f, const RouteAnswer& unfused, int fused_kind, int64_t N, bool has_col_scale, bool has_row_scale,
                 bool has_bias);
 
+// ---- 16-bit operands through a plan (gespmm_plan_spmm_x16): 0 = composition (widen, the plan's fp32 route, narrow), else `x16_kind`
+//      (1 batch-stream, 2 segmented-stream: the ONE 16-bit streaming kernel this launch could be; 0 = there is none).
+//      Consulted by the 16-bit launch only.
+int x16_route(int x16_kind);
+
 // ---- SDDMM through the plan: 0 = CSR form on the caller's arrays, 1 = COO form on expanded row ids (storage order),
 //      2 = the plan's clustered edge order + scatter
 int sddmm_route(const PlanFacts& f, bool reordered, double hits_after, int64_t N_launch);

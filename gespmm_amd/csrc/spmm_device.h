@@ -120,4 +120,52 @@ __device__ __forceinline__ float combine(float acc, float a, float b) {
     }
 }
 
+// ----------------------------------------------------------------------------- 16-bit operands (HalfSpmmArgs: spmm_stream.h, spmm_x16.hip)
+//
+// A 32-bit word of B or C holds two elements, the lower-addressed one in its low half. The kernels carry words in `float` registers
+// (loads, stores and moves keep every bit pattern); these helpers are the only places that look inside.
+// widen: exact — every fp16 / bf16 value (subnormals included) is an fp32 value.
+// narrow: ONE rounding to nearest even; overflow gives +-inf, results that are subnormal in the 16-bit type are rounded, NaN stays NaN.
+// bf16 narrows in integer arithmetic, (u + 0x7fff + ((u >> 16) & 1)) >> 16 on the fp32 bits u: the contract of gespmm.h as written.
+
+template <int DT>
+__device__ __forceinline__ void widen_x16(float word, float& lo, float& hi) {
+    const uint32_t u = __float_as_uint(word);
+    if constexpr (DT == kX16Bf16) {
+        lo = __uint_as_float(u << 16);
+        hi = __uint_as_float(u & 0xffff0000u);
+    } else {
+        lo = (float)__builtin_bit_cast(_Float16, (uint16_t)(u & 0xffffu));
+        hi = (float)__builtin_bit_cast(_Float16, (uint16_t)(u >> 16));
+    }
+}
+
+template <int DT>
+__device__ __forceinline__ uint32_t narrow_x16(float f) {
+    if constexpr (DT == kX16Bf16) {
+        const uint32_t u = __float_as_uint(f);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // NaN: keep it one (quiet bit), whatever the low half held
+        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    } else {
+        return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+    }
+}
+
+template <int DT, bool VALUED, int V>
+__device__ __forceinline__ void accumulate_x16(float (&acc)[2 * V], float a, const float (&words)[V]) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        float lo, hi;
+        widen_x16<DT>(words[i], lo, hi);
+        acc[2 * i] = combine<kReduceSum, VALUED>(acc[2 * i], a, lo);
+        acc[2 * i + 1] = combine<kReduceSum, VALUED>(acc[2 * i + 1], a, hi);
+    }
+}
+
+template <int DT, int V>
+__device__ __forceinline__ void pack_x16(float (&words)[V], const float (&acc)[2 * V]) {
+#pragma unroll
+    for (int i = 0; i < V; ++i) words[i] = __uint_as_float(narrow_x16<DT>(acc[2 * i]) | (narrow_x16<DT>(acc[2 * i + 1]) << 16));
+}
+
 }  // namespace gespmm

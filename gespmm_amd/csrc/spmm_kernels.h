@@ -82,6 +82,16 @@ struct FusedSpmmArgs : SpmmArgs {
 template <class ARGS> struct is_fused_args { static constexpr bool value = false; };
 template <> struct is_fused_args<FusedSpmmArgs> { static constexpr bool value = true; };
 
+// 16-bit dense operands (gespmm_csr_spmm_x16): B and C hold IEEE fp16 or bfloat16, the sum stays fp32 and is rounded once at the store.
+// Again a type of its own, and nothing but a tag: the kernels work in 32-bit WORDS, so the SpmmArgs inside carries B and C as arrays of
+// words (two elements each) and N as the number of words per row (the caller's N / 2) — the addresses, the lane geometry and the task
+// tables are those of the fp32 kernels at half the width (spmm_stream.h).
+constexpr int kX16F16 = 1;   // == GESPMM_X16_F16
+constexpr int kX16Bf16 = 2;  // == GESPMM_X16_BF16
+template <int DT> struct HalfSpmmArgs : SpmmArgs {};
+template <class ARGS> struct x16_args { static constexpr int dtype = 0; };
+template <int DT> struct x16_args<HalfSpmmArgs<DT>> { static constexpr int dtype = DT; };
+
 // A device word + the value a guarded launch runs for (run_spmm / the plan's launch: only paths that are ONE kernel take a guard).
 struct LaunchGuard {
     const int32_t* word;
@@ -122,6 +132,14 @@ hipError_t launch_spmm_fused_planned(const FusedSpmmArgs& a, const Geometry& geo
 // in place (either vector may be NULL), a separate multiply and add each.
 hipError_t launch_scale_rows(const float* B, const float* col_scale, float* Bs, int64_t K, int64_t N, hipStream_t st);
 hipError_t launch_scale_bias_inplace(float* C, const float* row_scale, const float* bias, int64_t M, int64_t N, hipStream_t st);
+// spmm_x16.hip / spmm_x16_plan.hip: the 16-bit forms of the two streaming kernels (spmm_x16.h: the geometries they exist in). `a` is the
+// launch in WORDS (a.N = N / 2, a.B / a.C the 16-bit arrays), `geo` the geometry resolved for that width. hipErrorInvalidValue where not served.
+bool x16_geometry_served(const Geometry& geo, bool segmented, bool planned);
+hipError_t launch_spmm_x16(const SpmmArgs& a, int dtype, const Geometry& geo, bool segmented, hipStream_t st);
+hipError_t launch_spmm_x16_planned(const SpmmArgs& a, int dtype, const Geometry& geo, bool segmented, hipStream_t st);
+// ... and the elementwise passes of the composition route: dst[i] = widen(src[i]); dst[i] = narrow(src[i]) (one rounding to nearest even)
+hipError_t launch_widen_x16(const void* src, float* dst, int dtype, int64_t n, hipStream_t st);
+hipError_t launch_narrow_x16(const float* src, void* dst, int dtype, int64_t n, hipStream_t st);
 // The two paths below need a temporary: the caller's (ext_ws, 16-byte aligned, >= *_workspace_bytes) or,
 // when that is absent or too small, a stream-ordered block from the library's pool (workspace.h).
 size_t longrows_workspace_bytes(int64_t nnz, int64_t N, int long_row);

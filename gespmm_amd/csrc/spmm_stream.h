@@ -48,6 +48,14 @@ namespace gespmm {
 // NULL col_scale / row_scale read as 1.0f (x * 1.0f keeps every bit pattern the chain can tell apart); NULL bias skips the add
 // (x + 0.0f would turn -0.0 into +0.0).
 
+//
+// ARGS = HalfSpmmArgs<DT> (spmm_kernels.h; spmm_x16.hip, spmm_x16_plan.hip): B and C hold 16-bit numbers (DT: IEEE fp16 or bfloat16). The
+// kernel works in 32-bit WORDS: a.N counts the words of a row (two elements each), a.B / a.C are the arrays seen as words, so every
+// address, the lane geometry, the CSR tile stream and the task tables are those of the fp32 kernel at half the width. Only the
+// arithmetic differs: each gathered word widens (exactly) into two fp32 values that feed 2 V S fp32 accumulators — the row's sum
+// lives in fp32 in ascending CSR position, as ever — and at the row-end store each pair is rounded ONCE (to nearest even) and packed
+// back into a word. With any other ARGS every `if constexpr (X16)` is discarded.
+
 template <bool FUSED>
 __device__ __forceinline__ float prescale(float b, float scale) {
     if constexpr (FUSED) return __fmul_rn(b, scale);
@@ -65,6 +73,9 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(ARGS a) {
     constexpr int G = 64 / W;
     constexpr bool FUSED = is_fused_args<ARGS>::value;
     static_assert(!FUSED || RED == kReduceSum, "the fused product is a sum");
+    constexpr int X16 = x16_args<ARGS>::dtype;  // 0, or the element type of 16-bit operands
+    constexpr int EW = X16 ? 2 : 1;             // fp32 accumulators per loaded word
+    static_assert(!X16 || (RED == kReduceSum && !IDX64), "16-bit operands: sum reducer, 32-bit offsets");
     using off_t = typename std::conditional<IDX64, uint64_t, uint32_t>::type;
 
     __shared__ off_t s_off[kWaves][kTile];
@@ -226,11 +237,11 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(ARGS a) {
                 hb = __builtin_amdgcn_readfirstlane(hb);
             }
 
-            float acc[S][V];
+            float acc[S][V * EW];
     #pragma unroll
             for (int s = 0; s < S; ++s)
     #pragma unroll
-                for (int i = 0; i < V; ++i) acc[s][i] = init;
+                for (int i = 0; i < V * EW; ++i) acc[s][i] = init;
             float rscale = 1.0f;  // fused: row_scale of this lane group's C row, on its way while the row is summed
             if constexpr (FUSED) {
                 if (rowok2 && a.row_scale != nullptr) {
@@ -265,10 +276,14 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(ARGS a) {
     #pragma unroll
                     for (int j = 0; j < U; ++j)
     #pragma unroll
-                        for (int s = 0; s < S; ++s)
+                        for (int s = 0; s < S; ++s) {
+                            if constexpr (X16) {
+                                accumulate_x16<X16, VALUED, V>(acc[s], v[j], bv[j][s]);
+                            } else {
     #pragma unroll
-                            for (int i = 0; i < V; ++i)
-                                acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                                for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                            }
+                        }
                 }
                 // Tail (1..U-1 entries): ONE predicated group, so a short row is a single round
                 // trip. It is not inside a loop, so there is no loop-carried register hazard and
@@ -302,10 +317,14 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(ARGS a) {
                     for (int j = 0; j < U - 1; ++j) {
                         if (j < rem) {
     #pragma unroll
-                            for (int s = 0; s < S; ++s)
+                            for (int s = 0; s < S; ++s) {
+                                if constexpr (X16) {
+                                    accumulate_x16<X16, VALUED, V>(acc[s], v[j], bv[j][s]);
+                                } else {
     #pragma unroll
-                                for (int i = 0; i < V; ++i)
-                                    acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                                    for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                                }
+                            }
                         }
                     }
                 }
@@ -336,9 +355,17 @@ __global__ __launch_bounds__(kThreads) void spmm_stream_kernel(ARGS a) {
     #pragma unroll
                 for (int s = 0; s < S; ++s)
                     if (colok[s]) {
-                        if (sc1) store_vec_sc1<V>(Crow + s * (W * V), acc[s]);
-                        else if (nts) store_vec<V, true>(Crow + s * (W * V), acc[s]);
-                        else store_vec<V, false>(Crow + s * (W * V), acc[s]);
+                        if constexpr (X16) {
+                            float pk[V];  // the row's 2 V sums of this strip, each rounded once, as V words
+                            pack_x16<X16, V>(pk, acc[s]);
+                            if (sc1) store_vec_sc1<V>(Crow + s * (W * V), pk);
+                            else if (nts) store_vec<V, true>(Crow + s * (W * V), pk);
+                            else store_vec<V, false>(Crow + s * (W * V), pk);
+                        } else {
+                            if (sc1) store_vec_sc1<V>(Crow + s * (W * V), acc[s]);
+                            else if (nts) store_vec<V, true>(Crow + s * (W * V), acc[s]);
+                            else store_vec<V, false>(Crow + s * (W * V), acc[s]);
+                        }
                     }
             }
         }
@@ -369,6 +396,9 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(ARGS a) {
     constexpr int G = 64 / W;
     constexpr bool FUSED = is_fused_args<ARGS>::value;
     static_assert(!FUSED || RED == kReduceSum, "the fused product is a sum");
+    constexpr int X16 = x16_args<ARGS>::dtype;  // 0, or the element type of 16-bit operands
+    constexpr int EW = X16 ? 2 : 1;             // fp32 accumulators per loaded word
+    static_assert(!X16 || (RED == kReduceSum && !IDX64), "16-bit operands: sum reducer, 32-bit offsets");
     constexpr int T = (W > 32) ? W : 32;  // entries per group tile
     constexpr int E = T / W;              // entries each lane stages per refill
     static_assert(T % U == 0, "tile must hold whole steps");
@@ -527,11 +557,11 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(ARGS a) {
     else fetch_tile_regs(tbase + T);
     wave_lds_sync();
 
-    float acc[S][V];
+    float acc[S][V * EW];
 #pragma unroll
     for (int s = 0; s < S; ++s)
 #pragma unroll
-        for (int i = 0; i < V; ++i) acc[s][i] = init;
+        for (int i = 0; i < V * EW; ++i) acc[s][i] = init;
     int cur = 0;                                       // current row of the task
     int rend = (nrows > 0) ? s_ptr[wave][g][1] : 0;    // CSR end of the current row
     float rscale = 1.0f;  // fused: row_scale of the current row's C row (loaded a row ahead of its use)
@@ -562,12 +592,20 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(ARGS a) {
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (colok[s]) {
-                if (sc1) store_vec_sc1<V>(Crow + s * (W * V), acc[s]);
-                else if (nts) store_vec<V, true>(Crow + s * (W * V), acc[s]);
-                else store_vec<V, false>(Crow + s * (W * V), acc[s]);
+                if constexpr (X16) {
+                    float pk[V];
+                    pack_x16<X16, V>(pk, acc[s]);
+                    if (sc1) store_vec_sc1<V>(Crow + s * (W * V), pk);
+                    else if (nts) store_vec<V, true>(Crow + s * (W * V), pk);
+                    else store_vec<V, false>(Crow + s * (W * V), pk);
+                } else {
+                    if (sc1) store_vec_sc1<V>(Crow + s * (W * V), acc[s]);
+                    else if (nts) store_vec<V, true>(Crow + s * (W * V), acc[s]);
+                    else store_vec<V, false>(Crow + s * (W * V), acc[s]);
+                }
             }
 #pragma unroll
-            for (int i = 0; i < V; ++i) acc[s][i] = init;
+            for (int i = 0; i < V * EW; ++i) acc[s][i] = init;
         }
         ++cur;
         rend = s_ptr[wave][g][(cur + 1 <= nrows) ? cur + 1 : nrows];
@@ -609,17 +647,27 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(ARGS a) {
 #pragma unroll
                 for (int j = 0; j < U; ++j)
 #pragma unroll
-                    for (int s = 0; s < S; ++s)
+                    for (int s = 0; s < S; ++s) {
+                        if constexpr (X16) {
+                            accumulate_x16<X16, VALUED, V>(acc[s], v[j], bv[j][s]);
+                        } else {
 #pragma unroll
-                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                            for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                        }
+                    }
             } else {
 #pragma unroll
                 for (int j = 0; j < U; ++j) {
                     while (k + j >= rend) flush_row();  // rows ending before this entry (incl. empty ones)
 #pragma unroll
-                    for (int s = 0; s < S; ++s)
+                    for (int s = 0; s < S; ++s) {
+                        if constexpr (X16) {
+                            accumulate_x16<X16, VALUED, V>(acc[s], v[j], bv[j][s]);
+                        } else {
 #pragma unroll
-                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                            for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                        }
+                    }
                 }
             }
         } else {
@@ -643,9 +691,14 @@ __global__ __launch_bounds__(kThreads) void spmm_segstream_kernel(ARGS a) {
                 if (j < cnt) {
                     while (k + j >= rend) flush_row();
 #pragma unroll
-                    for (int s = 0; s < S; ++s)
+                    for (int s = 0; s < S; ++s) {
+                        if constexpr (X16) {
+                            accumulate_x16<X16, VALUED, V>(acc[s], v[j], bv[j][s]);
+                        } else {
 #pragma unroll
-                        for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                            for (int i = 0; i < V; ++i) acc[s][i] = combine<RED, VALUED>(acc[s][i], v[j], prescale<FUSED>(bv[j][s][i], sc[j]));
+                        }
+                    }
                 }
             }
         }
@@ -685,7 +738,10 @@ static hipError_t launch_stream(const ARGS& a, int rpw, hipStream_t st) {
         hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                            dim3(kThreads), 0, st, args);
     } else {
-        if (a.flags & kFlagShallowUnroll)
+        if constexpr (x16_args<ARGS>::dtype != 0) {  // (no launch knobs with 16-bit operands: the shallow form is not built)
+            hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 8, PLANNED, ARGS>), dim3((unsigned)nitems),
+                               dim3(kThreads), 0, st, args);
+        } else if (a.flags & kFlagShallowUnroll)
             hipLaunchKernelGGL((spmm_stream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                                dim3(kThreads), 0, st, args);
         else
@@ -752,7 +808,10 @@ static hipError_t launch_segstream(const ARGS& a, int rpg, hipStream_t st) {
         hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                            dim3(kThreads), 0, st, args);
     } else {
-        if (a.flags & kFlagShallowUnroll)
+        if constexpr (x16_args<ARGS>::dtype != 0) {  // (no launch knobs with 16-bit operands: the shallow form is not built)
+            hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 8, PLANNED, ARGS>), dim3((unsigned)nitems),
+                               dim3(kThreads), 0, st, args);
+        } else if (a.flags & kFlagShallowUnroll)
             hipLaunchKernelGGL((spmm_segstream_kernel<V, S, W, VALUED, IDX64, RED, 4, PLANNED, ARGS>), dim3((unsigned)nitems),
                                dim3(kThreads), 0, st, args);
         else

@@ -28,6 +28,17 @@ void need(const torch::Tensor& t, const char* name, c10::ScalarType dtype, int64
     TORCH_CHECK_VALUE(t.is_contiguous(), name, " must be contiguous");
 }
 
+// `dense` of the products: fp32, or 16 bits (fp16 / bf16: gespmm_csr_spmm_x16 — the result has the operand's dtype). Returns GESPMM_X16_* or 0.
+int need_dense(const torch::Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be a HIP (cuda) device tensor; gespmm_amd has no CPU path");
+    const auto st = t.scalar_type();
+    TORCH_CHECK_TYPE(st == torch::kFloat32 || st == torch::kFloat16 || st == torch::kBFloat16, name,
+                     " must have dtype torch.float32, torch.float16 or torch.bfloat16, got ", st);
+    TORCH_CHECK_VALUE(t.dim() == 2, name, " must be 2-dimensional");
+    TORCH_CHECK_VALUE(t.is_contiguous(), name, " must be contiguous");
+    return st == torch::kFloat16 ? GESPMM_X16_F16 : st == torch::kBFloat16 ? GESPMM_X16_BF16 : 0;
+}
+
 void same_device(const torch::Tensor& a, const torch::Tensor& b) {
     TORCH_CHECK(a.device() == b.device(), "all tensors must live on the same device");
 }
@@ -45,7 +56,7 @@ torch::Tensor spmm_impl(const torch::Tensor& rowptr, const torch::Tensor& colind
                         const c10::optional<torch::Tensor>& workspace = c10::nullopt, int64_t flags = 0) {
     need(rowptr, "rowptr", torch::kInt32, 1);
     need(colind, "colind", torch::kInt32, 1);
-    need(dense, "dense", torch::kFloat32, 2);
+    const int x16 = need_dense(dense, "dense");
     same_device(dense, rowptr);
     same_device(dense, colind);
     const float* val = nullptr;
@@ -59,6 +70,13 @@ torch::Tensor spmm_impl(const torch::Tensor& rowptr, const torch::Tensor& colind
     const int64_t M = rowptr.numel() - 1, K = dense.size(0), N = dense.size(1), nnz = colind.numel();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dense.device());
     auto out = torch::empty({M, N}, dense.options());
+    if (x16) {  // 16-bit operands: no launch knobs, temporaries (composition route only) from the library's pool
+        TORCH_CHECK_VALUE(flags == 0, "launch flags need a torch.float32 dense");
+        check_rc(gespmm_csr_spmm_x16(rowptr.data_ptr<int32_t>(), colind.data_ptr<int32_t>(), val, dense.data_ptr(), out.data_ptr(), x16, M, K, N,
+                                     nnz, (int)variant, current_stream(dense)),
+                 "gespmm_csr_spmm_x16");
+        return out;
+    }
     // Scratch for the two paths that need it (dense-graph cache blocking, long-row pass) comes from
     // torch's caching allocator: no driver allocation per call, and legal under torch.cuda.graph.
     // A caller-kept workspace (gespmm_amd/spmm.py: SpmmPlan) is used as is.
@@ -181,16 +199,21 @@ torch::Tensor csr_sddmm(const torch::Tensor& rowptr, const torch::Tensor& colind
 // ---- plans (the analysis stage, gespmm_plan_*): the hot call of a training loop, so it gets the short path as well.
 // The Python class (spmm.SpmmPlan) owns the handle and the consistency checks; these two functions only launch.
 torch::Tensor plan_spmm(int64_t handle, const torch::Tensor& dense, const c10::optional<torch::Tensor>& out_opt, int64_t M) {
-    need(dense, "dense", torch::kFloat32, 2);
+    const int x16 = need_dense(dense, "dense");
     const int64_t N = dense.size(1);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dense.device());
     torch::Tensor out;
     if (out_opt.has_value()) {
         out = *out_opt;
-        need(out, "out", torch::kFloat32, 2);
-        TORCH_CHECK_VALUE(out.size(0) == M && out.size(1) == N && out.device() == dense.device(), "out must be f32[M, N] on the same device");
+        need(out, "out", dense.scalar_type(), 2);
+        TORCH_CHECK_VALUE(out.size(0) == M && out.size(1) == N && out.device() == dense.device(), "out must be [M, N] on the same device");
     } else {
         out = torch::empty({M, N}, dense.options());
+    }
+    if (x16) {
+        check_rc(gespmm_plan_spmm_x16(reinterpret_cast<gespmm_plan*>(handle), dense.data_ptr(), out.data_ptr(), x16, N, current_stream(dense)),
+                 "gespmm_plan_spmm_x16");
+        return out;
     }
     check_rc(gespmm_plan_spmm_f32(reinterpret_cast<gespmm_plan*>(handle), dense.data_ptr<float>(), out.data_ptr<float>(), N,
                                   current_stream(dense)),

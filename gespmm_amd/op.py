@@ -32,6 +32,11 @@ first forward's operands (``SpmmPlan.tune``: a few extra launches once per direc
 ``GCNConv(..., fused=True)`` (extension, off by default) runs the two scalings and the bias INSIDE the product
 (``FusedGCNFunction`` on ``spmm.csr_spmm_fused``): three elementwise passes over an M x N matrix less in forward, two less in
 backward, and the same output bits. It works with ``cached=True`` (plans) and without.
+16-bit features (extension): ``SPMMFunction`` takes ``feat`` of ``torch.float16`` / ``torch.bfloat16`` (a ``.half()`` / ``.bfloat16()``
+model, or ``torch.autocast``) and runs forward and backward on the 16-bit product (``spmm.csr_spmm`` with a 16-bit ``dense``: fp32 sum,
+one rounding; ``grad_out`` arrives in the forward's dtype); edge weights stay fp32. GCNConv casts its two scaling vectors to the dtype
+of ``x @ W`` so that the product stays 16-bit. fp32 only, with a TypeError otherwise: ``need_edge_grad=True`` (SDDMM), ``fused=True``
+and ``tune_plans=True``.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -52,6 +57,8 @@ class SPMMFunction(torch.autograd.Function):
                 need_edge_grad=False, plans=None):
         fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
         ctx.fwd_plan = fwd_plan
+        if need_edge_grad and feat.dtype != torch.float32:
+            raise TypeError("need_edge_grad=True needs torch.float32 feat (the SDDMM ops are fp32 only), got %s" % feat.dtype)
         if edge_weight_csr is None:
             out = _spmm.csr_spmm_no_edge_value(rowptr, colind, feat, plan=fwd_plan)
         else:
@@ -196,6 +203,10 @@ class GCNConv(torch.nn.Module):
     def forward(self, x, rowptr, colind, colptr, rowind, edge_weight_csr=None, edge_weight_csc=None):
         h = x @ self.weight
         in_scale, out_scale = self._scalings(h, rowptr, colptr)
+        if h.dtype in (torch.float16, torch.bfloat16):  # 16-bit features: keep `h * out_scale` (and with it the product) in that dtype
+            if self.fused:
+                raise TypeError("GCNConv(fused=True) needs torch.float32 features (the fused product is fp32 only), got %s" % h.dtype)
+            in_scale, out_scale = in_scale.to(h.dtype), out_scale.to(h.dtype)
         if self.normalize and not self.fused:
             h = h * out_scale
         plans = None

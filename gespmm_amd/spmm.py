@@ -13,6 +13,11 @@ through the ctypes binding of the same C ABI otherwise or when tuning knobs are 
 both validate identically and neither has a CPU path. Extra keyword
 arguments (``variant``, ``cfg``) expose the C ABI's tuning knobs and default to the
 library's choice.
+
+16-bit operands: ``csr_spmm``, ``csr_spmm_no_edge_value`` and ``SpmmPlan.run`` also take ``dense`` of ``torch.float16`` /
+``torch.bfloat16`` and return that dtype (gespmm_csr_spmm_x16 / gespmm_plan_spmm_x16: the sum is fp32 and is rounded once, so the result
+has the bits of ``op(dense.float()).to(dense.dtype)``). ``values`` stay fp32, ``out=`` must have the dtype of ``dense``, ``cfg=`` needs
+fp32. ``csr_spmm_fused``, ``csr_spmm_max`` / ``reduce_max=``, ``SpmmPlan.tune`` and the SDDMM ops are fp32 only.
 """
 import ctypes
 
@@ -34,6 +39,18 @@ def _need(t, name, dtype, ndim):
         raise ValueError("%s must be %d-dimensional" % (name, ndim))
     if not t.is_contiguous():
         raise ValueError("%s must be contiguous" % name)
+
+
+_X16 = {torch.float16: _lib.X16_F16, torch.bfloat16: _lib.X16_BF16}
+
+
+def _need_dense(t, name="dense"):
+    """``dense`` of the products: fp32, or fp16 / bf16 (the 16-bit entry points). Returns the GESPMM_X16_* code, 0 for fp32."""
+    if isinstance(t, torch.Tensor) and t.dtype in _X16:
+        _need(t, name, t.dtype, 2)
+        return _X16[t.dtype]
+    _need(t, name, torch.float32, 2)
+    return 0
 
 
 def _same_device(*ts):
@@ -142,7 +159,7 @@ class SpmmPlan:
 
     def tune(self, dense, out=None, reps=3):
         """Kernel choice by measurement (gespmm_plan_tune): the plan's candidate kernels run ``reps`` times each on ``dense`` and the
-        fastest is kept; returns the product (same bits whichever wins). ``dense`` must have the plan's width."""
+        fastest is kept; returns the product (same bits whichever wins). ``dense`` must have the plan's width. fp32 only."""
         _need(dense, "dense", torch.float32, 2)
         M, K, N, _, _ = self.shape
         if tuple(dense.shape) != (K, N):
@@ -191,13 +208,23 @@ class SpmmPlan:
             self._values, self._values_version = values, values._version
 
     def run(self, values, dense, out=None, reduce_max=None):
-        _need(dense, "dense", torch.float32, 2)
+        """``dense`` may be fp16 / bf16 (the result has its dtype; sum reducer only: ``reduce_max`` needs fp32)."""
+        x16 = _need_dense(dense) if reduce_max is None else _need(dense, "dense", torch.float32, 2)
         M, K, _, _, _ = self.shape
         N = dense.shape[1]
         if _ext is not None and reduce_max is None and hasattr(_ext, "plan_spmm"):
             return _ext.plan_spmm(self._handle.value, dense, out, M)  # pybind11 path: ~5 us per call instead of ~12
         if out is None:
-            out = torch.empty((M, N), dtype=torch.float32, device=self.device)
+            out = torch.empty((M, N), dtype=dense.dtype, device=self.device)
+        elif x16:
+            _need(out, "out", dense.dtype, 2)
+            if tuple(out.shape) != (M, N) or out.device != self.device:
+                raise ValueError("out must be [M, N] of the dtype of dense on the same device")
+        if x16:
+            with _on_device(self.device):
+                rc = lib.gespmm_plan_spmm_x16(self._handle, _ptr(dense), _ptr(out), x16, N, _stream(self.device))
+            check(rc, "gespmm_plan_spmm_x16")
+            return out
         with _on_device(self.device):
             if reduce_max is None:
                 rc = lib.gespmm_plan_spmm_f32(self._handle, _ptr(dense), _ptr(out), N, _stream(self.device))
@@ -227,6 +254,14 @@ class SpmmPlan:
                                                 _stream(self.device))
         check(rc, "gespmm_plan_spmm_fused_f32")
         return out
+
+    def x16_route(self, N=None, b_align=16, c_align=16):
+        """What ``run`` does with fp16 / bf16 operands at width N (default: the plan's) whose addresses ``b_align`` / ``c_align`` divide
+        (gespmm_plan_x16_route, host only): 0 widen + the fp32 route + narrow, 1 / 2 the 16-bit batch- / segmented-stream kernel."""
+        rc = lib.gespmm_plan_x16_route(self._handle, int(self.shape[2] if N is None else N), int(b_align), int(c_align))
+        if rc < 0:
+            check(rc, "gespmm_plan_x16_route")
+        return rc
 
     def fused_route(self, N=None, col_scale=True, row_scale=True, bias=True):
         """What ``run_fused`` does at width N (default: the plan's) with these vectors present (gespmm_plan_fused_route, host only):
@@ -268,7 +303,7 @@ def csr_spmm_fused(rowptr, colind, values, dense, col_scale=None, row_scale=None
                    variant=_lib.VARIANT_AUTO, reduce_max=None):
     """``C = ((A @ (col_scale[:, None] * dense)) * row_scale[:, None]) + bias`` in ONE product (gespmm_csr_spmm_fused_f32 /
     gespmm_plan_spmm_fused_f32) — the normalisation of a graph convolution without its three elementwise passes. ``values`` None: A == 1.
-    Every vector is optional; the result has the bits of torch ``mul``, ``csr_spmm``, ``mul``, ``add`` as separate steps (with no
+    fp32 only. Every vector is optional; the result has the bits of torch ``mul``, ``csr_spmm``, ``mul``, ``add`` as separate steps (with no
     vector at all the call IS the plain product). Sum reducer only: ``reduce_max`` together with a vector raises GESPMM_EINVAL."""
     _need(rowptr, "rowptr", torch.int32, 1)
     _need(colind, "colind", torch.int32, 1)
@@ -310,7 +345,7 @@ def csr_spmm_fused(rowptr, colind, values, dense, col_scale=None, row_scale=None
 def _spmm(rowptr, colind, values, dense, variant, cfg, out, plan=None):
     _need(rowptr, "rowptr", torch.int32, 1)
     _need(colind, "colind", torch.int32, 1)
-    _need(dense, "dense", torch.float32, 2)
+    x16 = _need_dense(dense)
     if values is not None:
         _need(values, "values", torch.float32, 1)
         if values.numel() != colind.numel():
@@ -323,18 +358,26 @@ def _spmm(rowptr, colind, values, dense, variant, cfg, out, plan=None):
     M = rowptr.numel() - 1
     K, N = dense.shape
     nnz = colind.numel()
+    if x16 and cfg is not None:
+        raise ValueError("cfg (launch knobs) needs a torch.float32 dense: the 16-bit kernels are built without them")
     if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=dev)
+        out = torch.empty((M, N), dtype=dense.dtype, device=dev)
     else:
-        _need(out, "out", torch.float32, 2)
+        _need(out, "out", dense.dtype, 2)
         if tuple(out.shape) != (M, N) or out.device != dev:
-            raise ValueError("out must be f32[M, N] on the same device")
+            raise ValueError("out must be [M, N] of the dtype of dense on the same device")
     c = _make_cfg(cfg)
     if plan is not None:
         if c is not None:
             raise ValueError("a plan fixes the launch configuration: pass either cfg or plan")
         plan._sync_inputs(rowptr, colind, values, dense, variant)
         return plan.run(values, dense, out)
+    if x16:
+        with _on_device(dev):
+            rc = lib.gespmm_csr_spmm_x16(_ptr(rowptr), _ptr(colind), _ptr(values) if values is not None else None, _ptr(dense), _ptr(out),
+                                         x16, M, K, N, nnz, int(variant), _stream(dev))
+        check(rc, "gespmm_csr_spmm_x16")
+        return out
     cref = ctypes.byref(c) if c is not None else None
     # scratch for the cache-blocked / long-row paths from torch's allocator (see torch_binding.cpp)
     ws_bytes = lib.gespmm_csr_spmm_workspace_bytes(M, K, N, nnz, int(variant), cref)
@@ -350,7 +393,7 @@ def _spmm(rowptr, colind, values, dense, variant, cfg, out, plan=None):
 
 
 def csr_spmm(rowptr, colind, values, dense, variant=_lib.VARIANT_AUTO, cfg=None, out=None, plan=None):
-    """C = A @ dense with A = CSR(rowptr, colind, values). Mirrors spmm.cpp:24-43."""
+    """C = A @ dense with A = CSR(rowptr, colind, values). Mirrors spmm.cpp:24-43. ``dense`` may be fp16 / bf16 (see the module text)."""
     if values is None:
         raise TypeError("csr_spmm needs edge values; use csr_spmm_no_edge_value for A == 1")
     if _ext is not None and cfg is None and out is None and plan is None:
@@ -359,7 +402,7 @@ def csr_spmm(rowptr, colind, values, dense, variant=_lib.VARIANT_AUTO, cfg=None,
 
 
 def csr_spmm_no_edge_value(rowptr, colind, dense, variant=_lib.VARIANT_AUTO, cfg=None, out=None, plan=None):
-    """C = A @ dense with A == 1 on its pattern. Mirrors spmm.cpp:45-60."""
+    """C = A @ dense with A == 1 on its pattern. Mirrors spmm.cpp:45-60. ``dense`` may be fp16 / bf16 (see the module text)."""
     if _ext is not None and cfg is None and out is None and plan is None:
         return _ext.csr_spmm_no_edge_value(rowptr, colind, dense, int(variant))
     return _spmm(rowptr, colind, None, dense, variant, cfg, out, plan)
@@ -368,7 +411,7 @@ def csr_spmm_no_edge_value(rowptr, colind, dense, variant=_lib.VARIANT_AUTO, cfg
 def csr_spmm_max(rowptr, colind, dense, empty_value=-10000.0, variant=_lib.VARIANT_AUTO):
     """C[r, :] = max over neighbours of dense[col, :] (DGL max reducer,
     binary_reduce_max.cu:182-207; rows without neighbours give ``empty_value``, the
-    reference's hard-coded -10000)."""
+    reference's hard-coded -10000). fp32 only."""
     if _ext is not None:
         return _ext.csr_spmm_max(rowptr, colind, dense, float(empty_value), int(variant))
     _need(rowptr, "rowptr", torch.int32, 1)

@@ -384,6 +384,40 @@ int gespmm_plan_spmm_fused_f32(gespmm_plan* plan, const float* B, const float* c
    0 composition, 1 fused batch-stream, 2 fused segmented-stream */
 int gespmm_plan_fused_route(const gespmm_plan* plan, int64_t N, int has_col_scale, int has_row_scale, int has_bias);
 /*
+ * 16-bit dense operands: C = A * B with B [K x N] and C [M x N] row-major arrays of IEEE fp16 (GESPMM_X16_F16) or bfloat16
+ * (GESPMM_X16_BF16); `val` stays fp32 (or NULL: A == 1 on its pattern). The sum is fp32 and is rounded ONCE:
+ *
+ *     b(k,c)   = widen(B[k,c])                         exact: every fp16 / bf16 value is an fp32 value, subnormals included
+ *     acc(r,c) = fma(val[p], b(colind[p],c), acc) over the row's entries in CSR order, acc0 = 0   (val == NULL: acc + b)
+ *     C[r,c]   = narrow(acc(r,c))                      one round-to-nearest-even fp32 -> 16 bits
+ *
+ * Overflow gives +-inf, a result that is subnormal in the 16-bit type is rounded (not flushed), NaN stays NaN (payload not pinned).
+ * For bf16, narrow of a non-NaN with fp32 bits u is (u + 0x7fff + ((u >> 16) & 1)) >> 16. The sum is never held in 16 bits. So the
+ * result has THE SAME BITS as widen, gespmm_csr_spmm_f32 / gespmm_plan_spmm_f32, narrow as separate passes; where that fp32 call
+ * re-associates (long-row pass) the 16-bit call re-associates identically.
+ *
+ * Two executions, same bits: ONE 16-bit streaming kernel (batch-stream or segmented-stream, on the caller's arrays or on a
+ * clustered plan's task tables) where N is even, B and C are 4-byte aligned (8 and 16 bytes allow wider accesses) and the fp32 call
+ * of the byte-equivalent width N / 2 would be one streaming kernel with 32-bit offsets (K N 2 < 2^32; no long-row pass, no cache
+ * blocking); else the composition — widen B into a K x N fp32 temporary, the unchanged fp32 route into an M x N one, narrow into C.
+ * The stateless call takes both temporaries stream-ordered from the library's pool; a plan owns them (allocated by the first call
+ * that needs them, freed with the plan). On a capturing stream a composition that would have to allocate returns
+ * hipErrorStreamCaptureUnsupported and launches nothing; a plan whose temporaries exist captures fine.
+ * The stateless entry does NOT take part in gespmm_set_auto_plan. gespmm_plan_describe names the route the last 16-bit call took.
+ * Conventions as everywhere in this header: device pointers, asynchronous on `stream`; GESPMM_EINVAL (unknown dtype, NULL pointers,
+ * negative sizes, bad variant) and GESPMM_EALIGN (B or C not 2-byte aligned, val not 4-byte aligned) are checked before any device
+ * work; M == 0 or N == 0 returns 0.
+ */
+#define GESPMM_X16_F16  1
+#define GESPMM_X16_BF16 2
+int gespmm_csr_spmm_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, void* C, int dtype,
+                        int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, void* stream);
+int gespmm_plan_spmm_x16(gespmm_plan* plan, const void* B, void* C, int dtype, int64_t N, void* stream);
+/* host only: what the calls above would do with operands whose addresses b_align / c_align (powers of two) divide, on a stream that
+   is not capturing. 0 composition, 1 16-bit batch-stream kernel, 2 16-bit segmented-stream kernel */
+int gespmm_x16_route(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, int b_align, int c_align);
+int gespmm_plan_x16_route(const gespmm_plan* plan, int64_t N, int b_align, int c_align);
+/*
  * Kernel choice by MEASUREMENT instead of by rule: runs the candidates of a clustered plan (batch-stream, segmented-stream,
  * staged-rows where the width is served, and at N <= 64 the batch-stream kernel with 4 floats per lane) `reps` (0 = 3) times each on these operands, synchronously, and fixes the plan
  * on the fastest; C holds the product afterwards (every candidate gives the same bits). N must be the plan's width. A no-op
