@@ -93,6 +93,10 @@ EXPORTS = [
     "gespmm_plan_spmm_x16",
     "gespmm_x16_route",
     "gespmm_plan_x16_route",
+    "gespmm_sddmm_coo_x16",
+    "gespmm_sddmm_csr_x16",
+    "gespmm_plan_sddmm_x16",
+    "gespmm_describe_sddmm_x16",
 ]
 
 X16_F16 = 1
@@ -246,6 +250,14 @@ def _load():
     lib.gespmm_plan_sddmm_route.argtypes = [p, c_int64]
     lib.gespmm_describe_sddmm.restype = c_int
     lib.gespmm_describe_sddmm.argtypes = [c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_sddmm_coo_x16.restype = c_int
+    lib.gespmm_sddmm_coo_x16.argtypes = [p, p, p, p, p, c_int, c_int64, c_int64, p]
+    lib.gespmm_sddmm_csr_x16.restype = c_int
+    lib.gespmm_sddmm_csr_x16.argtypes = [p, p, p, p, p, c_int, c_int64, c_int64, c_int64, p]
+    lib.gespmm_plan_sddmm_x16.restype = c_int
+    lib.gespmm_plan_sddmm_x16.argtypes = [p, p, p, p, c_int, c_int64, p]
+    lib.gespmm_describe_sddmm_x16.restype = c_int
+    lib.gespmm_describe_sddmm_x16.argtypes = [c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_plan_set_values.restype = c_int
     lib.gespmm_plan_set_values.argtypes = [p, p, p]
     lib.gespmm_plan_get_order.restype = c_int
@@ -304,13 +316,15 @@ def plan_policy(M, K, nnz, N, max_degree, hits_before=0.0, hits_after=0.0, stage
     return {n: getattr(a, n) for n, _ in PlanPolicyAnswer._fields_ if not n.startswith("reserved")}
 
 
-def describe_sddmm(csr, M, nnz, N, d1_align=16, d2_align=16, capturing=False):
-    """What gespmm_sddmm_{coo,csr}_f32 would launch for these arguments (gespmm_describe_sddmm: host only) — a dict with
-    "form" ("coo-edge", "csr-edge", "row-walk", "blocked" or "none") and the integers the form has: V, W, epw / nslab, slab_rows."""
+def describe_sddmm(csr, M, nnz, N, d1_align=16, d2_align=16, capturing=False, x16=False):
+    """What gespmm_sddmm_{coo,csr}_f32 — x16=True: gespmm_sddmm_{coo,csr}_x16, fp16 / bf16 operands — would launch for these arguments
+    (gespmm_describe_sddmm / gespmm_describe_sddmm_x16: host only) — a dict with "form" ("coo-edge", "csr-edge", "row-walk", "blocked" or
+    "none") and the integers the form has: V (elements per load), W, epw / nslab, slab_rows."""
     buf = ctypes.create_string_buffer(128)
-    n = lib.gespmm_describe_sddmm(1 if csr else 0, int(M), int(nnz), int(N), int(d1_align), int(d2_align), 1 if capturing else 0, buf, 128)
+    f, name = (lib.gespmm_describe_sddmm_x16, "gespmm_describe_sddmm_x16") if x16 else (lib.gespmm_describe_sddmm, "gespmm_describe_sddmm")
+    n = f(1 if csr else 0, int(M), int(nnz), int(N), int(d1_align), int(d2_align), 1 if capturing else 0, buf, 128)
     if n < 0:
-        raise GespmmError(n, "gespmm_describe_sddmm")
+        raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k == "form" else int(v)) for k, v in out.items()}
 

@@ -604,17 +604,44 @@ int gespmm_sddmm_csr_f32(const int32_t* rowptr, const int32_t* colind, const flo
                                      reinterpret_cast<hipStream_t>(stream));
 }
 
-int gespmm_describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing, char* out,
-                          int64_t capacity) {
+// 16-bit operands (fp16 / bf16 D1 and D2, fp32 out): the checks of the two entry points above, in their order, with the dtype
+// among the arguments that must make sense and D1 / D2 on 2-byte boundaries.
+static bool sddmm_x16_dtype(int dtype) { return dtype == GESPMM_X16_F16 || dtype == GESPMM_X16_BF16; }
+
+int gespmm_sddmm_coo_x16(const int32_t* rowind, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype,
+                         int64_t nnz, int64_t N, void* stream) {
+    if (nnz < 0 || N < 0 || !sddmm_x16_dtype(dtype)) return GESPMM_EINVAL;
+    if (nnz > gespmm::kSddmmMaxNnz || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    if (nnz == 0) return 0;
+    if (!rowind || !colind || !out || (N > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
+    if (!aligned_to(rowind, 4) || !aligned_to(colind, 4) || !aligned_to(D1, 2) || !aligned_to(D2, 2) || !aligned_to(out, 4))
+        return GESPMM_EALIGN;
+    return (int)gespmm::launch_sddmm_x16(rowind, false, colind, D1, D2, out, dtype, 0, nnz, N, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_sddmm_csr_x16(const int32_t* rowptr, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype,
+                         int64_t M, int64_t nnz, int64_t N, void* stream) {
+    if (M < 0 || nnz < 0 || N < 0 || !sddmm_x16_dtype(dtype)) return GESPMM_EINVAL;
+    if (M > 0x7fffffffLL - 1 || nnz > gespmm::kSddmmMaxNnz || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
+    if (nnz == 0) return 0;
+    if (!rowptr || !colind || !out || (N > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
+    if (!aligned_to(rowptr, 4) || !aligned_to(colind, 4) || !aligned_to(D1, 2) || !aligned_to(D2, 2) || !aligned_to(out, 4))
+        return GESPMM_EALIGN;
+    return (int)gespmm::launch_sddmm_x16(rowptr, true, colind, D1, D2, out, dtype, M, nnz, N, reinterpret_cast<hipStream_t>(stream));
+}
+
+static int describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing, char* out,
+                          int64_t capacity, int elem_size) {
     if (!out || capacity <= 0 || M < 0 || nnz < 0 || N < 0) return GESPMM_EINVAL;
-    if (d1_align < 4 || d2_align < 4 || (d1_align & (d1_align - 1)) != 0 || (d2_align & (d2_align - 1)) != 0) return GESPMM_EINVAL;
+    if (d1_align < elem_size || d2_align < elem_size || (d1_align & (d1_align - 1)) != 0 || (d2_align & (d2_align - 1)) != 0)
+        return GESPMM_EINVAL;
     if (M > 0x7fffffffLL - 1 || nnz > gespmm::kSddmmMaxNnz || N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
     int n;
     if (nnz == 0) {
         n = snprintf(out, (size_t)capacity, "form=none");
     } else {
         const gespmm::SddmmLaunch r = gespmm::resolve_sddmm(csr != 0, M, nnz, N, d1_align > 16 ? 16 : d1_align,
-                                                           d2_align > 16 ? 16 : d2_align, capturing != 0);
+                                                           d2_align > 16 ? 16 : d2_align, capturing != 0, elem_size);
         if (r.form == gespmm::kSddmmBlocked)
             n = snprintf(out, (size_t)capacity, "form=blocked V=%d W=%d nslab=%lld slab_rows=%lld", r.V, r.W, (long long)r.nslab,
                          (long long)r.slab_rows);
@@ -626,6 +653,16 @@ int gespmm_describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_ali
     }
     if (n < 0) return GESPMM_EINVAL;
     return n < capacity ? n : (int)capacity - 1;
+}
+
+int gespmm_describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing, char* out,
+                          int64_t capacity) {
+    return describe_sddmm(csr, M, nnz, N, d1_align, d2_align, capturing, out, capacity, 4);
+}
+
+int gespmm_describe_sddmm_x16(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing, char* out,
+                              int64_t capacity) {
+    return describe_sddmm(csr, M, nnz, N, d1_align, d2_align, capturing, out, capacity, 2);
 }
 
 int gespmm_baseline_atomic_scatter_f32(const int32_t* rowptr, const int32_t* colind, const float* in, float* out,

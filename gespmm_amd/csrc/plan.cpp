@@ -1177,16 +1177,27 @@ int gespmm_plan_tune(gespmm_plan* p, const float* B, float* C, int64_t N, int32_
 // caller's edge order). A clustered plan walks the edges in its own order — the rows of D2 that neighbouring rows share
 // are then found in L2, as in the SpMM — and scatters the results back; each dot product is the same lane butterfly as in
 // gespmm_sddmm_{coo,csr}_f32, so the bits are the same.
-int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, float* out, int64_t N, void* stream) {
-    // the checks of gespmm_sddmm_{coo,csr}_f32, in their order (routes 1 and 2 launch without passing through them)
+// dtype: 0 fp32 operands, GESPMM_X16_F16 / GESPMM_X16_BF16 16-bit ones (gespmm_plan_sddmm_x16) — the routes, the buffers the plan keeps for
+// them (row ids, edge maps, the fp32 temporary: `out` is fp32 either way) and the order of the checks are the same.
+static int plan_sddmm(gespmm_plan* p, const void* D1, const void* D2, float* out, int dtype, int64_t N, void* stream) {
+    // the checks of gespmm_sddmm_{coo,csr}_{f32,x16}, in their order (routes 1 and 2 launch without passing through them)
     if (!p || N < 0) return GESPMM_EINVAL;
+    if (dtype != 0 && dtype != GESPMM_X16_F16 && dtype != GESPMM_X16_BF16) return GESPMM_EINVAL;
     if (N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
     if (p->nnz > gespmm::kSddmmMaxNnz) return GESPMM_ERANGE;
     if (p->nnz == 0) return 0;
     if (!out || (N > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
-    for (const void* q : {(const void*)D1, (const void*)D2, (const void*)out})
-        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const uintptr_t operand_align = dtype == 0 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(D1) % operand_align != 0 || reinterpret_cast<uintptr_t>(D2) % operand_align != 0 ||
+        reinterpret_cast<uintptr_t>(out) % 4 != 0)
+        return GESPMM_EALIGN;
+    // the one launch all three routes make: the stateless library's, for the operand type
+    auto launch = [&](const int32_t* rows, bool csr, const int32_t* cols, float* dst) {
+        if (dtype == 0)
+            return gespmm::launch_sddmm(rows, csr, cols, static_cast<const float*>(D1), static_cast<const float*>(D2), dst, p->M, p->nnz, N, st);
+        return gespmm::launch_sddmm_x16(rows, csr, cols, D1, D2, dst, dtype, p->M, p->nnz, N, st);
+    };
     // which form: sddmm_route (plan_policy.cpp) — 0 CSR call, 1 COO on row ids expanded ONCE (same lane butterfly per edge, same
     // bits), 2 the plan's clustered edge order + scatter
     hipError_t e = hipSuccess;
@@ -1206,9 +1217,10 @@ int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, floa
                 }
                 p->d_coo_row_storage = rows;
             }
-            return (int)gespmm::launch_sddmm(p->d_coo_row_storage, false, p->colind, D1, D2, out, p->M, p->nnz, N, st);
+            return (int)launch(p->d_coo_row_storage, false, p->colind, out);
         }
-        return gespmm_sddmm_csr_f32(p->rowptr, p->colind, D1, D2, out, p->M, p->nnz, N, stream);
+        if (dtype == 0) return gespmm_sddmm_csr_f32(p->rowptr, p->colind, static_cast<const float*>(D1), static_cast<const float*>(D2), out, p->M, p->nnz, N, stream);
+        return gespmm_sddmm_csr_x16(p->rowptr, p->colind, D1, D2, out, dtype, p->M, p->nnz, N, stream);
     }
     if (!p->d_coo_row) {
         const size_t bytes = (size_t)p->nnz * 4;
@@ -1233,11 +1245,20 @@ int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, floa
         p->d_edge_dst = dst;
         p->d_sddmm_tmp = tmp;
     }
-    e = gespmm::launch_sddmm(p->d_coo_row, false, p->d_colind, D1, D2, p->d_sddmm_tmp, p->M, p->nnz, N, st);
+    e = launch(p->d_coo_row, false, p->d_colind, p->d_sddmm_tmp);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(scatter_by_index_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->d_sddmm_tmp,
                        p->d_edge_dst, out, (int)p->nnz);
     return (int)hipGetLastError();
+}
+
+int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, float* out, int64_t N, void* stream) {
+    return plan_sddmm(p, D1, D2, out, 0, N, stream);
+}
+
+int gespmm_plan_sddmm_x16(gespmm_plan* p, const void* D1, const void* D2, float* out, int dtype, int64_t N, void* stream) {
+    if (dtype != GESPMM_X16_F16 && dtype != GESPMM_X16_BF16) return GESPMM_EINVAL;
+    return plan_sddmm(p, D1, D2, out, dtype, N, stream);
 }
 
 int gespmm_plan_sddmm_route(const gespmm_plan* p, int64_t N) {

@@ -222,15 +222,17 @@ int resolve_geometry(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, 
 // small to block (profiles/r01/sddmm_heuristic_audit.log).
 constexpr int64_t kSddmmRowWalkMinDegree = 64;
 
-SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, bool capturing) {
-    SddmmLaunch r = {csr ? kSddmmCsrEdge : kSddmmCooEdge, 4, 4, 0, 0, 0};
-    while (r.V > 1 && ((N % r.V) != 0 || (d1_align % (4 * r.V)) != 0 || (d2_align % (4 * r.V)) != 0)) r.V >>= 1;
-    // Lanes per edge: a lane walks ~2 dwordx4 vectors (8 scalars when the rows allow no vector loads)
+SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, bool capturing, int elem_size) {
+    const int64_t es = elem_size;  // 4: fp32; 2: fp16 / bf16 — V counts elements, the rules below are about bytes
+    SddmmLaunch r = {csr ? kSddmmCsrEdge : kSddmmCooEdge, (int)(16 / es), 4, 0, 0, 0};
+    while (r.V > 1 && ((N % r.V) != 0 || (d1_align % (es * r.V)) != 0 || (d2_align % (es * r.V)) != 0)) r.V >>= 1;
+    // Lanes per edge: a lane walks ~2 dwordx4 vectors (~32 bytes, at most 8 loads: 8 scalars when the rows allow no vector loads)
     // of both rows, so a wavefront has 64/W edges in flight and the butterfly is log2(W) steps.
     // Measured against "just enough lanes to cover N" (profiles/r01/sddmm_group_width.log):
     // N=41 2.4-2.8x, N=64 1.35x, N=128 1.2x faster on reddit-like, equal or better on com-Amazon-like.
     // Every form uses the same width, so COO, CSR and the cache-blocked form agree bit for bit.
-    const int64_t per_lane = (r.V == 4) ? 2 : (r.V == 2) ? 4 : 8;
+    // (fp32: 2 / 4 / 8 vectors for V = 4 / 2 / 1; 16 bits: 2 / 4 / 8 / 8 for V = 8 / 4 / 2 / 1 — carried over, not measured at 16 bits)
+    const int64_t per_lane = (32 / (es * r.V) < 8) ? 32 / (es * r.V) : 8;
     while (r.W < 64 && (int64_t)r.W * r.V * per_lane < N) r.W <<= 1;
     const int G = 64 / r.W;
     if (csr && M > 0) {
@@ -239,14 +241,14 @@ SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_al
         // the slab count (columns past M land in the last slab — fewer hits, same result). Needs a
         // stream-ordered temporary for the split points, so not on a stream under capture.
         const int64_t avg_deg = nnz / M;
-        int64_t slab_rows = (6 << 20) / (N * 4 > 0 ? N * 4 : 4);  // 3..6 MB measured best (sddmm_slab.log)
+        int64_t slab_rows = (6 << 20) / (N * es > 0 ? N * es : es);  // 3..6 MB measured best (sddmm_slab.log)
         if (slab_rows < 64) slab_rows = 64;
         const int64_t nslab = (M + slab_rows - 1) / slab_rows;
         // (the edges of a row that fall into one slab must still gather >= ~4.5 KB of D2: with less the per-row
         // overhead of 'nslab' launches outweighs the L2 hits —
         // profiles/r01/sddmm_heuristic_audit.log; M = 10^6, degree 100, 41 slabs was 4.5x slower than streaming)
-        if (!capturing && N * 4 >= 256 && nslab >= 4 && nslab <= 4096 && avg_deg >= 64 &&
-            avg_deg * N * 4 >= 4608 * nslab) {
+        if (!capturing && N * es >= 256 && nslab >= 4 && nslab <= 4096 && avg_deg >= 64 &&
+            avg_deg * N * es >= 4608 * nslab) {
             r.form = kSddmmBlocked;
             r.nslab = nslab;
             r.slab_rows = slab_rows;

@@ -30,12 +30,13 @@ enum SddmmForm {
 };
 struct SddmmLaunch {
     int form;           // SddmmForm
-    int V, W;           // floats per load, lanes per edge: these two fix the summation order
+    int V, W;           // elements per load, lanes per edge: these two fix the summation order
     int epw;            // edges per wavefront of the edge-parallel forms (0 for the row-walking ones)
     int64_t nslab;      // blocked form: launches; else 0
     int64_t slab_rows;  // blocked form: D2 rows per slab; else 0
 };
 // d1_align / d2_align: largest power of two (bytes) that divides the operand's address, 16 is as good as more.
-SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, bool capturing);
+// elem_size: bytes per element of D1 / D2 — 4 (fp32) or 2 (fp16 / bf16: V up to 8, every byte threshold at half the width).
+SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, bool capturing, int elem_size = 4);
 
 }  // namespace gespmm

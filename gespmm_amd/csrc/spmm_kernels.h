@@ -269,7 +269,7 @@ hipError_t device_records_set_values(const RecordTables& t, int64_t M, const int
 void free_records(RecordTables* t);
 hipError_t launch_spmm_records(const RecordTables& t, const float* B, float* C, int64_t N, int flags, const LaunchGuard* guard, hipStream_t st);
 
-// sddmm_kernels.hip
+// sddmm_kernels.hip (fp32 operands), sddmm_x16.hip (fp16 / bf16 operands); the kernels of both: sddmm_edge.h
 // Most edges one SDDMM call takes. The kernels count edges in 32-bit registers: the first edge of a wavefront is
 // (block * kWaves + wave) * per_wave and its end that plus per_wave (<= 256), both formed before they are compared with nnz, for
 // every wavefront of the last workgroup — up to kWaves * 256 edges past nnz. 4096 keeps all of them below 2^31 (the SpMM entry
@@ -278,6 +278,10 @@ constexpr int64_t kSddmmMaxNnz = 0x7fffffffLL - 4096;
 hipError_t launch_sddmm(const int32_t* rowind_or_rowptr, bool csr, const int32_t* colind,
                         const float* D1, const float* D2, float* out,
                         int64_t M, int64_t nnz, int64_t N, hipStream_t st);
+// ... on 16-bit operands (dtype kX16F16 / kX16Bf16, D1 and D2 2-byte aligned; out stays fp32): the same decision — resolve_sddmm, at
+// element size 2 — and the same kernels
+hipError_t launch_sddmm_x16(const int32_t* rowind_or_rowptr, bool csr, const int32_t* colind, const void* D1, const void* D2,
+                            float* out, int dtype, int64_t M, int64_t nnz, int64_t N, hipStream_t st);
 // split[(nslab+1)][M]: per-row forward-scan split points of the column slabs (spmm_kernels.hip)
 hipError_t launch_slabplan(const int32_t* rowptr, const int32_t* colind, int32_t* split, int M, int nslab,
                            int slab_rows, hipStream_t st);

@@ -162,23 +162,34 @@ torch::Tensor sddmm_impl(const torch::Tensor& idx0, const char* name0, bool csr,
                          const torch::Tensor& D1, const torch::Tensor& D2) {
     need(idx0, name0, torch::kInt32, 1);
     need(colind, "colind", torch::kInt32, 1);
-    need(D1, "D1", torch::kFloat32, 2);
-    need(D2, "D2", torch::kFloat32, 2);
+    const int x16 = need_dense(D1, "D1");  // fp32, or both operands fp16 / both bf16 (gespmm_sddmm_*_x16); out is fp32 either way
+    need(D2, "D2", D1.scalar_type(), 2);
     TORCH_CHECK_VALUE(D1.size(1) == D2.size(1), "D1 and D2 must have the same number of columns");
     same_device(D1, D2);
     same_device(D1, idx0);
     same_device(D1, colind);
     const int64_t nnz = colind.numel(), N = D1.size(1);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(D1.device());
-    auto out = torch::empty({nnz}, D1.options());
+    auto out = torch::empty({nnz}, D1.options().dtype(torch::kFloat32));
     if (csr) {
+        TORCH_CHECK_VALUE(idx0.numel() == D1.size(0) + 1, "rowptr must have D1.size(0)+1 entries");
+    } else {
+        TORCH_CHECK_VALUE(idx0.numel() == nnz, "rowind and colind must have the same length");
+    }
+    if (x16 && csr) {
+        check_rc(gespmm_sddmm_csr_x16(idx0.data_ptr<int32_t>(), colind.data_ptr<int32_t>(), D1.data_ptr(), D2.data_ptr(), out.data_ptr<float>(),
+                                      x16, D1.size(0), nnz, N, current_stream(D1)),
+                 "gespmm_sddmm_csr_x16");
+    } else if (x16) {
+        check_rc(gespmm_sddmm_coo_x16(idx0.data_ptr<int32_t>(), colind.data_ptr<int32_t>(), D1.data_ptr(), D2.data_ptr(), out.data_ptr<float>(),
+                                      x16, nnz, N, current_stream(D1)),
+                 "gespmm_sddmm_coo_x16");
+    } else if (csr) {
         const int64_t M = D1.size(0);
-        TORCH_CHECK_VALUE(idx0.numel() == M + 1, "rowptr must have D1.size(0)+1 entries");
         check_rc(gespmm_sddmm_csr_f32(idx0.data_ptr<int32_t>(), colind.data_ptr<int32_t>(), D1.data_ptr<float>(),
                                       D2.data_ptr<float>(), out.data_ptr<float>(), M, nnz, N, current_stream(D1)),
                  "gespmm_sddmm_csr_f32");
     } else {
-        TORCH_CHECK_VALUE(idx0.numel() == nnz, "rowind and colind must have the same length");
         check_rc(gespmm_sddmm_coo_f32(idx0.data_ptr<int32_t>(), colind.data_ptr<int32_t>(), D1.data_ptr<float>(),
                                       D2.data_ptr<float>(), out.data_ptr<float>(), nnz, N, current_stream(D1)),
                  "gespmm_sddmm_coo_f32");
@@ -255,12 +266,18 @@ torch::Tensor plan_spmm_fused(int64_t handle, const torch::Tensor& dense, const 
 }
 
 torch::Tensor plan_sddmm(int64_t handle, const torch::Tensor& D1, const torch::Tensor& D2, int64_t nnz) {
-    need(D1, "D1", torch::kFloat32, 2);
-    need(D2, "D2", torch::kFloat32, 2);
+    const int x16 = need_dense(D1, "D1");
+    need(D2, "D2", D1.scalar_type(), 2);
     TORCH_CHECK_VALUE(D1.size(1) == D2.size(1), "D1 and D2 must have the same number of columns");
     same_device(D1, D2);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(D1.device());
-    auto out = torch::empty({nnz}, D1.options());
+    auto out = torch::empty({nnz}, D1.options().dtype(torch::kFloat32));
+    if (x16) {
+        check_rc(gespmm_plan_sddmm_x16(reinterpret_cast<gespmm_plan*>(handle), D1.data_ptr(), D2.data_ptr(), out.data_ptr<float>(), x16,
+                                       D1.size(1), current_stream(D1)),
+                 "gespmm_plan_sddmm_x16");
+        return out;
+    }
     check_rc(gespmm_plan_sddmm_f32(reinterpret_cast<gespmm_plan*>(handle), D1.data_ptr<float>(), D2.data_ptr<float>(),
                                    out.data_ptr<float>(), D1.size(1), current_stream(D1)),
              "gespmm_plan_sddmm_f32");

@@ -35,8 +35,9 @@ backward, and the same output bits. It works with ``cached=True`` (plans) and wi
 16-bit features (extension): ``SPMMFunction`` takes ``feat`` of ``torch.float16`` / ``torch.bfloat16`` (a ``.half()`` / ``.bfloat16()``
 model, or ``torch.autocast``) and runs forward and backward on the 16-bit product (``spmm.csr_spmm`` with a 16-bit ``dense``: fp32 sum,
 one rounding; ``grad_out`` arrives in the forward's dtype); edge weights stay fp32. GCNConv casts its two scaling vectors to the dtype
-of ``x @ W`` so that the product stays 16-bit. fp32 only, with a TypeError otherwise: ``need_edge_grad=True`` (SDDMM), ``fused=True``
-and ``tune_plans=True``.
+of ``x @ W`` so that the product stays 16-bit. fp32 only, with a TypeError otherwise: ``need_edge_grad=True``, ``fused=True``
+and ``tune_plans=True``. The edge-weight gradient of a 16-bit model is one call away all the same:
+``sddmm.csr_sddmm(rowptr, colind, grad_out, feat)`` takes fp16 / bf16 tensors as they are and returns the fp32 gradient.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -58,7 +59,8 @@ class SPMMFunction(torch.autograd.Function):
         fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
         ctx.fwd_plan = fwd_plan
         if need_edge_grad and feat.dtype != torch.float32:
-            raise TypeError("need_edge_grad=True needs torch.float32 feat (the SDDMM ops are fp32 only), got %s" % feat.dtype)
+            raise TypeError("need_edge_grad=True needs torch.float32 feat, got %s: on 16-bit tensors sddmm.csr_sddmm(rowptr, colind, grad_out, feat) "
+                            "computes the (fp32) edge-weight gradient" % feat.dtype)
         if edge_weight_csr is None:
             out = _spmm.csr_spmm_no_edge_value(rowptr, colind, feat, plan=fwd_plan)
         else:

@@ -5,36 +5,46 @@
 
 out[e] = <D1[row(e), :], D2[col(e), :]> in pattern order (sddmm.cu:7-424). As in the
 reference the feature width is D1.size(1) and, for the CSR form, M = D1.size(0).
+
+16-bit operands (extension): D1 and D2 may both be ``torch.float16`` or both ``torch.bfloat16`` (gespmm_sddmm_{coo,csr}_x16,
+gespmm_plan_sddmm_x16: 16-bit kernels at every width and alignment, nothing is widened in memory). The result stays
+``torch.float32[nnz]`` — edge values are fp32 everywhere in this package, so it feeds ``spmm.csr_spmm``'s ``values`` as it is — and
+``csr_sddmm(rowptr, colind, grad_out, feat)`` is the edge-weight gradient of a ``.half()`` / ``.bfloat16()`` / autocast model, which
+``SPMMFunction(need_edge_grad=True)`` does not compute. Mixed dtypes raise TypeError.
 """
 import torch
 
 from ._ext import ext as _ext
 from ._lib import check, lib
-from .spmm import _need, _on_device, _ptr, _same_device, _stream
+from .spmm import _need, _need_dense, _on_device, _ptr, _same_device, _stream
 
 
 def _checked(idx0, name0, colind, D1, D2):
+    """-> (device, GESPMM_X16_* code of the operands or 0 for fp32)"""
     _need(idx0, name0, torch.int32, 1)
     _need(colind, "colind", torch.int32, 1)
-    _need(D1, "D1", torch.float32, 2)
-    _need(D2, "D2", torch.float32, 2)
+    x16 = _need_dense(D1, "D1")
+    _need(D2, "D2", D1.dtype, 2)
     if D1.shape[1] != D2.shape[1]:
         raise ValueError("D1 and D2 must have the same number of columns")
-    return _same_device(D1, D2, idx0, colind)
+    return _same_device(D1, D2, idx0, colind), x16
 
 
 def coo_sddmm(rowind, colind, D1, D2):
     if _ext is not None:
         return _ext.coo_sddmm(rowind, colind, D1, D2)
-    dev = _checked(rowind, "rowind", colind, D1, D2)
+    dev, x16 = _checked(rowind, "rowind", colind, D1, D2)
     nnz = rowind.numel()
     if colind.numel() != nnz:
         raise ValueError("rowind and colind must have the same length")
     out = torch.empty((nnz,), dtype=torch.float32, device=dev)
     with _on_device(dev):
-        rc = lib.gespmm_sddmm_coo_f32(_ptr(rowind), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), nnz,
-                                      D1.shape[1], _stream(dev))
-    check(rc, "gespmm_sddmm_coo_f32")
+        if x16:
+            rc = lib.gespmm_sddmm_coo_x16(_ptr(rowind), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), x16, nnz, D1.shape[1], _stream(dev))
+        else:
+            rc = lib.gespmm_sddmm_coo_f32(_ptr(rowind), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), nnz,
+                                          D1.shape[1], _stream(dev))
+    check(rc, "gespmm_sddmm_coo_x16" if x16 else "gespmm_sddmm_coo_f32")
     return out
 
 
@@ -42,7 +52,7 @@ def csr_sddmm(rowptr, colind, D1, D2, plan=None):
     """``plan``: a ``spmm.SpmmPlan`` of the same pattern — a clustered plan walks the edges in its own order (rows of D2
     shared by neighbouring rows come from L2) and returns the same bits in the caller's edge order."""
     if plan is not None:
-        dev = _checked(rowptr, "rowptr", colind, D1, D2)
+        dev, x16 = _checked(rowptr, "rowptr", colind, D1, D2)
         if (rowptr.data_ptr(), colind.data_ptr()) != (plan._rowptr.data_ptr(), plan._colind.data_ptr()) or \
                 (rowptr._version, colind._version) != plan._pattern_version:
             raise ValueError("the plan was made for a different (or since modified) pattern")
@@ -52,19 +62,25 @@ def csr_sddmm(rowptr, colind, D1, D2, plan=None):
             return _ext.plan_sddmm(plan._handle.value, D1, D2, colind.numel())
         out = torch.empty((colind.numel(),), dtype=torch.float32, device=dev)
         with _on_device(dev):
-            rc = lib.gespmm_plan_sddmm_f32(plan._handle, _ptr(D1), _ptr(D2), _ptr(out), D1.shape[1], _stream(dev))
-        check(rc, "gespmm_plan_sddmm_f32")
+            if x16:
+                rc = lib.gespmm_plan_sddmm_x16(plan._handle, _ptr(D1), _ptr(D2), _ptr(out), x16, D1.shape[1], _stream(dev))
+            else:
+                rc = lib.gespmm_plan_sddmm_f32(plan._handle, _ptr(D1), _ptr(D2), _ptr(out), D1.shape[1], _stream(dev))
+        check(rc, "gespmm_plan_sddmm_x16" if x16 else "gespmm_plan_sddmm_f32")
         return out
     if _ext is not None:
         return _ext.csr_sddmm(rowptr, colind, D1, D2)
-    dev = _checked(rowptr, "rowptr", colind, D1, D2)
+    dev, x16 = _checked(rowptr, "rowptr", colind, D1, D2)
     M = D1.shape[0]
     if rowptr.numel() != M + 1:
         raise ValueError("rowptr must have D1.size(0)+1 entries")
     nnz = colind.numel()
     out = torch.empty((nnz,), dtype=torch.float32, device=dev)
     with _on_device(dev):
-        rc = lib.gespmm_sddmm_csr_f32(_ptr(rowptr), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), M, nnz,
-                                      D1.shape[1], _stream(dev))
-    check(rc, "gespmm_sddmm_csr_f32")
+        if x16:
+            rc = lib.gespmm_sddmm_csr_x16(_ptr(rowptr), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), x16, M, nnz, D1.shape[1], _stream(dev))
+        else:
+            rc = lib.gespmm_sddmm_csr_f32(_ptr(rowptr), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), M, nnz,
+                                          D1.shape[1], _stream(dev))
+    check(rc, "gespmm_sddmm_csr_x16" if x16 else "gespmm_sddmm_csr_f32")
     return out

@@ -17,7 +17,8 @@ library's choice.
 16-bit operands: ``csr_spmm``, ``csr_spmm_no_edge_value`` and ``SpmmPlan.run`` also take ``dense`` of ``torch.float16`` /
 ``torch.bfloat16`` and return that dtype (gespmm_csr_spmm_x16 / gespmm_plan_spmm_x16: the sum is fp32 and is rounded once, so the result
 has the bits of ``op(dense.float()).to(dense.dtype)``). ``values`` stay fp32, ``out=`` must have the dtype of ``dense``, ``cfg=`` needs
-fp32. ``csr_spmm_fused``, ``csr_spmm_max`` / ``reduce_max=``, ``SpmmPlan.tune`` and the SDDMM ops are fp32 only.
+fp32. ``csr_spmm_fused``, ``csr_spmm_max`` / ``reduce_max=`` and ``SpmmPlan.tune`` are fp32 only. The SDDMM ops (``sddmm.py``) take fp16 / bf16
+operands too and return fp32: ``sddmm.csr_sddmm(rowptr, colind, grad_out, feat)`` is the edge-weight gradient of a 16-bit model.
 """
 import ctypes
 

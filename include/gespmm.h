@@ -254,6 +254,31 @@ int gespmm_describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_ali
                           char* out, int64_t capacity);
 
 /*
+ * SDDMM on 16-bit dense operands (same ABI version): out[e] = sum_j D1[row(e), j] * D2[col(e), j] with D1 [M x N] and D2 [K x N]
+ * row-major IEEE fp16 (GESPMM_X16_F16) or bfloat16 (GESPMM_X16_BF16), both of the same type; out[nnz] is FP32 and is not narrowed
+ * (edge values are fp32 everywhere in this library: out feeds the `val` of the products directly). Every element is widened
+ * exactly (subnormals included) and the sum is the lane formula above in fp32: per edge W lanes each run ONE fmaf chain, from 0,
+ * over the elements j = l*V + t*W*V + i, then the xor butterfly over masks W/2 .. 1, lane 0's sum is out[e]. No dot2 and no
+ * packed-fp16 arithmetic. The product of two fp16 or two bf16 numbers is exact in fp32, so the result depends on (V, W) alone, and
+ * V counts ELEMENTS here: the widest of 8, 4, 2, 1 that divides N and whose 2*V bytes divide both operand addresses; W the smallest
+ * power of two in 4..64 with W * V * (2, 4, 8, 8 for V = 8, 4, 2, 1) >= N (64 beyond). This is the fp32 geometry at half the byte
+ * width — N = 128 is (8, 8), not the fp32 call's (4, 16) — so the order, and with it the last bits, DIFFER from
+ * gespmm_sddmm_*_f32 on the widened operands wherever (V, W) differ: SDDMM's order is pinned by the formula, not by the fp32 call.
+ * Every N and every 2-byte aligned address runs a 16-bit kernel (there is no widening pass and no temporary beyond the blocked
+ * form's split points); the forms and their thresholds are those of the fp32 calls with the row bytes taken as 2 N. Checks, in
+ * the order of the fp32 entry points and before any device work: negative sizes or a dtype other than the two -> GESPMM_EINVAL;
+ * sizes out of range -> GESPMM_ERANGE; nnz == 0 -> 0; NULL pointers -> GESPMM_EINVAL; D1 / D2 off a 2-byte boundary (index
+ * arrays and out: 4-byte) -> GESPMM_EALIGN. gespmm_describe_sddmm_x16: as gespmm_describe_sddmm, alignments powers of two >= 2.
+ * (GESPMM_X16_F16 = 1, GESPMM_X16_BF16 = 2: defined with gespmm_csr_spmm_x16 below.)
+ */
+int gespmm_sddmm_coo_x16(const int32_t* rowind, const int32_t* colind, const void* D1, const void* D2, float* out,
+                         int dtype, int64_t nnz, int64_t N, void* stream);
+int gespmm_sddmm_csr_x16(const int32_t* rowptr, const int32_t* colind, const void* D1, const void* D2, float* out,
+                         int dtype, int64_t M, int64_t nnz, int64_t N, void* stream);
+int gespmm_describe_sddmm_x16(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing,
+                              char* out, int64_t capacity);
+
+/*
  * CSR (M x K) -> CSC on the device: fills colptr[K+1], rowind[nnz] and, when
  * csr_val != NULL, csc_val[nnz]. Entries inside one column keep ascending row
  * order (stable), which is what makes backward SpMM on the CSC arrays
@@ -431,6 +456,9 @@ int gespmm_plan_spmm_max_f32(gespmm_plan* plan, const float* B, float* C, int64_
  * plan whose order is modelled to hit L2 walks the edges in its own order (shared rows of D2 come from L2) and scatters the
  * results back; otherwise the call is gespmm_sddmm_csr_f32 on the arrays the plan was made from (keep them alive). */
 int gespmm_plan_sddmm_f32(gespmm_plan* plan, const float* D1, const float* D2, float* out, int64_t N, void* stream);
+/* ... on 16-bit operands (gespmm_sddmm_csr_x16's bits): the same three routes, decided by the same rule (gespmm_plan_sddmm_route),
+ * on the same row ids / edge maps / fp32 temporary the plan keeps for the fp32 call. */
+int gespmm_plan_sddmm_x16(gespmm_plan* plan, const void* D1, const void* D2, float* out, int dtype, int64_t N, void* stream);
 /* host only (since 0.5): which way the call above goes at width N. 0 gespmm_sddmm_csr_f32 on the caller's arrays, 1 the COO form on row
  * ids the plan expands once, 2 the plan's clustered edge order + a scatter into the caller's order. */
 int gespmm_plan_sddmm_route(const gespmm_plan* plan, int64_t N);
