@@ -97,6 +97,10 @@ EXPORTS = [
     "gespmm_sddmm_csr_x16",
     "gespmm_plan_sddmm_x16",
     "gespmm_describe_sddmm_x16",
+    "gespmm_csr_spmm_heads_f32",
+    "gespmm_plan_spmm_heads_f32",
+    "gespmm_heads_route",
+    "gespmm_plan_heads_route",
 ]
 
 X16_F16 = 1
@@ -240,6 +244,14 @@ def _load():
     lib.gespmm_x16_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int]
     lib.gespmm_plan_x16_route.restype = c_int
     lib.gespmm_plan_x16_route.argtypes = [p, c_int64, c_int, c_int]
+    lib.gespmm_csr_spmm_heads_f32.restype = c_int
+    lib.gespmm_csr_spmm_heads_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_int64, p]
+    lib.gespmm_plan_spmm_heads_f32.restype = c_int
+    lib.gespmm_plan_spmm_heads_f32.argtypes = [p, p, p, p, c_int64, c_int64, p]
+    lib.gespmm_heads_route.restype = c_int
+    lib.gespmm_heads_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, p]
+    lib.gespmm_plan_heads_route.restype = c_int
+    lib.gespmm_plan_heads_route.argtypes = [p, c_int64, c_int64, c_int, c_int]
     lib.gespmm_plan_fused_route.restype = c_int
     lib.gespmm_plan_fused_route.argtypes = [p, c_int64, c_int, c_int, c_int]
     lib.gespmm_plan_spmm_max_f32.restype = c_int
@@ -327,6 +339,16 @@ def describe_sddmm(csr, M, nnz, N, d1_align=16, d2_align=16, capturing=False, x1
         raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k == "form" else int(v)) for k, v in out.items()}
+
+
+def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):
+    """What gespmm_csr_spmm_heads_f32 would do for these sizes and operand alignments (gespmm_heads_route: host only):
+    ``(route, (V, S, W, rpw))`` — route 1 the heads kernel with that lane geometry, route 0 the per-head composition (zeros)."""
+    geo = (ctypes.c_int32 * 4)()
+    rc = lib.gespmm_heads_route(int(M), int(K), int(H), int(F), int(nnz), int(b_align), int(c_align), geo)
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_heads_route")
+    return rc, tuple(int(x) for x in geo)
 
 
 def init(rows_hint=0, nnz_hint=0, stream=None):

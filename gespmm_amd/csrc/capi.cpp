@@ -10,12 +10,14 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/gespmm.h"
 #include "select.h"
 #include "auto_plan.h"
 #include "plan.h"
+#include "spmm_heads.h"
 #include "spmm_kernels.h"
 #include "workspace.h"
 
@@ -305,6 +307,71 @@ int run_spmm_x16(const int32_t* rowptr, const int32_t* colind, const float* val,
     return (int)launch_spmm_x16(a, dtype, sel.geo, seg, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- the multi-head product (gespmm.h: gespmm_csr_spmm_heads_f32). The argument checks of both entry points, no device work.
+int check_heads_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz) {
+    if (H < 1 || M < 0 || K < 0 || F < 0 || nnz < 0) return GESPMM_EINVAL;
+    if (M > 0x7fffffffLL - 64 || K > 0x7fffffffLL || H > 0x7fffffffLL / 4 || F > (0x7fffffffLL / 4) / H || nnz > 0x7fffffffLL - 4096)
+        return GESPMM_ERANGE;  // (H F, the width, within what the other entries take as N)
+    return 0;
+}
+
+int check_heads_args(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const float* C, int64_t M, int64_t K,
+                     int64_t H, int64_t F, int64_t nnz) {
+    const int rc = check_heads_sizes(M, K, H, F, nnz);
+    if (rc != 0) return rc;
+    if (M == 0 || F == 0) return 0;
+    if (!rowptr || !C) return GESPMM_EINVAL;
+    if ((nnz != 0) && (!colind || !B || !val)) return GESPMM_EINVAL;
+    if (!aligned_to(rowptr, 4) || !aligned_to(colind, 4) || !aligned_to(val, 4) || !aligned_to(B, 4) || !aligned_to(C, 4)) return GESPMM_EALIGN;
+    return 0;
+}
+
+// The multi-head counterpart of run_spmm_x16: ONE heads kernel or nothing (kHeadsUnavailable: the caller composes per head). The geometry
+// is what the selector resolves for width N = H F with the batch-stream kernel forced, strict order and no cache blocking; V is limited
+// to what divides F (a lane's vector stays inside one head) and to what B and C can be addressed with.
+int run_spmm_heads(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, float* C, int64_t M, int64_t K, int64_t H,
+                   int64_t F, int64_t nnz, int variant, int flags, void* stream, const PlanLaunch* pl, int b_align, int c_align, bool dry_run,
+                   int* kind, Geometry* geo_out) {
+    *kind = 0;
+    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    if (H < 2 || H > kHeadsMax || M <= 0 || F <= 0 || nnz < 0 || b_align < 4 || c_align < 4) return kHeadsUnavailable;
+    // GESPMM_HEADS_ROUTE=composition pins route 0 (read per call: scripts/heads_timing.py measures both routes in one process)
+    if (const char* env = getenv("GESPMM_HEADS_ROUTE"))
+        if (!strcmp(env, "composition")) return kHeadsUnavailable;
+    const int64_t N = H * F;
+    if ((uint64_t)K * (uint64_t)N * 4ull >= (1ull << 32) || nnz * H >= (1ll << 31)) return kHeadsUnavailable;  // 32-bit offsets only
+    int max_vec = 4;
+    while (max_vec > 1 && ((F % max_vec) != 0 || b_align < 4 * max_vec || c_align < 4 * max_vec)) max_vec >>= 1;
+    flags |= kFlagBatchStream | kFlagStrictOrder | kFlagNoSlabBlocked;
+    flags &= ~(kFlagSegStream | kFlagSlabBlocked | kFlagSplitLongRows | kFlagAllowReassoc | kFlagForceIdx64);
+    Selection sel;
+    if (resolve_geometry(M, K, N, nnz, variant, max_vec, 0, 0, 0, 0, 0, flags, &sel) != 0) return GESPMM_EINVAL;
+    sel.geo.reduce = kReduceSum;
+    if (sel.variant == GESPMM_VARIANT_NAIVE || sel.variant == GESPMM_VARIANT_PARREDUCE) return kHeadsUnavailable;
+    if (!heads_geometry_served(sel.geo, pl != nullptr)) return kHeadsUnavailable;
+    *kind = 1;
+    if (geo_out) *geo_out = sel.geo;
+    if (dry_run) return 0;
+    if (nnz != 0 && (!val || !colind || !B)) return GESPMM_EINVAL;  // (no entries: the kernel reads none of the three and writes zeros)
+
+    HeadsArgs a = {};
+    a.rowptr = rowptr;
+    a.colind = colind;
+    a.val = val;
+    a.B = B;
+    a.C = C;
+    a.M = (int32_t)M;
+    a.N = (int32_t)N;
+    a.flags = flags;
+    a.rpw = sel.geo.rows_per_wave;
+    a.tasks = pl ? pl->tasks : nullptr;
+    a.perm = pl ? pl->perm : nullptr;
+    a.ntasks = pl ? pl->ntasks : 0;
+    a.H = (int32_t)H;
+    a.F = (int32_t)F;
+    return (int)launch_spmm_heads(a, sel.geo, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // namespace gespmm
 
 namespace {
@@ -423,6 +490,61 @@ int gespmm_x16_route(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, 
     const int rc = gespmm::run_spmm_x16(nullptr, nullptr, nullptr, nullptr, nullptr, GESPMM_X16_BF16, M, K, N, nnz, variant, 0, nullptr, nullptr,
                                         b_align, c_align, true, &kind);
     if (rc != 0 && rc != gespmm::kX16Unavailable) return rc < 0 ? rc : GESPMM_EINVAL;
+    return kind;
+}
+
+// The multi-head product (gespmm.h): the heads kernel where it exists, else the composition — per head, gather the head's weights and
+// its slice of B into stream-ordered temporaries, the strict-order product into a third, scatter that into C. Same bits: each head IS
+// that product. H = 1 is the strict-order product on the caller's arrays.
+int gespmm_csr_spmm_heads_f32(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, float* C, int64_t M,
+                              int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream) {
+    const int rc0 = gespmm::check_heads_args(rowptr, colind, val, B, C, M, K, H, F, nnz);
+    if (rc0 != 0) return rc0;
+    if (M == 0 || F == 0) return 0;
+    int kind = 0;
+    int rc = gespmm::run_spmm_heads(rowptr, colind, val, B, C, M, K, H, F, nnz, GESPMM_VARIANT_AUTO, 0, stream, nullptr,
+                                    gespmm::pointer_alignment(B), gespmm::pointer_alignment(C), false, &kind);
+    if (rc != gespmm::kHeadsUnavailable) return rc;
+    const gespmm_launch_cfg strict = {0, 0, 0, 0, 0, GESPMM_FLAG_STRICT_ORDER};
+    if (H == 1) return run_spmm(rowptr, colind, val, B, C, M, K, F, nnz, GESPMM_VARIANT_AUTO, &strict, gespmm::kReduceSum, 0.0f, stream);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t v_bytes = up((size_t)nnz * 4), b_bytes = up((size_t)K * (size_t)F * 4), c_bytes = (size_t)M * (size_t)F * 4;
+    void* scratch = nullptr;
+    hipError_t e = gespmm::workspace_alloc(&scratch, v_bytes + b_bytes + c_bytes, st);
+    if (e != hipSuccess) return (int)e;
+    float* vh = static_cast<float*>(scratch);
+    float* Bh = reinterpret_cast<float*>(static_cast<char*>(scratch) + v_bytes);
+    float* Ch = reinterpret_cast<float*>(static_cast<char*>(scratch) + v_bytes + b_bytes);
+    const int64_t N = H * F;
+    rc = 0;
+    for (int64_t h = 0; h < H && rc == 0; ++h) {  // (stream order keeps one head's temporaries until its scatter has read them)
+        rc = (int)gespmm::launch_heads_slice(val, vh, nnz, H, h, 1, st);
+        if (rc == 0 && nnz != 0) rc = (int)gespmm::launch_heads_slice(B, Bh, K, N, h * F, F, st);
+        if (rc == 0) rc = run_spmm(rowptr, colind, vh, Bh, Ch, M, K, F, nnz, GESPMM_VARIANT_AUTO, &strict, gespmm::kReduceSum, 0.0f, stream);
+        if (rc == 0) rc = (int)gespmm::launch_heads_unslice(Ch, C, M, N, h * F, F, st);
+    }
+    e = gespmm::workspace_free(scratch, st);
+    if (rc == 0) rc = (int)e;
+    return rc;
+}
+
+int gespmm_heads_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int b_align, int c_align, int32_t* geometry_out) {
+    if (b_align < 1 || c_align < 1) return GESPMM_EINVAL;
+    const int rc0 = gespmm::check_heads_sizes(M, K, H, F, nnz);
+    if (rc0 != 0) return rc0;
+    int kind = 0;
+    gespmm::Geometry geo = {};
+    const int rc = gespmm::run_spmm_heads(nullptr, nullptr, nullptr, nullptr, nullptr, M, K, H, F, nnz, GESPMM_VARIANT_AUTO, 0, nullptr, nullptr,
+                                          b_align, c_align, true, &kind, &geo);
+    if (rc != 0 && rc != gespmm::kHeadsUnavailable) return rc < 0 ? rc : GESPMM_EINVAL;
+    if (geometry_out) {
+        geometry_out[0] = kind ? geo.vec : 0;
+        geometry_out[1] = kind ? geo.strips : 0;
+        geometry_out[2] = kind ? geo.group : 0;
+        geometry_out[3] = kind ? geo.rows_per_wave : 0;
+    }
     return kind;
 }
 

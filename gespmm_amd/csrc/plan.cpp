@@ -44,6 +44,7 @@
 #include "reorder.h"
 #include "select.h"
 #include "spmm_device.h"
+#include "spmm_heads.h"
 #include "spmm_kernels.h"
 
 struct gespmm_plan {
@@ -121,6 +122,13 @@ struct gespmm_plan {
     gespmm::Geometry x16_last_geo = {};
     int64_t x16_last_N = 0;
     int x16_last_dtype = 0;
+    // the multi-head product (gespmm_plan_spmm_heads_f32): the caller's [nnz, H] weights in the plan's entry order, rewritten by every call;
+    // made by the first call on a clustered plan and again when H grows
+    float* d_heads_val = nullptr;  // owner
+    int64_t heads_val_bytes = 0;
+    int heads_last_route = -1;  // what the last multi-head call RAN (-1: none yet), its H and F and the kernel's lane geometry: gespmm_plan_describe
+    gespmm::Geometry heads_last_geo = {};
+    int64_t heads_last_H = 0, heads_last_F = 0;
     bool records_kept_by_policy = false;  // want_record_tables() / keep_record_tables() said yes at creation (else the tables exist only while tune measures them / if they won)
 
     gespmm_plan() = default;
@@ -131,7 +139,7 @@ struct gespmm_plan {
         gespmm::free_staging(&slab);
         gespmm::free_slab_view(&slab_view, false);
         gespmm::free_records(&rec);
-        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp, (void*)d_fused_scratch, (void*)d_x16_b, (void*)d_x16_c})
+        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp, (void*)d_fused_scratch, (void*)d_x16_b, (void*)d_x16_c, (void*)d_heads_val})
             if (q) (void)hipFree(q);
     }
 };
@@ -1066,6 +1074,81 @@ int gespmm_plan_x16_route(const gespmm_plan* plan, int64_t N, int b_align, int c
     return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
 }
 
+// The multi-head product through a plan (gespmm.h). A storage-order plan runs the stateless call on the caller's arrays. A clustered plan
+// permutes the [nnz, H] weights into its own buffer (one copy kernel per call: the weights are an argument, nothing is cached) and runs the
+// plan-mode heads kernel on its batch-stream task table — which every clustered plan owns whatever its scalar route is — or, where that
+// kernel is not served, the stateless composition. `dry`: the answer only.
+static int plan_run_heads(gespmm_plan* p, const float* val, const float* B, float* C, int64_t H, int64_t F, void* stream, bool dry, int b_align,
+                          int c_align, int* route_out) {
+    *route_out = 0;
+    int kind = 0;
+    if (!p->reordered) {
+        gespmm::Geometry geo = {};
+        const int rc = gespmm::run_spmm_heads(nullptr, nullptr, nullptr, nullptr, nullptr, p->M, p->K, H, F, p->nnz, GESPMM_VARIANT_AUTO, 0, nullptr,
+                                              nullptr, b_align, c_align, true, &kind, &geo);
+        if (rc != 0 && rc != gespmm::kHeadsUnavailable) return rc;
+        *route_out = kind;
+        if (dry) return 0;
+        p->heads_last_H = H;
+        p->heads_last_F = F;
+        p->heads_last_route = kind;
+        p->heads_last_geo = geo;
+        return gespmm_csr_spmm_heads_f32(p->rowptr, p->colind, val, B, C, p->M, p->K, H, F, p->nnz, stream);
+    }
+    const int64_t N = H * F;
+    const gespmm::RouteAnswer ra = route_of(p, N, gespmm::kReduceSum, true);
+    const gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, nullptr, 0, false};
+    // (narrow_vec4 — four floats per lane at narrow widths — only where a dwordx4 stays inside one head and the operands allow it)
+    const int variant = (ra.vec4 && F % 4 == 0 && b_align >= 16 && c_align >= 16) ? GESPMM_VARIANT_CRC_CWM4 : p->variant;
+    int rc = gespmm::run_spmm_heads(p->d_rowptr, p->d_colind, nullptr, B, C, p->M, p->K, H, F, p->nnz, variant, p->launch_flags, stream, &pl,
+                                    b_align, c_align, true, &kind);
+    if (rc != 0 && rc != gespmm::kHeadsUnavailable) return rc;
+    if (p->d_tasks == nullptr) kind = 0;
+    *route_out = kind;
+    if (dry) return 0;
+    p->heads_last_H = H;
+    p->heads_last_F = F;
+    p->heads_last_route = kind;
+    if (kind == 0) return gespmm_csr_spmm_heads_f32(p->rowptr, p->colind, val, B, C, p->M, p->K, H, F, p->nnz, stream);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t need = p->nnz * H * 4;
+    if (p->heads_val_bytes < need) {
+        if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
+        if (p->d_heads_val) (void)hipFree(p->d_heads_val);  // (synchronises: no earlier launch still reads it)
+        p->d_heads_val = nullptr;
+        p->heads_val_bytes = 0;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_heads_val), (size_t)need);
+        if (e != hipSuccess) return (int)e;
+        p->heads_val_bytes = need;
+    }
+    const hipError_t e = gespmm::launch_permute_head_values(p->d_rowptr, p->d_src_begin, val, p->d_heads_val, p->M, p->nnz, H, st);
+    if (e != hipSuccess) return (int)e;
+    return gespmm::run_spmm_heads(p->d_rowptr, p->d_colind, p->d_heads_val, B, C, p->M, p->K, H, F, p->nnz, variant, p->launch_flags, stream, &pl,
+                                  b_align, c_align, false, &kind, &p->heads_last_geo);
+}
+
+int gespmm_plan_spmm_heads_f32(gespmm_plan* plan, const float* val, const float* B, float* C, int64_t H, int64_t F, void* stream) {
+    if (!plan) return GESPMM_EINVAL;
+    const int rc = gespmm::check_heads_sizes(plan->M, plan->K, H, F, plan->nnz);
+    if (rc != 0) return rc;
+    if (plan->M == 0 || F == 0) return 0;
+    if (!C || (plan->nnz != 0 && (!B || !val))) return GESPMM_EINVAL;
+    for (const void* q : {(const void*)val, (const void*)B, (const void*)C})
+        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
+    int route = 0;
+    return plan_run_heads(plan, val, B, C, H, F, stream, false, gespmm::pointer_alignment(B), gespmm::pointer_alignment(C), &route);
+}
+
+int gespmm_plan_heads_route(const gespmm_plan* plan, int64_t H, int64_t F, int b_align, int c_align) {
+    if (!plan || b_align < 1 || c_align < 1) return GESPMM_EINVAL;
+    const int rc0 = gespmm::check_heads_sizes(plan->M, plan->K, H, F, plan->nnz);
+    if (rc0 != 0) return rc0;
+    if (plan->M == 0 || F == 0) return 0;
+    int route = 0;
+    const int rc = plan_run_heads(const_cast<gespmm_plan*>(plan), nullptr, nullptr, nullptr, H, F, nullptr, true, b_align, c_align, &route);
+    return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
+}
+
 // Which kernel, MEASURED: the candidates of a clustered plan — batch-stream, segmented-stream and (at the plan's width) staged-rows —
 // run on the caller's operands, `reps` launches each between a pair of events; the fastest becomes the plan's kernel. Every
 // candidate produces the same bits, so C holds the product afterwards whatever wins. The static rules of plan_policy.cpp
@@ -1349,6 +1432,15 @@ int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
         snprintf(kern + used, sizeof kern - used, " | x16 %s N=%lld route=%d (%s%s)", p->x16_last_dtype == GESPMM_X16_F16 ? "f16" : "bf16",
                  (long long)p->x16_last_N, p->x16_last_route,
                  p->x16_last_route == 1 ? "16-bit batch-stream" : p->x16_last_route == 2 ? "16-bit segmented-stream" : "widen, fp32 route, narrow",
+                 geo);
+    }
+    if (p->heads_last_route >= 0) {  // the last multi-head call (gespmm_plan_spmm_heads_f32)
+        const size_t used = strlen(kern);
+        char geo[64] = "";
+        if (p->heads_last_route != 0)
+            snprintf(geo, sizeof geo, " V=%d S=%d W=%d", p->heads_last_geo.vec, p->heads_last_geo.strips, p->heads_last_geo.group);
+        snprintf(kern + used, sizeof kern - used, " | heads H=%lld F=%lld route=%d (%s%s)", (long long)p->heads_last_H, (long long)p->heads_last_F,
+                 p->heads_last_route, p->heads_last_route == 1 ? (p->reordered ? "heads kernel, task table" : "heads kernel") : "per-head composition",
                  geo);
     }
     int n;

@@ -53,6 +53,19 @@ int check_x16_args(const int32_t* rowptr, const int32_t* colind, const float* va
                    int64_t K, int64_t N, int64_t nnz);
 int pointer_alignment(const void* p);  // largest power of two (<= 16) that divides the address
 
+// The multi-head product (gespmm_csr_spmm_heads_f32 / gespmm_plan_spmm_heads_f32; spmm_heads.h) as ONE launch of the heads kernel: 2 <= H <=
+// kHeadsMax, 32-bit offsets (K H F 4 < 2^32, nnz H < 2^31) and a batch-stream geometry the kernel is built for, resolved for width H F with V
+// limited to what divides F and what b_align / c_align allow, strict order, no cache blocking. *kind: 1 the kernel, 0 not available
+// (kHeadsUnavailable is returned and nothing is launched: the caller composes per head). `val` is [nnz, H] — with `pl` in the plan's entry
+// order. dry_run: answer only, pointers are not looked at.
+constexpr int kHeadsUnavailable = -103;  // internal
+int run_spmm_heads(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, float* C, int64_t M, int64_t K, int64_t H,
+                   int64_t F, int64_t nnz, int variant, int flags, void* stream, const PlanLaunch* pl, int b_align, int c_align, bool dry_run,
+                   int* kind, Geometry* geo_out = nullptr);
+int check_heads_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz);  // GESPMM_EINVAL / GESPMM_ERANGE / 0: sizes alone
+int check_heads_args(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const float* C, int64_t M, int64_t K,
+                     int64_t H, int64_t F, int64_t nnz);
+
 // A plan's product behind a launch guard (auto_plan.cpp): kNotGuardable — and nothing launched — when the plan's launch is more than
 // one kernel (hub rows handed to the long-row pass, the cache-blocked path).
 int plan_spmm_guarded(gespmm_plan* plan, const float* B, float* C, int64_t N, int reduce, float empty, void* stream, const LaunchGuard* guard);

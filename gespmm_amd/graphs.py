@@ -437,23 +437,24 @@ def relabel_by_order(rowptr, colind, order):
     return rp.to(torch.int32), c.to(torch.int32)
 
 
-def transpose_csr(rowptr, colind, K=None, val=None):
+def transpose_csr(rowptr, colind, K=None, val=None, return_order=False):
     """CSC arrays (colptr, rowind[, cscval]) of a CSR pattern, rows ascending inside a
     column — host-side helper for callers that build both orders once, like
-    gcn_custom.py:39-46 does with scipy. Pure index manipulation with torch ops."""
+    gcn_custom.py:39-46 does with scipy. Pure index manipulation with torch ops.
+    ``return_order=True`` appends the int64 edge order: CSC position i holds CSR entry order[i] (so ``w[order]`` puts per-edge data of
+    any shape [nnz, ...] into CSC order). The sort is stable: repeated edges keep their CSR order, the same on every call."""
     M = rowptr.numel() - 1
     K = M if K is None else K
     dev = rowptr.device
     counts = (rowptr[1:] - rowptr[:-1]).to(torch.int64)
     rows = torch.repeat_interleave(torch.arange(M, device=dev), counts)
     key = colind.to(torch.int64) * M + rows
-    order = torch.argsort(key)
+    order = torch.argsort(key, stable=True)
     colptr = torch.zeros(K + 1, dtype=torch.int64, device=dev)
     colptr[1:] = torch.cumsum(torch.bincount(colind.to(torch.int64), minlength=K), 0)
     rowind = rows[order].to(torch.int32)
-    if val is not None:
-        return colptr.to(torch.int32), rowind, val[order]
-    return colptr.to(torch.int32), rowind
+    out = (colptr.to(torch.int32), rowind) if val is None else (colptr.to(torch.int32), rowind, val[order])
+    return out + (order,) if return_order else out
 
 
 def reference_B(K, N, seed=1, device="cpu"):

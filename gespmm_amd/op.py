@@ -138,6 +138,42 @@ class FusedGCNFunction(torch.autograd.Function):
         return None, None, None, None, grad_feat, None, None, grad_bias, None, None, None
 
 
+class MultiHeadSPMMFunction(torch.autograd.Function):
+    """out[r, h, :] = sum_e weight[e, h] * feat[col(e), h, :] — the aggregation of a multi-head attention layer
+    (``spmm.csr_spmm_heads``) with gradients for the features and, when asked for, the edge weights.
+
+        MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None)
+
+    ``feat`` f32[K, H, F], ``weight`` f32[nnz, H] in CSR edge order; ``colptr, rowind, csc_order`` =
+    ``graphs.transpose_csr(rowptr, colind, K, return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the
+    CSR and the CSC pattern. Backward: grad_feat is the same product on the CSC arrays with ``weight[csc_order]``;
+    grad_weight[e, h] = <grad_out[row(e), h, :], feat[col(e), h, :]> — one ``sddmm.csr_sddmm`` per head on contiguous copies — is
+    computed only when ``weight`` requires grad. Index tensors get no gradient."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None):
+        fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
+        feat_c, weight_c = feat.contiguous(), weight.contiguous()
+        out = _spmm.csr_spmm_heads(rowptr, colind, weight_c, feat_c, plan=fwd_plan)
+        ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
+        ctx.save_for_backward(feat_c, weight_c)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rowptr, colind, colptr, rowind, csc_order = ctx.graph
+        feat, weight = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        grad_feat = grad_weight = None
+        if ctx.needs_input_grad[5]:
+            grad_feat = _spmm.csr_spmm_heads(colptr, rowind, weight[csc_order].contiguous(), grad_out, plan=ctx.bwd_plan)
+        if ctx.needs_input_grad[6]:
+            H = weight.shape[1]
+            grad_weight = torch.stack([_sddmm.csr_sddmm(rowptr, colind, grad_out[:, h, :].contiguous(), feat[:, h, :].contiguous())
+                                       for h in range(H)], dim=1)
+        return None, None, None, None, None, grad_feat, grad_weight, None
+
+
 def glorot(tensor):
     """torch_geometric.nn.inits.glorot: U(-a, a), a = sqrt(6 / (fan_in + fan_out))."""
     if tensor is not None:

@@ -191,12 +191,9 @@ class SpmmPlan:
         return perm
 
     def _sync_inputs(self, rowptr, colind, values, dense, variant):
-        M, K, N, nnz, var = self.shape
-        if (rowptr.numel() - 1, dense.shape[0], colind.numel(), int(variant)) != (M, K, nnz, var) or \
-                rowptr.data_ptr() != self._rowptr.data_ptr() or colind.data_ptr() != self._colind.data_ptr():
+        if int(variant) != self.shape[4]:
             raise ValueError("SpmmPlan was made for a different matrix or variant")
-        if (self._rowptr._version, self._colind._version) != self._pattern_version:
-            raise ValueError("rowptr/colind were modified in place after the plan was made: create a new SpmmPlan")
+        self._check_pattern(rowptr, colind, dense.shape[0])
         if values is None:
             if self._values is not None:
                 with _on_device(self.device):
@@ -262,6 +259,31 @@ class SpmmPlan:
         rc = lib.gespmm_plan_x16_route(self._handle, int(self.shape[2] if N is None else N), int(b_align), int(c_align))
         if rc < 0:
             check(rc, "gespmm_plan_x16_route")
+        return rc
+
+    def _check_pattern(self, rowptr, colind, K):
+        """The plan was made for exactly these index tensors, unmodified since."""
+        M, K_, _, nnz, _ = self.shape
+        if (rowptr.numel() - 1, int(K), colind.numel()) != (M, K_, nnz) or rowptr.data_ptr() != self._rowptr.data_ptr() or \
+                colind.data_ptr() != self._colind.data_ptr():
+            raise ValueError("SpmmPlan was made for a different matrix or variant")
+        if (self._rowptr._version, self._colind._version) != self._pattern_version:
+            raise ValueError("rowptr/colind were modified in place after the plan was made: create a new SpmmPlan")
+
+    def run_heads(self, values, dense, out=None):
+        """The multi-head product through the plan (gespmm_plan_spmm_heads_f32; see ``csr_spmm_heads``): ``values`` f32[nnz, H] in the
+        caller's edge order — an argument of every call, the plan caches nothing of them and its own values stay what they are — and
+        ``dense`` f32[K, H, F] or f32[K, H * F]. Same bits as the call without a plan. A clustered plan copies the weights into its own
+        edge order on every call, which on a large graph with narrow heads costs more than clustering gains (com-amazon-sbm, H F <= 128:
+        1.1-1.4x the time of the call without a plan) — there, call ``csr_spmm_heads`` without ``plan=``."""
+        return csr_spmm_heads(self._rowptr, self._colind, values, dense, out=out, plan=self)
+
+    def heads_route(self, H, F, b_align=16, c_align=16):
+        """What ``run_heads`` does at H heads of F columns with operands whose addresses ``b_align`` / ``c_align`` divide
+        (gespmm_plan_heads_route, host only): 1 the heads kernel, 0 the per-head composition."""
+        rc = lib.gespmm_plan_heads_route(self._handle, int(H), int(F), int(b_align), int(c_align))
+        if rc < 0:
+            check(rc, "gespmm_plan_heads_route")
         return rc
 
     def fused_route(self, N=None, col_scale=True, row_scale=True, bias=True):
@@ -340,6 +362,59 @@ def csr_spmm_fused(rowptr, colind, values, dense, col_scale=None, row_scale=None
         rc = lib.gespmm_csr_spmm_fused_f32(_ptr(rowptr), _ptr(colind), _optr(values), _ptr(dense), _optr(col_scale), _optr(row_scale),
                                            _optr(bias), _ptr(out), M, K, N, colind.numel(), int(variant), _stream(dev))
     check(rc, "gespmm_csr_spmm_fused_f32")
+    return out
+
+
+def _heads_args(rowptr, colind, values, dense, out):
+    """Validation of the multi-head product: (H, F, the result array — of the rank of ``dense``, contiguous, so the library's [M, H F])."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    _need(values, "values", torch.float32, 2)
+    if not isinstance(dense, torch.Tensor):
+        raise TypeError("dense must be a torch.Tensor")
+    if dense.dim() not in (2, 3):
+        raise ValueError("dense must be [K, H, F] or [K, H * F]")
+    _need(dense, "dense", torch.float32, dense.dim())  # (16-bit operands have no multi-head entry: TypeError)
+    dev = _same_device(dense, rowptr, colind, values)
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have M+1 >= 1 entries")
+    M = rowptr.numel() - 1
+    nnz, H = values.shape
+    if nnz != colind.numel():
+        raise ValueError("values must be [nnz, H] with nnz = %d rows, got %d" % (colind.numel(), nnz))
+    if H < 1:
+        raise ValueError("values must have at least one head")
+    N = dense.shape[1] * dense.shape[2] if dense.dim() == 3 else dense.shape[1]
+    if (dense.dim() == 3 and dense.shape[1] != H) or N % H != 0:
+        raise ValueError("dense of shape %s does not hold H = %d heads" % (tuple(dense.shape), H))
+    F = N // H
+    shape = (M, H, F) if dense.dim() == 3 else (M, N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        _need(out, "out", torch.float32, len(shape))
+        if tuple(out.shape) != shape or out.device != dev:
+            raise ValueError("out must be f32%s on the same device" % (list(shape),))
+    return H, F, out
+
+
+def csr_spmm_heads(rowptr, colind, values, dense, out=None, plan=None):
+    """Multi-head product (attention aggregation): ``out[r, h, :] = sum_e values[e, h] * dense[col(e), h, :]`` over the entries e of row
+    r (gespmm_csr_spmm_heads_f32 / gespmm_plan_spmm_heads_f32). ``values`` f32[nnz, H]; ``dense`` f32[K, H, F] or f32[K, H * F], the
+    result has the matching rank. One fp32 fma chain per output element in strict CSR order, so head h has the bits of
+    ``csr_spmm(rowptr, colind, values[:, h].contiguous(), dense[:, h, :].contiguous(), cfg={"flags": FLAG_STRICT_ORDER})``.
+    One kernel for 2 <= H <= 8 (``_lib.heads_route``), a per-head composition otherwise. fp32 only."""
+    H, F, out = _heads_args(rowptr, colind, values, dense, out)
+    dev = dense.device
+    M, K = rowptr.numel() - 1, dense.shape[0]
+    with _on_device(dev):
+        if plan is not None:
+            plan._check_pattern(rowptr, colind, K)
+            rc = lib.gespmm_plan_spmm_heads_f32(plan._handle, _ptr(values), _ptr(dense), _ptr(out), H, F, _stream(dev))
+        else:
+            rc = lib.gespmm_csr_spmm_heads_f32(_ptr(rowptr), _ptr(colind), _ptr(values), _ptr(dense), _ptr(out), M, K, H, F, colind.numel(),
+                                               _stream(dev))
+    check(rc, "gespmm_plan_spmm_heads_f32" if plan is not None else "gespmm_csr_spmm_heads_f32")
     return out
 
 

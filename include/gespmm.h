@@ -443,6 +443,37 @@ int gespmm_plan_spmm_x16(gespmm_plan* plan, const void* B, void* C, int dtype, i
 int gespmm_x16_route(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant, int b_align, int c_align);
 int gespmm_plan_x16_route(const gespmm_plan* plan, int64_t N, int b_align, int c_align);
 /*
+ * Multi-head product: H weights per edge (attention layers). `val` is row-major [nnz, H], B is [K x H F] and C is [M x H F], fp32,
+ * contiguous, N = H F:
+ *
+ *     C[r, h F + f] = acc,  acc0 = 0,  acc = fmaf(val[p H + h], B[colind[p] N + h F + f], acc) over the row's entries p in CSR order
+ *
+ * ONE fp32 chain per output element in strict CSR order, never re-associated whatever the matrix size: head h has THE SAME BITS as
+ * gespmm_csr_spmm_f32_cfg with GESPMM_FLAG_STRICT_ORDER on the contiguous copies val[:, h] and B[:, h F : (h + 1) F].
+ *
+ * Two executions, same bits: route 1, ONE heads kernel (the batch-stream kernel at width N with the H weights of every staged entry
+ * in LDS; on the caller's arrays or on a clustered plan's task table) where 2 <= H <= 8 and offsets are 32-bit (K N 4 < 2^32,
+ * nnz H < 2^31); else route 0, the composition — per head, gather its weights and its slice of B into stream-ordered temporaries from
+ * the library's pool, the strict-order product, scatter into C (H = 1: that product on the caller's arrays, no temporaries). On a
+ * capturing stream a composition that would have to allocate returns hipErrorStreamCaptureUnsupported and launches nothing.
+ * Through a plan the weights are an argument of every call, in the CALLER's edge order; nothing is cached between calls and the plan's
+ * own values (gespmm_plan_set_values) are not touched. A clustered plan permutes them into a plan-owned buffer first (one copy kernel
+ * per call; the buffer is allocated by the first call and again when H grows — never on a capturing stream).
+ * A matrix without entries (nnz == 0; val, colind and B may then be NULL) gives C = 0 on either route.
+ * The environment variable GESPMM_HEADS_ROUTE=composition pins route 0 (a measurement knob, read with getenv on every call and route
+ * query: do not change the environment from another thread while calls are in flight).
+ * 16-bit operands, the max reducer and the fused vectors have no multi-head entry. Not part of gespmm_set_auto_plan.
+ * GESPMM_EINVAL (H < 1, negative sizes, NULL pointers), GESPMM_EALIGN (a pointer not 4-byte aligned) and GESPMM_ERANGE (H F or nnz
+ * beyond what the other entries take) are checked before any device work; M == 0 or H F == 0 returns 0 without looking at pointers.
+ */
+int gespmm_csr_spmm_heads_f32(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, float* C,
+                              int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream);
+int gespmm_plan_spmm_heads_f32(gespmm_plan* plan, const float* val, const float* B, float* C, int64_t H, int64_t F, void* stream);
+/* host only: the route of the calls above (0 / 1, or GESPMM_E*) for operands whose addresses b_align / c_align (powers of two) divide.
+   geometry_out: NULL or int32[4] — V, S, W and rows per wavefront of the kernel (zeros on route 0) */
+int gespmm_heads_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int b_align, int c_align, int32_t* geometry_out);
+int gespmm_plan_heads_route(const gespmm_plan* plan, int64_t H, int64_t F, int b_align, int c_align);
+/*
  * Kernel choice by MEASUREMENT instead of by rule: runs the candidates of a clustered plan (batch-stream, segmented-stream,
  * staged-rows where the width is served, and at N <= 64 the batch-stream kernel with 4 floats per lane) `reps` (0 = 3) times each on these operands, synchronously, and fixes the plan
  * on the fastest; C holds the product afterwards (every candidate gives the same bits). N must be the plan's width. A no-op
