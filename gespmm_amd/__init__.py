@@ -15,6 +15,6 @@ There is no CPU compute path anywhere in this package.
 """
 from . import _lib  # noqa: F401  (loads libgespmm.so, raises if it is not built)
 from . import spmm, sddmm, graphs  # noqa: F401
-from .op import SPMMFunction, FusedGCNFunction, MultiHeadSPMMFunction, GCNConv  # noqa: F401
+from .op import SPMMFunction, FusedGCNFunction, MultiHeadSPMMFunction, MultiHeadSDDMMFunction, GCNConv  # noqa: F401
 
-__all__ = ["spmm", "sddmm", "graphs", "SPMMFunction", "FusedGCNFunction", "MultiHeadSPMMFunction", "GCNConv"]
+__all__ = ["spmm", "sddmm", "graphs", "SPMMFunction", "FusedGCNFunction", "MultiHeadSPMMFunction", "MultiHeadSDDMMFunction", "GCNConv"]

@@ -101,6 +101,11 @@ EXPORTS = [
     "gespmm_plan_spmm_heads_f32",
     "gespmm_heads_route",
     "gespmm_plan_heads_route",
+    "gespmm_sddmm_coo_heads_f32",
+    "gespmm_sddmm_csr_heads_f32",
+    "gespmm_plan_sddmm_heads_f32",
+    "gespmm_describe_sddmm_heads",
+    "gespmm_plan_sddmm_heads_route",
 ]
 
 X16_F16 = 1
@@ -270,6 +275,16 @@ def _load():
     lib.gespmm_plan_sddmm_x16.argtypes = [p, p, p, p, c_int, c_int64, p]
     lib.gespmm_describe_sddmm_x16.restype = c_int
     lib.gespmm_describe_sddmm_x16.argtypes = [c_int, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_sddmm_coo_heads_f32.restype = c_int
+    lib.gespmm_sddmm_coo_heads_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, p]
+    lib.gespmm_sddmm_csr_heads_f32.restype = c_int
+    lib.gespmm_sddmm_csr_heads_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, p]
+    lib.gespmm_plan_sddmm_heads_f32.restype = c_int
+    lib.gespmm_plan_sddmm_heads_f32.argtypes = [p, p, p, p, c_int64, c_int64, p]
+    lib.gespmm_describe_sddmm_heads.restype = c_int
+    lib.gespmm_describe_sddmm_heads.argtypes = [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_plan_sddmm_heads_route.restype = c_int
+    lib.gespmm_plan_sddmm_heads_route.argtypes = [p, c_int64, c_int64]
     lib.gespmm_plan_set_values.restype = c_int
     lib.gespmm_plan_set_values.argtypes = [p, p, p]
     lib.gespmm_plan_get_order.restype = c_int
@@ -339,6 +354,19 @@ def describe_sddmm(csr, M, nnz, N, d1_align=16, d2_align=16, capturing=False, x1
         raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k == "form" else int(v)) for k, v in out.items()}
+
+
+def describe_sddmm_heads(csr, M, nnz, H, F, d1_align=16, d2_align=16, capturing=False):
+    """What gespmm_sddmm_{coo,csr}_heads_f32 would do for these arguments (gespmm_describe_sddmm_heads: host only) — a dict with "route"
+    ("kernel", "composition", "plain" or "zeros"; absent when nnz == 0) and what the route has: "form", V, W, epw (EDGES per wavefront)
+    for the kernel, V and W for the composition, ``describe_sddmm``'s entries at width F for "plain"."""
+    buf = ctypes.create_string_buffer(160)
+    n = lib.gespmm_describe_sddmm_heads(1 if csr else 0, int(M), int(nnz), int(H), int(F), int(d1_align), int(d2_align), 1 if capturing else 0,
+                                        buf, 160)
+    if n < 0:
+        raise GespmmError(n, "gespmm_describe_sddmm_heads")
+    out = dict(kv.split("=") for kv in buf.value.decode().split())
+    return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
 
 
 def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):

@@ -17,6 +17,7 @@
 #include "select.h"
 #include "auto_plan.h"
 #include "plan.h"
+#include "sddmm_heads.h"
 #include "spmm_heads.h"
 #include "spmm_kernels.h"
 #include "workspace.h"
@@ -370,6 +371,87 @@ int run_spmm_heads(const int32_t* rowptr, const int32_t* colind, const float* va
     a.H = (int32_t)H;
     a.F = (int32_t)F;
     return (int)launch_spmm_heads(a, sel.geo, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- the multi-head SDDMM (gespmm.h: gespmm_sddmm_{coo,csr}_heads_f32; sddmm_heads.h). GESPMM_SDDMM_HEADS_ROUTE=kernel|composition pins
+// the route (read per call: scripts/sddmm_heads_timing.py measures both in one process); resolve_sddmm_heads says where a pin is ignored.
+int sddmm_heads_pin() {
+    if (const char* env = getenv("GESPMM_SDDMM_HEADS_ROUTE")) {
+        if (!strcmp(env, "kernel")) return kSddmmHeadsPinKernel;
+        if (!strcmp(env, "composition")) return kSddmmHeadsPinComposition;
+    }
+    return kSddmmHeadsPinNone;
+}
+
+// Sizes alone, as check_heads_sizes: csr == false ignores M, and has no composition to take a pair count past the kernel's limit.
+int check_sddmm_heads_sizes(bool csr, int64_t M, int64_t H, int64_t F, int64_t nnz) {
+    if (H < 1 || F < 0 || nnz < 0 || (csr && M < 0)) return GESPMM_EINVAL;
+    if ((csr && M > 0x7fffffffLL - 1) || nnz > kSddmmMaxNnz || H > 0x7fffffffLL / 4 || F > (0x7fffffffLL / 4) / H) return GESPMM_ERANGE;
+    if (!csr && nnz > kSddmmMaxNnz / H) return GESPMM_ERANGE;
+    return 0;
+}
+
+// The checks of gespmm_sddmm_{coo,csr}_f32, in their order. 1: nothing left to do (no edges).
+int check_sddmm_heads_args(const int32_t* rows, bool csr, const int32_t* colind, const float* D1, const float* D2, const float* out, int64_t M,
+                           int64_t H, int64_t F, int64_t nnz) {
+    const int rc = check_sddmm_heads_sizes(csr, M, H, F, nnz);
+    if (rc != 0) return rc;
+    if (nnz == 0) return 1;
+    if (!rows || !colind || !out || (F > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
+    if (!aligned_to(rows, 4) || !aligned_to(colind, 4) || !aligned_to(D1, 4) || !aligned_to(D2, 4) || !aligned_to(out, 4)) return GESPMM_EALIGN;
+    return 0;
+}
+
+// One multi-head SDDMM on checked arguments, nnz > 0: what resolve_sddmm_heads answers, nothing else.
+//   plain        H == 1: launch_sddmm on the caller's arrays.
+//   kernel       one sddmm_heads_kernel; never allocates.
+//   composition  CSR only (past the kernel's pair limit, or pinned). Per head: D1[:, hF:(h+1)F] and D2[:, hF:(h+1)F] into stream-ordered temporaries that start address(D) % 16
+//                bytes past a 256-byte boundary — the caller's alignment class, hence the caller's V — launch_sddmm at width F into an
+//                nnz temporary, scatter into out[:, h]. K < 0: the call does not say how many rows D2 has; 1 + the largest column index
+//                is found on the device and read back (one stream synchronisation; a plan passes its K).
+int run_sddmm_heads(const int32_t* rows, bool csr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M, int64_t K,
+                    int64_t H, int64_t F, int64_t nnz, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (F == 0) return (int)hipMemsetAsync(out, 0, (size_t)nnz * (size_t)H * sizeof(float), st);
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    const SddmmHeadsLaunch r = resolve_sddmm_heads(csr, M, nnz, H, F, pointer_alignment(D1), pointer_alignment(D2), capturing, sddmm_heads_pin());
+    if (r.route == kSddmmHeadsPlain) return (int)launch_sddmm(rows, csr, colind, D1, D2, out, M, nnz, F, st);
+    if (r.route == kSddmmHeadsKernel) return (int)launch_sddmm_heads(rows, colind, D1, D2, out, M, nnz, H, F, r, st);
+    if (!csr) return GESPMM_ERANGE;  // (check_sddmm_heads_sizes lets no such call through)
+    int rc = refuse_allocation_under_capture(st);
+    if (rc != 0) return rc;  // (nothing launched)
+    if (K < 0) {
+        int32_t* d_max = nullptr;
+        int32_t h_max = 0;
+        hipError_t e = workspace_alloc(reinterpret_cast<void**>(&d_max), 256, st);
+        if (e != hipSuccess) return (int)e;
+        e = launch_max_index(colind, nnz, d_max, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&h_max, d_max, sizeof h_max, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        const hipError_t ef = workspace_free(d_max, st);
+        if (e != hipSuccess || ef != hipSuccess) return (int)(e != hipSuccess ? e : ef);
+        K = (int64_t)h_max + 1;
+    }
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t d1_bytes = up((size_t)M * (size_t)F * 4 + 16), d2_bytes = up((size_t)K * (size_t)F * 4 + 16), t_bytes = (size_t)nnz * 4;
+    char* scratch = nullptr;
+    hipError_t e = workspace_alloc(reinterpret_cast<void**>(&scratch), d1_bytes + d2_bytes + t_bytes, st);
+    if (e != hipSuccess) return (int)e;
+    float* D1h = reinterpret_cast<float*>(scratch + reinterpret_cast<uintptr_t>(D1) % 16);
+    float* D2h = reinterpret_cast<float*>(scratch + d1_bytes + reinterpret_cast<uintptr_t>(D2) % 16);
+    float* th = reinterpret_cast<float*>(scratch + d1_bytes + d2_bytes);
+    const int64_t N = H * F;
+    for (int64_t h = 0; h < H && rc == 0; ++h) {  // (stream order keeps one head's temporaries until its scatter has read them)
+        rc = (int)launch_heads_slice(D1, D1h, M, N, h * F, F, st);
+        if (rc == 0) rc = (int)launch_heads_slice(D2, D2h, K, N, h * F, F, st);
+        if (rc == 0) rc = (int)launch_sddmm(rows, true, colind, D1h, D2h, th, M, nnz, F, st);
+        if (rc == 0) rc = (int)launch_heads_unslice(th, out, nnz, H, h, 1, st);
+    }
+    e = workspace_free(scratch, st);
+    if (rc == 0) rc = (int)e;
+    return rc;
 }
 
 }  // namespace gespmm
@@ -785,6 +867,53 @@ int gespmm_describe_sddmm(int csr, int64_t M, int64_t nnz, int64_t N, int d1_ali
 int gespmm_describe_sddmm_x16(int csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, int capturing, char* out,
                               int64_t capacity) {
     return describe_sddmm(csr, M, nnz, N, d1_align, d2_align, capturing, out, capacity, 2);
+}
+
+// The multi-head SDDMM (gespmm.h): D1 [., H F], D2 [., H F], out [nnz, H]. The checks of the fp32 entries above, in their order.
+int gespmm_sddmm_coo_heads_f32(const int32_t* rowind, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t H,
+                               int64_t F, int64_t nnz, void* stream) {
+    const int rc = gespmm::check_sddmm_heads_args(rowind, false, colind, D1, D2, out, 0, H, F, nnz);
+    if (rc != 0) return rc < 0 ? rc : 0;
+    return gespmm::run_sddmm_heads(rowind, false, colind, D1, D2, out, 0, -1, H, F, nnz, stream);
+}
+
+int gespmm_sddmm_csr_heads_f32(const int32_t* rowptr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M,
+                               int64_t H, int64_t F, int64_t nnz, void* stream) {
+    const int rc = gespmm::check_sddmm_heads_args(rowptr, true, colind, D1, D2, out, M, H, F, nnz);
+    if (rc != 0) return rc < 0 ? rc : 0;
+    return gespmm::run_sddmm_heads(rowptr, true, colind, D1, D2, out, M, -1, H, F, nnz, stream);
+}
+
+int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing, char* out,
+                                int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    if (d1_align < 4 || d2_align < 4 || (d1_align & (d1_align - 1)) != 0 || (d2_align & (d2_align - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_sddmm_heads_sizes(csr != 0, M, H, F, nnz);
+    if (rc != 0) return rc;
+    int n;
+    if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else if (F == 0) {
+        n = snprintf(out, (size_t)capacity, "route=zeros");
+    } else {
+        const gespmm::SddmmHeadsLaunch r = gespmm::resolve_sddmm_heads(csr != 0, M, nnz, H, F, d1_align > 16 ? 16 : d1_align,
+                                                                       d2_align > 16 ? 16 : d2_align, capturing != 0, gespmm::sddmm_heads_pin());
+        if (r.route == gespmm::kSddmmHeadsPlain) {
+            n = snprintf(out, (size_t)capacity, "route=plain ");
+            if (n > 0 && n < capacity) {
+                const int m = describe_sddmm(csr, M, nnz, F, d1_align, d2_align, capturing, out + n, capacity - n, 4);
+                if (m < 0) return m;
+                n += m;
+            }
+        } else if (r.route == gespmm::kSddmmHeadsKernel) {
+            n = snprintf(out, (size_t)capacity, "route=kernel form=%s V=%d W=%d epw=%d", r.form == gespmm::kSddmmCsrEdge ? "csr-edge" : "coo-edge",
+                         r.V, r.W, r.epw);
+        } else {
+            n = snprintf(out, (size_t)capacity, "route=composition V=%d W=%d", r.V, r.W);
+        }
+    }
+    if (n < 0) return GESPMM_EINVAL;
+    return n < capacity ? n : (int)capacity - 1;
 }
 
 int gespmm_baseline_atomic_scatter_f32(const int32_t* rowptr, const int32_t* colind, const float* in, float* out,

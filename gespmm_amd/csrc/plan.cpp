@@ -42,6 +42,7 @@
 #include "plan_device.h"
 #include "plan_policy.h"
 #include "reorder.h"
+#include "sddmm_heads.h"
 #include "select.h"
 #include "spmm_device.h"
 #include "spmm_heads.h"
@@ -126,6 +127,10 @@ struct gespmm_plan {
     // made by the first call on a clustered plan and again when H grows
     float* d_heads_val = nullptr;  // owner
     int64_t heads_val_bytes = 0;
+    // the multi-head SDDMM on the clustered edge order (gespmm_plan_sddmm_heads_f32, route 2): [nnz, H] results before the scatter; made
+    // by the first such call and again when H grows, never on a capturing stream
+    float* d_sddmm_heads_tmp = nullptr;  // owner
+    int64_t sddmm_heads_tmp_bytes = 0;
     int heads_last_route = -1;  // what the last multi-head call RAN (-1: none yet), its H and F and the kernel's lane geometry: gespmm_plan_describe
     gespmm::Geometry heads_last_geo = {};
     int64_t heads_last_H = 0, heads_last_F = 0;
@@ -139,7 +144,7 @@ struct gespmm_plan {
         gespmm::free_staging(&slab);
         gespmm::free_slab_view(&slab_view, false);
         gespmm::free_records(&rec);
-        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp, (void*)d_fused_scratch, (void*)d_x16_b, (void*)d_x16_c, (void*)d_heads_val})
+        for (void* q : {d_block, (void*)d_val_late, (void*)d_tasks, ws, (void*)d_coo_row, (void*)d_coo_row_storage, (void*)d_edge_dst, (void*)d_sddmm_tmp, (void*)d_fused_scratch, (void*)d_x16_b, (void*)d_x16_c, (void*)d_heads_val, (void*)d_sddmm_heads_tmp})
             if (q) (void)hipFree(q);
     }
 };
@@ -1256,6 +1261,50 @@ int gespmm_plan_tune(gespmm_plan* p, const float* B, float* C, int64_t N, int32_
     return rc;
 }
 
+// The buffers a plan keeps for SDDMM, each made by the first call that needs it (gespmm_plan_sddmm_* and gespmm_plan_sddmm_heads_f32).
+// Route 1: the row id of every edge of the caller's CSR, expanded once.
+static hipError_t plan_sddmm_row_ids(gespmm_plan* p, hipStream_t st) {
+    if (p->d_coo_row_storage) return hipSuccess;
+    int32_t* rows = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&rows), (size_t)p->nnz * 4);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(expand_rows_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->rowptr, rows, (int)p->M, (int)p->nnz);
+    e = hipGetLastError();
+    if (e != hipSuccess) {
+        (void)hipFree(rows);
+        return e;
+    }
+    p->d_coo_row_storage = rows;
+    return hipSuccess;
+}
+
+// Route 2: row ids and destinations of the edges in the plan's clustered order, and the nnz temporary the results pass through.
+static hipError_t plan_sddmm_edge_maps(gespmm_plan* p, hipStream_t st) {
+    if (p->d_coo_row) return hipSuccess;
+    const size_t bytes = (size_t)p->nnz * 4;
+    // all three buffers or none: a half-built set must not survive into the next call
+    int32_t *coo = nullptr, *dst = nullptr;
+    float* tmp = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&coo), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dst), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&tmp), bytes);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(plan_edge_maps_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->d_rowptr, p->d_src_begin,
+                           p->d_perm, coo, dst, (int)p->M, (int)p->nnz);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        if (coo) (void)hipFree(coo);
+        if (dst) (void)hipFree(dst);
+        if (tmp) (void)hipFree(tmp);
+        return e;
+    }
+    p->d_coo_row = coo;
+    p->d_edge_dst = dst;
+    p->d_sddmm_tmp = tmp;
+    return hipSuccess;
+}
+
 // SDDMM on the plan's pattern: out[e] = <D1[row(e), :], D2[col(e), :]> for every edge e of the CALLER's CSR (out in the
 // caller's edge order). A clustered plan walks the edges in its own order — the rows of D2 that neighbouring rows share
 // are then found in L2, as in the SpMM — and scatters the results back; each dot product is the same lane butterfly as in
@@ -1287,47 +1336,15 @@ static int plan_sddmm(gespmm_plan* p, const void* D1, const void* D2, float* out
     const int route = gespmm::sddmm_route(p->facts, p->reordered, p->hits_after, N);
     if (route != 2) {
         if (route == 1) {
-            if (!p->d_coo_row_storage) {
-                int32_t* rows = nullptr;
-                e = hipMalloc(reinterpret_cast<void**>(&rows), (size_t)p->nnz * 4);
-                if (e != hipSuccess) return (int)e;
-                hipLaunchKernelGGL(expand_rows_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->rowptr, rows,
-                                   (int)p->M, (int)p->nnz);
-                e = hipGetLastError();
-                if (e != hipSuccess) {
-                    (void)hipFree(rows);
-                    return (int)e;
-                }
-                p->d_coo_row_storage = rows;
-            }
+            e = plan_sddmm_row_ids(p, st);
+            if (e != hipSuccess) return (int)e;
             return (int)launch(p->d_coo_row_storage, false, p->colind, out);
         }
         if (dtype == 0) return gespmm_sddmm_csr_f32(p->rowptr, p->colind, static_cast<const float*>(D1), static_cast<const float*>(D2), out, p->M, p->nnz, N, stream);
         return gespmm_sddmm_csr_x16(p->rowptr, p->colind, D1, D2, out, dtype, p->M, p->nnz, N, stream);
     }
-    if (!p->d_coo_row) {
-        const size_t bytes = (size_t)p->nnz * 4;
-        // all three buffers or none: a half-built set must not survive into the next call
-        int32_t *coo = nullptr, *dst = nullptr;
-        float* tmp = nullptr;
-        e = hipMalloc(reinterpret_cast<void**>(&coo), bytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dst), bytes);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&tmp), bytes);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(plan_edge_maps_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->d_rowptr,
-                               p->d_src_begin, p->d_perm, coo, dst, (int)p->M, (int)p->nnz);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            if (coo) (void)hipFree(coo);
-            if (dst) (void)hipFree(dst);
-            if (tmp) (void)hipFree(tmp);
-            return (int)e;
-        }
-        p->d_coo_row = coo;
-        p->d_edge_dst = dst;
-        p->d_sddmm_tmp = tmp;
-    }
+    e = plan_sddmm_edge_maps(p, st);
+    if (e != hipSuccess) return (int)e;
     e = launch(p->d_coo_row, false, p->d_colind, p->d_sddmm_tmp);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(scatter_by_index_kernel, dim3((unsigned)((p->nnz + 255) / 256)), dim3(256), 0, st, p->d_sddmm_tmp,
@@ -1347,6 +1364,55 @@ int gespmm_plan_sddmm_x16(gespmm_plan* p, const void* D1, const void* D2, float*
 int gespmm_plan_sddmm_route(const gespmm_plan* p, int64_t N) {
     if (!p || N < 0) return GESPMM_EINVAL;
     return gespmm::sddmm_route(p->facts, p->reordered, p->hits_after, N);
+}
+
+// The multi-head SDDMM on the plan's pattern (gespmm.h): out[e H + h] in the caller's CSR edge order, the bits of gespmm_sddmm_csr_heads_f32.
+// The routes are plan_sddmm's, decided by the same rule at the width of the gathered row, H F; a pair count past the heads kernel's
+// limit leaves only the stateless call (its composition).
+static int plan_sddmm_heads_route(const gespmm_plan* p, int64_t H, int64_t F) {
+    if (p->nnz > gespmm::kSddmmMaxNnz / H) return 0;
+    return gespmm::sddmm_route(p->facts, p->reordered, p->hits_after, H * F);
+}
+
+int gespmm_plan_sddmm_heads_f32(gespmm_plan* p, const float* D1, const float* D2, float* out, int64_t H, int64_t F, void* stream) {
+    if (!p) return GESPMM_EINVAL;
+    const int rc0 = gespmm::check_sddmm_heads_sizes(true, p->M, H, F, p->nnz);
+    if (rc0 != 0) return rc0;
+    if (p->nnz == 0) return 0;
+    if (!out || (F > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
+    for (const void* q : {(const void*)D1, (const void*)D2, (const void*)out})
+        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int route = F == 0 ? 0 : plan_sddmm_heads_route(p, H, F);
+    if (route == 0) return gespmm::run_sddmm_heads(p->rowptr, true, p->colind, D1, D2, out, p->M, p->K, H, F, p->nnz, stream);
+    if (route == 1) {
+        const hipError_t e = plan_sddmm_row_ids(p, st);
+        if (e != hipSuccess) return (int)e;
+        return gespmm::run_sddmm_heads(p->d_coo_row_storage, false, p->colind, D1, D2, out, p->M, p->K, H, F, p->nnz, stream);
+    }
+    hipError_t e = plan_sddmm_edge_maps(p, st);
+    if (e != hipSuccess) return (int)e;
+    const int64_t need = p->nnz * H * 4;
+    if (p->sddmm_heads_tmp_bytes < need) {
+        const int rc = gespmm::refuse_allocation_under_capture(st);
+        if (rc != 0) return rc;  // (nothing launched)
+        if (p->d_sddmm_heads_tmp) (void)hipFree(p->d_sddmm_heads_tmp);  // (synchronises: no earlier launch still reads it)
+        p->d_sddmm_heads_tmp = nullptr;
+        p->sddmm_heads_tmp_bytes = 0;
+        e = hipMalloc(reinterpret_cast<void**>(&p->d_sddmm_heads_tmp), (size_t)need);
+        if (e != hipSuccess) return (int)e;
+        p->sddmm_heads_tmp_bytes = need;
+    }
+    const int rc = gespmm::run_sddmm_heads(p->d_coo_row, false, p->d_colind, D1, D2, p->d_sddmm_heads_tmp, p->M, p->K, H, F, p->nnz, stream);
+    if (rc != 0) return rc;
+    return (int)gespmm::launch_scatter_heads(p->d_sddmm_heads_tmp, p->d_edge_dst, out, p->nnz, H, st);
+}
+
+int gespmm_plan_sddmm_heads_route(const gespmm_plan* p, int64_t H, int64_t F) {
+    if (!p) return GESPMM_EINVAL;
+    const int rc = gespmm::check_sddmm_heads_sizes(true, p->M, H, F, p->nnz);
+    if (rc != 0) return rc;
+    return plan_sddmm_heads_route(p, H, F);
 }
 
 int gespmm_plan_set_values(gespmm_plan* p, const float* val, void* stream) {

@@ -66,6 +66,13 @@ int check_heads_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz); 
 int check_heads_args(const int32_t* rowptr, const int32_t* colind, const float* val, const float* B, const float* C, int64_t M, int64_t K,
                      int64_t H, int64_t F, int64_t nnz);
 
+// The multi-head SDDMM (gespmm_sddmm_{coo,csr}_heads_f32 / gespmm_plan_sddmm_heads_f32; sddmm_heads.h) on checked arguments with nnz > 0:
+// the route resolve_sddmm_heads answers (select.h). rows: row pointers (csr) or row ids. K: rows of D2 where the caller knows them, else
+// -1 — only the CSR composition needs them and then finds a bound on the device (one stream synchronisation).
+int run_sddmm_heads(const int32_t* rows, bool csr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M, int64_t K,
+                    int64_t H, int64_t F, int64_t nnz, void* stream);
+int check_sddmm_heads_sizes(bool csr, int64_t M, int64_t H, int64_t F, int64_t nnz);  // GESPMM_EINVAL / GESPMM_ERANGE / 0: sizes alone
+
 // A plan's product behind a launch guard (auto_plan.cpp): kNotGuardable — and nothing launched — when the plan's launch is more than
 // one kernel (hub rows handed to the long-row pass, the cache-blocked path).
 int plan_spmm_guarded(gespmm_plan* plan, const float* B, float* C, int64_t N, int reduce, float empty, void* stream, const LaunchGuard* guard);

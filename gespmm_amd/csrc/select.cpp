@@ -269,4 +269,35 @@ SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_al
     return r;
 }
 
+// The multi-head SDDMM. V, W and the form are resolve_sddmm's at WIDTH F — a head slice is what a lane group walks — so the bits of a
+// head are those of the single-head call whatever this function answers. The kernel is taken wherever it can run (H >= 2, pair count
+// nnz H within its 32-bit pair arithmetic) — also on CSR patterns of mean degree >= 64, where resolve_sddmm walks rows or blocks: there
+// the edge-parallel heads kernel measured 1.8-12x faster than the per-head composition on a skewed and on a uniform dense pattern
+// (profiles/r09/sddmm_heads/timing.log). The composition is left with CSR calls past the pair limit, and with the pin.
+// Edges per wavefront: the fp32 thresholds of resolve_sddmm applied to the PAIR count nnz H (carried over, not measured on their own)
+// give pairs per wavefront — COO G * UE, CSR 256 / 64 / max(G * UE, 16) — and epw is that many pairs in whole edges, 1 .. 256.
+SddmmHeadsLaunch resolve_sddmm_heads(bool csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, bool capturing,
+                                     int pin) {
+    const SddmmLaunch b = resolve_sddmm(csr, M, nnz, F, d1_align, d2_align, capturing, 4);
+    SddmmHeadsLaunch r = {kSddmmHeadsComposition, b.form, b.V, b.W, 0, 0};
+    if (H == 1) {
+        r.route = kSddmmHeadsPlain;
+        return r;
+    }
+    const bool can_run = H >= 2 && F >= 1 && nnz <= kSddmmMaxNnz / H;
+    const bool kernel = can_run && (capturing || !(csr && pin == kSddmmHeadsPinComposition));
+    if (!kernel) return r;
+    r.route = kSddmmHeadsKernel;
+    r.form = csr ? kSddmmCsrEdge : kSddmmCooEdge;
+    const int64_t pairs = nnz * H;
+    const int G = 64 / r.W;
+    int64_t per_wave = G * 4;
+    if (csr) per_wave = (pairs >= 256 * 16384) ? 256 : (pairs >= 64 * 16384) ? 64 : (G * 4 > 16 ? G * 4 : 16);
+    const int64_t epw = per_wave / H;
+    r.epw = (int)(epw < 1 ? 1 : (epw > 256 ? 256 : epw));
+    // t / H == (t * magic) >> 32 for t < 256 H needs 256 H (magic H - 2^32) < 2^32, and magic H - 2^32 < H: H <= 4096
+    if (H <= 4096) r.magic = (uint32_t)(((1ull << 32) + (uint64_t)H - 1) / (uint64_t)H);
+    return r;
+}
+
 }  // namespace gespmm

@@ -39,4 +39,24 @@ struct SddmmLaunch {
 // elem_size: bytes per element of D1 / D2 — 4 (fp32) or 2 (fp16 / bf16: V up to 8, every byte threshold at half the width).
 SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_align, int d2_align, bool capturing, int elem_size = 4);
 
+// ---- multi-head SDDMM (sddmm_heads.h): which route a call takes and, for the kernel, its launch shape (run_sddmm_heads runs exactly
+// this; gespmm_describe_sddmm_heads prints it).
+enum SddmmHeadsRoute {
+    kSddmmHeadsComposition = 0,  // per head: slices of D1 and D2, launch_sddmm at width F, scatter into out[:, h] (allocates)
+    kSddmmHeadsKernel = 1,       // ONE sddmm_heads_kernel (never allocates)
+    kSddmmHeadsPlain = 2,        // H == 1: the single-head call on the caller's arrays
+};
+enum SddmmHeadsPin { kSddmmHeadsPinNone = 0, kSddmmHeadsPinKernel = 1, kSddmmHeadsPinComposition = 2 };
+struct SddmmHeadsLaunch {
+    int route;       // SddmmHeadsRoute
+    int form;        // kernel: kSddmmCooEdge or kSddmmCsrEdge; else the form resolve_sddmm answers at width F
+    int V, W;        // what resolve_sddmm answers for WIDTH F and the two operand addresses: they fix the bits of every route
+    int epw;         // kernel: EDGES per wavefront, 1 .. 256 (epw H pairs); else 0
+    uint32_t magic;  // kernel: ceil(2^32 / H) where t / H == umulhi(t, magic) for every t < 256 H, else 0 (the kernel divides)
+};
+// pin: GESPMM_SDDMM_HEADS_ROUTE of the caller (kernel: ignored where the kernel cannot run; composition: CSR form off a capturing
+// stream only). nnz > 0, H >= 1.
+SddmmHeadsLaunch resolve_sddmm_heads(bool csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, bool capturing,
+                                     int pin = kSddmmHeadsPinNone);
+
 }  // namespace gespmm

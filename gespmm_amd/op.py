@@ -38,6 +38,10 @@ one rounding; ``grad_out`` arrives in the forward's dtype); edge weights stay fp
 of ``x @ W`` so that the product stays 16-bit. fp32 only, with a TypeError otherwise: ``need_edge_grad=True``, ``fused=True``
 and ``tune_plans=True``. The edge-weight gradient of a 16-bit model is one call away all the same:
 ``sddmm.csr_sddmm(rowptr, colind, grad_out, feat)`` takes fp16 / bf16 tensors as they are and returns the fp32 gradient.
+Attention layers (extension): ``MultiHeadSPMMFunction`` is the aggregation with one weight per edge and head, ``MultiHeadSDDMMFunction``
+the dot-product score s[e, h] = <q[row(e), h, :], k[col(e), h, :]>; each has the other as its backward (``spmm.csr_spmm_heads``,
+``sddmm.csr_sddmm_heads``). ``MultiHeadSPMMFunction(..., heads_sddmm=True)`` computes the edge-weight gradient in one multi-head SDDMM
+instead of one ``sddmm.csr_sddmm`` per head on copies (the default, kept as it was): same bits.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -142,17 +146,22 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
     """out[r, h, :] = sum_e weight[e, h] * feat[col(e), h, :] — the aggregation of a multi-head attention layer
     (``spmm.csr_spmm_heads``) with gradients for the features and, when asked for, the edge weights.
 
-        MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None)
+        MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None, heads_sddmm=False)
 
     ``feat`` f32[K, H, F], ``weight`` f32[nnz, H] in CSR edge order; ``colptr, rowind, csc_order`` =
     ``graphs.transpose_csr(rowptr, colind, K, return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the
     CSR and the CSC pattern. Backward: grad_feat is the same product on the CSC arrays with ``weight[csc_order]``;
-    grad_weight[e, h] = <grad_out[row(e), h, :], feat[col(e), h, :]> — one ``sddmm.csr_sddmm`` per head on contiguous copies — is
-    computed only when ``weight`` requires grad. Index tensors get no gradient."""
+    grad_weight[e, h] = <grad_out[row(e), h, :], feat[col(e), h, :]> is computed only when ``weight`` requires grad — by default as one
+    ``sddmm.csr_sddmm`` per head on contiguous copies, with ``heads_sddmm=True`` as ONE ``sddmm.csr_sddmm_heads(rowptr, colind, grad_out,
+    feat, plan=forward plan)`` on the tensors as they are (no copies, one launch). The two settings give the same bits on
+    torch-allocated tensors (16-byte aligned: the per-head copies and the head slices take the same vector width).
+    Index tensors get no gradient."""
 
     @staticmethod
-    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None):
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None, heads_sddmm=False):
         fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
+        ctx.fwd_plan = fwd_plan
+        ctx.heads_sddmm = bool(heads_sddmm)
         feat_c, weight_c = feat.contiguous(), weight.contiguous()
         out = _spmm.csr_spmm_heads(rowptr, colind, weight_c, feat_c, plan=fwd_plan)
         ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
@@ -168,10 +177,48 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
         if ctx.needs_input_grad[5]:
             grad_feat = _spmm.csr_spmm_heads(colptr, rowind, weight[csc_order].contiguous(), grad_out, plan=ctx.bwd_plan)
         if ctx.needs_input_grad[6]:
-            H = weight.shape[1]
-            grad_weight = torch.stack([_sddmm.csr_sddmm(rowptr, colind, grad_out[:, h, :].contiguous(), feat[:, h, :].contiguous())
-                                       for h in range(H)], dim=1)
-        return None, None, None, None, None, grad_feat, grad_weight, None
+            if ctx.heads_sddmm:
+                grad_weight = _sddmm.csr_sddmm_heads(rowptr, colind, grad_out, feat, plan=ctx.fwd_plan)
+            else:
+                H = weight.shape[1]
+                grad_weight = torch.stack([_sddmm.csr_sddmm(rowptr, colind, grad_out[:, h, :].contiguous(), feat[:, h, :].contiguous())
+                                           for h in range(H)], dim=1)
+        return None, None, None, None, None, grad_feat, grad_weight, None, None
+
+
+class MultiHeadSDDMMFunction(torch.autograd.Function):
+    """s[e, h] = <q[row(e), h, :], k[col(e), h, :]> — the scores of a dot-product attention layer on the edges of a graph
+    (``sddmm.csr_sddmm_heads``), with gradients for both operands.
+
+        MultiHeadSDDMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, q, k, plans=None) -> f32[nnz, H]
+
+    ``q`` f32[M, H, F], ``k`` f32[K, H, F]; ``colptr, rowind, csc_order`` = ``graphs.transpose_csr(rowptr, colind, K,
+    return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the CSR and the CSC pattern. Backward is two
+    multi-head products (``spmm.csr_spmm_heads``), each computed only for an input that requires grad:
+    grad_q = A(grad_s) @ k on the CSR arrays, grad_k = A(grad_s)^T @ q on the CSC arrays with ``grad_s[csc_order]``.
+    Index tensors get no gradient."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, q, k, plans=None):
+        fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
+        ctx.fwd_plan = fwd_plan
+        q_c, k_c = q.contiguous(), k.contiguous()
+        out = _sddmm.csr_sddmm_heads(rowptr, colind, q_c, k_c, plan=fwd_plan)
+        ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
+        ctx.save_for_backward(q_c, k_c)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_s):
+        rowptr, colind, colptr, rowind, csc_order = ctx.graph
+        q, k = ctx.saved_tensors
+        grad_s = grad_s.contiguous()
+        grad_q = grad_k = None
+        if ctx.needs_input_grad[5]:
+            grad_q = _spmm.csr_spmm_heads(rowptr, colind, grad_s, k, plan=ctx.fwd_plan)
+        if ctx.needs_input_grad[6]:
+            grad_k = _spmm.csr_spmm_heads(colptr, rowind, grad_s[csc_order].contiguous(), q, plan=ctx.bwd_plan)
+        return None, None, None, None, None, grad_q, grad_k, None
 
 
 def glorot(tensor):

@@ -286,6 +286,15 @@ class SpmmPlan:
             check(rc, "gespmm_plan_heads_route")
         return rc
 
+    def sddmm_heads_route(self, H, F):
+        """Which way ``sddmm.csr_sddmm_heads(..., plan=self)`` goes at H heads of F columns (gespmm_plan_sddmm_heads_route, host only):
+        0 the stateless CSR call, 1 the heads kernel in COO form on row ids the plan expands once, 2 the plan's clustered edge order and
+        a scatter into the caller's."""
+        rc = lib.gespmm_plan_sddmm_heads_route(self._handle, int(H), int(F))
+        if rc < 0:
+            check(rc, "gespmm_plan_sddmm_heads_route")
+        return rc
+
     def fused_route(self, N=None, col_scale=True, row_scale=True, bias=True):
         """What ``run_fused`` does at width N (default: the plan's) with these vectors present (gespmm_plan_fused_route, host only):
         0 the composition around the unfused launch, 1 the fused batch-stream kernel, 2 the fused segmented-stream kernel."""

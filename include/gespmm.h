@@ -493,6 +493,45 @@ int gespmm_plan_sddmm_x16(gespmm_plan* plan, const void* D1, const void* D2, flo
 /* host only (since 0.5): which way the call above goes at width N. 0 gespmm_sddmm_csr_f32 on the caller's arrays, 1 the COO form on row
  * ids the plan expands once, 2 the plan's clustered edge order + a scatter into the caller's order. */
 int gespmm_plan_sddmm_route(const gespmm_plan* plan, int64_t N);
+/*
+ * Multi-head SDDMM (since 0.5): the edge dot products of an attention layer, all heads in one call. D1 is [M x H F], D2 is [K x H F],
+ * out is [nnz x H], fp32, contiguous, row-major:
+ *
+ *     out[e H + h] = dot( D1[row(e), h F : (h + 1) F], D2[col(e), h F : (h + 1) F] )
+ *
+ * in the summation order of gespmm_sddmm_*_f32 at WIDTH F: the (V, W) gespmm_describe_sddmm answers for N = F and the two operand
+ * alignments. Head h has the bits of gespmm_sddmm_csr_f32 on contiguous copies of the two head slices with the same alignment class
+ * (16-byte aligned operands: any 16-byte aligned copies). The bits depend on F and the two alignments only — not on H, the form, the
+ * route, a plan or stream capture.
+ * Routes: "kernel" — ONE launch, a wavefront resolves the row and column of each of its edges once for all H heads; never allocates;
+ * taken wherever it can run: H >= 2 and nnz H <= 2^31 - 4097, whatever the pattern (also at mean degree >= 64, where
+ * gespmm_sddmm_csr_f32 walks rows: measured faster there). "composition" — CSR calls past the pair limit: per head, the two
+ * slices copied into stream-ordered temporaries of the caller's alignment class, gespmm_sddmm_csr_f32's launch at width F, a scatter into
+ * out[:, h]; not on a capturing stream (hipErrorStreamCaptureUnsupported, nothing launched). The call does not carry the number of rows
+ * of D2: the composition finds the largest column index on the device and WAITS for the stream once (through a plan, which knows K, it
+ * does not). "plain" — H == 1: gespmm_sddmm_*_f32.
+ * GESPMM_SDDMM_HEADS_ROUTE=kernel|composition pins the route (a measurement knob, read with getenv on every call and describe; "kernel"
+ * is ignored where the kernel cannot run, "composition" in COO form and on a capturing stream).
+ * Checks, before any device work and in the order of gespmm_sddmm_*_f32: negative sizes or H < 1 -> GESPMM_EINVAL; M, nnz, H, H F (and,
+ * in COO form, nnz H) out of range -> GESPMM_ERANGE; nnz == 0 -> 0 without looking at pointers; NULL -> GESPMM_EINVAL; a pointer not
+ * 4-byte aligned -> GESPMM_EALIGN. F == 0 writes nnz H zeros. fp32 only.
+ */
+int gespmm_sddmm_coo_heads_f32(const int32_t* rowind, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t H,
+                               int64_t F, int64_t nnz, void* stream);
+int gespmm_sddmm_csr_heads_f32(const int32_t* rowptr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M,
+                               int64_t H, int64_t F, int64_t nnz, void* stream);
+/* host only: what the two calls above do, as text — "route=kernel form=csr-edge V=4 W=4 epw=16" (epw: EDGES per wavefront, 1 .. 256),
+ * "route=composition V=4 W=4", "route=plain " followed by gespmm_describe_sddmm's line at width F, "route=zeros" (F == 0) or "form=none"
+ * (nnz == 0). Arguments and return value as gespmm_describe_sddmm. */
+int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing, char* out,
+                                int64_t capacity);
+/* ... on the plan's pattern, out in the caller's CSR edge order, the same bits. The three routes of gespmm_plan_sddmm_f32, decided by the
+ * same rule at the width of the gathered row, H F (gespmm_plan_sddmm_heads_route: 0 the stateless CSR call, 1 the COO form of the heads
+ * kernel on row ids the plan expands once, 2 the clustered edge order into a plan-owned [nnz, H] temporary + a scatter of H words per
+ * edge; 0 as well where nnz H is past the kernel's limit). The route-2 temporary is made by the first call that needs it and again when
+ * H grows — never on a capturing stream (hipErrorStreamCaptureUnsupported, nothing launched) — and freed with the plan. */
+int gespmm_plan_sddmm_heads_f32(gespmm_plan* plan, const float* D1, const float* D2, float* out, int64_t H, int64_t F, void* stream);
+int gespmm_plan_sddmm_heads_route(const gespmm_plan* plan, int64_t H, int64_t F);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
