@@ -1,0 +1,146 @@
+#!/usr/bin/env python3
+"""GAT training on the custom ops: two ``GATConv`` layers — 8 heads x 8 features, then 1 head — the model of Velickovic et al.
+(2018) for the citation graphs. Every sparse step is a kernel of this library: the additive scores (multi-head SDDMM), the softmax over
+each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-head SpMM), and their backwards.
+
+    python examples/gat_custom.py                                  # pubmed
+    python examples/gat_custom.py --dataset cora --epochs 50
+    python examples/gat_custom.py --graph-capture                  # replay each step from a HIP graph (one stream)
+
+Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
+chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+import gespmm_amd  # noqa: E402,F401
+from gcn_custom import load_edges, proc  # noqa: E402
+from gespmm_amd import GATConv, graphs  # noqa: E402
+
+
+def gat_graph(edge_index, n_v, device):
+    """The self-looped graph in both index orders, plus the edge order between them (what ``GATConv.forward`` takes)."""
+    g = proc(edge_index, n_v, device)
+    rowptr, colind = g["rowptr"], g["colind"]
+    colptr, rowind, order = graphs.transpose_csr(rowptr, colind, n_v, return_order=True)
+    return {"rowptr": rowptr, "colind": colind, "colptr": colptr, "rowind": rowind, "csc_order": order}
+
+
+class Net(torch.nn.Module):
+    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6):
+        super().__init__()
+        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True)
+        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False)
+        self.dropout = dropout
+
+    def forward(self, x, g):
+        a = (g["rowptr"], g["colind"], g["colptr"], g["rowind"], g["csc_order"])
+        x = F.dropout(x, p=self.dropout, training=self.training)
+        x = F.elu(self.conv1(x, *a))
+        x = F.dropout(x, p=self.dropout, training=self.training)
+        return F.log_softmax(self.conv2(x, *a), dim=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n-hidden", type=int, default=8, help="features per head of the first layer")
+    ap.add_argument("--heads", type=int, default=8)
+    ap.add_argument("--dataset", default="pubmed")
+    ap.add_argument("--epochs", type=int, default=200)
+    ap.add_argument("--dropout", type=float, default=0.6)
+    ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("needs a HIP device (the ops have no CPU path)")
+    device = torch.device("cuda")
+
+    edge_index, n_v, n_feat, n_cls = load_edges(args.dataset, device)
+    g = gat_graph(edge_index, n_v, device)
+    gen = torch.Generator().manual_seed(0)
+    x = torch.rand(n_v, n_feat, generator=gen)
+    x = (x / x.sum(1, keepdim=True)).to(device)
+    y = torch.randint(0, n_cls, (n_v,), generator=gen).to(device)
+    perm = torch.randperm(n_v, generator=gen)
+    masks = {}
+    for name, (a, b) in (("train", (0, 20 * n_cls)), ("val", (20 * n_cls, 20 * n_cls + 500)),
+                         ("test", (20 * n_cls + 500, 20 * n_cls + 1500))):
+        m = torch.zeros(n_v, dtype=torch.bool)
+        m[perm[a:b]] = True
+        masks[name] = m.to(device)
+
+    model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout).to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
+    train_idx = masks["train"].nonzero().squeeze(1)
+    y_train = y[train_idx]
+
+    def train_step():
+        optimizer.zero_grad(set_to_none=False)
+        out = model(x, g)
+        loss = F.nll_loss(out.index_select(0, train_idx), y_train)
+        loss.backward()
+        optimizer.step()
+        return loss
+
+    @torch.no_grad()
+    def test():
+        model.eval()
+        logits, accs = model(x, g), []
+        for m in masks.values():
+            pred = logits[m].max(1)[1]
+            accs.append(pred.eq(y[m]).sum().item() / m.sum().item())
+        model.train()
+        return accs
+
+    model.train()
+    graph = None
+    if args.graph_capture:
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(3):
+                train_step()
+        torch.cuda.current_stream().wait_stream(s)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            static_loss = train_step()
+    else:
+        for _ in range(3):
+            train_step()
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    e0.record()
+    best_val = test_acc = 0.0
+    for epoch in range(1, args.epochs + 1):
+        if graph is not None:
+            graph.replay()
+            loss = static_loss
+        else:
+            loss = train_step()
+        if epoch % 50 == 0 or epoch == args.epochs:
+            tr, va, te = test()
+            if va > best_val:
+                best_val, test_acc = va, te
+            print("Epoch: {:03d}, Loss: {:.4f}, Train: {:.4f}, Val: {:.4f}, Test: {:.4f}".format(
+                epoch, float(loss), tr, best_val, test_acc))
+    e1.record()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s" %
+          (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture))
+    print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
+          (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
+
+
+if __name__ == "__main__":
+    main()

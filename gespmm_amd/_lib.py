@@ -106,6 +106,9 @@ EXPORTS = [
     "gespmm_plan_sddmm_heads_f32",
     "gespmm_describe_sddmm_heads",
     "gespmm_plan_sddmm_heads_route",
+    "gespmm_edge_softmax_f32",
+    "gespmm_edge_softmax_backward_f32",
+    "gespmm_describe_edge_softmax",
 ]
 
 X16_F16 = 1
@@ -285,6 +288,12 @@ def _load():
     lib.gespmm_describe_sddmm_heads.argtypes = [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_plan_sddmm_heads_route.restype = c_int
     lib.gespmm_plan_sddmm_heads_route.argtypes = [p, c_int64, c_int64]
+    lib.gespmm_edge_softmax_f32.restype = c_int
+    lib.gespmm_edge_softmax_f32.argtypes = [p, p, p, c_int64, c_int64, c_int64, c_float, p]
+    lib.gespmm_edge_softmax_backward_f32.restype = c_int
+    lib.gespmm_edge_softmax_backward_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_float, p]
+    lib.gespmm_describe_edge_softmax.restype = c_int
+    lib.gespmm_describe_edge_softmax.argtypes = [c_int64, c_int64, c_int64, c_char_p, c_int64]
     lib.gespmm_plan_set_values.restype = c_int
     lib.gespmm_plan_set_values.argtypes = [p, p, p]
     lib.gespmm_plan_get_order.restype = c_int
@@ -367,6 +376,21 @@ def describe_sddmm_heads(csr, M, nnz, H, F, d1_align=16, d2_align=16, capturing=
         raise GespmmError(n, "gespmm_describe_sddmm_heads")
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
+
+
+def describe_edge_softmax(M, nnz, H):
+    """The launch shape of gespmm_edge_softmax_f32 / _backward_f32 for these sizes (gespmm_describe_edge_softmax: host only) — a dict:
+    ``{"W": lanes per (row, head) pair, "L": rows of more entries take a whole wavefront}``, or ``{"form": "none"}`` when nnz == 0.
+    W and L depend on (M, nnz) alone."""
+    buf = ctypes.create_string_buffer(64)
+    n = lib.gespmm_describe_edge_softmax(int(M), int(nnz), int(H), buf, 64)
+    if n < 0:
+        raise GespmmError(n, "gespmm_describe_edge_softmax")
+    text = buf.value.decode()
+    if text == "form=none":
+        return {"form": "none"}
+    w, long_rows = text.split()
+    return {"W": int(w.split("=")[1]), "L": int(long_rows.split(">")[1])}
 
 
 def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include "../../include/gespmm.h"
 #include "select.h"
 #include "auto_plan.h"
+#include "edge_softmax.h"
 #include "plan.h"
 #include "sddmm_heads.h"
 #include "spmm_heads.h"
@@ -381,6 +383,14 @@ int sddmm_heads_pin() {
         if (!strcmp(env, "composition")) return kSddmmHeadsPinComposition;
     }
     return kSddmmHeadsPinNone;
+}
+
+// ---- the edge softmax (gespmm.h: gespmm_edge_softmax_f32 / _backward_f32; edge_softmax.h). Sizes alone: what makes no sense, then what is
+// too large for the kernel's 32-bit word positions p H + h (there is no other route).
+int check_edge_softmax_sizes(int64_t M, int64_t H, int64_t nnz, float slope) {
+    if (M < 0 || H < 1 || nnz < 0 || !std::isfinite(slope) || (M == 0 && nnz > 0)) return GESPMM_EINVAL;
+    if (M > kEdgeSoftmaxMaxRows || H > kSddmmMaxNnz || nnz > kSddmmMaxNnz / H) return GESPMM_ERANGE;
+    return 0;
 }
 
 // Sizes alone, as check_heads_sizes: csr == false ignores M, and has no composition to take a pair count past the kernel's limit.
@@ -911,6 +921,47 @@ int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int6
         } else {
             n = snprintf(out, (size_t)capacity, "route=composition V=%d W=%d", r.V, r.W);
         }
+    }
+    if (n < 0) return GESPMM_EINVAL;
+    return n < capacity ? n : (int)capacity - 1;
+}
+
+/* The edge softmax over CSR rows (gespmm.h). One kernel for every size the checks let through; resolve_edge_softmax decides its shape. */
+int gespmm_edge_softmax_f32(const int32_t* rowptr, const float* score, float* out, int64_t M, int64_t H, int64_t nnz, float slope,
+                            void* stream) {
+    const int rc = gespmm::check_edge_softmax_sizes(M, H, nnz, slope);
+    if (rc != 0) return rc;
+    if (nnz == 0) return 0;
+    if (!rowptr || !score || !out) return GESPMM_EINVAL;
+    if (!aligned_to(rowptr, 4) || !aligned_to(score, 4) || !aligned_to(out, 4)) return GESPMM_EALIGN;
+    return (int)gespmm::launch_edge_softmax(rowptr, score, out, M, H, nnz, slope, gespmm::resolve_edge_softmax(M, nnz, H),
+                                            reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_edge_softmax_backward_f32(const int32_t* rowptr, const float* alpha, const float* grad_alpha, const float* score,
+                                     float* grad_score, int64_t M, int64_t H, int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_edge_softmax_sizes(M, H, nnz, slope);
+    if (rc != 0) return rc;
+    if (nnz == 0) return 0;
+    const bool leaky = slope != 1.0f;  // (score is looked at only then)
+    if (!rowptr || !alpha || !grad_alpha || !grad_score || (leaky && !score)) return GESPMM_EINVAL;
+    if (!aligned_to(rowptr, 4) || !aligned_to(alpha, 4) || !aligned_to(grad_alpha, 4) || !aligned_to(grad_score, 4) ||
+        (leaky && !aligned_to(score, 4)))
+        return GESPMM_EALIGN;
+    return (int)gespmm::launch_edge_softmax_backward(rowptr, alpha, grad_alpha, leaky ? score : nullptr, grad_score, M, H, nnz, slope,
+                                                     gespmm::resolve_edge_softmax(M, nnz, H), reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_describe_edge_softmax(int64_t M, int64_t nnz, int64_t H, char* out, int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_edge_softmax_sizes(M, H, nnz, 1.0f);
+    if (rc != 0) return rc;
+    int n;
+    if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else {
+        const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(M, nnz, H);
+        n = snprintf(out, (size_t)capacity, "W=%d long_rows>%d", r.W, r.L);
     }
     if (n < 0) return GESPMM_EINVAL;
     return n < capacity ? n : (int)capacity - 1;

@@ -1,0 +1,38 @@
+// edge_softmax.h — softmax over the entries of each CSR row, per head, and its backward (gespmm_edge_softmax_f32 /
+// gespmm_edge_softmax_backward_f32; kernels in edge_softmax.hip).
+//
+// score, out, alpha, grad_alpha, grad_score are [nnz, H], row-major, in CSR edge order. For row r with entries [lo, hi) and head h:
+//   forward    x_p = leaky(score[p H + h]),  m = max_p x_p,  t_p = exp(x_p - m),  out[p H + h] = t_p / sum_p t_p
+//   backward   dot = sum_p alpha_p g_p,      grad[p H + h] = alpha_p (g_p - dot) (score_p >= 0 ? 1 : slope)
+// leaky(x) = x >= 0 ? x : slope x; slope == 1 means none (no multiply, the backward reads no score). Empty rows write nothing.
+//
+// The unit of work is the (row, head) PAIR, as in sddmm_heads.h: a wavefront owns rpw consecutive rows (their rpw + 1 row pointers
+// are one coalesced load, kept in a register per lane), a group of W lanes takes one pair, the 64 / W groups take consecutive pairs
+// (consecutive heads of the same entries: contiguous words). Lane l of the W takes entries lo + l + t W. H is a run-time value.
+//
+// Summation order, fixed by the row's degree d and (M, nnz) alone — never by the head, H, capture or the run:
+//   d <= L   lane l folds its entries in entry order (fmaxf for the maximum, plain adds of t_p for the sum, an fmaf chain for the dot),
+//            then an xor butterfly with masks W/2 .. 1.   W = smallest power of two >= ceil(nnz / M), clamped to [4, 16].
+//   d >  L   the same at W = 64 (a whole wavefront per pair): a wave-uniform branch of the one kernel — the wavefront that owns a hub row
+//            walks its H pairs after its short rows. L = kLongRowThreshold.
+// A row of at most kEdgeSoftmaxIT entries per lane is read once and kept in registers; a longer one is swept three times (maximum, sum,
+// write; the backward twice), the later sweeps from L2. Both regimes fold in the same order, so which one ran leaves no trace.
+// No atomics, no workspace, no host synchronisation: capturable. resolve_edge_softmax (select.cpp) answers W and L.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "select.h"
+
+namespace gespmm {
+
+// nnz > 0, M > 0, H >= 1, nnz H <= kSddmmMaxNnz, M <= kEdgeSoftmaxMaxRows. slope == 1: no leaky ReLU.
+hipError_t launch_edge_softmax(const int32_t* rowptr, const float* score, float* out, int64_t M, int64_t H, int64_t nnz, float slope,
+                               const EdgeSoftmaxLaunch& r, hipStream_t st);
+// score is read only when slope != 1 (for its sign).
+hipError_t launch_edge_softmax_backward(const int32_t* rowptr, const float* alpha, const float* grad_alpha, const float* score,
+                                        float* grad_score, int64_t M, int64_t H, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r,
+                                        hipStream_t st);
+
+}  // namespace gespmm

@@ -300,4 +300,20 @@ SddmmHeadsLaunch resolve_sddmm_heads(bool csr, int64_t M, int64_t nnz, int64_t H
     return r;
 }
 
+// The edge softmax. A lane group should cover a typical row in one or two steps, so W follows the mean degree alone — up to 16 lanes:
+// the starting rule went on to 64, and on products-sbm (mean degree 50.5) W = 64 measured 1.3-2.4x slower than W = 16 at H = 1, 4 and 8,
+// forward and backward (a whole wavefront per pair leaves no lane group for the neighbouring heads, so at H > 1 every load instruction
+// touches 64 separate words; profiles/r10/edge_softmax/w_cap.log). Rows past kLongRowThreshold take a whole wavefront; that
+// value is carried over from the SpMM's long-row pass, not tuned. H only sizes a wavefront's share of rows (about 64 pairs), which no
+// result bit depends on.
+EdgeSoftmaxLaunch resolve_edge_softmax(int64_t M, int64_t nnz, int64_t H) {
+    EdgeSoftmaxLaunch r = {kEdgeSoftmaxMaxW, kLongRowThreshold, 1};
+    const int64_t mean = M > 0 ? (nnz + M - 1) / M : kEdgeSoftmaxMaxW;
+    int W = 4;
+    while (W < kEdgeSoftmaxMaxW && W < mean) W *= 2;
+    r.W = W;
+    if (H < 64) r.rpw = (int)(64 / (H < 1 ? 1 : H) > 63 ? 63 : 64 / (H < 1 ? 1 : H));
+    return r;
+}
+
 }  // namespace gespmm

@@ -59,4 +59,16 @@ struct SddmmHeadsLaunch {
 SddmmHeadsLaunch resolve_sddmm_heads(bool csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, bool capturing,
                                      int pin = kSddmmHeadsPinNone);
 
+// ---- edge softmax (edge_softmax.h): the launch shape of forward and backward alike (gespmm_describe_edge_softmax prints W and L).
+constexpr int kEdgeSoftmaxIT = 4;                                // entries per lane a row may have to be read once (registers)
+constexpr int kEdgeSoftmaxMaxW = 16;                             // most lanes per pair of a row of at most L entries (measured: select.cpp)
+constexpr int64_t kEdgeSoftmaxMaxRows = 0x7fffffffLL - 4096;     // row ids of the last workgroup's wavefronts stay below 2^31
+struct EdgeSoftmaxLaunch {
+    int W;    // lanes per (row, head) pair of a row of at most L entries: smallest power of two >= ceil(nnz / M), within [4, 16]
+    int L;    // rows of more entries take a whole wavefront per pair, W = 64 (kLongRowThreshold)
+    int rpw;  // rows per wavefront, 1 .. 63: about 64 pairs (one row where H >= 64). Never changes a bit of the result.
+};
+// M >= 1, nnz >= 1, H >= 1. W and L depend on (M, nnz) alone.
+EdgeSoftmaxLaunch resolve_edge_softmax(int64_t M, int64_t nnz, int64_t H);
+
 }  // namespace gespmm

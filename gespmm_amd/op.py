@@ -42,6 +42,8 @@ Attention layers (extension): ``MultiHeadSPMMFunction`` is the aggregation with 
 the dot-product score s[e, h] = <q[row(e), h, :], k[col(e), h, :]>; each has the other as its backward (``spmm.csr_spmm_heads``,
 ``sddmm.csr_sddmm_heads``). ``MultiHeadSPMMFunction(..., heads_sddmm=True)`` computes the edge-weight gradient in one multi-head SDDMM
 instead of one ``sddmm.csr_sddmm`` per head on copies (the default, kept as it was): same bits.
+``EdgeSoftmaxFunction`` is the step between the two — softmax over the entries of each row, per head, with the leaky ReLU of a GAT
+fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` the graph attention layer composed from the three.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -51,6 +53,7 @@ import torch
 from torch.nn import Parameter
 
 from . import sddmm as _sddmm
+from . import softmax as _softmax
 from . import spmm as _spmm
 
 _warned_no_grad = False
@@ -221,6 +224,37 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
         return None, None, None, None, None, grad_q, grad_k, None
 
 
+class EdgeSoftmaxFunction(torch.autograd.Function):
+    """alpha[e, h] = softmax over the entries e of each CSR row of leaky_relu(score[e, h], negative_slope) — the attention weights of
+    a graph attention layer (``softmax.edge_softmax``), with the gradient for ``score`` (``softmax.edge_softmax_backward``).
+
+        EdgeSoftmaxFunction.apply(rowptr, score, negative_slope=None) -> f32, the shape of score
+
+    ``score`` f32[nnz] or f32[nnz, H] in CSR edge order; ``negative_slope=None``: no leaky ReLU. Backward needs ``alpha`` alone — and
+    the sign of ``score`` when a slope is given, so ``score`` is saved only then. ``rowptr`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, rowptr, score, negative_slope=None):
+        score_c = score.contiguous()
+        alpha = _softmax.edge_softmax(rowptr, score_c, negative_slope=negative_slope)
+        ctx.rowptr, ctx.negative_slope = rowptr, negative_slope
+        if negative_slope is None:
+            ctx.save_for_backward(alpha)
+        else:
+            ctx.save_for_backward(alpha, score_c)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        alpha = ctx.saved_tensors[0]
+        score = ctx.saved_tensors[1] if ctx.negative_slope is not None else None
+        grad_score = None
+        if ctx.needs_input_grad[1]:
+            grad_score = _softmax.edge_softmax_backward(ctx.rowptr, alpha, grad_alpha.contiguous(), score=score,
+                                                        negative_slope=ctx.negative_slope)
+        return None, grad_score, None
+
+
 def glorot(tensor):
     """torch_geometric.nn.inits.glorot: U(-a, a), a = sqrt(6 / (fan_in + fan_out))."""
     if tensor is not None:
@@ -327,3 +361,60 @@ class GCNConv(torch.nn.Module):
 
     def __repr__(self):
         return "%s(%d, %d)" % (type(self).__name__, self.in_channels, self.out_channels)
+
+
+class GATConv(torch.nn.Module):
+    """Graph attention layer (Velickovic et al., 2018) on the library's ops, H heads in every call:
+
+        xw = (x W).view(K, H, F),  el = <xw, att_dst>,  er = <xw, att_src>                                     (dense, torch)
+        score[e, h] = el[row(e), h] + er[col(e), h]                ``MultiHeadSDDMMFunction`` on q = (el, 1), k = (1, er)
+        alpha = softmax over each row's entries of leaky_relu(score, negative_slope)      ``EdgeSoftmaxFunction``
+        out[r, h, :] = sum_e alpha[e, h] xw[col(e), h, :]          ``MultiHeadSPMMFunction(..., heads_sddmm=True)``
+
+    then heads concatenated (``concat=True``: [M, H F]) or averaged ([M, F]), plus bias. No torch index op touches an edge array: the
+    additive score is a width-2 dot product whose pinned chain is fmaf(1, er, fmaf(el, 1, 0)) = fl(el + er) (or el + er across two lanes),
+    and its backward hands grad_el and grad_er back as component 0 of grad_q and component 1 of grad_k.
+
+        GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True)
+        forward(x, rowptr, colind, colptr, rowind, csc_order)
+
+    The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
+    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True):
+        super().__init__()
+        if heads < 1:
+            raise ValueError("heads must be at least 1")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, int(heads)
+        self.concat, self.negative_slope = bool(concat), negative_slope
+        self.weight = Parameter(torch.empty(in_channels, self.heads * out_channels))
+        self.att_dst = Parameter(torch.empty(1, self.heads, out_channels))  # scores the aggregating node (the row of an edge)
+        self.att_src = Parameter(torch.empty(1, self.heads, out_channels))  # scores the neighbour (the column of an edge)
+        self.bias = Parameter(torch.empty(self.heads * out_channels if self.concat else out_channels)) if bias else None
+        if not bias:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot(self.weight)
+        glorot(self.att_dst)
+        glorot(self.att_src)
+        zeros(self.bias)
+
+    def forward(self, x, rowptr, colind, colptr, rowind, csc_order):
+        n, H, F = x.shape[0], self.heads, self.out_channels
+        if rowptr.numel() != n + 1 or colptr.numel() != n + 1:
+            raise ValueError("GATConv needs a square graph: rowptr and colptr must have x.size(0) + 1 entries")
+        xw = (x @ self.weight).view(n, H, F)
+        el = (xw * self.att_dst).sum(-1)
+        er = (xw * self.att_src).sum(-1)
+        q = torch.stack((el, torch.ones_like(el)), dim=-1)  # [n, H, 2]
+        k = torch.stack((torch.ones_like(er), er), dim=-1)
+        score = MultiHeadSDDMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, q, k)
+        alpha = EdgeSoftmaxFunction.apply(rowptr, score, self.negative_slope)
+        out = MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, xw, alpha, None, True)
+        out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
+        return out if self.bias is None else out + self.bias
+
+    def __repr__(self):
+        return "%s(%d, %d, heads=%d)" % (type(self).__name__, self.in_channels, self.out_channels, self.heads)

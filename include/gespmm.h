@@ -28,6 +28,7 @@
  *                               spmm_cuda spmm_kernel.cu:425-458, CustomCsrmm dgl-custom/binary_reduce_sum.cu:338-360
  *   gespmm_cluster_rows / gespmm_simulate_l2_hits <- (new) the plan's host-side row clustering and its L2 model
  *   gespmm_baseline_atomic_scatter_f32 <- Gunrock app's edge map  gunrock-test/app/spmm/spmm_enactor.cuh:92-105
+ *   gespmm_edge_softmax_f32 / _backward_f32 <- (new) softmax over the entries of a CSR row, per head; no reference counterpart
  *   gespmm_baseline_copy_f32 <- (new) streaming-copy yardstick for the roofline record; no reference counterpart
  *
  * Conventions (all device entry points):
@@ -532,6 +533,44 @@ int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int6
  * H grows — never on a capturing stream (hipErrorStreamCaptureUnsupported, nothing launched) — and freed with the plan. */
 int gespmm_plan_sddmm_heads_f32(gespmm_plan* plan, const float* D1, const float* D2, float* out, int64_t H, int64_t F, void* stream);
 int gespmm_plan_sddmm_heads_route(const gespmm_plan* plan, int64_t H, int64_t F);
+/*
+ * Edge softmax over the entries of each CSR row, per head (since 0.5): the step between the scores of an attention layer
+ * (gespmm_sddmm_csr_heads_f32) and its aggregation (gespmm_csr_spmm_heads_f32). score and out are [nnz x H], fp32, contiguous,
+ * row-major, in CSR edge order; rowptr has M + 1 entries and rowptr[M] == nnz. For row r with entries [lo, hi) and head h:
+ *
+ *     x_p = score[p H + h] >= 0 ? score[p H + h] : slope * score[p H + h]        (leaky ReLU; slope == 1: none, no multiply)
+ *     out[p H + h] = exp(x_p - max_p x_p) / sum_p exp(x_p - max_p x_p)
+ *
+ * Empty rows write nothing. A NaN or +inf score, or a row of -inf only, makes its own (row, head) NaN and nothing else; -inf among
+ * finite scores gives +0. The exponential is exp2(fl(x log2(e))) on the hardware's exp2 (results below 2^-126 flush to zero).
+ * Summation order (pinned): a row of d <= L entries is folded by W lanes — lane l takes entries lo + l + t W in order, fmaxf for the
+ * maximum, plain adds for the sum, then an xor butterfly with masks W/2 .. 1 — and a row of d > L entries the same way by 64 lanes.
+ * W is the smallest power of two >= ceil(nnz / M) within [4, 16], L = 2048 (gespmm_describe_edge_softmax prints both). Head h of a call
+ * has the bits of the H = 1 call on a contiguous copy of score[:, h]; the bits do not depend on H, on stream capture or on the run.
+ * One kernel, no atomics, no workspace, no allocation, no host synchronisation: it can be captured in a graph.
+ * Checks, before any device work and in this order: H < 1, a negative size, M == 0 with nnz > 0, a NaN or infinite slope ->
+ * GESPMM_EINVAL; M > 2^31 - 4097, or nnz H > 2^31 - 4097 (32-bit word positions; there is no other route) -> GESPMM_ERANGE; nnz == 0 -> 0
+ * without looking at pointers; NULL -> GESPMM_EINVAL; a pointer not 4-byte aligned -> GESPMM_EALIGN. out must not overlap score or rowptr
+ * (not checked). fp32 only.
+ */
+int gespmm_edge_softmax_f32(const int32_t* rowptr, const float* score, float* out, int64_t M, int64_t H, int64_t nnz, float slope,
+                            void* stream);
+/*
+ * Its backward (since 0.5): alpha is the forward's output, grad_alpha the gradient with respect to it, both [nnz x H];
+ *
+ *     dot = sum_p alpha_p grad_alpha_p                  (fmaf chains in the forward's lane order, then the butterfly)
+ *     grad_score[p H + h] = alpha_p * (grad_alpha_p - dot) * (score_p >= 0 ? 1 : slope)
+ *
+ * score (the forward's input) is read for its sign only, and only when slope != 1: it must be NULL or is ignored when slope == 1. Same
+ * checks, order and limits as the forward; grad_score must not overlap an input (not checked).
+ */
+int gespmm_edge_softmax_backward_f32(const int32_t* rowptr, const float* alpha, const float* grad_alpha, const float* score,
+                                     float* grad_score, int64_t M, int64_t H, int64_t nnz, float slope, void* stream);
+/* host only (since 0.5): the launch shape of the two calls above, from the function the launch itself runs — "W=8 long_rows>2048" (lanes
+ * per (row, head) pair; rows of more entries than that take a whole wavefront) or "form=none" (nnz == 0). H never changes the answer.
+ * out / capacity / return value as gespmm_describe_sddmm: the text is truncated to capacity - 1 characters and NUL-terminated, the
+ * return value is the number of characters written, or a GESPMM_E* code for sizes the calls above refuse. */
+int gespmm_describe_edge_softmax(int64_t M, int64_t nnz, int64_t H, char* out, int64_t capacity);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
