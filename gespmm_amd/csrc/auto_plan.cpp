@@ -401,8 +401,8 @@ bool auto_plan_try(const int32_t* rowptr, const int32_t* colind, const float* va
                 int r1 = plan_spmm_guarded(en->plan, B, C, N, reduce, empty, stream, &run_plan);
                 int r0 = r1;
                 if (r1 == 0)
-                    r0 = run_spmm(rowptr, colind, val, B, C, M, dgl ? M : K, N, en->nnz, variant, &fallback_cfg, reduce, empty, stream, nullptr, 0,
-                                  nullptr, &run_plain);
+                    r0 = run_spmm(csr_view(rowptr, colind, val, M, dgl ? M : K, en->nnz, variant), B, C, N, &fallback_cfg, reduce, empty, stream,
+                                  nullptr, 0, &run_plain);
                 if (r1 == 0 && r0 == 0) {
                     g_stats.calls_planned += 1;
                     g_stats.calls_async += 1;
@@ -471,7 +471,7 @@ bool auto_plan_try(const int32_t* rowptr, const int32_t* colind, const float* va
         // asynchronous mode from the next call on, if both launches are single kernels (dry runs: nothing is launched)
         const LaunchGuard dry = {nullptr, -1};
         en->async_ok = g_auto_async.load(std::memory_order_relaxed) && plan_spmm_guarded(p, B, C, N, reduce, empty, stream, &dry) == 0 &&
-                       run_spmm(rowptr, colind, val, B, C, M, dgl ? M : K, N, nnz, variant, &fallback_cfg, reduce, empty, stream, nullptr, 0, nullptr,
+                       run_spmm(csr_view(rowptr, colind, val, M, dgl ? M : K, nnz, variant), B, C, N, &fallback_cfg, reduce, empty, stream, nullptr, 0,
                                 &dry) == 0 &&
                        async_setup(*en, dev, st) == hipSuccess;
         (void)hipGetLastError();
@@ -542,7 +542,7 @@ int gespmm_init(int64_t rows_hint, int64_t nnz_hint, void* stream) {
         rc = e != hipSuccess ? (int)e : (int)hipGetLastError();
         // every kernel family once: the plain call, a clustered plan on the streaming kernels (both), the staged-rows kernels (tuned,
         // general, lane groups) — building the plans runs every analysis pass
-        if (rc == 0) rc = gespmm::run_spmm(rp, ci, nullptr, B, C, M, M, N, nnz, GESPMM_VARIANT_AUTO, nullptr, gespmm::kReduceSum, 0.0f, stream, nullptr, 0, nullptr);
+        if (rc == 0) rc = gespmm::run_spmm(gespmm::csr_view(rp, ci, nullptr, M, M, nnz, GESPMM_VARIANT_AUTO), B, C, N, nullptr, gespmm::kReduceSum, 0.0f, stream, nullptr, 0);
         const int kernels[5] = {GESPMM_PLAN_KERNEL_STREAM, GESPMM_PLAN_KERNEL_SEG_STREAM, GESPMM_PLAN_KERNEL_STAGED, GESPMM_PLAN_KERNEL_STAGED,
                                 GESPMM_PLAN_KERNEL_RECORDS};  // (... and the padded-record kernel with its table passes)
         const int widths[5] = {N, N, N, 32, 32};

@@ -272,6 +272,35 @@ gespmm::RouteAnswer route_of(const gespmm_plan* p, int64_t N, int reduce, bool o
     return gespmm::plan_route(p->facts, s, N, reduce, operands_aligned16);
 }
 
+// The matrix a streaming launch of the plan works on, for the route's answer: a clustered plan's copy with both task tables (which
+// streaming kernel: ra.segmented; which lane geometry at narrow widths: ra.vec4 — plan_policy.cpp), else the caller's arrays.
+gespmm::CsrView plan_view(const gespmm_plan* p, const gespmm::RouteAnswer& ra) {
+    if (!p->reordered) return gespmm::csr_view(p->rowptr, p->colind, p->valued ? p->val : nullptr, p->M, p->K, p->nnz, p->variant);
+    gespmm::CsrView A = gespmm::csr_view(p->d_rowptr, p->d_colind, p->valued ? p->d_val : nullptr, p->M, p->K, p->nnz,
+                                         ra.vec4 ? GESPMM_VARIANT_CRC_CWM4 : p->variant);
+    A.planned = true;
+    A.pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, ra.segmented};
+    return A;
+}
+
+// A buffer the plan owns (one of the destructor's list), made at least `need` bytes by the call that needs it. resize_owned: the old
+// block goes first — hipFree synchronises, no earlier launch still uses it — and what the plan holds stays consistent when hipMalloc
+// fails. grow_owned: the same, never on a capturing stream (hipErrorStreamCaptureUnsupported: nothing touched, the caller launches nothing).
+hipError_t resize_owned(float** q, int64_t* have, int64_t need) {
+    if (*have >= need) return hipSuccess;
+    if (*q) (void)hipFree(*q);
+    *q = nullptr;
+    *have = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(q), (size_t)need);
+    if (e == hipSuccess) *have = need;
+    return e;
+}
+int grow_owned(float** q, int64_t* have, int64_t need, hipStream_t st) {
+    if (*have >= need) return 0;
+    const int rc = gespmm::refuse_allocation_under_capture(st);
+    return rc != 0 ? rc : (int)resize_owned(q, have, need);
+}
+
 }  // namespace
 
 namespace gespmm {
@@ -481,9 +510,9 @@ struct Creation {  // what the stages hand on
 
 static int check_create_args(const int32_t* rowptr, const int32_t* colind, int64_t M, int64_t K, int64_t nnz, int64_t N, int variant,
                              const gespmm_plan_options* opt) {
-    if (M < 0 || K < 0 || N < 0 || nnz < 0) return GESPMM_EINVAL;
-    if (M > 0x7fffffffLL - 64 || K > 0x7fffffffLL || N > 0x7fffffffLL / 4 || nnz > 0x7fffffffLL - 4096) return GESPMM_ERANGE;
-    if (variant < GESPMM_VARIANT_AUTO || variant >= GESPMM_NUM_VARIANTS) return GESPMM_EINVAL;
+    const int rc = gespmm::check_csr_sizes(M, K, N, nnz, 0);
+    if (rc != 0) return rc;
+    if (!gespmm::valid_variant(variant)) return GESPMM_EINVAL;
     if (M > 0 && !rowptr) return GESPMM_EINVAL;
     if (nnz > 0 && !colind) return GESPMM_EINVAL;
     if (!opt) return 0;
@@ -535,8 +564,7 @@ static int validate_and_decide(gespmm_plan* p, Creation& cx, const gespmm_plan_o
     f.wedge_probe = wedge_probe;
     f.cold_start = !gespmm::analysis_is_warm();
     gespmm::Selection sel;
-    int max_vec = 4;
-    while (max_vec > 1 && (N % max_vec) != 0) max_vec >>= 1;
+    const int max_vec = gespmm::vec_limit(N, 16);
     const int lr_flags = gespmm::long_row_flags(M, nnz, max_deg, f.user_flags);
     if (gespmm::resolve_geometry(M, K, N > 0 ? N : 1, nnz, p->variant, max_vec, 0, 0, 0, 0, 0, lr_flags, &sel) != 0) return GESPMM_EINVAL;
     f.sel_variant = sel.variant;
@@ -852,13 +880,9 @@ static int plan_run(gespmm_plan* p, const float* B, float* C, int64_t N, int red
     const int64_t ws_bytes = (N == p->N) ? p->ws_bytes : 0;
     // the slab geometry (rows per slab) depends on the vector width the operands' alignment allows: split points kept from
     // a call with other alignment must not be reused
-    int vec_now = 4;
-    while (vec_now > 1 && ((N % vec_now) != 0 || (reinterpret_cast<uintptr_t>(B) % (4u * vec_now)) != 0 ||
-                           (reinterpret_cast<uintptr_t>(C) % (4u * vec_now)) != 0))
-        vec_now >>= 1;
+    const int vec_now = gespmm::vec_limit(N, gespmm::min_alignment(B, C));
     if (ws && p->split_ready && p->split_vec == vec_now) cfg.flags |= GESPMM_FLAG_REUSE_SPLIT;
     hipStream_t hst = reinterpret_cast<hipStream_t>(stream);
-    const float* pval = p->valued ? p->d_val : nullptr;
     const gespmm::RouteAnswer ra = route_of(p, N, reduce, aligned16(B, C));
     if (ra.route == PlanRoute::Records || ra.route == PlanRoute::StagedSlabs || ra.staged()) {  // the kernels that walk the plan's tables
         if (!B || !C) return GESPMM_EINVAL;
@@ -891,25 +915,19 @@ static int plan_run(gespmm_plan* p, const float* B, float* C, int64_t N, int red
         if (rc == 0 && ra.hub_pass) {
             // hub rows (written as empty rows above): one-row tasks through the batch-stream kernel, whose long-row pass splits
             // them — under GESPMM_FLAG_STRICT_ORDER each is one lane group's chain instead, as everywhere else
-            gespmm::PlanLaunch pl = {p->stg.ltasks, p->stg.nlong, p->d_perm, nullptr, 0, false};
+            gespmm::CsrView hubs = plan_view(p, ra);
+            hubs.variant = p->variant;
+            hubs.pl = {p->stg.ltasks, p->stg.nlong, p->d_perm, nullptr, 0, false};
             gespmm_launch_cfg lcfg = cfg;
             lcfg.flags = (lcfg.flags | GESPMM_FLAG_BATCH_STREAM | GESPMM_FLAG_NO_SLAB_BLOCKED) & ~GESPMM_FLAG_REUSE_SPLIT;
             if (!(lcfg.flags & GESPMM_FLAG_STRICT_ORDER)) lcfg.flags |= GESPMM_FLAG_SPLIT_LONG_ROWS;
-            rc = gespmm::run_spmm(p->d_rowptr, p->d_colind, pval, B, C, p->M, p->K, N, p->nnz, p->variant, &lcfg, reduce, empty, stream, ws,
-                                  ws_bytes, &pl);
+            rc = gespmm::run_spmm(hubs, B, C, N, &lcfg, reduce, empty, stream, ws, ws_bytes);
         }
         return rc;
     }
-    case PlanRoute::PlanStream: {
-        // (which streaming kernel: prefer_segmented; which lane geometry at narrow widths: narrow_vec4 — plan_policy.cpp)
-        gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, ra.segmented};
-        rc = gespmm::run_spmm(p->d_rowptr, p->d_colind, pval, B, C, p->M, p->K, N, p->nnz, ra.vec4 ? GESPMM_VARIANT_CRC_CWM4 : p->variant, &cfg,
-                              reduce, empty, stream, ws, ws_bytes, &pl, guard);
-        break;
-    }
-    case PlanRoute::StorageOrder:
-        rc = gespmm::run_spmm(p->rowptr, p->colind, p->valued ? p->val : nullptr, B, C, p->M, p->K, N, p->nnz, p->variant, &cfg, reduce, empty,
-                              stream, ws, ws_bytes, nullptr, guard);
+    case PlanRoute::PlanStream:    // the plan's copy and task tables
+    case PlanRoute::StorageOrder:  // the caller's arrays
+        rc = gespmm::run_spmm(plan_view(p, ra), B, C, N, &cfg, reduce, empty, stream, ws, ws_bytes, guard);
         break;
     }
     if (rc == 0 && ws) {
@@ -936,34 +954,18 @@ static int plan_run_fused(gespmm_plan* p, const float* B, const gespmm::FusedVec
                           int* route_out) {
     *route_out = 0;
     const gespmm::RouteAnswer ra = route_of(p, N, gespmm::kReduceSum, dry ? true : aligned16(B, C));
-    const float* pval = p->valued ? (p->reordered ? p->d_val : p->val) : nullptr;
-    const gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, ra.segmented};
-    const int32_t* rp = p->reordered ? p->d_rowptr : p->rowptr;
-    const int32_t* ci = p->reordered ? p->d_colind : p->colind;
-    const int variant = (p->reordered && ra.vec4) ? GESPMM_VARIANT_CRC_CWM4 : p->variant;
+    const gespmm::CsrView A = plan_view(p, ra);
     int kind = 0;
-    int rc = gespmm::run_spmm_fused(rp, ci, pval, B, fx, C, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
-                                    p->reordered ? &pl : nullptr, true, &kind);
+    int rc = gespmm::run_spmm_fused(A, B, fx, C, N, p->launch_flags, stream, true, &kind);
     if (rc != 0 && rc != gespmm::kFusedUnavailable) return rc;
     const int route = gespmm::fused_route(p->facts, ra, kind, N, fx.col_scale != nullptr, fx.row_scale != nullptr, fx.bias != nullptr);
     *route_out = route;
     if (dry) return 0;
-    if (route != 0)
-        return gespmm::run_spmm_fused(rp, ci, pval, B, fx, C, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
-                                      p->reordered ? &pl : nullptr, false, &kind);
+    if (route != 0) return gespmm::run_spmm_fused(A, B, fx, C, N, p->launch_flags, stream, false, &kind);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const float* Bin = B;
     if (fx.col_scale && p->nnz > 0 && p->K > 0) {
-        const int64_t need = p->K * N * 4;
-        if (p->fused_scratch_bytes < need) {
-            if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
-            if (p->d_fused_scratch) (void)hipFree(p->d_fused_scratch);  // (synchronises: no earlier launch still reads it)
-            p->d_fused_scratch = nullptr;
-            p->fused_scratch_bytes = 0;
-            const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_fused_scratch), (size_t)need);
-            if (e != hipSuccess) return (int)e;
-            p->fused_scratch_bytes = need;
-        }
+        if ((rc = grow_owned(&p->d_fused_scratch, &p->fused_scratch_bytes, p->K * N * 4, st)) != 0) return rc;  // (nothing launched)
         const hipError_t e = gespmm::launch_scale_rows(B, fx.col_scale, p->d_fused_scratch, p->K, N, st);
         if (e != hipSuccess) return (int)e;
         Bin = p->d_fused_scratch;
@@ -977,11 +979,11 @@ int gespmm_plan_spmm_fused_f32(gespmm_plan* plan, const float* B, const float* c
                                float* C, int64_t N, void* stream) {
     if (!plan || N < 0) return GESPMM_EINVAL;
     const gespmm::FusedVectors fx = {col_scale, row_scale, bias};
-    if (N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
-    if (plan->M > 0 && N > 0 && (!C || (plan->nnz != 0 && !B))) return GESPMM_EINVAL;
-    for (const void* q : {(const void*)B, (const void*)C, (const void*)col_scale, (const void*)row_scale, (const void*)bias})
-        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
-    if (plan->M == 0 || N == 0) return 0;
+    if (N > gespmm::kMaxWidth) return GESPMM_ERANGE;
+    const bool work = plan->M > 0 && N > 0;
+    if (const int rc = gespmm::check_pointers({{C, 4, work}, {B, 4, work && plan->nnz != 0}, {col_scale, 4, false}, {row_scale, 4, false}, {bias, 4, false}}))
+        return rc;
+    if (!work) return 0;
     if (!fx.any()) return plan_run(plan, B, C, N, gespmm::kReduceSum, 0.0f, stream);
     int route = 0;
     return plan_run_fused(plan, B, fx, C, N, stream, false, &route);
@@ -994,7 +996,7 @@ int gespmm_plan_fused_route(const gespmm_plan* plan, int64_t N, int has_col_scal
     const gespmm::FusedVectors fx = {has_col_scale ? &present : nullptr, has_row_scale ? &present : nullptr, has_bias ? &present : nullptr};
     int route = 0;
     const int rc = plan_run_fused(const_cast<gespmm_plan*>(plan), nullptr, fx, nullptr, N, nullptr, true, &route);
-    return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
+    return gespmm::route_result(rc, route);
 }
 
 // 16-bit dense operands through a plan. Two executions with the same bits (plan_policy.cpp: x16_route chooses):
@@ -1005,17 +1007,11 @@ int gespmm_plan_fused_route(const gespmm_plan* plan, int64_t N, int has_col_scal
 static int plan_run_x16(gespmm_plan* p, const void* B, void* C, int dtype, int64_t N, void* stream, bool dry, int b_align, int c_align,
                         int* route_out) {
     *route_out = 0;
-    const gespmm::RouteAnswer ra = route_of(p, N, gespmm::kReduceSum, true);  // the fp32 route of the composition (its temporaries are aligned)
-    // the streaming launch on the task tables is chosen at the byte-equivalent fp32 width, like the lane geometry
-    const gespmm::RouteAnswer rw = (N % 2 == 0 && N > 0) ? route_of(p, N / 2, gespmm::kReduceSum, true) : ra;
-    const float* pval = p->valued ? (p->reordered ? p->d_val : p->val) : nullptr;
-    const gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, p->d_gtasks, p->ngtasks, rw.segmented};
-    const int32_t* rp = p->reordered ? p->d_rowptr : p->rowptr;
-    const int32_t* ci = p->reordered ? p->d_colind : p->colind;
-    const int variant = (p->reordered && rw.vec4) ? GESPMM_VARIANT_CRC_CWM4 : p->variant;
+    // the streaming launch on the task tables is chosen at the byte-equivalent fp32 width, like the lane geometry (the composition's
+    // fp32 route is plan_run's own business: its temporaries are aligned)
+    const gespmm::CsrView A = plan_view(p, route_of(p, (N % 2 == 0 && N > 0) ? N / 2 : N, gespmm::kReduceSum, true));
     int kind = 0;
-    int rc = gespmm::run_spmm_x16(rp, ci, pval, B, C, dtype, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
-                                  p->reordered ? &pl : nullptr, b_align, c_align, true, &kind);
+    int rc = gespmm::run_spmm_x16(A, B, C, dtype, N, p->launch_flags, stream, b_align, c_align, true, &kind);
     if (rc != 0 && rc != gespmm::kX16Unavailable) return rc;
     const int route = gespmm::x16_route(kind);
     *route_out = route;
@@ -1026,8 +1022,7 @@ static int plan_run_x16(gespmm_plan* p, const void* B, void* C, int dtype, int64
         // the launch itself looks at the stream: while it is capturing the selection drops the multi-kernel routes, so the kernel that
         // runs may be the other streaming kernel than the dry answer — what ran is what describe reports — and should the geometry
         // come out unserved the call falls through to the composition
-        rc = gespmm::run_spmm_x16(rp, ci, pval, B, C, dtype, p->M, p->K, N, p->nnz, variant, p->launch_flags, stream,
-                                  p->reordered ? &pl : nullptr, b_align, c_align, false, &kind, &p->x16_last_geo);
+        rc = gespmm::run_spmm_x16(A, B, C, dtype, N, p->launch_flags, stream, b_align, c_align, false, &kind, &p->x16_last_geo);
         if (rc != gespmm::kX16Unavailable) {
             p->x16_last_route = kind;
             return rc;
@@ -1036,19 +1031,10 @@ static int plan_run_x16(gespmm_plan* p, const void* B, void* C, int dtype, int64
     p->x16_last_route = 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t need_b = (p->nnz != 0 && p->K > 0) ? p->K * N * 4 : 0, need_c = p->M * N * 4;
-    if (p->x16_b_bytes < need_b || p->x16_c_bytes < need_c) {
+    if (p->x16_b_bytes < need_b || p->x16_c_bytes < need_c) {  // (one refusal for the pair, before either buffer is touched)
         if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
-        auto grow = [](float** q, int64_t* have, int64_t need) -> hipError_t {
-            if (*have >= need) return hipSuccess;
-            if (*q) (void)hipFree(*q);  // (synchronises: no earlier launch still uses it)
-            *q = nullptr;
-            *have = 0;
-            const hipError_t e = hipMalloc(reinterpret_cast<void**>(q), (size_t)need);
-            if (e == hipSuccess) *have = need;
-            return e;
-        };
-        hipError_t e = grow(&p->d_x16_b, &p->x16_b_bytes, need_b);
-        if (e == hipSuccess) e = grow(&p->d_x16_c, &p->x16_c_bytes, need_c);
+        hipError_t e = resize_owned(&p->d_x16_b, &p->x16_b_bytes, need_b);
+        if (e == hipSuccess) e = resize_owned(&p->d_x16_c, &p->x16_c_bytes, need_c);
         if (e != hipSuccess) return (int)e;
     }
     if (need_b > 0) {
@@ -1061,12 +1047,11 @@ static int plan_run_x16(gespmm_plan* p, const void* B, void* C, int dtype, int64
 }
 
 int gespmm_plan_spmm_x16(gespmm_plan* plan, const void* B, void* C, int dtype, int64_t N, void* stream) {
-    if (!plan || N < 0) return GESPMM_EINVAL;
-    if (dtype != GESPMM_X16_F16 && dtype != GESPMM_X16_BF16) return GESPMM_EINVAL;
-    if (N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
-    if (plan->M > 0 && N > 0 && (!C || (plan->nnz != 0 && !B))) return GESPMM_EINVAL;
-    if (reinterpret_cast<uintptr_t>(B) % 2 != 0 || reinterpret_cast<uintptr_t>(C) % 2 != 0) return GESPMM_EALIGN;
-    if (plan->M == 0 || N == 0) return 0;
+    if (!plan || N < 0 || !gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    if (N > gespmm::kMaxWidth) return GESPMM_ERANGE;
+    const bool work = plan->M > 0 && N > 0;
+    if (const int rc = gespmm::check_pointers({{C, 2, work}, {B, 2, work && plan->nnz != 0}})) return rc;
+    if (!work) return 0;
     int route = 0;
     return plan_run_x16(plan, B, C, dtype, N, stream, false, gespmm::pointer_alignment(B), gespmm::pointer_alignment(C), &route);
 }
@@ -1076,7 +1061,7 @@ int gespmm_plan_x16_route(const gespmm_plan* plan, int64_t N, int b_align, int c
     if (plan->M == 0 || N == 0) return 0;
     int route = 0;
     const int rc = plan_run_x16(const_cast<gespmm_plan*>(plan), nullptr, nullptr, GESPMM_X16_BF16, N, nullptr, true, b_align, c_align, &route);
-    return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
+    return gespmm::route_result(rc, route);
 }
 
 // The multi-head product through a plan (gespmm.h). A storage-order plan runs the stateless call on the caller's arrays. A clustered plan
@@ -1087,59 +1072,41 @@ static int plan_run_heads(gespmm_plan* p, const float* val, const float* B, floa
                           int c_align, int* route_out) {
     *route_out = 0;
     int kind = 0;
-    if (!p->reordered) {
-        gespmm::Geometry geo = {};
-        const int rc = gespmm::run_spmm_heads(nullptr, nullptr, nullptr, nullptr, nullptr, p->M, p->K, H, F, p->nnz, GESPMM_VARIANT_AUTO, 0, nullptr,
-                                              nullptr, b_align, c_align, true, &kind, &geo);
-        if (rc != 0 && rc != gespmm::kHeadsUnavailable) return rc;
-        *route_out = kind;
-        if (dry) return 0;
-        p->heads_last_H = H;
-        p->heads_last_F = F;
-        p->heads_last_route = kind;
-        p->heads_last_geo = geo;
-        return gespmm_csr_spmm_heads_f32(p->rowptr, p->colind, val, B, C, p->M, p->K, H, F, p->nnz, stream);
+    gespmm::CsrView A = plan_view(p, route_of(p, H * F, gespmm::kReduceSum, true));
+    if (p->reordered) {
+        // (narrow_vec4 — four floats per lane at narrow widths — only where a dwordx4 stays inside one head and the operands allow it)
+        if (!(F % 4 == 0 && b_align >= 16 && c_align >= 16)) A.variant = p->variant;
+        A.pl = {p->d_tasks, p->ntasks, p->d_perm, nullptr, 0, false};  // the batch-stream table alone
+        A.val = nullptr;                                                 // (the permuted weights: made below, once the route is known)
+    } else {
+        A.variant = GESPMM_VARIANT_AUTO;  // (what the stateless call below asks with)
     }
-    const int64_t N = H * F;
-    const gespmm::RouteAnswer ra = route_of(p, N, gespmm::kReduceSum, true);
-    const gespmm::PlanLaunch pl = {p->d_tasks, p->ntasks, p->d_perm, nullptr, 0, false};
-    // (narrow_vec4 — four floats per lane at narrow widths — only where a dwordx4 stays inside one head and the operands allow it)
-    const int variant = (ra.vec4 && F % 4 == 0 && b_align >= 16 && c_align >= 16) ? GESPMM_VARIANT_CRC_CWM4 : p->variant;
-    int rc = gespmm::run_spmm_heads(p->d_rowptr, p->d_colind, nullptr, B, C, p->M, p->K, H, F, p->nnz, variant, p->launch_flags, stream, &pl,
-                                    b_align, c_align, true, &kind);
+    gespmm::Geometry geo = {};
+    const int rc = gespmm::run_spmm_heads(A, B, C, H, F, p->reordered ? p->launch_flags : 0, stream, b_align, c_align, true, &kind, &geo);
     if (rc != 0 && rc != gespmm::kHeadsUnavailable) return rc;
-    if (p->d_tasks == nullptr) kind = 0;
+    if (p->reordered && p->d_tasks == nullptr) kind = 0;
     *route_out = kind;
     if (dry) return 0;
     p->heads_last_H = H;
     p->heads_last_F = F;
     p->heads_last_route = kind;
-    if (kind == 0) return gespmm_csr_spmm_heads_f32(p->rowptr, p->colind, val, B, C, p->M, p->K, H, F, p->nnz, stream);
+    if (!p->reordered) p->heads_last_geo = geo;
+    if (!p->reordered || kind == 0) return gespmm_csr_spmm_heads_f32(p->rowptr, p->colind, val, B, C, p->M, p->K, H, F, p->nnz, stream);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int64_t need = p->nnz * H * 4;
-    if (p->heads_val_bytes < need) {
-        if ((rc = gespmm::refuse_allocation_under_capture(st)) != 0) return rc;  // (nothing launched)
-        if (p->d_heads_val) (void)hipFree(p->d_heads_val);  // (synchronises: no earlier launch still reads it)
-        p->d_heads_val = nullptr;
-        p->heads_val_bytes = 0;
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p->d_heads_val), (size_t)need);
-        if (e != hipSuccess) return (int)e;
-        p->heads_val_bytes = need;
-    }
+    if (const int rcg = grow_owned(&p->d_heads_val, &p->heads_val_bytes, p->nnz * H * 4, st)) return rcg;  // (nothing launched)
     const hipError_t e = gespmm::launch_permute_head_values(p->d_rowptr, p->d_src_begin, val, p->d_heads_val, p->M, p->nnz, H, st);
     if (e != hipSuccess) return (int)e;
-    return gespmm::run_spmm_heads(p->d_rowptr, p->d_colind, p->d_heads_val, B, C, p->M, p->K, H, F, p->nnz, variant, p->launch_flags, stream, &pl,
-                                  b_align, c_align, false, &kind, &p->heads_last_geo);
+    A.val = p->d_heads_val;
+    return gespmm::run_spmm_heads(A, B, C, H, F, p->launch_flags, stream, b_align, c_align, false, &kind, &p->heads_last_geo);
 }
 
 int gespmm_plan_spmm_heads_f32(gespmm_plan* plan, const float* val, const float* B, float* C, int64_t H, int64_t F, void* stream) {
     if (!plan) return GESPMM_EINVAL;
-    const int rc = gespmm::check_heads_sizes(plan->M, plan->K, H, F, plan->nnz);
+    int rc = gespmm::check_heads_sizes(plan->M, plan->K, H, F, plan->nnz);
     if (rc != 0) return rc;
     if (plan->M == 0 || F == 0) return 0;
-    if (!C || (plan->nnz != 0 && (!B || !val))) return GESPMM_EINVAL;
-    for (const void* q : {(const void*)val, (const void*)B, (const void*)C})
-        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
+    const bool entries = plan->nnz != 0;
+    if ((rc = gespmm::check_pointers({{C, 4, true}, {B, 4, entries}, {val, 4, entries}})) != 0) return rc;
     int route = 0;
     return plan_run_heads(plan, val, B, C, H, F, stream, false, gespmm::pointer_alignment(B), gespmm::pointer_alignment(C), &route);
 }
@@ -1151,7 +1118,7 @@ int gespmm_plan_heads_route(const gespmm_plan* plan, int64_t H, int64_t F, int b
     if (plan->M == 0 || F == 0) return 0;
     int route = 0;
     const int rc = plan_run_heads(const_cast<gespmm_plan*>(plan), nullptr, nullptr, nullptr, H, F, nullptr, true, b_align, c_align, &route);
-    return rc != 0 ? (rc < 0 ? rc : GESPMM_EINVAL) : route;
+    return gespmm::route_result(rc, route);
 }
 
 // Which kernel, MEASURED: the candidates of a clustered plan — batch-stream, segmented-stream and (at the plan's width) staged-rows —
@@ -1201,9 +1168,7 @@ int gespmm_plan_tune(gespmm_plan* p, const float* B, float* C, int64_t N, int32_
     if (!p->reordered || p->kernel_choice != GESPMM_PLAN_KERNEL_AUTO || p->slab.ev)
         return plan_run(p, B, C, N, gespmm::kReduceSum, 0.0f, stream);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return GESPMM_EINVAL;
-    (void)hipGetLastError();
+    if (gespmm::is_capturing(st)) return GESPMM_EINVAL;
     if (reps <= 0) reps = 3;
     if (reps > 50) reps = 50;
     TuneScope scope(p);
@@ -1314,16 +1279,12 @@ static hipError_t plan_sddmm_edge_maps(gespmm_plan* p, hipStream_t st) {
 static int plan_sddmm(gespmm_plan* p, const void* D1, const void* D2, float* out, int dtype, int64_t N, void* stream) {
     // the checks of gespmm_sddmm_{coo,csr}_{f32,x16}, in their order (routes 1 and 2 launch without passing through them)
     if (!p || N < 0) return GESPMM_EINVAL;
-    if (dtype != 0 && dtype != GESPMM_X16_F16 && dtype != GESPMM_X16_BF16) return GESPMM_EINVAL;
-    if (N > 0x7fffffffLL / 4) return GESPMM_ERANGE;
-    if (p->nnz > gespmm::kSddmmMaxNnz) return GESPMM_ERANGE;
+    if (dtype != 0 && !gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    if (N > gespmm::kMaxWidth || p->nnz > gespmm::kSddmmMaxNnz) return GESPMM_ERANGE;
     if (p->nnz == 0) return 0;
-    if (!out || (N > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
+    const int elem = dtype == 0 ? 4 : 2;
+    if (const int rc = gespmm::check_pointers({{out, 4, true}, {D1, elem, N > 0}, {D2, elem, N > 0}})) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const uintptr_t operand_align = dtype == 0 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(D1) % operand_align != 0 || reinterpret_cast<uintptr_t>(D2) % operand_align != 0 ||
-        reinterpret_cast<uintptr_t>(out) % 4 != 0)
-        return GESPMM_EALIGN;
     // the one launch all three routes make: the stateless library's, for the operand type
     auto launch = [&](const int32_t* rows, bool csr, const int32_t* cols, float* dst) {
         if (dtype == 0)
@@ -1357,7 +1318,7 @@ int gespmm_plan_sddmm_f32(gespmm_plan* p, const float* D1, const float* D2, floa
 }
 
 int gespmm_plan_sddmm_x16(gespmm_plan* p, const void* D1, const void* D2, float* out, int dtype, int64_t N, void* stream) {
-    if (dtype != GESPMM_X16_F16 && dtype != GESPMM_X16_BF16) return GESPMM_EINVAL;
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
     return plan_sddmm(p, D1, D2, out, dtype, N, stream);
 }
 
@@ -1379,9 +1340,7 @@ int gespmm_plan_sddmm_heads_f32(gespmm_plan* p, const float* D1, const float* D2
     const int rc0 = gespmm::check_sddmm_heads_sizes(true, p->M, H, F, p->nnz);
     if (rc0 != 0) return rc0;
     if (p->nnz == 0) return 0;
-    if (!out || (F > 0 && (!D1 || !D2))) return GESPMM_EINVAL;
-    for (const void* q : {(const void*)D1, (const void*)D2, (const void*)out})
-        if (reinterpret_cast<uintptr_t>(q) % 4 != 0) return GESPMM_EALIGN;
+    if (const int rc = gespmm::check_pointers({{out, 4, true}, {D1, 4, F > 0}, {D2, 4, F > 0}})) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int route = F == 0 ? 0 : plan_sddmm_heads_route(p, H, F);
     if (route == 0) return gespmm::run_sddmm_heads(p->rowptr, true, p->colind, D1, D2, out, p->M, p->K, H, F, p->nnz, stream);
@@ -1392,17 +1351,7 @@ int gespmm_plan_sddmm_heads_f32(gespmm_plan* p, const float* D1, const float* D2
     }
     hipError_t e = plan_sddmm_edge_maps(p, st);
     if (e != hipSuccess) return (int)e;
-    const int64_t need = p->nnz * H * 4;
-    if (p->sddmm_heads_tmp_bytes < need) {
-        const int rc = gespmm::refuse_allocation_under_capture(st);
-        if (rc != 0) return rc;  // (nothing launched)
-        if (p->d_sddmm_heads_tmp) (void)hipFree(p->d_sddmm_heads_tmp);  // (synchronises: no earlier launch still reads it)
-        p->d_sddmm_heads_tmp = nullptr;
-        p->sddmm_heads_tmp_bytes = 0;
-        e = hipMalloc(reinterpret_cast<void**>(&p->d_sddmm_heads_tmp), (size_t)need);
-        if (e != hipSuccess) return (int)e;
-        p->sddmm_heads_tmp_bytes = need;
-    }
+    if (const int rcg = grow_owned(&p->d_sddmm_heads_tmp, &p->sddmm_heads_tmp_bytes, p->nnz * H * 4, st)) return rcg;  // (nothing launched)
     const int rc = gespmm::run_sddmm_heads(p->d_coo_row, false, p->d_colind, D1, D2, p->d_sddmm_heads_tmp, p->M, p->K, H, F, p->nnz, stream);
     if (rc != 0) return rc;
     return (int)gespmm::launch_scatter_heads(p->d_sddmm_heads_tmp, p->d_edge_dst, out, p->nnz, H, st);
@@ -1534,8 +1483,7 @@ int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
         n = snprintf(out, (size_t)capacity, "order=storage max_degree=%d l2_model=%.3f->%.3f analysis=%.4fs%s | %s",
                      p->max_degree, p->hits_before, p->hits_after, p->analysis_seconds, why, kern);
     }
-    if (n < 0) return GESPMM_EINVAL;
-    return n < capacity ? n : (int)capacity - 1;
+    return gespmm::describe_result(n, capacity);
 }
 
 void gespmm_release_cached_memory(void) { gespmm::release_cached_arena(); }
