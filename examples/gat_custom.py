@@ -6,6 +6,7 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
     python examples/gat_custom.py                                  # pubmed
     python examples/gat_custom.py --dataset cora --epochs 50
     python examples/gat_custom.py --graph-capture                  # replay each step from a HIP graph (one stream)
+    python examples/gat_custom.py --fused-score                    # el + er added inside the softmax kernel: no score array
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
 chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
@@ -27,19 +28,22 @@ from gcn_custom import load_edges, proc  # noqa: E402
 from gespmm_amd import GATConv, graphs  # noqa: E402
 
 
-def gat_graph(edge_index, n_v, device):
-    """The self-looped graph in both index orders, plus the edge order between them (what ``GATConv.forward`` takes)."""
+def gat_graph(edge_index, n_v, device, int32_order=False):
+    """The self-looped graph in both index orders, plus the edge order between them (what ``GATConv.forward`` takes).
+    ``int32_order``: the order as int32, converted here once — what ``GATConv(fused_score=True)`` hands its kernels as it is."""
     g = proc(edge_index, n_v, device)
     rowptr, colind = g["rowptr"], g["colind"]
     colptr, rowind, order = graphs.transpose_csr(rowptr, colind, n_v, return_order=True)
+    if int32_order:
+        order = order.to(torch.int32)
     return {"rowptr": rowptr, "colind": colind, "colptr": colptr, "rowind": rowind, "csc_order": order}
 
 
 class Net(torch.nn.Module):
-    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6):
+    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False):
         super().__init__()
-        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True)
-        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False)
+        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, fused_score=fused_score)
+        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, fused_score=fused_score)
         self.dropout = dropout
 
     def forward(self, x, g):
@@ -58,13 +62,14 @@ def main():
     ap.add_argument("--epochs", type=int, default=200)
     ap.add_argument("--dropout", type=float, default=0.6)
     ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
+    ap.add_argument("--fused-score", action="store_true", help="GATConv(fused_score=True): score and softmax in one kernel")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device (the ops have no CPU path)")
     device = torch.device("cuda")
 
     edge_index, n_v, n_feat, n_cls = load_edges(args.dataset, device)
-    g = gat_graph(edge_index, n_v, device)
+    g = gat_graph(edge_index, n_v, device, int32_order=args.fused_score)
     gen = torch.Generator().manual_seed(0)
     x = torch.rand(n_v, n_feat, generator=gen)
     x = (x / x.sum(1, keepdim=True)).to(device)
@@ -77,7 +82,7 @@ def main():
         m[perm[a:b]] = True
         masks[name] = m.to(device)
 
-    model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout).to(device)
+    model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
     train_idx = masks["train"].nonzero().squeeze(1)
     y_train = y[train_idx]
@@ -136,8 +141,8 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s" %
-          (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture))
+    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s" %
+          (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
 

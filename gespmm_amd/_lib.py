@@ -109,6 +109,9 @@ EXPORTS = [
     "gespmm_edge_softmax_f32",
     "gespmm_edge_softmax_backward_f32",
     "gespmm_describe_edge_softmax",
+    "gespmm_gat_softmax_f32",
+    "gespmm_gat_softmax_backward_f32",
+    "gespmm_edge_segment_sum_f32",
 ]
 
 X16_F16 = 1
@@ -292,6 +295,12 @@ def _load():
     lib.gespmm_edge_softmax_f32.argtypes = [p, p, p, c_int64, c_int64, c_int64, c_float, p]
     lib.gespmm_edge_softmax_backward_f32.restype = c_int
     lib.gespmm_edge_softmax_backward_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_float, p]
+    lib.gespmm_gat_softmax_f32.restype = c_int
+    lib.gespmm_gat_softmax_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_float, p]
+    lib.gespmm_gat_softmax_backward_f32.restype = c_int
+    lib.gespmm_gat_softmax_backward_f32.argtypes = [p, p, p, p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_float, p]
+    lib.gespmm_edge_segment_sum_f32.restype = c_int
+    lib.gespmm_edge_segment_sum_f32.argtypes = [p, p, p, p, c_int64, c_int64, c_int64, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
     lib.gespmm_describe_edge_softmax.argtypes = [c_int64, c_int64, c_int64, c_char_p, c_int64]
     lib.gespmm_plan_set_values.restype = c_int

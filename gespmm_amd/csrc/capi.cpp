@@ -340,6 +340,18 @@ int check_edge_softmax_sizes(int64_t M, int64_t H, int64_t nnz, float slope) {
     return 0;
 }
 
+// ... and the dense [rows, H] operands and results of the fused forms (el, er, grad_el, the segment sums): 32-bit word positions too
+int check_dense_words(int64_t rows, int64_t H) { return rows > kSddmmMaxNnz / H ? GESPMM_ERANGE : 0; }
+
+// gespmm_gat_softmax_f32 / _backward_f32: the softmax's own checks and K — what makes no sense before what is too large
+int check_gat_softmax_sizes(int64_t M, int64_t K, int64_t H, int64_t nnz, float slope) {
+    const int rc = check_edge_softmax_sizes(M, H, nnz, slope);
+    if (rc == GESPMM_EINVAL || K < 1) return GESPMM_EINVAL;
+    if (rc != 0) return rc;
+    if (const int rcm = check_dense_words(M, H)) return rcm;
+    return check_dense_words(K, H);
+}
+
 // One multi-head SDDMM on checked arguments, nnz > 0: what resolve_sddmm_heads answers, nothing else.
 //   plain        H == 1: launch_sddmm on the caller's arrays.
 //   kernel       one sddmm_heads_kernel; never allocates.
@@ -833,6 +845,54 @@ int gespmm_edge_softmax_backward_f32(const int32_t* rowptr, const float* alpha, 
         return rcp;
     return (int)gespmm::launch_edge_softmax_backward(rowptr, alpha, grad_alpha, leaky ? score : nullptr, grad_score, M, H, nnz, slope,
                                                      gespmm::resolve_edge_softmax(M, nnz, H), reinterpret_cast<hipStream_t>(stream));
+}
+
+/* The same on the additive score el[row] + er[col] of a graph attention layer (gespmm.h): the score is a source trait of the one kernel. */
+int gespmm_gat_softmax_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* out, int64_t M, int64_t K,
+                           int64_t H, int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_gat_softmax_sizes(M, K, H, nnz, slope);
+    if (rc != 0) return rc;
+    if (nnz == 0) return 0;
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {el, 4, true}, {er, 4, true}, {out, 4, true}})) return rcp;
+    return (int)gespmm::launch_gat_softmax(rowptr, colind, el, er, out, M, K, H, nnz, slope, gespmm::resolve_edge_softmax(M, nnz, H),
+                                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_gat_softmax_backward_f32(const int32_t* rowptr, const int32_t* colind, const float* alpha, const float* grad_alpha,
+                                    const float* el, const float* er, float* grad_score, float* grad_el, int64_t M, int64_t K, int64_t H,
+                                    int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_gat_softmax_sizes(M, K, H, nnz, slope);
+    if (rc != 0) return rc;
+    if (M == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(M, nnz, H);
+    if (nnz == 0) {  // every word of grad_el is still written
+        if (const int rcp = check_pointers({{grad_el, 4, true}})) return rcp;
+        return (int)gespmm::launch_gat_softmax_backward(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, grad_el, M, K, H, 0,
+                                                        slope, r, st);
+    }
+    const bool leaky = slope != 1.0f;  // (the sign of el + er is looked at only then)
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {alpha, 4, true}, {grad_alpha, 4, true}, {grad_score, 4, true},
+                                        {grad_el, 4, true}, {leaky ? colind : nullptr, 4, leaky}, {leaky ? el : nullptr, 4, leaky},
+                                        {leaky ? er : nullptr, 4, leaky}}))
+        return rcp;
+    return (int)gespmm::launch_gat_softmax_backward(rowptr, leaky ? colind : nullptr, alpha, grad_alpha, leaky ? el : nullptr,
+                                                    leaky ? er : nullptr, grad_score, grad_el, M, K, H, nnz, slope, r, st);
+}
+
+int gespmm_edge_segment_sum_f32(const int32_t* ptr, const int32_t* order, const float* x, float* out, int64_t S, int64_t H, int64_t nnz,
+                                void* stream) {
+    int rc = gespmm::check_edge_softmax_sizes(S, H, nnz, 1.0f);
+    if (rc == 0) rc = gespmm::check_dense_words(S, H);
+    if (rc != 0) return rc;
+    if (S == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0) {  // every word of out is still written
+        if (const int rcp = check_pointers({{out, 4, true}})) return rcp;
+        return (int)gespmm::launch_edge_segment_sum(nullptr, nullptr, nullptr, out, S, H, 0, gespmm::resolve_edge_softmax(S, 0, H), st);
+    }
+    if (const int rcp = check_pointers({{ptr, 4, true}, {x, 4, true}, {out, 4, true}, {order, 4, false}})) return rcp;
+    return (int)gespmm::launch_edge_segment_sum(ptr, order, x, out, S, H, nnz, gespmm::resolve_edge_softmax(S, nnz, H), st);
 }
 
 int gespmm_describe_edge_softmax(int64_t M, int64_t nnz, int64_t H, char* out, int64_t capacity) {

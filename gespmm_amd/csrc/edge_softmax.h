@@ -35,4 +35,23 @@ hipError_t launch_edge_softmax_backward(const int32_t* rowptr, const float* alph
                                         float* grad_score, int64_t M, int64_t H, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r,
                                         hipStream_t st);
 
+
+// ---- the same softmax on the additive score of a graph attention layer, score[e, h] = fl(el[row(e), h] + er[colind[e], h]), which is
+// never written (gespmm_gat_softmax_f32 / _backward_f32): el is [M, H], er [K, H], colind within [0, K). The score is a source trait of
+// the one kernel; per pair el is loaded once, per entry colind and er (a row longer than kEdgeSoftmaxIT W entries gathers again in
+// each sweep). Bits: those of the calls above on the score array the width-2 SDDMM writes. M H and K H <= kSddmmMaxNnz, K >= 1.
+hipError_t launch_gat_softmax(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* out, int64_t M,
+                              int64_t K, int64_t H, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st);
+// grad_score as launch_edge_softmax_backward, and grad_el[r, h] = the sum of the row's grad_score values as stored, every word of
+// [M, H] written (empty rows +0; nnz == 0: zero-filled). colind, el, er are read only when slope != 1 (the sign of fl(el + er)).
+// Summation order of grad_el, pinned: lane l adds its entries lo + l + t W in entry order, plain adds from +0, a masked position adds
+// +0; then the xor butterfly W/2 .. 1 (W = 64 for d > L). The register regime and the sweep regime give the same chain.
+hipError_t launch_gat_softmax_backward(const int32_t* rowptr, const int32_t* colind, const float* alpha, const float* grad_alpha,
+                                       const float* el, const float* er, float* grad_score, float* grad_el, int64_t M, int64_t K, int64_t H,
+                                       int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st);
+// out[s, h] = sum over p in [ptr[s], ptr[s + 1]) of x[(order ? order[p] : p) H + h], in the order above (gespmm_edge_segment_sum_f32):
+// every word of [S, H] written. r = resolve_edge_softmax(S, nnz, H). order: int32[nnz] within [0, nnz), or null. S H <= kSddmmMaxNnz.
+hipError_t launch_edge_segment_sum(const int32_t* ptr, const int32_t* order, const float* x, float* out, int64_t S, int64_t H, int64_t nnz,
+                                   const EdgeSoftmaxLaunch& r, hipStream_t st);
+
 }  // namespace gespmm

@@ -44,6 +44,7 @@ the dot-product score s[e, h] = <q[row(e), h, :], k[col(e), h, :]>; each has the
 instead of one ``sddmm.csr_sddmm`` per head on copies (the default, kept as it was): same bits.
 ``EdgeSoftmaxFunction`` is the step between the two — softmax over the entries of each row, per head, with the leaky ReLU of a GAT
 fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` the graph attention layer composed from the three.
+``GATSoftmaxFunction`` is the first two in one: the softmax of el[row] + er[col] with no score array (``GATConv(fused_score=True)``).
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -255,6 +256,49 @@ class EdgeSoftmaxFunction(torch.autograd.Function):
         return None, grad_score, None
 
 
+class GATSoftmaxFunction(torch.autograd.Function):
+    """alpha[e, h] = softmax over the entries e of each CSR row of leaky_relu(el[row(e), h] + er[col(e), h], negative_slope) — the
+    attention weights of a graph attention layer straight from the two per-node terms (``softmax.gat_edge_softmax``): no score array is
+    written, saved or read.
+
+        GATSoftmaxFunction.apply(rowptr, colind, colptr, csc_order, el, er, negative_slope=None) -> f32[nnz, H]
+
+    ``el`` f32[M, H], ``er`` f32[K, H]; ``colptr, _, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. The
+    bits of ``alpha`` are those of ``EdgeSoftmaxFunction`` on the score of ``MultiHeadSDDMMFunction`` with q = (el, 1), k = (1, er).
+    Saved: ``alpha``, and ``el``, ``er`` when a slope is given (their sum's sign) — nothing else of size nnz H. Backward is two
+    launches: ``softmax.gat_edge_softmax_backward`` (grad_score, and grad_el as its row sums), then ``softmax.edge_segment_sum`` on
+    ``(colptr, csc_order)`` for grad_er, only when ``er`` requires grad. An int64 ``csc_order`` is converted to int32 once per forward
+    and kept for the backward; pass an int32 one to convert it once per graph. Index tensors get no gradient."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, csc_order, el, er, negative_slope=None):
+        el_c, er_c = el.contiguous(), er.contiguous()
+        alpha = _softmax.gat_edge_softmax(rowptr, colind, el_c, er_c, negative_slope=negative_slope)
+        order = csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)
+        ctx.graph = (rowptr, colind, colptr, order.contiguous())
+        ctx.negative_slope = negative_slope
+        if negative_slope is None:
+            ctx.save_for_backward(alpha)
+        else:
+            ctx.save_for_backward(alpha, el_c, er_c)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        rowptr, colind, colptr, order = ctx.graph
+        alpha = ctx.saved_tensors[0]
+        el, er = ctx.saved_tensors[1:] if ctx.negative_slope is not None else (None, None)
+        grad_el = grad_er = None
+        if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
+            grad_score, grad_el = _softmax.gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha.contiguous(), el=el, er=er,
+                                                                     negative_slope=ctx.negative_slope)
+            if ctx.needs_input_grad[5]:
+                grad_er = _softmax.edge_segment_sum(colptr, grad_score, order=order)
+            if not ctx.needs_input_grad[4]:
+                grad_el = None
+        return None, None, None, None, grad_el, grad_er, None
+
+
 def glorot(tensor):
     """torch_geometric.nn.inits.glorot: U(-a, a), a = sqrt(6 / (fan_in + fan_out))."""
     if tensor is not None:
@@ -375,14 +419,19 @@ class GATConv(torch.nn.Module):
     additive score is a width-2 dot product whose pinned chain is fmaf(1, er, fmaf(el, 1, 0)) = fl(el + er) (or el + er across two lanes),
     and its backward hands grad_el and grad_er back as component 0 of grad_q and component 1 of grad_k.
 
-        GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True)
+        GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False)
         forward(x, rowptr, colind, colptr, rowind, csc_order)
+
+    ``fused_score=True``: the score and the softmax are ONE ``GATSoftmaxFunction`` — el + er is added inside the softmax kernel, no
+    score, q or k tensor exists, and the backward sums grad_score over rows and columns in two launches. Same output bits. Pass an
+    int32 ``csc_order`` then (an int64 one is converted in every forward).
 
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
     ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False):
         super().__init__()
+        self.fused_score = bool(fused_score)
         if heads < 1:
             raise ValueError("heads must be at least 1")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, int(heads)
@@ -408,10 +457,13 @@ class GATConv(torch.nn.Module):
         xw = (x @ self.weight).view(n, H, F)
         el = (xw * self.att_dst).sum(-1)
         er = (xw * self.att_src).sum(-1)
-        q = torch.stack((el, torch.ones_like(el)), dim=-1)  # [n, H, 2]
-        k = torch.stack((torch.ones_like(er), er), dim=-1)
-        score = MultiHeadSDDMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, q, k)
-        alpha = EdgeSoftmaxFunction.apply(rowptr, score, self.negative_slope)
+        if self.fused_score:
+            alpha = GATSoftmaxFunction.apply(rowptr, colind, colptr, csc_order, el, er, self.negative_slope)
+        else:
+            q = torch.stack((el, torch.ones_like(el)), dim=-1)  # [n, H, 2]
+            k = torch.stack((torch.ones_like(er), er), dim=-1)
+            score = MultiHeadSDDMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, q, k)
+            alpha = EdgeSoftmaxFunction.apply(rowptr, score, self.negative_slope)
         out = MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, xw, alpha, None, True)
         out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
         return out if self.bias is None else out + self.bias

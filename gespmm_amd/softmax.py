@@ -3,6 +3,9 @@ gespmm_edge_softmax_backward_f32 — the reference has no counterpart).
 
     edge_softmax(rowptr, score, out=None, negative_slope=None)                                    -> f32, the shape of score
     edge_softmax_backward(rowptr, alpha, grad_alpha, score=None, negative_slope=None, out=None)   -> f32, the shape of alpha
+    gat_edge_softmax(rowptr, colind, el, er, negative_slope=None, out=None)                       -> f32[nnz, H]
+    gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=None, er=None, negative_slope=None) -> (grad_score, grad_el)
+    edge_segment_sum(ptr, x, order=None, out=None)                                                -> f32[S, H] (or f32[S])
 
 ``score`` is f32[nnz] or f32[nnz, H] in CSR edge order — what ``sddmm.csr_sddmm`` / ``sddmm.csr_sddmm_heads`` return and what
 ``spmm.csr_spmm`` / ``spmm.csr_spmm_heads`` take as edge weights. For row r with entries [lo, hi) and head h
@@ -13,8 +16,14 @@ gespmm_edge_softmax_backward_f32 — the reference has no counterpart).
 in ONE kernel on the row pointers as they are: no expanded row ids, no ``segment_reduce`` / ``repeat_interleave`` passes over an
 [nnz, H] array. Empty rows write nothing. Head h has the bits of the single-head call on ``score[:, h].contiguous()``; the bits do not
 depend on H, on stream capture or on the run (``_lib.describe_edge_softmax``). ``rowptr[M] == score.shape[0]`` is a precondition, as
-everywhere in this package; ``out`` must not overlap an input. fp32 only: 16-bit and fp64 tensors raise TypeError. Both calls go
-through ctypes."""
+everywhere in this package; ``out`` must not overlap an input. fp32 only: 16-bit and fp64 tensors raise TypeError.
+
+``gat_edge_softmax`` is the same softmax on the additive score of a graph attention layer, ``score[e, h] = el[row(e), h] +
+er[colind[e], h]``, computed inside the kernel: no ``[nnz, H]`` score exists, and the result has the bits of ``edge_softmax`` on the
+score ``sddmm.csr_sddmm_heads`` writes for ``q = (el, 1), k = (1, er)``. Its backward returns ``grad_score`` and, from the same launch,
+``grad_el = sum_row(grad_score)``; ``edge_segment_sum`` on the CSC arrays (``ptr=colptr, order=csc_order``) gives ``grad_er`` without a
+permuted copy. The sums have a pinned order (include/gespmm.h), the one ``edge_segment_sum(rowptr, grad_score)`` reproduces.
+All calls go through ctypes."""
 import torch
 
 from ._lib import check, lib
@@ -99,4 +108,129 @@ def edge_softmax_backward(rowptr, alpha, grad_alpha, score=None, negative_slope=
         rc = lib.gespmm_edge_softmax_backward_f32(_ptr(rowptr), _ptr(alpha), _ptr(grad_alpha), _ptr(score) if score is not None else None,
                                                   _ptr(out), M, H, nnz, slope, _stream(dev))
     check(rc, "gespmm_edge_softmax_backward_f32")
+    return out
+
+
+def _index_vector(t, name, dev, n=None):
+    """int32, contiguous, one-dimensional, on ``dev`` (``n`` entries when given)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != torch.int32:
+        raise TypeError("%s must have dtype torch.int32, got %s" % (name, t.dtype))
+    if t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError("%s must be a contiguous vector%s" % (name, "" if n is None else " of %d entries" % n))
+    if t.device != dev:
+        raise ValueError("%s must live on %s, as the other operands" % (name, dev))
+
+
+def _node_array(t, name, like=None, rows=None):
+    """fp32, contiguous, [rows, H] on a HIP device; the head count and device of ``like`` when that is given."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must have dtype torch.float32, got %s" % (name, t.dtype))
+    if t.dim() != 2 or t.shape[1] < 1:
+        raise ValueError("%s must be [rows, H] with at least one head" % name)
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    if t.device.type != "cuda":
+        raise ValueError("%s must be a HIP (cuda) device tensor; gespmm_amd has no CPU path" % name)
+    if rows is not None and t.shape[0] != rows:
+        raise ValueError("%s must have %d rows, got %d" % (name, rows, t.shape[0]))
+    if like is not None and (t.shape[1] != like.shape[1] or t.device != like.device):
+        raise ValueError("%s must have %d heads on %s, as the other operands" % (name, like.shape[1], like.device))
+
+
+def _checked_rowptr(rowptr, dev=None):
+    if not isinstance(rowptr, torch.Tensor):
+        raise TypeError("rowptr must be a torch.Tensor")
+    if rowptr.dtype != torch.int32:
+        raise TypeError("rowptr must have dtype torch.int32, got %s" % rowptr.dtype)
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or not rowptr.is_contiguous():
+        raise ValueError("rowptr must be a contiguous vector of M + 1 entries")
+    if dev is not None and rowptr.device != dev:
+        raise ValueError("rowptr must live on %s, as the other operands" % (dev,))
+    return rowptr.numel() - 1
+
+
+def gat_edge_softmax(rowptr, colind, el, er, negative_slope=None, out=None):
+    """``edge_softmax(rowptr, el[row] + er[colind], negative_slope)`` with the score never written (gespmm_gat_softmax_f32): ``el``
+    f32[M, H] scores the row of an entry, ``er`` f32[K, H] its column; ``colind`` int32[nnz] within [0, K) (a precondition). One launch
+    that writes ``out`` f32[nnz, H] only; the bits are those of ``edge_softmax`` on the score array of the width-2 ``csr_sddmm_heads``."""
+    slope = _slope(negative_slope)
+    M = _checked_rowptr(rowptr)
+    _node_array(el, "el", rows=M)
+    _node_array(er, "er", like=el)
+    dev = el.device
+    _checked_rowptr(rowptr, dev)
+    _index_vector(colind, "colind", dev)
+    nnz, H, K = colind.numel(), el.shape[1], er.shape[0]
+    if out is None:
+        out = torch.empty(nnz, H, dtype=torch.float32, device=dev)
+    else:
+        _edge_array(out, "out")
+        if out.shape != (nnz, H) or out.device != dev:
+            raise ValueError("out must be f32[%d, %d] on %s" % (nnz, H, dev))
+    with _on_device(dev):
+        rc = lib.gespmm_gat_softmax_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(out), M, K, H, nnz, slope, _stream(dev))
+    check(rc, "gespmm_gat_softmax_f32")
+    return out
+
+
+def gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=None, er=None, negative_slope=None):
+    """Backward of ``gat_edge_softmax`` in one launch (gespmm_gat_softmax_backward_f32) -> ``(grad_score, grad_el)``: ``grad_score``
+    f32[nnz, H] is ``edge_softmax_backward`` with the sign of ``el[row] + er[colind]`` in place of a score array, ``grad_el`` f32[M, H]
+    its row sums (empty rows +0). ``el`` and ``er`` are needed exactly when ``negative_slope`` is given. ``grad_er`` is
+    ``edge_segment_sum(colptr, grad_score, order=csc_order)``."""
+    slope = _slope(negative_slope)
+    M = _checked_rowptr(rowptr)
+    _edge_array(alpha, "alpha")
+    if alpha.dim() != 2:
+        raise ValueError("alpha must be [nnz, H]")
+    _edge_array(grad_alpha, "grad_alpha", like=alpha)
+    dev = alpha.device
+    _checked_rowptr(rowptr, dev)
+    nnz, H = alpha.shape
+    _index_vector(colind, "colind", dev, nnz)
+    K = 1
+    if slope != 1.0:
+        if el is None or er is None:
+            raise ValueError("negative_slope needs el and er (the forward's inputs)")
+        _node_array(el, "el", like=alpha, rows=M)
+        _node_array(er, "er", like=alpha)
+        K = er.shape[0]
+    else:
+        el = er = None
+    grad_score = torch.empty_like(alpha)
+    grad_el = torch.empty(M, H, dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib.gespmm_gat_softmax_backward_f32(_ptr(rowptr), _ptr(colind), _ptr(alpha), _ptr(grad_alpha),
+                                                 _ptr(el) if el is not None else None, _ptr(er) if er is not None else None,
+                                                 _ptr(grad_score), _ptr(grad_el), M, K, H, nnz, slope, _stream(dev))
+    check(rc, "gespmm_gat_softmax_backward_f32")
+    return grad_score, grad_el
+
+
+def edge_segment_sum(ptr, x, order=None, out=None):
+    """``out[s, h] = sum of x[order[p], h] over p in [ptr[s], ptr[s + 1])`` (``order=None``: ``x[p, h]``) in one launch, in the pinned
+    order of the edge softmax (gespmm_edge_segment_sum_f32). ``x`` f32[nnz] or f32[nnz, H]; ``order`` int32[nnz] within [0, nnz) — an
+    int64 order raises TypeError, convert it once; ``out`` f32[S, H] (f32[S] for a one-dimensional ``x``), every word written, empty
+    segments +0. With ``ptr=colptr, order=csc_order`` it sums an edge array over the columns of the pattern."""
+    dev, S, H, nnz = _checked(ptr, x, "x")
+    if order is not None:
+        _index_vector(order, "order", dev, nnz)
+    shape = (S, H) if x.dim() == 2 else (S,)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch.Tensor")
+        if out.dtype != torch.float32:
+            raise TypeError("out must have dtype torch.float32, got %s" % out.dtype)
+        if out.shape != shape or out.device != dev or not out.is_contiguous():
+            raise ValueError("out must be contiguous f32%s on %s" % (list(shape), dev))
+    with _on_device(dev):
+        rc = lib.gespmm_edge_segment_sum_f32(_ptr(ptr), _ptr(order) if order is not None else None, _ptr(x), _ptr(out), S, H, nnz,
+                                             _stream(dev))
+    check(rc, "gespmm_edge_segment_sum_f32")
     return out

@@ -29,6 +29,8 @@
  *   gespmm_cluster_rows / gespmm_simulate_l2_hits <- (new) the plan's host-side row clustering and its L2 model
  *   gespmm_baseline_atomic_scatter_f32 <- Gunrock app's edge map  gunrock-test/app/spmm/spmm_enactor.cuh:92-105
  *   gespmm_edge_softmax_f32 / _backward_f32 <- (new) softmax over the entries of a CSR row, per head; no reference counterpart
+ *   gespmm_gat_softmax_f32 / _backward_f32 / gespmm_edge_segment_sum_f32 <- (new) the same softmax on the additive score of a graph
+ *                               attention layer, el[row] + er[col], never written; the per-segment sum of an edge array
  *   gespmm_baseline_copy_f32 <- (new) streaming-copy yardstick for the roofline record; no reference counterpart
  *
  * Conventions (all device entry points):
@@ -571,6 +573,48 @@ int gespmm_edge_softmax_backward_f32(const int32_t* rowptr, const float* alpha, 
  * out / capacity / return value as gespmm_describe_sddmm: the text is truncated to capacity - 1 characters and NUL-terminated, the
  * return value is the number of characters written, or a GESPMM_E* code for sizes the calls above refuse. */
 int gespmm_describe_edge_softmax(int64_t M, int64_t nnz, int64_t H, char* out, int64_t capacity);
+/*
+ * The edge softmax on the additive score of a graph attention layer (since 0.5), with no score array:
+ *
+ *     score[p, h] = fl(el[r H + h] + er[colind[p] H + h])        (one fp32 add; r = the row of entry p)
+ *     out = gespmm_edge_softmax_f32(rowptr, score, ..)           bit for bit, in ONE kernel that writes out only
+ *
+ * el is [M x H], er [K x H], out [nnz x H], fp32, contiguous, row-major; colind has nnz entries within [0, K) (a precondition, not
+ * checked). These are the bits of gespmm_sddmm_csr_heads_f32 at F = 2 on q = (el, 1), k = (1, er) followed by the softmax above: the
+ * width-2 chain fmaf(1, er, fmaf(el, 1, 0)) is fl(el + er). Lane geometry, W, L and the summation order are the softmax's own
+ * (gespmm_describe_edge_softmax(M, nnz, H)); a row of more than 4 W entries gathers colind and er again in each of its three sweeps.
+ * A NaN or +inf in el makes the (row, head) pairs of its own row NaN and nothing else.
+ * Checks, in this order: what gespmm_edge_softmax_f32 answers GESPMM_EINVAL for on (M, H, nnz, slope), or K < 1 -> GESPMM_EINVAL; its
+ * range limits, or M H or K H > 2^31 - 4097 (32-bit word positions) -> GESPMM_ERANGE; nnz == 0 -> 0 without looking at pointers; NULL -> GESPMM_EINVAL; a pointer not 4-byte
+ * aligned -> GESPMM_EALIGN. out must not overlap an input (not checked). No atomics, no workspace, no allocation: capturable.
+ */
+int gespmm_gat_softmax_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* out, int64_t M, int64_t K,
+                           int64_t H, int64_t nnz, float slope, void* stream);
+/*
+ * Its backward (since 0.5), one kernel: grad_score [nnz x H] has the bits of gespmm_edge_softmax_backward_f32 with score = fl(el + er)
+ * (colind, el, er are read for that sign only, and only when slope != 1: they may be NULL when slope == 1), and
+ *
+ *     grad_el[r H + h] = sum over the entries p of row r of grad_score[p H + h]          (the fp32 values as stored)
+ *
+ * [M x H], every word written (an empty row: +0). Summation order (pinned): lane l of the row's W lanes adds its entries lo + l + t W
+ * in entry order with plain adds starting from +0, then the xor butterfly with masks W/2 .. 1; rows of more than L entries the same at
+ * W = 64. grad_er is gespmm_edge_segment_sum_f32 of grad_score on the CSC arrays. Checks as the forward; nnz == 0 looks at grad_el
+ * alone (NULL -> GESPMM_EINVAL, alignment) and zero-fills it.
+ */
+int gespmm_gat_softmax_backward_f32(const int32_t* rowptr, const int32_t* colind, const float* alpha, const float* grad_alpha,
+                                    const float* el, const float* er, float* grad_score, float* grad_el, int64_t M, int64_t K, int64_t H,
+                                    int64_t nnz, float slope, void* stream);
+/*
+ * Per-segment sum of an edge array (since 0.5): out[s H + h] = sum over p in [ptr[s], ptr[s + 1]) of x[(order ? order[p] : p) H + h].
+ * ptr has S + 1 entries, ptr[S] == nnz; x is [nnz x H]; order is NULL or a permutation-like int32[nnz] within [0, nnz) (not checked);
+ * out is [S x H], every word written (an empty segment: +0). The geometry and the pinned order above, with W and L from
+ * gespmm_describe_edge_softmax(S, nnz, H); on (rowptr, NULL) it reproduces grad_el of the call above bit for bit, on (colptr,
+ * csc_order) it gives grad_er with no permuted copy of grad_score. Checks: H < 1, a negative size, S == 0 with nnz > 0 ->
+ * GESPMM_EINVAL; S > 2^31 - 4097, nnz H or S H > 2^31 - 4097 -> GESPMM_ERANGE; S == 0 -> 0; nnz == 0 looks at out alone and
+ * zero-fills it; NULL (ptr, x, out) -> GESPMM_EINVAL; alignment -> GESPMM_EALIGN. One kernel, capturable.
+ */
+int gespmm_edge_segment_sum_f32(const int32_t* ptr, const int32_t* order, const float* x, float* out, int64_t S, int64_t H, int64_t nnz,
+                                void* stream);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
