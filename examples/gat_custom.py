@@ -7,6 +7,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
     python examples/gat_custom.py --dataset cora --epochs 50
     python examples/gat_custom.py --graph-capture                  # replay each step from a HIP graph (one stream)
     python examples/gat_custom.py --fused-score                    # el + er added inside the softmax kernel: no score array
+    python examples/gat_custom.py --fused-aggregate                # ... and the weights computed inside the aggregation: no alpha array
+    python examples/gat_custom.py --seed 0 --fused-aggregate       # seeded parameters and dropout: the losses of --seed 0 --fused-score
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
 chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
@@ -40,10 +42,10 @@ def gat_graph(edge_index, n_v, device, int32_order=False):
 
 
 class Net(torch.nn.Module):
-    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False):
+    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False, fused_aggregate=False):
         super().__init__()
-        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, fused_score=fused_score)
-        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, fused_score=fused_score)
+        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, fused_score=fused_score, fused_aggregate=fused_aggregate)
+        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, fused_score=fused_score, fused_aggregate=fused_aggregate)
         self.dropout = dropout
 
     def forward(self, x, g):
@@ -63,13 +65,18 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.6)
     ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
     ap.add_argument("--fused-score", action="store_true", help="GATConv(fused_score=True): score and softmax in one kernel")
+    ap.add_argument("--fused-aggregate", action="store_true",
+                    help="GATConv(fused_aggregate=True): softmax and aggregation in one kernel, no [nnz, H] array saved")
+    ap.add_argument("--seed", type=int, default=None,
+                    help="torch.manual_seed before the model is made (parameters and dropout masks): two runs, or two fused settings, "
+                         "then print the same losses")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device (the ops have no CPU path)")
     device = torch.device("cuda")
 
     edge_index, n_v, n_feat, n_cls = load_edges(args.dataset, device)
-    g = gat_graph(edge_index, n_v, device, int32_order=args.fused_score)
+    g = gat_graph(edge_index, n_v, device, int32_order=args.fused_score or args.fused_aggregate)
     gen = torch.Generator().manual_seed(0)
     x = torch.rand(n_v, n_feat, generator=gen)
     x = (x / x.sum(1, keepdim=True)).to(device)
@@ -82,7 +89,10 @@ def main():
         m[perm[a:b]] = True
         masks[name] = m.to(device)
 
-    model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score).to(device)
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+    model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score,
+                fused_aggregate=args.fused_aggregate).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
     train_idx = masks["train"].nonzero().squeeze(1)
     y_train = y[train_idx]
@@ -141,8 +151,8 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s" %
-          (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score))
+    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s" %
+          (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score, args.fused_aggregate))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
 

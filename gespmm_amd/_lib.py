@@ -112,6 +112,9 @@ EXPORTS = [
     "gespmm_gat_softmax_f32",
     "gespmm_gat_softmax_backward_f32",
     "gespmm_edge_segment_sum_f32",
+    "gespmm_gat_softmax_stats_f32",
+    "gespmm_gat_aggregate_f32",
+    "gespmm_gat_aggregate_route",
 ]
 
 X16_F16 = 1
@@ -301,6 +304,12 @@ def _load():
     lib.gespmm_gat_softmax_backward_f32.argtypes = [p, p, p, p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_float, p]
     lib.gespmm_edge_segment_sum_f32.restype = c_int
     lib.gespmm_edge_segment_sum_f32.argtypes = [p, p, p, p, c_int64, c_int64, c_int64, p]
+    lib.gespmm_gat_softmax_stats_f32.restype = c_int
+    lib.gespmm_gat_softmax_stats_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_float, p]
+    lib.gespmm_gat_aggregate_f32.restype = c_int
+    lib.gespmm_gat_aggregate_f32.argtypes = [p, p, p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int, p]
+    lib.gespmm_gat_aggregate_route.restype = c_int
+    lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
     lib.gespmm_describe_edge_softmax.argtypes = [c_int64, c_int64, c_int64, c_char_p, c_int64]
     lib.gespmm_plan_set_values.restype = c_int
@@ -409,6 +418,17 @@ def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):
     rc = lib.gespmm_heads_route(int(M), int(K), int(H), int(F), int(nnz), int(b_align), int(c_align), geo)
     if rc < 0:
         raise GespmmError(rc, "gespmm_heads_route")
+    return rc, tuple(int(x) for x in geo)
+
+
+def gat_aggregate_route(M, K, H, F, nnz, transposed=False, b_align=16, c_align=16):
+    """What gespmm_gat_aggregate_f32 would do for these sizes and operand alignments (gespmm_gat_aggregate_route: host only):
+    ``(route, (V, S, W, rpw))`` — route 1 the one kernel with that lane geometry, route 0 the composition (zeros). ``M``, ``K`` are
+    the rows and columns of the pattern in both modes."""
+    geo = (ctypes.c_int32 * 4)()
+    rc = lib.gespmm_gat_aggregate_route(int(M), int(K), int(H), int(F), int(nnz), 1 if transposed else 0, int(b_align), int(c_align), geo)
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_gat_aggregate_route")
     return rc, tuple(int(x) for x in geo)
 
 

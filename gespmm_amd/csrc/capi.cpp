@@ -23,6 +23,7 @@
 #include "select.h"
 #include "auto_plan.h"
 #include "edge_softmax.h"
+#include "gat_aggregate.h"
 #include "plan.h"
 #include "sddmm_heads.h"
 #include "spmm_heads.h"
@@ -320,6 +321,47 @@ int run_spmm_heads(const CsrView& A, const float* B, float* C, int64_t H, int64_
     a.H = (int32_t)H;
     a.F = (int32_t)F;
     return (int)launch_spmm_heads(a, r.sel.geo, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The fused GAT aggregation (gat_aggregate.h): ONE kernel or nothing (kHeadsUnavailable: the caller materialises the weights and calls
+// the multi-head product). A is the pattern the segments come from — (rowptr, colind) with M rows, or (colptr, rowind) with K — and
+// A.K the rows of B; the geometry is run_spmm_heads's, H = 1 included. The stream is never asked.
+int check_gat_softmax_sizes(int64_t M, int64_t K, int64_t H, int64_t nnz, float slope);  // (below, with the softmax's other checks)
+int run_gat_aggregate(const CsrView& A, const GatTerms& t, const float* B, float* C, int64_t H, int64_t F, bool transposed, void* stream,
+                      int b_align, int c_align, bool dry_run, int* kind, Geometry* geo_out) {
+    *kind = 0;
+    if (H < 1 || H > kHeadsMax || A.M <= 0 || F <= 0 || A.nnz < 0 || b_align < 4 || c_align < 4) return kHeadsUnavailable;
+    // GESPMM_GAT_AGGREGATE_ROUTE=composition pins route 0 (read per call: scripts/gat_aggregate_timing.py measures both in one process)
+    if (const char* env = getenv("GESPMM_GAT_AGGREGATE_ROUTE"))
+        if (!strcmp(env, "composition")) return kHeadsUnavailable;
+    const int64_t N = H * F;
+    if ((uint64_t)A.K * (uint64_t)N * 4ull >= (1ull << 32) || A.nnz * H >= (1ll << 31)) return kHeadsUnavailable;  // 32-bit offsets only
+    const int flags = kFlagBatchStream | kFlagStrictOrder | kFlagNoSlabBlocked;
+    const StreamQuery q = {A.M, A.K, N, A.nnz, vec_limit(F, std::min(b_align, c_align)), A.variant, flags, kReduceSum, nullptr, nullptr, false, nullptr};
+    StreamLaunch r;
+    const int rc = resolve_stream_launch(q, &r);
+    if (rc != 0) return rc == kNotStreaming ? kHeadsUnavailable : GESPMM_EINVAL;
+    if (!heads_geometry_served(r.sel.geo, false)) return kHeadsUnavailable;
+    *kind = 1;
+    if (geo_out) *geo_out = r.sel.geo;
+    if (dry_run) return 0;
+    GatAggregateArgs a = stream_args<GatAggregateArgs>(A, B, C, N, r);
+    a.H = (int32_t)H;
+    a.F = (int32_t)F;
+    a.el = t.el;
+    a.er = t.er;
+    a.stats = t.stats;
+    a.slope = t.slope;
+    return (int)launch_gat_aggregate(a, r.sel.geo, transposed, reinterpret_cast<hipStream_t>(stream));
+}
+
+// gespmm_gat_aggregate_f32 / gespmm_gat_aggregate_route: the ladder of gespmm_gat_softmax_f32 on (M, K, H, nnz), then the multi-head
+// product's on the width (segments x rows of B: M x K, transposed K x M)
+int check_gat_aggregate_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, bool transposed) {
+    if (F < 0) return GESPMM_EINVAL;
+    const int rc = check_gat_softmax_sizes(M, K, H, nnz, slope);
+    if (rc != 0) return rc;
+    return check_heads_sizes(transposed ? K : M, transposed ? M : K, H, F, nnz);
 }
 
 // ---- the multi-head SDDMM (gespmm.h: gespmm_sddmm_{coo,csr}_heads_f32; sddmm_heads.h). GESPMM_SDDMM_HEADS_ROUTE=kernel|composition pins
@@ -893,6 +935,73 @@ int gespmm_edge_segment_sum_f32(const int32_t* ptr, const int32_t* order, const 
     }
     if (const int rcp = check_pointers({{ptr, 4, true}, {x, 4, true}, {out, 4, true}, {order, 4, false}})) return rcp;
     return (int)gespmm::launch_edge_segment_sum(ptr, order, x, out, S, H, nnz, gespmm::resolve_edge_softmax(S, nnz, H), st);
+}
+
+/* The row statistics of gespmm_gat_softmax_f32 (gespmm.h): the same kernel without the pass that writes alpha. */
+int gespmm_gat_softmax_stats_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* stats, int64_t M,
+                                 int64_t K, int64_t H, int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_gat_softmax_sizes(M, K, H, nnz, slope);
+    if (rc != 0) return rc;
+    if (M == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(M, nnz, H);
+    if (nnz == 0) {  // every word of stats is still written
+        if (const int rcp = check_pointers({{stats, 8, true}})) return rcp;
+        return (int)gespmm::launch_gat_softmax_stats(nullptr, nullptr, nullptr, nullptr, stats, M, K, H, 0, slope, r, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true}})) return rcp;
+    return (int)gespmm::launch_gat_softmax_stats(rowptr, colind, el, er, stats, M, K, H, nnz, slope, r, st);
+}
+
+/* The fused GAT aggregation (gespmm.h): one kernel that computes the weights where the multi-head product loads them, else the
+   composition — the same weights into a stream-ordered temporary, then gespmm_csr_spmm_heads_f32 on it. Same bits either way. */
+int gespmm_gat_aggregate_f32(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const float* B,
+                             float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed, void* stream) {
+    if (transposed != 0 && transposed != 1) return GESPMM_EINVAL;
+    int rc = gespmm::check_gat_aggregate_sizes(M, K, H, F, nnz, slope, transposed != 0);
+    if (rc != 0) return rc;
+    const int64_t S = transposed ? K : M, Kb = transposed ? M : K;  // segments, rows of B
+    if (S == 0 || F == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0) {  // C = 0
+        if (const int rcp = check_pointers({{C, 4, true}})) return rcp;
+        return (int)hipMemsetAsync(C, 0, (size_t)S * (size_t)H * (size_t)F * sizeof(float), st);
+    }
+    rc = check_pointers({{ptr, 4, true}, {ind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true}, {B, 4, true}, {C, 4, true}});
+    if (rc != 0) return rc;
+    const gespmm::GatTerms terms = {el, er, stats, slope};
+    int kind = 0;
+    rc = gespmm::run_gat_aggregate(csr_view(ptr, ind, nullptr, S, Kb, nnz, GESPMM_VARIANT_AUTO), terms, B, C, H, F, transposed != 0, stream,
+                                   pointer_alignment(B), pointer_alignment(C), false, &kind, nullptr);
+    if (rc != kHeadsUnavailable) return rc;
+    const size_t w_bytes = (size_t)nnz * (size_t)H * 4;
+    PooledScratch scratch;
+    if ((rc = scratch.open(w_bytes, st)) != 0) return rc;  // (nothing launched; a capturing stream: what the heads composition returns)
+    float* w = scratch.take(w_bytes);
+    rc = (int)gespmm::launch_gat_weights(ptr, ind, el, er, stats, w, S, H, nnz, slope, transposed != 0, st);
+    if (rc == 0) rc = gespmm_csr_spmm_heads_f32(ptr, ind, w, B, C, S, Kb, H, F, nnz, stream);
+    return scratch.close(rc);
+}
+
+int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,
+                               int32_t* geometry_out) {
+    if (b_align < 1 || c_align < 1 || (transposed != 0 && transposed != 1)) return GESPMM_EINVAL;
+    const int rc0 = gespmm::check_gat_aggregate_sizes(M, K, H, F, nnz, 1.0f, transposed != 0);
+    if (rc0 != 0) return rc0;
+    const int64_t S = transposed ? K : M, Kb = transposed ? M : K;
+    int kind = 0;
+    Geometry geo = {};
+    const gespmm::GatTerms none = {nullptr, nullptr, nullptr, 1.0f};
+    const int rc = gespmm::run_gat_aggregate(csr_view(nullptr, nullptr, nullptr, S, Kb, nnz, GESPMM_VARIANT_AUTO), none, nullptr, nullptr, H, F,
+                                             transposed != 0, nullptr, b_align, c_align, true, &kind, &geo);
+    const int route = route_result(rc == kHeadsUnavailable ? 0 : rc, kind);
+    if (route >= 0 && geometry_out) {
+        geometry_out[0] = kind ? geo.vec : 0;
+        geometry_out[1] = kind ? geo.strips : 0;
+        geometry_out[2] = kind ? geo.group : 0;
+        geometry_out[3] = kind ? geo.rows_per_wave : 0;
+    }
+    return route;
 }
 
 int gespmm_describe_edge_softmax(int64_t M, int64_t nnz, int64_t H, char* out, int64_t capacity) {

@@ -42,6 +42,11 @@ hipError_t launch_edge_softmax_backward(const int32_t* rowptr, const float* alph
 // each sweep). Bits: those of the calls above on the score array the width-2 SDDMM writes. M H and K H <= kSddmmMaxNnz, K >= 1.
 hipError_t launch_gat_softmax(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* out, int64_t M,
                               int64_t K, int64_t H, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st);
+// stats[r, h, :] = (m, s): the row maximum and the row sum of exp(x - m) launch_gat_softmax divides by, with ITS bits — the same lane
+// geometry r, regimes, chains and hub branch, minus the pass that writes (gespmm_gat_softmax_stats_f32). Every word of [M, H, 2]
+// written: empty rows (+0, +0); nnz == 0: zero-filled. One 8-byte store per pair.
+hipError_t launch_gat_softmax_stats(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* stats, int64_t M,
+                                    int64_t K, int64_t H, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st);
 // grad_score as launch_edge_softmax_backward, and grad_el[r, h] = the sum of the row's grad_score values as stored, every word of
 // [M, H] written (empty rows +0; nnz == 0: zero-filled). colind, el, er are read only when slope != 1 (the sign of fl(el + er)).
 // Summation order of grad_el, pinned: lane l adds its entries lo + l + t W in entry order, plain adds from +0, a masked position adds

@@ -152,6 +152,55 @@ __device__ __forceinline__ void softmax_pair(GESPMM_SRC_PTRS, float* __restrict_
     }
 }
 
+// The pair's row maximum m and row sum s of exp(x - m), and nothing else: softmax_pair without its third pass, statement for
+// statement — both regimes, the same fmaxf chain and butterfly, the same `s += t` chain in which a masked position adds +0 — so
+// (m, s) carry the bits softmax_pair divides by. A function of its own, not a helper softmax_pair calls: behind a call hipcc
+// schedules the forward's sweeps differently (see kInPlace above). A pair without entries answers (+0, +0).
+template <int W, bool LEAKY, class SRC>
+__device__ __forceinline__ float2 stats_pair(GESPMM_SRC_PTRS, int row, int lo, int d, int h, int H, int l, float slope) {
+    const int dm = wave_max_degree<W>(d);
+    if (dm == 0) return make_float2(0.0f, 0.0f);
+    auto word = [&](int p) { return (lo + (p < d ? p : 0)) * H + h; };
+    auto entry = [&](int p) { return lo + (p < d ? p : 0); };
+    const typename SRC::Row sr = SRC::row(idx, a, b, row, h, H);
+    float m = -INFINITY, s = 0.0f;
+    if (dm <= IT * W) {
+        float x[IT];
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            x[it] = -INFINITY;
+            if (it * W < dm) {  // wave-uniform
+                const int p = l + it * W;
+                const float v = SRC::at(idx, a, b, sr, entry(p), word(p), h, H);
+                x[it] = p < d ? leaky<LEAKY>(v, slope) : -INFINITY;
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < IT; ++it) m = fmaxf(m, x[it]);
+        m = group_max<W>(m);
+#pragma unroll
+        for (int it = 0; it < IT; ++it) s += (l + it * W < d) ? __expf(x[it] - m) : 0.0f;
+        s = group_sum<W>(s);
+    } else {
+        const int nt = (dm + W - 1) / W;  // wave-uniform
+#pragma unroll 4
+        for (int k = 0; k < nt; ++k) {
+            const int p = l + k * W;
+            const float v = SRC::at(idx, a, b, sr, entry(p), word(p), h, H);
+            m = fmaxf(m, p < d ? leaky<LEAKY>(v, slope) : -INFINITY);
+        }
+        m = group_max<W>(m);
+#pragma unroll 4
+        for (int k = 0; k < nt; ++k) {
+            const int p = l + k * W;
+            const float v = SRC::at(idx, a, b, sr, entry(p), word(p), h, H);
+            s += p < d ? __expf(leaky<LEAKY>(v, slope) - m) : 0.0f;
+        }
+        s = group_sum<W>(s);
+    }
+    return d > 0 ? make_float2(m, s) : make_float2(0.0f, 0.0f);  // (a group without entries beside one with: -inf and 0 are not stored)
+}
+
 // ROWSUM: the return value is the sum of the pair's grad values AS STORED, in the pinned order (edge_softmax.h) — plain adds from +0, a
 // masked position adds +0, in both regimes; 0 otherwise. The sign of the score comes from SRC (LEAKY only).
 template <int W, bool LEAKY, bool ROWSUM, class SRC>
@@ -238,6 +287,7 @@ enum Op {
     kBackward,     // in0 = alpha, in1 = grad_alpha, SRC on (idx, in2, in3) = the score (LEAKY only, for its sign); out = grad_score
     kBackwardSum,  // ... and row_out = the row sums of grad_score
     kSegmentSum,   // row_out = the row sums of SRC on (idx, in0, in1)
+    kStats,        // SRC on (idx, in0, in1) = the score; row_out ([M, H, 2], every word written: empty rows (+0, +0)) = (maximum, sum)
 };
 
 template <int W, bool LEAKY, Op OP, class SRC>
@@ -287,9 +337,14 @@ __global__ __launch_bounds__(kThreads) void edge_softmax_kernel(const int32_t* _
             d = 0;
             lo = 0;
         }
-        const float s = pair<W, LEAKY, OP, SRC>(idx, in0, in1, in2, in3, out, r0 + ri, lo, d, h, H, l, slope);
-        if constexpr (ROWOUT)
-            if (mine && l == 0) row_out[(r0 + ri) * H + h] = s;  // (M H <= kSddmmMaxNnz)
+        if constexpr (OP == kStats) {  // (its own statement: the other operations' code stays what it was)
+            const float2 ms = stats_pair<W, LEAKY, SRC>(idx, in0, in1, r0 + ri, lo, d, h, H, l, slope);
+            if (mine && l == 0) reinterpret_cast<float2*>(row_out)[(r0 + ri) * H + h] = ms;  // one 8-byte store (M H <= kSddmmMaxNnz)
+        } else {
+            const float s = pair<W, LEAKY, OP, SRC>(idx, in0, in1, in2, in3, out, r0 + ri, lo, d, h, H, l, slope);
+            if constexpr (ROWOUT)
+                if (mine && l == 0) row_out[(r0 + ri) * H + h] = s;  // (M H <= kSddmmMaxNnz)
+        }
     }
     // ---- hub rows: a whole wavefront per pair (wave-uniform branch: rp lives in lanes, the row index is a loop counter)
     if (hubs) {
@@ -298,9 +353,14 @@ __global__ __launch_bounds__(kThreads) void edge_softmax_kernel(const int32_t* _
             const int d = __builtin_amdgcn_readlane(rp, i + 1) - lo;
             if (d > L)
                 for (int h = 0; h < H; ++h) {
-                    const float s = pair<64, LEAKY, OP, SRC>(idx, in0, in1, in2, in3, out, r0 + i, lo, d, h, H, lane, slope);
-                    if constexpr (ROWOUT)
-                        if (lane == 0) row_out[(r0 + i) * H + h] = s;
+                    if constexpr (OP == kStats) {
+                        const float2 ms = stats_pair<64, LEAKY, SRC>(idx, in0, in1, r0 + i, lo, d, h, H, lane, slope);
+                        if (lane == 0) reinterpret_cast<float2*>(row_out)[(r0 + i) * H + h] = ms;
+                    } else {
+                        const float s = pair<64, LEAKY, OP, SRC>(idx, in0, in1, in2, in3, out, r0 + i, lo, d, h, H, lane, slope);
+                        if constexpr (ROWOUT)
+                            if (lane == 0) row_out[(r0 + i) * H + h] = s;
+                    }
                 }
         }
     }
@@ -362,6 +422,17 @@ hipError_t launch_gat_softmax(const int32_t* rowptr, const int32_t* colind, cons
     const float* no = nullptr;
     if (slope != 1.0f) return launch_w<true, kForward, AddedScore>(rowptr, colind, el, er, no, no, out, nullptr, (int)M, (int)H, slope, r, st);
     return launch_w<false, kForward, AddedScore>(rowptr, colind, el, er, no, no, out, nullptr, (int)M, (int)H, slope, r, st);
+}
+
+hipError_t launch_gat_softmax_stats(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* stats, int64_t M,
+                                    int64_t K, int64_t H, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st) {
+    if (M == 0) return hipSuccess;
+    if (H < 1 || !dense_words_fit(M, H)) return hipErrorInvalidValue;
+    if (nnz == 0) return hipMemsetAsync(stats, 0, (size_t)M * (size_t)H * 2 * sizeof(float), st);
+    if (!launchable(M, H, nnz, r) || K < 1 || !dense_words_fit(K, H)) return hipErrorInvalidValue;
+    const float* no = nullptr;
+    if (slope != 1.0f) return launch_w<true, kStats, AddedScore>(rowptr, colind, el, er, no, no, nullptr, stats, (int)M, (int)H, slope, r, st);
+    return launch_w<false, kStats, AddedScore>(rowptr, colind, el, er, no, no, nullptr, stats, (int)M, (int)H, slope, r, st);
 }
 
 hipError_t launch_gat_softmax_backward(const int32_t* rowptr, const int32_t* colind, const float* alpha, const float* grad_alpha,

@@ -45,6 +45,7 @@ instead of one ``sddmm.csr_sddmm`` per head on copies (the default, kept as it w
 ``EdgeSoftmaxFunction`` is the step between the two — softmax over the entries of each row, per head, with the leaky ReLU of a GAT
 fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` the graph attention layer composed from the three.
 ``GATSoftmaxFunction`` is the first two in one: the softmax of el[row] + er[col] with no score array (``GATConv(fused_score=True)``).
+``GATAggregateFunction`` is all three in one: no score and no attention array, nothing of size nnz x H saved (``GATConv(fused_aggregate=True)``).
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -299,6 +300,57 @@ class GATSoftmaxFunction(torch.autograd.Function):
         return None, None, None, None, grad_el, grad_er, None
 
 
+class GATAggregateFunction(torch.autograd.Function):
+    """out[r, h, :] = sum_e alpha[e, h] feat[col(e), h, :] with alpha = softmax over each row's entries of
+    leaky_relu(el[row(e), h] + er[col(e), h], negative_slope) — the softmax AND the aggregation of a graph attention layer with no
+    attention array (``softmax.gat_softmax_stats`` + ``spmm.gat_aggregate``): the weights are computed inside the product's kernel
+    from el, er and two words per (row, head).
+
+        GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None) -> f32[M, H, F]
+
+    ``el`` f32[M, H], ``er`` f32[K, H], ``feat`` f32[K, H, F]; ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K,
+    return_order=True)``. The output has the bits of ``MultiHeadSPMMFunction`` on ``GATSoftmaxFunction``'s alpha. Saved: ``el``,
+    ``er``, ``feat`` and the statistics — node-sized tensors only. Backward, each part only when asked for: grad_feat is
+    ``spmm.gat_aggregate(colptr, rowind, .., grad_out, transposed=True)`` (no alpha, no ``alpha[csc_order]`` copy); for grad_el /
+    grad_er alpha is recomputed (``softmax.gat_edge_softmax``: the forward's bits) and the steps are those of the two functions
+    above — ``sddmm.csr_sddmm_heads`` for grad_alpha, ``softmax.gat_edge_softmax_backward``, ``softmax.edge_segment_sum`` on
+    ``(colptr, csc_order)`` — so every gradient has their bits; alpha and grad_alpha live only inside the backward. An int64
+    ``csc_order`` is converted to int32 in every forward; pass an int32 one. Index tensors get no gradient."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None):
+        el_c, er_c, feat_c = el.contiguous(), er.contiguous(), feat.contiguous()
+        stats = _softmax.gat_softmax_stats(rowptr, colind, el_c, er_c, negative_slope=negative_slope)
+        out = _spmm.gat_aggregate(rowptr, colind, el_c, er_c, stats, feat_c, negative_slope=negative_slope)
+        order = csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)
+        ctx.graph = (rowptr, colind, colptr, rowind, order.contiguous())
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(el_c, er_c, feat_c, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rowptr, colind, colptr, rowind, order = ctx.graph
+        el, er, feat, stats = ctx.saved_tensors
+        slope = ctx.negative_slope
+        grad_out = grad_out.contiguous()
+        grad_el = grad_er = grad_feat = None
+        if ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:  # (first: its three edge-sized temporaries are gone before grad_feat exists)
+            alpha = _softmax.gat_edge_softmax(rowptr, colind, el, er, negative_slope=slope)
+            grad_alpha = _sddmm.csr_sddmm_heads(rowptr, colind, grad_out, feat)
+            grad_score, grad_el = _softmax.gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=el if slope is not None else None,
+                                                                     er=er if slope is not None else None, negative_slope=slope)
+            del alpha, grad_alpha
+            if ctx.needs_input_grad[6]:
+                grad_er = _softmax.edge_segment_sum(colptr, grad_score, order=order)
+            del grad_score
+            if not ctx.needs_input_grad[5]:
+                grad_el = None
+        if ctx.needs_input_grad[7]:
+            grad_feat = _spmm.gat_aggregate(colptr, rowind, el, er, stats, grad_out, negative_slope=slope, transposed=True)
+        return None, None, None, None, None, grad_el, grad_er, grad_feat, None
+
+
 def glorot(tensor):
     """torch_geometric.nn.inits.glorot: U(-a, a), a = sqrt(6 / (fan_in + fan_out))."""
     if tensor is not None:
@@ -419,19 +471,27 @@ class GATConv(torch.nn.Module):
     additive score is a width-2 dot product whose pinned chain is fmaf(1, er, fmaf(el, 1, 0)) = fl(el + er) (or el + er across two lanes),
     and its backward hands grad_el and grad_er back as component 0 of grad_q and component 1 of grad_k.
 
-        GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False)
+        GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
+                fused_aggregate=False)
         forward(x, rowptr, colind, colptr, rowind, csc_order)
 
     ``fused_score=True``: the score and the softmax are ONE ``GATSoftmaxFunction`` — el + er is added inside the softmax kernel, no
     score, q or k tensor exists, and the backward sums grad_score over rows and columns in two launches. Same output bits. Pass an
     int32 ``csc_order`` then (an int64 one is converted in every forward).
 
+    ``fused_aggregate=True`` (implies the fused score): the softmax AND the aggregation are ONE ``GATAggregateFunction`` — alpha is
+    never an array. The forward keeps two words per (node, head) instead of ``[nnz, H]``, the feature gradient is one product on the
+    CSC arrays with no ``alpha[csc_order]`` copy, and only the backward for ``att_dst`` / ``att_src`` recomputes alpha, transiently.
+    Output and all gradients have the bits of ``fused_score=True``. Off by default.
+
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
     ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
+                 fused_aggregate=False):
         super().__init__()
-        self.fused_score = bool(fused_score)
+        self.fused_aggregate = bool(fused_aggregate)
+        self.fused_score = bool(fused_score) or self.fused_aggregate
         if heads < 1:
             raise ValueError("heads must be at least 1")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, int(heads)
@@ -457,6 +517,10 @@ class GATConv(torch.nn.Module):
         xw = (x @ self.weight).view(n, H, F)
         el = (xw * self.att_dst).sum(-1)
         er = (xw * self.att_src).sum(-1)
+        if self.fused_aggregate:
+            out = GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, xw, self.negative_slope)
+            out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
+            return out if self.bias is None else out + self.bias
         if self.fused_score:
             alpha = GATSoftmaxFunction.apply(rowptr, colind, colptr, csc_order, el, er, self.negative_slope)
         else:

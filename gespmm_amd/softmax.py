@@ -6,6 +6,7 @@ gespmm_edge_softmax_backward_f32 — the reference has no counterpart).
     gat_edge_softmax(rowptr, colind, el, er, negative_slope=None, out=None)                       -> f32[nnz, H]
     gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=None, er=None, negative_slope=None) -> (grad_score, grad_el)
     edge_segment_sum(ptr, x, order=None, out=None)                                                -> f32[S, H] (or f32[S])
+    gat_softmax_stats(rowptr, colind, el, er, negative_slope=None, out=None)                      -> f32[M, H, 2]
 
 ``score`` is f32[nnz] or f32[nnz, H] in CSR edge order — what ``sddmm.csr_sddmm`` / ``sddmm.csr_sddmm_heads`` return and what
 ``spmm.csr_spmm`` / ``spmm.csr_spmm_heads`` take as edge weights. For row r with entries [lo, hi) and head h
@@ -23,6 +24,8 @@ er[colind[e], h]``, computed inside the kernel: no ``[nnz, H]`` score exists, an
 score ``sddmm.csr_sddmm_heads`` writes for ``q = (el, 1), k = (1, er)``. Its backward returns ``grad_score`` and, from the same launch,
 ``grad_el = sum_row(grad_score)``; ``edge_segment_sum`` on the CSC arrays (``ptr=colptr, order=csc_order``) gives ``grad_er`` without a
 permuted copy. The sums have a pinned order (include/gespmm.h), the one ``edge_segment_sum(rowptr, grad_score)`` reproduces.
+``gat_softmax_stats`` returns what that softmax divides by — per (row, head) the maximum and the sum, with its bits — for
+``spmm.gat_aggregate``, which computes the weights inside the aggregation and needs no ``[nnz, H]`` array at all.
 All calls go through ctypes."""
 import torch
 
@@ -174,6 +177,46 @@ def gat_edge_softmax(rowptr, colind, el, er, negative_slope=None, out=None):
     with _on_device(dev):
         rc = lib.gespmm_gat_softmax_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(out), M, K, H, nnz, slope, _stream(dev))
     check(rc, "gespmm_gat_softmax_f32")
+    return out
+
+
+def _gat_terms(rowptr, colind, el, er):
+    """The shared checks of the calls on (rowptr, colind, el, er) -> (device, M, K, H, nnz)."""
+    M = _checked_rowptr(rowptr)
+    _node_array(el, "el", rows=M)
+    _node_array(er, "er", like=el)
+    dev = el.device
+    _checked_rowptr(rowptr, dev)
+    _index_vector(colind, "colind", dev)
+    return dev, M, er.shape[0], el.shape[1], colind.numel()
+
+
+def _stats_array(t, name, M, H, dev):
+    """fp32, contiguous, [M, H, 2] on ``dev``, 8-byte aligned (the kernels move a pair as one 8-byte word)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must have dtype torch.float32, got %s" % (name, t.dtype))
+    if tuple(t.shape) != (M, H, 2) or t.device != dev:
+        raise ValueError("%s must be f32[%d, %d, 2] on %s" % (name, M, H, dev))
+    if not t.is_contiguous() or t.data_ptr() % 8 != 0:
+        raise ValueError("%s must be contiguous and 8-byte aligned" % name)
+
+
+def gat_softmax_stats(rowptr, colind, el, er, negative_slope=None, out=None):
+    """The row statistics of ``gat_edge_softmax`` -> f32[M, H, 2] (gespmm_gat_softmax_stats_f32): ``[r, h, 0]`` the maximum m of
+    ``leaky_relu(el[r, h] + er[colind, h])`` over the row's entries, ``[r, h, 1]`` the sum s of ``exp(x - m)``, with exactly the bits
+    ``gat_edge_softmax`` divides by (the same kernel without its last pass), so ``alpha[e, h] == exp(x - m) / s`` bit for bit. Every
+    word is written; an empty row gives (+0, +0). Node-sized: what ``spmm.gat_aggregate`` needs in place of ``alpha``."""
+    slope = _slope(negative_slope)
+    dev, M, K, H, nnz = _gat_terms(rowptr, colind, el, er)
+    if out is None:
+        out = torch.empty(M, H, 2, dtype=torch.float32, device=dev)
+    else:
+        _stats_array(out, "out", M, H, dev)
+    with _on_device(dev):
+        rc = lib.gespmm_gat_softmax_stats_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(out), M, K, H, nnz, slope, _stream(dev))
+    check(rc, "gespmm_gat_softmax_stats_f32")
     return out
 
 

@@ -427,6 +427,67 @@ def csr_spmm_heads(rowptr, colind, values, dense, out=None, plan=None):
     return out
 
 
+def _overlaps(a, b):
+    """Do the byte ranges of two contiguous tensors intersect?"""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transposed=False, out=None):
+    """GAT aggregation with no attention array (gespmm_gat_aggregate_f32): ``csr_spmm_heads`` with the weight of an entry computed
+    inside the kernel, ``exp(leaky_relu(el[r, h] + er[c, h]) - stats[r, h, 0]) / stats[r, h, 1]`` for the entry's row r and column c —
+    the bits of ``softmax.gat_edge_softmax`` when ``stats = softmax.gat_softmax_stats(rowptr, colind, el, er, negative_slope)``.
+
+        transposed=False  (ptr, ind) = (rowptr, colind), dense f32[K, H, F] -> f32[M, H, F]: csr_spmm_heads(rowptr, colind, alpha, dense)
+        transposed=True   (ptr, ind) = (colptr, rowind), dense f32[M, H, F] -> f32[K, H, F]: csr_spmm_heads(colptr, rowind,
+                          alpha[csc_order], dense) — the feature gradient, without alpha and without its permuted copy
+
+    bit for bit. ``el`` f32[M, H], ``er`` f32[K, H], ``stats`` f32[M, H, 2] are the same tensors in both modes. ``dense`` may be
+    rank 2 ([rows, H * F]); the result has its rank. One kernel for H <= 8 (``_lib.gat_aggregate_route``), else the weights go through
+    a pooled temporary. ``out`` must not overlap an input. fp32 only."""
+    from . import softmax as _sm  # (softmax imports this module)
+
+    slope = _sm._slope(negative_slope)
+    _sm._node_array(el, "el")
+    _sm._node_array(er, "er", like=el)
+    dev = el.device
+    M, K, H = el.shape[0], er.shape[0], el.shape[1]
+    S, Kb = (K, M) if transposed else (M, K)
+    if _sm._checked_rowptr(ptr, dev) != S:
+        raise ValueError("ptr must have %d + 1 entries (%s)" % (S, "colptr: transposed" if transposed else "rowptr"))
+    _sm._index_vector(ind, "ind", dev)
+    _sm._stats_array(stats, "stats", M, H, dev)
+    if not isinstance(dense, torch.Tensor):
+        raise TypeError("dense must be a torch.Tensor")
+    if dense.dtype != torch.float32:
+        raise TypeError("dense must have dtype torch.float32, got %s" % dense.dtype)
+    if dense.dim() not in (2, 3) or dense.shape[0] != Kb:
+        raise ValueError("dense must be [%d, H, F] or [%d, H * F]" % (Kb, Kb))
+    N = dense.shape[1] * dense.shape[2] if dense.dim() == 3 else dense.shape[1]
+    if (dense.dim() == 3 and dense.shape[1] != H) or N % H != 0:
+        raise ValueError("dense of shape %s does not hold H = %d heads" % (tuple(dense.shape), H))
+    if not dense.is_contiguous() or dense.device != dev:
+        raise ValueError("dense must be contiguous on %s, as the other operands" % (dev,))
+    F = N // H
+    shape = (S, H, F) if dense.dim() == 3 else (S, N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("out must be a torch.Tensor")
+        if out.dtype != torch.float32:
+            raise TypeError("out must have dtype torch.float32, got %s" % out.dtype)
+        if tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
+            raise ValueError("out must be contiguous f32%s on %s" % (list(shape), dev))
+        if any(_overlaps(out, t) for t in (el, er, stats, dense)):
+            raise ValueError("out must not overlap an input")
+    with _on_device(dev):
+        rc = lib.gespmm_gat_aggregate_f32(_ptr(ptr), _ptr(ind), _ptr(el), _ptr(er), _ptr(stats), _ptr(dense), _ptr(out), M, K, H, F,
+                                          ind.numel(), slope, 1 if transposed else 0, _stream(dev))
+    check(rc, "gespmm_gat_aggregate_f32")
+    return out
+
+
 def _spmm(rowptr, colind, values, dense, variant, cfg, out, plan=None):
     _need(rowptr, "rowptr", torch.int32, 1)
     _need(colind, "colind", torch.int32, 1)

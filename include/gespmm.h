@@ -31,6 +31,8 @@
  *   gespmm_edge_softmax_f32 / _backward_f32 <- (new) softmax over the entries of a CSR row, per head; no reference counterpart
  *   gespmm_gat_softmax_f32 / _backward_f32 / gespmm_edge_segment_sum_f32 <- (new) the same softmax on the additive score of a graph
  *                               attention layer, el[row] + er[col], never written; the per-segment sum of an edge array
+ *   gespmm_gat_softmax_stats_f32 / gespmm_gat_aggregate_f32 / gespmm_gat_aggregate_route <- (new) that softmax's row statistics, and the
+ *                               multi-head product that computes the attention weights from them: no [nnz x H] array at all
  *   gespmm_baseline_copy_f32 <- (new) streaming-copy yardstick for the roofline record; no reference counterpart
  *
  * Conventions (all device entry points):
@@ -615,6 +617,51 @@ int gespmm_gat_softmax_backward_f32(const int32_t* rowptr, const int32_t* colind
  */
 int gespmm_edge_segment_sum_f32(const int32_t* ptr, const int32_t* order, const float* x, float* out, int64_t S, int64_t H, int64_t nnz,
                                 void* stream);
+/*
+ * The row statistics of gespmm_gat_softmax_f32 (since 0.5): stats is [M x H x 2], fp32, 8-byte aligned, and for row r, head h, with
+ * x(r, c, h) = leaky(fl(el[r H + h] + er[c H + h]), slope)
+ *
+ *     stats[r, h, 0] = m = the maximum of x over the row's entries,    stats[r, h, 1] = s = the sum of __expf(x - m) over them
+ *
+ * with EXACTLY the bits gespmm_gat_softmax_f32 uses for that pair: the same kernel — lane geometry W / L of
+ * gespmm_describe_edge_softmax(M, nnz, H), the register and the sweep regime, the fmaxf chain and xor butterfly, the `s += t` chain in
+ * which a masked lane adds +0, the W = 64 branch for rows of more than L entries — without its last pass; one 8-byte store per pair.
+ * Every word is written; an empty row writes (+0, +0). Checks: the ladder of gespmm_gat_softmax_f32; M == 0 -> 0; nnz == 0 looks at
+ * stats alone and zero-fills it (hipMemsetAsync); stats not 8-byte aligned -> GESPMM_EALIGN. One kernel, no workspace: capturable.
+ */
+int gespmm_gat_softmax_stats_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, float* stats, int64_t M,
+                                 int64_t K, int64_t H, int64_t nnz, float slope, void* stream);
+/*
+ * The aggregation of a graph attention layer with no attention array (since 0.5). el [M x H], er [K x H], stats [M x H x 2] (the call
+ * above) are the same arrays in both modes; the weight of row index r, column index c, head h is
+ *
+ *     w(r, c, h) = __expf(x(r, c, h) - stats[r, h, 0]) / stats[r, h, 1]        (the bits of gespmm_gat_softmax_f32's out)
+ *
+ *     transposed == 0   (ptr, ind) = (rowptr[M + 1], colind)   B [K x H F]   C [M x H F]   entry p of segment i, j = ind[p]: w(i, j, h)
+ *     transposed == 1   (ptr, ind) = (colptr[K + 1], rowind)   B [M x H F]   C [K x H F]   entry p of segment i, j = ind[p]: w(j, i, h)
+ *
+ *     C[i, h F + f] = fmaf(w, B[j, h F + f], acc) over the segment's entries, ascending, from +0
+ *
+ * — one fp32 chain per output element in strict order. transposed == 0 has the bits of gespmm_csr_spmm_heads_f32(rowptr, colind,
+ * alpha, B) with alpha = gespmm_gat_softmax_f32(..); transposed == 1 those of gespmm_csr_spmm_heads_f32(colptr, rowind, alpha in CSC
+ * order, B): the product of the backward, without alpha and without its permuted copy. A NaN or inf in el poisons what it poisons
+ * there. nnz == 0 gives C = 0 (hipMemsetAsync).
+ * Routes (gespmm_gat_aggregate_route): 1 = ONE kernel — the multi-head batch-stream kernel computing its staged weights — for
+ * 1 <= H <= 8, 32-bit offsets (rows of B x H F x 4 < 2^32, nnz H < 2^31) and the lane geometries gespmm_heads_route serves; no
+ * workspace, no allocation: capturable. 0 = the composition: the weights into a stream-ordered temporary [nnz x H] from the library's
+ * pool (the same expression: the same bits), then gespmm_csr_spmm_heads_f32; on a capturing stream it returns
+ * hipErrorStreamCaptureUnsupported and launches nothing. GESPMM_GAT_AGGREGATE_ROUTE=composition pins route 0 (a measurement knob,
+ * read with getenv on every call).
+ * Checks, in this order: transposed not 0 / 1, F < 0, then the ladder of gespmm_gat_softmax_f32 on (M, K, H, nnz, slope), then that of
+ * gespmm_csr_spmm_heads_f32 on the width; no segments (M == 0, transposed == 0) or F == 0 -> 0; nnz == 0 looks at C alone; NULL ->
+ * GESPMM_EINVAL; a pointer not 4-byte (stats: 8-byte) aligned -> GESPMM_EALIGN. C must not overlap an input (not checked).
+ */
+int gespmm_gat_aggregate_f32(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const float* B,
+                             float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed, void* stream);
+/* Host only: the route of the call above for these sizes and operand alignments, as gespmm_heads_route — 1 or 0, or a GESPMM_E*
+ * code; geometry_out (may be NULL): V, strips, W, rows per wavefront of route 1, zeros for route 0. */
+int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,
+                               int32_t* geometry_out);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
