@@ -8,6 +8,7 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
     python examples/gat_custom.py --graph-capture                  # replay each step from a HIP graph (one stream)
     python examples/gat_custom.py --fused-score                    # el + er added inside the softmax kernel: no score array
     python examples/gat_custom.py --fused-aggregate                # ... and the weights computed inside the aggregation: no alpha array
+    python examples/gat_custom.py --fused-backward                 # ... and no [nnz, H] array in the backward either
     python examples/gat_custom.py --seed 0 --fused-aggregate       # seeded parameters and dropout: the losses of --seed 0 --fused-score
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
@@ -42,10 +43,11 @@ def gat_graph(edge_index, n_v, device, int32_order=False):
 
 
 class Net(torch.nn.Module):
-    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False, fused_aggregate=False):
+    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False, fused_aggregate=False, fused_backward=False):
         super().__init__()
-        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, fused_score=fused_score, fused_aggregate=fused_aggregate)
-        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, fused_score=fused_score, fused_aggregate=fused_aggregate)
+        fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward)
+        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, **fused)
+        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, **fused)
         self.dropout = dropout
 
     def forward(self, x, g):
@@ -67,6 +69,9 @@ def main():
     ap.add_argument("--fused-score", action="store_true", help="GATConv(fused_score=True): score and softmax in one kernel")
     ap.add_argument("--fused-aggregate", action="store_true",
                     help="GATConv(fused_aggregate=True): softmax and aggregation in one kernel, no [nnz, H] array saved")
+    ap.add_argument("--fused-backward", action="store_true",
+                    help="GATConv(fused_backward=True): the fused aggregation, and its backward for the attention terms in two "
+                         "launches with no [nnz, H] array")
     ap.add_argument("--seed", type=int, default=None,
                     help="torch.manual_seed before the model is made (parameters and dropout masks): two runs, or two fused settings, "
                          "then print the same losses")
@@ -76,7 +81,7 @@ def main():
     device = torch.device("cuda")
 
     edge_index, n_v, n_feat, n_cls = load_edges(args.dataset, device)
-    g = gat_graph(edge_index, n_v, device, int32_order=args.fused_score or args.fused_aggregate)
+    g = gat_graph(edge_index, n_v, device, int32_order=args.fused_score or args.fused_aggregate or args.fused_backward)
     gen = torch.Generator().manual_seed(0)
     x = torch.rand(n_v, n_feat, generator=gen)
     x = (x / x.sum(1, keepdim=True)).to(device)
@@ -92,7 +97,7 @@ def main():
     if args.seed is not None:
         torch.manual_seed(args.seed)
     model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score,
-                fused_aggregate=args.fused_aggregate).to(device)
+                fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
     train_idx = masks["train"].nonzero().squeeze(1)
     y_train = y[train_idx]
@@ -151,8 +156,9 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s" %
-          (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score, args.fused_aggregate))
+    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s fused_backward=%s" %
+          (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score, args.fused_aggregate,
+           args.fused_backward))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
 

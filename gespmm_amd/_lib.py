@@ -115,6 +115,8 @@ EXPORTS = [
     "gespmm_gat_softmax_stats_f32",
     "gespmm_gat_aggregate_f32",
     "gespmm_gat_aggregate_route",
+    "gespmm_gat_backward_el_f32",
+    "gespmm_gat_backward_er_f32",
 ]
 
 X16_F16 = 1
@@ -308,6 +310,9 @@ def _load():
     lib.gespmm_gat_softmax_stats_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_float, p]
     lib.gespmm_gat_aggregate_f32.restype = c_int
     lib.gespmm_gat_aggregate_f32.argtypes = [p, p, p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int, p]
+    for f in (lib.gespmm_gat_backward_el_f32, lib.gespmm_gat_backward_er_f32):
+        f.restype = c_int
+        f.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, p]
     lib.gespmm_gat_aggregate_route.restype = c_int
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int

@@ -24,6 +24,7 @@
 #include "auto_plan.h"
 #include "edge_softmax.h"
 #include "gat_aggregate.h"
+#include "gat_backward.h"
 #include "plan.h"
 #include "sddmm_heads.h"
 #include "spmm_heads.h"
@@ -392,6 +393,16 @@ int check_gat_softmax_sizes(int64_t M, int64_t K, int64_t H, int64_t nnz, float 
     if (rc != 0) return rc;
     if (const int rcm = check_dense_words(M, H)) return rcm;
     return check_dense_words(K, H);
+}
+
+// gespmm_gat_backward_el_f32 / _er_f32: the ladder of gespmm_gat_aggregate_f32 in both directions, then the 32-bit word positions of the
+// two [*, H, F] operands (no other route takes what the kernel cannot address)
+int check_gat_backward_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope) {
+    int rc = check_gat_aggregate_sizes(M, K, H, F, nnz, slope, false);
+    if (rc == 0) rc = check_gat_aggregate_sizes(M, K, H, F, nnz, slope, true);
+    if (rc != 0 || F == 0) return rc;
+    if (const int rcm = check_dense_words(M, H * F)) return rcm;  // (H F <= kMaxWidth: no overflow)
+    return check_dense_words(K, H * F);
 }
 
 // One multi-head SDDMM on checked arguments, nnz > 0: what resolve_sddmm_heads answers, nothing else.
@@ -981,6 +992,45 @@ int gespmm_gat_aggregate_f32(const int32_t* ptr, const int32_t* ind, const float
     rc = (int)gespmm::launch_gat_weights(ptr, ind, el, er, stats, w, S, H, nnz, slope, transposed != 0, st);
     if (rc == 0) rc = gespmm_csr_spmm_heads_f32(ptr, ind, w, B, C, S, Kb, H, F, nnz, stream);
     return scratch.close(rc);
+}
+
+/* The fused backward of a GAT layer for el / er (gespmm.h; gat_backward.h): two launches on node-sized words, no [nnz x H] array. The
+   ladder is check_gat_backward_sizes, then the pointers. */
+int gespmm_gat_backward_el_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                               const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
+                               int64_t F, int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
+    if (rc != 0) return rc;
+    if (M == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(M, nnz, H);
+    if (nnz == 0 || F == 0) {  // every g is an empty sum: every word of delta and grad_el is still written
+        if (const int rcp = check_pointers({{delta, 4, true}, {grad_el, 4, true}})) return rcp;
+        return (int)gespmm::launch_gat_backward_el(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, delta, grad_el, M, K, H, F,
+                                                   0, slope, r, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true},
+                                        {grad_out, 4, true}, {feat, 4, true}, {delta, 4, true}, {grad_el, 4, true}}))
+        return rcp;
+    return (int)gespmm::launch_gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, delta, grad_el, M, K, H, F, nnz, slope, r, st);
+}
+
+int gespmm_gat_backward_er_f32(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                               const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K, int64_t H,
+                               int64_t F, int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(K, nnz, H);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{grad_er, 4, true}})) return rcp;
+        return (int)gespmm::launch_gat_backward_er(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, grad_er, M, K, H, F,
+                                                   0, slope, r, st);
+    }
+    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true},
+                                        {delta, 4, true}, {grad_out, 4, true}, {feat, 4, true}, {grad_er, 4, true}}))
+        return rcp;
+    return (int)gespmm::launch_gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope, r, st);
 }
 
 int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,

@@ -27,6 +27,26 @@
 
 namespace gespmm {
 
+// ---- the two cross-lane steps of the geometry above, shared by the kernels that use it (edge_softmax.hip, gat_backward.hip)
+// Sum over the W lanes of a group: the xor butterfly W/2 .. 1, the same bits in every lane.
+template <int W>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int m = W >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// Largest degree among the wavefront's 64 / W lane groups, in a scalar register.
+template <int W>
+__device__ __forceinline__ int wave_max_degree(int d) {
+#pragma unroll
+    for (int m = 32; m >= W; m >>= 1) {
+        const int o = __shfl_xor(d, m, 64);
+        d = o > d ? o : d;
+    }
+    return __builtin_amdgcn_readfirstlane(d);
+}
+
 // nnz > 0, M > 0, H >= 1, nnz H <= kSddmmMaxNnz, M <= kEdgeSoftmaxMaxRows. slope == 1: no leaky ReLU.
 hipError_t launch_edge_softmax(const int32_t* rowptr, const float* score, float* out, int64_t M, int64_t H, int64_t nnz, float slope,
                                const EdgeSoftmaxLaunch& r, hipStream_t st);

@@ -26,24 +26,6 @@ __device__ __forceinline__ float group_max(float v) {
     return v;
 }
 
-template <int W>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int m = W >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// Largest degree among the wavefront's 64 / W lane groups, in a scalar register.
-template <int W>
-__device__ __forceinline__ int wave_max_degree(int d) {
-#pragma unroll
-    for (int m = 32; m >= W; m >>= 1) {
-        const int o = __shfl_xor(d, m, 64);
-        d = o > d ? o : d;
-    }
-    return __builtin_amdgcn_readfirstlane(d);
-}
-
 template <bool LEAKY>
 __device__ __forceinline__ float leaky(float x, float slope) {
     if constexpr (LEAKY) return x >= 0.0f ? x : slope * x;

@@ -14,6 +14,14 @@
 
 namespace gespmm {
 
+// The ONE expression of a weight, shared by the aggregation kernel, the composition and the fused backward (gat_backward.hip):
+// softmax_pair's, term for term.
+__device__ __forceinline__ float gat_weight(float el, float er, float2 ms, float slope) {
+    float x = el + er;
+    x = x >= 0.0f ? x : slope * x;
+    return __expf(x - ms.x) / ms.y;
+}
+
 // rowptr / colind = (ptr, ind), M = segments, N = H F, val unused. 1 <= H <= kHeadsMax (H = 1 runs the kernel too).
 struct GatAggregateArgs : SpmmArgs {
     int32_t H;

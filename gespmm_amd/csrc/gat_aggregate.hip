@@ -11,13 +11,6 @@
 
 namespace gespmm {
 
-// The ONE expression of a weight (gat_aggregate.h), shared by the kernel and the composition: softmax_pair's, term for term.
-__device__ __forceinline__ float gat_weight(float el, float er, float2 ms, float slope) {
-    float x = el + er;
-    x = x >= 0.0f ? x : slope * x;
-    return __expf(x - ms.x) / ms.y;
-}
-
 // ----------------------------------------------------------------------------- the kernel
 //
 // Structure, row walk and store are spmm_heads_kernel's (see there; storage order only). What differs is where s_val comes from:

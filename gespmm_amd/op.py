@@ -306,7 +306,8 @@ class GATAggregateFunction(torch.autograd.Function):
     attention array (``softmax.gat_softmax_stats`` + ``spmm.gat_aggregate``): the weights are computed inside the product's kernel
     from el, er and two words per (row, head).
 
-        GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None) -> f32[M, H, F]
+        GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None,
+                                   fused_backward=False) -> f32[M, H, F]
 
     ``el`` f32[M, H], ``er`` f32[K, H], ``feat`` f32[K, H, F]; ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K,
     return_order=True)``. The output has the bits of ``MultiHeadSPMMFunction`` on ``GATSoftmaxFunction``'s alpha. Saved: ``el``,
@@ -315,16 +316,23 @@ class GATAggregateFunction(torch.autograd.Function):
     grad_er alpha is recomputed (``softmax.gat_edge_softmax``: the forward's bits) and the steps are those of the two functions
     above — ``sddmm.csr_sddmm_heads`` for grad_alpha, ``softmax.gat_edge_softmax_backward``, ``softmax.edge_segment_sum`` on
     ``(colptr, csc_order)`` — so every gradient has their bits; alpha and grad_alpha live only inside the backward. An int64
-    ``csc_order`` is converted to int32 in every forward; pass an int32 one. Index tensors get no gradient."""
+    ``csc_order`` is converted to int32 in every forward; pass an int32 one. Index tensors get no gradient.
+
+    ``fused_backward=True``: grad_el / grad_er are ``softmax.gat_backward_el`` and ``softmax.gat_backward_er`` — two launches that
+    recompute weight, dot product and softmax backward per entry from node-sized words; the backward allocates nothing of size
+    nnz H either (``csc_order`` is not looked at). The second launch is made only when ``er`` requires grad. grad_feat is the same
+    launch; grad_el / grad_er differ from the default's by the rounding of the dot product's summation order."""
 
     @staticmethod
-    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None):
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None, fused_backward=False):
         el_c, er_c, feat_c = el.contiguous(), er.contiguous(), feat.contiguous()
         stats = _softmax.gat_softmax_stats(rowptr, colind, el_c, er_c, negative_slope=negative_slope)
         out = _spmm.gat_aggregate(rowptr, colind, el_c, er_c, stats, feat_c, negative_slope=negative_slope)
-        order = csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)
-        ctx.graph = (rowptr, colind, colptr, rowind, order.contiguous())
-        ctx.negative_slope = negative_slope
+        order = None
+        if not fused_backward:
+            order = (csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)).contiguous()
+        ctx.graph = (rowptr, colind, colptr, rowind, order)
+        ctx.negative_slope, ctx.fused_backward = negative_slope, bool(fused_backward)
         ctx.save_for_backward(el_c, er_c, feat_c, stats)
         return out
 
@@ -335,7 +343,13 @@ class GATAggregateFunction(torch.autograd.Function):
         slope = ctx.negative_slope
         grad_out = grad_out.contiguous()
         grad_el = grad_er = grad_feat = None
-        if ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:  # (first: its three edge-sized temporaries are gone before grad_feat exists)
+        if ctx.fused_backward and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):  # node-sized tensors only
+            delta, grad_el = _softmax.gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=slope)
+            if ctx.needs_input_grad[6]:
+                grad_er = _softmax.gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=slope)
+            if not ctx.needs_input_grad[5]:
+                grad_el = None
+        elif ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:  # (first: its three edge-sized temporaries are gone before grad_feat exists)
             alpha = _softmax.gat_edge_softmax(rowptr, colind, el, er, negative_slope=slope)
             grad_alpha = _sddmm.csr_sddmm_heads(rowptr, colind, grad_out, feat)
             grad_score, grad_el = _softmax.gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=el if slope is not None else None,
@@ -348,7 +362,7 @@ class GATAggregateFunction(torch.autograd.Function):
                 grad_el = None
         if ctx.needs_input_grad[7]:
             grad_feat = _spmm.gat_aggregate(colptr, rowind, el, er, stats, grad_out, negative_slope=slope, transposed=True)
-        return None, None, None, None, None, grad_el, grad_er, grad_feat, None
+        return None, None, None, None, None, grad_el, grad_er, grad_feat, None, None
 
 
 def glorot(tensor):
@@ -472,7 +486,7 @@ class GATConv(torch.nn.Module):
     and its backward hands grad_el and grad_er back as component 0 of grad_q and component 1 of grad_k.
 
         GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
-                fused_aggregate=False)
+                fused_aggregate=False, fused_backward=False)
         forward(x, rowptr, colind, colptr, rowind, csc_order)
 
     ``fused_score=True``: the score and the softmax are ONE ``GATSoftmaxFunction`` — el + er is added inside the softmax kernel, no
@@ -484,13 +498,18 @@ class GATConv(torch.nn.Module):
     CSC arrays with no ``alpha[csc_order]`` copy, and only the backward for ``att_dst`` / ``att_src`` recomputes alpha, transiently.
     Output and all gradients have the bits of ``fused_score=True``. Off by default.
 
+    ``fused_backward=True`` (implies the fused aggregation): that backward recomputes nothing edge-sized either — the gradients for
+    ``att_dst`` / ``att_src`` come from ``softmax.gat_backward_el`` / ``gat_backward_er``, so a layer allocates no ``[nnz, H]`` array
+    forward or backward. Same output bits; the two gradients agree to rounding. Off by default.
+
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
     ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
-                 fused_aggregate=False):
+                 fused_aggregate=False, fused_backward=False):
         super().__init__()
-        self.fused_aggregate = bool(fused_aggregate)
+        self.fused_backward = bool(fused_backward)
+        self.fused_aggregate = bool(fused_aggregate) or self.fused_backward
         self.fused_score = bool(fused_score) or self.fused_aggregate
         if heads < 1:
             raise ValueError("heads must be at least 1")
@@ -518,7 +537,8 @@ class GATConv(torch.nn.Module):
         el = (xw * self.att_dst).sum(-1)
         er = (xw * self.att_src).sum(-1)
         if self.fused_aggregate:
-            out = GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, xw, self.negative_slope)
+            out = GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, xw, self.negative_slope,
+                                             self.fused_backward)
             out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
             return out if self.bias is None else out + self.bias
         if self.fused_score:

@@ -7,6 +7,8 @@ gespmm_edge_softmax_backward_f32 — the reference has no counterpart).
     gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=None, er=None, negative_slope=None) -> (grad_score, grad_el)
     edge_segment_sum(ptr, x, order=None, out=None)                                                -> f32[S, H] (or f32[S])
     gat_softmax_stats(rowptr, colind, el, er, negative_slope=None, out=None)                      -> f32[M, H, 2]
+    gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None) -> (delta f32[M, H], grad_el f32[M, H])
+    gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None) -> grad_er f32[K, H]
 
 ``score`` is f32[nnz] or f32[nnz, H] in CSR edge order — what ``sddmm.csr_sddmm`` / ``sddmm.csr_sddmm_heads`` return and what
 ``spmm.csr_spmm`` / ``spmm.csr_spmm_heads`` take as edge weights. For row r with entries [lo, hi) and head h
@@ -26,6 +28,9 @@ score ``sddmm.csr_sddmm_heads`` writes for ``q = (el, 1), k = (1, er)``. Its bac
 permuted copy. The sums have a pinned order (include/gespmm.h), the one ``edge_segment_sum(rowptr, grad_score)`` reproduces.
 ``gat_softmax_stats`` returns what that softmax divides by — per (row, head) the maximum and the sum, with its bits — for
 ``spmm.gat_aggregate``, which computes the weights inside the aggregation and needs no ``[nnz, H]`` array at all.
+``gat_backward_el`` / ``gat_backward_er`` are that aggregation's backward for ``el`` and ``er``: two launches that compute the weight,
+the dot product ``<grad_out[row], feat[col]>`` and the softmax's backward per entry from node-sized words, over the rows and over the
+columns, and sum them in the pinned order — no ``[nnz, H]`` array there either.
 All calls go through ctypes."""
 import torch
 
@@ -276,4 +281,96 @@ def edge_segment_sum(ptr, x, order=None, out=None):
         rc = lib.gespmm_edge_segment_sum_f32(_ptr(ptr), _ptr(order) if order is not None else None, _ptr(x), _ptr(out), S, H, nnz,
                                              _stream(dev))
     check(rc, "gespmm_edge_segment_sum_f32")
+    return out
+
+
+def _head_rows(t, name, rows, H, dev, F=None):
+    """fp32, contiguous, [rows, H, F] on ``dev`` (F >= 1; the given F when there is one) -> F"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must have dtype torch.float32, got %s" % (name, t.dtype))
+    if t.dim() != 3 or t.shape[0] != rows or t.shape[1] != H or t.shape[2] < 1 or (F is not None and t.shape[2] != F):
+        raise ValueError("%s must be f32[%d, %d, %s], got %s" % (name, rows, H, "F" if F is None else F, list(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    if t.device != dev:
+        raise ValueError("%s must live on %s, as the other operands" % (name, dev))
+    return t.shape[2]
+
+
+def _node_result(t, name, rows, H, dev):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must have dtype torch.float32, got %s" % (name, t.dtype))
+    if tuple(t.shape) != (rows, H) or t.device != dev or not t.is_contiguous():
+        raise ValueError("%s must be contiguous f32[%d, %d] on %s" % (name, rows, H, dev))
+
+
+def _typed(dtype, **operands):
+    """TypeError for what is no tensor of ``dtype`` — for every operand before any of them is looked at more closely."""
+    for name, t in operands.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != dtype:
+            raise TypeError("%s must have dtype %s, got %s" % (name, dtype, t.dtype))
+
+
+def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None):
+    """Backward of ``spmm.gat_aggregate`` for ``el`` with no edge array (gespmm_gat_backward_el_f32) -> ``(delta, grad_el)``, both
+    f32[M, H]: per entry the weight (``stats = gat_softmax_stats(..)``: the bits of alpha), ``g = <grad_out[row], feat[col]>`` (one
+    fmaf chain over ascending f) and ``gs = w (g - delta) * leaky'``, with ``delta = sum_row(w g)`` and ``grad_el = sum_row(gs)`` in
+    the pinned order of ``gat_edge_softmax_backward``. ``grad_out`` f32[M, H, F], ``feat`` f32[K, H, F]. ``delta`` is what
+    ``gat_backward_er`` needs. ``out``: a pair of tensors ``(delta, grad_el)`` to write into; every word is written, empty rows +0."""
+    slope = _slope(negative_slope)
+    _typed(torch.int32, rowptr=rowptr, colind=colind)
+    _typed(torch.float32, el=el, er=er, stats=stats, grad_out=grad_out, feat=feat)
+    dev, M, K, H, nnz = _gat_terms(rowptr, colind, el, er)
+    _stats_array(stats, "stats", M, H, dev)
+    F = _head_rows(grad_out, "grad_out", M, H, dev)
+    _head_rows(feat, "feat", K, H, dev, F)
+    if out is None:
+        delta = torch.empty(M, H, dtype=torch.float32, device=dev)
+        grad_el = torch.empty(M, H, dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise TypeError("out must be a pair of tensors (delta, grad_el)")
+        delta, grad_el = out
+        _node_result(delta, "out[0]", M, H, dev)
+        _node_result(grad_el, "out[1]", M, H, dev)
+    with _on_device(dev):
+        rc = lib.gespmm_gat_backward_el_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(stats), _ptr(grad_out), _ptr(feat),
+                                            _ptr(delta), _ptr(grad_el), M, K, H, F, nnz, slope, _stream(dev))
+    check(rc, "gespmm_gat_backward_el_f32")
+    return delta, grad_el
+
+
+def gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None):
+    """Backward of ``spmm.gat_aggregate`` for ``er`` with no edge array (gespmm_gat_backward_er_f32) -> ``grad_er`` f32[K, H]: the same
+    per-entry ``gs`` as ``gat_backward_el``, recomputed with the same bits from ``delta`` (that call's first result), summed over the
+    entries of each column in the pinned order of ``edge_segment_sum(colptr, .., order=csc_order)``. ``colptr, rowind`` are the CSC
+    arrays (``graphs.transpose_csr``); no ``csc_order`` is needed. Every word is written, empty columns +0."""
+    slope = _slope(negative_slope)
+    _typed(torch.int32, colptr=colptr, rowind=rowind)
+    _typed(torch.float32, el=el, er=er, stats=stats, delta=delta, grad_out=grad_out, feat=feat)
+    K = _checked_rowptr(colptr)
+    _node_array(er, "er", rows=K)
+    _node_array(el, "el", like=er)
+    dev = er.device
+    _checked_rowptr(colptr, dev)
+    _index_vector(rowind, "rowind", dev)
+    M, H, nnz = el.shape[0], er.shape[1], rowind.numel()
+    _stats_array(stats, "stats", M, H, dev)
+    _node_result(delta, "delta", M, H, dev)
+    F = _head_rows(grad_out, "grad_out", M, H, dev)
+    _head_rows(feat, "feat", K, H, dev, F)
+    if out is None:
+        out = torch.empty(K, H, dtype=torch.float32, device=dev)
+    else:
+        _node_result(out, "out", K, H, dev)
+    with _on_device(dev):
+        rc = lib.gespmm_gat_backward_er_f32(_ptr(colptr), _ptr(rowind), _ptr(el), _ptr(er), _ptr(stats), _ptr(delta), _ptr(grad_out),
+                                            _ptr(feat), _ptr(out), M, K, H, F, nnz, slope, _stream(dev))
+    check(rc, "gespmm_gat_backward_er_f32")
     return out

@@ -33,6 +33,8 @@
  *                               attention layer, el[row] + er[col], never written; the per-segment sum of an edge array
  *   gespmm_gat_softmax_stats_f32 / gespmm_gat_aggregate_f32 / gespmm_gat_aggregate_route <- (new) that softmax's row statistics, and the
  *                               multi-head product that computes the attention weights from them: no [nnz x H] array at all
+ *   gespmm_gat_backward_el_f32 / gespmm_gat_backward_er_f32 <- (new) the backward of that layer for el and er: two launches on
+ *                               node-sized words, no [nnz x H] array either
  *   gespmm_baseline_copy_f32 <- (new) streaming-copy yardstick for the roofline record; no reference counterpart
  *
  * Conventions (all device entry points):
@@ -662,6 +664,36 @@ int gespmm_gat_aggregate_f32(const int32_t* ptr, const int32_t* ind, const float
  * code; geometry_out (may be NULL): V, strips, W, rows per wavefront of route 1, zeros for route 0. */
 int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,
                                int32_t* geometry_out);
+/*
+ * The backward of a graph attention layer for its two score terms with no [nnz x H] array (since 0.5). el [M x H], er [K x H], stats
+ * [M x H x 2] as above; grad_out [M x H x F] is the gradient of gespmm_gat_aggregate_f32's C, feat [K x H x F] its B. For entry p of
+ * row r, column c, head h
+ *
+ *     g_p = sum_f grad_out[r, h, f] feat[c, h, f]             delta[r, h] = sum over row r of w(r, c, h) g_p
+ *     gs_p = w(r, c, h) (g_p - delta[r, h]) (fl(el[r H + h] + er[c H + h]) >= 0 ? 1 : slope)         (the factor only when slope != 1)
+ *     grad_el[r, h] = sum over row r of gs_p                  grad_er[c, h] = sum over column c of gs_p
+ *
+ * gespmm_gat_backward_el_f32 walks the rows (rowptr, colind) and writes delta and grad_el [M x H]; gespmm_gat_backward_er_f32 walks
+ * the columns (colptr, rowind: the CSC arrays, no csc_order), reads delta and writes grad_er [K x H]. gs_p is computed in both, from
+ * node-sized words alone, with the same bits. Lane geometry: the edge softmax's, W and L from gespmm_describe_edge_softmax(M, nnz, H)
+ * for the rows and (K, nnz, H) for the columns. Pinned orders: g_p is ONE fmaf chain over ascending f from +0, whatever F, the
+ * alignment (16-byte loads when F % 4 == 0 and grad_out and feat are 16-byte aligned, 4-byte loads otherwise) or the mode; delta is
+ * the dot of gespmm_gat_softmax_backward_f32 (fmaf(w, g, dot) per lane in entry order, then the xor butterfly W/2 .. 1); gs_p is
+ * `r = w * (g - delta); r *= factor`; grad_el and grad_er are the chain of gespmm_edge_segment_sum_f32 (plain adds from +0, then the
+ * butterfly). Where g_p has the bits gespmm_sddmm_csr_heads_f32 gives it (always when its partial sums are exact), delta, grad_el and
+ * grad_er have the bits of gespmm_gat_softmax_f32 + gespmm_sddmm_csr_heads_f32 + gespmm_gat_softmax_backward_f32 +
+ * gespmm_edge_segment_sum_f32(colptr, .., csc_order). Every word of the results is written (an empty row or column: +0).
+ * Checks, in this order: the ladder of gespmm_gat_aggregate_f32 on (M, K, H, F, nnz, slope) in both directions; M H F or K H F >
+ * 2^31 - 4097 -> GESPMM_ERANGE; gespmm_gat_backward_el_f32 with M == 0 -> 0; nnz == 0 or F == 0 looks at the results alone and
+ * zero-fills them (hipMemsetAsync); NULL -> GESPMM_EINVAL; a pointer not 4-byte (stats: 8-byte) aligned -> GESPMM_EALIGN. One kernel
+ * each, no atomics, no workspace, no allocation: capturable. The results must not overlap an input (not checked).
+ */
+int gespmm_gat_backward_el_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                               const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
+                               int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gat_backward_er_f32(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                               const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K, int64_t H,
+                               int64_t F, int64_t nnz, float slope, void* stream);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
