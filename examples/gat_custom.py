@@ -9,6 +9,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
     python examples/gat_custom.py --fused-score                    # el + er added inside the softmax kernel: no score array
     python examples/gat_custom.py --fused-aggregate                # ... and the weights computed inside the aggregation: no alpha array
     python examples/gat_custom.py --fused-backward                 # ... and no [nnz, H] array in the backward either
+    python examples/gat_custom.py --fused-backward --attn-dropout 0.6   # the paper's dropout on the attention coefficients: a mask recomputed
+                                                                   # from a seed wherever an entry is seen, never stored
     python examples/gat_custom.py --seed 0 --fused-aggregate       # seeded parameters and dropout: the losses of --seed 0 --fused-score
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
@@ -43,9 +45,10 @@ def gat_graph(edge_index, n_v, device, int32_order=False):
 
 
 class Net(torch.nn.Module):
-    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False, fused_aggregate=False, fused_backward=False):
+    def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False, fused_aggregate=False, fused_backward=False,
+                 attn_dropout=0.0):
         super().__init__()
-        fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward)
+        fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward, dropout=attn_dropout)
         self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, **fused)
         self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, **fused)
         self.dropout = dropout
@@ -64,7 +67,9 @@ def main():
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--dataset", default="pubmed")
     ap.add_argument("--epochs", type=int, default=200)
-    ap.add_argument("--dropout", type=float, default=0.6)
+    ap.add_argument("--dropout", type=float, default=0.6, help="dropout on the features in front of each layer")
+    ap.add_argument("--attn-dropout", type=float, default=0.0,
+                    help="GATConv(dropout=P) in both layers: dropout on the attention coefficients (the paper: 0.6)")
     ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
     ap.add_argument("--fused-score", action="store_true", help="GATConv(fused_score=True): score and softmax in one kernel")
     ap.add_argument("--fused-aggregate", action="store_true",
@@ -97,7 +102,7 @@ def main():
     if args.seed is not None:
         torch.manual_seed(args.seed)
     model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score,
-                fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward).to(device)
+                fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward, attn_dropout=args.attn_dropout).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
     train_idx = masks["train"].nonzero().squeeze(1)
     y_train = y[train_idx]
@@ -156,9 +161,9 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s fused_backward=%s" %
+    print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s fused_backward=%s%s" %
           (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score, args.fused_aggregate,
-           args.fused_backward))
+           args.fused_backward, " attn_dropout=%g" % args.attn_dropout if args.attn_dropout else ""))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
 

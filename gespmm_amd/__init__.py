@@ -16,7 +16,7 @@ There is no CPU compute path anywhere in this package.
 """
 from . import _lib  # noqa: F401  (loads libgespmm.so, raises if it is not built)
 from . import spmm, sddmm, softmax, graphs  # noqa: F401
-from .op import SPMMFunction, FusedGCNFunction, MultiHeadSPMMFunction, MultiHeadSDDMMFunction, EdgeSoftmaxFunction, GATSoftmaxFunction, GATAggregateFunction, GCNConv, GATConv  # noqa: F401
+from .op import SPMMFunction, FusedGCNFunction, MultiHeadSPMMFunction, MultiHeadSDDMMFunction, EdgeSoftmaxFunction, EdgeDropoutFunction, GATSoftmaxFunction, GATAggregateFunction, GCNConv, GATConv  # noqa: F401
 
 __all__ = ["spmm", "sddmm", "softmax", "graphs", "SPMMFunction", "FusedGCNFunction", "MultiHeadSPMMFunction", "MultiHeadSDDMMFunction",
-           "EdgeSoftmaxFunction", "GATSoftmaxFunction", "GATAggregateFunction", "GCNConv", "GATConv"]
+           "EdgeSoftmaxFunction", "EdgeDropoutFunction", "GATSoftmaxFunction", "GATAggregateFunction", "GCNConv", "GATConv"]

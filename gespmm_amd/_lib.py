@@ -117,6 +117,12 @@ EXPORTS = [
     "gespmm_gat_aggregate_route",
     "gespmm_gat_backward_el_f32",
     "gespmm_gat_backward_er_f32",
+    "gespmm_edge_dropout_f32",
+    "gespmm_gat_aggregate_dropout_f32",
+    "gespmm_gat_backward_el_dropout_f32",
+    "gespmm_gat_backward_er_dropout_f32",
+    "gespmm_edge_dropout_bits",
+    "gespmm_edge_dropout_threshold",
 ]
 
 X16_F16 = 1
@@ -313,6 +319,17 @@ def _load():
     for f in (lib.gespmm_gat_backward_el_f32, lib.gespmm_gat_backward_er_f32):
         f.restype = c_int
         f.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_edge_dropout_f32.restype = c_int
+    lib.gespmm_edge_dropout_f32.argtypes = [p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_float, p, p]
+    lib.gespmm_gat_aggregate_dropout_f32.restype = c_int
+    lib.gespmm_gat_aggregate_dropout_f32.argtypes = lib.gespmm_gat_aggregate_f32.argtypes[:-1] + [c_float, p, p]
+    for f in (lib.gespmm_gat_backward_el_dropout_f32, lib.gespmm_gat_backward_er_dropout_f32):
+        f.restype = c_int
+        f.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_edge_dropout_bits.restype = ctypes.c_uint32
+    lib.gespmm_edge_dropout_bits.argtypes = [ctypes.c_uint32] * 5
+    lib.gespmm_edge_dropout_threshold.restype = ctypes.c_uint32
+    lib.gespmm_edge_dropout_threshold.argtypes = [c_float]
     lib.gespmm_gat_aggregate_route.restype = c_int
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
@@ -424,6 +441,17 @@ def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):
     if rc < 0:
         raise GespmmError(rc, "gespmm_heads_route")
     return rc, tuple(int(x) for x in geo)
+
+
+def edge_dropout_bits(s0, s1, r, c, h):
+    """The 32 bits the dropout mask compares with its threshold for entry (r, c), head h and seed (s0, s1), as the library's C++
+    computes them (gespmm_edge_dropout_bits: host only)."""
+    return int(lib.gespmm_edge_dropout_bits(int(s0) & 0xFFFFFFFF, int(s1) & 0xFFFFFFFF, int(r), int(c), int(h)))
+
+
+def edge_dropout_threshold(p):
+    """The threshold T of the dropout mask for probability p: an entry is kept when its bits are >= T (gespmm_edge_dropout_threshold)."""
+    return int(lib.gespmm_edge_dropout_threshold(float(p)))
 
 
 def gat_aggregate_route(M, K, H, F, nnz, transposed=False, b_align=16, c_align=16):

@@ -22,6 +22,7 @@
 #include "../../include/gespmm.h"
 #include "select.h"
 #include "auto_plan.h"
+#include "edge_dropout.h"
 #include "edge_softmax.h"
 #include "gat_aggregate.h"
 #include "gat_backward.h"
@@ -329,7 +330,7 @@ int run_spmm_heads(const CsrView& A, const float* B, float* C, int64_t H, int64_
 // A.K the rows of B; the geometry is run_spmm_heads's, H = 1 included. The stream is never asked.
 int check_gat_softmax_sizes(int64_t M, int64_t K, int64_t H, int64_t nnz, float slope);  // (below, with the softmax's other checks)
 int run_gat_aggregate(const CsrView& A, const GatTerms& t, const float* B, float* C, int64_t H, int64_t F, bool transposed, void* stream,
-                      int b_align, int c_align, bool dry_run, int* kind, Geometry* geo_out) {
+                      int b_align, int c_align, bool dry_run, int* kind, Geometry* geo_out, const EdgeDropout* drop = nullptr) {
     *kind = 0;
     if (H < 1 || H > kHeadsMax || A.M <= 0 || F <= 0 || A.nnz < 0 || b_align < 4 || c_align < 4) return kHeadsUnavailable;
     // GESPMM_GAT_AGGREGATE_ROUTE=composition pins route 0 (read per call: scripts/gat_aggregate_timing.py measures both in one process)
@@ -353,7 +354,7 @@ int run_gat_aggregate(const CsrView& A, const GatTerms& t, const float* B, float
     a.er = t.er;
     a.stats = t.stats;
     a.slope = t.slope;
-    return (int)launch_gat_aggregate(a, r.sel.geo, transposed, reinterpret_cast<hipStream_t>(stream));
+    return (int)launch_gat_aggregate(a, r.sel.geo, transposed, drop, reinterpret_cast<hipStream_t>(stream));
 }
 
 // gespmm_gat_aggregate_f32 / gespmm_gat_aggregate_route: the ladder of gespmm_gat_softmax_f32 on (M, K, H, nnz), then the multi-head
@@ -363,6 +364,13 @@ int check_gat_aggregate_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_
     const int rc = check_gat_softmax_sizes(M, K, H, nnz, slope);
     if (rc != 0) return rc;
     return check_heads_sizes(transposed ? K : M, transposed ? M : K, H, F, nnz);
+}
+
+// ---- dropout on the attention coefficients (gespmm.h: gespmm_edge_dropout_f32 and the *_dropout_f32 forms; edge_dropout.h). A bad p joins
+// the step of the base entry's ladder that rejects a bad slope: `rc` is what the base's size checks said.
+int check_dropout_p(int rc, float p) {
+    if (rc == GESPMM_EINVAL || !(p >= 0.0f && p < 1.0f)) return GESPMM_EINVAL;
+    return rc;
 }
 
 // ---- the multi-head SDDMM (gespmm.h: gespmm_sddmm_{coo,csr}_heads_f32; sddmm_heads.h). GESPMM_SDDMM_HEADS_ROUTE=kernel|composition pins
@@ -966,71 +974,143 @@ int gespmm_gat_softmax_stats_f32(const int32_t* rowptr, const int32_t* colind, c
 
 /* The fused GAT aggregation (gespmm.h): one kernel that computes the weights where the multi-head product loads them, else the
    composition — the same weights into a stream-ordered temporary, then gespmm_csr_spmm_heads_f32 on it. Same bits either way. */
-int gespmm_gat_aggregate_f32(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const float* B,
-                             float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed, void* stream) {
+static int gat_aggregate_entry(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const float* B,
+                               float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed,
+                               const float* p, const void* seed, void* stream) {
     if (transposed != 0 && transposed != 1) return GESPMM_EINVAL;
     int rc = gespmm::check_gat_aggregate_sizes(M, K, H, F, nnz, slope, transposed != 0);
+    if (p) rc = gespmm::check_dropout_p(rc, *p);
     if (rc != 0) return rc;
     const int64_t S = transposed ? K : M, Kb = transposed ? M : K;  // segments, rows of B
     if (S == 0 || F == 0) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (nnz == 0) {  // C = 0
-        if (const int rcp = check_pointers({{C, 4, true}})) return rcp;
+        if (const int rcp = check_pointers({{C, 4, true}, {seed, 4, p != nullptr}})) return rcp;
         return (int)hipMemsetAsync(C, 0, (size_t)S * (size_t)H * (size_t)F * sizeof(float), st);
     }
-    rc = check_pointers({{ptr, 4, true}, {ind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true}, {B, 4, true}, {C, 4, true}});
+    rc = check_pointers({{ptr, 4, true}, {ind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true}, {B, 4, true}, {C, 4, true},
+                         {seed, 4, p != nullptr}});
     if (rc != 0) return rc;
     const gespmm::GatTerms terms = {el, er, stats, slope};
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    const gespmm::EdgeDropout* drop = p ? &dropout : nullptr;
     int kind = 0;
     rc = gespmm::run_gat_aggregate(csr_view(ptr, ind, nullptr, S, Kb, nnz, GESPMM_VARIANT_AUTO), terms, B, C, H, F, transposed != 0, stream,
-                                   pointer_alignment(B), pointer_alignment(C), false, &kind, nullptr);
+                                   pointer_alignment(B), pointer_alignment(C), false, &kind, nullptr, drop);
     if (rc != kHeadsUnavailable) return rc;
     const size_t w_bytes = (size_t)nnz * (size_t)H * 4;
     PooledScratch scratch;
     if ((rc = scratch.open(w_bytes, st)) != 0) return rc;  // (nothing launched; a capturing stream: what the heads composition returns)
     float* w = scratch.take(w_bytes);
     rc = (int)gespmm::launch_gat_weights(ptr, ind, el, er, stats, w, S, H, nnz, slope, transposed != 0, st);
+    if (rc == 0 && drop) rc = (int)gespmm::launch_edge_dropout(ptr, ind, w, w, S, H, nnz, *drop, transposed != 0, st);  // the same expression
     if (rc == 0) rc = gespmm_csr_spmm_heads_f32(ptr, ind, w, B, C, S, Kb, H, F, nnz, stream);
     return scratch.close(rc);
 }
 
+int gespmm_gat_aggregate_f32(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const float* B,
+                             float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed, void* stream) {
+    return gat_aggregate_entry(ptr, ind, el, er, stats, B, C, M, K, H, F, nnz, slope, transposed, nullptr, nullptr, stream);
+}
+
+/* ... with dropout on the weights (gespmm.h; edge_dropout.h): the staged weight is dropout(weight), route 0 applies the same expression
+   to its temporary. The ladder is the base entry's; a bad p joins the bad slope, the seed the pointers. */
+int gespmm_gat_aggregate_dropout_f32(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats,
+                                     const float* B, float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                     int transposed, float p, const void* seed, void* stream) {
+    return gat_aggregate_entry(ptr, ind, el, er, stats, B, C, M, K, H, F, nnz, slope, transposed, &p, seed, stream);
+}
+
+/* Dropout on an [nnz, H] array of the pattern (gespmm.h; edge_dropout.h): the softmax's ladder on (M, K, H, nnz) with p in the slope's
+   place, then the pointers. */
+int gespmm_edge_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* x, float* y, int64_t M, int64_t K, int64_t H,
+                            int64_t nnz, float p, const void* seed, void* stream) {
+    const int rc = gespmm::check_dropout_p(gespmm::check_gat_softmax_sizes(M, K, H, nnz, 1.0f), p);
+    if (rc != 0) return rc;
+    if (nnz == 0) return 0;
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {x, 4, true}, {y, 4, true}, {seed, 4, true}})) return rcp;
+    return (int)gespmm::launch_edge_dropout(rowptr, colind, x, y, M, H, nnz, gespmm::make_edge_dropout(p, seed), false,
+                                            reinterpret_cast<hipStream_t>(stream));
+}
+
+uint32_t gespmm_edge_dropout_bits(uint32_t s0, uint32_t s1, uint32_t r, uint32_t c, uint32_t h) {
+    return gespmm::edge_dropout_bits(s0, s1, r, c, h);
+}
+
+/* T of edge_dropout.h for 0 <= p < 1. Anything else (NaN included) answers 0xffffffff, which no legal p gives (the largest float below 1
+   gives 2^32 - 256). */
+uint32_t gespmm_edge_dropout_threshold(float p) { return (p >= 0.0f && p < 1.0f) ? gespmm::edge_dropout_threshold(p) : 0xffffffffu; }
+
 /* The fused backward of a GAT layer for el / er (gespmm.h; gat_backward.h): two launches on node-sized words, no [nnz x H] array. The
    ladder is check_gat_backward_sizes, then the pointers. */
-int gespmm_gat_backward_el_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
-                               const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
-                               int64_t F, int64_t nnz, float slope, void* stream) {
-    const int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
+static int gat_backward_el_entry(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                 const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
+                                 int64_t F, int64_t nnz, float slope, const float* p, const void* seed, void* stream) {
+    int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
+    if (p) rc = gespmm::check_dropout_p(rc, *p);
     if (rc != 0) return rc;
     if (M == 0) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(M, nnz, H);
     if (nnz == 0 || F == 0) {  // every g is an empty sum: every word of delta and grad_el is still written
-        if (const int rcp = check_pointers({{delta, 4, true}, {grad_el, 4, true}})) return rcp;
+        if (const int rcp = check_pointers({{delta, 4, true}, {grad_el, 4, true}, {seed, 4, p != nullptr}})) return rcp;
         return (int)gespmm::launch_gat_backward_el(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, delta, grad_el, M, K, H, F,
-                                                   0, slope, r, st);
+                                                   0, slope, r, nullptr, st);
     }
     if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true},
-                                        {grad_out, 4, true}, {feat, 4, true}, {delta, 4, true}, {grad_el, 4, true}}))
+                                        {grad_out, 4, true}, {feat, 4, true}, {delta, 4, true}, {grad_el, 4, true}, {seed, 4, p != nullptr}}))
         return rcp;
-    return (int)gespmm::launch_gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, delta, grad_el, M, K, H, F, nnz, slope, r, st);
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, delta, grad_el, M, K, H, F, nnz, slope, r,
+                                               p ? &dropout : nullptr, st);
+}
+
+int gespmm_gat_backward_el_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                               const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
+                               int64_t F, int64_t nnz, float slope, void* stream) {
+    return gat_backward_el_entry(rowptr, colind, el, er, stats, grad_out, feat, delta, grad_el, M, K, H, F, nnz, slope, nullptr, nullptr, stream);
+}
+
+int gespmm_gat_backward_el_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                       const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K,
+                                       int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream) {
+    return gat_backward_el_entry(rowptr, colind, el, er, stats, grad_out, feat, delta, grad_el, M, K, H, F, nnz, slope, &p, seed, stream);
+}
+
+static int gat_backward_er_entry(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                 const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K, int64_t H,
+                                 int64_t F, int64_t nnz, float slope, const float* p, const void* seed, void* stream) {
+    int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
+    if (p) rc = gespmm::check_dropout_p(rc, *p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(K, nnz, H);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{grad_er, 4, true}, {seed, 4, p != nullptr}})) return rcp;
+        return (int)gespmm::launch_gat_backward_er(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, grad_er, M, K, H, F,
+                                                   0, slope, r, nullptr, st);
+    }
+    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true},
+                                        {delta, 4, true}, {grad_out, 4, true}, {feat, 4, true}, {grad_er, 4, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope, r,
+                                               p ? &dropout : nullptr, st);
 }
 
 int gespmm_gat_backward_er_f32(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
                                const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K, int64_t H,
                                int64_t F, int64_t nnz, float slope, void* stream) {
-    const int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
-    if (rc != 0) return rc;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(K, nnz, H);
-    if (nnz == 0 || F == 0) {
-        if (const int rcp = check_pointers({{grad_er, 4, true}})) return rcp;
-        return (int)gespmm::launch_gat_backward_er(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, grad_er, M, K, H, F,
-                                                   0, slope, r, st);
-    }
-    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true},
-                                        {delta, 4, true}, {grad_out, 4, true}, {feat, 4, true}, {grad_er, 4, true}}))
-        return rcp;
-    return (int)gespmm::launch_gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope, r, st);
+    return gat_backward_er_entry(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope, nullptr, nullptr, stream);
+}
+
+int gespmm_gat_backward_er_dropout_f32(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                       const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
+                                       int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream) {
+    return gat_backward_er_entry(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope, &p, seed, stream);
 }
 
 int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,

@@ -40,8 +40,11 @@ struct GatTerms {
     float slope;
 };
 
+struct EdgeDropout;  // edge_dropout.h
+
 // One kernel: the geometries heads_geometry_served serves without a plan, 32-bit offsets. hipErrorInvalidValue otherwise.
-hipError_t launch_gat_aggregate(const GatAggregateArgs& a, const Geometry& geo, bool transposed, hipStream_t st);
+// drop != nullptr: the staged weight is dropout(weight(r, c, h)) with edge_dropout.h's mask — the same (r, c) in both modes.
+hipError_t launch_gat_aggregate(const GatAggregateArgs& a, const Geometry& geo, bool transposed, const EdgeDropout* drop, hipStream_t st);
 // The composition's first step: w[p H + h] = weight(..) of entry p in the order of (ptr, ind), S segments. nnz H < 2^31.
 hipError_t launch_gat_weights(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, float* w,
                               int64_t S, int64_t H, int64_t nnz, float slope, bool transposed, hipStream_t st);

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "edge_dropout.h"
 #include "gat_aggregate.h"
 #include "spmm_device.h"
 
@@ -24,8 +25,14 @@ namespace gespmm {
 // A lane past the range's end keeps a valid index (0, or one it loaded earlier) and finds a valid segment (the search never leaves
 // [0, nrows)), so every load is of a valid word; what it publishes is never read. No scratch, no atomics, no workspace.
 
-template <int V, int S, int W, int U, bool TRANSPOSED>
-__global__ __launch_bounds__(kThreads) void gat_aggregate_kernel(GatAggregateArgs a) {
+//
+// DROP (gespmm_gat_aggregate_dropout_f32; edge_dropout.h): the published weight becomes dropout(gat_weight(..)). The entry's (row, column)
+// is known where its terms are fetched — forward (segment, index), transposed (index, segment): the same pair — so fetch_terms folds it
+// into one word (the two mixes the heads share) and publish_tile spends one mix per head. The seed's two words are loaded once per
+// wavefront, uniformly. Everything of it sits behind `if constexpr`: the DROP = false body is the kernel as it was.
+
+template <int V, int S, int W, int U, bool TRANSPOSED, bool DROP>
+__device__ __forceinline__ void gat_aggregate_body(const GatAggregateArgs& a, const EdgeDropout& drop) {
     constexpr int G = 64 / W;
 
     __shared__ uint32_t s_off[kWaves][kTile];
@@ -37,6 +44,11 @@ __global__ __launch_bounds__(kThreads) void gat_aggregate_kernel(GatAggregateArg
     const int g = lane / W;
     const int l = lane % W;
     const int H = a.H;  // wave-uniform (kernel argument)
+    uint32_t seed0 = 0, seed1 = 0, pent = 0;  // (DROP only) the seed; the entry's part of the mask's bits, fetched with its terms
+    if constexpr (DROP) {
+        seed0 = drop.seed[0];
+        seed1 = drop.seed[1];
+    }
 
     const int nitems = a.nblk * a.ntile;
     const int item = (a.flags & kFlagNoXcdRemap) ? (int)blockIdx.x : xcd_contiguous(blockIdx.x, nitems);
@@ -96,6 +108,8 @@ __global__ __launch_bounds__(kThreads) void gat_aggregate_kernel(GatAggregateArg
         }
         const int rowi = (TRANSPOSED ? pc : row_first + seg) * H;  // (M H and K H words: 32-bit positions)
         const int coli = (TRANSPOSED ? row_first + seg : pc) * H;
+        if constexpr (DROP)
+            pent = edge_dropout_entry(seed0, (uint32_t)(TRANSPOSED ? pc : row_first + seg), (uint32_t)(TRANSPOSED ? row_first + seg : pc));
 #pragma unroll
         for (int i = 0; i < kHeadsMax; ++i)
             if (i < H) {
@@ -108,7 +122,13 @@ __global__ __launch_bounds__(kThreads) void gat_aggregate_kernel(GatAggregateArg
         s_off[wave][lane] = (uint32_t)pc * rowbytes;
 #pragma unroll
         for (int i = 0; i < kHeadsMax; ++i)
-            if (i < H) s_val[wave][lane * H + i] = gat_weight(pel[i], per[i], pms[i], a.slope);
+            if (i < H) {
+                if constexpr (DROP)
+                    s_val[wave][lane * H + i] = edge_dropout_apply(gat_weight(pel[i], per[i], pms[i], a.slope),
+                                                                   edge_dropout_head(pent, seed1, (uint32_t)i), drop.threshold, drop.scale);
+                else
+                    s_val[wave][lane * H + i] = gat_weight(pel[i], per[i], pms[i], a.slope);
+            }
     };
     auto advance = [&](int t0_) {  // after a publish: the registers move on by one tile
         pc = pc2;
@@ -223,10 +243,20 @@ __global__ __launch_bounds__(kThreads) void gat_aggregate_kernel(GatAggregateArg
     }
 }
 
+template <int V, int S, int W, int U, bool TRANSPOSED>
+__global__ __launch_bounds__(kThreads) void gat_aggregate_kernel(GatAggregateArgs a) {
+    gat_aggregate_body<V, S, W, U, TRANSPOSED, false>(a, EdgeDropout{});
+}
+
+template <int V, int S, int W, int U, bool TRANSPOSED>
+__global__ __launch_bounds__(kThreads) void gat_aggregate_dropout_kernel(GatAggregateArgs a, EdgeDropout drop) {
+    gat_aggregate_body<V, S, W, U, TRANSPOSED, true>(a, drop);
+}
+
 // ----------------------------------------------------------------------------- launch table (launch_heads of spmm_heads.hip, storage order)
 
 template <int V, int S, int W>
-static hipError_t launch_gat(const GatAggregateArgs& a, int rpw, bool transposed, hipStream_t st) {
+static hipError_t launch_gat(const GatAggregateArgs& a, int rpw, bool transposed, const EdgeDropout* drop, hipStream_t st) {
     constexpr int G = 64 / W;
     constexpr int U = (V * S >= 8) ? 4 : 8;
     GatAggregateArgs args = a;
@@ -244,17 +274,25 @@ static hipError_t launch_gat(const GatAggregateArgs& a, int rpw, bool transposed
     const int64_t nitems = (int64_t)args.nblk * args.ntile;
     if (nitems <= 0) return hipSuccess;
     if (nitems > kMaxGridBlocks) return hipErrorInvalidConfiguration;
+    if (drop) {
+        if (transposed)
+            hipLaunchKernelGGL((gat_aggregate_dropout_kernel<V, S, W, U, true>), dim3((unsigned)nitems), dim3(kThreads), 0, st, args, *drop);
+        else
+            hipLaunchKernelGGL((gat_aggregate_dropout_kernel<V, S, W, U, false>), dim3((unsigned)nitems), dim3(kThreads), 0, st, args, *drop);
+        return hipGetLastError();
+    }
     if (transposed) hipLaunchKernelGGL((gat_aggregate_kernel<V, S, W, U, true>), dim3((unsigned)nitems), dim3(kThreads), 0, st, args);
     else hipLaunchKernelGGL((gat_aggregate_kernel<V, S, W, U, false>), dim3((unsigned)nitems), dim3(kThreads), 0, st, args);
     return hipGetLastError();
 }
 
-hipError_t launch_gat_aggregate(const GatAggregateArgs& a, const Geometry& g, bool transposed, hipStream_t st) {
+hipError_t launch_gat_aggregate(const GatAggregateArgs& a, const Geometry& g, bool transposed, const EdgeDropout* drop, hipStream_t st) {
+    if (drop && !drop->seed) return hipErrorInvalidValue;
     if (a.H < 1 || a.H > kHeadsMax || a.F < 1 || a.N != a.H * a.F || a.F % g.vec != 0) return hipErrorInvalidValue;
     if (!a.rowptr || !a.colind || !a.B || !a.C || !a.el || !a.er || !a.stats) return hipErrorInvalidValue;
     if (!heads_geometry_served(g, false)) return hipErrorInvalidValue;
 #define GESPMM_GAT(V_, S_, W_) \
-    if (g.vec == V_ && g.strips == S_ && g.group == W_) return launch_gat<V_, S_, W_>(a, g.rows_per_wave, transposed, st);
+    if (g.vec == V_ && g.strips == S_ && g.group == W_) return launch_gat<V_, S_, W_>(a, g.rows_per_wave, transposed, drop, st);
     GESPMM_GAT(1, 1, 4)
     GESPMM_GAT(1, 1, 8)
     GESPMM_GAT(1, 1, 16)

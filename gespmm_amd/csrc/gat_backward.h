@@ -41,13 +41,20 @@
 
 namespace gespmm {
 
+struct EdgeDropout;  // edge_dropout.h
+
+// drop != nullptr (gespmm_gat_backward_{el,er}_dropout_f32): g_p is replaced by g'_p = dropout(g_p) — edge_dropout.h's mask of (r, c, h),
+// one rounding fl(g_p s) or +0 — directly after its chain; delta, gs_p and the sums are the statements above on g'_p, w_p the undropped
+// weight. The bits are then those of the composition with launch_edge_dropout between the SDDMM and the softmax's backward.
+//
 // M, K >= 1, H, F >= 1; nnz H, M H, K H, M H F and K H F <= kSddmmMaxNnz (32-bit word positions). r = resolve_edge_softmax(M, nnz, H).
 hipError_t launch_gat_backward_el(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
                                   const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
-                                  int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st);
+                                  int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, const EdgeDropout* drop, hipStream_t st);
 // ... r = resolve_edge_softmax(K, nnz, H).
 hipError_t launch_gat_backward_er(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
                                   const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
-                                  int64_t H, int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st);
+                                  int64_t H, int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, const EdgeDropout* drop,
+                                  hipStream_t st);
 
 }  // namespace gespmm

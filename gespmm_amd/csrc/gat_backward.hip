@@ -19,6 +19,7 @@
 
 #include <math.h>
 
+#include "edge_dropout.h"
 #include "edge_softmax.h"
 #include "gat_aggregate.h"
 #include "spmm_kernels.h"
@@ -38,6 +39,15 @@ __device__ __forceinline__ void load_words(float (&v)[V], const float* __restric
     }
 }
 
+// DROP (gespmm_gat_backward_{el,er}_dropout_f32; edge_dropout.h): the dot becomes g'_p = dropout(g_p) directly after its chain — one
+// rounding fl(g s), or +0 by a select — and every statement after it is unchanged (w_p stays the undropped weight). The entry's (row,
+// column) is (segment, index) in the row pass and (index, segment) in the column pass: the same pair, hence the same decision. The
+// seed's two words are loaded once per wavefront, uniformly; everything of it sits behind `if constexpr`.
+struct DropWords {
+    uint32_t s0, s1, threshold;
+    float scale;
+};
+
 // The operands of a launch. fixed / gathered: [S, H, F] of the segments' side and [*, H, F] of the side ind points into — grad_out and
 // feat in the row pass, feat and grad_out in the column pass. delta: read in the column pass only.
 #define GESPMM_GB_PTRS                                                                                                                \
@@ -48,8 +58,9 @@ __device__ __forceinline__ void load_words(float (&v)[V], const float* __restric
 // One (segment, head) pair per lane group -> (delta, sum of gs): the segment's d entries start at entry lo, lane l of the W takes
 // entries l + t W. All 64 lanes arrive together; d is uniform in the group, d == 0 (then lo == 0) means the group has nothing to do and
 // only keeps the others company. seg is a valid segment for an idle group too. V: words per load of the F-wide rows.
-template <int W, bool LEAKY, bool TRANSPOSED, int V>
-__device__ __forceinline__ float2 backward_pair(GESPMM_GB_PTRS, int seg, int lo, int d, int h, int H, int F, int l, float slope) {
+template <int W, bool LEAKY, bool TRANSPOSED, int V, bool DROP>
+__device__ __forceinline__ float2 backward_pair(GESPMM_GB_PTRS, int seg, int lo, int d, int h, int H, int F, int l, float slope,
+                                                const DropWords& dw) {
     const int dm = wave_max_degree<W>(d);
     if (dm == 0) return make_float2(0.0f, 0.0f);
     const int sw = seg * H + h;  // the pair's word (M H, K H, M H F and K H F <= kSddmmMaxNnz: 32-bit word positions)
@@ -67,14 +78,19 @@ __device__ __forceinline__ float2 backward_pair(GESPMM_GB_PTRS, int seg, int lo,
     // factor and, in the column pass, the delta of the entry's row. An `it` past the longest segment of the wavefront loads nothing.
     auto batch = [&](int k0) {
         int off[IT];
+        uint32_t mb[IT];  // (DROP only) the mask's bits of the entry
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             w[it] = g[it] = dl[it] = 0.0f;
             f[it] = 1.0f;
             off[it] = 0;
+            mb[it] = 0;
             if ((k0 + it) * W < dm) {  // wave-uniform
                 const int p = l + (k0 + it) * W;
-                const int nw = ind[lo + (p < d ? p : 0)] * H + h;
+                const int j = ind[lo + (p < d ? p : 0)];
+                const int nw = j * H + h;
+                if constexpr (DROP)
+                    mb[it] = edge_dropout_bits(dw.s0, dw.s1, (uint32_t)(TRANSPOSED ? j : seg), (uint32_t)(TRANSPOSED ? seg : j), (uint32_t)h);
                 off[it] = nw * F;
                 float x;
                 if constexpr (TRANSPOSED) {
@@ -102,6 +118,10 @@ __device__ __forceinline__ float2 backward_pair(GESPMM_GB_PTRS, int seg, int lo,
 #pragma unroll
                     for (int i = 0; i < V; ++i) g[it] = fmaf(a[i], b[i], g[it]);
                 }
+        }
+        if constexpr (DROP) {
+#pragma unroll
+            for (int it = 0; it < IT; ++it) g[it] = edge_dropout_apply(g[it], mb[it], dw.threshold, dw.scale);
         }
     };
     const int nt = (dm + W - 1) / W;  // wave-uniform
@@ -148,18 +168,21 @@ __device__ __forceinline__ float2 backward_pair(GESPMM_GB_PTRS, int seg, int lo,
     return make_float2(dot, rs);
 }
 
-template <int W, bool LEAKY, bool TRANSPOSED>
-__device__ __forceinline__ float2 pair(GESPMM_GB_PTRS, int seg, int lo, int d, int h, int H, int F, int l, float slope, bool vec4) {
-    if (vec4) return backward_pair<W, LEAKY, TRANSPOSED, 4>(GESPMM_GB_ARGS, seg, lo, d, h, H, F, l, slope);  // wave-uniform
-    return backward_pair<W, LEAKY, TRANSPOSED, 1>(GESPMM_GB_ARGS, seg, lo, d, h, H, F, l, slope);
+template <int W, bool LEAKY, bool TRANSPOSED, bool DROP>
+__device__ __forceinline__ float2 pair(GESPMM_GB_PTRS, int seg, int lo, int d, int h, int H, int F, int l, float slope, bool vec4,
+                                       const DropWords& dw) {
+    if (vec4) return backward_pair<W, LEAKY, TRANSPOSED, 4, DROP>(GESPMM_GB_ARGS, seg, lo, d, h, H, F, l, slope, dw);  // wave-uniform
+    return backward_pair<W, LEAKY, TRANSPOSED, 1, DROP>(GESPMM_GB_ARGS, seg, lo, d, h, H, F, l, slope, dw);
 }
 
 // out_delta: [S, H] in the row pass (null in the column pass); out_grad: grad_el [M, H] or grad_er [K, H]. Every word written.
-template <int W, bool LEAKY, bool TRANSPOSED>
-__global__ __launch_bounds__(kThreads) void gat_backward_kernel(const int32_t* __restrict__ ptr, GESPMM_GB_PTRS, float* __restrict__ out_delta,
-                                                                 float* __restrict__ out_grad, int S, int H, int F, int rpw, int L,
-                                                                 float slope, int vec) {
+template <int W, bool LEAKY, bool TRANSPOSED, bool DROP>
+__device__ __forceinline__ void gat_backward_body(const int32_t* __restrict__ ptr, GESPMM_GB_PTRS, float* __restrict__ out_delta,
+                                                  float* __restrict__ out_grad, int S, int H, int F, int rpw, int L, float slope, int vec,
+                                                  const EdgeDropout& drop) {
     constexpr int G = 64 / W;
+    DropWords dw = {0u, 0u, 0u, 1.0f};
+    if constexpr (DROP) dw = {drop.seed[0], drop.seed[1], drop.threshold, drop.scale};  // wave-uniform loads
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int g = lane / W;
@@ -186,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void gat_backward_kernel(const int32_t* _
             d = 0;
             lo = 0;
         }
-        const float2 r = pair<W, LEAKY, TRANSPOSED>(GESPMM_GB_ARGS, s0 + si, lo, d, h, H, F, l, slope, vec4);
+        const float2 r = pair<W, LEAKY, TRANSPOSED, DROP>(GESPMM_GB_ARGS, s0 + si, lo, d, h, H, F, l, slope, vec4, dw);
         if (mine && l == 0) {
             if constexpr (!TRANSPOSED) out_delta[(s0 + si) * H + h] = r.x;
             out_grad[(s0 + si) * H + h] = r.y;
@@ -199,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void gat_backward_kernel(const int32_t* _
             const int d = __builtin_amdgcn_readlane(sp, i + 1) - lo;
             if (d > L)
                 for (int h = 0; h < H; ++h) {
-                    const float2 r = pair<64, LEAKY, TRANSPOSED>(GESPMM_GB_ARGS, s0 + i, lo, d, h, H, F, lane, slope, vec4);
+                    const float2 r = pair<64, LEAKY, TRANSPOSED, DROP>(GESPMM_GB_ARGS, s0 + i, lo, d, h, H, F, lane, slope, vec4, dw);
                     if (lane == 0) {
                         if constexpr (!TRANSPOSED) out_delta[(s0 + i) * H + h] = r.x;
                         out_grad[(s0 + i) * H + h] = r.y;
@@ -209,15 +232,35 @@ __global__ __launch_bounds__(kThreads) void gat_backward_kernel(const int32_t* _
     }
 }
 
+template <int W, bool LEAKY, bool TRANSPOSED>
+__global__ __launch_bounds__(kThreads) void gat_backward_kernel(const int32_t* __restrict__ ptr, GESPMM_GB_PTRS, float* __restrict__ out_delta,
+                                                                 float* __restrict__ out_grad, int S, int H, int F, int rpw, int L,
+                                                                 float slope, int vec) {
+    gat_backward_body<W, LEAKY, TRANSPOSED, false>(ptr, GESPMM_GB_ARGS, out_delta, out_grad, S, H, F, rpw, L, slope, vec, EdgeDropout{});
+}
+
+template <int W, bool LEAKY, bool TRANSPOSED>
+__global__ __launch_bounds__(kThreads) void gat_backward_dropout_kernel(const int32_t* __restrict__ ptr, GESPMM_GB_PTRS,
+                                                                         float* __restrict__ out_delta, float* __restrict__ out_grad, int S,
+                                                                         int H, int F, int rpw, int L, float slope, int vec, EdgeDropout drop) {
+    gat_backward_body<W, LEAKY, TRANSPOSED, true>(ptr, GESPMM_GB_ARGS, out_delta, out_grad, S, H, F, rpw, L, slope, vec, drop);
+}
+
 template <bool LEAKY, bool TRANSPOSED>
 hipError_t launch_w(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const float* delta,
                     const float* fixed, const float* gathered, float* out_delta, float* out_grad, int S, int H, int F, float slope,
-                    const EdgeSoftmaxLaunch& r, hipStream_t st) {
+                    const EdgeSoftmaxLaunch& r, const EdgeDropout* drop, hipStream_t st) {
     const int nblk = (int)(((int64_t)S + kWaves * r.rpw - 1) / (kWaves * r.rpw));
     const bool aligned = (reinterpret_cast<uintptr_t>(fixed) | reinterpret_cast<uintptr_t>(gathered)) % 16 == 0;
     const int vec = (F % 4 == 0 && aligned) ? 4 : 1;
 #define GESPMM_GB(WW)                                                                                                                   \
     case WW:                                                                                                                            \
+        if (drop) {                                                                                                                     \
+            hipLaunchKernelGGL((gat_backward_dropout_kernel<WW, LEAKY, TRANSPOSED>), dim3(nblk), dim3(kThreads), 0, st, ptr, ind, el, er, \
+                               reinterpret_cast<const float2*>(stats), delta, fixed, gathered, out_delta, out_grad, S, H, F, r.rpw,    \
+                               r.L, slope, vec, *drop);                                                                                 \
+            return hipGetLastError();                                                                                                   \
+        }                                                                                                                               \
         hipLaunchKernelGGL((gat_backward_kernel<WW, LEAKY, TRANSPOSED>), dim3(nblk), dim3(kThreads), 0, st, ptr, ind, el, er,           \
                            reinterpret_cast<const float2*>(stats), delta, fixed, gathered, out_delta, out_grad, S, H, F, r.rpw, r.L,   \
                            slope, vec);                                                                                                 \
@@ -244,29 +287,30 @@ bool launchable(int64_t S, int64_t M, int64_t K, int64_t H, int64_t F, int64_t n
 
 hipError_t launch_gat_backward_el(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
                                   const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
-                                  int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st) {
+                                  int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, const EdgeDropout* drop, hipStream_t st) {
     if (M == 0) return hipSuccess;
     if (!dense_words_fit(M, H, 1)) return hipErrorInvalidValue;
     if (nnz == 0) {
         const hipError_t rc = hipMemsetAsync(delta, 0, (size_t)M * (size_t)H * sizeof(float), st);
         return rc != hipSuccess ? rc : hipMemsetAsync(grad_el, 0, (size_t)M * (size_t)H * sizeof(float), st);
     }
-    if (!launchable(M, M, K, H, F, nnz, r)) return hipErrorInvalidValue;
+    if (!launchable(M, M, K, H, F, nnz, r) || (drop && !drop->seed)) return hipErrorInvalidValue;
     if (slope != 1.0f)
-        return launch_w<true, false>(rowptr, colind, el, er, stats, nullptr, grad_out, feat, delta, grad_el, (int)M, (int)H, (int)F, slope, r, st);
-    return launch_w<false, false>(rowptr, colind, el, er, stats, nullptr, grad_out, feat, delta, grad_el, (int)M, (int)H, (int)F, slope, r, st);
+        return launch_w<true, false>(rowptr, colind, el, er, stats, nullptr, grad_out, feat, delta, grad_el, (int)M, (int)H, (int)F, slope, r, drop, st);
+    return launch_w<false, false>(rowptr, colind, el, er, stats, nullptr, grad_out, feat, delta, grad_el, (int)M, (int)H, (int)F, slope, r, drop, st);
 }
 
 hipError_t launch_gat_backward_er(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
                                   const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
-                                  int64_t H, int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, hipStream_t st) {
+                                  int64_t H, int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, const EdgeDropout* drop,
+                                  hipStream_t st) {
     if (K == 0) return hipSuccess;
     if (!dense_words_fit(K, H, 1)) return hipErrorInvalidValue;
     if (nnz == 0) return hipMemsetAsync(grad_er, 0, (size_t)K * (size_t)H * sizeof(float), st);
-    if (!launchable(K, M, K, H, F, nnz, r)) return hipErrorInvalidValue;
+    if (!launchable(K, M, K, H, F, nnz, r) || (drop && !drop->seed)) return hipErrorInvalidValue;
     if (slope != 1.0f)
-        return launch_w<true, true>(colptr, rowind, el, er, stats, delta, feat, grad_out, nullptr, grad_er, (int)K, (int)H, (int)F, slope, r, st);
-    return launch_w<false, true>(colptr, rowind, el, er, stats, delta, feat, grad_out, nullptr, grad_er, (int)K, (int)H, (int)F, slope, r, st);
+        return launch_w<true, true>(colptr, rowind, el, er, stats, delta, feat, grad_out, nullptr, grad_er, (int)K, (int)H, (int)F, slope, r, drop, st);
+    return launch_w<false, true>(colptr, rowind, el, er, stats, delta, feat, grad_out, nullptr, grad_er, (int)K, (int)H, (int)F, slope, r, drop, st);
 }
 
 }  // namespace gespmm

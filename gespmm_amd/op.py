@@ -45,6 +45,7 @@ instead of one ``sddmm.csr_sddmm`` per head on copies (the default, kept as it w
 ``EdgeSoftmaxFunction`` is the step between the two — softmax over the entries of each row, per head, with the leaky ReLU of a GAT
 fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` the graph attention layer composed from the three.
 ``GATSoftmaxFunction`` is the first two in one: the softmax of el[row] + er[col] with no score array (``GATConv(fused_score=True)``).
+``EdgeDropoutFunction`` is dropout on alpha with a mask recomputed from (seed, row, column, head), never stored (``GATConv(dropout=p)``).
 ``GATAggregateFunction`` is all three in one: no score and no attention array, nothing of size nnz x H saved (``GATConv(fused_aggregate=True)``).
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
@@ -257,6 +258,34 @@ class EdgeSoftmaxFunction(torch.autograd.Function):
         return None, grad_score, None
 
 
+class EdgeDropoutFunction(torch.autograd.Function):
+    """y[e, h] = keep(row(e), col(e), h) ? x[e, h] / (1 - p) : 0 — dropout on the attention coefficients of a CSR pattern with a mask
+    that is a pure function of ``(seed, row, column, head)`` and is never stored (``softmax.edge_dropout``).
+
+        EdgeDropoutFunction.apply(rowptr, colind, x, p, seed) -> f32, the shape of x
+
+    ``x`` f32[nnz] or f32[nnz, H] in CSR edge order; ``p`` a Python number in [0, 1); ``seed`` an int32[2] device tensor. The op is
+    its own adjoint: the backward is the same call on the gradient with the same seed, so the two seed words are all it saves —
+    nothing edge-sized. The seed is read when the backward runs: do not overwrite it between a forward and its backward. Two entries
+    with the same (row, column) share their decision."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, x, p, seed):
+        y = _softmax.edge_dropout(rowptr, colind, x.contiguous(), p, seed)
+        ctx.graph, ctx.p = (rowptr, colind), float(p)
+        ctx.save_for_backward(seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        rowptr, colind = ctx.graph
+        (seed,) = ctx.saved_tensors
+        grad_x = None
+        if ctx.needs_input_grad[2]:
+            grad_x = _softmax.edge_dropout(rowptr, colind, grad_y.contiguous(), ctx.p, seed)
+        return None, None, grad_x, None, None
+
+
 class GATSoftmaxFunction(torch.autograd.Function):
     """alpha[e, h] = softmax over the entries e of each CSR row of leaky_relu(el[row(e), h] + er[col(e), h], negative_slope) — the
     attention weights of a graph attention layer straight from the two per-node terms (``softmax.gat_edge_softmax``): no score array is
@@ -307,7 +336,7 @@ class GATAggregateFunction(torch.autograd.Function):
     from el, er and two words per (row, head).
 
         GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None,
-                                   fused_backward=False) -> f32[M, H, F]
+                                   fused_backward=False, dropout_p=0.0, seed=None) -> f32[M, H, F]
 
     ``el`` f32[M, H], ``er`` f32[K, H], ``feat`` f32[K, H, F]; ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K,
     return_order=True)``. The output has the bits of ``MultiHeadSPMMFunction`` on ``GATSoftmaxFunction``'s alpha. Saved: ``el``,
@@ -321,37 +350,56 @@ class GATAggregateFunction(torch.autograd.Function):
     ``fused_backward=True``: grad_el / grad_er are ``softmax.gat_backward_el`` and ``softmax.gat_backward_er`` — two launches that
     recompute weight, dot product and softmax backward per entry from node-sized words; the backward allocates nothing of size
     nnz H either (``csc_order`` is not looked at). The second launch is made only when ``er`` requires grad. grad_feat is the same
-    launch; grad_el / grad_er differ from the default's by the rounding of the dot product's summation order."""
+    launch; grad_el / grad_er differ from the default's by the rounding of the dot product's summation order.
+
+    ``dropout_p > 0`` with ``seed`` (int32[2] on the device): dropout on alpha, as ``EdgeDropoutFunction`` between the two functions
+    above would apply it, with the mask recomputed wherever an entry is seen — in the aggregation, in its transposed form for
+    grad_feat and in both backward passes (``dropout=(p, seed)`` of those calls; the default backward applies ``softmax.edge_dropout``
+    to its transient grad_alpha). The two seed words are the only thing saved on top; with ``dropout_p == 0`` the launches are exactly
+    those above."""
 
     @staticmethod
-    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None, fused_backward=False):
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None, fused_backward=False, dropout_p=0.0,
+                seed=None):
         el_c, er_c, feat_c = el.contiguous(), er.contiguous(), feat.contiguous()
+        dropout_p = float(dropout_p)
+        if dropout_p != 0.0 and seed is None:
+            raise ValueError("dropout_p needs a seed (an int32[2] device tensor)")
+        ctx.dropout_p = dropout_p
+        drop = (dropout_p, seed) if dropout_p != 0.0 else None
         stats = _softmax.gat_softmax_stats(rowptr, colind, el_c, er_c, negative_slope=negative_slope)
-        out = _spmm.gat_aggregate(rowptr, colind, el_c, er_c, stats, feat_c, negative_slope=negative_slope)
+        out = _spmm.gat_aggregate(rowptr, colind, el_c, er_c, stats, feat_c, negative_slope=negative_slope, dropout=drop)
         order = None
         if not fused_backward:
             order = (csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)).contiguous()
         ctx.graph = (rowptr, colind, colptr, rowind, order)
         ctx.negative_slope, ctx.fused_backward = negative_slope, bool(fused_backward)
-        ctx.save_for_backward(el_c, er_c, feat_c, stats)
+        if drop is None:
+            ctx.save_for_backward(el_c, er_c, feat_c, stats)
+        else:
+            ctx.save_for_backward(el_c, er_c, feat_c, stats, seed)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         rowptr, colind, colptr, rowind, order = ctx.graph
-        el, er, feat, stats = ctx.saved_tensors
+        el, er, feat, stats = ctx.saved_tensors[:4]
+        drop = (ctx.dropout_p, ctx.saved_tensors[4]) if ctx.dropout_p != 0.0 else None
         slope = ctx.negative_slope
         grad_out = grad_out.contiguous()
         grad_el = grad_er = grad_feat = None
         if ctx.fused_backward and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):  # node-sized tensors only
-            delta, grad_el = _softmax.gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=slope)
+            delta, grad_el = _softmax.gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=slope, dropout=drop)
             if ctx.needs_input_grad[6]:
-                grad_er = _softmax.gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=slope)
+                grad_er = _softmax.gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=slope,
+                                                   dropout=drop)
             if not ctx.needs_input_grad[5]:
                 grad_el = None
         elif ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:  # (first: its three edge-sized temporaries are gone before grad_feat exists)
             alpha = _softmax.gat_edge_softmax(rowptr, colind, el, er, negative_slope=slope)
             grad_alpha = _sddmm.csr_sddmm_heads(rowptr, colind, grad_out, feat)
+            if drop is not None:  # the gradient of the undropped alpha, in place
+                _softmax.edge_dropout(rowptr, colind, grad_alpha, drop[0], drop[1], out=grad_alpha)
             grad_score, grad_el = _softmax.gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=el if slope is not None else None,
                                                                      er=er if slope is not None else None, negative_slope=slope)
             del alpha, grad_alpha
@@ -361,8 +409,8 @@ class GATAggregateFunction(torch.autograd.Function):
             if not ctx.needs_input_grad[5]:
                 grad_el = None
         if ctx.needs_input_grad[7]:
-            grad_feat = _spmm.gat_aggregate(colptr, rowind, el, er, stats, grad_out, negative_slope=slope, transposed=True)
-        return None, None, None, None, None, grad_el, grad_er, grad_feat, None, None
+            grad_feat = _spmm.gat_aggregate(colptr, rowind, el, er, stats, grad_out, negative_slope=slope, transposed=True, dropout=drop)
+        return None, None, None, None, None, grad_el, grad_er, grad_feat, None, None, None, None
 
 
 def glorot(tensor):
@@ -486,8 +534,8 @@ class GATConv(torch.nn.Module):
     and its backward hands grad_el and grad_er back as component 0 of grad_q and component 1 of grad_k.
 
         GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
-                fused_aggregate=False, fused_backward=False)
-        forward(x, rowptr, colind, colptr, rowind, csc_order)
+                fused_aggregate=False, fused_backward=False, dropout=0.0)
+        forward(x, rowptr, colind, colptr, rowind, csc_order, attn_seed=None)
 
     ``fused_score=True``: the score and the softmax are ONE ``GATSoftmaxFunction`` — el + er is added inside the softmax kernel, no
     score, q or k tensor exists, and the backward sums grad_score over rows and columns in two launches. Same output bits. Pass an
@@ -502,12 +550,23 @@ class GATConv(torch.nn.Module):
     ``att_dst`` / ``att_src`` come from ``softmax.gat_backward_el`` / ``gat_backward_er``, so a layer allocates no ``[nnz, H]`` array
     forward or backward. Same output bits; the two gradients agree to rounding. Off by default.
 
+    ``dropout=p`` (0 <= p < 1): dropout on the attention coefficients, as in the paper (p = 0.6 on the citation graphs), in training
+    mode and in all four paths — ``EdgeDropoutFunction`` on alpha where alpha exists, ``dropout=`` of the fused calls where it does
+    not. The mask is a pure function of ``(seed, row, column, head)`` and is never stored, so the fused paths still allocate nothing of
+    size ``[nnz, H]``. Each training forward draws the two seed words from torch's device generator (``torch.manual_seed`` fixes the
+    mask; a draw inside a captured region is fresh at every replay) unless ``attn_seed``, an int32[2] device tensor, is given. Outputs
+    of the four paths are bit-equal under one seed. Two entries with the same (row, column) — a multigraph — share their decision.
+    In ``eval()`` mode or with ``dropout == 0`` the layer makes exactly the launches it makes without the argument.
+
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
     ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
-                 fused_aggregate=False, fused_backward=False):
+                 fused_aggregate=False, fused_backward=False, dropout=0.0):
         super().__init__()
+        self.dropout = float(dropout)
+        if not (0.0 <= self.dropout < 1.0):
+            raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
         self.fused_backward = bool(fused_backward)
         self.fused_aggregate = bool(fused_aggregate) or self.fused_backward
         self.fused_score = bool(fused_score) or self.fused_aggregate
@@ -529,16 +588,26 @@ class GATConv(torch.nn.Module):
         glorot(self.att_src)
         zeros(self.bias)
 
-    def forward(self, x, rowptr, colind, colptr, rowind, csc_order):
+    def forward(self, x, rowptr, colind, colptr, rowind, csc_order, attn_seed=None):
         n, H, F = x.shape[0], self.heads, self.out_channels
+        p, seed = 0.0, None
+        if self.training and self.dropout > 0.0:
+            p = self.dropout
+            seed = attn_seed
+            if seed is None:  # two 32-bit words from the device generator: no host synchronisation
+                seed = torch.randint(-(2 ** 31), 2 ** 31, (2,), dtype=torch.int32, device=x.device)
         if rowptr.numel() != n + 1 or colptr.numel() != n + 1:
             raise ValueError("GATConv needs a square graph: rowptr and colptr must have x.size(0) + 1 entries")
         xw = (x @ self.weight).view(n, H, F)
         el = (xw * self.att_dst).sum(-1)
         er = (xw * self.att_src).sum(-1)
         if self.fused_aggregate:
-            out = GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, xw, self.negative_slope,
-                                             self.fused_backward)
+            if seed is None:
+                out = GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, xw, self.negative_slope,
+                                                 self.fused_backward)
+            else:
+                out = GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, xw, self.negative_slope,
+                                                 self.fused_backward, p, seed)
             out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
             return out if self.bias is None else out + self.bias
         if self.fused_score:
@@ -548,6 +617,8 @@ class GATConv(torch.nn.Module):
             k = torch.stack((torch.ones_like(er), er), dim=-1)
             score = MultiHeadSDDMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, q, k)
             alpha = EdgeSoftmaxFunction.apply(rowptr, score, self.negative_slope)
+        if seed is not None:
+            alpha = EdgeDropoutFunction.apply(rowptr, colind, alpha, p, seed)
         out = MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, xw, alpha, None, True)
         out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
         return out if self.bias is None else out + self.bias

@@ -7,8 +7,9 @@ gespmm_edge_softmax_backward_f32 — the reference has no counterpart).
     gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=None, er=None, negative_slope=None) -> (grad_score, grad_el)
     edge_segment_sum(ptr, x, order=None, out=None)                                                -> f32[S, H] (or f32[S])
     gat_softmax_stats(rowptr, colind, el, er, negative_slope=None, out=None)                      -> f32[M, H, 2]
-    gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None) -> (delta f32[M, H], grad_el f32[M, H])
-    gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None) -> grad_er f32[K, H]
+    gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None, dropout=None) -> (delta f32[M, H], grad_el f32[M, H])
+    gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None, dropout=None) -> grad_er f32[K, H]
+    edge_dropout(rowptr, colind, x, p, seed, out=None)                                            -> f32[nnz, H] (or f32[nnz])
 
 ``score`` is f32[nnz] or f32[nnz, H] in CSR edge order — what ``sddmm.csr_sddmm`` / ``sddmm.csr_sddmm_heads`` return and what
 ``spmm.csr_spmm`` / ``spmm.csr_spmm_heads`` take as edge weights. For row r with entries [lo, hi) and head h
@@ -31,11 +32,84 @@ permuted copy. The sums have a pinned order (include/gespmm.h), the one ``edge_s
 ``gat_backward_el`` / ``gat_backward_er`` are that aggregation's backward for ``el`` and ``er``: two launches that compute the weight,
 the dot product ``<grad_out[row], feat[col]>`` and the softmax's backward per entry from node-sized words, over the rows and over the
 columns, and sum them in the pinned order — no ``[nnz, H]`` array there either.
+``edge_dropout`` is dropout on the attention coefficients with a mask that is never stored: whether entry (row, column) keeps head h is
+a pure function of ``(seed, row, column, h)`` (``restate_edge_dropout_bits``; include/gespmm.h), so the fused aggregation and both
+passes of the fused backward recompute it (``dropout=(p, seed)``) and nothing edge-sized is saved for it. ``seed`` is an int32[2]
+DEVICE tensor: no host synchronisation, and a seed drawn or overwritten on the device between two replays of a captured graph
+changes the mask. Two entries with the same (row, column) — a multigraph — share their decision.
 All calls go through ctypes."""
 import torch
 
 from ._lib import check, lib
 from .spmm import _on_device, _ptr, _stream
+
+
+def _dropout_typed(dropout):
+    """TypeError for what is no pair (p, seed) with an int32 seed tensor (``None`` passes: no dropout)."""
+    if dropout is None:
+        return
+    if not isinstance(dropout, (tuple, list)) or len(dropout) != 2:
+        raise TypeError("dropout must be a pair (p, seed)")
+    p, seed = dropout
+    if not isinstance(seed, torch.Tensor):
+        raise TypeError("seed must be a torch.Tensor")
+    if seed.dtype != torch.int32:
+        raise TypeError("seed must have dtype torch.int32, got %s" % seed.dtype)
+    if isinstance(p, torch.Tensor) or not isinstance(p, (int, float)):
+        raise TypeError("the dropout probability must be a Python number (the seed, not p, is what lives on the device)")
+
+
+def _dropout(dropout, dev):
+    """``(p, seed)`` -> (float p in [0, 1), the int32[2] seed tensor on ``dev``)."""
+    _dropout_typed(dropout)
+    p, seed = dropout
+    p = float(p)
+    if not (0.0 <= p < 1.0):  # (NaN included)
+        raise ValueError("the dropout probability must be in [0, 1), got %r" % (p,))
+    if tuple(seed.shape) != (2,) or not seed.is_contiguous():
+        raise ValueError("seed must be a contiguous int32[2] tensor")
+    if seed.device != dev:
+        raise ValueError("seed must live on %s, as the other operands" % (dev,))
+    return p, seed
+
+
+def restate_edge_dropout_bits(s0, s1, r, c, h):
+    """The mask's bits in numpy (uint32 arrays or scalars, broadcast) — the restatement the tests hold the kernels and
+    ``gespmm_edge_dropout_bits`` to. An entry keeps its value when ``bits >= _lib.edge_dropout_threshold(p)``."""
+    import numpy as np
+
+    def mix(x):
+        x = x ^ (x >> np.uint32(16))
+        x = x * np.uint32(0x7FEB352D)
+        x = x ^ (x >> np.uint32(15))
+        x = x * np.uint32(0x846CA68B)
+        return x ^ (x >> np.uint32(16))
+
+    with np.errstate(over="ignore"):
+        s0, s1, r, c, h = (np.asarray(v).astype(np.uint32) for v in (s0, s1, r, c, h))
+        return mix(mix(mix(r ^ s0) ^ c) ^ (h * np.uint32(0x9E3779B9)) ^ s1)
+
+
+def edge_dropout(rowptr, colind, x, p, seed, out=None):
+    """``out[e, h] = keep(row(e), colind[e], h) ? x[e, h] / (1 - p) : +0`` on an edge array of the CSR pattern (gespmm_edge_dropout_f32):
+    one launch, no workspace, capturable. ``x`` f32[nnz] or f32[nnz, H]; ``seed`` int32[2] on the device; ``out`` may be ``x``. The
+    drop is a select — a dropped NaN or inf becomes +0 — and ``p == 0`` returns the bits of ``x``. The op is its own adjoint: the
+    backward is the same call on the gradient."""
+    _typed(torch.int32, rowptr=rowptr, colind=colind)
+    _typed(torch.float32, x=x)
+    _dropout_typed((p, seed))
+    dev, M, H, nnz = _checked(rowptr, x, "x")
+    _index_vector(colind, "colind", dev, nnz)
+    p, seed = _dropout((p, seed), dev)
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _edge_array(out, "out", like=x)
+    with _on_device(dev):
+        # (K: the entry point checks it for sense only; no kernel addresses by it)
+        rc = lib.gespmm_edge_dropout_f32(_ptr(rowptr), _ptr(colind), _ptr(x), _ptr(out), M, 1, H, nnz, p, _ptr(seed), _stream(dev))
+    check(rc, "gespmm_edge_dropout_f32")
+    return out
 
 
 def _slope(negative_slope):
@@ -317,15 +391,18 @@ def _typed(dtype, **operands):
             raise TypeError("%s must have dtype %s, got %s" % (name, dtype, t.dtype))
 
 
-def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None):
+def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None, dropout=None):
     """Backward of ``spmm.gat_aggregate`` for ``el`` with no edge array (gespmm_gat_backward_el_f32) -> ``(delta, grad_el)``, both
     f32[M, H]: per entry the weight (``stats = gat_softmax_stats(..)``: the bits of alpha), ``g = <grad_out[row], feat[col]>`` (one
     fmaf chain over ascending f) and ``gs = w (g - delta) * leaky'``, with ``delta = sum_row(w g)`` and ``grad_el = sum_row(gs)`` in
     the pinned order of ``gat_edge_softmax_backward``. ``grad_out`` f32[M, H, F], ``feat`` f32[K, H, F]. ``delta`` is what
-    ``gat_backward_er`` needs. ``out``: a pair of tensors ``(delta, grad_el)`` to write into; every word is written, empty rows +0."""
+    ``gat_backward_er`` needs. ``out``: a pair of tensors ``(delta, grad_el)`` to write into; every word is written, empty rows +0.
+    ``dropout=(p, seed)``: the backward of ``spmm.gat_aggregate(.., dropout=(p, seed))`` (gespmm_gat_backward_el_dropout_f32): ``g``
+    becomes ``edge_dropout``'s value of it, recomputed from the seed; ``w`` stays the undropped weight."""
     slope = _slope(negative_slope)
     _typed(torch.int32, rowptr=rowptr, colind=colind)
     _typed(torch.float32, el=el, er=er, stats=stats, grad_out=grad_out, feat=feat)
+    _dropout_typed(dropout)
     dev, M, K, H, nnz = _gat_terms(rowptr, colind, el, er)
     _stats_array(stats, "stats", M, H, dev)
     F = _head_rows(grad_out, "grad_out", M, H, dev)
@@ -339,6 +416,14 @@ def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slop
         delta, grad_el = out
         _node_result(delta, "out[0]", M, H, dev)
         _node_result(grad_el, "out[1]", M, H, dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+        with _on_device(dev):
+            rc = lib.gespmm_gat_backward_el_dropout_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(stats), _ptr(grad_out),
+                                                        _ptr(feat), _ptr(delta), _ptr(grad_el), M, K, H, F, nnz, slope, p, _ptr(seed),
+                                                        _stream(dev))
+        check(rc, "gespmm_gat_backward_el_dropout_f32")
+        return delta, grad_el
     with _on_device(dev):
         rc = lib.gespmm_gat_backward_el_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(stats), _ptr(grad_out), _ptr(feat),
                                             _ptr(delta), _ptr(grad_el), M, K, H, F, nnz, slope, _stream(dev))
@@ -346,14 +431,16 @@ def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slop
     return delta, grad_el
 
 
-def gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None):
+def gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None, dropout=None):
     """Backward of ``spmm.gat_aggregate`` for ``er`` with no edge array (gespmm_gat_backward_er_f32) -> ``grad_er`` f32[K, H]: the same
     per-entry ``gs`` as ``gat_backward_el``, recomputed with the same bits from ``delta`` (that call's first result), summed over the
     entries of each column in the pinned order of ``edge_segment_sum(colptr, .., order=csc_order)``. ``colptr, rowind`` are the CSC
-    arrays (``graphs.transpose_csr``); no ``csc_order`` is needed. Every word is written, empty columns +0."""
+    arrays (``graphs.transpose_csr``); no ``csc_order`` is needed. Every word is written, empty columns +0. ``dropout=(p, seed)``: as in
+    ``gat_backward_el`` (gespmm_gat_backward_er_dropout_f32) — the walk over the columns recomputes the decisions of the walk over rows."""
     slope = _slope(negative_slope)
     _typed(torch.int32, colptr=colptr, rowind=rowind)
     _typed(torch.float32, el=el, er=er, stats=stats, delta=delta, grad_out=grad_out, feat=feat)
+    _dropout_typed(dropout)
     K = _checked_rowptr(colptr)
     _node_array(er, "er", rows=K)
     _node_array(el, "el", like=er)
@@ -369,6 +456,14 @@ def gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negati
         out = torch.empty(K, H, dtype=torch.float32, device=dev)
     else:
         _node_result(out, "out", K, H, dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+        with _on_device(dev):
+            rc = lib.gespmm_gat_backward_er_dropout_f32(_ptr(colptr), _ptr(rowind), _ptr(el), _ptr(er), _ptr(stats), _ptr(delta),
+                                                        _ptr(grad_out), _ptr(feat), _ptr(out), M, K, H, F, nnz, slope, p, _ptr(seed),
+                                                        _stream(dev))
+        check(rc, "gespmm_gat_backward_er_dropout_f32")
+        return out
     with _on_device(dev):
         rc = lib.gespmm_gat_backward_er_f32(_ptr(colptr), _ptr(rowind), _ptr(el), _ptr(er), _ptr(stats), _ptr(delta), _ptr(grad_out),
                                             _ptr(feat), _ptr(out), M, K, H, F, nnz, slope, _stream(dev))

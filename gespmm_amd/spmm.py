@@ -433,7 +433,7 @@ def _overlaps(a, b):
     return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
-def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transposed=False, out=None):
+def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transposed=False, out=None, dropout=None):
     """GAT aggregation with no attention array (gespmm_gat_aggregate_f32): ``csr_spmm_heads`` with the weight of an entry computed
     inside the kernel, ``exp(leaky_relu(el[r, h] + er[c, h]) - stats[r, h, 0]) / stats[r, h, 1]`` for the entry's row r and column c —
     the bits of ``softmax.gat_edge_softmax`` when ``stats = softmax.gat_softmax_stats(rowptr, colind, el, er, negative_slope)``.
@@ -444,10 +444,16 @@ def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transpose
 
     bit for bit. ``el`` f32[M, H], ``er`` f32[K, H], ``stats`` f32[M, H, 2] are the same tensors in both modes. ``dense`` may be
     rank 2 ([rows, H * F]); the result has its rank. One kernel for H <= 8 (``_lib.gat_aggregate_route``), else the weights go through
-    a pooled temporary. ``out`` must not overlap an input. fp32 only."""
+    a pooled temporary. ``out`` must not overlap an input. fp32 only.
+
+    ``dropout=(p, seed)`` (gespmm_gat_aggregate_dropout_f32): the weight becomes ``softmax.edge_dropout``'s value of it — kept and
+    scaled by 1 / (1 - p), or +0 — recomputed inside the kernel from ``seed`` (int32[2] on the device) and the entry's (row, column,
+    head), which are the same in both modes: the bits of ``csr_spmm_heads`` on ``edge_dropout(gat_edge_softmax(..))``. ``stats`` stay
+    those of the softmax without dropout."""
     from . import softmax as _sm  # (softmax imports this module)
 
     slope = _sm._slope(negative_slope)
+    _sm._dropout_typed(dropout)
     _sm._node_array(el, "el")
     _sm._node_array(er, "er", like=el)
     dev = el.device
@@ -481,6 +487,13 @@ def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transpose
             raise ValueError("out must be contiguous f32%s on %s" % (list(shape), dev))
         if any(_overlaps(out, t) for t in (el, er, stats, dense)):
             raise ValueError("out must not overlap an input")
+    if dropout is not None:
+        p, seed = _sm._dropout(dropout, dev)
+        with _on_device(dev):
+            rc = lib.gespmm_gat_aggregate_dropout_f32(_ptr(ptr), _ptr(ind), _ptr(el), _ptr(er), _ptr(stats), _ptr(dense), _ptr(out), M, K,
+                                                      H, F, ind.numel(), slope, 1 if transposed else 0, p, _ptr(seed), _stream(dev))
+        check(rc, "gespmm_gat_aggregate_dropout_f32")
+        return out
     with _on_device(dev):
         rc = lib.gespmm_gat_aggregate_f32(_ptr(ptr), _ptr(ind), _ptr(el), _ptr(er), _ptr(stats), _ptr(dense), _ptr(out), M, K, H, F,
                                           ind.numel(), slope, 1 if transposed else 0, _stream(dev))

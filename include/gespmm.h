@@ -35,6 +35,8 @@
  *                               multi-head product that computes the attention weights from them: no [nnz x H] array at all
  *   gespmm_gat_backward_el_f32 / gespmm_gat_backward_er_f32 <- (new) the backward of that layer for el and er: two launches on
  *                               node-sized words, no [nnz x H] array either
+ *   gespmm_edge_dropout_f32 / gespmm_gat_aggregate_dropout_f32 / gespmm_gat_backward_{el,er}_dropout_f32 / gespmm_edge_dropout_bits /
+ *                               _threshold <- (new) dropout on the attention coefficients with a mask that is never stored
  *   gespmm_baseline_copy_f32 <- (new) streaming-copy yardstick for the roofline record; no reference counterpart
  *
  * Conventions (all device entry points):
@@ -694,6 +696,56 @@ int gespmm_gat_backward_el_f32(const int32_t* rowptr, const int32_t* colind, con
 int gespmm_gat_backward_er_f32(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
                                const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K, int64_t H,
                                int64_t F, int64_t nnz, float slope, void* stream);
+/*
+ * Dropout on the attention coefficients with a mask that is never stored (new symbols of 0.5). Whether entry (r, c) of the pattern
+ * keeps head h is a pure function of (seed, r, c, h), in uint32 arithmetic:
+ *
+ *     mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *     bits(s0, s1, r, c, h) = mix( mix( mix(r ^ s0) ^ c ) ^ (h * 0x9E3779B9) ^ s1 )
+ *     keep = bits >= T,  T = min(floor((double)p 2^32), 2^32 - 1)         dropout(x) = keep ? x * s : +0,  s = 1.0f / (1.0f - p)
+ *
+ * dropout is a select: a dropped NaN or inf becomes +0. r and c are the row and the column of the entry whichever way the pattern is
+ * walked, so the walk over rows (rowptr, colind) and the walk over columns (colptr, rowind; no CSR position, no csc_order) recompute
+ * the same decision. Two entries with the same (r, c) — a multigraph — therefore share theirs. `seed` is a DEVICE pointer to two
+ * 32-bit words, 4-byte aligned, read by the kernels with ordinary loads and never written: no host synchronisation, and a seed drawn
+ * or overwritten on the device between two replays of a captured graph changes the mask. p == 0 is legal (T = 0, s = 1: the bits of
+ * the base entry point).
+ * Known answers with (s0, s1) = (0x12345678, 0x9abcdef0): bits(0, 0, 0) = 0xffb6cd07, bits(1, 5, 1) = 0xf2651a06,
+ * bits(2, 2, 7) = 0x8cee38f8, bits(511, 300, 3) = 0x75f57072.
+ *
+ * gespmm_edge_dropout_f32: y[p H + h] = dropout(x[p H + h]) for entry p of the CSR pattern, [nnz x H]; y == x is allowed. Forward on
+ * alpha and backward on its gradient: the op is its own adjoint. One grid-stride kernel, no workspace: capturable. Checks: the ladder
+ * of gespmm_gat_softmax_f32 on (M, K, H, nnz), !(0 <= p < 1) (NaN included) -> GESPMM_EINVAL with the other senseless arguments;
+ * nnz == 0 -> 0; NULL (seed included) -> GESPMM_EINVAL; not 4-byte aligned -> GESPMM_EALIGN.
+ *
+ * gespmm_gat_aggregate_dropout_f32: gespmm_gat_aggregate_f32 with the staged weight dropout(w(r, c, h)) — the bits of
+ * gespmm_csr_spmm_heads_f32 on gespmm_edge_dropout_f32(gespmm_gat_softmax_f32(..)), for transposed == 1 on the CSC arrays with that
+ * array permuted. Route 0 applies the same expression to its temporary. stats are those of the softmax WITHOUT dropout: it comes after
+ * the normalisation.
+ *
+ * gespmm_gat_backward_el_dropout_f32 / _er_dropout_f32: the fused backward with g_p replaced by g'_p = dropout(g_p) directly after its
+ * chain (one rounding fl(g_p s), or +0); delta = sum w g', gs_p = w (g'_p - delta) factor with w the UNDROPPED weight. Where the dot's
+ * partial sums are exact, the bits of gespmm_gat_softmax_f32 + gespmm_sddmm_csr_heads_f32 + gespmm_edge_dropout_f32 +
+ * gespmm_gat_softmax_backward_f32 + gespmm_edge_segment_sum_f32.
+ *
+ * The three fused forms follow their base entry's ladder: a bad p joins the step that rejects a bad slope, a NULL seed the NULL step,
+ * a misaligned seed the alignment step; nnz == 0 behaves as in the base entry (the seed is still checked).
+ */
+int gespmm_edge_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* x, float* y, int64_t M, int64_t K, int64_t H,
+                            int64_t nnz, float p, const void* seed, void* stream);
+int gespmm_gat_aggregate_dropout_f32(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats,
+                                     const float* B, float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                     int transposed, float p, const void* seed, void* stream);
+int gespmm_gat_backward_el_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                       const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K,
+                                       int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream);
+int gespmm_gat_backward_er_dropout_f32(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                       const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
+                                       int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream);
+/* Host only: the mask's bits and the threshold T as the kernels compute them. gespmm_edge_dropout_threshold answers 0xffffffff for a p
+ * outside [0, 1), which no legal p gives. */
+uint32_t gespmm_edge_dropout_bits(uint32_t s0, uint32_t s1, uint32_t r, uint32_t c, uint32_t h);
+uint32_t gespmm_edge_dropout_threshold(float p);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
