@@ -12,6 +12,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
     python examples/gat_custom.py --fused-backward --attn-dropout 0.6   # the paper's dropout on the attention coefficients: a mask recomputed
                                                                    # from a seed wherever an entry is seen, never stored
     python examples/gat_custom.py --seed 0 --fused-aggregate       # seeded parameters and dropout: the losses of --seed 0 --fused-score
+    python examples/gat_custom.py --v2                             # two ``GATv2Conv`` layers (Brody et al.): the non-linearity inside the
+                                                                   # score's sum, one kernel, nothing of size nnz x H x F
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
 chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
@@ -30,7 +32,7 @@ import torch.nn.functional as F  # noqa: E402
 
 import gespmm_amd  # noqa: E402,F401
 from gcn_custom import load_edges, proc  # noqa: E402
-from gespmm_amd import GATConv, graphs  # noqa: E402
+from gespmm_amd import GATConv, GATv2Conv, graphs  # noqa: E402
 
 
 def gat_graph(edge_index, n_v, device, int32_order=False):
@@ -46,11 +48,17 @@ def gat_graph(edge_index, n_v, device, int32_order=False):
 
 class Net(torch.nn.Module):
     def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False, fused_aggregate=False, fused_backward=False,
-                 attn_dropout=0.0):
+                 attn_dropout=0.0, v2=False):
         super().__init__()
-        fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward, dropout=attn_dropout)
-        self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, **fused)
-        self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, **fused)
+        if v2:
+            if fused_score or fused_aggregate or fused_backward:
+                raise ValueError("the fused paths are GATConv's: GATv2Conv has none")
+            self.conv1 = GATv2Conv(n_in, n_hidden, heads=heads, concat=True, dropout=attn_dropout)
+            self.conv2 = GATv2Conv(n_hidden * heads, n_out, heads=1, concat=False, dropout=attn_dropout)
+        else:
+            fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward, dropout=attn_dropout)
+            self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, **fused)
+            self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, **fused)
         self.dropout = dropout
 
     def forward(self, x, g):
@@ -77,10 +85,14 @@ def main():
     ap.add_argument("--fused-backward", action="store_true",
                     help="GATConv(fused_backward=True): the fused aggregation, and its backward for the attention terms in two "
                          "launches with no [nnz, H] array")
+    ap.add_argument("--v2", action="store_true",
+                    help="GATv2Conv in both layers (the score's non-linearity inside its sum); not together with the --fused-* flags")
     ap.add_argument("--seed", type=int, default=None,
                     help="torch.manual_seed before the model is made (parameters and dropout masks): two runs, or two fused settings, "
                          "then print the same losses")
     args = ap.parse_args()
+    if args.v2 and (args.fused_score or args.fused_aggregate or args.fused_backward):
+        ap.error("--v2 has no fused path: --fused-score, --fused-aggregate and --fused-backward are GATConv's")
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device (the ops have no CPU path)")
     device = torch.device("cuda")
@@ -102,7 +114,7 @@ def main():
     if args.seed is not None:
         torch.manual_seed(args.seed)
     model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score,
-                fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward, attn_dropout=args.attn_dropout).to(device)
+                fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward, attn_dropout=args.attn_dropout, v2=args.v2).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
     train_idx = masks["train"].nonzero().squeeze(1)
     y_train = y[train_idx]
@@ -163,7 +175,7 @@ def main():
     wall = time.perf_counter() - t0
     print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s fused_backward=%s%s" %
           (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score, args.fused_aggregate,
-           args.fused_backward, " attn_dropout=%g" % args.attn_dropout if args.attn_dropout else ""))
+           args.fused_backward, (" attn_dropout=%g" % args.attn_dropout if args.attn_dropout else "") + (" v2=True" if args.v2 else "")))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
 

@@ -123,6 +123,9 @@ EXPORTS = [
     "gespmm_gat_backward_er_dropout_f32",
     "gespmm_edge_dropout_bits",
     "gespmm_edge_dropout_threshold",
+    "gespmm_gatv2_score_f32",
+    "gespmm_gatv2_score_backward_f32",
+    "gespmm_describe_gatv2_score",
 ]
 
 X16_F16 = 1
@@ -330,6 +333,12 @@ def _load():
     lib.gespmm_edge_dropout_bits.argtypes = [ctypes.c_uint32] * 5
     lib.gespmm_edge_dropout_threshold.restype = ctypes.c_uint32
     lib.gespmm_edge_dropout_threshold.argtypes = [c_float]
+    lib.gespmm_gatv2_score_f32.restype = c_int
+    lib.gespmm_gatv2_score_f32.argtypes = [p] * 6 + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_score_backward_f32.restype = c_int
+    lib.gespmm_gatv2_score_backward_f32.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_describe_gatv2_score.restype = c_int
+    lib.gespmm_describe_gatv2_score.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_gat_aggregate_route.restype = c_int
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
@@ -431,6 +440,19 @@ def describe_edge_softmax(M, nnz, H):
         return {"form": "none"}
     w, long_rows = text.split()
     return {"W": int(w.split("=")[1]), "L": int(long_rows.split(">")[1])}
+
+
+def describe_gatv2_score(M, nnz, H, F, xl_align=16, xr_align=16, att_align=16):
+    """What gespmm_gatv2_score_f32 would launch for these sizes and operand alignments (gespmm_describe_gatv2_score: host only) — a
+    dict ``{"V": floats per load, "W": lanes per (entry, head) pair, "epw": ENTRIES per wavefront}``; ``{"route": "zeros"}`` when
+    F == 0 and ``{"form": "none"}`` when nnz == 0. V and W fix the summation order; V divides F and 4 V bytes divide all three
+    operand addresses."""
+    buf = ctypes.create_string_buffer(96)
+    n = lib.gespmm_describe_gatv2_score(int(M), int(nnz), int(H), int(F), int(xl_align), int(xr_align), int(att_align), buf, 96)
+    if n < 0:
+        raise GespmmError(n, "gespmm_describe_gatv2_score")
+    out = dict(kv.split("=") for kv in buf.value.decode().split())
+    return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
 
 
 def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):

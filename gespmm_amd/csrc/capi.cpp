@@ -26,6 +26,7 @@
 #include "edge_softmax.h"
 #include "gat_aggregate.h"
 #include "gat_backward.h"
+#include "gatv2_score.h"
 #include "plan.h"
 #include "sddmm_heads.h"
 #include "spmm_heads.h"
@@ -456,6 +457,20 @@ int run_sddmm_heads(const int32_t* rows, bool csr, const int32_t* colind, const 
         if (rc == 0) rc = (int)launch_heads_unslice(th, out, nnz, H, h, 1, st);
     }
     return scratch.close(rc);
+}
+
+// ---- the GATv2 score (gespmm.h: gespmm_gatv2_score_f32 / _backward_f32; gatv2_score.h). S segments of x_seg, T rows of x_ind (forward:
+// M and K). Sizes alone: what makes no sense, then what is too large for 32-bit word positions (there is no other route).
+int check_gatv2_sizes(int64_t S, int64_t T, int64_t H, int64_t F, int64_t nnz, float slope) {
+    const int rc = check_edge_softmax_sizes(S, H, nnz, slope);
+    if (rc == GESPMM_EINVAL || T < 0 || F < 0 || (nnz > 0 && T < 1)) return GESPMM_EINVAL;
+    if (rc != 0) return rc;
+    if (S > kSddmmMaxNnz || T > kSddmmMaxNnz) return GESPMM_ERANGE;
+    if (const int rcs = check_dense_words(S, H)) return rcs;
+    if (const int rct = check_dense_words(T, H)) return rct;
+    if (F == 0) return 0;
+    if (const int rcs = check_dense_words(S * H, F)) return rcs;  // (S H <= kSddmmMaxNnz: no overflow)
+    return check_dense_words(T * H, F);
 }
 
 }  // namespace gespmm
@@ -1144,6 +1159,68 @@ int gespmm_describe_edge_softmax(int64_t M, int64_t nnz, int64_t H, char* out, i
     } else {
         const gespmm::EdgeSoftmaxLaunch r = gespmm::resolve_edge_softmax(M, nnz, H);
         n = snprintf(out, (size_t)capacity, "W=%d long_rows>%d", r.W, r.L);
+    }
+    return describe_result(n, capacity);
+}
+
+/* The GATv2 edge score and its gradients (gespmm.h; gatv2_score.h): one kernel each, nothing larger than [nnz x H]. */
+int gespmm_gatv2_score_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att, float* score,
+                           int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_gatv2_sizes(M, K, H, F, nnz, slope);
+    if (rc != 0) return rc;
+    if (nnz == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (F == 0) {
+        if (const int rcp = check_pointers({{score, 4, true}})) return rcp;
+        return (int)hipMemsetAsync(score, 0, (size_t)nnz * (size_t)H * sizeof(float), st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {xl, 4, true}, {xr, 4, true}, {att, 4, true}, {score, 4, true}}))
+        return rcp;
+    const gespmm::Gatv2ScoreLaunch r =
+        gespmm::resolve_gatv2_score(M, nnz, H, F, pointer_alignment(xl), pointer_alignment(xr), pointer_alignment(att));
+    return (int)gespmm::launch_gatv2_score(rowptr, colind, xl, xr, att, score, M, nnz, H, F, slope, r, st);
+}
+
+int gespmm_gatv2_score_backward_f32(const int32_t* ptr, const int32_t* ind, const int32_t* order, const float* grad_score,
+                                    const float* x_seg, const float* x_ind, const float* att, float* grad_x, float* att_part, int64_t S,
+                                    int64_t T, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    const int rc = gespmm::check_gatv2_sizes(S, T, H, F, nnz, slope);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {  // every chain is empty: every word of the results is still written
+        if (const int rcp = check_pointers({{grad_x, 4, true}, {att_part, 4, false}})) return rcp;
+        const size_t bytes = (size_t)S * (size_t)H * (size_t)F * sizeof(float);
+        if (bytes == 0) return 0;
+        hipError_t e = hipMemsetAsync(grad_x, 0, bytes, st);
+        if (e == hipSuccess && att_part) e = hipMemsetAsync(att_part, 0, bytes, st);
+        return (int)e;
+    }
+    if (const int rcp = check_pointers({{ptr, 4, true}, {ind, 4, true}, {grad_score, 4, true}, {x_seg, 4, true}, {x_ind, 4, true},
+                                        {att, 4, true}, {grad_x, 4, true}, {order, 4, false}, {att_part, 4, false}}))
+        return rcp;
+    int align = 16;
+    for (const void* p : {(const void*)x_seg, (const void*)x_ind, (const void*)att, (const void*)grad_x, (const void*)att_part})
+        if (p) align = std::min(align, pointer_alignment(p));
+    return (int)gespmm::launch_gatv2_score_backward(ptr, ind, order, grad_score, x_seg, x_ind, att, grad_x, att_part, S, H, F, nnz, slope,
+                                                    vec_limit(F, align) == 4, st);
+}
+
+int gespmm_describe_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align, char* out,
+                                int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    for (const int a : {xl_align, xr_align, att_align})
+        if (a < 4 || (a & (a - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_sizes(M, nnz > 0 ? 1 : 0, H, F, nnz, 1.0f);  // (the forward's launch shape does not depend on K)
+    if (rc != 0) return rc;
+    int n;
+    if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else if (F == 0) {
+        n = snprintf(out, (size_t)capacity, "route=zeros");
+    } else {
+        const gespmm::Gatv2ScoreLaunch r = gespmm::resolve_gatv2_score(M, nnz, H, F, xl_align > 16 ? 16 : xl_align,
+                                                                       xr_align > 16 ? 16 : xr_align, att_align > 16 ? 16 : att_align);
+        n = snprintf(out, (size_t)capacity, "V=%d W=%d epw=%d", r.V, r.W, r.epw);
     }
     return describe_result(n, capacity);
 }

@@ -316,4 +316,21 @@ EdgeSoftmaxLaunch resolve_edge_softmax(int64_t M, int64_t nnz, int64_t H) {
     return r;
 }
 
+// The GATv2 score. V and W are resolve_sddmm's at WIDTH F — asked in its COO form, which has no row-walking or blocked answer — with the
+// less aligned of xl and xr as one operand and att as the other: V divides F and 4 V bytes divide all THREE bases. Entries per wavefront
+// and the multiply-shift for t / H are resolve_sddmm_heads' rule for its CSR kernel, on the pair count nnz H. None of these thresholds
+// was measured for this kernel, which loads three vectors per pair where the SDDMM loads two: all are carried over.
+Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align) {
+    const SddmmLaunch b = resolve_sddmm(false, M, nnz, F, xl_align < xr_align ? xl_align : xr_align, att_align, false, 4);
+    Gatv2ScoreLaunch r = {b.V, b.W, 0, 0};
+    const int64_t pairs = nnz * H;
+    const int G = 64 / r.W;
+    const int64_t per_wave = (pairs >= 256 * 16384) ? 256 : (pairs >= 64 * 16384) ? 64 : (G * 4 > 16 ? G * 4 : 16);
+    const int64_t epw = per_wave / H;
+    r.epw = (int)(epw < 1 ? 1 : (epw > 256 ? 256 : epw));
+    // t / H == (t * magic) >> 32 for t < 256 H needs 256 H (magic H - 2^32) < 2^32, and magic H - 2^32 < H: H <= 4096
+    if (H <= 4096) r.magic = (uint32_t)(((1ull << 32) + (uint64_t)H - 1) / (uint64_t)H);
+    return r;
+}
+
 }  // namespace gespmm

@@ -71,4 +71,13 @@ struct EdgeSoftmaxLaunch {
 // M >= 1, nnz >= 1, H >= 1. W and L depend on (M, nnz) alone.
 EdgeSoftmaxLaunch resolve_edge_softmax(int64_t M, int64_t nnz, int64_t H);
 
+// ---- GATv2 edge score (gatv2_score.h): the launch shape of the forward (gespmm_describe_gatv2_score prints it).
+struct Gatv2ScoreLaunch {
+    int V, W;        // what resolve_sddmm answers for WIDTH F, with att's address as a third operand: they fix the summation order
+    int epw;         // ENTRIES per wavefront, 1 .. 256 (epw H pairs)
+    uint32_t magic;  // ceil(2^32 / H) where t / H == umulhi(t, magic) for every t < 256 H, else 0 (the kernel divides)
+};
+// nnz >= 1, H >= 1, F >= 1. *_align: largest power of two (bytes) that divides the operand's address, 16 is as good as more.
+Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align);
+
 }  // namespace gespmm

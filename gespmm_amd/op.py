@@ -625,3 +625,120 @@ class GATConv(torch.nn.Module):
 
     def __repr__(self):
         return "%s(%d, %d, heads=%d)" % (type(self).__name__, self.in_channels, self.out_channels, self.heads)
+
+
+class GATv2ScoreFunction(torch.autograd.Function):
+    """score[e, h] = sum_f att[h, f] leaky_relu(xl[row(e), h, f] + xr[col(e), h, f], negative_slope) — the attention score of GATv2
+    (Brody et al.) on the entries of a CSR pattern (``sddmm.gatv2_score``), with gradients for all three operands.
+
+        GATv2ScoreFunction.apply(rowptr, colind, colptr, rowind, csc_order, xl, xr, att, negative_slope) -> f32[nnz, H]
+
+    ``xl`` f32[M, H, F] (the aggregating node), ``xr`` f32[K, H, F] (the neighbour), ``att`` f32[H, F]; ``colptr, rowind, csc_order =
+    graphs.transpose_csr(rowptr, colind, K, return_order=True)``; ``negative_slope=None``: no leaky ReLU. Forward: one launch. Backward:
+    the row pass of ``sddmm.gatv2_score_backward`` when ``xl`` or ``att`` needs a gradient (grad_att is the sum over nodes of its second,
+    node-sized result), the column pass on the CSC arrays when ``xr`` does. Saved: the three operands — no saved or allocated tensor
+    has nnz * H * F words. An int64 ``csc_order`` is converted to int32 in every forward; pass an int32 one. Index tensors get no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, xl, xr, att, negative_slope=None):
+        xl_c, xr_c, att_c = xl.contiguous(), xr.contiguous(), att.contiguous()
+        score = _sddmm.gatv2_score(rowptr, colind, xl_c, xr_c, att_c, negative_slope=negative_slope)
+        order = (csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)).contiguous()
+        ctx.graph = (rowptr, colind, colptr, rowind, order)
+        ctx.negative_slope = negative_slope
+        ctx.save_for_backward(xl_c, xr_c, att_c)
+        return score
+
+    @staticmethod
+    def backward(ctx, grad_score):
+        rowptr, colind, colptr, rowind, order = ctx.graph
+        xl, xr, att = ctx.saved_tensors
+        slope = ctx.negative_slope
+        grad_score = grad_score.contiguous()
+        grad_xl = grad_xr = grad_att = None
+        if ctx.needs_input_grad[5] or ctx.needs_input_grad[7]:
+            want_att = bool(ctx.needs_input_grad[7])
+            res = _sddmm.gatv2_score_backward(rowptr, colind, grad_score, xl, xr, att, negative_slope=slope, want_att_part=want_att)
+            grad_xl, att_part = res if want_att else (res, None)
+            if want_att:
+                grad_att = att_part.sum(0)
+                del att_part
+            if not ctx.needs_input_grad[5]:
+                grad_xl = None
+        if ctx.needs_input_grad[6]:
+            grad_xr = _sddmm.gatv2_score_backward(colptr, rowind, grad_score, xr, xl, att, negative_slope=slope, order=order)
+        return None, None, None, None, None, grad_xl, grad_xr, grad_att, None
+
+
+class GATv2Conv(torch.nn.Module):
+    """GATv2 layer (Brody et al., "How attentive are graph attention networks?") on the library's ops, H heads in every call:
+
+        xl = (x W_dst).view(n, H, F),  xr = (x W_src).view(n, H, F)                                        (dense, torch)
+        score[e, h] = sum_f att[h, f] leaky_relu(xl[row(e), h, f] + xr[col(e), h, f])     ``GATv2ScoreFunction``: nothing of size nnz H F
+        alpha = softmax over each row's entries of score                                  ``EdgeSoftmaxFunction`` (no second leaky ReLU)
+        out[r, h, :] = sum_e alpha[e, h] xr[col(e), h, :]                                 ``MultiHeadSPMMFunction(..., heads_sddmm=True)``
+
+    then heads concatenated (``concat=True``: [n, H F]) or averaged ([n, F]), plus bias.
+
+        GATv2Conv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0)
+        forward(x, rowptr, colind, colptr, rowind, csc_order, attn_seed=None)
+
+    ``share_weights=True``: one matrix for both terms (W_dst is W_src). ``dropout=p`` (0 <= p < 1): ``EdgeDropoutFunction`` on alpha in
+    training mode, the seed handled exactly as in ``GATConv`` (two words from torch's device generator unless ``attn_seed``, an int32[2]
+    device tensor, is given); in ``eval()`` mode or with ``dropout == 0`` the layer makes exactly the launches it makes without it.
+    The ``[nnz, H]`` score and alpha arrays exist (folding the score into the softmax or the aggregation is out of scope).
+
+    The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
+    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0):
+        super().__init__()
+        self.dropout = float(dropout)
+        if not (0.0 <= self.dropout < 1.0):
+            raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
+        if heads < 1:
+            raise ValueError("heads must be at least 1")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, int(heads)
+        self.concat, self.negative_slope, self.share_weights = bool(concat), negative_slope, bool(share_weights)
+        self.weight_src = Parameter(torch.empty(in_channels, self.heads * out_channels))  # the neighbour's term (the column of an edge)
+        if self.share_weights:
+            self.weight_dst = self.weight_src
+        else:
+            self.weight_dst = Parameter(torch.empty(in_channels, self.heads * out_channels))  # the aggregating node's term (the row)
+        self.att = Parameter(torch.empty(1, self.heads, out_channels))
+        if bias:
+            self.bias = Parameter(torch.empty(self.heads * out_channels if self.concat else out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot(self.weight_src)
+        if not self.share_weights:
+            glorot(self.weight_dst)
+        glorot(self.att)
+        zeros(self.bias)
+
+    def forward(self, x, rowptr, colind, colptr, rowind, csc_order, attn_seed=None):
+        n, H, F = x.shape[0], self.heads, self.out_channels
+        p, seed = 0.0, None
+        if self.training and self.dropout > 0.0:
+            p = self.dropout
+            seed = attn_seed
+            if seed is None:  # two 32-bit words from the device generator: no host synchronisation
+                seed = torch.randint(-(2 ** 31), 2 ** 31, (2,), dtype=torch.int32, device=x.device)
+        if rowptr.numel() != n + 1 or colptr.numel() != n + 1:
+            raise ValueError("GATv2Conv needs a square graph: rowptr and colptr must have x.size(0) + 1 entries")
+        xr = (x @ self.weight_src).view(n, H, F)
+        xl = xr if self.share_weights else (x @ self.weight_dst).view(n, H, F)
+        score = GATv2ScoreFunction.apply(rowptr, colind, colptr, rowind, csc_order, xl, xr, self.att.view(H, F), self.negative_slope)
+        alpha = EdgeSoftmaxFunction.apply(rowptr, score, None)
+        if seed is not None:
+            alpha = EdgeDropoutFunction.apply(rowptr, colind, alpha, p, seed)
+        out = MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, xr, alpha, None, True)
+        out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
+        return out if self.bias is None else out + self.bias
+
+    def __repr__(self):
+        return "%s(%d, %d, heads=%d)" % (type(self).__name__, self.in_channels, self.out_channels, self.heads)

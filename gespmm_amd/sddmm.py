@@ -21,6 +21,16 @@ D1 f32[M, H, F], D2 f32[K, H, F]: out[e, h] = <D1[row(e), h, :], D2[col(e), h, :
 layer, or the edge-weight gradient of ``spmm.csr_spmm_heads`` — in ONE kernel that finds the row and column of an edge once for all
 heads. Head h has the bits of ``csr_sddmm`` on ``D1[:, h, :].contiguous()`` and ``D2[:, h, :].contiguous()``. fp32 only: 16-bit
 operands raise TypeError.
+
+GATv2 edge score (extension; gespmm_gatv2_score_f32, gespmm_gatv2_score_backward_f32):
+
+    gatv2_score(rowptr, colind, xl, xr, att, negative_slope=0.2, out=None)                         -> f32[nnz, H]
+    gatv2_score_backward(ptr, ind, grad_score, x_seg, x_ind, att, negative_slope=0.2, order=None,
+                         want_att_part=False, out=None)                                            -> grad_x f32[S, H, F] (, att_part)
+
+score[p, h] = sum_f att[h, f] leaky_relu(xl[row(p), h, f] + xr[col(p), h, f]) — the non-linearity inside the sum, so the score is no
+dot product of a row term and a column term — in ONE kernel, and its gradients in one kernel that serves both node terms; nothing of
+size nnz * H * F exists in either direction. fp32 and CSR form only.
 """
 import torch
 
@@ -156,3 +166,137 @@ def csr_sddmm_heads(rowptr, colind, D1, D2, out=None, plan=None):
             rc = lib.gespmm_sddmm_csr_heads_f32(_ptr(rowptr), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), M, H, F, nnz, _stream(dev))
     check(rc, "gespmm_plan_sddmm_heads_f32" if plan is not None else "gespmm_sddmm_csr_heads_f32")
     return out
+
+
+# ---- GATv2 edge score (extension; gespmm_gatv2_score_f32 / gespmm_gatv2_score_backward_f32)
+
+def _gatv2_typed(int_ops, float_ops):
+    """TypeError for every operand that is no tensor of its dtype — before any shape is looked at (``None`` passes)."""
+    for dtype, ops in ((torch.int32, int_ops), (torch.float32, float_ops)):
+        for name, t in ops:
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("%s must be a torch.Tensor" % name)
+            if t.dtype != dtype:  # (16-bit and fp64 operands have no entry point: TypeError)
+                raise TypeError("%s must have dtype %s, got %s" % (name, dtype, t.dtype))
+
+
+def _gatv2_slope(negative_slope):
+    if negative_slope is None:
+        return 1.0
+    s = float(negative_slope)
+    if s != s or s in (float("inf"), float("-inf")):
+        raise ValueError("negative_slope must be finite, got %r" % (negative_slope,))
+    return s
+
+
+def _gatv2_shaped(named, dev):
+    """ValueError for what is not contiguous or not on ``dev`` (shapes were checked by the caller)."""
+    for name, t in named:
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+        if t.device != dev:
+            raise ValueError("%s must live on %s, as the other operands" % (name, dev))
+    if dev.type != "cuda":
+        raise ValueError("the operands must be HIP (cuda) device tensors; gespmm_amd has no CPU path")
+
+
+def gatv2_score(rowptr, colind, xl, xr, att, negative_slope=0.2, out=None):
+    """The GATv2 attention score (Brody et al.) on the entries of a CSR pattern, H heads in ONE launch (gespmm_gatv2_score_f32):
+
+        score[p, h] = sum_f att[h, f] * leaky_relu(xl[row(p), h, f] + xr[colind[p], h, f], negative_slope)
+
+    ``xl`` f32[M, H, F] is the aggregating node's term, ``xr`` f32[K, H, F] the neighbour's, ``att`` f32[H, F]; the result is f32[nnz, H]
+    in CSR entry order — what ``softmax.edge_softmax`` reads. Nothing of size nnz * H * F exists. ``negative_slope=None``: no leaky
+    ReLU. ``out``: an f32[nnz, H] tensor to write into. The summation order is pinned by ``_lib.describe_gatv2_score`` (include/gespmm.h).
+    ``colind`` within [0, K) and ``rowptr[M] == nnz`` are preconditions. fp32 only: other dtypes raise TypeError."""
+    _gatv2_typed((("rowptr", rowptr), ("colind", colind)), (("xl", xl), ("xr", xr), ("att", att), ("out", out)))
+    for name, t in (("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att)):
+        if t is None:
+            raise TypeError("%s must be a torch.Tensor" % name)
+    slope = _gatv2_slope(negative_slope)
+    if xl.dim() != 3 or xr.dim() != 3 or xl.shape[1] < 1:
+        raise ValueError("xl and xr must be [rows, H, F] with at least one head")
+    M, H, F = xl.shape
+    K = xr.shape[0]
+    if tuple(xr.shape[1:]) != (H, F):
+        raise ValueError("xl %s and xr %s must have the same heads and columns" % (tuple(xl.shape), tuple(xr.shape)))
+    if tuple(att.shape) != (H, F):
+        raise ValueError("att must be f32[%d, %d], got %s" % (H, F, tuple(att.shape)))
+    if rowptr.dim() != 1 or rowptr.numel() != M + 1:
+        raise ValueError("rowptr must be a vector of xl.size(0) + 1 entries")
+    if colind.dim() != 1:
+        raise ValueError("colind must be a vector")
+    nnz = colind.numel()
+    if out is not None and tuple(out.shape) != (nnz, H):
+        raise ValueError("out must be f32[%d, %d]" % (nnz, H))
+    dev = xl.device
+    _gatv2_shaped((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("out", out)), dev)
+    if out is None:
+        out = torch.empty((nnz, H), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib.gespmm_gatv2_score_f32(_ptr(rowptr), _ptr(colind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(out), M, K, H, F, nnz, slope,
+                                        _stream(dev))
+    check(rc, "gespmm_gatv2_score_f32")
+    return out
+
+
+def gatv2_score_backward(ptr, ind, grad_score, x_seg, x_ind, att, negative_slope=0.2, order=None, want_att_part=False, out=None):
+    """The gradient of ``gatv2_score`` for one node term, over the segments ``(ptr, ind)`` describe (gespmm_gatv2_score_backward_f32):
+
+        grad_x[s, h, f]   = sum over the entries p of segment s of grad_score[q, h] * (t >= 0 ? att[h, f] : att[h, f] * negative_slope)
+        att_part[s, h, f] = sum over the entries p of segment s of grad_score[q, h] * leaky_relu(t, negative_slope)
+
+    with ``t = x_seg[s, h, f] + x_ind[ind[p], h, f]`` and ``q = order[p]`` (``p`` without ``order``). Row pass — ``(rowptr, colind, grad_score,
+    xl, xr, att, want_att_part=True)`` — returns ``(grad_xl, att_part)``, and ``att_part.sum(0)`` is the gradient of ``att``; column pass
+    — ``(colptr, rowind, grad_score, xr, xl, att, order=csc_order)`` — returns ``grad_xr``. One fp32 chain per output word in segment
+    order, whatever the lane geometry; every word is written (+0 for an empty segment). ``order`` is int32. ``out``: the f32[S, H, F]
+    tensor for grad_x, or the pair ``(grad_x, att_part)`` with ``want_att_part``. Nothing of size nnz * H * F exists."""
+    out_x, out_a = out if isinstance(out, (tuple, list)) and len(out) == 2 else (out, None)
+    _gatv2_typed((("ptr", ptr), ("ind", ind), ("order", order)),
+                 (("grad_score", grad_score), ("x_seg", x_seg), ("x_ind", x_ind), ("att", att), ("out", out_x), ("out[1]", out_a)))
+    for name, t in (("ptr", ptr), ("ind", ind), ("grad_score", grad_score), ("x_seg", x_seg), ("x_ind", x_ind), ("att", att)):
+        if t is None:
+            raise TypeError("%s must be a torch.Tensor" % name)
+    slope = _gatv2_slope(negative_slope)
+    if x_seg.dim() != 3 or x_ind.dim() != 3 or x_seg.shape[1] < 1:
+        raise ValueError("x_seg and x_ind must be [rows, H, F] with at least one head")
+    S, H, F = x_seg.shape
+    T = x_ind.shape[0]
+    if tuple(x_ind.shape[1:]) != (H, F):
+        raise ValueError("x_seg %s and x_ind %s must have the same heads and columns" % (tuple(x_seg.shape), tuple(x_ind.shape)))
+    if tuple(att.shape) != (H, F):
+        raise ValueError("att must be f32[%d, %d], got %s" % (H, F, tuple(att.shape)))
+    if ptr.dim() != 1 or ptr.numel() != S + 1:
+        raise ValueError("ptr must be a vector of x_seg.size(0) + 1 entries")
+    if ind.dim() != 1:
+        raise ValueError("ind must be a vector")
+    nnz = ind.numel()
+    if tuple(grad_score.shape) != (nnz, H):
+        raise ValueError("grad_score must be f32[%d, %d], got %s" % (nnz, H, tuple(grad_score.shape)))
+    if order is not None and tuple(order.shape) != (nnz,):
+        raise ValueError("order must be a vector of %d entries" % nnz)
+    if out_a is not None and not want_att_part:
+        raise ValueError("out is a pair only with want_att_part")
+    for name, t in (("out", out_x), ("out[1]", out_a)):
+        if t is not None and tuple(t.shape) != (S, H, F):
+            raise ValueError("%s must be f32[%d, %d, %d]" % (name, S, H, F))
+    dev = x_seg.device
+    _gatv2_shaped((("ptr", ptr), ("ind", ind), ("order", order), ("grad_score", grad_score), ("x_seg", x_seg), ("x_ind", x_ind),
+                   ("att", att), ("out", out_x), ("out[1]", out_a)), dev)
+    if out_x is None:
+        out_x = torch.empty((S, H, F), dtype=torch.float32, device=dev)
+    if want_att_part and out_a is None:
+        out_a = torch.empty((S, H, F), dtype=torch.float32, device=dev)
+    if out_x.numel() == 0:  # (results of no words have no address to hand over)
+        return (out_x, out_a) if want_att_part else out_x
+    with _on_device(dev):
+        rc = lib.gespmm_gatv2_score_backward_f32(_ptr(ptr), _ptr(ind), _ptr(order) if order is not None else None, _ptr(grad_score),
+                                                 _ptr(x_seg), _ptr(x_ind), _ptr(att), _ptr(out_x), _ptr(out_a) if want_att_part else None,
+                                                 S, T, H, F, nnz, slope, _stream(dev))
+    check(rc, "gespmm_gatv2_score_backward_f32")
+    return (out_x, out_a) if want_att_part else out_x
+

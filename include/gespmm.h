@@ -746,6 +746,47 @@ int gespmm_gat_backward_er_dropout_f32(const int32_t* colptr, const int32_t* row
  * outside [0, 1), which no legal p gives. */
 uint32_t gespmm_edge_dropout_bits(uint32_t s0, uint32_t s1, uint32_t r, uint32_t c, uint32_t h);
 uint32_t gespmm_edge_dropout_threshold(float p);
+/*
+ * The GATv2 edge score (Brody et al.) and its gradients with nothing larger than [nnz x H] (new symbols of 0.5). xl [M x H x F] is the
+ * aggregating node's term (the row of an entry), xr [K x H x F] the neighbour's (the column), att [H x F]; score is [nnz x H] in CSR
+ * entry order, head-minor — what gespmm_edge_softmax_f32 reads:
+ *
+ *     score[p H + h] = sum_f att[h, f] leaky(fl(xl[row(p), h, f] + xr[col(p), h, f]))      leaky(t) = t >= 0 ? t : slope t
+ *
+ * (one fp32 add; slope == 1: no multiply). One kernel in the geometry of gespmm_sddmm_csr_heads_f32, att's head slice a third operand:
+ * (V, W, epw) from gespmm_describe_gatv2_score for width F and the THREE operand addresses (V divides F, 4 V bytes divide all three).
+ * Pinned order: lane l of W runs ONE chain acc = fmaf(att[h, j], leaky(fl(xl_j + xr_j)), acc) from +0 over j = l V + i + t W V (i
+ * ascending inside a vector, t ascending), then the xor butterfly W/2 .. 1; a lane past the slice contributes fmaf(0, 0, 0).
+ *
+ * gespmm_gatv2_score_backward_f32 serves both node terms. For segment s with entries p in [ptr[s], ptr[s + 1]), c = ind[p],
+ * q = order ? order[p] : p and t = fl(x_seg[s, h, f] + x_ind[c, h, f]):
+ *
+ *     m_pf              = t >= 0 ? att[h, f] : fl(att[h, f] slope)                (att[h, f] for every t when slope == 1)
+ *     grad_x[s, h, f]   = chain over p ascending from +0 of fmaf(grad_score[q H + h], m_pf, acc)
+ *     att_part[s, h, f] = chain over p ascending from +0 of fmaf(grad_score[q H + h], leaky(t), acc)       (only when att_part != NULL)
+ *
+ * Row pass (grad_xl and att_part): ptr = rowptr, ind = colind, order = NULL, x_seg = xl, x_ind = xr, S = M, T = K. Column pass
+ * (grad_xr): ptr = colptr, ind = rowind, order = csc_order, x_seg = xr, x_ind = xl, att_part = NULL, S = K, T = M. fp32 addition
+ * commutes bit for bit: both passes see the same t. The gradient of att is att_part summed over s by the caller. Pinned order: ONE
+ * fp32 fmaf chain per output word in segment order (the contract of gespmm_csr_spmm_heads_f32); lane geometry and vector width (16-byte
+ * loads when F % 4 == 0 and x_seg, x_ind, att and the results are 16-byte aligned, 4-byte loads otherwise) leave no trace in the bits.
+ * There is no long-row pass: a hub segment is walked by one lane group. Every word of grad_x (and att_part) is written, +0 for an
+ * empty segment.
+ * Checks, in this order (S, T stand for M, K in the forward): a negative size, H < 1, T < 1 or S < 1 with nnz > 0, a NaN or infinite
+ * slope -> GESPMM_EINVAL; S, nnz, nnz H, S H F or T H F > 2^31 - 4097 -> GESPMM_ERANGE (32-bit word positions, no other route);
+ * forward: nnz == 0 -> 0 without looking at pointers; backward: nnz == 0 or F == 0 looks at the results alone and zero-fills them;
+ * forward: F == 0 zero-fills score; NULL (order and att_part may be NULL) -> GESPMM_EINVAL; a pointer not 4-byte aligned ->
+ * GESPMM_EALIGN. No atomics, no workspace, no allocation, no host synchronisation: capturable. Results must not overlap an input.
+ */
+int gespmm_gatv2_score_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att, float* score,
+                           int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gatv2_score_backward_f32(const int32_t* ptr, const int32_t* ind, const int32_t* order, const float* grad_score,
+                                    const float* x_seg, const float* x_ind, const float* att, float* grad_x, float* att_part, int64_t S,
+                                    int64_t T, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+/* Host only: what gespmm_gatv2_score_f32 would launch, as text: "V=.. W=.. epw=..", "route=zeros" (F == 0) or "form=none" (nnz == 0).
+ * *_align: largest power of two (>= 4) dividing the operand's address. Returns the length written or a GESPMM_E* code. */
+int gespmm_describe_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align, char* out,
+                                int64_t capacity);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
