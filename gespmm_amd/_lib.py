@@ -77,6 +77,7 @@ EXPORTS = [
     "gespmm_device_cluster_rows",
     "gespmm_device_l2_model",
     "gespmm_plan_debug_tasks",
+    "gespmm_plan_debug_staging",
     "gespmm_release_cached_memory",
     "gespmm_init",
     "gespmm_set_auto_plan",
@@ -171,7 +172,7 @@ class PlanPolicyAnswer(Structure):
                                                                                        ("est_cost_us", ctypes.c_double), ("cluster_sweeps", c_int32),
                                                                                        ("staged_rows", c_int32), ("build_records", c_int32),
                                                                                        ("keep_records", c_int32), ("records_batches", c_int32),
-                                                                                       ("slab_ranges", c_int32)]
+                                                                                       ("slab_ranges", c_int32), ("staged_fill_window", c_int32)]
 
 
 class AutoPlanStats(Structure):
@@ -361,6 +362,8 @@ def _load():
     lib.gespmm_release_cached_memory.argtypes = []
     lib.gespmm_plan_debug_tasks.restype = c_int
     lib.gespmm_plan_debug_tasks.argtypes = [p, c_int32, p, c_int64]
+    lib.gespmm_plan_debug_staging.restype = c_int64
+    lib.gespmm_plan_debug_staging.argtypes = [p, p, p, c_int64]
     lib.gespmm_simulate_l2_hits.restype = ctypes.c_double
     lib.gespmm_simulate_l2_hits.argtypes = [p, p, c_int64, c_int64, p, c_int32, c_int64]
     lib.gespmm_row_partition.restype = c_int

@@ -418,6 +418,22 @@ int gespmm_plan_debug_tasks(const gespmm_plan* p, int32_t which, int32_t* out_ho
     return n;
 }
 
+// Test hook: the staging lists of the plan's staged-rows tables (blocks x slots columns, -1 = unused) in HOST memory.
+int64_t gespmm_plan_debug_staging(const gespmm_plan* p, int32_t* info_host, int32_t* out_host, int64_t capacity) {
+    if (!p) return GESPMM_EINVAL;
+    if (!p->stg.ev || !p->stg.hot_cols) return 0;
+    const int64_t n = (int64_t)p->stg.nblocks * p->stg.slots;
+    if (info_host) {
+        info_host[0] = p->stg.nblocks;
+        info_host[1] = p->stg.slots;
+        info_host[2] = p->stg.rows;
+        info_host[3] = p->stg.fill_window;
+    }
+    const int64_t take = n < capacity ? n : capacity;
+    if (take > 0 && out_host && hipMemcpy(out_host, p->stg.hot_cols, (size_t)take * 4, hipMemcpyDeviceToHost) != hipSuccess) return GESPMM_EINVAL;
+    return n;
+}
+
 // Tables of the staged-rows kernel for the plan's width (plan_device.hip). Hub rows (one wavefront would walk such a row
 // alone) are taken out: the staged kernel sees them empty, the streaming kernel's long-row pass gets them as one-row tasks
 // (plan_run). Leaves p->stg empty when there is nothing but hub rows.
@@ -440,9 +456,14 @@ static hipError_t build_staging_tables(gespmm_plan* p, hipStream_t st) {
         val_s = val_tmp;
         nnz_s = p->stg.nnz_s;
     }
+    // the fill pass's window (plan_policy.cpp: staged_fill_window) — GESPMM_STAGED_FILL overrides it, read per plan so that one process
+    // can build the same plan with and without the pass (0: none)
+    int fill = gespmm::staged_fill_window(p->facts, shape);
+    if (const char* fe = getenv("GESPMM_STAGED_FILL")) fill = M == K ? atoi(fe) : 0;
+    fill = fill < 0 ? 0 : (fill > gespmm::kStagedFillMaxWindow ? gespmm::kStagedFillMaxWindow : fill);
     if (e == hipSuccess && nnz_s > 0)
         e = gespmm::device_build_staging(M, K, nnz_s, rp_s, ci_s, val_s, p->d_perm, shape.rows, shape.slots, shape.waves,
-                                         shape.tasks_per_block, &p->stg, st);
+                                         shape.tasks_per_block, &p->stg, st, 0, false, fill);
     if (ci_tmp) (void)hipFree(ci_tmp);
     if (val_tmp) (void)hipFree(val_tmp);
     if (e == hipSuccess && !p->stg.ev) gespmm::free_staging(&p->stg);  // (nothing but hub rows)
@@ -817,6 +838,17 @@ static int plan_create_impl(gespmm_plan** out, const int32_t* rowptr, const int3
         if ((rc = validate_and_decide(p, cx, opt)) != 0) return rc;
         bool clustered = false;
         if (cx.ad.analyse && (rc = cx.on_host ? order_on_host(p, cx, &clustered) : order_on_device(p, cx, &clustered)) != 0) return rc;
+        if (!clustered && !cx.ad.analyse && !cx.on_host && p->facts.reorder_mode == GESPMM_PLAN_NO_REORDER &&
+            p->kernel_choice == GESPMM_PLAN_KERNEL_STAGED && M > 0 && nnz > 0) {
+            // the caller keeps the order AND asks for the staged-rows kernel, which walks the plan's tables: the plan's copy in the identity
+            // order, as for a matrix that AUTO finds already clustered (dropped again in build_device_tables where no tables come of it)
+            hipError_t e = alloc_plan_copy(p);
+            if (e == hipSuccess)
+                e = gespmm::device_identity_copy(M, nnz, p->rowptr, p->colind, p->d_perm, p->d_rowptr, p->d_colind, p->d_src_begin, cx.st);
+            if (e != hipSuccess) return (int)e;
+            p->identity_order = true;
+            clustered = true;
+        }
         if (clustered) {
             const gespmm::PlanKernelDecision kd = gespmm::choose_plan_kernel(p->facts, p->hits_after);
             if ((rc = make_task_tables(p, cx, kd)) != 0) return rc;
@@ -1436,8 +1468,8 @@ int gespmm_plan_describe(const gespmm_plan* p, char* out, int64_t capacity) {
         snprintf(kern, sizeof kern, "kernel=staged-slabs slabs=%d blocks=%d rows_in_lds<=%d staged_entries=%.3f tables=%.4fs (max / other widths: %s)",
                  p->slab_view.slabs, p->slab.nblocks, p->slab.slots, p->slab.staged_fraction, p->slab_seconds, what);
     else if (ra.staged())
-        snprintf(kern, sizeof kern, "kernel=staged-rows blocks=%d rows_in_lds<=%d staged_entries=%.3f hub_rows=%d tables=%.4fs (max / other widths: %s)",
-                 p->stg.nblocks, gespmm::staged_block_shape(p->N).slots, p->stg.staged_fraction, p->stg.nlong, p->staging_seconds, what);
+        snprintf(kern, sizeof kern, "kernel=staged-rows blocks=%d rows_in_lds<=%d staged_entries=%.3f filled_entries=%.3f hub_rows=%d tables=%.4fs (max / other widths: %s)",
+                 p->stg.nblocks, gespmm::staged_block_shape(p->N).slots, p->stg.staged_fraction, p->stg.filled_fraction, p->stg.nlong, p->staging_seconds, what);
     else snprintf(kern, sizeof kern, "%s", what);
     if (p->x16_last_route >= 0) {  // the last 16-bit call (gespmm_plan_spmm_x16)
         const size_t used = strlen(kern);

@@ -58,7 +58,10 @@ struct StagingTables {
     int32_t nblocks = 0;
     int32_t waves = 0;            // wavefronts (tasks) per block
     int32_t slots = 0;            // staged rows per block (H)
-    double staged_fraction = 0.0;
+    int32_t rows = 0;             // rows per block (R)
+    int32_t fill_window = 0;      // blocks on each side whose rows counted as near in the fill pass (0: no fill pass)
+    double staged_fraction = 0.0;  // share of the entries staged by the >= 2 rule (what the policy's thresholds were set on)
+    double filled_fraction = 0.0;  // share of the entries staged by the fill pass on top of it (single-use columns of near rows)
     // hub rows (device_split_long_rows): the staged kernel walks a copy of the row pointers in which they are EMPTY, and they
     // are handed to the streaming kernel's long-row pass as one-row tasks. NULL / 0: no such rows, the plan's own row pointers.
     int32_t* rowptr_s = nullptr;  // M + 1
@@ -74,9 +77,13 @@ hipError_t device_split_long_rows(int64_t M, int64_t nnz, const int32_t* rowptr_
                                   int limit, StagingTables* t, int32_t** colind_s, float** val_s, hipStream_t st);
 // perm (clustered position -> C row; NULL = identity) goes into the row-end records of the stream.
 // `parts`: tasks per block (the wide kernel: one per wavefront = waves; the narrow kernel: one per lane group = waves x G)
+// `fill_window` (0 ... kStagedFillMaxWindow; square matrices, one segment, no slab tables — otherwise it is taken as 0): slots the >= 2
+// rule leaves free go to columns the block uses ONCE whose own row lies in the block or within fill_window blocks of it in the plan's order
+// (perm inverted; NULL = the identity order) — nearest blocks first, ties in column order. 0: the tables of the >= 2 rule alone, bit for bit.
+constexpr int kStagedFillMaxWindow = 8;
 hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t* rowptr_p, const int32_t* colind_p,
                                 const float* val_p, const int32_t* perm, int R, int H, int waves, int parts, StagingTables* out,
-                                hipStream_t st, int64_t seg_rows = 0, bool slab_tables = false);
+                                hipStream_t st, int64_t seg_rows = 0, bool slab_tables = false, int fill_window = 0);
 // (seg_rows > 0: blocks never straddle a segment of seg_rows rows, M a multiple of it; slab_tables: the tables of a column-slab view —
 //  task word 0 = C row of the task's first row, row-end codes carry the C row of the next row: spmm_staged.hip's continuing launches)
 

@@ -1742,13 +1742,23 @@ hipError_t device_cut_tasks(int64_t M, const int32_t* rowptr_p, const int64_t bu
 //
 // Blocks of R consecutive rows of the clustered matrix (R = the block shape's rows). Per block: the block's column indices sorted (one segment of
 // a segmented radix sort, payload = position of the entry), runs of equal columns = how often the block uses a B row; the H
-// most used ones (>= 2 uses; ties taken in column order, so the tables are the same on every build) get LDS slots.
+// most used ones (>= 2 uses; ties taken in column order, so the tables are the same on every build) get LDS slots. Slots left over go
+// to columns used once whose own row is near in the plan's order (the fill pass: StageFill, plan_policy.cpp: staged_fill_window).
 
 namespace {
 
 constexpr int kStageHistBins = 256;
 constexpr int kStageCounters = 64;  // partial sums of the staged-entry count (power of two)
 constexpr int kStageKeysLds = 8192;  // keys of a block kept in LDS by k_stage_select (32 KB)
+
+// The fill pass of k_stage_select (window == 0: none). rank[c] = position of row c in the plan's order (NULL: the identity order).
+struct StageFill {
+    const int32_t* rank;
+    int window;  // blocks on each side of a block whose rows count as near (<= kStagedFillMaxWindow)
+    int rows;    // R
+    int64_t M, nblk;
+};
+constexpr int kStageFillMaxWindow = kStagedFillMaxWindow;
 
 // First row of block `blk`: blocks of R rows that never straddle a SEGMENT of seg_rows rows (column-slab tables: one segment per slab —
 // a launch covers the blocks of one segment; every other table: one segment = the matrix). nb_seg = blocks per segment.
@@ -1770,15 +1780,28 @@ __global__ void k_stage_offsets(const int32_t* __restrict__ rowptr_p, int64_t M,
 __global__ __launch_bounds__(256) void k_stage_select(const int32_t* __restrict__ blkoff, const int32_t* __restrict__ keys,
                                                        const int32_t* __restrict__ idx, int H, int32_t* __restrict__ code,
                                                        int32_t* __restrict__ hot_cols, int32_t* __restrict__ nhot,
-                                                       unsigned long long* __restrict__ staged_entries) {
+                                                       unsigned long long* __restrict__ staged_entries, StageFill fill) {
     using BlockScan = rocprim::block_scan<int, 256>;
     __shared__ typename BlockScan::storage_type scan_storage;
     __shared__ int hist[kStageHistBins];
     __shared__ int s_t, s_ngt, s_quota;
+    __shared__ int dhist[kStageFillMaxWindow + 1];  // fill pass: single-use columns by block distance of their own row
+    __shared__ int s_fd, s_fnlt, s_fquota;
     const int tid = threadIdx.x;
     const int64_t blk = blockIdx.x;
     const int b = blkoff[blk], e = blkoff[blk + 1];
     hist[tid] = 0;
+    if (tid <= kStageFillMaxWindow) dhist[tid] = 0;
+    // Fill pass (fill.window > 0): block distance of column `key`'s own row from this block's rows [row0, row1) in the plan's order — 0 inside
+    // the block, d for the d-th block of fill.rows rows before or behind it, -1 beyond the window. rank[key] is one independent global load
+    // per single-use column and pass (no chain: nothing like the run walks above it).
+    const int row0 = fill.window > 0 ? (int)stage_block_begin(blk, fill.rows, fill.M, fill.nblk, fill.M) : 0;
+    const int row1 = fill.window > 0 ? (int)stage_block_begin(blk + 1, fill.rows, fill.M, fill.nblk, fill.M) : 0;
+    auto fill_dist = [&](int key) -> int {
+        const int r = fill.rank ? fill.rank[key] : key;
+        const int d = r < row0 ? (row0 - 1 - r) / fill.rows + 1 : (r >= row1 ? (r - row1) / fill.rows + 1 : 0);
+        return d <= fill.window ? d : -1;
+    };
     // the block's sorted keys are walked run by run, twice, by the thread at each run's head: from LDS when they fit (they do unless the
     // block holds more than kStageKeysLds entries) — the walk is a chain of dependent loads as long as the longest run, and from global
     // memory that chain was most of this kernel's 180-197 us on the headline graph
@@ -1801,6 +1824,10 @@ __global__ __launch_bounds__(256) void k_stage_select(const int32_t* __restrict_
         int key = 0;
         const int len = run_at(p0 + tid, key);
         if (len >= 2) atomicAdd(&hist[len < kStageHistBins ? len : kStageHistBins - 1], 1);
+        if (len == 1 && fill.window > 0) {
+            const int d = fill_dist(key);
+            if (d >= 0) atomicAdd(&dhist[d], 1);
+        }
     }
     __syncthreads();
     {
@@ -1826,7 +1853,26 @@ __global__ __launch_bounds__(256) void k_stage_select(const int32_t* __restrict_
     }
     __syncthreads();
     const int t = s_t, ngt = s_ngt, quota = s_quota;
-    int base_gt = 0, base_eq = 0;
+    // Fill pass: slots the >= 2 rule leaves free (none when it overflowed: t >= 2) go to single-use columns whose own row is near — a
+    // staged column is fetched at block start, when the neighbouring block that owns the row fetches it too; gathered in the walk it
+    // arrives after the line has left L2 about half the time. Nearest blocks first, ties in column order: every candidate
+    // closer than fd (nlt of them), then `fquota` at distance exactly fd.
+    if (tid == 0) {
+        int fd = 0, nlt = 0, fq = 0;
+        if (fill.window > 0 && t < 2) {
+            const int nfree = H - ngt;
+            while (fd <= fill.window && nlt + dhist[fd] <= nfree) nlt += dhist[fd++];
+            fq = fd <= fill.window ? nfree - nlt : 0;
+        }
+        s_fd = fd;
+        s_fnlt = nlt;
+        s_fquota = fq;
+    }
+    __syncthreads();
+    const int fd = s_fd, fnlt = s_fnlt, fquota = s_fquota;
+    const bool filling = fnlt + fquota > 0;  // (uniform over the workgroup)
+    int base_gt = 0, base_eq = 0, base_lt = 0, base_fd = 0;
+    unsigned long long mine_fill = 0;
     unsigned long long mine = 0;
     for (int p0 = b; p0 < e; p0 += 256) {
         const int p = p0 + tid;
@@ -1840,19 +1886,34 @@ __global__ __launch_bounds__(256) void k_stage_select(const int32_t* __restrict_
         int slot = -1;
         if (f_gt) slot = base_gt + (ex & 0xffff);
         else if (f_eq && base_eq + (ex >> 16) < quota) slot = ngt + base_eq + (ex >> 16);
+        if (filling) {
+            const int d = len == 1 ? fill_dist(key) : -1;
+            const int f_lt = (d >= 0 && d < fd) ? 1 : 0;
+            const int f_fd = (d >= 0 && d == fd) ? 1 : 0;
+            int fex = 0, ftotal = 0;
+            __syncthreads();  // scan_storage again
+            BlockScan().exclusive_scan(f_lt | (f_fd << 16), fex, 0, ftotal, scan_storage, rocprim::plus<int>());
+            if (f_lt) slot = ngt + base_lt + (fex & 0xffff);
+            else if (f_fd && base_fd + (fex >> 16) < fquota) slot = ngt + fnlt + base_fd + (fex >> 16);
+            if (len == 1 && slot >= 0) mine_fill += 1;
+            base_lt += ftotal & 0xffff;
+            base_fd += ftotal >> 16;
+        }
         if (len > 0) {
             const int c = slot >= 0 ? (int)(0x80000000u | (unsigned)slot) : key;
             for (int i = 0; i < len; ++i) code[idx[p + i]] = c;
             if (slot >= 0) {
                 hot_cols[blk * H + slot] = key;
-                mine += (unsigned long long)len;
+                if (len >= 2) mine += (unsigned long long)len;
             }
         }
         base_gt += total & 0xffff;
         base_eq += total >> 16;
         __syncthreads();  // scan_storage is reused by the next tile
     }
-    if (tid == 0) nhot[blk] = ngt + (base_eq < quota ? base_eq : quota);
+    if (tid == 0) nhot[blk] = ngt + (base_eq < quota ? base_eq : quota) + fnlt + (base_fd < fquota ? base_fd : fquota);
+    // (staged entries and filled entries travel in one word: a block holds fewer than 2^31 entries)
+    mine |= mine_fill << 32;
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
     // (one atomic per workgroup, spread over kStageCounters addresses the host adds up: 14 000 same-address 64-bit atomics, one per
     //  wavefront, were 130 of this kernel's 180 us on the headline graph)
@@ -1861,7 +1922,8 @@ __global__ __launch_bounds__(256) void k_stage_select(const int32_t* __restrict_
     __syncthreads();
     if (tid == 0) {
         const unsigned long long all = s_mine[0] + s_mine[1] + s_mine[2] + s_mine[3];
-        if (all) atomicAdd(&staged_entries[blk & (kStageCounters - 1)], all);
+        if (all & 0xffffffffull) atomicAdd(&staged_entries[blk & (kStageCounters - 1)], all & 0xffffffffull);
+        if (all >> 32) atomicAdd(&staged_entries[kStageCounters + (blk & (kStageCounters - 1))], all >> 32);
     }
 }
 
@@ -2021,7 +2083,7 @@ void free_staging(StagingTables* t) {
 
 hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t* rowptr_p, const int32_t* colind_p,
                                 const float* val_p, const int32_t* perm, int R, int H, int waves, int parts, StagingTables* out,
-                                hipStream_t st, int64_t seg_rows, bool slab_tables) {
+                                hipStream_t st, int64_t seg_rows, bool slab_tables, int fill_window) {
     // (rowptr_p / colind_p / val_p / nnz describe what the staged kernel walks: the clustered matrix, or its copy without hub rows —
     // `out` then already carries rowptr_s / ltasks / nlong / nnz_s from device_split_long_rows, which stay)
     if (M <= 0 || nnz <= 0 || K <= 0 || H <= 0 || R <= 0 || waves <= 0 || waves > kStagedMaxWaves || parts < waves || parts > 64 * waves)
@@ -2029,6 +2091,8 @@ hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t
     const int kStagedWaves = parts;  // tasks per block
     if (seg_rows <= 0 || seg_rows > M) seg_rows = M;
     if (M % seg_rows != 0 || (slab_tables && (!perm || M >= (1ll << 30)))) return hipErrorInvalidValue;
+    if (fill_window < 0 || fill_window > kStagedFillMaxWindow) return hipErrorInvalidValue;
+    if (slab_tables || seg_rows != M || K != M) fill_window = 0;  // (a column has a home row in a square matrix only)
     const int64_t nb_seg = (seg_rows + R - 1) / R;  // blocks per segment (column-slab tables: per slab)
     const int64_t nblk = (M / seg_rows) * nb_seg;
     // (Round 3 marked columns whose own row sits far away in the clustered order and gathered them `nt`; level or harmful once the block
@@ -2043,7 +2107,7 @@ hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t
     // temporaries (16 bytes per entry + the sort's own) from the analysis arena: a products-sized matrix needs ~2.5 GB here, about
     // what its clustering needed a moment ago — the cached block is reused instead of a multi-GB hipMalloc / hipFree per plan
     Scratch sc(st);
-    GESPMM_TRY(sc.init(0, 0, 16 * (size_t)nnz + 4 * (size_t)(M + nblk) + sort_bytes + (8 << 20)));
+    GESPMM_TRY(sc.init(0, 0, 16 * (size_t)nnz + 4 * (size_t)(2 * M + nblk) + sort_bytes + (8 << 20)));
     sc.use(Scratch::kTemp);
     int32_t *blkoff = nullptr, *keys = nullptr, *idx_in = nullptr, *idx_out = nullptr, *code = nullptr;
     unsigned long long* staged = nullptr;
@@ -2053,11 +2117,14 @@ hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t
     GESPMM_TRY(sc.get(&idx_in, nnz));
     GESPMM_TRY(sc.get(&idx_out, nnz));
     GESPMM_TRY(sc.get(&code, nnz));
-    GESPMM_TRY(sc.get(&staged, kStageCounters));
+    GESPMM_TRY(sc.get(&staged, 2 * kStageCounters));  // (second half: entries staged by the fill pass)
+    int32_t* rank = nullptr;
+    if (fill_window > 0 && perm) GESPMM_TRY(sc.get(&rank, M));
     GESPMM_TRY(sc.get(&tmp, (int64_t)(sort_bytes ? sort_bytes : 256)));
     StagingTables t;  // the four tables built here; merged into *out on success
     auto body = [&]() -> hipError_t {
-        GESPMM_TRY(hipMemsetAsync(staged, 0, 8 * kStageCounters, st));
+        GESPMM_TRY(hipMemsetAsync(staged, 0, 2 * 8 * kStageCounters, st));
+        if (rank) hipLaunchKernelGGL(k_invert, dim3(grid_for(M)), dim3(256), 0, st, perm, M, rank);
         hipLaunchKernelGGL(k_stage_offsets, dim3(grid_for(nblk + 1)), dim3(256), 0, st, rowptr_p, M, nblk, R, seg_rows, nb_seg, blkoff);
         hipLaunchKernelGGL(k_iota, dim3(grid_for(nnz)), dim3(256), 0, st, idx_in, nnz);
         GESPMM_TRY(rocprim::segmented_radix_sort_pairs(tmp, sort_bytes, colind_p, keys, (const int32_t*)idx_in, idx_out, (size_t)nnz,
@@ -2077,18 +2144,20 @@ hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t
         }
         GESPMM_TRY(hipMemsetAsync(t.hot_cols, 0xFF, (size_t)nblk * H * 4, st));  // unused slots: -1 (the kernel copies nothing for them)
         hipLaunchKernelGGL(k_stage_select, dim3((unsigned)nblk), dim3(256), 0, st, (const int32_t*)blkoff, (const int32_t*)keys,
-                           (const int32_t*)idx_out, H, code, t.hot_cols, t.nhot, staged);
+                           (const int32_t*)idx_out, H, code, t.hot_cols, t.nhot, staged,
+                           StageFill{(const int32_t*)rank, fill_window, R, M, nblk});
         hipLaunchKernelGGL(k_stage_tasks, dim3(grid_for(nblk * kStagedWaves)), dim3(256), 0, st, rowptr_p, M, nblk, R, seg_rows, nb_seg,
                            kStagedWaves, slab_tables ? perm : (const int32_t*)nullptr, t.tasks);
         hipLaunchKernelGGL(k_stage_interleave, dim3(grid_for(nnz)), dim3(256), 0, st, (const int32_t*)code, val_p, rowptr_p, (int)M, nnz,
                            t.ev);
         hipLaunchKernelGGL(k_stage_rowends, dim3(grid_for(M + kStagedPad)), dim3(256), 0, st, rowptr_p, perm, M, nnz, slab_tables ? 1 : 0, t.ev);
         GESPMM_TRY(hipGetLastError());
-        unsigned long long hs[kStageCounters], h = 0;
-        GESPMM_TRY(fetch(hs, (const unsigned long long*)staged, kStageCounters, st));  // (synchronises: the temporaries may go)
-        for (int i = 0; i < kStageCounters; ++i) h += hs[i];
+        unsigned long long hs[2 * kStageCounters], h = 0, hf = 0;
+        GESPMM_TRY(fetch(hs, (const unsigned long long*)staged, 2 * kStageCounters, st));  // (synchronises: the temporaries may go)
+        for (int i = 0; i < kStageCounters; ++i) h += hs[i], hf += hs[kStageCounters + i];
         t.nblocks = (int32_t)nblk;
         t.staged_fraction = (double)h / (double)nnz;
+        t.filled_fraction = (double)hf / (double)nnz;
         return hipSuccess;
     };
     const hipError_t e = body();
@@ -2105,7 +2174,10 @@ hipError_t device_build_staging(int64_t M, int64_t K, int64_t nnz, const int32_t
     out->nblocks = t.nblocks;
     out->waves = waves;
     out->slots = H;
+    out->rows = R;
+    out->fill_window = fill_window;
     out->staged_fraction = t.staged_fraction;
+    out->filled_fraction = t.filled_fraction;
     if (!out->rowptr_s) out->nnz_s = nnz;
     return hipSuccess;
 }

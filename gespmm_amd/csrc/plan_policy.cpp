@@ -413,6 +413,27 @@ int staged_rows_for(const PlanFacts& f, const StagedShape& shape) {
     return shape.rows;  // (64-column tiles: the general kernel's default)
 }
 
+// Fill pass of the staging tables (plan_device.hip: k_stage_select): slots the >= 2 rule leaves free go to columns a block uses ONCE whose own
+// row lies in the block or within this many blocks of it in the plan's order. Such a column costs one fetch either way; staged, the fetch
+// happens at block start, when the neighbouring block that owns the row fetches it too (an L2 hit or a joined miss, and an LDS read instead
+// of a gather in the walk). Square matrices only: a column has a home row there. Measured (profiles/staging_fill/window_sweep.log,
+// us per launch, window 0 / 1 / 2 / 4, seven alternating rounds of 100 launches, spread +-0.1):
+//   com-Amazon-shaped N = 128 at 112 rows per block: 81.27 / 80.31 / 80.27 / 80.25 (filled entries 0 / 0.051 / 0.060 / 0.063 — the blocks
+//     run out of slots, not of near columns); at 96 rows 80.57 / 79.76 / 79.52 / 79.55, at 80 rows 80.66 / - / 80.17 / 80.28.
+//   other widths of the same graph, window 0 / 2 (profiles/staging_fill/other_graphs.log): N = 64 (lane groups) 53.65 / 52.90, N = 100
+//     86.83 / 84.89, N = 200 132.76 / 132.37, N = 256 158.67 / 157.46.
+//   other graphs at N = 128, window 0 / 2: LFR mu = 0.1 153.41 / 153.09, geometric 170.29 / 170.19, small-world 293.77 / 294.16 (filled
+//     0.002-0.005: their single-use columns are far), products-shaped 2598 / 2599 (filled 0.000: the >= 2 rule takes every slot). No class
+//     loses, so one window serves all of them. Two blocks: beyond that nothing more fits.
+// Rows per block stay as staged_rows_for has them: with the fill on, 96 rows gain 0.9 % on the headline graph and lose 3 % on LFR
+// (153.09 -> 157.76), 1.6 % on the small-world graph (294.16 -> 298.96) and 1 % on the geometric one (170.19 -> 171.97).
+// The analysis pays one more scan per tile of a block's keys: plan_ms 3.59 -> 3.64 on the headline graph, inside its run-to-run spread.
+int staged_fill_window(const PlanFacts& f, const StagedShape& shape) {
+    (void)shape;
+    if (f.M != f.K || f.host_analysis) return 0;
+    return 2;
+}
+
 // Which streaming kernel a clustered plan launches (AUTO rule + the caller's choice).
 //   segmented-stream (one continuous gather stream per lane group): ahead of the batch kernel on clustered matrices with
 //     longer rows at one column tile (products-shaped communities, N = 128: 3.95 vs 4.37 ms; N = 16: 1.06 vs 1.17 ms; N = 32:
@@ -650,6 +671,7 @@ extern "C" int gespmm_plan_policy_v2(const gespmm_plan_policy_query* q_in, int64
     {
         const gespmm::StagedShape sh = gespmm::staged_block_shape(q->N);
         a->staged_rows = sh.waves ? gespmm::staged_rows_for(f, sh) : 0;
+        a->staged_fill_window = sh.waves ? gespmm::staged_fill_window(f, sh) : 0;
     }
     // the padded-record kernel (plan.cpp builds its tables after the staged ones: not beside tables that were kept)
     a->build_records = gespmm::records_serves(q->M, q->K, q->N, q->max_degree) && q->nnz > 0 && gespmm::want_record_tables(f, !ad.analyse ? -1.0 : (keep ? q->hits_after : q->hits_before)) &&

@@ -75,6 +75,8 @@ int cluster_levels_for(const PlanFacts& f);
 int cluster_sweeps_for(const PlanFacts& f);  // label-propagation sweeps per level (0 = the clustering's own default)
 int model_points_for(const PlanFacts& f);    // sampled accesses per slice in the L2 model
 int staged_rows_for(const PlanFacts& f, const StagedShape& shape);  // rows per block of the staged-rows kernel
+// blocks on each side of a block whose rows count as near in the fill pass of the staging tables (plan_device.hip: k_stage_select); 0 = no fill
+int staged_fill_window(const PlanFacts& f, const StagedShape& shape);
 
 // ---- after the model: is the clustered order worth its per-launch indirection?
 bool keep_clustered_order(const PlanFacts& f, const AnalysisDecision& a, double hits_before, double hits_after);

@@ -363,7 +363,10 @@ typedef struct gespmm_plan_options {
                                           (N = 128, 256, 512 or 1024 — 256-column tiles bound to XCDs beyond 256; sum reducer, device
                                           analysis; rows beyond 2048 entries go to the long-row pass). AUTO takes it for clustered
                                           matrices with mean degree >= 12 (N = 128) / >= 5 (wider) when >= 60 % (N = 128) / 42 % of
-                                          the entries find their B row staged (csrc/plan_policy.cpp: hold-out audit) */
+                                          the entries find their B row staged (csrc/plan_policy.cpp: hold-out audit). With
+                                          reorder = GESPMM_PLAN_NO_REORDER the plan copies the matrix in the caller's order and builds the
+                                          tables on that (a matrix that arrives clustered). On square matrices slots a block leaves free
+                                          go to single-use columns of near rows (the fill pass: GESPMM_STAGED_FILL) */
 #define GESPMM_PLAN_KERNEL_RECORDS 6    /* padded-record kernel (since 0.3, round 6): 4 <= N <= 64, rows of <= 1024 entries, sum reducer,
                                           max(M, K) * N * 4 < 4 GB — the plan lays its copy of the matrix out as batches of 8-slot row pieces
                                           (one coalesced load per lane, all 8 gathers of a piece in flight at once); AUTO takes it for short
@@ -881,6 +884,9 @@ double gespmm_device_l2_model(const int32_t* rowptr, const int32_t* colind, int6
                               int32_t samples_per_slice, void* stream);
 /* Test hook: task table of a clustered plan (which = 0 wavefront tasks, 1 lane-group tasks), int4 records, HOST memory. */
 int gespmm_plan_debug_tasks(const gespmm_plan* plan, int32_t which, int32_t* out_host, int64_t capacity);
+/* Test hook: the staging lists of a plan's staged-rows tables — blocks x slots column indices (-1: slot not used), HOST memory; info_host =
+ * {blocks, slots per block, rows per block, window of the fill pass (0: none)}. Returns blocks * slots (<= capacity words are copied), 0 without such tables. */
+int64_t gespmm_plan_debug_staging(const gespmm_plan* plan, int32_t* info_host, int32_t* out_host, int64_t capacity);
 
 /*
  * The plan's POLICY by itself (host only, no device, no matrix): what gespmm_plan_create / gespmm_plan_spmm_f32 decide for a
@@ -929,6 +935,8 @@ typedef struct gespmm_plan_policy_answer {
     int32_t records_batches;   /* batches a wavefront task of those tables is cut at */
     int32_t slab_ranges;       /* column-slab tables (GESPMM_PLAN_KERNEL_STAGED_SLABS): ascending column ranges the plan cuts its clustered matrix
                                   into at this width — 0: no such tables (kept once >= 50 % of the entries find their B row staged) */
+    int32_t staged_fill_window; /* fill pass of the staged-rows tables (written when a_bytes covers it): free slots of a block go to columns it
+                                   uses once whose own row lies within this many blocks in the plan's order — 0: no fill pass */
 } gespmm_plan_policy_answer;
 int gespmm_plan_policy(const gespmm_plan_policy_query* q, gespmm_plan_policy_answer* a);  /* the 0.2 layouts (up to staged_fraction / model_sample) */
 int gespmm_plan_policy_v2(const gespmm_plan_policy_query* q, int64_t q_bytes, gespmm_plan_policy_answer* a, int64_t a_bytes);
