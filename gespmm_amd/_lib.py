@@ -127,6 +127,9 @@ EXPORTS = [
     "gespmm_gatv2_score_f32",
     "gespmm_gatv2_score_backward_f32",
     "gespmm_describe_gatv2_score",
+    "gespmm_csr_spmm_max_arg_f32",
+    "gespmm_csr_spmm_max_backward_f32",
+    "gespmm_max_arg_route",
 ]
 
 X16_F16 = 1
@@ -340,6 +343,12 @@ def _load():
     lib.gespmm_gatv2_score_backward_f32.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, p]
     lib.gespmm_describe_gatv2_score.restype = c_int
     lib.gespmm_describe_gatv2_score.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_csr_spmm_max_arg_f32.restype = c_int
+    lib.gespmm_csr_spmm_max_arg_f32.argtypes = [p] * 5 + [c_int64] * 4 + [c_float, p]
+    lib.gespmm_csr_spmm_max_backward_f32.restype = c_int
+    lib.gespmm_csr_spmm_max_backward_f32.argtypes = [p] * 6 + [c_int64] * 4 + [p]
+    lib.gespmm_max_arg_route.restype = c_int
+    lib.gespmm_max_arg_route.argtypes = [c_int64, c_int64, c_int64, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_gat_aggregate_route.restype = c_int
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
@@ -466,6 +475,21 @@ def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):
     if rc < 0:
         raise GespmmError(rc, "gespmm_heads_route")
     return rc, tuple(int(x) for x in geo)
+
+
+def max_arg_route(M, nnz, N, b_align=16, c_align=16):
+    """The lane geometry gespmm_csr_spmm_max_arg_f32 takes for M rows, nnz entries and width N — and gespmm_csr_spmm_max_backward_f32
+    for M = its K columns — with operands on these alignments (gespmm_max_arg_route: host only): ``(V, S, W)``, or ``None`` when there
+    is nothing to launch (M == 0 or N == 0)."""
+    buf = ctypes.create_string_buffer(64)
+    n = lib.gespmm_max_arg_route(int(M), int(nnz), int(N), int(b_align), int(c_align), buf, 64)
+    if n < 0:
+        raise GespmmError(n, "gespmm_max_arg_route")
+    text = buf.value.decode()
+    if text == "form=none":
+        return None
+    out = dict(kv.split("=") for kv in text.split())
+    return int(out["V"]), int(out["S"]), int(out["W"])
 
 
 def edge_dropout_bits(s0, s1, r, c, h):

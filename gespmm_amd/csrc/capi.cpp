@@ -30,6 +30,7 @@
 #include "plan.h"
 #include "sddmm_heads.h"
 #include "spmm_heads.h"
+#include "spmm_max_arg.h"
 #include "spmm_kernels.h"
 #include "workspace.h"
 
@@ -649,6 +650,103 @@ int gespmm_csr_spmm_max_f32(const int32_t* rowptr, const int32_t* colind, const 
     }
     return run_spmm(rowptr, colind, nullptr, B, C, M, K, N, nnz, variant, nullptr, gespmm::kReduceMax, empty_value,
                     stream);
+}
+
+/* The max reducer with argmax and its gradient (gespmm.h; spmm_max_arg.h): one kernel each, the batch-stream walk in the geometry the
+   selector resolves for (segments, width) with strict order and no cache blocking. S segments (M forward, K backward), T rows of the
+   gathered operand (K forward, M backward). There is no second route: what the kernels' 32-bit byte offsets cannot address is refused. */
+static int max_arg_sizes(int64_t M, int64_t K, int64_t N, int64_t nnz) {
+    const int rc = gespmm::check_csr_sizes(M, K, N, nnz, 0);
+    if (rc != 0) return rc;
+    if ((uint64_t)K * (uint64_t)N * 4ull >= (1ull << 32) || (uint64_t)M * (uint64_t)N * 4ull >= (1ull << 32)) return GESPMM_ERANGE;
+    return 0;
+}
+
+static bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    if (!a || !b || a_bytes == 0 || b_bytes == 0) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// align: what the three dense operands can be addressed with. dry_run: the geometry alone.
+static int max_arg_geometry(int64_t S, int64_t T, int64_t N, int64_t nnz, int align, Geometry* geo) {
+    const int flags = kFlagBatchStream | kFlagStrictOrder | kFlagNoSlabBlocked;
+    const StreamQuery q = {S, T, N, nnz, vec_limit(N, align), GESPMM_VARIANT_AUTO, flags, kReduceMax, nullptr, nullptr, false, nullptr};
+    StreamLaunch r;
+    const int rc = resolve_stream_launch(q, &r);
+    if (rc != 0) return GESPMM_EINVAL;
+    if (!gespmm::max_arg_geometry_served(r.sel.geo)) return GESPMM_ERANGE;
+    *geo = r.sel.geo;
+    return 0;
+}
+
+int gespmm_csr_spmm_max_arg_f32(const int32_t* rowptr, const int32_t* colind, const float* B, float* C, int32_t* arg, int64_t M, int64_t K,
+                                int64_t N, int64_t nnz, float empty_value, void* stream) {
+    int rc = max_arg_sizes(M, K, N, nnz);
+    if (rc == GESPMM_EINVAL || std::isnan(empty_value)) return GESPMM_EINVAL;
+    if (rc != 0) return rc;
+    if (M == 0 || N == 0) return 0;
+    if ((rc = check_pointers({{rowptr, 4, true}, {C, 4, true}, {arg, 4, true}, {colind, 4, nnz != 0}, {B, 4, nnz != 0}})) != 0) return rc;
+    const uint64_t b_bytes = (uint64_t)K * (uint64_t)N * 4, c_bytes = (uint64_t)M * (uint64_t)N * 4;
+    if (ranges_overlap(C, c_bytes, B, b_bytes) || ranges_overlap(arg, c_bytes, B, b_bytes) || ranges_overlap(C, c_bytes, arg, c_bytes))
+        return GESPMM_EINVAL;
+    Geometry geo = {};
+    const int align = std::min(nnz != 0 ? pointer_alignment(B) : 16, min_alignment(C, arg));
+    if ((rc = max_arg_geometry(M, K, N, nnz, align, &geo)) != 0) return rc;
+    gespmm::MaxArgArgs a = {};
+    a.ptr = rowptr;
+    a.ind = colind;
+    a.src = B;
+    a.dst = C;
+    a.arg_out = arg;
+    a.S = (int32_t)M;
+    a.N = (int32_t)N;
+    a.empty = empty_value;
+    return (int)gespmm::launch_spmm_max_arg(a, geo, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_csr_spmm_max_backward_f32(const int32_t* colptr, const int32_t* rowind, const int32_t* order, const int32_t* arg,
+                                     const float* grad_out, float* grad_B, int64_t M, int64_t K, int64_t N, int64_t nnz, void* stream) {
+    int rc = max_arg_sizes(M, K, N, nnz);
+    if (rc != 0) return rc;
+    if (K == 0 || N == 0) return 0;
+    if ((rc = check_pointers({{colptr, 4, true}, {grad_B, 4, true}, {rowind, 4, nnz != 0}, {order, 4, nnz != 0}, {arg, 4, nnz != 0},
+                              {grad_out, 4, nnz != 0}})) != 0)
+        return rc;
+    const uint64_t g_bytes = (uint64_t)K * (uint64_t)N * 4, o_bytes = (uint64_t)M * (uint64_t)N * 4;
+    if (ranges_overlap(grad_B, g_bytes, grad_out, o_bytes) || ranges_overlap(grad_B, g_bytes, arg, o_bytes)) return GESPMM_EINVAL;
+    Geometry geo = {};
+    const int align = std::min(nnz != 0 ? min_alignment(arg, grad_out) : 16, pointer_alignment(grad_B));
+    if ((rc = max_arg_geometry(K, M, N, nnz, align, &geo)) != 0) return rc;
+    gespmm::MaxArgArgs a = {};
+    a.ptr = colptr;
+    a.ind = rowind;
+    a.order = order;
+    a.src = grad_out;
+    a.arg_in = arg;
+    a.dst = grad_B;
+    a.S = (int32_t)K;
+    a.N = (int32_t)N;
+    return (int)gespmm::launch_spmm_max_backward(a, geo, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_max_arg_route(int64_t M, int64_t nnz, int64_t N, int b_align, int c_align, char* out, int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    for (const int al : {b_align, c_align})
+        if (al < 4 || (al & (al - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_csr_sizes(M, 1, N, nnz, 0);
+    if (rc != 0) return rc;
+    int n;
+    if (M == 0 || N == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else {
+        Geometry geo = {};
+        // (the lane geometry does not depend on the rows of the gathered operand, once they are within the 32-bit offsets)
+        const int rcg = max_arg_geometry(M, 1, N, nnz, std::min(std::min(b_align, c_align), 16), &geo);
+        if (rcg != 0) return rcg;
+        n = snprintf(out, (size_t)capacity, "V=%d S=%d W=%d", geo.vec, geo.strips, geo.group);
+    }
+    return describe_result(n, capacity);
 }
 
 int64_t gespmm_csr_spmm_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant,

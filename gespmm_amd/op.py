@@ -47,12 +47,16 @@ fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` 
 ``GATSoftmaxFunction`` is the first two in one: the softmax of el[row] + er[col] with no score array (``GATConv(fused_score=True)``).
 ``EdgeDropoutFunction`` is dropout on alpha with a mask recomputed from (seed, row, column, head), never stored (``GATConv(dropout=p)``).
 ``GATAggregateFunction`` is all three in one: no score and no attention array, nothing of size nnz x H saved (``GATConv(fused_aggregate=True)``).
+GraphSAGE (extension): ``SpmmMaxFunction`` is the max over neighbours with a gradient — the forward saves the winning CSR position of
+every output word (``spmm.csr_spmm_max_arg``), the backward adds ``grad_out`` where that position sits (``spmm.csr_spmm_max_backward``) —
+and ``SAGEConv`` DGL's layer of that name with the ``mean``, ``gcn`` and ``pool`` aggregators.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 from torch.nn import Parameter
 
 from . import sddmm as _sddmm
@@ -742,3 +746,95 @@ class GATv2Conv(torch.nn.Module):
 
     def __repr__(self):
         return "%s(%d, %d, heads=%d)" % (type(self).__name__, self.in_channels, self.out_channels, self.heads)
+
+
+class SpmmMaxFunction(torch.autograd.Function):
+    """out[r, :] = max over the entries of row r of feat[col, :], with a gradient (``spmm.csr_spmm_max_arg`` / ``csr_spmm_max_backward``).
+
+        SpmmMaxFunction.apply(rowptr, colind, colptr, rowind, csc_order, feat, empty_value=-10000.0)
+
+    The forward saves ``arg`` (int32 [M, N]: the CSR position that won each output word, -1 where none did) and nothing else — not
+    ``feat``. The backward gives each word of ``grad_out`` to the ONE entry ``arg`` names: grad_feat[k, c] is the sum, in CSC order,
+    of grad_out[r, c] over the rows that chose an entry of node k; words nobody chose (and rows that kept ``empty_value``) pass
+    nothing on. Among equal values the first entry of the row gets the gradient. ``csc_order`` (int32) maps a CSC position to its CSR
+    position, as in the GAT functions. Index tensors get no gradient; once differentiable; fp32 only."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, csc_order, feat, empty_value=-10000.0):
+        out, arg = _spmm.csr_spmm_max_arg(rowptr, colind, feat.contiguous(), empty_value=empty_value)
+        ctx.save_for_backward(colptr, rowind, csc_order, arg)
+        ctx.K = feat.shape[0]
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        colptr, rowind, csc_order, arg = ctx.saved_tensors
+        grad_feat = None
+        if ctx.needs_input_grad[5]:
+            grad_feat = _spmm.csr_spmm_max_backward(colptr, rowind, csc_order, arg, grad_out.contiguous(), ctx.K)
+        return None, None, None, None, None, grad_feat, None
+
+
+class SAGEConv(torch.nn.Module):
+    """GraphSAGE layer (Hamilton et al., 2017) with the constructor and semantics of DGL's ``SAGEConv``, on the library's ops:
+
+        mean   fc_self(h) + fc_neigh(D^-1 A h)                    the fused product with row_scale = 1 / deg (``FusedGCNFunction``)
+        gcn    fc_neigh((A h + h) / (deg + 1))                    ``SPMMFunction``
+        pool   fc_self(h) + fc_neigh(max_nbr relu(fc_pool(h)))    ``SpmmMaxFunction`` with empty_value = 0: after the relu, 0 never
+                                                                  changes a non-empty row, and a row without neighbours gets DGL's 0
+
+    with h = feat_drop(x), deg the row's entry count (rows without entries aggregate 0), then ``activation``, then ``norm``.
+    ``forward(x, rowptr, colind, colptr, rowind, csc_order)`` takes the square pattern in both orders; ``csc_order`` (int32: CSC
+    position -> CSR position, ``graphs.transpose_csr(..., return_order=True)``) is read by ``pool`` alone and may be None otherwise.
+    ``lstm`` is not served (ValueError). fp32 only."""
+
+    def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0.0, bias=True, norm=None, activation=None):
+        super().__init__()
+        if aggregator_type not in ("mean", "gcn", "pool"):
+            raise ValueError("aggregator_type must be 'mean', 'gcn' or 'pool', got %r%s"
+                             % (aggregator_type, " (the lstm aggregator is not served)" if aggregator_type == "lstm" else ""))
+        self.in_feats, self.out_feats, self.aggregator_type = in_feats, out_feats, aggregator_type
+        self.norm, self.activation = norm, activation
+        self.feat_drop = torch.nn.Dropout(feat_drop)
+        if aggregator_type == "pool":
+            self.fc_pool = torch.nn.Linear(in_feats, in_feats)
+        if aggregator_type != "gcn":
+            self.fc_self = torch.nn.Linear(in_feats, out_feats, bias=bias)
+        self.fc_neigh = torch.nn.Linear(in_feats, out_feats, bias=bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        for name in ("fc_pool", "fc_self", "fc_neigh"):
+            fc = getattr(self, name, None)
+            if fc is not None:
+                torch.nn.init.xavier_uniform_(fc.weight, gain=gain)
+
+    def forward(self, x, rowptr, colind, colptr, rowind, csc_order=None):
+        n = rowptr.numel() - 1
+        if x.dim() != 2 or x.shape[0] != n or colptr.numel() - 1 != n:
+            raise ValueError("SAGEConv needs a square pattern and x of [%d, in_feats]" % n)
+        h = self.feat_drop(x)
+        degree = torch.diff(rowptr).to(torch.float32)
+        if self.aggregator_type == "mean":
+            inv_deg = torch.where(degree > 0, 1 / degree, torch.zeros_like(degree))
+            h_neigh = FusedGCNFunction.apply(rowptr, colind, colptr, rowind, h, None, inv_deg, None)
+            out = self.fc_self(h) + self.fc_neigh(h_neigh)
+        elif self.aggregator_type == "gcn":
+            h_sum = SPMMFunction.apply(rowptr, colind, colptr, rowind, h.contiguous())
+            out = self.fc_neigh((h_sum + h) / (degree + 1).unsqueeze(1))
+        else:
+            if csc_order is None:
+                raise ValueError("the pool aggregator needs csc_order (graphs.transpose_csr(..., return_order=True), int32)")
+            m = torch.relu(self.fc_pool(h))
+            h_neigh = SpmmMaxFunction.apply(rowptr, colind, colptr, rowind, csc_order, m, 0.0)
+            out = self.fc_self(h) + self.fc_neigh(h_neigh)
+        if self.activation is not None:
+            out = self.activation(out)
+        if self.norm is not None:
+            out = self.norm(out)
+        return out
+
+    def __repr__(self):
+        return "%s(%d, %d, %s)" % (type(self).__name__, self.in_feats, self.out_feats, self.aggregator_type)

@@ -587,6 +587,69 @@ def csr_spmm_max(rowptr, colind, dense, empty_value=-10000.0, variant=_lib.VARIA
     return out
 
 
+def _result(t, name, dtype, shape, dev, inputs):
+    """A caller's result tensor: contiguous ``dtype`` of ``shape`` on ``dev`` that overlaps no input."""
+    _need(t, name, dtype, len(shape))
+    if tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError("%s must be %s%s on %s" % (name, dtype, list(shape), dev))
+    if any(_overlaps(t, x) for x in inputs):
+        raise ValueError("%s must not overlap an input" % name)
+    return t
+
+
+def csr_spmm_max_arg(rowptr, colind, dense, empty_value=-10000.0, out=None, arg=None):
+    """``csr_spmm_max`` that also says which neighbour won (gespmm_csr_spmm_max_arg_f32): returns ``(out, arg)``, f32[M, N] and
+    int32[M, N]. Per output word ONE chain over the row's entries in CSR order, ``if dense[colind[p], c] > acc: acc, a = that, p`` from
+    ``(empty_value, -1)``: ``arg`` is a CSR POSITION (not a column id), the first of equal values wins (+0 == -0), NaN and values
+    ``<= empty_value`` never win. ``out`` has the bits of ``csr_spmm_max`` wherever no zeros of both signs compete for a maximum.
+    fp32 only; ``out=`` / ``arg=`` reuse the caller's tensors."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    _need(dense, "dense", torch.float32, 2)
+    dev = _same_device(dense, rowptr, colind)
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have M+1 >= 1 entries")
+    empty_value = float(empty_value)
+    if empty_value != empty_value:
+        raise ValueError("empty_value must not be NaN")
+    M = rowptr.numel() - 1
+    K, N = dense.shape
+    out = torch.empty((M, N), dtype=torch.float32, device=dev) if out is None else _result(out, "out", torch.float32, (M, N), dev, (dense,))
+    arg = torch.empty((M, N), dtype=torch.int32, device=dev) if arg is None else _result(arg, "arg", torch.int32, (M, N), dev, (dense, out))
+    with _on_device(dev):
+        rc = lib.gespmm_csr_spmm_max_arg_f32(_ptr(rowptr), _ptr(colind), _ptr(dense), _ptr(out), _ptr(arg), M, K, N, colind.numel(),
+                                             empty_value, _stream(dev))
+    check(rc, "gespmm_csr_spmm_max_arg_f32")
+    return out, arg
+
+
+def csr_spmm_max_backward(colptr, rowind, order, arg, grad_out, K, out=None):
+    """The gradient of ``csr_spmm_max_arg`` for ``dense`` (gespmm_csr_spmm_max_backward_f32): f32[K, N] with
+    ``out[k, c] = sum of grad_out[r, c] over the entries (r, k) whose position arg[r, c] names`` — per word one fp32 add chain from +0 in
+    CSC order, no atomics: bit-reproducible. ``(colptr, rowind)`` are the CSC arrays of the pattern and ``order`` (int32) maps a CSC
+    position to its CSR position: ``graphs.transpose_csr(..., return_order=True)``, cast to int32. Nodes no row chose get +0."""
+    _need(colptr, "colptr", torch.int32, 1)
+    _need(rowind, "rowind", torch.int32, 1)
+    _need(order, "order", torch.int32, 1)
+    _need(grad_out, "grad_out", torch.float32, 2)
+    _need(arg, "arg", torch.int32, 2)
+    dev = _same_device(grad_out, colptr, rowind, order, arg)
+    K = int(K)
+    if colptr.numel() != K + 1:
+        raise ValueError("colptr must have K + 1 = %d entries" % (K + 1))
+    if order.numel() != rowind.numel():
+        raise ValueError("order and rowind must have the same length")
+    if tuple(arg.shape) != tuple(grad_out.shape):
+        raise ValueError("arg must have the shape of grad_out, %s" % (list(grad_out.shape),))
+    M, N = grad_out.shape
+    out = torch.empty((K, N), dtype=torch.float32, device=dev) if out is None else _result(out, "out", torch.float32, (K, N), dev, (grad_out, arg))
+    with _on_device(dev):
+        rc = lib.gespmm_csr_spmm_max_backward_f32(_ptr(colptr), _ptr(rowind), _ptr(order), _ptr(arg), _ptr(grad_out), _ptr(out), M, K, N,
+                                                  rowind.numel(), _stream(dev))
+    check(rc, "gespmm_csr_spmm_max_backward_f32")
+    return out
+
+
 def csr2csc(rowptr, colind, colptr, rowind, csr_data):
     """Fill ``colptr`` / ``rowind`` in place with the CSC form of CSR(rowptr, colind)
     and return the values in CSC order. Mirrors spmm.cpp:70-93 (whose CUDA

@@ -13,6 +13,9 @@
  *                               spmm_cuda_no_edge_value()     pytorch-custom/spmm_kernel.cu:175-207
  *                               XTopoCsrmm<float>()           dgl-custom/binary_reduce_sum.cu:310-335
  *   gespmm_csr_spmm_max_f32  <- XTopoCsrmmmax<float>()        dgl-custom/binary_reduce_max.cu:182-207
+ *   gespmm_csr_spmm_max_arg_f32 / gespmm_csr_spmm_max_backward_f32 / gespmm_max_arg_route <- (new) the same reducer with the
+ *                               winning CSR position per output word, and the gradient that position gives: what the `pool`
+ *                               aggregator of dgl-custom/benchmark/sage/sage_dgl.py needs to train
  *   gespmm_dgl_csrmm_{sum,max}_f32  <- the same two, with exactly their argument lists
  *   gespmm_csr_spmm_workspace_bytes / gespmm_csr_spmm_f32_ws  <- (new) caller-owned scratch, no reference counterpart
  *   gespmm_select_variant    <- the N-based 3-way dispatch    pytorch-custom/spmm_kernel.cu:186-206,437-457
@@ -134,6 +137,48 @@ int gespmm_csr_spmm_max_f32(const int32_t* rowptr, const int32_t* colind,
                             const float* B, float* C,
                             int64_t M, int64_t K, int64_t N, int64_t nnz,
                             float empty_value, int variant, void* stream);
+
+/*
+ * The max reducer WITH ARGMAX, and its gradient. Forward — one sequential chain per output word (r, c), whatever the lane geometry:
+ *
+ *     acc = empty_value; a = -1
+ *     for p = rowptr[r] .. rowptr[r + 1] - 1, ascending:  b = B[colind[p] N + c];  if (b > acc) { acc = b; a = p; }
+ *     C[r, c] = acc;  arg[r, c] = a
+ *
+ * arg is int32 [M, N] and holds a CSR POSITION, not a column id: repeated (row, column) entries stay distinguishable. Among equal values
+ * the smallest position wins; +0 and -0 compare equal, so the first one wins and keeps its sign bit; NaN never wins; a value <=
+ * empty_value never wins, and a row that is empty or holds only such values gives (empty_value, -1). C has the bits of
+ * gespmm_csr_spmm_max_f32 on every input where no zeros of both signs compete for a maximum (there that entry's fmaxf chain is
+ * undefined; this one is not). Every word of C and arg is written.
+ *
+ * Backward — for node k and column c, over the CSC arrays of the pattern, CSC position q being CSR entry order[q] (what
+ * gespmm_csr2csc_f32 gives when csr_val holds the positions; the csc_order of the GAT entries):
+ *
+ *     g = +0
+ *     for q = colptr[k] .. colptr[k + 1] - 1, ascending:  r = rowind[q];  if (arg[r N + c] == order[q]) g = g + grad_out[r N + c]
+ *     grad_B[k, c] = g
+ *
+ * One plain fp32 add chain per output word in CSC order: bit-reproducible, no atomics, no workspace. Every word of grad_B is written,
+ * +0 for a node nobody chose. The VALUES of order and arg are trusted (they are compared, never used as an address); rowind must lie
+ * in [0, M) as colind in [0, K).
+ *
+ * One kernel each: the batch-stream walk (a wavefront owns a contiguous range of segments, 64-entry index tiles through LDS, W lanes per
+ * segment with V floats per lane) in the geometry gespmm_max_arg_route prints. 32-bit byte offsets and no second route; fp32 only; no
+ * plan form; no long-row pass (a hub segment is walked by one lane group). No allocation, no host synchronisation: capturable.
+ * Checks, in this order: a negative size, a NaN empty_value -> GESPMM_EINVAL; M, K, N, nnz beyond what gespmm_csr_spmm_f32 takes, or
+ * K N 4 >= 2^32 or M N 4 >= 2^32 -> GESPMM_ERANGE; no segment or N == 0 (forward: M == 0, backward: K == 0) -> 0; a NULL operand
+ * (colind and B, or rowind, order, arg and grad_out, may be NULL when nnz == 0) -> GESPMM_EINVAL; a pointer not 4-byte aligned ->
+ * GESPMM_EALIGN; a result overlapping a dense operand -> GESPMM_EINVAL. nnz == 0 writes every word: (empty_value, -1) or +0. Dense
+ * operands that are only 4- or 8-byte aligned, or an N the vector width does not divide, take a narrower vector — same bits.
+ */
+int gespmm_csr_spmm_max_arg_f32(const int32_t* rowptr, const int32_t* colind, const float* B, float* C, int32_t* arg, int64_t M, int64_t K,
+                                int64_t N, int64_t nnz, float empty_value, void* stream);
+int gespmm_csr_spmm_max_backward_f32(const int32_t* colptr, const int32_t* rowind, const int32_t* order, const int32_t* arg,
+                                     const float* grad_out, float* grad_B, int64_t M, int64_t K, int64_t N, int64_t nnz, void* stream);
+/* Host only: the lane geometry of the two calls above as text, "V=.. S=.. W=.." ("form=none" when M == 0 or N == 0), for M segments (the
+ * backward: K) of mean length nnz / M at width N. b_align: largest power of two (>= 4) dividing the address of the gathered operands (B;
+ * arg and grad_out), c_align: of the results (C and arg; grad_B). Returns the length written or a GESPMM_E* code. */
+int gespmm_max_arg_route(int64_t M, int64_t nnz, int64_t N, int b_align, int c_align, char* out, int64_t capacity);
 
 /* The variant `GESPMM_VARIANT_AUTO` resolves to for this shape (pure host logic). */
 int gespmm_select_variant(int64_t M, int64_t nnz, int64_t N);
