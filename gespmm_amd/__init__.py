@@ -8,15 +8,16 @@ Layout (only what the hot path needs):
   spmm.py    mirror of the reference's pybind module `spmm`   (pytorch-custom/spmm.cpp:96-101)
   sddmm.py   mirror of the reference's pybind module `sddmm`  (pytorch-custom/sddmm.cpp:62-67)
   softmax.py edge softmax over CSR rows, forward and backward  (extension: no reference counterpart)
-  op.py      SPMMFunction / GCNConv                           (pytorch-custom/op.py); attention: the MultiHead functions, GATConv, GATv2Conv; GraphSAGE: SpmmMaxFunction, SAGEConv
+  attention.py fused dot-product attention over the edges, forward and backward (extension: no reference counterpart)
+  op.py      SPMMFunction / GCNConv                           (pytorch-custom/op.py); attention: the MultiHead functions, GATConv, GATv2Conv, DotAttentionFunction, TransformerConv; GraphSAGE: SpmmMaxFunction, SAGEConv
   graphs.py  MatrixMarket loading via the C ABI + seeded synthetic stand-in graphs
   dist.py    1-D row partition + B exchange over torch.distributed (RCCL)
 
 There is no CPU compute path anywhere in this package.
 """
 from . import _lib  # noqa: F401  (loads libgespmm.so, raises if it is not built)
-from . import spmm, sddmm, softmax, graphs  # noqa: F401
-from .op import SPMMFunction, FusedGCNFunction, MultiHeadSPMMFunction, MultiHeadSDDMMFunction, EdgeSoftmaxFunction, EdgeDropoutFunction, GATSoftmaxFunction, GATAggregateFunction, GATv2ScoreFunction, GCNConv, GATConv, GATv2Conv, SpmmMaxFunction, SAGEConv  # noqa: F401
+from . import spmm, sddmm, softmax, attention, graphs  # noqa: F401
+from .op import SPMMFunction, FusedGCNFunction, MultiHeadSPMMFunction, MultiHeadSDDMMFunction, EdgeSoftmaxFunction, EdgeDropoutFunction, GATSoftmaxFunction, GATAggregateFunction, GATv2ScoreFunction, GCNConv, GATConv, GATv2Conv, SpmmMaxFunction, SAGEConv, DotAttentionFunction, TransformerConv  # noqa: F401
 
-__all__ = ["spmm", "sddmm", "softmax", "graphs", "SPMMFunction", "FusedGCNFunction", "MultiHeadSPMMFunction", "MultiHeadSDDMMFunction",
-           "EdgeSoftmaxFunction", "EdgeDropoutFunction", "GATSoftmaxFunction", "GATAggregateFunction", "GATv2ScoreFunction", "GCNConv", "GATConv", "GATv2Conv", "SpmmMaxFunction", "SAGEConv"]
+__all__ = ["spmm", "sddmm", "softmax", "attention", "graphs", "SPMMFunction", "FusedGCNFunction", "MultiHeadSPMMFunction", "MultiHeadSDDMMFunction",
+           "EdgeSoftmaxFunction", "EdgeDropoutFunction", "GATSoftmaxFunction", "GATAggregateFunction", "GATv2ScoreFunction", "GCNConv", "GATConv", "GATv2Conv", "SpmmMaxFunction", "SAGEConv", "DotAttentionFunction", "TransformerConv"]

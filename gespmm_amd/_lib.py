@@ -127,6 +127,13 @@ EXPORTS = [
     "gespmm_gatv2_score_f32",
     "gespmm_gatv2_score_backward_f32",
     "gespmm_describe_gatv2_score",
+    "gespmm_dot_attention_f32",
+    "gespmm_dot_attention_dropout_f32",
+    "gespmm_dot_attention_backward_q_f32",
+    "gespmm_dot_attention_backward_q_dropout_f32",
+    "gespmm_dot_attention_backward_kv_f32",
+    "gespmm_dot_attention_backward_kv_dropout_f32",
+    "gespmm_describe_dot_attention",
     "gespmm_csr_spmm_max_arg_f32",
     "gespmm_csr_spmm_max_backward_f32",
     "gespmm_max_arg_route",
@@ -343,6 +350,18 @@ def _load():
     lib.gespmm_gatv2_score_backward_f32.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, p]
     lib.gespmm_describe_gatv2_score.restype = c_int
     lib.gespmm_describe_gatv2_score.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_dot_attention_f32.restype = c_int
+    lib.gespmm_dot_attention_f32.argtypes = [p] * 7 + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_dot_attention_dropout_f32.restype = c_int
+    lib.gespmm_dot_attention_dropout_f32.argtypes = [p] * 7 + [c_int64] * 5 + [c_float, c_float, p, p]
+    for f in (lib.gespmm_dot_attention_backward_q_f32, lib.gespmm_dot_attention_backward_kv_f32):
+        f.restype = c_int
+        f.argtypes = [p] * 10 + [c_int64] * 5 + [c_float, p]
+    for f in (lib.gespmm_dot_attention_backward_q_dropout_f32, lib.gespmm_dot_attention_backward_kv_dropout_f32):
+        f.restype = c_int
+        f.argtypes = [p] * 10 + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_describe_dot_attention.restype = c_int
+    lib.gespmm_describe_dot_attention.argtypes = [c_int64] * 5 + [c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_csr_spmm_max_arg_f32.restype = c_int
     lib.gespmm_csr_spmm_max_arg_f32.argtypes = [p] * 5 + [c_int64] * 4 + [c_float, p]
     lib.gespmm_csr_spmm_max_backward_f32.restype = c_int
@@ -463,6 +482,23 @@ def describe_gatv2_score(M, nnz, H, F, xl_align=16, xr_align=16, att_align=16):
     n = lib.gespmm_describe_gatv2_score(int(M), int(nnz), int(H), int(F), int(xl_align), int(xr_align), int(att_align), buf, 96)
     if n < 0:
         raise GespmmError(n, "gespmm_describe_gatv2_score")
+    out = dict(kv.split("=") for kv in buf.value.decode().split())
+    return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
+
+
+ERR_UNSUPPORTED = -7
+DOT_ATTENTION_MAX_F = 512
+
+
+def describe_dot_attention(M, K, H, F, nnz, q_align=16, k_align=16, v_align=16):
+    """The lane geometry of gespmm_dot_attention_f32 and its two backward passes for these sizes and operand alignments
+    (gespmm_describe_dot_attention: host only) — a dict ``{"V": floats per load, "W": lanes per (segment, head) pair}``;
+    ``{"route": "unsupported"}`` when F > 512 (no kernel), ``{"route": "zeros"}`` when F == 0 and ``{"form": "none"}`` when nnz == 0.
+    V and W fix the dot's summation order; the least aligned dense operand of a launch decides V."""
+    buf = ctypes.create_string_buffer(96)
+    n = lib.gespmm_describe_dot_attention(int(M), int(K), int(H), int(F), int(nnz), int(q_align), int(k_align), int(v_align), buf, 96)
+    if n < 0:
+        raise GespmmError(n, "gespmm_describe_dot_attention")
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
 

@@ -26,6 +26,7 @@
 #include "edge_softmax.h"
 #include "gat_aggregate.h"
 #include "gat_backward.h"
+#include "dot_attention.h"
 #include "gatv2_score.h"
 #include "plan.h"
 #include "sddmm_heads.h"
@@ -474,6 +475,23 @@ int check_gatv2_sizes(int64_t S, int64_t T, int64_t H, int64_t F, int64_t nnz, f
     return check_dense_words(T * H, F);
 }
 
+// ---- the fused dot-product attention (gespmm.h: gespmm_dot_attention_f32 and its backward; dot_attention.h). Sizes alone: what makes no
+// sense (a scale that is no finite number and a bad p with it), what is too large for 32-bit word positions — the GATv2 ladder, and the
+// [M, H, 2] words of stats — then the slice no kernel serves.
+int check_dot_attention_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, const float* p) {
+    int rc = check_gatv2_sizes(M, K, H, F, nnz, scale);
+    if (p) rc = check_dropout_p(rc, *p);
+    if (rc != 0) return rc;
+    if (const int rcs = check_dense_words(M * H, 2)) return rcs;  // (M H <= kSddmmMaxNnz: no overflow)
+    return F > kDotAttentionMaxF ? GESPMM_ERR_UNSUPPORTED : 0;
+}
+
+int least_alignment(std::initializer_list<const void*> ps) {
+    int align = 16;
+    for (const void* p : ps) align = std::min(align, pointer_alignment(p));
+    return align;
+}
+
 }  // namespace gespmm
 
 namespace {
@@ -501,6 +519,7 @@ const char* gespmm_error_string(int code) {
         case GESPMM_EIO: return "gespmm: file not found or unreadable";
         case GESPMM_EFORMAT: return "gespmm: could not process Matrix Market banner or size line";
         case GESPMM_ENOMEM: return "gespmm: host allocation failed";
+        case GESPMM_ERR_UNSUPPORTED: return "gespmm: no kernel serves this shape (fused dot-product attention: F <= 512)";
     }
     if (code > 0) return hipGetErrorString((hipError_t)code);
     return "gespmm: unknown error code";
@@ -1319,6 +1338,145 @@ int gespmm_describe_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, in
         const gespmm::Gatv2ScoreLaunch r = gespmm::resolve_gatv2_score(M, nnz, H, F, xl_align > 16 ? 16 : xl_align,
                                                                        xr_align > 16 ? 16 : xr_align, att_align > 16 ? 16 : att_align);
         n = snprintf(out, (size_t)capacity, "V=%d W=%d epw=%d", r.V, r.W, r.epw);
+    }
+    return describe_result(n, capacity);
+}
+
+/* Fused scaled dot-product attention over a pattern and its backward (gespmm.h; dot_attention.h): one kernel each, nothing of size nnz
+   but the index arrays. The ladder is check_dot_attention_sizes, nnz == 0, F == 0, then the pointers. */
+static int zero_fill(std::initializer_list<std::pair<float*, size_t>> outs, hipStream_t st) {
+    for (const auto& o : outs)
+        if (!o.first && o.second) return GESPMM_EINVAL;
+    for (const auto& o : outs)
+        if (reinterpret_cast<uintptr_t>(o.first) % 4 != 0) return GESPMM_EALIGN;
+    for (const auto& o : outs) {
+        if (o.second == 0) continue;
+        const hipError_t e = hipMemsetAsync(o.first, 0, o.second * sizeof(float), st);
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+static int dot_attention_entry(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v, float* out,
+                               float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, const float* p,
+                               const void* seed, void* stream) {
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, scale, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {  // every row is empty (F == 0: there is nothing to attend with): every word of the results is still written
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill({{out, (size_t)(M * H * F)}, {stats, (size_t)(M * H * 2)}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {q, 4, true}, {k, 4, true}, {v, 4, true}, {out, 4, true},
+                                        {stats, 8, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({q, k, v, out});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_dot_attention(rowptr, colind, q, k, v, out, stats, M, K, H, F, nnz, scale,
+                                             gespmm::resolve_dot_attention(F, a, a, a), p ? &dropout : nullptr, st);
+}
+
+int gespmm_dot_attention_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v, float* out,
+                             float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream) {
+    return dot_attention_entry(rowptr, colind, q, k, v, out, stats, M, K, H, F, nnz, scale, nullptr, nullptr, stream);
+}
+
+int gespmm_dot_attention_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v, float* out,
+                                     float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                     const void* seed, void* stream) {
+    return dot_attention_entry(rowptr, colind, q, k, v, out, stats, M, K, H, F, nnz, scale, &p, seed, stream);
+}
+
+static int dot_attention_backward_q_entry(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v,
+                                          const float* stats, const float* out, const float* grad_out, float* delta, float* grad_q,
+                                          int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, const float* p,
+                                          const void* seed, void* stream) {
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, scale, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill({{delta, (size_t)(M * H)}, {grad_q, (size_t)(M * H * F)}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {q, 4, true}, {k, 4, true}, {v, 4, true}, {stats, 8, true},
+                                        {out, 4, true}, {grad_out, 4, true}, {delta, 4, true}, {grad_q, 4, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({q, k, v, out, grad_out, grad_q});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_dot_attention_backward_q(rowptr, colind, q, k, v, stats, out, grad_out, delta, grad_q, M, K, H, F, nnz, scale,
+                                                        gespmm::resolve_dot_attention(F, a, a, a), p ? &dropout : nullptr, st);
+}
+
+int gespmm_dot_attention_backward_q_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v,
+                                        const float* stats, const float* out, const float* grad_out, float* delta, float* grad_q, int64_t M,
+                                        int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream) {
+    return dot_attention_backward_q_entry(rowptr, colind, q, k, v, stats, out, grad_out, delta, grad_q, M, K, H, F, nnz, scale, nullptr, nullptr,
+                                          stream);
+}
+
+int gespmm_dot_attention_backward_q_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v,
+                                                const float* stats, const float* out, const float* grad_out, float* delta, float* grad_q,
+                                                int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p, const void* seed,
+                                                void* stream) {
+    return dot_attention_backward_q_entry(rowptr, colind, q, k, v, stats, out, grad_out, delta, grad_q, M, K, H, F, nnz, scale, &p, seed, stream);
+}
+
+static int dot_attention_backward_kv_entry(const int32_t* colptr, const int32_t* rowind, const float* q, const float* k, const float* v,
+                                           const float* stats, const float* delta, const float* grad_out, float* grad_k, float* grad_v,
+                                           int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, const float* p,
+                                           const void* seed, void* stream) {
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, scale, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill({{grad_k, (size_t)(K * H * F)}, {grad_v, (size_t)(K * H * F)}}, st);
+    }
+    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {q, 4, true}, {k, 4, true}, {v, 4, true}, {stats, 8, true},
+                                        {delta, 4, true}, {grad_out, 4, true}, {grad_k, 4, true}, {grad_v, 4, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({q, k, v, grad_out, grad_k, grad_v});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_dot_attention_backward_kv(colptr, rowind, q, k, v, stats, delta, grad_out, grad_k, grad_v, M, K, H, F, nnz,
+                                                         scale, gespmm::resolve_dot_attention(F, a, a, a), p ? &dropout : nullptr, st);
+}
+
+int gespmm_dot_attention_backward_kv_f32(const int32_t* colptr, const int32_t* rowind, const float* q, const float* k, const float* v,
+                                         const float* stats, const float* delta, const float* grad_out, float* grad_k, float* grad_v,
+                                         int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream) {
+    return dot_attention_backward_kv_entry(colptr, rowind, q, k, v, stats, delta, grad_out, grad_k, grad_v, M, K, H, F, nnz, scale, nullptr,
+                                           nullptr, stream);
+}
+
+int gespmm_dot_attention_backward_kv_dropout_f32(const int32_t* colptr, const int32_t* rowind, const float* q, const float* k, const float* v,
+                                                 const float* stats, const float* delta, const float* grad_out, float* grad_k, float* grad_v,
+                                                 int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                                 const void* seed, void* stream) {
+    return dot_attention_backward_kv_entry(colptr, rowind, q, k, v, stats, delta, grad_out, grad_k, grad_v, M, K, H, F, nnz, scale, &p, seed,
+                                           stream);
+}
+
+int gespmm_describe_dot_attention(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int q_align, int k_align, int v_align, char* out,
+                                  int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    for (const int a : {q_align, k_align, v_align})
+        if (a < 4 || (a & (a - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, 1.0f, nullptr);
+    if (rc != 0 && rc != GESPMM_ERR_UNSUPPORTED) return rc;
+    int n;
+    if (rc == GESPMM_ERR_UNSUPPORTED) {
+        n = snprintf(out, (size_t)capacity, "route=unsupported");
+    } else if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else if (F == 0) {
+        n = snprintf(out, (size_t)capacity, "route=zeros");
+    } else {
+        const gespmm::DotAttentionLaunch r =
+            gespmm::resolve_dot_attention(F, q_align > 16 ? 16 : q_align, k_align > 16 ? 16 : k_align, v_align > 16 ? 16 : v_align);
+        n = snprintf(out, (size_t)capacity, "V=%d W=%d", r.V, r.W);
     }
     return describe_result(n, capacity);
 }

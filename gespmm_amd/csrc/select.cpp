@@ -333,4 +333,13 @@ Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t 
     return r;
 }
 
+// The fused dot-product attention. V and W are resolve_sddmm's at WIDTH F (its COO form: no row-walking or blocked answer) for the least
+// aligned operand: V divides F and 4 V bytes divide every base, W is the smallest power of two in 4 .. 64 with 8 W >= F. The kernels keep
+// a head slice in 8 floats per lane, so a slice wider than 8 * 64 floats has no kernel. Nothing here was measured for these kernels.
+DotAttentionLaunch resolve_dot_attention(int64_t F, int q_align, int k_align, int v_align) {
+    const int kv = k_align < v_align ? k_align : v_align;
+    const SddmmLaunch b = resolve_sddmm(false, 1, 1, F, q_align, kv, false, 4);
+    return DotAttentionLaunch{b.V, b.W, F <= kDotAttentionMaxF};
+}
+
 }  // namespace gespmm

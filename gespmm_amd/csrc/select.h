@@ -80,4 +80,13 @@ struct Gatv2ScoreLaunch {
 // nnz >= 1, H >= 1, F >= 1. *_align: largest power of two (bytes) that divides the operand's address, 16 is as good as more.
 Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align);
 
+// ---- fused dot-product attention (dot_attention.h): the lane geometry of its three kernels (gespmm_describe_dot_attention prints it).
+constexpr int64_t kDotAttentionMaxF = 512;  // a lane holds 8 floats of a head slice, a lane group has at most 64 lanes
+struct DotAttentionLaunch {
+    int V, W;        // what resolve_sddmm answers for WIDTH F and the least aligned dense operand: they fix the dot's summation order
+    bool supported;  // F <= kDotAttentionMaxF; false: no kernel serves the shape, V and W mean nothing
+};
+// F >= 1. *_align: largest power of two (bytes) that divides an operand's address — the least of a launch's dense operands decides.
+DotAttentionLaunch resolve_dot_attention(int64_t F, int q_align, int k_align, int v_align);
+
 }  // namespace gespmm

@@ -50,6 +50,9 @@ fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` 
 GraphSAGE (extension): ``SpmmMaxFunction`` is the max over neighbours with a gradient — the forward saves the winning CSR position of
 every output word (``spmm.csr_spmm_max_arg``), the backward adds ``grad_out`` where that position sits (``spmm.csr_spmm_max_backward``) —
 and ``SAGEConv`` DGL's layer of that name with the ``mean``, ``gcn`` and ``pool`` aggregators.
+Graph transformers (extension): ``DotAttentionFunction`` is scaled dot-product attention over the edges in three fused launches
+(``attention.dot_attention`` and its two backward passes: no score, no alpha, nothing of size nnz saved), ``TransformerConv`` PyG's layer
+of that name on it (``fused=True``) or on the composition of the functions above (the default).
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -59,6 +62,7 @@ import torch
 from torch.autograd.function import once_differentiable
 from torch.nn import Parameter
 
+from . import attention as _attention
 from . import sddmm as _sddmm
 from . import softmax as _softmax
 from . import spmm as _spmm
@@ -743,6 +747,149 @@ class GATv2Conv(torch.nn.Module):
         out = MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, xr, alpha, None, True)
         out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
         return out if self.bias is None else out + self.bias
+
+    def __repr__(self):
+        return "%s(%d, %d, heads=%d)" % (type(self).__name__, self.in_channels, self.out_channels, self.heads)
+
+
+class DotAttentionFunction(torch.autograd.Function):
+    """out[r, h, :] = sum_e softmax_row(scale <q[r, h, :], k[col(e), h, :]>)_e v[col(e), h, :] — scaled dot-product attention over the
+    edges of a graph in ONE launch (``attention.dot_attention``), with gradients for q, k and v in two more
+    (``attention.dot_attention_backward_q`` over the rows, ``attention.dot_attention_backward_kv`` over the columns).
+
+        DotAttentionFunction.apply(q, k, v, rowptr, colind, colptr, rowind, scale=None, dropout_p=0.0, seed=None) -> f32[M, H, F]
+
+    ``q`` f32[M, H, F], ``k`` and ``v`` f32[K, H, F]; ``colptr, rowind = graphs.transpose_csr(rowptr, colind, K)`` — no ``csc_order``;
+    ``scale=None``: 1 / sqrt(F). No score and no attention array exists in either direction: the function saves ``q, k, v, out`` and the
+    [M, H, 2] softmax statistics (and the two seed words), nothing of size nnz. ``dropout_p > 0`` with ``seed`` (int32[2] on the device):
+    dropout on the coefficients with ``EdgeDropoutFunction``'s mask, recomputed in all three launches; the seed is read when the backward
+    runs. F <= 512. Index tensors get no gradient. Both backward launches run whenever any of q, k, v requires grad."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rowptr, colind, colptr, rowind, scale=None, dropout_p=0.0, seed=None):
+        dropout_p = float(dropout_p)
+        if dropout_p != 0.0 and seed is None:
+            raise ValueError("dropout_p needs a seed (an int32[2] device tensor)")
+        drop = (dropout_p, seed) if dropout_p != 0.0 else None
+        q_c, k_c, v_c = q.contiguous(), k.contiguous(), v.contiguous()
+        out, stats = _attention.dot_attention(rowptr, colind, q_c, k_c, v_c, scale=scale, dropout=drop)
+        ctx.graph = (rowptr, colind, colptr, rowind)
+        ctx.scale, ctx.dropout_p = scale, dropout_p
+        if drop is None:
+            ctx.save_for_backward(q_c, k_c, v_c, out, stats)
+        else:
+            ctx.save_for_backward(q_c, k_c, v_c, out, stats, seed)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        rowptr, colind, colptr, rowind = ctx.graph
+        q, k, v, out, stats = ctx.saved_tensors[:5]
+        drop = (ctx.dropout_p, ctx.saved_tensors[5]) if ctx.dropout_p != 0.0 else None
+        grad_q = grad_k = grad_v = None
+        if any(ctx.needs_input_grad[:3]):
+            grad_out = grad_out.contiguous()
+            delta, grad_q = _attention.dot_attention_backward_q(rowptr, colind, q, k, v, stats, out, grad_out, scale=ctx.scale, dropout=drop)
+            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                grad_k, grad_v = _attention.dot_attention_backward_kv(colptr, rowind, q, k, v, stats, delta, grad_out, scale=ctx.scale,
+                                                                      dropout=drop)
+        return grad_q, grad_k, grad_v, None, None, None, None, None, None, None
+
+
+class TransformerConv(torch.nn.Module):
+    """The graph transformer layer of Shi et al. ("Masked label prediction: unified message passing model for semi-supervised
+    classification"; PyG's ``TransformerConv`` without edge features) on the library's ops, H heads in every call:
+
+        q = lin_query(x).view(n, H, F),  k = lin_key(x).view(n, H, F),  v = lin_value(x).view(n, H, F)              (dense, torch)
+        alpha[e, h] = softmax over each row's entries of <q[row(e), h, :], k[col(e), h, :]> / sqrt(F)
+        out[r, h, :] = sum_e alpha[e, h] v[col(e), h, :]
+
+    then heads concatenated (``concat=True``: [n, H F]) or averaged ([n, F]); with ``root_weight`` the skip term ``x_r = lin_skip(x)`` is
+    added — or, with ``beta``, gated: ``b = sigmoid(lin_beta([out, x_r, out - x_r]))``, ``out = b x_r + (1 - b) out``.
+
+        TransformerConv(in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, bias=True, root_weight=True, fused=False,
+                        attn_seed=None)
+        forward(x, rowptr, colind, colptr, rowind, csc_order)
+
+    ``fused=False`` (the default) composes the attention from ``MultiHeadSDDMMFunction``, the scaling, ``EdgeSoftmaxFunction`` (no slope),
+    ``EdgeDropoutFunction`` and ``MultiHeadSPMMFunction``: [nnz, H] score and alpha arrays in both directions, any F. ``fused=True`` runs
+    ``DotAttentionFunction``: three launches per training step, nothing of size nnz allocated; it serves ``out_channels <= 512`` and raises
+    at construction beyond. ``dropout=p`` (0 <= p < 1) is dropout on alpha in training mode with the mask of ``EdgeDropoutFunction``: the
+    two seed words come from torch's device generator at every forward unless ``attn_seed``, an int32[2] device tensor, is given; both
+    settings of ``fused`` apply the same mask under one seed. In ``eval()`` mode or with ``dropout == 0`` no mask exists. ``bias``
+    switches the bias of the four linear maps, as in PyG. ``beta`` needs ``root_weight``.
+
+    The graph is square (row r and column r are the same node); ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K,
+    return_order=True)`` (``csc_order`` int32; the fused path does not read it). fp32 only."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, bias=True, root_weight=True, fused=False,
+                 attn_seed=None):
+        super().__init__()
+        self.dropout = float(dropout)
+        if not (0.0 <= self.dropout < 1.0):
+            raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
+        if heads < 1:
+            raise ValueError("heads must be at least 1")
+        if in_channels < 1 or out_channels < 1:
+            raise ValueError("in_channels and out_channels must be at least 1")
+        if beta and not root_weight:
+            raise ValueError("beta gates the skip term: it needs root_weight=True")
+        if fused and out_channels > _attention.DOT_ATTENTION_MAX_F:
+            raise ValueError("fused=True serves out_channels <= %d (a head slice is held in registers), got %d" %
+                             (_attention.DOT_ATTENTION_MAX_F, out_channels))
+        if attn_seed is not None and (not isinstance(attn_seed, torch.Tensor) or attn_seed.dtype != torch.int32 or
+                                      tuple(attn_seed.shape) != (2,)):
+            raise TypeError("attn_seed must be an int32[2] tensor")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, int(heads)
+        self.concat, self.beta, self.root_weight, self.fused = bool(concat), bool(beta), bool(root_weight), bool(fused)
+        self.attn_seed = attn_seed
+        hf = self.heads * out_channels
+        self.lin_key = torch.nn.Linear(in_channels, hf, bias=bias)
+        self.lin_query = torch.nn.Linear(in_channels, hf, bias=bias)
+        self.lin_value = torch.nn.Linear(in_channels, hf, bias=bias)
+        width = hf if self.concat else out_channels
+        self.lin_skip = torch.nn.Linear(in_channels, width, bias=bias) if self.root_weight else None
+        self.lin_beta = torch.nn.Linear(3 * width, 1, bias=False) if self.beta else None
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip, self.lin_beta):
+            if lin is not None:
+                lin.reset_parameters()
+
+    def forward(self, x, rowptr, colind, colptr, rowind, csc_order=None):
+        n, H, F = x.shape[0], self.heads, self.out_channels
+        if rowptr.numel() != n + 1 or colptr.numel() != n + 1:
+            raise ValueError("TransformerConv needs a square graph: rowptr and colptr must have x.size(0) + 1 entries")
+        p, seed = 0.0, None
+        if self.training and self.dropout > 0.0:
+            p = self.dropout
+            seed = self.attn_seed
+            if seed is None:  # two 32-bit words from the device generator: no host synchronisation
+                seed = torch.randint(-(2 ** 31), 2 ** 31, (2,), dtype=torch.int32, device=x.device)
+        q = self.lin_query(x).view(n, H, F)
+        k = self.lin_key(x).view(n, H, F)
+        v = self.lin_value(x).view(n, H, F)
+        scale = 1.0 / math.sqrt(F)
+        if self.fused:
+            out = DotAttentionFunction.apply(q, k, v, rowptr, colind, colptr, rowind, scale, p, seed)
+        else:
+            if csc_order is None:
+                raise ValueError("fused=False needs csc_order (graphs.transpose_csr(..., return_order=True))")
+            score = MultiHeadSDDMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, q, k) * scale
+            alpha = EdgeSoftmaxFunction.apply(rowptr, score, None)
+            if seed is not None:
+                alpha = EdgeDropoutFunction.apply(rowptr, colind, alpha, p, seed)
+            out = MultiHeadSPMMFunction.apply(rowptr, colind, colptr, rowind, csc_order, v, alpha, None, True)
+        out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
+        if self.root_weight:
+            x_r = self.lin_skip(x)
+            if self.beta:
+                b = torch.sigmoid(self.lin_beta(torch.cat([out, x_r, out - x_r], dim=-1)))
+                out = b * x_r + (1.0 - b) * out
+            else:
+                out = out + x_r
+        return out
 
     def __repr__(self):
         return "%s(%d, %d, heads=%d)" % (type(self).__name__, self.in_channels, self.out_channels, self.heads)

@@ -80,6 +80,7 @@ extern "C" {
 #define GESPMM_EIO      (-4)  /* loader: file not found / unreadable */
 #define GESPMM_EFORMAT  (-5)  /* loader: bad MatrixMarket banner or size line */
 #define GESPMM_ENOMEM   (-6)  /* host allocation failed */
+#define GESPMM_ERR_UNSUPPORTED (-7)  /* no kernel serves this shape, and there is no other route (gespmm_dot_attention_f32: F > 512) */
 
 /*
  * Kernel variants. Numbers 0..4 keep the reference's `method` numbering
@@ -835,6 +836,66 @@ int gespmm_gatv2_score_backward_f32(const int32_t* ptr, const int32_t* ind, cons
  * *_align: largest power of two (>= 4) dividing the operand's address. Returns the length written or a GESPMM_E* code. */
 int gespmm_describe_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align, char* out,
                                 int64_t capacity);
+/*
+ * Fused scaled dot-product attention over the entries of a pattern (the attention of a graph transformer: PyG's TransformerConv, UniMP)
+ * and its backward, with NOTHING of size nnz but the index arrays (new symbols of 0.5). q [M x H x F] is the aggregating node's term
+ * (the row of an entry), k and v [K x H x F] the neighbour's (the column); out and grad_out [M x H x F], stats [M x H x 2], delta
+ * [M x H]. For entry p of row r with column c and head h
+ *
+ *     s_p = fl(scale dot(q[r, h, :], k[c, h, :]))      a_p = exp(s_p - m) / l,  (m, l) = stats[r, h] = (max_p s_p, sum_p exp(s_p - m))
+ *     out[r, h, :] = sum_p a_p v[c, h, :]
+ *
+ * Geometry of all three kernels: a group of W lanes owns a (segment, head) pair — rows in the forward and in _backward_q, columns in
+ * _backward_kv — with V floats per load and 8 floats per lane and operand; (V, W) from gespmm_describe_dot_attention: V the widest of
+ * 4 / 2 / 1 that divides F and whose bytes divide every dense operand's address, W the smallest power of two in 4 .. 64 with 8 W >= F.
+ * F > 512 is not served: GESPMM_ERR_UNSUPPORTED, nothing launched. A hub segment is walked by its one lane group (a limit).
+ * Pinned orders: dot(x, y): lane l runs ONE chain acc = fmaf(x_j, y_j, acc) from +0 over j = l V + i + t W V (i ascending inside a
+ * vector, t ascending), then the xor butterfly W/2 .. 1; a lane past the slice contributes fmaf(0, 0, acc). fmaf commutes in its
+ * factors: the row pass and the column pass of the backward see the same bits of s_p and g_p. Every per-word accumulation is one chain
+ * per output word in segment (entry) order; the head, H, alignment, capture and run leave no trace beyond V.
+ *
+ * Forward — one sweep with an online softmax; per entry, in entry order:
+ *     m' = fmaxf(m, s_p);  c = __expf(m - m');  t = __expf(s_p - m');  l = fmaf(l, c, t);  acc_f = fmaf(t, v_f, fl(acc_f c));  m = m'
+ * from (m, l, acc) = (s_0, 0, 0) — the first entry gives l = 1, acc = v with no exp(-inf - ..) — and out = acc / l. Every word of out
+ * and stats is written; an empty row writes +0 everywhere.
+ * gespmm_dot_attention_backward_q_f32 (rowptr, colind) writes delta and grad_q:
+ *     delta[r, h] = dot(grad_out[r, h, :], out[r, h, :])     g_p = dot(grad_out[r, h, :], v[c, h, :])      ds_p = a_p (g_p - delta[r, h])
+ *     grad_q[r, h, f] = fl(scale chain over p of fmaf(ds_p, k[c, h, f], acc))                 with a_p = __expf(s_p - m) / l
+ * gespmm_dot_attention_backward_kv_f32 (colptr, rowind: the CSC arrays, no csc_order) reads delta and writes
+ *     grad_k[c, h, f] = fl(scale chain over p of fmaf(ds_p, q[r, h, f], acc))       grad_v[c, h, f] = chain of fmaf(a_p, grad_out[r, h, f], acc)
+ * The *_dropout_f32 forms put dropout on a_p (the mask of gespmm_edge_dropout_f32: a function of (seed, r, c, h)): the forward's l sums
+ * every entry and acc takes fl(t s) for a kept entry, +0 for a dropped one; the backward replaces g_p by fl(g_p s) or +0 directly after
+ * its chain, delta stays dot(grad_out, out), grad_v uses fl(a_p s) or +0.
+ * Checks, in this order: a negative size, H < 1, M < 1 or K < 1 with nnz > 0, a NaN or infinite scale, !(0 <= p < 1) -> GESPMM_EINVAL;
+ * M, K, nnz, nnz H, M H F, K H F or 2 M H > 2^31 - 4097 -> GESPMM_ERANGE; F > 512 -> GESPMM_ERR_UNSUPPORTED; nnz == 0 or F == 0 looks at
+ * the results (and the seed) alone and zero-fills them (hipMemsetAsync); NULL -> GESPMM_EINVAL; a pointer not 4-byte (stats: 8-byte)
+ * aligned -> GESPMM_EALIGN. No atomics, no workspace, no allocation, no host synchronisation: capturable. Results must not overlap an
+ * input (not checked). colind within [0, K), rowind within [0, M) and ptr[last] == nnz are preconditions.
+ */
+int gespmm_dot_attention_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v, float* out,
+                             float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream);
+int gespmm_dot_attention_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v, float* out,
+                                     float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                     const void* seed, void* stream);
+int gespmm_dot_attention_backward_q_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v,
+                                        const float* stats, const float* out, const float* grad_out, float* delta, float* grad_q, int64_t M,
+                                        int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream);
+int gespmm_dot_attention_backward_q_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* q, const float* k, const float* v,
+                                                const float* stats, const float* out, const float* grad_out, float* delta, float* grad_q,
+                                                int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p, const void* seed,
+                                                void* stream);
+int gespmm_dot_attention_backward_kv_f32(const int32_t* colptr, const int32_t* rowind, const float* q, const float* k, const float* v,
+                                         const float* stats, const float* delta, const float* grad_out, float* grad_k, float* grad_v,
+                                         int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream);
+int gespmm_dot_attention_backward_kv_dropout_f32(const int32_t* colptr, const int32_t* rowind, const float* q, const float* k, const float* v,
+                                                 const float* stats, const float* delta, const float* grad_out, float* grad_k, float* grad_v,
+                                                 int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                                 const void* seed, void* stream);
+/* Host only: what the three entry points would launch, as text: "V=.. W=..", "route=unsupported" (F > 512), "route=zeros" (F == 0) or
+ * "form=none" (nnz == 0). *_align: largest power of two (>= 4) dividing the operand's address; the least of them decides V. Returns the
+ * length written or a GESPMM_E* code. */
+int gespmm_describe_dot_attention(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int q_align, int k_align, int v_align, char* out,
+                                  int64_t capacity);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
