@@ -14,6 +14,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
     python examples/gat_custom.py --seed 0 --fused-aggregate       # seeded parameters and dropout: the losses of --seed 0 --fused-score
     python examples/gat_custom.py --v2                             # two ``GATv2Conv`` layers (Brody et al.): the non-linearity inside the
                                                                    # score's sum, one kernel, nothing of size nnz x H x F
+    python examples/gat_custom.py --dtype bf16                     # a .bfloat16() model on bf16 features (or fp16): the aggregation is the
+                                                                   # 16-bit multi-head product, everything edge-sized stays fp32
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
 chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
@@ -90,7 +92,13 @@ def main():
     ap.add_argument("--seed", type=int, default=None,
                     help="torch.manual_seed before the model is made (parameters and dropout masks): two runs, or two fused settings, "
                          "then print the same losses")
+    ap.add_argument("--dtype", choices=("fp32", "bf16", "fp16"), default="fp32",
+                    help="cast the model and the features (bf16 / fp16: GATConv on the 16-bit multi-head product; not with "
+                         "--fused-aggregate, --fused-backward or --v2, which are fp32 only)")
     args = ap.parse_args()
+    if args.dtype != "fp32" and (args.fused_aggregate or args.fused_backward or args.v2):
+        ap.error("--dtype %s: --fused-aggregate, --fused-backward and --v2 run fp32-only kernels; use the default path or --fused-score"
+                 % args.dtype)
     if args.v2 and (args.fused_score or args.fused_aggregate or args.fused_backward):
         ap.error("--v2 has no fused path: --fused-score, --fused-aggregate and --fused-backward are GATConv's")
     if not torch.cuda.is_available():
@@ -115,7 +123,13 @@ def main():
         torch.manual_seed(args.seed)
     model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score,
                 fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward, attn_dropout=args.attn_dropout, v2=args.v2).to(device)
-    optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
+    if args.dtype != "fp32":
+        dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+        model = model.to(dtype)
+        x = x.to(dtype)
+    # (fp16 parameters: Adam's default eps, 1e-8, is zero in fp16 and a parameter whose gradient is zero would be updated by 0 / 0)
+    adam = {"eps": 1e-4} if args.dtype == "fp16" else {}
+    optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture, **adam)
     train_idx = masks["train"].nonzero().squeeze(1)
     y_train = y[train_idx]
 
@@ -175,7 +189,8 @@ def main():
     wall = time.perf_counter() - t0
     print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s fused_backward=%s%s" %
           (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score, args.fused_aggregate,
-           args.fused_backward, (" attn_dropout=%g" % args.attn_dropout if args.attn_dropout else "") + (" v2=True" if args.v2 else "")))
+           args.fused_backward, (" attn_dropout=%g" % args.attn_dropout if args.attn_dropout else "") + (" v2=True" if args.v2 else "") +
+           (" dtype=%s" % args.dtype if args.dtype != "fp32" else "")))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
 

@@ -107,6 +107,11 @@ EXPORTS = [
     "gespmm_plan_sddmm_heads_f32",
     "gespmm_describe_sddmm_heads",
     "gespmm_plan_sddmm_heads_route",
+    "gespmm_csr_spmm_heads_x16",
+    "gespmm_heads_x16_route",
+    "gespmm_sddmm_coo_heads_x16",
+    "gespmm_sddmm_csr_heads_x16",
+    "gespmm_describe_sddmm_heads_x16",
     "gespmm_edge_softmax_f32",
     "gespmm_edge_softmax_backward_f32",
     "gespmm_describe_edge_softmax",
@@ -316,6 +321,16 @@ def _load():
     lib.gespmm_describe_sddmm_heads.argtypes = [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_plan_sddmm_heads_route.restype = c_int
     lib.gespmm_plan_sddmm_heads_route.argtypes = [p, c_int64, c_int64]
+    lib.gespmm_csr_spmm_heads_x16.restype = c_int
+    lib.gespmm_csr_spmm_heads_x16.argtypes = [p, p, p, p, p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, p]
+    lib.gespmm_heads_x16_route.restype = c_int
+    lib.gespmm_heads_x16_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, p]
+    lib.gespmm_sddmm_coo_heads_x16.restype = c_int
+    lib.gespmm_sddmm_coo_heads_x16.argtypes = [p, p, p, p, p, c_int, c_int64, c_int64, c_int64, p]
+    lib.gespmm_sddmm_csr_heads_x16.restype = c_int
+    lib.gespmm_sddmm_csr_heads_x16.argtypes = [p, p, p, p, p, c_int, c_int64, c_int64, c_int64, c_int64, p]
+    lib.gespmm_describe_sddmm_heads_x16.restype = c_int
+    lib.gespmm_describe_sddmm_heads_x16.argtypes = [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_edge_softmax_f32.restype = c_int
     lib.gespmm_edge_softmax_f32.argtypes = [p, p, p, c_int64, c_int64, c_int64, c_float, p]
     lib.gespmm_edge_softmax_backward_f32.restype = c_int
@@ -445,15 +460,17 @@ def describe_sddmm(csr, M, nnz, N, d1_align=16, d2_align=16, capturing=False, x1
     return {k: (v if k == "form" else int(v)) for k, v in out.items()}
 
 
-def describe_sddmm_heads(csr, M, nnz, H, F, d1_align=16, d2_align=16, capturing=False):
-    """What gespmm_sddmm_{coo,csr}_heads_f32 would do for these arguments (gespmm_describe_sddmm_heads: host only) — a dict with "route"
-    ("kernel", "composition", "plain" or "zeros"; absent when nnz == 0) and what the route has: "form", V, W, epw (EDGES per wavefront)
-    for the kernel, V and W for the composition, ``describe_sddmm``'s entries at width F for "plain"."""
+def describe_sddmm_heads(csr, M, nnz, H, F, d1_align=16, d2_align=16, capturing=False, x16=False):
+    """What gespmm_sddmm_{coo,csr}_heads_f32 — x16=True: gespmm_sddmm_{coo,csr}_heads_x16, fp16 / bf16 operands — would do for these
+    arguments (gespmm_describe_sddmm_heads / _x16: host only) — a dict with "route"
+    ("kernel", "composition", "plain" or "zeros"; absent when nnz == 0) and what the route has: "form", V (elements per load), W, epw
+    (EDGES per wavefront) for the kernel, V and W for the composition, ``describe_sddmm``'s entries at width F for "plain"."""
     buf = ctypes.create_string_buffer(160)
-    n = lib.gespmm_describe_sddmm_heads(1 if csr else 0, int(M), int(nnz), int(H), int(F), int(d1_align), int(d2_align), 1 if capturing else 0,
-                                        buf, 160)
+    f, name = (lib.gespmm_describe_sddmm_heads_x16, "gespmm_describe_sddmm_heads_x16") if x16 else \
+        (lib.gespmm_describe_sddmm_heads, "gespmm_describe_sddmm_heads")
+    n = f(1 if csr else 0, int(M), int(nnz), int(H), int(F), int(d1_align), int(d2_align), 1 if capturing else 0, buf, 160)
     if n < 0:
-        raise GespmmError(n, "gespmm_describe_sddmm_heads")
+        raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
 
@@ -510,6 +527,17 @@ def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):
     rc = lib.gespmm_heads_route(int(M), int(K), int(H), int(F), int(nnz), int(b_align), int(c_align), geo)
     if rc < 0:
         raise GespmmError(rc, "gespmm_heads_route")
+    return rc, tuple(int(x) for x in geo)
+
+
+def heads_x16_route(M, K, H, F, nnz, b_align=16, c_align=16):
+    """What gespmm_csr_spmm_heads_x16 would do for these sizes and operand alignments (gespmm_heads_x16_route: host only):
+    ``(route, (V, S, W, rpw))`` — route 1 the 16-bit heads kernel with that lane geometry (V in 32-bit words: V divides F / 2),
+    route 0 the composition widen, gespmm_csr_spmm_heads_f32, narrow (zeros)."""
+    geo = (ctypes.c_int32 * 4)()
+    rc = lib.gespmm_heads_x16_route(int(M), int(K), int(H), int(F), int(nnz), int(b_align), int(c_align), geo)
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_heads_x16_route")
     return rc, tuple(int(x) for x in geo)
 
 

@@ -328,6 +328,35 @@ int run_spmm_heads(const CsrView& A, const float* B, float* C, int64_t H, int64_
     return (int)launch_spmm_heads(a, r.sel.geo, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ... and on 16-bit B and C (gespmm_csr_spmm_heads_x16): ONE 16-bit heads kernel or nothing (kHeadsUnavailable: the caller composes widen,
+// the fp32 entry, narrow). The kernel works in 32-bit words, so the geometry is run_spmm_heads's for H heads of F / 2 WORDS: the width
+// H F / 2, V limited to what divides F / 2 and to what B and C can be addressed with. Storage order only; the stream is never asked.
+int run_spmm_heads_x16(const CsrView& A, const void* B, void* C, int dtype, int64_t H, int64_t F, void* stream, int b_align, int c_align,
+                       bool dry_run, int* kind, Geometry* geo_out) {
+    *kind = 0;
+    if (H < 2 || H > kHeadsMax || A.M <= 0 || F <= 0 || F % 2 != 0 || A.nnz < 0 || b_align < 4 || c_align < 4) return kHeadsUnavailable;
+    // GESPMM_HEADS_X16_ROUTE=composition pins route 0 (read per call: scripts/heads_x16_timing.py measures both routes in one process)
+    if (const char* env = getenv("GESPMM_HEADS_X16_ROUTE"))
+        if (!strcmp(env, "composition")) return kHeadsUnavailable;
+    const int64_t Fw = F / 2, Nw = H * Fw;  // words per head, words per row
+    if ((uint64_t)A.K * (uint64_t)Nw * 4ull >= (1ull << 32) || A.nnz * H >= (1ll << 31)) return kHeadsUnavailable;  // 32-bit offsets only
+    const int flags = kFlagBatchStream | kFlagStrictOrder | kFlagNoSlabBlocked;
+    const StreamQuery q = {A.M, A.K, Nw, A.nnz, vec_limit(Fw, std::min(b_align, c_align)), GESPMM_VARIANT_AUTO, flags, kReduceSum, nullptr, nullptr, false, nullptr};
+    StreamLaunch r;
+    const int rc = resolve_stream_launch(q, &r);
+    if (rc != 0) return rc == kNotStreaming ? kHeadsUnavailable : GESPMM_EINVAL;
+    if (!heads_geometry_served(r.sel.geo, false)) return kHeadsUnavailable;
+    *kind = 1;
+    if (geo_out) *geo_out = r.sel.geo;
+    if (dry_run) return 0;
+    if (A.nnz != 0 && (!A.val || !A.colind || !B)) return GESPMM_EINVAL;  // (no entries: the kernel reads none of the three and writes zeros)
+    // (arrays of words: spmm_heads.h)
+    HeadsArgs a = stream_args<HeadsArgs>(A, static_cast<const float*>(B), static_cast<float*>(C), Nw, r);
+    a.H = (int32_t)H;
+    a.F = (int32_t)Fw;
+    return (int)launch_spmm_heads_x16(a, dtype, r.sel.geo, reinterpret_cast<hipStream_t>(stream));
+}
+
 // The fused GAT aggregation (gat_aggregate.h): ONE kernel or nothing (kHeadsUnavailable: the caller materialises the weights and calls
 // the multi-head product). A is the pattern the segments come from — (rowptr, colind) with M rows, or (colptr, rowind) with K — and
 // A.K the rows of B; the geometry is run_spmm_heads's, H = 1 included. The stream is never asked.
@@ -423,15 +452,29 @@ int check_gat_backward_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t
 //                bytes past a 256-byte boundary — the caller's alignment class, hence the caller's V — launch_sddmm at width F into an
 //                nnz temporary, scatter into out[:, h]. K < 0: the call does not say how many rows D2 has; 1 + the largest column index
 //                is found on the device and read back (one stream synchronisation; a plan passes its K).
-int run_sddmm_heads(const int32_t* rows, bool csr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M, int64_t K,
-                    int64_t H, int64_t F, int64_t nnz, void* stream) {
+// dtype 0: fp32 operands; kX16F16 / kX16Bf16: 16-bit operands (gespmm_sddmm_*_heads_x16) — the same routes at element size 2, every launch
+// the 16-bit one, the slices 2-byte copies.
+static int run_sddmm_heads_elem(const int32_t* rows, bool csr, const int32_t* colind, const void* D1v, const void* D2v, float* out, int dtype,
+                                int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const bool x16 = dtype != 0;
+    const size_t es = x16 ? 2 : 4;
+    const float* D1 = static_cast<const float*>(D1v);  // (looked at through these names on the fp32 path only)
+    const float* D2 = static_cast<const float*>(D2v);
+    // one single-head launch on contiguous operands, of either element type
+    auto single = [&](const void* d1, const void* d2, float* o) {
+        return x16 ? (int)launch_sddmm_x16(rows, csr, colind, d1, d2, o, dtype, M, nnz, F, st)
+                   : (int)launch_sddmm(rows, csr, colind, static_cast<const float*>(d1), static_cast<const float*>(d2), o, M, nnz, F, st);
+    };
     if (F == 0) return (int)hipMemsetAsync(out, 0, (size_t)nnz * (size_t)H * sizeof(float), st);
     const bool capturing = stream_capture(st) != Capture::No;  // (a failed query counts as capturing)
     (void)hipGetLastError();
-    const SddmmHeadsLaunch r = resolve_sddmm_heads(csr, M, nnz, H, F, pointer_alignment(D1), pointer_alignment(D2), capturing, sddmm_heads_pin());
-    if (r.route == kSddmmHeadsPlain) return (int)launch_sddmm(rows, csr, colind, D1, D2, out, M, nnz, F, st);
-    if (r.route == kSddmmHeadsKernel) return (int)launch_sddmm_heads(rows, colind, D1, D2, out, M, nnz, H, F, r, st);
+    const SddmmHeadsLaunch r = resolve_sddmm_heads(csr, M, nnz, H, F, pointer_alignment(D1v), pointer_alignment(D2v), capturing, sddmm_heads_pin(),
+                                                   (int)es);
+    if (r.route == kSddmmHeadsPlain) return single(D1v, D2v, out);
+    if (r.route == kSddmmHeadsKernel)
+        return x16 ? (int)launch_sddmm_heads_x16(rows, colind, D1v, D2v, out, dtype, M, nnz, H, F, r, st)
+                   : (int)launch_sddmm_heads(rows, colind, D1, D2, out, M, nnz, H, F, r, st);
     if (!csr) return GESPMM_ERANGE;  // (check_sddmm_heads_sizes lets no such call through)
     int rc = 0;
     if (K < 0) {
@@ -445,20 +488,25 @@ int run_sddmm_heads(const int32_t* rows, bool csr, const int32_t* colind, const 
         if ((rc = probe.close((int)e)) != 0) return rc;
         K = (int64_t)h_max + 1;
     }
-    const size_t d1_bytes = (size_t)M * (size_t)F * 4 + 16, d2_bytes = (size_t)K * (size_t)F * 4 + 16, t_bytes = (size_t)nnz * 4;
+    const size_t d1_bytes = (size_t)M * (size_t)F * es + 16, d2_bytes = (size_t)K * (size_t)F * es + 16, t_bytes = (size_t)nnz * 4;
     PooledScratch scratch;
     if ((rc = scratch.open(PooledScratch::slice(d1_bytes) + PooledScratch::slice(d2_bytes) + t_bytes, st)) != 0) return rc;  // (nothing launched)
-    float* D1h = scratch.take(d1_bytes, D1);
-    float* D2h = scratch.take(d2_bytes, D2);
+    float* D1h = scratch.take(d1_bytes, D1v);
+    float* D2h = scratch.take(d2_bytes, D2v);
     float* th = scratch.take(t_bytes);
     const int64_t N = H * F;
     for (int64_t h = 0; h < H && rc == 0; ++h) {  // (stream order keeps one head's temporaries until its scatter has read them)
-        rc = (int)launch_heads_slice(D1, D1h, M, N, h * F, F, st);
-        if (rc == 0) rc = (int)launch_heads_slice(D2, D2h, K, N, h * F, F, st);
-        if (rc == 0) rc = (int)launch_sddmm(rows, true, colind, D1h, D2h, th, M, nnz, F, st);
+        rc = x16 ? (int)launch_heads_slice_x16(D1v, D1h, M, N, h * F, F, st) : (int)launch_heads_slice(D1, D1h, M, N, h * F, F, st);
+        if (rc == 0) rc = x16 ? (int)launch_heads_slice_x16(D2v, D2h, K, N, h * F, F, st) : (int)launch_heads_slice(D2, D2h, K, N, h * F, F, st);
+        if (rc == 0) rc = single(D1h, D2h, th);
         if (rc == 0) rc = (int)launch_heads_unslice(th, out, nnz, H, h, 1, st);
     }
     return scratch.close(rc);
+}
+
+int run_sddmm_heads(const int32_t* rows, bool csr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M, int64_t K,
+                    int64_t H, int64_t F, int64_t nnz, void* stream) {
+    return run_sddmm_heads_elem(rows, csr, colind, D1, D2, out, 0, M, K, H, F, nnz, stream);
 }
 
 // ---- the GATv2 score (gespmm.h: gespmm_gatv2_score_f32 / _backward_f32; gatv2_score.h). S segments of x_seg, T rows of x_ind (forward:
@@ -643,6 +691,52 @@ int gespmm_heads_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, 
     Geometry geo = {};
     const int rc = run_spmm_heads(csr_view(nullptr, nullptr, nullptr, M, K, nnz, GESPMM_VARIANT_AUTO), nullptr, nullptr, H, F, 0, nullptr, b_align,
                                   c_align, true, &kind, &geo);
+    const int route = route_result(rc == kHeadsUnavailable ? 0 : rc, kind);
+    if (route >= 0 && geometry_out) {
+        geometry_out[0] = kind ? geo.vec : 0;
+        geometry_out[1] = kind ? geo.strips : 0;
+        geometry_out[2] = kind ? geo.group : 0;
+        geometry_out[3] = kind ? geo.rows_per_wave : 0;
+    }
+    return route;
+}
+
+// The multi-head product on 16-bit operands (gespmm.h): the 16-bit heads kernel where it exists, else the composition — widen B into a
+// stream-ordered temporary, gespmm_csr_spmm_heads_f32 unchanged into a second one, narrow into C. Same bits: widening is exact and either
+// way each fp32 chain is rounded once.
+int gespmm_csr_spmm_heads_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, void* C, int dtype, int64_t M,
+                              int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream) {
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    int rc = check_heads_sizes(M, K, H, F, nnz);
+    if (rc != 0) return rc;
+    if (M == 0 || F == 0) return 0;
+    rc = check_pointers({{rowptr, 4, true}, {C, 2, true}, {colind, 4, nnz != 0}, {B, 2, nnz != 0}, {val, 4, nnz != 0}});
+    if (rc != 0) return rc;
+    int kind = 0;
+    rc = run_spmm_heads_x16(csr_view(rowptr, colind, val, M, K, nnz, GESPMM_VARIANT_AUTO), B, C, dtype, H, F, stream, pointer_alignment(B),
+                            pointer_alignment(C), false, &kind, nullptr);
+    if (rc != kHeadsUnavailable) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int64_t N = H * F;
+    const size_t b_bytes = (size_t)K * (size_t)N * 4, c_bytes = (size_t)M * (size_t)N * 4;
+    PooledScratch scratch;
+    if ((rc = scratch.open(PooledScratch::slice(b_bytes) + c_bytes, st)) != 0) return rc;  // (nothing launched)
+    float* Bf = scratch.take(b_bytes);
+    float* Cf = scratch.take(c_bytes);
+    if (B && nnz != 0) rc = (int)launch_widen_x16(B, Bf, dtype, K * N, st);
+    if (rc == 0) rc = gespmm_csr_spmm_heads_f32(rowptr, colind, val, Bf, Cf, M, K, H, F, nnz, stream);
+    if (rc == 0) rc = (int)launch_narrow_x16(Cf, C, dtype, M * N, st);
+    return scratch.close(rc);
+}
+
+int gespmm_heads_x16_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int b_align, int c_align, int32_t* geometry_out) {
+    if (b_align < 1 || c_align < 1) return GESPMM_EINVAL;
+    const int rc0 = check_heads_sizes(M, K, H, F, nnz);
+    if (rc0 != 0) return rc0;
+    int kind = 0;
+    Geometry geo = {};
+    const int rc = run_spmm_heads_x16(csr_view(nullptr, nullptr, nullptr, M, K, nnz, GESPMM_VARIANT_AUTO), nullptr, nullptr, GESPMM_X16_BF16, H, F,
+                                      nullptr, b_align, c_align, true, &kind, &geo);
     const int route = route_result(rc == kHeadsUnavailable ? 0 : rc, kind);
     if (route >= 0 && geometry_out) {
         geometry_out[0] = kind ? geo.vec : 0;
@@ -965,30 +1059,42 @@ int gespmm_describe_sddmm_x16(int csr, int64_t M, int64_t nnz, int64_t N, int d1
 }
 
 // The multi-head SDDMM (gespmm.h): D1 [., H F], D2 [., H F], out [nnz, H]. The checks of the single-head entries above, in their order.
-static int sddmm_heads_entry(const int32_t* rows, bool csr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M,
-                             int64_t H, int64_t F, int64_t nnz, void* stream) {
+// elem: bytes per element of D1 / D2 — 4: fp32 (dtype is not looked at), 2: fp16 / bf16, the dtype checked first (as sddmm_entry).
+static int sddmm_heads_entry(const int32_t* rows, bool csr, const int32_t* colind, const void* D1, const void* D2, float* out, int elem,
+                             int dtype, int64_t M, int64_t H, int64_t F, int64_t nnz, void* stream) {
+    if (elem == 2 && !valid_x16_dtype(dtype)) return GESPMM_EINVAL;
     int rc = check_sddmm_heads_sizes(csr, M, H, F, nnz);
     if (rc != 0) return rc;
     if (nnz == 0) return 0;
-    rc = check_pointers({{rows, 4, true}, {colind, 4, true}, {out, 4, true}, {D1, 4, F > 0}, {D2, 4, F > 0}});
+    rc = check_pointers({{rows, 4, true}, {colind, 4, true}, {out, 4, true}, {D1, elem, F > 0}, {D2, elem, F > 0}});
     if (rc != 0) return rc;
-    return run_sddmm_heads(rows, csr, colind, D1, D2, out, M, -1, H, F, nnz, stream);
+    return run_sddmm_heads_elem(rows, csr, colind, D1, D2, out, elem == 2 ? dtype : 0, M, -1, H, F, nnz, stream);
 }
 
 int gespmm_sddmm_coo_heads_f32(const int32_t* rowind, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t H,
                                int64_t F, int64_t nnz, void* stream) {
-    return sddmm_heads_entry(rowind, false, colind, D1, D2, out, 0, H, F, nnz, stream);
+    return sddmm_heads_entry(rowind, false, colind, D1, D2, out, 4, 0, 0, H, F, nnz, stream);
 }
 
 int gespmm_sddmm_csr_heads_f32(const int32_t* rowptr, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M,
                                int64_t H, int64_t F, int64_t nnz, void* stream) {
-    return sddmm_heads_entry(rowptr, true, colind, D1, D2, out, M, H, F, nnz, stream);
+    return sddmm_heads_entry(rowptr, true, colind, D1, D2, out, 4, 0, M, H, F, nnz, stream);
 }
 
-int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing, char* out,
-                                int64_t capacity) {
+int gespmm_sddmm_coo_heads_x16(const int32_t* rowind, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype, int64_t H,
+                               int64_t F, int64_t nnz, void* stream) {
+    return sddmm_heads_entry(rowind, false, colind, D1, D2, out, 2, dtype, 0, H, F, nnz, stream);
+}
+
+int gespmm_sddmm_csr_heads_x16(const int32_t* rowptr, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype, int64_t M,
+                               int64_t H, int64_t F, int64_t nnz, void* stream) {
+    return sddmm_heads_entry(rowptr, true, colind, D1, D2, out, 2, dtype, M, H, F, nnz, stream);
+}
+
+static int describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing, char* out,
+                                int64_t capacity, int elem_size) {
     if (!out || capacity <= 0) return GESPMM_EINVAL;
-    if (d1_align < 4 || d2_align < 4 || (d1_align & (d1_align - 1)) != 0 || (d2_align & (d2_align - 1)) != 0) return GESPMM_EINVAL;
+    if (d1_align < elem_size || d2_align < elem_size || (d1_align & (d1_align - 1)) != 0 || (d2_align & (d2_align - 1)) != 0) return GESPMM_EINVAL;
     const int rc = gespmm::check_sddmm_heads_sizes(csr != 0, M, H, F, nnz);
     if (rc != 0) return rc;
     int n;
@@ -998,11 +1104,12 @@ int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int6
         n = snprintf(out, (size_t)capacity, "route=zeros");
     } else {
         const gespmm::SddmmHeadsLaunch r = gespmm::resolve_sddmm_heads(csr != 0, M, nnz, H, F, d1_align > 16 ? 16 : d1_align,
-                                                                       d2_align > 16 ? 16 : d2_align, capturing != 0, gespmm::sddmm_heads_pin());
+                                                                       d2_align > 16 ? 16 : d2_align, capturing != 0, gespmm::sddmm_heads_pin(),
+                                                                       elem_size);
         if (r.route == gespmm::kSddmmHeadsPlain) {
             n = snprintf(out, (size_t)capacity, "route=plain ");
             if (n > 0 && n < capacity) {
-                const int m = describe_sddmm(csr, M, nnz, F, d1_align, d2_align, capturing, out + n, capacity - n, 4);
+                const int m = describe_sddmm(csr, M, nnz, F, d1_align, d2_align, capturing, out + n, capacity - n, elem_size);
                 if (m < 0) return m;
                 n += m;
             }
@@ -1014,6 +1121,16 @@ int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int6
         }
     }
     return describe_result(n, capacity);
+}
+
+int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing, char* out,
+                                int64_t capacity) {
+    return describe_sddmm_heads(csr, M, nnz, H, F, d1_align, d2_align, capturing, out, capacity, 4);
+}
+
+int gespmm_describe_sddmm_heads_x16(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing,
+                                    char* out, int64_t capacity) {
+    return describe_sddmm_heads(csr, M, nnz, H, F, d1_align, d2_align, capturing, out, capacity, 2);
 }
 
 /* The edge softmax over CSR rows (gespmm.h). One kernel for every size the checks let through; resolve_edge_softmax decides its shape. */

@@ -1,10 +1,11 @@
-// sddmm_heads.h — the MULTI-HEAD SDDMM (gespmm_sddmm_{coo,csr}_heads_f32; instantiated for fp32 in sddmm_heads.hip).
+// sddmm_heads.h — the MULTI-HEAD SDDMM (gespmm_sddmm_{coo,csr}_heads_f32: instantiated for fp32 in sddmm_heads.hip;
+// gespmm_sddmm_{coo,csr}_heads_x16: for fp16 / bf16 operands, on the trait SddmmX16<DT>, in sddmm_x16.hip).
 //
 // D1 is [M, H F], D2 is [K, H F], out is [nnz, H], all row-major, and
 //   out[e H + h] = dot_{V,W}( D1[row(e), h F : (h + 1) F], D2[col(e), h F : (h + 1) F] )
 // where dot_{V,W} is the summation order sddmm_edge.h pins — lane l of W runs one fmaf chain over j = l V + i + t W V, then an xor
-// butterfly with masks W/2 .. 1 — at the (V, W) resolve_sddmm answers for WIDTH F. V divides F and 4 V bytes divide both base
-// addresses, so every head slice of every row is a legal V-vector address and no vector spans two heads: head h has the bits of the
+// butterfly with masks W/2 .. 1 — at the (V, W) resolve_sddmm answers for WIDTH F and the operands' element size. V counts elements,
+// divides F, and V elements' bytes (4 V; 16-bit operands: 2 V, V up to 8) divide both base addresses, so every head slice of every row is a legal V-vector address and no vector spans two heads: head h has the bits of the
 // single-head product on D1[:, hF:(h+1)F] and D2[:, hF:(h+1)F], whatever H, the form or the route.
 //
 // The kernel is the edge-parallel kernel of sddmm_edge.h with the (edge, head) PAIR q = e H + h as the unit of work: a wavefront owns
@@ -24,6 +25,9 @@ namespace gespmm {
 // r.route == kSddmmHeadsKernel. rows: row ids (r.form == kSddmmCooEdge) or row pointers (kSddmmCsrEdge). nnz H <= kSddmmMaxNnz, F >= 1.
 hipError_t launch_sddmm_heads(const int32_t* rows, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t M,
                               int64_t nnz, int64_t H, int64_t F, const SddmmHeadsLaunch& r, hipStream_t st);
+// The same on 16-bit operands (dtype kX16F16 / kX16Bf16; out stays fp32): r is resolve_sddmm_heads' answer at element size 2.
+hipError_t launch_sddmm_heads_x16(const int32_t* rows, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype,
+                                  int64_t M, int64_t nnz, int64_t H, int64_t F, const SddmmHeadsLaunch& r, hipStream_t st);
 // *result = max(0, max_i idx[i]) — the composition route's bound on the rows of D2 a CSR call touches (the call does not carry K).
 hipError_t launch_max_index(const int32_t* idx, int64_t n, int32_t* result, hipStream_t st);
 // dst[dst_index[p] H + h] = src[p H + h]: a plan's clustered edge order back into the caller's (H words per edge).

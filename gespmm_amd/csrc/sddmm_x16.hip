@@ -10,6 +10,12 @@
 // the bits depend on (V, W) alone — resolve_sddmm at element size 2: V up to 8, a V = 8 edge in the registers a V = 4 fp32 edge has.
 // There is no composition route: every N and every 2-byte aligned address runs one of these kernels, and the only temporary is
 // the blocked form's split points.
+//
+// The multi-head form (gespmm_sddmm_{coo,csr}_heads_x16) is the kernel of sddmm_heads.h on the same trait: head h has the bits of the
+// single-head call above on the contiguous copies of its slices, at the same (V, W).
+
+#define GESPMM_SDDMM_HEADS_KERNELS
+#include "sddmm_heads.h"
 
 #include "sddmm_edge.h"
 #include "spmm_device.h"
@@ -58,6 +64,15 @@ hipError_t launch_sddmm_x16(const int32_t* rows, bool csr, const int32_t* colind
     const uint16_t* d2 = static_cast<const uint16_t*>(D2);
     if (dtype == kX16F16) return launch_sddmm_op<SddmmX16<kX16F16>>(rows, csr, colind, d1, d2, out, M, nnz, N, st);
     if (dtype == kX16Bf16) return launch_sddmm_op<SddmmX16<kX16Bf16>>(rows, csr, colind, d1, d2, out, M, nnz, N, st);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_sddmm_heads_x16(const int32_t* rows, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype,
+                                  int64_t M, int64_t nnz, int64_t H, int64_t F, const SddmmHeadsLaunch& r, hipStream_t st) {
+    const uint16_t* d1 = static_cast<const uint16_t*>(D1);
+    const uint16_t* d2 = static_cast<const uint16_t*>(D2);
+    if (dtype == kX16F16) return launch_sddmm_heads_op<SddmmX16<kX16F16>>(rows, colind, d1, d2, out, M, nnz, H, F, r, st);
+    if (dtype == kX16Bf16) return launch_sddmm_heads_op<SddmmX16<kX16Bf16>>(rows, colind, d1, d2, out, M, nnz, H, F, r, st);
     return hipErrorInvalidValue;
 }
 

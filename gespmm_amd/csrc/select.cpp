@@ -276,9 +276,10 @@ SddmmLaunch resolve_sddmm(bool csr, int64_t M, int64_t nnz, int64_t N, int d1_al
 // (profiles/r09/sddmm_heads/timing.log). The composition is left with CSR calls past the pair limit, and with the pin.
 // Edges per wavefront: the fp32 thresholds of resolve_sddmm applied to the PAIR count nnz H (carried over, not measured on their own)
 // give pairs per wavefront — COO G * UE, CSR 256 / 64 / max(G * UE, 16) — and epw is that many pairs in whole edges, 1 .. 256.
+// elem_size 2 (fp16 / bf16 operands): V, W and the form are resolve_sddmm's at that element size; route and epw do not look at it.
 SddmmHeadsLaunch resolve_sddmm_heads(bool csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, bool capturing,
-                                     int pin) {
-    const SddmmLaunch b = resolve_sddmm(csr, M, nnz, F, d1_align, d2_align, capturing, 4);
+                                     int pin, int elem_size) {
+    const SddmmLaunch b = resolve_sddmm(csr, M, nnz, F, d1_align, d2_align, capturing, elem_size);
     SddmmHeadsLaunch r = {kSddmmHeadsComposition, b.form, b.V, b.W, 0, 0};
     if (H == 1) {
         r.route = kSddmmHeadsPlain;

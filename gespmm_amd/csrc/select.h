@@ -55,9 +55,9 @@ struct SddmmHeadsLaunch {
     uint32_t magic;  // kernel: ceil(2^32 / H) where t / H == umulhi(t, magic) for every t < 256 H, else 0 (the kernel divides)
 };
 // pin: GESPMM_SDDMM_HEADS_ROUTE of the caller (kernel: ignored where the kernel cannot run; composition: CSR form off a capturing
-// stream only). nnz > 0, H >= 1.
+// stream only). nnz > 0, H >= 1. elem_size: bytes per element of D1 / D2, as resolve_sddmm's (2: V up to 8).
 SddmmHeadsLaunch resolve_sddmm_heads(bool csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, bool capturing,
-                                     int pin = kSddmmHeadsPinNone);
+                                     int pin = kSddmmHeadsPinNone, int elem_size = 4);
 
 // ---- edge softmax (edge_softmax.h): the launch shape of forward and backward alike (gespmm_describe_edge_softmax prints W and L).
 constexpr int kEdgeSoftmaxIT = 4;                                // entries per lane a row may have to be read once (registers)

@@ -11,6 +11,11 @@
 //   V = 1: W = 4 .. 64 · V = 4: W = 32, 64 and two strips at W = 64 · V = 2 at W = 64 (one or two strips) · V = 1 with two strips at W = 64
 //   plans only: V = 4 at W = 4, 8, 16 (plan_policy.cpp: narrow_vec4)
 // Everything else — H = 1, H > kHeadsMax, 64-bit offsets — is the composition route (capi.cpp: per head gather, strict product, scatter).
+//
+// 16-bit B and C (gespmm_csr_spmm_heads_x16; kernels: spmm_heads_x16.hip): the same kernel body (spmm_heads_kernel.h) in 32-bit WORDS —
+// HeadsArgs then carries B and C as arrays of words, N = H F / 2 and F = the words of a head, F / 2 — for the storage-order geometries
+// above at the width in words. Odd F, operands that are only 2-byte aligned and everything the fp32 kernel leaves to its composition go
+// through widen, gespmm_csr_spmm_heads_f32, narrow (capi.cpp): the same bits.
 #pragma once
 #include "spmm_kernels.h"
 
@@ -38,6 +43,10 @@ inline bool heads_geometry_served(const Geometry& g, bool planned) {
 
 // a.tasks + a.perm set: the plan-mode kernels. hipErrorInvalidValue where the geometry is not served or H is outside 2 .. kHeadsMax.
 hipError_t launch_spmm_heads(const HeadsArgs& a, const Geometry& geo, hipStream_t st);
+// spmm_heads_x16.hip: `a` in words (above), storage order only (a.tasks == NULL); hipErrorInvalidValue where the geometry is not served.
+hipError_t launch_spmm_heads_x16(const HeadsArgs& a, int dtype, const Geometry& geo, hipStream_t st);
+// ... and dst[r, 0:width] = src[r, off:off+width] on 16-bit elements (the per-head route of the 16-bit multi-head SDDMM)
+hipError_t launch_heads_slice_x16(const void* src, void* dst, int64_t rows, int64_t stride, int64_t off, int64_t width, hipStream_t st);
 // The composition route's two copies: dst[r, 0:width] = src[r, off:off+width] (src rows `stride` floats apart) and its inverse
 // dst[r, off:off+width] = src[r, 0:width].
 hipError_t launch_heads_slice(const float* src, float* dst, int64_t rows, int64_t stride, int64_t off, int64_t width, hipStream_t st);

@@ -42,6 +42,10 @@ Attention layers (extension): ``MultiHeadSPMMFunction`` is the aggregation with 
 the dot-product score s[e, h] = <q[row(e), h, :], k[col(e), h, :]>; each has the other as its backward (``spmm.csr_spmm_heads``,
 ``sddmm.csr_sddmm_heads``). ``MultiHeadSPMMFunction(..., heads_sddmm=True)`` computes the edge-weight gradient in one multi-head SDDMM
 instead of one ``sddmm.csr_sddmm`` per head on copies (the default, kept as it was): same bits.
+16-bit attention (extension): both functions take fp16 / bf16 node tensors (``feat``; ``q`` and ``k``) and run forward and backward on
+``spmm.csr_spmm_heads_x16`` / ``sddmm.csr_sddmm_heads_x16``; everything edge-sized — scores, weights, their gradients — stays fp32.
+``GATConv`` (default and ``fused_score=True`` paths) and ``TransformerConv(fused=False)`` therefore work as ``.half()`` / ``.bfloat16()``
+models and under ``torch.autocast``; the fused aggregation / backward, ``GATv2Conv`` and ``TransformerConv(fused=True)`` are fp32 only.
 ``EdgeSoftmaxFunction`` is the step between the two — softmax over the entries of each row, per head, with the leaky ReLU of a GAT
 fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` the graph attention layer composed from the three.
 ``GATSoftmaxFunction`` is the first two in one: the softmax of el[row] + er[col] with no score array (``GATConv(fused_score=True)``).
@@ -68,6 +72,10 @@ from . import softmax as _softmax
 from . import spmm as _spmm
 
 _warned_no_grad = False
+
+
+def _is_x16(t):
+    return isinstance(t, torch.Tensor) and t.dtype in (torch.float16, torch.bfloat16)
 
 
 class SPMMFunction(torch.autograd.Function):
@@ -169,15 +177,26 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
     ``sddmm.csr_sddmm`` per head on contiguous copies, with ``heads_sddmm=True`` as ONE ``sddmm.csr_sddmm_heads(rowptr, colind, grad_out,
     feat, plan=forward plan)`` on the tensors as they are (no copies, one launch). The two settings give the same bits on
     torch-allocated tensors (16-byte aligned: the per-head copies and the head slices take the same vector width).
-    Index tensors get no gradient."""
+    Index tensors get no gradient.
+
+    16-bit ``feat`` (fp16 / bf16) with fp32 ``weight``: the output has ``feat``'s dtype (``spmm.csr_spmm_heads_x16``: fp32 sums, one
+    rounding), grad_feat is ``csr_spmm_heads_x16`` on the CSC arrays with ``weight[csc_order]``, grad_weight stays fp32 —
+    ``sddmm.csr_sddmm_heads_x16(rowptr, colind, grad_out, feat)`` with ``heads_sddmm=True``, the 16-bit ``sddmm.csr_sddmm`` per head
+    otherwise. ``plans=`` with 16-bit tensors raises TypeError (the 16-bit multi-head ops have no plan form)."""
 
     @staticmethod
     def forward(ctx, rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None, heads_sddmm=False):
         fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
         ctx.fwd_plan = fwd_plan
         ctx.heads_sddmm = bool(heads_sddmm)
+        ctx.x16 = _is_x16(feat)
+        if ctx.x16 and plans is not None:
+            raise TypeError("plans= needs torch.float32 feat, got %s: spmm.csr_spmm_heads_x16 has no plan form" % feat.dtype)
         feat_c, weight_c = feat.contiguous(), weight.contiguous()
-        out = _spmm.csr_spmm_heads(rowptr, colind, weight_c, feat_c, plan=fwd_plan)
+        if ctx.x16:
+            out = _spmm.csr_spmm_heads_x16(rowptr, colind, weight_c, feat_c)
+        else:
+            out = _spmm.csr_spmm_heads(rowptr, colind, weight_c, feat_c, plan=fwd_plan)
         ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
         ctx.save_for_backward(feat_c, weight_c)
         return out
@@ -189,9 +208,14 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         grad_feat = grad_weight = None
         if ctx.needs_input_grad[5]:
-            grad_feat = _spmm.csr_spmm_heads(colptr, rowind, weight[csc_order].contiguous(), grad_out, plan=ctx.bwd_plan)
+            if ctx.x16:
+                grad_feat = _spmm.csr_spmm_heads_x16(colptr, rowind, weight[csc_order].contiguous(), grad_out)
+            else:
+                grad_feat = _spmm.csr_spmm_heads(colptr, rowind, weight[csc_order].contiguous(), grad_out, plan=ctx.bwd_plan)
         if ctx.needs_input_grad[6]:
-            if ctx.heads_sddmm:
+            if ctx.heads_sddmm and ctx.x16:
+                grad_weight = _sddmm.csr_sddmm_heads_x16(rowptr, colind, grad_out, feat)
+            elif ctx.heads_sddmm:
                 grad_weight = _sddmm.csr_sddmm_heads(rowptr, colind, grad_out, feat, plan=ctx.fwd_plan)
             else:
                 H = weight.shape[1]
@@ -210,14 +234,23 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
     return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the CSR and the CSC pattern. Backward is two
     multi-head products (``spmm.csr_spmm_heads``), each computed only for an input that requires grad:
     grad_q = A(grad_s) @ k on the CSR arrays, grad_k = A(grad_s)^T @ q on the CSC arrays with ``grad_s[csc_order]``.
-    Index tensors get no gradient."""
+    Index tensors get no gradient.
+
+    16-bit ``q`` and ``k`` (both fp16 or both bf16): the score stays fp32 (``sddmm.csr_sddmm_heads_x16``), grad_q / grad_k are
+    ``spmm.csr_spmm_heads_x16`` products with the fp32 ``grad_s`` and come back in the operands' dtype. ``plans=`` raises TypeError."""
 
     @staticmethod
     def forward(ctx, rowptr, colind, colptr, rowind, csc_order, q, k, plans=None):
         fwd_plan, ctx.bwd_plan = plans if plans is not None else (None, None)
         ctx.fwd_plan = fwd_plan
+        ctx.x16 = _is_x16(q) or _is_x16(k)
+        if ctx.x16 and plans is not None:
+            raise TypeError("plans= needs torch.float32 q and k, got %s: sddmm.csr_sddmm_heads_x16 has no plan form" % q.dtype)
         q_c, k_c = q.contiguous(), k.contiguous()
-        out = _sddmm.csr_sddmm_heads(rowptr, colind, q_c, k_c, plan=fwd_plan)
+        if ctx.x16:
+            out = _sddmm.csr_sddmm_heads_x16(rowptr, colind, q_c, k_c)
+        else:
+            out = _sddmm.csr_sddmm_heads(rowptr, colind, q_c, k_c, plan=fwd_plan)
         ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
         ctx.save_for_backward(q_c, k_c)
         return out
@@ -228,6 +261,12 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
         q, k = ctx.saved_tensors
         grad_s = grad_s.contiguous()
         grad_q = grad_k = None
+        if ctx.x16:
+            if ctx.needs_input_grad[5]:
+                grad_q = _spmm.csr_spmm_heads_x16(rowptr, colind, grad_s, k)
+            if ctx.needs_input_grad[6]:
+                grad_k = _spmm.csr_spmm_heads_x16(colptr, rowind, grad_s[csc_order].contiguous(), q)
+            return None, None, None, None, None, grad_q, grad_k, None
         if ctx.needs_input_grad[5]:
             grad_q = _spmm.csr_spmm_heads(rowptr, colind, grad_s, k, plan=ctx.fwd_plan)
         if ctx.needs_input_grad[6]:
@@ -567,7 +606,12 @@ class GATConv(torch.nn.Module):
     In ``eval()`` mode or with ``dropout == 0`` the layer makes exactly the launches it makes without the argument.
 
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
-    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
+    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``.
+
+    16-bit features (a ``.half()`` / ``.bfloat16()`` layer, or ``torch.autocast``), default and ``fused_score=True`` paths: ``xw`` stays
+    16-bit, ``el`` and ``er`` — node-sized — are computed by torch from it and widened (``.float()``), score, softmax and dropout are the
+    unchanged fp32 ops, the aggregation is the 16-bit product (``MultiHeadSPMMFunction`` on ``spmm.csr_spmm_heads_x16``: fp32 sums, one
+    rounding) and the bias add is torch's. ``fused_aggregate`` / ``fused_backward`` are fp32 only: 16-bit features raise TypeError."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
                  fused_aggregate=False, fused_backward=False, dropout=0.0):
@@ -607,8 +651,11 @@ class GATConv(torch.nn.Module):
         if rowptr.numel() != n + 1 or colptr.numel() != n + 1:
             raise ValueError("GATConv needs a square graph: rowptr and colptr must have x.size(0) + 1 entries")
         xw = (x @ self.weight).view(n, H, F)
-        el = (xw * self.att_dst).sum(-1)
-        er = (xw * self.att_src).sum(-1)
+        if self.fused_aggregate and _is_x16(xw):
+            raise TypeError("GATConv(fused_aggregate=True / fused_backward=True) needs torch.float32 features, got %s: "
+                            "spmm.gat_aggregate (GATAggregateFunction) is fp32 only" % xw.dtype)
+        el = (xw * self.att_dst).sum(-1).float()  # (node-sized; fp32 features: the same tensor)
+        er = (xw * self.att_src).sum(-1).float()
         if self.fused_aggregate:
             if seed is None:
                 out = GATAggregateFunction.apply(rowptr, colind, colptr, rowind, csc_order, el, er, xw, self.negative_slope,
@@ -698,7 +745,8 @@ class GATv2Conv(torch.nn.Module):
     The ``[nnz, H]`` score and alpha arrays exist (folding the score into the softmax or the aggregation is out of scope).
 
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
-    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only."""
+    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only: the fused edge score and its
+    backward have no 16-bit form (the 16-bit multi-head ops serve ``GATConv`` and ``TransformerConv(fused=False)``)."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0):
         super().__init__()
@@ -821,7 +869,11 @@ class TransformerConv(torch.nn.Module):
     switches the bias of the four linear maps, as in PyG. ``beta`` needs ``root_weight``.
 
     The graph is square (row r and column r are the same node); ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K,
-    return_order=True)`` (``csc_order`` int32; the fused path does not read it). fp32 only."""
+    return_order=True)`` (``csc_order`` int32; the fused path does not read it).
+
+    16-bit ``x`` (a ``.half()`` / ``.bfloat16()`` layer, or ``torch.autocast``) with ``fused=False``: q, k and v stay 16-bit, the score
+    (``MultiHeadSDDMMFunction`` on ``sddmm.csr_sddmm_heads_x16``), the scaling, softmax and dropout are fp32, the aggregation is the 16-bit
+    product. ``fused=True`` — the fused dot-product attention kernels — is fp32 only: 16-bit features raise TypeError."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, bias=True, root_weight=True, fused=False,
                  attn_seed=None):
@@ -871,6 +923,9 @@ class TransformerConv(torch.nn.Module):
         k = self.lin_key(x).view(n, H, F)
         v = self.lin_value(x).view(n, H, F)
         scale = 1.0 / math.sqrt(F)
+        if self.fused and (_is_x16(q) or _is_x16(k) or _is_x16(v)):
+            raise TypeError("TransformerConv(fused=True) needs torch.float32 features, got %s: attention.dot_attention "
+                            "(DotAttentionFunction) is fp32 only; fused=False serves fp16 / bf16" % q.dtype)
         if self.fused:
             out = DotAttentionFunction.apply(q, k, v, rowptr, colind, colptr, rowind, scale, p, seed)
         else:

@@ -19,8 +19,13 @@ Multi-head form (extension; gespmm_sddmm_{coo,csr}_heads_f32, gespmm_plan_sddmm_
 
 D1 f32[M, H, F], D2 f32[K, H, F]: out[e, h] = <D1[row(e), h, :], D2[col(e), h, :]> — the attention score of a dot-product attention
 layer, or the edge-weight gradient of ``spmm.csr_spmm_heads`` — in ONE kernel that finds the row and column of an edge once for all
-heads. Head h has the bits of ``csr_sddmm`` on ``D1[:, h, :].contiguous()`` and ``D2[:, h, :].contiguous()``. fp32 only: 16-bit
-operands raise TypeError.
+heads. Head h has the bits of ``csr_sddmm`` on ``D1[:, h, :].contiguous()`` and ``D2[:, h, :].contiguous()``. These two are fp32 only
+(16-bit operands raise TypeError); fp16 / bf16 operands have names of their own (gespmm_sddmm_{coo,csr}_heads_x16):
+
+    coo_sddmm_heads_x16(rowind, colind, D1, D2, out=None) -> f32[nnz, H]
+    csr_sddmm_heads_x16(rowptr, colind, D1, D2, out=None) -> f32[nnz, H]
+
+D1 and D2 both ``torch.float16`` or both ``torch.bfloat16``; head h has the bits of the 16-bit ``csr_sddmm`` on the contiguous slices.
 
 GATv2 edge score (extension; gespmm_gatv2_score_f32, gespmm_gatv2_score_backward_f32):
 
@@ -165,6 +170,57 @@ def csr_sddmm_heads(rowptr, colind, D1, D2, out=None, plan=None):
         else:
             rc = lib.gespmm_sddmm_csr_heads_f32(_ptr(rowptr), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), M, H, F, nnz, _stream(dev))
     check(rc, "gespmm_plan_sddmm_heads_f32" if plan is not None else "gespmm_sddmm_csr_heads_f32")
+    return out
+
+
+def _checked_heads_x16(idx0, name0, colind, D1, D2):
+    """-> (device, H, F, GESPMM_X16_* code): rank-3 operands, both fp16 or both bf16, same H and F on both sides."""
+    from .spmm import _X16
+
+    _need(idx0, name0, torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    for t, name in ((D1, "D1"), (D2, "D2")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+    if D1.dtype not in _X16:
+        raise TypeError("D1 must have dtype torch.float16 or torch.bfloat16, got %s (fp32: the functions without _x16)" % D1.dtype)
+    for t, name in ((D1, "D1"), (D2, "D2")):
+        if t.dim() != 3:
+            raise ValueError("%s must be [rows, H, F]" % name)
+        _need(t, name, D1.dtype, 3)  # (mixed 16-bit dtypes: TypeError)
+    if D1.shape[1:] != D2.shape[1:]:
+        raise ValueError("D1 %s and D2 %s must have the same heads and columns" % (tuple(D1.shape), tuple(D2.shape)))
+    if D1.shape[1] < 1:
+        raise ValueError("D1 and D2 must have at least one head")
+    return _same_device(D1, D2, idx0, colind), D1.shape[1], D1.shape[2], _X16[D1.dtype]
+
+
+def coo_sddmm_heads_x16(rowind, colind, D1, D2, out=None):
+    """``coo_sddmm_heads`` on fp16 / bf16 operands (gespmm_sddmm_coo_heads_x16): the result stays f32[nnz, H]; see ``csr_sddmm_heads_x16``."""
+    dev, H, F, x16 = _checked_heads_x16(rowind, "rowind", colind, D1, D2)
+    nnz = rowind.numel()
+    if colind.numel() != nnz:
+        raise ValueError("rowind and colind must have the same length")
+    out = _heads_out(out, nnz, H, dev)
+    with _on_device(dev):
+        rc = lib.gespmm_sddmm_coo_heads_x16(_ptr(rowind), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), x16, H, F, nnz, _stream(dev))
+    check(rc, "gespmm_sddmm_coo_heads_x16")
+    return out
+
+
+def csr_sddmm_heads_x16(rowptr, colind, D1, D2, out=None):
+    """Multi-head SDDMM on 16-bit operands (gespmm_sddmm_csr_heads_x16): D1 [M, H, F] and D2 [K, H, F] both fp16 or both bf16, result
+    f32[nnz, H] — the fp32 score of a 16-bit dot-product attention layer, or the fp32 edge-weight gradient of ``spmm.csr_spmm_heads_x16``.
+    Every element is widened exactly at its FMA; head h has the bits of ``csr_sddmm(rowptr, colind, D1[:, h, :].contiguous(),
+    D2[:, h, :].contiguous())`` (``_lib.describe_sddmm_heads(..., x16=True)``). No plan form."""
+    dev, H, F, x16 = _checked_heads_x16(rowptr, "rowptr", colind, D1, D2)
+    M, nnz = D1.shape[0], colind.numel()
+    if rowptr.numel() != M + 1:
+        raise ValueError("rowptr must have D1.size(0)+1 entries")
+    out = _heads_out(out, nnz, H, dev)
+    with _on_device(dev):
+        rc = lib.gespmm_sddmm_csr_heads_x16(_ptr(rowptr), _ptr(colind), _ptr(D1), _ptr(D2), _ptr(out), x16, M, H, F, nnz, _stream(dev))
+    check(rc, "gespmm_sddmm_csr_heads_x16")
     return out
 
 

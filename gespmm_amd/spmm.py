@@ -412,7 +412,8 @@ def csr_spmm_heads(rowptr, colind, values, dense, out=None, plan=None):
     r (gespmm_csr_spmm_heads_f32 / gespmm_plan_spmm_heads_f32). ``values`` f32[nnz, H]; ``dense`` f32[K, H, F] or f32[K, H * F], the
     result has the matching rank. One fp32 fma chain per output element in strict CSR order, so head h has the bits of
     ``csr_spmm(rowptr, colind, values[:, h].contiguous(), dense[:, h, :].contiguous(), cfg={"flags": FLAG_STRICT_ORDER})``.
-    One kernel for 2 <= H <= 8 (``_lib.heads_route``), a per-head composition otherwise. fp32 only."""
+    One kernel for 2 <= H <= 8 (``_lib.heads_route``), a per-head composition otherwise. fp32 only (TypeError otherwise): fp16 / bf16
+    features go through ``csr_spmm_heads_x16``."""
     H, F, out = _heads_args(rowptr, colind, values, dense, out)
     dev = dense.device
     M, K = rowptr.numel() - 1, dense.shape[0]
@@ -424,6 +425,49 @@ def csr_spmm_heads(rowptr, colind, values, dense, out=None, plan=None):
             rc = lib.gespmm_csr_spmm_heads_f32(_ptr(rowptr), _ptr(colind), _ptr(values), _ptr(dense), _ptr(out), M, K, H, F, colind.numel(),
                                                _stream(dev))
     check(rc, "gespmm_plan_spmm_heads_f32" if plan is not None else "gespmm_csr_spmm_heads_f32")
+    return out
+
+
+def csr_spmm_heads_x16(rowptr, colind, values, dense, out=None):
+    """The multi-head product on 16-bit features (gespmm_csr_spmm_heads_x16): ``values`` f32[nnz, H] — edge-sized arrays stay fp32 —
+    ``dense`` fp16 or bf16, [K, H, F] or [K, H * F]; the result has the dtype and rank of ``dense``. Each output element is one fp32 fma
+    chain in strict CSR order, rounded once at the store: the bits of ``csr_spmm_heads(rowptr, colind, values, dense.float()).to(dense.dtype)``.
+    One kernel for 2 <= H <= 8, even F and 4-byte aligned operands (``_lib.heads_x16_route``), the composition widen / fp32 / narrow
+    otherwise (not on a capturing stream). No plan form."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    _need(values, "values", torch.float32, 2)
+    if not isinstance(dense, torch.Tensor):
+        raise TypeError("dense must be a torch.Tensor")
+    if dense.dtype not in _X16:
+        raise TypeError("dense must have dtype torch.float16 or torch.bfloat16, got %s (fp32: csr_spmm_heads)" % dense.dtype)
+    if dense.dim() not in (2, 3):
+        raise ValueError("dense must be [K, H, F] or [K, H * F]")
+    _need(dense, "dense", dense.dtype, dense.dim())
+    dev = _same_device(dense, rowptr, colind, values)
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have M+1 >= 1 entries")
+    M, K = rowptr.numel() - 1, dense.shape[0]
+    nnz, H = values.shape
+    if nnz != colind.numel():
+        raise ValueError("values must be [nnz, H] with nnz = %d rows, got %d" % (colind.numel(), nnz))
+    if H < 1:
+        raise ValueError("values must have at least one head")
+    N = dense.shape[1] * dense.shape[2] if dense.dim() == 3 else dense.shape[1]
+    if (dense.dim() == 3 and dense.shape[1] != H) or N % H != 0:
+        raise ValueError("dense of shape %s does not hold H = %d heads" % (tuple(dense.shape), H))
+    F = N // H
+    shape = (M, H, F) if dense.dim() == 3 else (M, N)
+    if out is None:
+        out = torch.empty(shape, dtype=dense.dtype, device=dev)
+    else:
+        _need(out, "out", dense.dtype, len(shape))
+        if tuple(out.shape) != shape or out.device != dev:
+            raise ValueError("out must be %s%s on the same device" % (dense.dtype, list(shape)))
+    with _on_device(dev):
+        rc = lib.gespmm_csr_spmm_heads_x16(_ptr(rowptr), _ptr(colind), _ptr(values), _ptr(dense), _ptr(out), _X16[dense.dtype], M, K, H, F,
+                                           nnz, _stream(dev))
+    check(rc, "gespmm_csr_spmm_heads_x16")
     return out
 
 

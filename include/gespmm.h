@@ -520,7 +520,8 @@ int gespmm_plan_x16_route(const gespmm_plan* plan, int64_t N, int b_align, int c
  * A matrix without entries (nnz == 0; val, colind and B may then be NULL) gives C = 0 on either route.
  * The environment variable GESPMM_HEADS_ROUTE=composition pins route 0 (a measurement knob, read with getenv on every call and route
  * query: do not change the environment from another thread while calls are in flight).
- * 16-bit operands, the max reducer and the fused vectors have no multi-head entry. Not part of gespmm_set_auto_plan.
+ * The max reducer and the fused vectors have no multi-head entry; 16-bit B and C have one of their own, gespmm_csr_spmm_heads_x16
+ * below (stateless only). Not part of gespmm_set_auto_plan.
  * GESPMM_EINVAL (H < 1, negative sizes, NULL pointers), GESPMM_EALIGN (a pointer not 4-byte aligned) and GESPMM_ERANGE (H F or nnz
  * beyond what the other entries take) are checked before any device work; M == 0 or H F == 0 returns 0 without looking at pointers.
  */
@@ -531,6 +532,30 @@ int gespmm_plan_spmm_heads_f32(gespmm_plan* plan, const float* val, const float*
    geometry_out: NULL or int32[4] — V, S, W and rows per wavefront of the kernel (zeros on route 0) */
 int gespmm_heads_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int b_align, int c_align, int32_t* geometry_out);
 int gespmm_plan_heads_route(const gespmm_plan* plan, int64_t H, int64_t F, int b_align, int c_align);
+/*
+ * The multi-head product on 16-bit dense operands (since 0.5): B [K x H F] and C [M x H F] hold IEEE fp16 or bfloat16 (dtype:
+ * GESPMM_X16_F16 / GESPMM_X16_BF16, both the same), val stays fp32 [nnz x H] — edge-sized arrays are fp32 everywhere in this library.
+ * C has the bits of narrow(gespmm_csr_spmm_heads_f32(val, widen(B))): every output element is one fp32 fmaf chain in strict CSR order,
+ * never re-associated and never held in 16 bits, rounded ONCE, to nearest even, at the store (overflow gives +-inf, NaN stays NaN);
+ * widening is exact, fp16 subnormals included.
+ * Routes (gespmm_heads_x16_route): 1 = ONE kernel, the multi-head batch-stream kernel working in 32-bit words (two elements each, both
+ * under the staged weight of their head): 2 <= H <= 8, F even, B and C 4-byte aligned (8 / 16 bytes allow wider vectors), 32-bit
+ * offsets (K H F 2 < 2^32, nnz H < 2^31) and a lane geometry of gespmm_heads_route's list resolved for the width in words, H F / 2,
+ * with V | F / 2; no workspace, no allocation: capturable. 0 = the composition — everything else: H = 1, H > 8, odd F, operands that are
+ * only 2-byte aligned, 64-bit offsets: B widened into a stream-ordered temporary from the library's pool, gespmm_csr_spmm_heads_f32
+ * into a second one, narrowed into C; the same bits; on a capturing stream it returns hipErrorStreamCaptureUnsupported and launches
+ * nothing. GESPMM_HEADS_X16_ROUTE=composition pins route 0 (a measurement knob, read with getenv on every call and route query).
+ * There is no plan form: a clustered plan's per-call permutation of the weights costs more than its order gains for this product.
+ * Checks before any device work: an unknown dtype, H < 1, negative sizes -> GESPMM_EINVAL; sizes beyond what the fp32 entry takes ->
+ * GESPMM_ERANGE; M == 0 or H F == 0 -> 0 without looking at pointers; NULL pointers -> GESPMM_EINVAL; B or C not 2-byte aligned, val,
+ * rowptr or colind not 4-byte aligned -> GESPMM_EALIGN. nnz == 0 (val, colind and B may then be NULL) gives C = all-zero bits on
+ * either route.
+ */
+int gespmm_csr_spmm_heads_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const void* B, void* C, int dtype,
+                              int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream);
+/* host only: the route of the call above (0 / 1, or GESPMM_E*), as gespmm_heads_route; geometry_out: V (in 32-bit words), S, W and rows
+   per wavefront of the kernel (zeros on route 0) */
+int gespmm_heads_x16_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int b_align, int c_align, int32_t* geometry_out);
 /*
  * Kernel choice by MEASUREMENT instead of by rule: runs the candidates of a clustered plan (batch-stream, segmented-stream,
  * staged-rows where the width is served, and at N <= 64 the batch-stream kernel with 4 floats per lane) `reps` (0 = 3) times each on these operands, synchronously, and fixes the plan
@@ -572,7 +597,7 @@ int gespmm_plan_sddmm_route(const gespmm_plan* plan, int64_t N);
  * is ignored where the kernel cannot run, "composition" in COO form and on a capturing stream).
  * Checks, before any device work and in the order of gespmm_sddmm_*_f32: negative sizes or H < 1 -> GESPMM_EINVAL; M, nnz, H, H F (and,
  * in COO form, nnz H) out of range -> GESPMM_ERANGE; nnz == 0 -> 0 without looking at pointers; NULL -> GESPMM_EINVAL; a pointer not
- * 4-byte aligned -> GESPMM_EALIGN. F == 0 writes nnz H zeros. fp32 only.
+ * 4-byte aligned -> GESPMM_EALIGN. F == 0 writes nnz H zeros. fp32 operands; fp16 / bf16: the *_heads_x16 forms below.
  */
 int gespmm_sddmm_coo_heads_f32(const int32_t* rowind, const int32_t* colind, const float* D1, const float* D2, float* out, int64_t H,
                                int64_t F, int64_t nnz, void* stream);
@@ -583,6 +608,20 @@ int gespmm_sddmm_csr_heads_f32(const int32_t* rowptr, const int32_t* colind, con
  * (nnz == 0). Arguments and return value as gespmm_describe_sddmm. */
 int gespmm_describe_sddmm_heads(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing, char* out,
                                 int64_t capacity);
+/*
+ * The multi-head SDDMM on 16-bit operands (since 0.5): D1 [M x H F] and D2 [K x H F] both IEEE fp16 or both bfloat16 (dtype as in
+ * gespmm_sddmm_csr_x16), out fp32 [nnz x H]. Head h has the bits of gespmm_sddmm_csr_x16 on contiguous copies of the two head slices
+ * with the same alignment class, at the (V, W) gespmm_describe_sddmm_x16 answers for N = F: V counts elements (up to 8), divides F, and
+ * 2 V bytes divide both base addresses. Routes, pin and checks are those of the fp32 forms above — the composition copies 16-bit slices
+ * and calls gespmm_sddmm_csr_x16's launch per head — with the dtype checked first (GESPMM_EINVAL) and D1 / D2 2-byte aligned.
+ */
+int gespmm_sddmm_coo_heads_x16(const int32_t* rowind, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype,
+                               int64_t H, int64_t F, int64_t nnz, void* stream);
+int gespmm_sddmm_csr_heads_x16(const int32_t* rowptr, const int32_t* colind, const void* D1, const void* D2, float* out, int dtype,
+                               int64_t M, int64_t H, int64_t F, int64_t nnz, void* stream);
+/* host only: gespmm_describe_sddmm_heads for the two calls above (alignments from 2 bytes) */
+int gespmm_describe_sddmm_heads_x16(int csr, int64_t M, int64_t nnz, int64_t H, int64_t F, int d1_align, int d2_align, int capturing,
+                                    char* out, int64_t capacity);
 /* ... on the plan's pattern, out in the caller's CSR edge order, the same bits. The three routes of gespmm_plan_sddmm_f32, decided by the
  * same rule at the width of the gathered row, H F (gespmm_plan_sddmm_heads_route: 0 the stateless CSR call, 1 the COO form of the heads
  * kernel on row ids the plan expands once, 2 the clustered edge order into a plan-owned [nnz, H] temporary + a scatter of H words per
