@@ -15,6 +15,8 @@ Layout (only what the hot path needs):
 
 There is no CPU compute path anywhere in this package.
 """
+import torch  # noqa: F401  FIRST: libgespmm.so then binds to the HIP runtime torch brings. Loaded before torch it pulls in the system's
+#                     copy, torch adds its own, and every call of the library answers "no ROCm-capable device is detected".
 from . import _lib  # noqa: F401  (loads libgespmm.so, raises if it is not built)
 from . import spmm, sddmm, softmax, attention, graphs  # noqa: F401
 from .op import SPMMFunction, FusedGCNFunction, MultiHeadSPMMFunction, MultiHeadSDDMMFunction, EdgeSoftmaxFunction, EdgeDropoutFunction, GATSoftmaxFunction, GATAggregateFunction, GATv2ScoreFunction, GCNConv, GATConv, GATv2Conv, SpmmMaxFunction, SAGEConv, DotAttentionFunction, TransformerConv  # noqa: F401

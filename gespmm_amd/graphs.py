@@ -437,12 +437,47 @@ def relabel_by_order(rowptr, colind, order):
     return rp.to(torch.int32), c.to(torch.int32)
 
 
+def take_edges(x, order, chunk_rows=1 << 24):
+    """A contiguous copy of ``x[order]`` for per-edge data ``x`` of shape [nnz] or [nnz, ...] and an int32 / int64 edge order of length
+    nnz (``csc_order`` of ``transpose_csr``), gathered in pieces of at most ``chunk_rows`` index rows into one preallocated result.
+
+    Why not ``x[order]``: on torch 2.10.0+rocm7.0 both advanced indexing and ``torch.index_select`` leave rows ``len(order) - 2^26 ..``
+    of the result UNWRITTEN when a row is 16 bytes (fp32 [nnz, 4], bf16 / fp16 [nnz, 8]) and there are more than 2^26 index rows — one
+    workgroup of 64 threads per row, and rows * 64 wraps modulo 2^32 (DESIGN.md §10 item 8 has the probe). Any piece below 2^26 rows
+    is safe; 2^24 leaves a factor of four and costs eight launches at 2^27 edges. Every place of this package that permutes an edge
+    array goes through here.
+
+    The bits are those of a copy. ``x`` may be non-contiguous and of any dtype; nnz = 0 gives an empty result. A wrong length raises
+    ValueError; an entry outside [0, nnz) raises IndexError on CPU tensors (on the device it is torch's own device-side check, as
+    with ``x[order]``). When ``x`` requires grad under an enabled grad mode the pieces are concatenated instead, so the result stays
+    differentiable; the layers of this package call it on detached tensors."""
+    if order.dim() != 1 or x.dim() < 1 or order.numel() != x.shape[0]:
+        raise ValueError("take_edges: order must be 1-D with one entry per row of x, got order %s for x %s" % (
+            tuple(order.shape), tuple(x.shape)))
+    if order.dtype not in (torch.int32, torch.int64):
+        raise TypeError("take_edges: order must be torch.int32 or torch.int64, got %s" % order.dtype)
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("take_edges: chunk_rows must be positive, got %d" % chunk_rows)
+    n = order.numel()
+    if n and not x.is_cuda and (int(order.min()) < 0 or int(order.max()) >= n):
+        raise IndexError("take_edges: order has an entry outside [0, %d)" % n)
+    if x.requires_grad and torch.is_grad_enabled():
+        if n == 0:
+            return x.index_select(0, order).contiguous()
+        return torch.cat([x.index_select(0, order[a:a + chunk_rows]) for a in range(0, n, chunk_rows)])
+    out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    for a in range(0, n, chunk_rows):
+        torch.index_select(x, 0, order[a:a + chunk_rows], out=out[a:a + chunk_rows])
+    return out
+
+
 def transpose_csr(rowptr, colind, K=None, val=None, return_order=False):
     """CSC arrays (colptr, rowind[, cscval]) of a CSR pattern, rows ascending inside a
     column — host-side helper for callers that build both orders once, like
     gcn_custom.py:39-46 does with scipy. Pure index manipulation with torch ops.
-    ``return_order=True`` appends the int64 edge order: CSC position i holds CSR entry order[i] (so ``w[order]`` puts per-edge data of
-    any shape [nnz, ...] into CSC order). The sort is stable: repeated edges keep their CSR order, the same on every call."""
+    ``return_order=True`` appends the int64 edge order: CSC position i holds CSR entry order[i] (so ``take_edges(w, order)`` puts per-edge
+    data of any shape [nnz, ...] into CSC order; ``val`` goes through it too). The sort is stable: repeated edges keep their CSR order, the same on every call."""
     M = rowptr.numel() - 1
     K = M if K is None else K
     dev = rowptr.device
@@ -452,8 +487,8 @@ def transpose_csr(rowptr, colind, K=None, val=None, return_order=False):
     order = torch.argsort(key, stable=True)
     colptr = torch.zeros(K + 1, dtype=torch.int64, device=dev)
     colptr[1:] = torch.cumsum(torch.bincount(colind.to(torch.int64), minlength=K), 0)
-    rowind = rows[order].to(torch.int32)
-    out = (colptr.to(torch.int32), rowind) if val is None else (colptr.to(torch.int32), rowind, val[order])
+    rowind = take_edges(rows, order).to(torch.int32)
+    out = (colptr.to(torch.int32), rowind) if val is None else (colptr.to(torch.int32), rowind, take_edges(val, order))
     return out + (order,) if return_order else out
 
 

@@ -67,6 +67,7 @@ from torch.autograd.function import once_differentiable
 from torch.nn import Parameter
 
 from . import attention as _attention
+from . import graphs as _graphs
 from . import sddmm as _sddmm
 from . import softmax as _softmax
 from . import spmm as _spmm
@@ -172,7 +173,7 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
 
     ``feat`` f32[K, H, F], ``weight`` f32[nnz, H] in CSR edge order; ``colptr, rowind, csc_order`` =
     ``graphs.transpose_csr(rowptr, colind, K, return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the
-    CSR and the CSC pattern. Backward: grad_feat is the same product on the CSC arrays with ``weight[csc_order]``;
+    CSR and the CSC pattern. Backward: grad_feat is the same product on the CSC arrays with ``graphs.take_edges(weight, csc_order)``;
     grad_weight[e, h] = <grad_out[row(e), h, :], feat[col(e), h, :]> is computed only when ``weight`` requires grad — by default as one
     ``sddmm.csr_sddmm`` per head on contiguous copies, with ``heads_sddmm=True`` as ONE ``sddmm.csr_sddmm_heads(rowptr, colind, grad_out,
     feat, plan=forward plan)`` on the tensors as they are (no copies, one launch). The two settings give the same bits on
@@ -180,7 +181,7 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
     Index tensors get no gradient.
 
     16-bit ``feat`` (fp16 / bf16) with fp32 ``weight``: the output has ``feat``'s dtype (``spmm.csr_spmm_heads_x16``: fp32 sums, one
-    rounding), grad_feat is ``csr_spmm_heads_x16`` on the CSC arrays with ``weight[csc_order]``, grad_weight stays fp32 —
+    rounding), grad_feat is ``csr_spmm_heads_x16`` on the CSC arrays with ``graphs.take_edges(weight, csc_order)``, grad_weight stays fp32 —
     ``sddmm.csr_sddmm_heads_x16(rowptr, colind, grad_out, feat)`` with ``heads_sddmm=True``, the 16-bit ``sddmm.csr_sddmm`` per head
     otherwise. ``plans=`` with 16-bit tensors raises TypeError (the 16-bit multi-head ops have no plan form)."""
 
@@ -209,9 +210,9 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
         grad_feat = grad_weight = None
         if ctx.needs_input_grad[5]:
             if ctx.x16:
-                grad_feat = _spmm.csr_spmm_heads_x16(colptr, rowind, weight[csc_order].contiguous(), grad_out)
+                grad_feat = _spmm.csr_spmm_heads_x16(colptr, rowind, _graphs.take_edges(weight, csc_order), grad_out)
             else:
-                grad_feat = _spmm.csr_spmm_heads(colptr, rowind, weight[csc_order].contiguous(), grad_out, plan=ctx.bwd_plan)
+                grad_feat = _spmm.csr_spmm_heads(colptr, rowind, _graphs.take_edges(weight, csc_order), grad_out, plan=ctx.bwd_plan)
         if ctx.needs_input_grad[6]:
             if ctx.heads_sddmm and ctx.x16:
                 grad_weight = _sddmm.csr_sddmm_heads_x16(rowptr, colind, grad_out, feat)
@@ -233,7 +234,7 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
     ``q`` f32[M, H, F], ``k`` f32[K, H, F]; ``colptr, rowind, csc_order`` = ``graphs.transpose_csr(rowptr, colind, K,
     return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the CSR and the CSC pattern. Backward is two
     multi-head products (``spmm.csr_spmm_heads``), each computed only for an input that requires grad:
-    grad_q = A(grad_s) @ k on the CSR arrays, grad_k = A(grad_s)^T @ q on the CSC arrays with ``grad_s[csc_order]``.
+    grad_q = A(grad_s) @ k on the CSR arrays, grad_k = A(grad_s)^T @ q on the CSC arrays with ``graphs.take_edges(grad_s, csc_order)``.
     Index tensors get no gradient.
 
     16-bit ``q`` and ``k`` (both fp16 or both bf16): the score stays fp32 (``sddmm.csr_sddmm_heads_x16``), grad_q / grad_k are
@@ -265,12 +266,12 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
             if ctx.needs_input_grad[5]:
                 grad_q = _spmm.csr_spmm_heads_x16(rowptr, colind, grad_s, k)
             if ctx.needs_input_grad[6]:
-                grad_k = _spmm.csr_spmm_heads_x16(colptr, rowind, grad_s[csc_order].contiguous(), q)
+                grad_k = _spmm.csr_spmm_heads_x16(colptr, rowind, _graphs.take_edges(grad_s, csc_order), q)
             return None, None, None, None, None, grad_q, grad_k, None
         if ctx.needs_input_grad[5]:
             grad_q = _spmm.csr_spmm_heads(rowptr, colind, grad_s, k, plan=ctx.fwd_plan)
         if ctx.needs_input_grad[6]:
-            grad_k = _spmm.csr_spmm_heads(colptr, rowind, grad_s[csc_order].contiguous(), q, plan=ctx.bwd_plan)
+            grad_k = _spmm.csr_spmm_heads(colptr, rowind, _graphs.take_edges(grad_s, csc_order), q, plan=ctx.bwd_plan)
         return None, None, None, None, None, grad_q, grad_k, None
 
 

@@ -126,10 +126,10 @@ def measure(rp, ci, csc, K, H, F, launches, b_limit):
     def b_bwd():
         alpha = kept["alpha"]
         ga = sddmm.csr_sddmm_heads(rp, ci, go, v)
-        kept["gv"] = spmm.csr_spmm_heads(colptr, rowind, alpha[order].contiguous(), go)
+        kept["gv"] = spmm.csr_spmm_heads(colptr, rowind, graphs.take_edges(alpha, order), go)
         gs = softmax.edge_softmax_backward(rp, alpha, ga) * scale
         kept["gq"] = spmm.csr_spmm_heads(rp, ci, gs, k)
-        kept["gk"] = spmm.csr_spmm_heads(colptr, rowind, gs[order].contiguous(), q)
+        kept["gk"] = spmm.csr_spmm_heads(colptr, rowind, graphs.take_edges(gs, order), q)
 
     b_fwd(), b_bwd()
     res["rel"] = sampled_errors(rp, ci, colptr, rowind, q, k, v, go, stats, delta, scale, (out, gq, gk, gv))
