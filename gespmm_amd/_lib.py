@@ -142,6 +142,10 @@ EXPORTS = [
     "gespmm_csr_spmm_max_arg_f32",
     "gespmm_csr_spmm_max_backward_f32",
     "gespmm_max_arg_route",
+    "gespmm_csr_spmm_heads_order_f32",
+    "gespmm_csr_spmm_heads_order_x16",
+    "gespmm_plan_spmm_heads_order_f32",
+    "gespmm_edge_gather",
 ]
 
 X16_F16 = 1
@@ -289,6 +293,14 @@ def _load():
     lib.gespmm_csr_spmm_heads_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_int64, p]
     lib.gespmm_plan_spmm_heads_f32.restype = c_int
     lib.gespmm_plan_spmm_heads_f32.argtypes = [p, p, p, p, c_int64, c_int64, p]
+    lib.gespmm_csr_spmm_heads_order_f32.restype = c_int
+    lib.gespmm_csr_spmm_heads_order_f32.argtypes = [p, p, p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_int64, p]
+    lib.gespmm_csr_spmm_heads_order_x16.restype = c_int
+    lib.gespmm_csr_spmm_heads_order_x16.argtypes = [p, p, p, p, p, p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, p]
+    lib.gespmm_plan_spmm_heads_order_f32.restype = c_int
+    lib.gespmm_plan_spmm_heads_order_f32.argtypes = [p, p, p, p, p, c_int64, c_int64, p]
+    lib.gespmm_edge_gather.restype = c_int
+    lib.gespmm_edge_gather.argtypes = [p, p, c_int, p, c_int64, c_int64, p]
     lib.gespmm_heads_route.restype = c_int
     lib.gespmm_heads_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, p]
     lib.gespmm_plan_heads_route.restype = c_int

@@ -302,7 +302,7 @@ int run_spmm_x16(const CsrView& A, const void* B, void* C, int dtype, int64_t N,
 // selector resolves for width N = H F with the batch-stream kernel forced, strict order and no cache blocking; V is limited to what
 // divides F (a lane's vector stays inside one head) and to what B and C can be addressed with. The stream is never asked.
 int run_spmm_heads(const CsrView& A, const float* B, float* C, int64_t H, int64_t F, int flags, void* stream, int b_align, int c_align,
-                   bool dry_run, int* kind, Geometry* geo_out) {
+                   bool dry_run, int* kind, Geometry* geo_out, const int32_t* order) {
     *kind = 0;
     if (!valid_variant(A.variant)) return GESPMM_EINVAL;
     if (H < 2 || H > kHeadsMax || A.M <= 0 || F <= 0 || A.nnz < 0 || b_align < 4 || c_align < 4) return kHeadsUnavailable;
@@ -325,6 +325,8 @@ int run_spmm_heads(const CsrView& A, const float* B, float* C, int64_t H, int64_
     HeadsArgs a = stream_args<HeadsArgs>(A, B, C, N, r);
     a.H = (int32_t)H;
     a.F = (int32_t)F;
+    // (through an edge order: the ordered kernels, storage order only — a plan composes the order into its own copy of the weights)
+    if (order) return A.planned ? GESPMM_EINVAL : (int)launch_spmm_heads_order(a, order, 0, r.sel.geo, reinterpret_cast<hipStream_t>(stream));
     return (int)launch_spmm_heads(a, r.sel.geo, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -332,7 +334,7 @@ int run_spmm_heads(const CsrView& A, const float* B, float* C, int64_t H, int64_
 // the fp32 entry, narrow). The kernel works in 32-bit words, so the geometry is run_spmm_heads's for H heads of F / 2 WORDS: the width
 // H F / 2, V limited to what divides F / 2 and to what B and C can be addressed with. Storage order only; the stream is never asked.
 int run_spmm_heads_x16(const CsrView& A, const void* B, void* C, int dtype, int64_t H, int64_t F, void* stream, int b_align, int c_align,
-                       bool dry_run, int* kind, Geometry* geo_out) {
+                       bool dry_run, int* kind, Geometry* geo_out, const int32_t* order = nullptr) {
     *kind = 0;
     if (H < 2 || H > kHeadsMax || A.M <= 0 || F <= 0 || F % 2 != 0 || A.nnz < 0 || b_align < 4 || c_align < 4) return kHeadsUnavailable;
     // GESPMM_HEADS_X16_ROUTE=composition pins route 0 (read per call: scripts/heads_x16_timing.py measures both routes in one process)
@@ -354,6 +356,7 @@ int run_spmm_heads_x16(const CsrView& A, const void* B, void* C, int dtype, int6
     HeadsArgs a = stream_args<HeadsArgs>(A, static_cast<const float*>(B), static_cast<float*>(C), Nw, r);
     a.H = (int32_t)H;
     a.F = (int32_t)Fw;
+    if (order) return (int)launch_spmm_heads_order(a, order, dtype, r.sel.geo, reinterpret_cast<hipStream_t>(stream));
     return (int)launch_spmm_heads_x16(a, dtype, r.sel.geo, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -727,6 +730,74 @@ int gespmm_csr_spmm_heads_x16(const int32_t* rowptr, const int32_t* colind, cons
     if (rc == 0) rc = gespmm_csr_spmm_heads_f32(rowptr, colind, val, Bf, Cf, M, K, H, F, nnz, stream);
     if (rc == 0) rc = (int)launch_narrow_x16(Cf, C, dtype, M * N, st);
     return scratch.close(rc);
+}
+
+// The multi-head product with its weights read through an edge order (gespmm.h). order == NULL: the unordered entry, nothing else. The
+// ordered kernel exists exactly where the unordered one does (run_spmm_heads / run_spmm_heads_x16 answer for the same sizes and
+// alignments); everywhere else — and under GESPMM_HEADS_ORDER_ROUTE=composition, read per call (scripts/heads_order_timing.py measures
+// both routes in one process) — the composition: gather val through order into a stream-ordered temporary (launch_edge_gather), then the
+// unordered entry on it. Same bits: the kernel's row loop is the unordered kernel's on the same staged weights.
+static bool heads_order_pinned() {
+    const char* env = getenv("GESPMM_HEADS_ORDER_ROUTE");
+    return env && !strcmp(env, "composition");
+}
+
+// dtype 0: fp32 B and C; kX16F16 / kX16Bf16: 16-bit ones. Checked arguments, order != NULL, nnz > 0.
+static int heads_order_entry(const int32_t* rowptr, const int32_t* colind, const int32_t* order, const float* val, const void* B, void* C,
+                             int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream) {
+    int rc = kHeadsUnavailable, kind = 0;
+    if (!heads_order_pinned()) {
+        const CsrView A = csr_view(rowptr, colind, val, M, K, nnz, GESPMM_VARIANT_AUTO);
+        rc = dtype == 0 ? run_spmm_heads(A, static_cast<const float*>(B), static_cast<float*>(C), H, F, 0, stream, pointer_alignment(B),
+                                         pointer_alignment(C), false, &kind, nullptr, order)
+                        : run_spmm_heads_x16(A, B, C, dtype, H, F, stream, pointer_alignment(B), pointer_alignment(C), false, &kind, nullptr, order);
+    }
+    if (rc != kHeadsUnavailable) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t v_bytes = (size_t)nnz * (size_t)H * 4;
+    PooledScratch scratch;
+    if ((rc = scratch.open(v_bytes, st)) != 0) return rc;  // (nothing launched; a capturing stream: what every allocating composition returns)
+    float* vo = scratch.take(v_bytes);
+    rc = (int)launch_edge_gather(val, order, false, vo, nnz, H * 4, st);
+    if (rc == 0)
+        rc = dtype == 0 ? gespmm_csr_spmm_heads_f32(rowptr, colind, vo, static_cast<const float*>(B), static_cast<float*>(C), M, K, H, F, nnz, stream)
+                        : gespmm_csr_spmm_heads_x16(rowptr, colind, vo, B, C, dtype, M, K, H, F, nnz, stream);
+    return scratch.close(rc);
+}
+
+int gespmm_csr_spmm_heads_order_f32(const int32_t* rowptr, const int32_t* colind, const int32_t* order, const float* val, const float* B,
+                                    float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream) {
+    if (!order) return gespmm_csr_spmm_heads_f32(rowptr, colind, val, B, C, M, K, H, F, nnz, stream);
+    int rc = check_heads_sizes(M, K, H, F, nnz);
+    if (rc != 0) return rc;
+    if (M == 0 || F == 0) return 0;
+    rc = check_pointers({{rowptr, 4, true}, {C, 4, true}, {colind, 4, nnz != 0}, {B, 4, nnz != 0}, {val, 4, nnz != 0}, {order, 4, false}});
+    if (rc != 0) return rc;
+    if (nnz == 0) return gespmm_csr_spmm_heads_f32(rowptr, nullptr, nullptr, nullptr, C, M, K, H, F, 0, stream);  // C = 0, no edge array is read
+    return heads_order_entry(rowptr, colind, order, val, B, C, 0, M, K, H, F, nnz, stream);
+}
+
+int gespmm_csr_spmm_heads_order_x16(const int32_t* rowptr, const int32_t* colind, const int32_t* order, const float* val, const void* B,
+                                    void* C, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream) {
+    if (!order) return gespmm_csr_spmm_heads_x16(rowptr, colind, val, B, C, dtype, M, K, H, F, nnz, stream);
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    int rc = check_heads_sizes(M, K, H, F, nnz);
+    if (rc != 0) return rc;
+    if (M == 0 || F == 0) return 0;
+    rc = check_pointers({{rowptr, 4, true}, {C, 2, true}, {colind, 4, nnz != 0}, {B, 2, nnz != 0}, {val, 4, nnz != 0}, {order, 4, false}});
+    if (rc != 0) return rc;
+    if (nnz == 0) return gespmm_csr_spmm_heads_x16(rowptr, nullptr, nullptr, nullptr, C, dtype, M, K, H, F, 0, stream);
+    return heads_order_entry(rowptr, colind, order, val, B, C, dtype, M, K, H, F, nnz, stream);
+}
+
+// out[i, :] = x[order[i], :] (gespmm.h): the gather behind graphs.take_edges and behind the composition above.
+int gespmm_edge_gather(const void* x, const void* order, int order_is_64, void* out, int64_t n, int64_t row_bytes, void* stream) {
+    if (n < 0 || row_bytes < 4 || row_bytes % 4 != 0 || row_bytes > 64 || (order_is_64 != 0 && order_is_64 != 1)) return GESPMM_EINVAL;
+    if (n > kMaxNnz) return GESPMM_ERANGE;
+    if (n == 0) return 0;
+    const int rc = check_pointers({{x, 4, true}, {out, 4, true}, {order, order_is_64 ? 8 : 4, true}});
+    if (rc != 0) return rc;
+    return (int)launch_edge_gather(x, order, order_is_64 != 0, out, n, row_bytes, reinterpret_cast<hipStream_t>(stream));
 }
 
 int gespmm_heads_x16_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int b_align, int c_align, int32_t* geometry_out) {

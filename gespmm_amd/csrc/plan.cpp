@@ -1099,9 +1099,10 @@ int gespmm_plan_x16_route(const gespmm_plan* plan, int64_t N, int b_align, int c
 // The multi-head product through a plan (gespmm.h). A storage-order plan runs the stateless call on the caller's arrays. A clustered plan
 // permutes the [nnz, H] weights into its own buffer (one copy kernel per call: the weights are an argument, nothing is cached) and runs the
 // plan-mode heads kernel on its batch-stream task table — which every clustered plan owns whatever its scalar route is — or, where that
-// kernel is not served, the stateless composition. `dry`: the answer only.
+// kernel is not served, the stateless composition. `dry`: the answer only. `order` (may be NULL): the weights of entry e are row order[e]
+// of val — a storage-order plan hands it to the stateless ordered entry, a clustered plan composes it into the copy it makes anyway.
 static int plan_run_heads(gespmm_plan* p, const float* val, const float* B, float* C, int64_t H, int64_t F, void* stream, bool dry, int b_align,
-                          int c_align, int* route_out) {
+                          int c_align, int* route_out, const int32_t* order = nullptr) {
     *route_out = 0;
     int kind = 0;
     gespmm::CsrView A = plan_view(p, route_of(p, H * F, gespmm::kReduceSum, true));
@@ -1123,10 +1124,11 @@ static int plan_run_heads(gespmm_plan* p, const float* val, const float* B, floa
     p->heads_last_F = F;
     p->heads_last_route = kind;
     if (!p->reordered) p->heads_last_geo = geo;
-    if (!p->reordered || kind == 0) return gespmm_csr_spmm_heads_f32(p->rowptr, p->colind, val, B, C, p->M, p->K, H, F, p->nnz, stream);
+    if (!p->reordered || kind == 0)
+        return gespmm_csr_spmm_heads_order_f32(p->rowptr, p->colind, order, val, B, C, p->M, p->K, H, F, p->nnz, stream);  // (NULL order: the plain entry)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (const int rcg = grow_owned(&p->d_heads_val, &p->heads_val_bytes, p->nnz * H * 4, st)) return rcg;  // (nothing launched)
-    const hipError_t e = gespmm::launch_permute_head_values(p->d_rowptr, p->d_src_begin, val, p->d_heads_val, p->M, p->nnz, H, st);
+    const hipError_t e = gespmm::launch_permute_head_values(p->d_rowptr, p->d_src_begin, val, p->d_heads_val, p->M, p->nnz, H, st, order);
     if (e != hipSuccess) return (int)e;
     A.val = p->d_heads_val;
     return gespmm::run_spmm_heads(A, B, C, H, F, p->launch_flags, stream, b_align, c_align, false, &kind, &p->heads_last_geo);
@@ -1141,6 +1143,20 @@ int gespmm_plan_spmm_heads_f32(gespmm_plan* plan, const float* val, const float*
     if ((rc = gespmm::check_pointers({{C, 4, true}, {B, 4, entries}, {val, 4, entries}})) != 0) return rc;
     int route = 0;
     return plan_run_heads(plan, val, B, C, H, F, stream, false, gespmm::pointer_alignment(B), gespmm::pointer_alignment(C), &route);
+}
+
+int gespmm_plan_spmm_heads_order_f32(gespmm_plan* plan, const int32_t* order, const float* val, const float* B, float* C, int64_t H, int64_t F,
+                                     void* stream) {
+    if (!order) return gespmm_plan_spmm_heads_f32(plan, val, B, C, H, F, stream);
+    if (!plan) return GESPMM_EINVAL;
+    int rc = gespmm::check_heads_sizes(plan->M, plan->K, H, F, plan->nnz);
+    if (rc != 0) return rc;
+    if (plan->M == 0 || F == 0) return 0;
+    const bool entries = plan->nnz != 0;
+    if ((rc = gespmm::check_pointers({{C, 4, true}, {B, 4, entries}, {val, 4, entries}, {order, 4, false}})) != 0) return rc;
+    int route = 0;
+    return plan_run_heads(plan, val, B, C, H, F, stream, false, gespmm::pointer_alignment(B), gespmm::pointer_alignment(C), &route,
+                          entries ? order : nullptr);
 }
 
 int gespmm_plan_heads_route(const gespmm_plan* plan, int64_t H, int64_t F, int b_align, int c_align) {

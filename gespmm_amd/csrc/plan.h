@@ -125,8 +125,9 @@ int run_spmm_x16(const CsrView& A, const void* B, void* C, int dtype, int64_t N,
 // limited to what divides F and what b_align / c_align allow, strict order, no cache blocking. *kind: 1 the kernel, 0 not available
 // (kHeadsUnavailable is returned and nothing is launched: the caller composes per head). dry_run: answer only, pointers are not looked at.
 constexpr int kHeadsUnavailable = -103;  // internal
+// order (may be NULL; storage order only): the weights of entry p are row order[p] of A.val — the ordered kernels (spmm_heads_order.hip).
 int run_spmm_heads(const CsrView& A, const float* B, float* C, int64_t H, int64_t F, int flags, void* stream, int b_align, int c_align,
-                   bool dry_run, int* kind, Geometry* geo_out = nullptr);
+                   bool dry_run, int* kind, Geometry* geo_out = nullptr, const int32_t* order = nullptr);
 
 // The multi-head SDDMM (gespmm_sddmm_{coo,csr}_heads_f32 / gespmm_plan_sddmm_heads_f32; sddmm_heads.h) on checked arguments with nnz > 0:
 // the route resolve_sddmm_heads answers (select.h). rows: row pointers (csr) or row ids. K: rows of D2 where the caller knows them, else

@@ -29,6 +29,21 @@ struct HeadsArgs : SpmmArgs {
     int32_t F;
 };
 
+// ... through an edge order (spmm_heads_order.hip): the weights of CSR entry p are row order[p] of val. order: int32[nnz], entries in [0, nnz).
+struct HeadsOrderArgs : HeadsArgs {
+    const int32_t* order;
+};
+template <bool ORDERED>
+struct HeadsArgsFor {
+    using type = HeadsArgs;
+};
+template <>
+struct HeadsArgsFor<true> {
+    using type = HeadsOrderArgs;
+};
+template <bool ORDERED>
+using HeadsArgsOf = typename HeadsArgsFor<ORDERED>::type;
+
 inline bool heads_geometry_served(const Geometry& g, bool planned) {
     if (g.idx64 || g.reduce != kReduceSum || g.slab_blocked || g.split_long_rows) return false;
     const int V = g.vec, S = g.strips, W = g.group;
@@ -45,6 +60,13 @@ inline bool heads_geometry_served(const Geometry& g, bool planned) {
 hipError_t launch_spmm_heads(const HeadsArgs& a, const Geometry& geo, hipStream_t st);
 // spmm_heads_x16.hip: `a` in words (above), storage order only (a.tasks == NULL); hipErrorInvalidValue where the geometry is not served.
 hipError_t launch_spmm_heads_x16(const HeadsArgs& a, int dtype, const Geometry& geo, hipStream_t st);
+// spmm_heads_order.hip: the storage-order kernels with the weights read through `order` (ORDERED of spmm_heads_kernel.h). dtype 0: `a` as
+// launch_spmm_heads takes it; kX16F16 / kX16Bf16: `a` in words as launch_spmm_heads_x16 takes it. a.tasks must be NULL, order not.
+hipError_t launch_spmm_heads_order(const HeadsArgs& a, const int32_t* order, int dtype, const Geometry& geo, hipStream_t st);
+// ... and out[i, :] = x[order[i], :] for i < n on rows of row_bytes bytes (a multiple of 4; the C entry takes at most 64), order int32 or int64: one
+// grid-stride kernel, consecutive lanes on consecutive words of out (16-byte pieces where row_bytes and both arrays allow). An index
+// outside [0, n) reads nothing: that row of out is all-ones words.
+hipError_t launch_edge_gather(const void* x, const void* order, bool order_is_64, void* out, int64_t n, int64_t row_bytes, hipStream_t st);
 // ... and dst[r, 0:width] = src[r, off:off+width] on 16-bit elements (the per-head route of the 16-bit multi-head SDDMM)
 hipError_t launch_heads_slice_x16(const void* src, void* dst, int64_t rows, int64_t stride, int64_t off, int64_t width, hipStream_t st);
 // The composition route's two copies: dst[r, 0:width] = src[r, off:off+width] (src rows `stride` floats apart) and its inverse
@@ -52,8 +74,9 @@ hipError_t launch_heads_slice_x16(const void* src, void* dst, int64_t rows, int6
 hipError_t launch_heads_slice(const float* src, float* dst, int64_t rows, int64_t stride, int64_t off, int64_t width, hipStream_t st);
 hipError_t launch_heads_unslice(const float* src, float* dst, int64_t rows, int64_t stride, int64_t off, int64_t width, hipStream_t st);
 // val_p[p, :] = val[src_begin[r] + (p - rowptr_p[r]), :] for entry p of row r of a plan's permuted copy: the [nnz, H] weights in the
-// plan's entry order (plan.cpp: permute_values, H floats per entry).
+// plan's entry order (plan.cpp: permute_values, H floats per entry). order (may be NULL): the caller's weights are read through it,
+// val_p[p, :] = val[order[src(p)], :] — the two permutations composed in the one copy.
 hipError_t launch_permute_head_values(const int32_t* rowptr_p, const int32_t* src_begin, const float* val, float* val_p, int64_t M,
-                                      int64_t nnz, int64_t H, hipStream_t st);
+                                      int64_t nnz, int64_t H, hipStream_t st, const int32_t* order = nullptr);
 
 }  // namespace gespmm

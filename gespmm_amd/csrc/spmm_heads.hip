@@ -98,15 +98,17 @@ hipError_t launch_heads_unslice(const float* src, float* dst, int64_t rows, int6
 }
 
 // A workgroup permutes 256 entries: ONE row search per entry (thread t finds where entry p0 + t comes from), then the 256 H words of the
-// block are copied with consecutive threads on consecutive words of val_p.
+// block are copied with consecutive threads on consecutive words of val_p. `order` (may be NULL) is applied to where the entry comes
+// from: the caller's weights through an edge order, in the same copy.
 __global__ __launch_bounds__(256) void permute_head_values_kernel(const int32_t* __restrict__ rowptr_p, const int32_t* __restrict__ src_begin,
                                                                   const float* __restrict__ val, float* __restrict__ val_p, int M, int nnz,
-                                                                  int H) {
+                                                                  int H, const int32_t* __restrict__ order) {
     __shared__ int s_src[256];
     const int p0 = blockIdx.x * 256, p = p0 + threadIdx.x;
     if (p < nnz) {
         const int r = row_of_entry(rowptr_p, M, p);
-        s_src[threadIdx.x] = src_begin[r] + (p - rowptr_p[r]);
+        const int src = src_begin[r] + (p - rowptr_p[r]);
+        s_src[threadIdx.x] = order ? order[src] : src;
     }
     __syncthreads();
     const int cnt = (nnz - p0 < 256 ? nnz - p0 : 256) * H;  // words of this block (nnz H < 2^31 on this route)
@@ -117,11 +119,11 @@ __global__ __launch_bounds__(256) void permute_head_values_kernel(const int32_t*
 }
 
 hipError_t launch_permute_head_values(const int32_t* rowptr_p, const int32_t* src_begin, const float* val, float* val_p, int64_t M,
-                                      int64_t nnz, int64_t H, hipStream_t st) {
+                                      int64_t nnz, int64_t H, hipStream_t st, const int32_t* order) {
     if (nnz <= 0 || H <= 0) return hipSuccess;
     if (nnz * H >= (1ll << 31)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(permute_head_values_kernel, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, st, rowptr_p, src_begin, val, val_p, (int)M,
-                       (int)nnz, (int)H);
+                       (int)nnz, (int)H, order);
     return hipGetLastError();
 }
 

@@ -18,6 +18,13 @@
 // address, the lane geometry and the staged weights are the fp32 kernel's at half the width. A gathered word widens — exactly — into
 // two fp32 values that share the staged weight of their head (2 V S accumulators, one fmaf chain each in CSR order), and the row-end
 // store rounds each sum once, to nearest even, and packs the pairs (widen_x16 / narrow_x16 of spmm_device.h).
+//
+// ORDERED (spmm_heads_order.hip; storage order only): the weights of tile entry p are row a.order[p] of val, not row p. Only the tile
+// staging differs — the lane that owns entry p = base + lane loads order[p] (coalesced, like colind) ONE TILE FURTHER AHEAD than the
+// weights, so the dependent gather of the H words val[order[p] H ..] (the widest load H and the alignment of val allow: 16 bytes for
+// H = 4 / 8, 8 bytes for H = 2 / 4 / 8, dwords otherwise; wave-uniform) is issued one tile ahead like the unordered weights, with its
+// address already in a register. The lane publishes its H words at s_val[lane H + head], where the row loop reads them. Row loop,
+// gathers of B, accumulators and stores are the unordered kernel's: the bits are those of the unordered kernel on the permuted copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,13 +34,14 @@
 
 namespace gespmm {
 
-template <int DT, int V, int S, int W, int U, bool PLANNED>
-__global__ __launch_bounds__(kThreads) void spmm_heads_kernel_t(HeadsArgs a) {
+template <int DT, int V, int S, int W, int U, bool PLANNED, bool ORDERED = false>
+__global__ __launch_bounds__(kThreads) void spmm_heads_kernel_t(HeadsArgsOf<ORDERED> a) {
+    static_assert(!(ORDERED && PLANNED), "a plan permutes its weights through the order in the copy it already makes");
     constexpr int G = 64 / W;
     constexpr int E = (DT != 0) ? 2 : 1;  // fp32 sums per gathered word
 
     __shared__ uint32_t s_off[kWaves][kTile];
-    __shared__ float s_val[kWaves][kTile * kHeadsMax];
+    __shared__ alignas(ORDERED ? 16 : alignof(float)) float s_val[kWaves][kTile * kHeadsMax];  // (ORDERED publishes 16-byte slots)
     __shared__ int s_ptr[kWaves][kMaxRowsPerWave + 1];
     __shared__ int s_perm[PLANNED ? kWaves : 1][PLANNED ? kMaxRowsPerWave : 1];
 
@@ -72,9 +80,44 @@ __global__ __launch_bounds__(kThreads) void spmm_heads_kernel_t(HeadsArgs a) {
     float pv[kHeadsMax];
 #pragma unroll
     for (int i = 0; i < kHeadsMax; ++i) pv[i] = 0.0f;
+    int po = 0;  // ORDERED: order[] of the entry this lane owns in the tile AFTER the one whose weights are fetched next
+    int vw = 1;  // ORDERED: words per weight load (wave-uniform)
+    if constexpr (ORDERED) {
+        const uint32_t va = (uint32_t)reinterpret_cast<uintptr_t>(a.val);
+        if ((H == 4 || H == 8) && va % 16u == 0) vw = 4;
+        else if ((H == 2 || H == 4 || H == 8) && va % 8u == 0) vw = 2;
+    }
     auto fetch_tile_regs = [&](int base) {
         const int p = base + lane;
         if (p < we) pc = load_csr(a.colind + p);
+        if constexpr (ORDERED) {
+            // `po` is order[p], loaded when the previous tile was fetched (or before the first): the H words of that row of val now,
+            // order[p + 64] for the next call. Neither array is read at or past `we`.
+            if (p < we) {
+                const float* src = a.val + (uint32_t)po * (uint32_t)H;  // (nnz H < 2^31: no wrap)
+                if (vw == 4) {
+#pragma unroll
+                    for (int j = 0; j < kHeadsMax / 4; ++j)
+                        if (j * 4 < H) {
+                            const float4 w = *reinterpret_cast<const float4*>(src + j * 4);
+                            pv[j * 4] = w.x, pv[j * 4 + 1] = w.y, pv[j * 4 + 2] = w.z, pv[j * 4 + 3] = w.w;
+                        }
+                } else if (vw == 2) {
+#pragma unroll
+                    for (int j = 0; j < kHeadsMax / 2; ++j)
+                        if (j * 2 < H) {
+                            const float2 w = *reinterpret_cast<const float2*>(src + j * 2);
+                            pv[j * 2] = w.x, pv[j * 2 + 1] = w.y;
+                        }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < kHeadsMax; ++i)
+                        if (i < H) pv[i] = src[i];
+                }
+            }
+            if (p + kTile < we) po = load_csr(a.order + p + kTile);
+            return;
+        }
         // the tile's weights: words [base H, min(base + 64, we) H) of val, 64 consecutive words per load (nnz H < 2^31: no wrap)
         const uint32_t vb = (uint32_t)base * (uint32_t)H;
         const uint32_t vfull = vb + (uint32_t)(kTile * H), vlast = (uint32_t)we * (uint32_t)H;
@@ -87,6 +130,19 @@ __global__ __launch_bounds__(kThreads) void spmm_heads_kernel_t(HeadsArgs a) {
     };
     auto publish_tile = [&]() {
         s_off[wave][lane] = (uint32_t)pc * rowbytes;
+        if constexpr (ORDERED) {  // pv[] holds the H weights of entry `lane`: slots lane H .. lane H + H - 1
+            float* dst = &s_val[wave][lane * H];
+            if (H == 4 || H == 8) {  // (16-byte slots: one or two ds_write_b128, consecutive lanes on consecutive slots)
+#pragma unroll
+                for (int j = 0; j < kHeadsMax / 4; ++j)
+                    if (j * 4 < H) *reinterpret_cast<float4*>(dst + j * 4) = make_float4(pv[j * 4], pv[j * 4 + 1], pv[j * 4 + 2], pv[j * 4 + 3]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < kHeadsMax; ++i)
+                    if (i < H) dst[i] = pv[i];
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < kHeadsMax; ++i)
             if (i < H) s_val[wave][i * kTile + lane] = pv[i];
@@ -111,6 +167,9 @@ __global__ __launch_bounds__(kThreads) void spmm_heads_kernel_t(HeadsArgs a) {
         if (lane <= kMaxRowsPerWave) s_ptr[wave][lane] = rp;
         wb = __builtin_amdgcn_readfirstlane(rp);
         we = __builtin_amdgcn_readlane(rp, nrows);
+    }
+    if constexpr (ORDERED) {
+        if (wb + lane < we) po = load_csr(a.order + wb + lane);
     }
     fetch_tile_regs(wb);
 

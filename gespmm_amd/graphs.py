@@ -447,10 +447,17 @@ def take_edges(x, order, chunk_rows=1 << 24):
     is safe; 2^24 leaves a factor of four and costs eight launches at 2^27 edges. Every place of this package that permutes an edge
     array goes through here.
 
+    Two routes. The GATHER route — ``x`` a contiguous device tensor that does not require grad (or grad mode is off), a row of 4, 8,
+    .. 64 bytes, ``order`` contiguous on the same device — is one HIP kernel (gespmm_edge_gather) into a result torch allocates (so it
+    stays capturable): coalesced writes, any nnz in one launch, and no ``chunk_rows`` pieces. Everything else — CPU tensors, rows of
+    other sizes (2-byte rows, rows above 64 bytes), a non-contiguous ``x``, ``requires_grad`` under grad mode — is the chunked
+    ``index_select`` described above, unchanged.
+
     The bits are those of a copy. ``x`` may be non-contiguous and of any dtype; nnz = 0 gives an empty result. A wrong length raises
-    ValueError; an entry outside [0, nnz) raises IndexError on CPU tensors (on the device it is torch's own device-side check, as
-    with ``x[order]``). When ``x`` requires grad under an enabled grad mode the pieces are concatenated instead, so the result stays
-    differentiable; the layers of this package call it on detached tensors."""
+    ValueError; an entry outside [0, nnz) raises IndexError on CPU tensors. On the device the gather route never reads outside ``x``:
+    an out-of-range index gives that row of the result as all-ones words (NaN as a float, -1 as an integer) instead of torch's
+    device-side assert, which the ``index_select`` route still raises. When ``x`` requires grad under an enabled grad mode the pieces are
+    concatenated instead, so the result stays differentiable; the layers of this package call it on detached tensors."""
     if order.dim() != 1 or x.dim() < 1 or order.numel() != x.shape[0]:
         raise ValueError("take_edges: order must be 1-D with one entry per row of x, got order %s for x %s" % (
             tuple(order.shape), tuple(x.shape)))
@@ -467,6 +474,15 @@ def take_edges(x, order, chunk_rows=1 << 24):
             return x.index_select(0, order).contiguous()
         return torch.cat([x.index_select(0, order[a:a + chunk_rows]) for a in range(0, n, chunk_rows)])
     out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    row_bytes = x.element_size() * (x.numel() // n) if n else 0
+    if n and x.is_cuda and order.device == x.device and x.is_contiguous() and order.is_contiguous() and row_bytes % 4 == 0 and \
+            4 <= row_bytes <= 64:
+        with torch.cuda.device(x.device):
+            rc = lib.gespmm_edge_gather(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(order.data_ptr()), int(order.dtype == torch.int64),
+                                        ctypes.c_void_p(out.data_ptr()), n, row_bytes,
+                                        ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        check(rc, "gespmm_edge_gather")
+        return out
     for a in range(0, n, chunk_rows):
         torch.index_select(x, 0, order[a:a + chunk_rows], out=out[a:a + chunk_rows])
     return out

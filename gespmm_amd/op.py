@@ -70,9 +70,29 @@ from . import attention as _attention
 from . import graphs as _graphs
 from . import sddmm as _sddmm
 from . import softmax as _softmax
+from . import _lib
 from . import spmm as _spmm
 
 _warned_no_grad = False
+
+
+def _csc_heads_order(csc_order, rows, cols, H, F, nnz, x16, plan):
+    """The int32 edge order a multi-head backward hands to its product on the CSC arrays (``csr_spmm_heads(..., order=)``: the weights
+    read through the order, no permuted copy), or None where that product has no ordered kernel — H = 1, H > 8, odd F in 16 bits —
+    and the backward does ``graphs.take_edges`` plus the plain call. ``rows`` x ``cols``: the CSC product's shape (K x M). A plan
+    always takes the order. An int64 ``csc_order`` is converted once, here, in the forward."""
+    if plan is None and (_lib.heads_x16_route if x16 else _lib.heads_route)(rows, cols, H, F, nnz)[0] != 1:
+        return None
+    return (csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)).contiguous()
+
+
+def _csc_heads_product(ctx, colptr, rowind, csc_order, weight, dense):
+    """grad = A(weight)^T @ dense on the CSC arrays, ``weight`` f32[nnz, H] in CSR edge order: read through the order (``order=``, handed
+    over as ``spmm.OrderedValues`` in the place of the weights) where the forward found the ordered kernel, gathered otherwise."""
+    values = _spmm.OrderedValues(weight, ctx.order) if ctx.order is not None else _graphs.take_edges(weight, csc_order)
+    if ctx.x16:
+        return _spmm.csr_spmm_heads_x16(colptr, rowind, values, dense)
+    return _spmm.csr_spmm_heads(colptr, rowind, values, dense, plan=ctx.bwd_plan)
 
 
 def _is_x16(t):
@@ -173,7 +193,10 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
 
     ``feat`` f32[K, H, F], ``weight`` f32[nnz, H] in CSR edge order; ``colptr, rowind, csc_order`` =
     ``graphs.transpose_csr(rowptr, colind, K, return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the
-    CSR and the CSC pattern. Backward: grad_feat is the same product on the CSC arrays with ``graphs.take_edges(weight, csc_order)``;
+    CSR and the CSC pattern. Backward: grad_feat is the same product on the CSC arrays with the weights read through ``csc_order``
+    (``csr_spmm_heads(colptr, rowind, weight, grad_out, order=)``: no permuted copy of ``weight``; an int64 ``csc_order`` is converted to
+    int32 once per forward — pass an int32 one) wherever the ordered kernel exists — ``_lib.heads_route`` answers 1 for the CSC
+    product, or a plan is given — and with ``graphs.take_edges(weight, csc_order)`` elsewhere (H = 1, H > 8); the same bits either way;
     grad_weight[e, h] = <grad_out[row(e), h, :], feat[col(e), h, :]> is computed only when ``weight`` requires grad — by default as one
     ``sddmm.csr_sddmm`` per head on contiguous copies, with ``heads_sddmm=True`` as ONE ``sddmm.csr_sddmm_heads(rowptr, colind, grad_out,
     feat, plan=forward plan)`` on the tensors as they are (no copies, one launch). The two settings give the same bits on
@@ -181,7 +204,8 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
     Index tensors get no gradient.
 
     16-bit ``feat`` (fp16 / bf16) with fp32 ``weight``: the output has ``feat``'s dtype (``spmm.csr_spmm_heads_x16``: fp32 sums, one
-    rounding), grad_feat is ``csr_spmm_heads_x16`` on the CSC arrays with ``graphs.take_edges(weight, csc_order)``, grad_weight stays fp32 —
+    rounding), grad_feat is ``csr_spmm_heads_x16`` on the CSC arrays with ``order=`` (``take_edges`` where ``_lib.heads_x16_route`` is 0: odd F
+    too), grad_weight stays fp32 —
     ``sddmm.csr_sddmm_heads_x16(rowptr, colind, grad_out, feat)`` with ``heads_sddmm=True``, the 16-bit ``sddmm.csr_sddmm`` per head
     otherwise. ``plans=`` with 16-bit tensors raises TypeError (the 16-bit multi-head ops have no plan form)."""
 
@@ -199,6 +223,10 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
         else:
             out = _spmm.csr_spmm_heads(rowptr, colind, weight_c, feat_c, plan=fwd_plan)
         ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
+        ctx.order = None
+        if ctx.needs_input_grad[5]:
+            ctx.order = _csc_heads_order(csc_order, colptr.numel() - 1, rowptr.numel() - 1, weight_c.shape[1],
+                                         math.prod(feat_c.shape[1:]) // max(weight_c.shape[1], 1), colind.numel(), ctx.x16, ctx.bwd_plan)
         ctx.save_for_backward(feat_c, weight_c)
         return out
 
@@ -209,10 +237,7 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         grad_feat = grad_weight = None
         if ctx.needs_input_grad[5]:
-            if ctx.x16:
-                grad_feat = _spmm.csr_spmm_heads_x16(colptr, rowind, _graphs.take_edges(weight, csc_order), grad_out)
-            else:
-                grad_feat = _spmm.csr_spmm_heads(colptr, rowind, _graphs.take_edges(weight, csc_order), grad_out, plan=ctx.bwd_plan)
+            grad_feat = _csc_heads_product(ctx, colptr, rowind, csc_order, weight, grad_out)
         if ctx.needs_input_grad[6]:
             if ctx.heads_sddmm and ctx.x16:
                 grad_weight = _sddmm.csr_sddmm_heads_x16(rowptr, colind, grad_out, feat)
@@ -234,7 +259,9 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
     ``q`` f32[M, H, F], ``k`` f32[K, H, F]; ``colptr, rowind, csc_order`` = ``graphs.transpose_csr(rowptr, colind, K,
     return_order=True)``; ``plans=(forward, backward)`` are ``spmm.SpmmPlan`` objects of the CSR and the CSC pattern. Backward is two
     multi-head products (``spmm.csr_spmm_heads``), each computed only for an input that requires grad:
-    grad_q = A(grad_s) @ k on the CSR arrays, grad_k = A(grad_s)^T @ q on the CSC arrays with ``graphs.take_edges(grad_s, csc_order)``.
+    grad_q = A(grad_s) @ k on the CSR arrays, grad_k = A(grad_s)^T @ q on the CSC arrays with ``grad_s`` read through ``csc_order``
+    (``order=``: no permuted copy; int64 is converted to int32 once per forward) where the ordered kernel exists or a plan is given, with
+    ``graphs.take_edges(grad_s, csc_order)`` elsewhere (H = 1, H > 8, odd F in 16 bits) — the same bits.
     Index tensors get no gradient.
 
     16-bit ``q`` and ``k`` (both fp16 or both bf16): the score stays fp32 (``sddmm.csr_sddmm_heads_x16``), grad_q / grad_k are
@@ -253,6 +280,10 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
         else:
             out = _sddmm.csr_sddmm_heads(rowptr, colind, q_c, k_c, plan=fwd_plan)
         ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
+        ctx.order = None
+        if ctx.needs_input_grad[6]:
+            ctx.order = _csc_heads_order(csc_order, colptr.numel() - 1, rowptr.numel() - 1, out.shape[1],
+                                         math.prod(q_c.shape[1:]) // max(out.shape[1], 1), colind.numel(), ctx.x16, ctx.bwd_plan)
         ctx.save_for_backward(q_c, k_c)
         return out
 
@@ -266,12 +297,12 @@ class MultiHeadSDDMMFunction(torch.autograd.Function):
             if ctx.needs_input_grad[5]:
                 grad_q = _spmm.csr_spmm_heads_x16(rowptr, colind, grad_s, k)
             if ctx.needs_input_grad[6]:
-                grad_k = _spmm.csr_spmm_heads_x16(colptr, rowind, _graphs.take_edges(grad_s, csc_order), q)
+                grad_k = _csc_heads_product(ctx, colptr, rowind, csc_order, grad_s, q)
             return None, None, None, None, None, grad_q, grad_k, None
         if ctx.needs_input_grad[5]:
             grad_q = _spmm.csr_spmm_heads(rowptr, colind, grad_s, k, plan=ctx.fwd_plan)
         if ctx.needs_input_grad[6]:
-            grad_k = _spmm.csr_spmm_heads(colptr, rowind, _graphs.take_edges(grad_s, csc_order), q, plan=ctx.bwd_plan)
+            grad_k = _csc_heads_product(ctx, colptr, rowind, csc_order, grad_s, q)
         return None, None, None, None, None, grad_q, grad_k, None
 
 

@@ -270,13 +270,14 @@ class SpmmPlan:
         if (self._rowptr._version, self._colind._version) != self._pattern_version:
             raise ValueError("rowptr/colind were modified in place after the plan was made: create a new SpmmPlan")
 
-    def run_heads(self, values, dense, out=None):
+    def run_heads(self, values, dense, out=None, order=None):
         """The multi-head product through the plan (gespmm_plan_spmm_heads_f32; see ``csr_spmm_heads``): ``values`` f32[nnz, H] in the
         caller's edge order — an argument of every call, the plan caches nothing of them and its own values stay what they are — and
         ``dense`` f32[K, H, F] or f32[K, H * F]. Same bits as the call without a plan. A clustered plan copies the weights into its own
         edge order on every call, which on a large graph with narrow heads costs more than clustering gains (com-amazon-sbm, H F <= 128:
-        1.1-1.4x the time of the call without a plan) — there, call ``csr_spmm_heads`` without ``plan=``."""
-        return csr_spmm_heads(self._rowptr, self._colind, values, dense, out=out, plan=self)
+        1.1-1.4x the time of the call without a plan) — there, call ``csr_spmm_heads`` without ``plan=``.
+        ``order=`` (int32[nnz]): the weights of entry e are ``values[order[e]]``; a clustered plan composes it into that copy."""
+        return csr_spmm_heads(self._rowptr, self._colind, values, dense, out=out, plan=self, order=order)
 
     def heads_route(self, H, F, b_align=16, c_align=16):
         """What ``run_heads`` does at H heads of F columns with operands whose addresses ``b_align`` / ``c_align`` divide
@@ -407,33 +408,93 @@ def _heads_args(rowptr, colind, values, dense, out):
     return H, F, out
 
 
-def csr_spmm_heads(rowptr, colind, values, dense, out=None, plan=None):
+class OrderedValues:
+    """``values`` of the multi-head products read through an edge order, as ONE argument: ``csr_spmm_heads(rowptr, colind,
+    OrderedValues(values, order), dense)`` is ``csr_spmm_heads(rowptr, colind, values, dense, order=order)`` — for callers that hand the
+    weights on positionally (the autograd functions of ``op.py`` do: whatever wraps the product sees one call of its usual shape)."""
+
+    __slots__ = ("values", "order")
+
+    def __init__(self, values, order):
+        self.values, self.order = values, order
+
+    dtype = property(lambda self: self.values.dtype)
+    shape = property(lambda self: self.values.shape)
+    device = property(lambda self: self.values.device)
+
+
+def _split_ordered(values, order):
+    if isinstance(values, OrderedValues):
+        if order is not None:
+            raise ValueError("order= given twice: values is already an OrderedValues")
+        return values.values, values.order
+    return values, order
+
+
+def _need_order(order, nnz, dev):
+    """``order=`` of the multi-head products: int32[nnz], contiguous, on ``dev``. Raises before any launch."""
+    if not isinstance(order, torch.Tensor):
+        raise TypeError("order must be a torch.Tensor")
+    if order.dtype == torch.int64:
+        raise TypeError("order must have dtype torch.int32, got torch.int64: convert it once (order.to(torch.int32)), not per call")
+    if order.dtype != torch.int32:
+        raise TypeError("order must have dtype torch.int32, got %s" % order.dtype)
+    if order.dim() != 1 or order.numel() != nnz:
+        raise ValueError("order must be int32[nnz] with nnz = %d entries, got shape %s" % (nnz, tuple(order.shape)))
+    if order.device != dev:
+        raise ValueError("order must live on %s like the other tensors, got %s" % (dev, order.device))
+    if not order.is_contiguous():
+        raise ValueError("order must be contiguous")
+
+
+def csr_spmm_heads(rowptr, colind, values, dense, out=None, plan=None, order=None):
     """Multi-head product (attention aggregation): ``out[r, h, :] = sum_e values[e, h] * dense[col(e), h, :]`` over the entries e of row
     r (gespmm_csr_spmm_heads_f32 / gespmm_plan_spmm_heads_f32). ``values`` f32[nnz, H]; ``dense`` f32[K, H, F] or f32[K, H * F], the
     result has the matching rank. One fp32 fma chain per output element in strict CSR order, so head h has the bits of
     ``csr_spmm(rowptr, colind, values[:, h].contiguous(), dense[:, h, :].contiguous(), cfg={"flags": FLAG_STRICT_ORDER})``.
     One kernel for 2 <= H <= 8 (``_lib.heads_route``), a per-head composition otherwise. fp32 only (TypeError otherwise): fp16 / bf16
-    features go through ``csr_spmm_heads_x16``."""
+    features go through ``csr_spmm_heads_x16``.
+
+    ``order=`` (int32[nnz], contiguous, same device; entries in [0, nnz), not checked): the weights of entry e are ``values[order[e]]``
+    — the bits of ``csr_spmm_heads(rowptr, colind, graphs.take_edges(values, order), dense)`` with no permuted copy
+    (gespmm_csr_spmm_heads_order_f32 / gespmm_plan_spmm_heads_order_f32): one kernel wherever ``_lib.heads_route`` answers 1, allocating
+    nothing; elsewhere a HIP gather into a stream-ordered temporary and the call above (not on a capturing stream). An int64 order
+    raises TypeError — convert it once. ``values=OrderedValues(values, order)`` is the same call."""
+    values, order = _split_ordered(values, order)
     H, F, out = _heads_args(rowptr, colind, values, dense, out)
     dev = dense.device
     M, K = rowptr.numel() - 1, dense.shape[0]
+    if order is not None:
+        _need_order(order, colind.numel(), dev)
     with _on_device(dev):
         if plan is not None:
             plan._check_pattern(rowptr, colind, K)
-            rc = lib.gespmm_plan_spmm_heads_f32(plan._handle, _ptr(values), _ptr(dense), _ptr(out), H, F, _stream(dev))
-        else:
+            if order is None:
+                name = "gespmm_plan_spmm_heads_f32"
+                rc = lib.gespmm_plan_spmm_heads_f32(plan._handle, _ptr(values), _ptr(dense), _ptr(out), H, F, _stream(dev))
+            else:
+                name = "gespmm_plan_spmm_heads_order_f32"
+                rc = lib.gespmm_plan_spmm_heads_order_f32(plan._handle, _ptr(order), _ptr(values), _ptr(dense), _ptr(out), H, F, _stream(dev))
+        elif order is None:
+            name = "gespmm_csr_spmm_heads_f32"
             rc = lib.gespmm_csr_spmm_heads_f32(_ptr(rowptr), _ptr(colind), _ptr(values), _ptr(dense), _ptr(out), M, K, H, F, colind.numel(),
                                                _stream(dev))
-    check(rc, "gespmm_plan_spmm_heads_f32" if plan is not None else "gespmm_csr_spmm_heads_f32")
+        else:
+            name = "gespmm_csr_spmm_heads_order_f32"
+            rc = lib.gespmm_csr_spmm_heads_order_f32(_ptr(rowptr), _ptr(colind), _ptr(order), _ptr(values), _ptr(dense), _ptr(out), M, K, H, F,
+                                                     colind.numel(), _stream(dev))
+    check(rc, name)
     return out
 
 
-def csr_spmm_heads_x16(rowptr, colind, values, dense, out=None):
+def csr_spmm_heads_x16(rowptr, colind, values, dense, out=None, order=None):
     """The multi-head product on 16-bit features (gespmm_csr_spmm_heads_x16): ``values`` f32[nnz, H] — edge-sized arrays stay fp32 —
     ``dense`` fp16 or bf16, [K, H, F] or [K, H * F]; the result has the dtype and rank of ``dense``. Each output element is one fp32 fma
     chain in strict CSR order, rounded once at the store: the bits of ``csr_spmm_heads(rowptr, colind, values, dense.float()).to(dense.dtype)``.
     One kernel for 2 <= H <= 8, even F and 4-byte aligned operands (``_lib.heads_x16_route``), the composition widen / fp32 / narrow
-    otherwise (not on a capturing stream). No plan form."""
+    otherwise (not on a capturing stream). No plan form. ``order=``: as for ``csr_spmm_heads`` (gespmm_csr_spmm_heads_order_x16; one
+    kernel wherever ``_lib.heads_x16_route`` answers 1)."""
+    values, order = _split_ordered(values, order)
     _need(rowptr, "rowptr", torch.int32, 1)
     _need(colind, "colind", torch.int32, 1)
     _need(values, "values", torch.float32, 2)
@@ -464,10 +525,18 @@ def csr_spmm_heads_x16(rowptr, colind, values, dense, out=None):
         _need(out, "out", dense.dtype, len(shape))
         if tuple(out.shape) != shape or out.device != dev:
             raise ValueError("out must be %s%s on the same device" % (dense.dtype, list(shape)))
+    if order is not None:
+        _need_order(order, nnz, dev)
     with _on_device(dev):
-        rc = lib.gespmm_csr_spmm_heads_x16(_ptr(rowptr), _ptr(colind), _ptr(values), _ptr(dense), _ptr(out), _X16[dense.dtype], M, K, H, F,
-                                           nnz, _stream(dev))
-    check(rc, "gespmm_csr_spmm_heads_x16")
+        if order is None:
+            name = "gespmm_csr_spmm_heads_x16"
+            rc = lib.gespmm_csr_spmm_heads_x16(_ptr(rowptr), _ptr(colind), _ptr(values), _ptr(dense), _ptr(out), _X16[dense.dtype], M, K, H, F,
+                                               nnz, _stream(dev))
+        else:
+            name = "gespmm_csr_spmm_heads_order_x16"
+            rc = lib.gespmm_csr_spmm_heads_order_x16(_ptr(rowptr), _ptr(colind), _ptr(order), _ptr(values), _ptr(dense), _ptr(out),
+                                                     _X16[dense.dtype], M, K, H, F, nnz, _stream(dev))
+    check(rc, name)
     return out
 
 

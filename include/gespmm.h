@@ -557,6 +557,40 @@ int gespmm_csr_spmm_heads_x16(const int32_t* rowptr, const int32_t* colind, cons
    per wavefront of the kernel (zeros on route 0) */
 int gespmm_heads_x16_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int b_align, int c_align, int32_t* geometry_out);
 /*
+ * The multi-head product with its weights read THROUGH AN EDGE ORDER (since 0.5): order is int32 [nnz] with entries in [0, nnz) (not
+ * checked, as for gespmm_edge_segment_sum_f32; repeated entries are legal), and
+ *   C[r, h F + f] = fmaf(val[order[p] H + h], B[colind[p] N + h F + f], acc)   over the entries p of row r, ascending
+ * — bit for bit the unordered entry on the gathered array val_o[p, :] = val[order[p], :], without that array: the backward of an
+ * attention layer is this product on the CSC arrays with order = the CSC-position -> CSR-position map. order == NULL is the unordered
+ * entry, through the same code path. _x16: B and C in fp16 / bf16 as gespmm_csr_spmm_heads_x16, one rounding at the store.
+ * Routes: 1 = ONE kernel exactly where gespmm_heads_route / gespmm_heads_x16_route answer 1 for the sizes and alignments (there is no
+ * route query of its own): the unordered kernel with the tile staging reading order[] one tile further ahead than the weights and
+ * gathering each entry's H words (16-byte loads for H = 4 / 8 on a 16-byte aligned val, 8-byte loads for H = 2 / 4 / 8 on 8 bytes,
+ * dwords otherwise); allocates nothing, capturable. 0 = the composition — gespmm_edge_gather of val through order into a stream-ordered
+ * temporary from the library's pool, then the unordered entry; the same bits; on a capturing stream it returns
+ * hipErrorStreamCaptureUnsupported and launches nothing. GESPMM_HEADS_ORDER_ROUTE=composition pins route 0 (a measurement knob, read
+ * with getenv on every call).
+ * Checks: those of the unordered entries, and order not 4-byte aligned -> GESPMM_EALIGN. nnz == 0 gives C = all-zero bits and reads no
+ * edge array. The plan form: a storage-order plan takes the route above; a clustered plan composes order into the permuted copy of the
+ * weights it makes on every call (one pass, one buffer) and runs its task-table kernel.
+ */
+int gespmm_csr_spmm_heads_order_f32(const int32_t* rowptr, const int32_t* colind, const int32_t* order, const float* val, const float* B,
+                                    float* C, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream);
+int gespmm_csr_spmm_heads_order_x16(const int32_t* rowptr, const int32_t* colind, const int32_t* order, const float* val, const void* B,
+                                    void* C, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, void* stream);
+int gespmm_plan_spmm_heads_order_f32(gespmm_plan* plan, const int32_t* order, const float* val, const float* B, float* C, int64_t H,
+                                     int64_t F, void* stream);
+/*
+ * Row gather of an edge array (since 0.5): out[i, :] = x[order[i], :] for i < n, rows of row_bytes bytes (a multiple of 4, at most 64),
+ * order int32 (order_is_64 == 0) or int64 (1). One grid-stride kernel with 64-bit addressing; consecutive lanes write consecutive words
+ * of out, or 16-byte pieces where row_bytes is a multiple of 16 and x and out are 16-byte aligned. Memory-safe: an index outside
+ * [0, n) is never used as an address, and its row of out is written as all-ones words (NaN as fp32 / bf16 / fp16, -1 as an integer) so
+ * that it shows. x and out must not overlap. n < 0, a bad row_bytes or order_is_64 -> GESPMM_EINVAL; n beyond the entry limit of the
+ * products -> GESPMM_ERANGE; n == 0 -> 0 without looking at pointers; NULL -> GESPMM_EINVAL; x or out not 4-byte aligned, order not
+ * aligned to its element -> GESPMM_EALIGN.
+ */
+int gespmm_edge_gather(const void* x, const void* order, int order_is_64, void* out, int64_t n, int64_t row_bytes, void* stream);
+/*
  * Kernel choice by MEASUREMENT instead of by rule: runs the candidates of a clustered plan (batch-stream, segmented-stream,
  * staged-rows where the width is served, and at N <= 64 the batch-stream kernel with 4 floats per lane) `reps` (0 = 3) times each on these operands, synchronously, and fixes the plan
  * on the fastest; C holds the product afterwards (every candidate gives the same bits). N must be the plan's width. A no-op
