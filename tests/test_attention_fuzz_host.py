@@ -1,0 +1,506 @@
+"""The seeded sweep of tests/test_gpu_attention_fuzz.py, as far as it can be judged without a GPU: the generator is deterministic, the
+case lists reach the launch parameters of every family's tables (a condition on the inputs: the seeds of FAMILY_SEEDS were chosen until
+it held), every family's comparison rejects a result that lost one entry, and the float64 references moved into
+tests/attention_refs.py give what the private helpers of the GPU test files gave before the move."""
+import numpy as np
+import pytest
+import torch
+
+import attention_refs as refs
+import test_gpu_attention_fuzz as fz
+from test_dot_attention_host import geometry
+from test_edge_softmax_host import IT, WANT_L, want_W
+
+POW2 = {4, 8, 16, 32, 64}
+
+
+# ------------------------------------------------------------------------------------------------------------------ determinism
+
+def test_the_generator_is_deterministic():
+    for family in fz.FAMILIES:
+        a, b = fz.family_cases(family), fz.family_cases(family)
+        assert len(a) == fz.N_CASES
+        for x, y in zip(a, b):
+            assert {k: v for k, v in x.items() if k != "G"} == {k: v for k, v in y.items() if k != "G"}
+            assert sorted(x["G"]) == sorted(y["G"])
+            for k, v in x["G"].items():
+                assert np.array_equal(v, y["G"][k]), (family, x["index"], k)
+    assert len(set(fz.FAMILY_SEEDS.values())) == len(fz.FAMILIES)
+
+
+def test_every_case_lies_inside_the_set_of_sizes():
+    laws = set()
+    for family in fz.FAMILIES:
+        for c in fz.family_cases(family):
+            G = c["G"]
+            assert G["M"] in fz.MS and G["K"] in fz.KS and c["H"] in fz.HS and c["F"] in fz.FS and c["offset"] in fz.OFFSETS
+            assert G["nnz"] * c["H"] * c["F"] <= fz.CAP
+            assert G["degs"].max() <= WANT_L or G["degs"].max() in fz.HUBS or c["law"] == "powerlaw", fz.what(family, c)
+            # the CSC arrays are the pattern's: the same entries, columns ascending, a column's entries in CSR order
+            assert np.array_equal(G["colind"][G["order"]], np.repeat(np.arange(G["K"]), np.diff(G["colptr"])))
+            assert np.array_equal(G["rows"][G["order"]], G["rowind"])
+            assert all(np.all(np.diff(G["order"][a:b]) > 0) for a, b in zip(G["colptr"][:-1], G["colptr"][1:]))
+            laws.add(c["law"])
+    assert laws == {"uniform", "powerlaw", "sparse", "hub", "empty", "lone hub", "mean"}, laws
+
+
+# ------------------------------------------------------------------------------------------------------------------------ reach
+
+def regimes(ptr, W):
+    """Which of the softmax's three regimes the segments of ``ptr`` ask for at lane width W (tests/test_gpu_gat_backward.py)."""
+    d = np.diff(ptr)
+    return {name for name, hit in (("register", ((d > 0) & (d <= IT * W)).any()), ("sweep", ((d > IT * W) & (d <= WANT_L)).any()),
+                                   ("hub", (d > WANT_L).any())) if hit}
+
+
+def _segments(cases, L):
+    """(W, regime) pairs of the rows and of the columns of the cases, W asserted against gespmm_describe_edge_softmax."""
+    rows, cols = set(), set()
+    for c in cases:
+        G = c["G"]
+        if G["nnz"] == 0:
+            continue
+        for S, ptr, into in ((G["M"], G["rowptr"], rows), (G["K"], G["colptr"], cols)):
+            W = want_W(S, G["nnz"])
+            assert L.describe_edge_softmax(S, G["nnz"], c["H"]) == {"W": W, "L": WANT_L}
+            into |= {(W, r) for r in regimes(ptr, W)}
+    return rows, cols
+
+
+def _bwd_shape(H, F, align):
+    """(V, W, strips) of the GATv2 backward launch: the rule of tests/test_gpu_gatv2_score.py, V = 4 on 16-byte aligned operands only."""
+    V = 4 if F % 4 == 0 and align == 16 else 1
+    need, W = H * F // V, 4
+    while W < 64 and W < need:
+        W *= 2
+    return V, W, -(-H * F // (W * V))
+
+
+def reach(family, L, seed=None):
+    """-> {parameter: the set of its values the family's case list reaches}, from the host-only describe / route functions."""
+    cases = fz.family_cases(family, seed=seed)
+    live = [c for c in cases if c["G"]["nnz"] > 0]
+    r = {"laws": {c["law"] for c in cases}, "M": {c["G"]["M"] for c in cases}, "K": {c["G"]["K"] for c in cases},
+         "H": {c["H"] for c in cases}, "F": {c["F"] for c in cases}, "offset": {c["offset"] for c in cases},
+         "lone hub only": {c["G"]["M"] > 1 for c in cases if c["law"] == "lone hub"},
+         "M H below a wavefront": {c["G"]["M"] * c["H"] < 4 for c in live}}
+    rows, cols = _segments(cases, L)
+    r["row W"], r["col W"] = {w for w, _ in rows}, {w for w, _ in cols}
+    r["row regimes"], r["col regimes"] = rows, cols
+
+    def geo(name, triples):
+        r[name + " V"], r[name + " S"], r[name + " W"] = ({t[i] for t in triples} for i in range(3))
+
+    if family == "heads":
+        for name, f in (("heads", L.heads_route), ("x16", L.heads_x16_route)):
+            got = [f(c["G"]["M"], c["G"]["K"], c["H"], c["F"], c["G"]["nnz"], fz.align_of(c["offset"]), fz.align_of(c["offset"])) for c in live]
+            r[name + " route"] = {g[0] for g in got}
+            geo(name, [g[1] for g in got if g[0] == 1])
+    elif family == "sddmm":
+        for x16 in (False, True):
+            name = "x16" if x16 else "f32"
+            got = [L.describe_sddmm_heads(csr, c["G"]["M"], c["G"]["nnz"], c["H"], c["F"], fz.align_of(c["offset"]), fz.align_of(c["offset"]),
+                                          x16=x16) for c in live for csr in (True, False)]
+            r[name + " route"] = {d["route"] for d in got}
+            r[name + " V"], r[name + " W"] = {d["V"] for d in got if "V" in d}, {d["W"] for d in got if "W" in d}
+    elif family in ("aggregate", "dropout"):
+        for transposed in (False, True):
+            got = [L.gat_aggregate_route(c["G"]["M"], c["G"]["K"], c["H"], c["F"], c["G"]["nnz"], transposed, fz.align_of(c["offset"]),
+                                         fz.align_of(c["offset"])) for c in live]
+            name = "transposed" if transposed else "forward"
+            r[name + " route"] = {g[0] for g in got}
+            geo(name, [g[1] for g in got if g[0] == 1])
+        r["p"] = {c["p"] for c in cases}
+    elif family == "gatv2":
+        got = [L.describe_gatv2_score(c["G"]["M"], c["G"]["nnz"], c["H"], c["F"], *(fz.align_of(c["offset"]),) * 3) for c in live]
+        r["score (V, W)"] = {(d["V"], d["W"]) for d in got}
+        bwd = {_bwd_shape(c["H"], c["F"], fz.align_of(c["offset"])) for c in live}
+        r["backward (V, W)"], r["backward strips"] = {b[:2] for b in bwd}, {b[2] for b in bwd}
+    elif family == "dot":
+        for c in live:
+            a = fz.align_of(c["offset"])
+            V, W = geometry(c["F"], a)
+            assert L.describe_dot_attention(c["G"]["M"], c["G"]["K"], c["H"], c["F"], c["G"]["nnz"], a, a, a) == {"V": V, "W": W}
+        r["(V, W)"] = {geometry(c["F"], fz.align_of(c["offset"])) for c in live}
+        r["p"] = {c["p"] for c in cases}
+    elif family == "max_arg":
+        a = [fz.align_of(c["offset"]) for c in cases]
+        for name, S in (("forward", "M"), ("backward", "K")):
+            got = [L.max_arg_route(c["G"][S], c["G"]["nnz"], c["H"] * c["F"], x, x) for c, x in zip(cases, a)]
+            geo(name, [g for g in got if g is not None])
+    return r
+
+
+def wanted(family):
+    """-> {parameter: the values that must be reached}: every value of every launch parameter in the family's table of its own GPU
+    test — each V, each S, each W on its own, not every combination: a W is tied to one or two of the eleven widths, a V to the width's
+    divisors and the offset, so most combinations have a handful of the 6 x 11 x 3 draws behind them and 24 cases cannot hold them all
+    (e.g. the dot attention's V = 4 at W = 32 needs a width in (128, 256] that 4 divides: none of the widths is)."""
+    # every family: the shapes no attention test ran on — one row, one column, fewer (row, head) pairs than a wavefront has lane groups,
+    # a hub as the only non-empty row, no entries at all — every operand offset and every lane width of the softmax
+    w = {"offset": set(fz.OFFSETS), "row W": {4, 8, 16}, "lone hub only": {True}, "M": {1}, "K": {1}, "M H below a wavefront": {True},
+         "laws": {"lone hub", "hub", "empty"}}
+    both = {(W, r) for W in (4, 8, 16) for r in ("register", "sweep")}
+    if family == "heads":
+        from test_gpu_heads import _launch_table
+        from test_gpu_heads_x16 import _launch_table as _launch_table_x16
+
+        table = {t[:3] for t in _launch_table() if not t[3]}
+        for name, tab in (("heads", table), ("x16", _launch_table_x16())):
+            w[name + " V"], w[name + " S"], w[name + " W"] = ({t[i] for t in tab} for i in range(3))
+            w[name + " route"] = {0, 1}
+    elif family == "sddmm":
+        # (the composition is reached under the pin alone; at two bytes a word W = 64 would need a width above 512)
+        w.update({"f32 route": {"kernel", "plain"}, "f32 V": {1, 2, 4}, "f32 W": POW2,
+                  "x16 route": {"kernel", "plain"}, "x16 V": {1, 2, 4, 8}, "x16 W": POW2 - {64}})
+    elif family == "softmax":
+        # (columns are drawn uniformly: none is swept while the mean column degree keeps W below 16)
+        w.update({"col W": {4, 8, 16}, "row regimes": both | {(16, "hub")}, "col regimes": both - {(4, "sweep"), (8, "sweep")}})
+    elif family in ("aggregate", "dropout"):
+        from test_gpu_gat_aggregate import _launch_table
+
+        for name in ("forward", "transposed"):
+            w[name + " V"], w[name + " S"], w[name + " W"] = ({t[i] for t in _launch_table()} for i in range(3))
+            w[name + " route"] = {0, 1}
+        w["row regimes"] = {(W, r) for W in (4, 8, 16) for r in ("register",)} | {(16, "hub")}
+        w["p"] = set(fz.PS)
+    elif family == "gatv2":
+        from test_gpu_gatv2_score import BWD, HF
+
+        w["score (V, W)"] = set(HF.values()) - {(4, 32)}  # (no width in (128, 256] is a multiple of 4)
+        w["backward (V, W)"] = {b[:2] for b in BWD.values()} - {(4, 4)}  # (H F <= 16 at V = 4: (1, 8) and (2, 8) alone, on 16-byte operands)
+        w["backward strips"] = {1, 2}
+    elif family == "dot":
+        w["(V, W)"] = {geometry(F, a) for F in fz.FS for a in (16, 8, 4)} & {(V, W) for V in (1, 2, 4) for W in POW2}
+        w["p"] = set(fz.PS)
+    elif family == "max_arg":
+        from test_gpu_max_arg import BUILT
+
+        for name in ("forward", "backward"):
+            w[name + " V"], w[name + " S"], w[name + " W"] = ({t[i] for t in BUILT} for i in range(3))
+    return w
+
+
+def _short(values):
+    return sorted(values, key=repr)
+
+
+@pytest.mark.parametrize("family", fz.FAMILIES)
+def test_reach(pkg, family):
+    """Counts at the seeds of FAMILY_SEEDS (24 cases a family): see DESIGN.md, "The attention sweep"."""
+    got, want = reach(family, pkg._lib), wanted(family)
+    if family == "dot":  # every V and every W, and of the 14 pairs the widths allow all but the ones tied to one (width, offset) draw
+        pairs = got.pop("(V, W)")
+        want.pop("(V, W)")
+        got["V"], got["W"] = {p[0] for p in pairs}, {p[1] for p in pairs}
+        want["V"], want["W"] = {1, 2, 4}, POW2
+    if family == "gatv2":
+        for k in ("score (V, W)", "backward (V, W)"):
+            pairs = got.pop(k)
+            want.pop(k)
+            got[k + ": V"], got[k + ": W"] = {p[0] for p in pairs}, {p[1] for p in pairs}
+            want[k + ": V"], want[k + ": W"] = ({1, 2, 4} if k.startswith("score") else {1, 4}), POW2
+    print(family, {k: _short(v) for k, v in got.items()})
+    missing = {k: _short(v - got[k]) for k, v in want.items() if not v <= got[k]}
+    assert not missing, (family, missing)
+
+
+# ------------------------------------------------------------------------------------------------- the comparison can fail
+
+def _short_case(family, need=2):
+    """The first case of the family whose rows have at most 65 entries, that has a row of at least ``need`` and at least 64 columns (on
+    one column every weighted mean of the features is that column's feature, whatever entry is lost) — and the entry of the largest
+    share of its longest row is what the tests below remove."""
+    for c in fz.family_cases(family):
+        d = c["G"]["degs"]
+        if d.size and need <= d.max() <= 65 and c["G"]["K"] >= 64 and c["H"] * c["F"] * c["G"]["nnz"] <= 1 << 18:
+            return c
+    raise AssertionError("no case of %s has rows of at most 65 entries" % family)
+
+
+def _without(G, e):
+    """The pattern without entry e (a CSR position), CSC arrays included."""
+    rows, cols = np.delete(G["rows"], e), np.delete(G["colind"], e)
+    rowptr = np.zeros(G["M"] + 1, dtype=np.int32)
+    rowptr[1:] = np.cumsum(np.bincount(rows, minlength=G["M"]))
+    colptr, rowind, order = refs.max_arg_transpose(rowptr, cols, G["K"])
+    return {"M": G["M"], "K": G["K"], "nnz": G["nnz"] - 1, "rowptr": rowptr, "colind": cols, "colptr": colptr, "rowind": rowind, "order": order,
+            "rows": rows, "degs": np.diff(rowptr)}
+
+
+def _longest_row(G):
+    r = int(np.argmax(G["degs"]))
+    return r, np.arange(G["rowptr"][r], G["rowptr"][r + 1])
+
+
+def test_heads_comparison_rejects_a_lost_entry():
+    c = _short_case("heads")
+    G, H, F = c["G"], c["H"], c["F"]
+    rng = np.random.RandomState(c["seed"])
+    val, B = fz.uniform(rng, (G["nnz"], H)), fz.uniform(rng, (G["K"], H, F))
+    full, mag = refs.heads_float64(G["rows"], G["colind"], G["M"], val, B)
+    r, e = _longest_row(G)
+    val2 = val.copy()
+    val2[e[np.argmax(np.abs(val[e, 0]))]] = 0  # the largest weight of head 0 in the longest row
+    lost, _ = refs.heads_float64(G["rows"], G["colind"], G["M"], val2, B)
+    worst, ok = refs.bound_ratio(lost.astype(np.float32), full, mag)
+    assert worst > 1 and not ok, worst
+    assert refs.bound_ratio(full.astype(np.float32), full, mag)[1]
+
+
+def test_sddmm_comparison_rejects_a_lost_term():
+    """An SDDMM result is one word per entry: what a walk can lose is a term of the dot. The largest term of one entry goes."""
+    c = _short_case("sddmm", need=1)
+    G, H, F = c["G"], c["H"], c["F"]
+    rng = np.random.RandomState(c["seed"])
+    D1, D2 = fz.away_from_zero(rng, (G["M"], H, F)), fz.away_from_zero(rng, (G["K"], H, F))
+    ref, mag = refs.sddmm_float64(G["rows"], G["colind"], D1, D2)
+    e = int(_longest_row(G)[1][0])
+    f = int(np.argmax(np.abs(D1[G["rows"][e], 0] * D2[G["colind"][e], 0])))
+    got = ref.copy()
+    got[e, 0] -= float(D1[G["rows"][e], 0, f]) * float(D2[G["colind"][e], 0, f])
+    worst, ok = refs.bound_ratio(got, ref, mag)
+    assert worst > 1 and not ok, worst
+
+
+def test_softmax_comparison_rejects_a_lost_entry():
+    c = _short_case("softmax")
+    G, H = c["G"], c["H"]
+    rng = np.random.RandomState(c["seed"])
+    s, g = fz.uniform(rng, (G["nnz"], H), 64), fz.uniform(rng, (G["nnz"], H), 8)
+    for slope in fz.SLOPES:
+        a, _ = refs.softmax_ref_forward(G["rowptr"], s, slope)
+        r, e = _longest_row(G)
+        lost = int(e[np.argmax(a[e, 0])])
+        G2 = _without(G, lost)
+        a2, tol2 = refs.softmax_ref_forward(G2["rowptr"], np.delete(s, lost, 0), slope)
+        got = np.delete(a, lost, 0).astype(np.float32)  # a walk over every entry, where the reference lost one
+        assert refs.softmax_worst_ratio(got, a2, tol2) > 1
+        assert refs.softmax_worst_ratio(a2.astype(np.float32), a2, tol2) <= 1
+        gb, _ = refs.softmax_ref_backward(G["rowptr"], a.astype(np.float32), g, s, slope)
+        gb2, gtol2 = refs.softmax_ref_backward(G2["rowptr"], a2.astype(np.float32), np.delete(g, lost, 0), np.delete(s, lost, 0), slope)
+        assert refs.softmax_worst_ratio(np.delete(gb, lost, 0).astype(np.float32), gb2, gtol2) > 1
+
+
+@pytest.mark.parametrize("family", ("aggregate", "dropout"))
+def test_gat_comparison_rejects_a_lost_entry(family):
+    c = _short_case(family)
+    G, H, slope = c["G"], c["H"], 0.2  # (without a slope grad_el is a sum of softmax gradients: zero whatever the entries are)
+    x = fz.gat_inputs(c)
+    keep = ks = None
+    if family == "dropout":
+        keep, ks = fz.keep_of(G, H, c["p"] or 0.25)
+    w, _ = refs.gat_weights_float64(G["rows"], G["colind"], G["M"], x["el"], x["er"], slope)
+    r, e = _longest_row(G)
+    share = w[e, 0] * (1.0 if keep is None else keep[e, 0])
+    assert share.max() > 0
+    lost = int(e[np.argmax(share)])
+    G2 = _without(G, lost)
+    keep2 = None if keep is None else np.delete(keep, lost, 0)
+    for transposed in (False, True):
+        dense = x["gout"] if transposed else x["feat"]
+        full, _ = refs.gat_aggregate_float64(G["rows"], G["colind"], G["M"], G["K"], x["el"], x["er"], dense, slope, transposed, keep, ks)
+        ref, mag = refs.gat_aggregate_float64(G2["rows"], G2["colind"], G["M"], G["K"], x["el"], x["er"], dense, slope, transposed, keep2, ks)
+        worst, ok = refs.bound_ratio(full.astype(np.float32), ref, mag)
+        assert worst > 1 and not ok, (transposed, worst)
+    full = refs.gat_backward_float64(G["rows"], G["colind"], G["M"], G["K"], x["el"], x["er"], x["gout"], x["feat"], slope, keep, ks)
+    ref = refs.gat_backward_float64(G2["rows"], G2["colind"], G["M"], G["K"], x["el"], x["er"], x["gout"], x["feat"], slope, keep2, ks)
+    for i, name in ((0, "grad_el"), (1, "grad_er")):
+        worst, ok = refs.bound_ratio(full[i].astype(np.float32), ref[i], ref[i + 2])
+        assert worst > 1 and not ok, (name, worst)
+
+
+def test_gatv2_comparison_rejects_a_lost_entry_and_a_lost_term():
+    c = _short_case("gatv2")
+    G, H, F, slope = c["G"], c["H"], c["F"], c["slope"]
+    o = fz.gatv2_inputs(c)
+    host = lambda P: {"rowptr": P["rowptr"], "colind": P["colind"], "colptr_h": P["colptr"], "rowind_h": P["rowind"],  # noqa: E731
+                      "order_h": P["order"]}
+    (score, terms), row, col = refs.gatv2_float64(host(G), o, slope)
+    r, e = _longest_row(G)
+    lost = int(e[np.argmax(np.abs(o["gs"][e, 0]))])
+    G2 = _without(G, lost)
+    o2 = dict(o, gs=np.delete(o["gs"], lost, 0))
+    _, row2, col2 = refs.gatv2_float64(host(G2), o2, slope)
+    for full, ref, tm, name in ((row[0], row2[0], row2[2], "grad_xl"), (row[1], row2[1], row2[3], "att_part"), (col[0], col2[0], col2[2], "grad_xr")):
+        assert refs.gatv2_worst_ratio(full.astype(np.float32), ref, tm, name) > 1, name
+    # the score is one word per entry: the largest term of one dot goes
+    t = o["xl"][G["rows"][lost], 0].astype(np.float64) + o["xr"][G["colind"][lost], 0].astype(np.float64)
+    k = 1.0 if slope is None else float(slope)
+    prod = o["att"][0].astype(np.float64) * np.where(t >= 0, t, t * k)
+    got = score.copy()
+    got[lost, 0] -= prod[np.argmax(np.abs(prod))]
+    assert refs.gatv2_worst_ratio(got, score, terms, "score") > 1
+
+
+def test_edge_dropout_comparison_rejects_a_flipped_decision():
+    c = _short_case("dropout")
+    G, H = c["G"], c["H"]
+    x = fz.uniform(np.random.RandomState(c["seed"]), (G["nnz"], H), 4)
+    for p in (0.25, 0.6):
+        keep, ks = fz.keep_of(G, H, p)
+        assert 0 < keep.sum() < keep.size
+        want = np.where(keep, x * ks, np.float32(0.0)).astype(np.float32)
+        e = int(_longest_row(G)[1][0])
+        flipped = keep.copy()
+        flipped[e, 0] = ~flipped[e, 0]
+        got = np.where(flipped, x * ks, np.float32(0.0)).astype(np.float32)
+        assert x[e, 0] != 0 and not np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def test_dot_attention_comparison_rejects_a_lost_entry():
+    c = _short_case("dot")
+    G, H = c["G"], c["H"]
+    x = fz.dot_inputs(c)
+    f = refs.dot_ref_forward(G, x)
+    stats = np.stack((f["m"], f["l"]), -1).astype(np.float32)
+    b = refs.dot_ref_backward(G, x, stats, f["out"].astype(np.float32))
+    got = {"out": f["out"].astype(np.float32), "stats": stats, "delta": b["delta"].astype(np.float32),
+           "grad_q": b["grad_q"].astype(np.float32), "grad_k": b["grad_k"].astype(np.float32), "grad_v": b["grad_v"].astype(np.float32)}
+    assert max(refs.dot_check_all(G, x, got, what="float64 itself").values()) <= 1
+    r, e = _longest_row(G)
+    lost = int(e[np.argmax(f["a"][e, 0])])
+    ratios = refs.dot_check_all(_without(G, lost), x, got, what="one entry lost")
+    for name in ("out", "l", "grad_q", "grad_k", "grad_v"):
+        assert ratios[name] > 1, (name, ratios)
+
+
+def test_max_arg_comparison_rejects_a_lost_entry():
+    c = _short_case("max_arg")
+    G, N = c["G"], c["H"] * c["F"]
+    B = np.abs(np.random.RandomState(c["seed"]).standard_normal((G["K"], N))).astype(np.float32)
+    C, arg = refs.max_arg_forward(G["rowptr"], G["colind"], B, -10000.0)
+    r, e = _longest_row(G)
+    lost = int(arg[r, 0])  # the winner of the longest row's first word
+    assert lost in e
+    G2 = _without(G, lost)
+    C2, arg2 = refs.max_arg_forward(G2["rowptr"], G2["colind"], B, -10000.0)
+    assert not np.array_equal(C.view(np.uint32), C2.view(np.uint32)) or len(np.unique(G["colind"][e])) < len(e)
+    assert not np.array_equal(arg, arg2)
+    grad = np.ones((G["M"], N), dtype=np.float32)
+    g1 = refs.max_backward(G["colptr"], G["rowind"], G["order"], arg, grad, G["K"])
+    g2 = refs.max_backward(G2["colptr"], G2["rowind"], G2["order"], arg2, grad, G["K"])
+    assert not np.array_equal(g1, g2)
+
+
+@pytest.mark.parametrize("H,F", ((8, 3), (8, 32), (33, 3), (33, 32)))
+def test_witness_for_the_head_counts_added_on_the_device(H, F):
+    """test_dot_attention_host.test_witness_every_entry_shows for the (H, F) that tests/test_gpu_dot_attention.py adds on the "hand"
+    pattern, at the seeds its SEEDS table names. At H = 33, F = 32 the condition holds for out, grad_q and grad_v; for grad_k no seed
+    below 1500 reaches it — the least share of an entry in a word of grad_k is a minimum over 33 heads now, and the best seed (1080, the
+    one in the table) brings it to 0.89 tolerances, short of the 1.25 that prove a skipped entry lands outside: there a skipped entry
+    shows through the other three results."""
+    from test_dot_attention_host import check_all, inputs, pattern, restate_all, witness_ratios
+
+    P, x = pattern("hand"), inputs("hand", H, F)
+    got, _, _ = restate_all(P, x, *geometry(F))
+    assert max(check_all(P, x, got, what="hand F=%d H=%d" % (F, H)).values()) <= 0.25
+    worst = witness_ratios(P, x)
+    print("hand F=%d H=%d least (change by a skipped entry / tolerance): %s" % (F, H, "  ".join("%s %.3g" % kv for kv in worst.items())))
+    if (H, F) == (33, 32):
+        assert worst.pop("grad_k") > 0.8, worst
+    assert min(worst.values()) > 1.25, worst
+
+
+# ------------------------------------------------------------------------------------------------- the references agree
+# The private helpers of the GPU test files as they stood before the move (``c`` holds torch tensors: ``.cpu().numpy()``), their own text.
+
+def _parent_aggregate_float64(G, c, dense_h, slope, transposed):
+    rows, cols = G["rows_h"], G["colind"]
+    x = (c["el"].cpu().numpy()[rows] + c["er"].cpu().numpy()[cols]).astype(np.float64)
+    if slope is not None:
+        x = np.where(x >= 0, x, x * float(np.float32(slope)))
+    M, H = G["M"], x.shape[1]
+    top = np.full((M, H), -np.inf)
+    np.maximum.at(top, rows, x)
+    t = np.exp(x - top[rows])
+    den = np.zeros((M, H))
+    np.add.at(den, rows, t)
+    w = t / den[rows]
+    src, dst, n = (rows, cols, G["K"]) if transposed else (cols, rows, M)
+    terms = w[:, :, None] * dense_h.astype(np.float64)[src]
+    ref, mag = np.zeros((n,) + dense_h.shape[1:]), np.zeros((n,) + dense_h.shape[1:])
+    np.add.at(ref, dst, terms)
+    np.add.at(mag, dst, np.abs(terms))
+    return ref, mag
+
+
+def _parent_backward_float64(G, c, gout_h, feat_h, slope, keep=None, s=None):
+    """test_gpu_gat_backward.py's helper and test_gpu_edge_dropout.py's (the same text with ``d``), joined by the one ``if``"""
+    rows, cols = G["rows_h"], G["colind"]
+    sc = (c["el"].cpu().numpy()[rows] + c["er"].cpu().numpy()[cols]).astype(np.float64)
+    k = 1.0 if slope is None else float(np.float32(slope))
+    x = np.where(sc >= 0, sc, sc * k)
+    M, K, H = G["M"], G["K"], x.shape[1]
+    top = np.full((M, H), -np.inf)
+    np.maximum.at(top, rows, x)
+    t = np.exp(x - top[rows])
+    den = np.zeros((M, H))
+    np.add.at(den, rows, t)
+    w = t / den[rows]
+    terms = gout_h.astype(np.float64)[rows] * feat_h.astype(np.float64)[cols]
+    if keep is None:
+        g, gabs = terms.sum(-1), np.abs(terms).sum(-1)
+    else:
+        d = np.where(keep, float(s), 0.0)
+        g, gabs = terms.sum(-1) * d, np.abs(terms).sum(-1) * d
+    dot, dabs = np.zeros((M, H)), np.zeros((M, H))
+    np.add.at(dot, rows, w * g)
+    np.add.at(dabs, rows, w * gabs)
+    gs = w * (g - dot[rows]) * np.where(sc >= 0, 1.0, k)
+    mag = w * (gabs + dabs[rows])
+    gel, ger, sel, ser = np.zeros((M, H)), np.zeros((K, H)), np.zeros((M, H)), np.zeros((K, H))
+    np.add.at(gel, rows, gs)
+    np.add.at(sel, rows, mag)
+    np.add.at(ger, cols, gs)
+    np.add.at(ser, cols, mag)
+    return gel, ger, sel, ser
+
+
+def _parent_gatv2_reference(G, o, slope):
+    from test_gatv2_host import restate_backward, restate_score
+
+    return (restate_score(G["rowptr"], G["colind"], o["xl"], o["xr"], o["att"], slope),
+            restate_backward(G["rowptr"], G["colind"], o["gs"], o["xl"], o["xr"], o["att"], slope),
+            restate_backward(G["colptr_h"], G["rowind_h"], o["gs"], o["xr"], o["xl"], o["att"], slope, order=G["order_h"]))
+
+
+def _flat(x):
+    return [x] if isinstance(x, np.ndarray) else [a for part in x for a in _flat(part)]
+
+
+def test_the_moved_references_give_what_the_private_helpers_gave():
+    c = _short_case("aggregate")
+    G, H = c["G"], c["H"]
+    x = fz.gat_inputs(c)
+    Gp = {"rows_h": G["rows"], "colind": G["colind"], "M": G["M"], "K": G["K"]}
+    cp = {"el": torch.from_numpy(x["el"]), "er": torch.from_numpy(x["er"])}
+    keep, ks = fz.keep_of(G, H, 0.6)
+    for slope in fz.SLOPES:
+        for transposed in (False, True):
+            dense = x["gout"] if transposed else x["feat"]
+            old = _parent_aggregate_float64(Gp, cp, dense, slope, transposed)
+            new = refs.gat_aggregate_float64(G["rows"], G["colind"], G["M"], G["K"], x["el"], x["er"], dense, slope, transposed)
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(old, new)), (slope, transposed)
+        for kp, s in ((None, None), (keep, ks)):
+            old = _parent_backward_float64(Gp, cp, x["gout"], x["feat"], slope, kp, s)
+            new = refs.gat_backward_float64(G["rows"], G["colind"], G["M"], G["K"], x["el"], x["er"], x["gout"], x["feat"], slope, kp, s)
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(old, new)), (slope, kp is not None)
+    c = _short_case("gatv2")
+    G = c["G"]
+    o = fz.gatv2_inputs(c)
+    host = {"rowptr": G["rowptr"], "colind": G["colind"], "colptr_h": G["colptr"], "rowind_h": G["rowind"], "order_h": G["order"]}
+    for slope in (None, 0.2):
+        old, new = _flat(_parent_gatv2_reference(host, o, slope)), _flat(refs.gatv2_float64(host, o, slope))
+        assert len(old) == len(new) == 10 and all(a.tobytes() == b.tobytes() for a, b in zip(old, new))
+    # the re-exports are the host modules' own objects
+    import max_arg_ref
+    import test_dot_attention_host as dot
+    import test_edge_softmax_host as es
+    import test_gatv2_host as v2
+
+    assert refs.softmax_ref_forward is es.ref_forward and refs.softmax_ref_backward is es.ref_backward and refs.softmax_worst_ratio is es.worst_ratio
+    assert refs.gatv2_restate_score is v2.restate_score and refs.gatv2_restate_backward is v2.restate_backward
+    assert refs.gatv2_worst_ratio is v2.worst_ratio and refs.dot_ref_forward is dot.ref_forward and refs.dot_ref_backward is dot.ref_backward
+    assert refs.dot_check_all is dot.check_all and refs.max_arg_forward is max_arg_ref.max_arg_forward
+    assert refs.max_backward is max_arg_ref.max_backward

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_dot_attention_host import F32, F64, FS, HS, SEED, check_all, geometry, inputs, keep_mask, pattern, ratio, ref_forward, seg_sum
+from test_dot_attention_host import (F32, F64, FS, HS, SEED, _chain_case, check_all, geometry, inputs, keep_mask, pattern, ratio, ref_forward,
+                                     seg_sum, transpose)
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +86,61 @@ def test_three_launches_against_float64(pkg, F, H):
         again = _run(P, x)
         for key in got:
             assert _bits_equal(got[key], again[key]), "second run: " + key
+
+
+@pytest.mark.parametrize("H", (8, 33))
+@pytest.mark.parametrize("F", (3, 32))
+def test_many_heads_against_float64(pkg, F, H):
+    """Head counts past the kernels' own tests (the other ops go up to 33) on the "hand" pattern, with the inputs of ``inputs()``: the
+    witness condition for these (H, F) is asserted in tests/test_attention_fuzz_host.py."""
+    from gespmm_amd import _lib
+
+    assert _lib.describe_dot_attention(71, 53, H, F, 100) == dict(zip("VW", geometry(F)))
+    P, x = pattern("hand"), inputs("hand", H, F)
+    got = _run(P, x)
+    h = _host(got)
+    for key, a in h.items():
+        assert not np.isnan(a).any(), "a word of %s was not written" % key
+    r = check_all(P, x, h, what="gpu hand F=%d H=%d" % (F, H))
+    assert max(r.values()) <= 1.0, r
+    one, none = np.nonzero(P["degs"] == 1)[0], np.nonzero(P["degs"] == 0)[0]
+    assert h["out"][one].tobytes() == x["v"][P["colind"][P["rowptr"][one]]].tobytes() and np.all(h["stats"][one, :, 1] == 1.0)
+    for key in ("out", "stats", "delta", "grad_q"):
+        assert not h[key][none].any() and not np.signbit(h[key][none]).any(), key
+    again = _run(P, x)
+    for key in got:
+        assert _bits_equal(got[key], again[key]), "second run: " + key
+
+
+_UP = np.linspace(-3, 3, 40)
+CHAINS = {"single": [0.37], "ascending": _UP, "descending": _UP[::-1], "far": [-80.0, 80.0, -79.0, 0.0, 79.5, -80.0]}
+
+
+@pytest.mark.parametrize("name", sorted(CHAINS))
+def test_online_softmax_corner_cases_on_the_kernel(pkg, name):
+    """``_chain_case`` of the host module on the kernels, held to what test_special_shapes_exact asserts of the restatement: a single
+    entry (out and stats exact, the rows around it +0), 40 ascending scores (a rescale at every entry), 40 descending ones (none), and
+    scores of +-80 where t underflows — and both backward launches on each, against ``ref_backward``."""
+    P, x = _chain_case(CHAINS[name])
+    P = dict(P)
+    P["colptr"], P["rowind"], P["order"] = transpose(P["rowptr"], P["colind"], P["K"])
+    x = dict(x, go=np.random.RandomState(5).uniform(0.5, 1.0, size=x["q"].shape).astype(F32))
+    h = _host(_run(P, x))
+    for key, a in h.items():
+        assert np.isfinite(a).all(), "%s: a word of %s was not written, or is not finite" % (name, key)
+    out, stats = h["out"], h["stats"]
+    f = ref_forward(P, x)
+    if name == "single":
+        assert out[1].tobytes() == x["v"][0].tobytes() and stats[1, 0, 0] == F32(0.37) and stats[1, 0, 1] == 1.0
+        assert not out[[0, 2]].any() and not stats[[0, 2]].any() and not np.signbit(out[[0, 2]]).any() and not np.signbit(stats[[0, 2]]).any()
+    elif name == "far":
+        assert stats[1, 0, 0] == F32(80.0)
+        assert ratio(out, f["out"], f["tol_out"]) <= 1.0
+    else:
+        assert stats[1, 0, 0] == F32(3.0)
+        assert ratio(out, f["out"], f["tol_out"]) <= 1.0 and ratio(stats[..., 1], f["l"], f["tol_l"]) <= 1.0
+    r = check_all(P, x, h, what="gpu chain %s" % name)
+    assert max(r.values()) <= 1.0, r
 
 
 @pytest.mark.parametrize("F", (3, 8, 64, 100))

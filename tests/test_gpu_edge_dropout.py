@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from attention_refs import gat_backward_float64
 from test_edge_dropout_host import restate
 from test_gpu_edge_softmax import NAN, _dev, _guard_ok, _out, _same
 from test_gpu_gat_aggregate import PIN
@@ -248,35 +249,6 @@ def test_backward_equals_the_composition_where_the_dot_is_exact(pkg, graphs_, H,
     assert compared > 0, "no (row, head) pair had exact products: delta was compared nowhere"
 
 
-def _float64(G, c, gout_h, feat_h, slope, keep, s):
-    """tests/test_gpu_gat_backward.py's float64 restatement with g' = keep ? g s : 0 -> (grad_el, grad_er, scale_el, scale_er)."""
-    rows, cols = G["rows_h"], G["colind"]
-    sc = (c["el"].cpu().numpy()[rows] + c["er"].cpu().numpy()[cols]).astype(np.float64)
-    k = 1.0 if slope is None else float(np.float32(slope))
-    x = np.where(sc >= 0, sc, sc * k)
-    M, K, H = G["M"], G["K"], x.shape[1]
-    top = np.full((M, H), -np.inf)
-    np.maximum.at(top, rows, x)
-    t = np.exp(x - top[rows])
-    den = np.zeros((M, H))
-    np.add.at(den, rows, t)
-    w = t / den[rows]
-    terms = gout_h.astype(np.float64)[rows] * feat_h.astype(np.float64)[cols]
-    d = np.where(keep, float(s), 0.0)
-    g, gabs = terms.sum(-1) * d, np.abs(terms).sum(-1) * d
-    dot, dabs = np.zeros((M, H)), np.zeros((M, H))
-    np.add.at(dot, rows, w * g)
-    np.add.at(dabs, rows, w * gabs)
-    gs = w * (g - dot[rows]) * np.where(sc >= 0, 1.0, k)
-    mag = w * (gabs + dabs[rows])
-    gel, ger, sel, ser = np.zeros((M, H)), np.zeros((K, H)), np.zeros((M, H)), np.zeros((K, H))
-    np.add.at(gel, rows, gs)
-    np.add.at(sel, rows, mag)
-    np.add.at(ger, cols, gs)
-    np.add.at(ser, cols, mag)
-    return gel, ger, sel, ser
-
-
 @pytest.mark.parametrize("H,F", ((4, 2), (8, 8), (1, 64), (3, 5)))
 def test_backward_against_float64(pkg, graphs_, H, F):
     """The new kernels AND the composition, each inside 1e-4 max(|ref|, scale) of float64 with the numpy mask."""
@@ -287,7 +259,9 @@ def test_backward_against_float64(pkg, graphs_, H, F):
             for p, pair in zip(PS, SEEDS):
                 c = _case(G, H, slope)
                 gout, feat = _reals(G["M"], H, F, 900 + H + F), _reals(G["K"], H, F, 901 + H + F)
-                ref_el, ref_er, sc_el, sc_er = _float64(G, c, gout.cpu().numpy(), feat.cpu().numpy(), slope, _keep(G, pair, p, H), _scale(p))
+                ref_el, ref_er, sc_el, sc_er = gat_backward_float64(G["rows_h"], G["colind"], G["M"], G["K"], c["el"].cpu().numpy(),
+                                                                    c["er"].cpu().numpy(), gout.cpu().numpy(), feat.cpu().numpy(), slope,
+                                                                    _keep(G, pair, p, H), _scale(p))
                 _, gel, ger = _fused(G, c, gout, feat, slope, (p, _seed(pair)))
                 _, _, cel, cer = _composition(G, c, gout, feat, slope, p, pair)
                 for what, got, ref, scale in (("kernel grad_el", gel, ref_el, sc_el), ("kernel grad_er", ger, ref_er, sc_er),

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from attention_refs import gat_aggregate_float64
 from helpers import ROOT
 from test_gat_softmax_host import csc_of
 from test_gpu_edge_softmax import NAN, _dev, _guard_ok, _out, _same
@@ -224,27 +225,6 @@ def test_every_instantiation_of_the_launch_table_runs(pkg, graphs_, monkeypatch)
 
 # ---------------------------------------------------------------------------------------------------------- 4. independent check
 
-def _float64(G, c, dense_h, slope, transposed):
-    """Softmax, then product, in float64 on the host -> (ref, sum |w b|). The score is the contract's rounded sum fl(el + er)."""
-    rows, cols = G["rows_h"], G["colind"]
-    x = (c["el"].cpu().numpy()[rows] + c["er"].cpu().numpy()[cols]).astype(np.float64)
-    if slope is not None:
-        x = np.where(x >= 0, x, x * float(np.float32(slope)))
-    M, H = G["M"], x.shape[1]
-    top = np.full((M, H), -np.inf)
-    np.maximum.at(top, rows, x)
-    t = np.exp(x - top[rows])
-    den = np.zeros((M, H))
-    np.add.at(den, rows, t)
-    w = t / den[rows]
-    src, dst, n = (rows, cols, G["K"]) if transposed else (cols, rows, M)
-    terms = w[:, :, None] * dense_h.astype(np.float64)[src]
-    ref, mag = np.zeros((n,) + dense_h.shape[1:]), np.zeros((n,) + dense_h.shape[1:])
-    np.add.at(ref, dst, terms)
-    np.add.at(mag, dst, np.abs(terms))
-    return ref, mag
-
-
 @pytest.mark.parametrize("transposed", (False, True))
 @pytest.mark.parametrize("H,F", ((4, 2), (8, 8), (1, 64)))
 def test_against_float64(pkg, graphs_, H, F, transposed, monkeypatch):
@@ -255,7 +235,8 @@ def test_against_float64(pkg, graphs_, H, F, transposed, monkeypatch):
         for slope in SLOPES:
             c = _case(G, H, slope)
             dense = _feat(G["M"] if transposed else G["K"], H, F, 900 + H + F)
-            ref, mag = _float64(G, c, dense.cpu().numpy(), slope, transposed)
+            ref, mag = gat_aggregate_float64(G["rows_h"], G["colind"], G["M"], G["K"], c["el"].cpu().numpy(), c["er"].cpu().numpy(),
+                                             dense.cpu().numpy(), slope, transposed)
             bound = 1e-4 * np.maximum(np.abs(ref), mag)
             assert _route(G, H, F, transposed)[0] == 1
             for what, got in (("kernel", _aggregate(G, c, dense, slope, transposed)), ("composition", _composition(G, c, dense, transposed))):

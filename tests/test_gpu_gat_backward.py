@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from attention_refs import gat_backward_float64
 from test_edge_softmax_host import IT, WANT_L, want_W
 from test_gat_softmax_host import csc_of
 from test_gpu_edge_softmax import NAN, _dev, _guard_ok, _out, _same
@@ -184,35 +185,6 @@ def test_one_rounded_product_at_width_one(pkg, graphs_, H, slope):
 
 # ------------------------------------------------------------------------------------------------------------------ 3. accuracy
 
-def _float64(G, c, gout_h, feat_h, slope):
-    """Softmax, dot, backward and both sums in float64 on the host -> (grad_el, grad_er, scale_el, scale_er) with
-    scale = sum_p w_p (G_p + sum_q w_q G_q), G_p = sum_f |grad_out feat|. The score is the contract's rounded sum fl(el + er)."""
-    rows, cols = G["rows_h"], G["colind"]
-    s = (c["el"].cpu().numpy()[rows] + c["er"].cpu().numpy()[cols]).astype(np.float64)
-    k = 1.0 if slope is None else float(np.float32(slope))
-    x = np.where(s >= 0, s, s * k)
-    M, K, H = G["M"], G["K"], x.shape[1]
-    top = np.full((M, H), -np.inf)
-    np.maximum.at(top, rows, x)
-    t = np.exp(x - top[rows])
-    den = np.zeros((M, H))
-    np.add.at(den, rows, t)
-    w = t / den[rows]
-    terms = gout_h.astype(np.float64)[rows] * feat_h.astype(np.float64)[cols]
-    g, gabs = terms.sum(-1), np.abs(terms).sum(-1)
-    dot, dabs = np.zeros((M, H)), np.zeros((M, H))
-    np.add.at(dot, rows, w * g)
-    np.add.at(dabs, rows, w * gabs)
-    gs = w * (g - dot[rows]) * np.where(s >= 0, 1.0, k)
-    mag = w * (gabs + dabs[rows])
-    gel, ger, sel, ser = np.zeros((M, H)), np.zeros((K, H)), np.zeros((M, H)), np.zeros((K, H))
-    np.add.at(gel, rows, gs)
-    np.add.at(sel, rows, mag)
-    np.add.at(ger, cols, gs)
-    np.add.at(ser, cols, mag)
-    return gel, ger, sel, ser
-
-
 @pytest.mark.parametrize("H,F", ((4, 2), (8, 8), (1, 64), (3, 5)))
 def test_against_float64(pkg, graphs_, H, F):
     """The new kernels AND the composition, each inside 1e-4 max(|ref|, scale) of float64."""
@@ -221,7 +193,8 @@ def test_against_float64(pkg, graphs_, H, F):
         for slope in SLOPES:
             c = _case(G, H, slope)
             gout, feat = _reals(G["M"], H, F, 900 + H + F), _reals(G["K"], H, F, 901 + H + F)
-            ref_el, ref_er, sc_el, sc_er = _float64(G, c, gout.cpu().numpy(), feat.cpu().numpy(), slope)
+            ref_el, ref_er, sc_el, sc_er = gat_backward_float64(G["rows_h"], G["colind"], G["M"], G["K"], c["el"].cpu().numpy(),
+                                                                c["er"].cpu().numpy(), gout.cpu().numpy(), feat.cpu().numpy(), slope)
             _, gel, ger = _fused(G, c, gout, feat, slope)
             _, _, cel, cer = _composition(G, c, slope, gout=gout, feat=feat)
             for what, got, ref, scale in (("kernel grad_el", gel, ref_el, sc_el), ("kernel grad_er", ger, ref_er, sc_er),

@@ -9,16 +9,16 @@ import numpy as np
 import pytest
 import torch
 
+from attention_refs import gat_backward_float64
 from helpers import ROOT
 from test_gpu_gat import _dev, _gat_float64, _rand, _random_graph
 from test_gpu_gat_aggregate_layer import _bits_equal, _cora, _square_edge
-from test_gpu_gat_backward import _float64
 
 pytestmark = pytest.mark.gpu
 
 
 def _graph(name):
-    """-> (n, host dict for _float64, the five device index tensors GATConv.forward takes)"""
+    """-> (n, host dict for gat_backward_float64, the five device index tensors GATConv.forward takes)"""
     from gespmm_amd import graphs
 
     if name == "random":
@@ -54,7 +54,8 @@ def test_function_fused_backward_against_the_default(pkg, name, heads, slope):
         assert el.grad.shape == (n, H) and er.grad.shape == (n, H)
     assert _bits_equal(got[True][0], got[False][0]), "forward"
     assert _bits_equal(got[True][1], got[False][1]), "grad_feat: the same launch"
-    ref_el, ref_er, sc_el, sc_er = _float64(host, {"el": el0, "er": er0}, gout.cpu().numpy(), feat0.cpu().numpy(), slope)
+    ref_el, ref_er, sc_el, sc_er = gat_backward_float64(host["rows_h"], host["colind"], n, n, el0.cpu().numpy(), er0.cpu().numpy(),
+                                                        gout.cpu().numpy(), feat0.cpu().numpy(), slope)
     for fused in (True, False):
         for what, g, ref, scale in (("grad_el", got[fused][2], ref_el, sc_el), ("grad_er", got[fused][3], ref_er, sc_er)):
             bound = 1e-4 * np.maximum(np.abs(ref), scale)

@@ -12,9 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+from attention_refs import gatv2_float64
 from test_edge_softmax_host import WANT_L
 from test_gat_softmax_host import csc_of
-from test_gatv2_host import restate_backward, restate_score, worst_ratio
+from test_gatv2_host import worst_ratio
 from test_gpu_edge_softmax import NAN, _dev, _guard_ok, _out, _same
 from test_gpu_gat_softmax import PATTERNS, _pattern
 from test_gpu_heads import _carve
@@ -111,13 +112,6 @@ def _operands(G, H, F, kind):
     return G["cache"][key]
 
 
-def _reference(G, o, slope):
-    """float64: (score, terms), the row pass (grad_xl, att_part, terms, terms) and the column pass (grad_xr, _, terms, _)."""
-    return (restate_score(G["rowptr"], G["colind"], o["xl"], o["xr"], o["att"], slope),
-            restate_backward(G["rowptr"], G["colind"], o["gs"], o["xl"], o["xr"], o["att"], slope),
-            restate_backward(G["colptr_h"], G["rowind_h"], o["gs"], o["xr"], o["xl"], o["att"], slope, order=G["order_h"]))
-
-
 def _run(G, d, slope, H, F):
     """The three launches into guarded, NaN-prefilled tensors -> (score, grad_xl, att_part, grad_xr)."""
     from gespmm_amd import sddmm
@@ -152,7 +146,7 @@ def test_bits_on_exact_operands(pkg, graphs_, name, H, F, slope):
     o = _operands(G, H, F, "int")
     longest = max(np.diff(G["rowptr"]).max(), np.diff(G["colptr_h"]).max())
     assert 2 * 8 * F < 2 ** 22 and 2 * 8 * longest < 2 ** 22 and 2 * 2 * longest < 2 ** 22
-    (score, terms), row, col = _reference(G, o, slope)
+    (score, terms), row, col = gatv2_float64(G, o, slope)
     assert max(terms.max(), row[2].max(), row[3].max(), col[2].max()) < 2 ** 22
     for ref in (score, row[0], row[1], col[0]):
         assert np.array_equal(ref * 4, np.round(ref * 4))
@@ -185,7 +179,7 @@ def test_real_operands_against_float64(pkg, graphs_, name, H, F):
     G = graphs_[name]
     o = _operands(G, H, F, "real")
     for slope in (None, 0.2):
-        (score, terms), row, col = _reference(G, o, slope)
+        (score, terms), row, col = gatv2_float64(G, o, slope)
         got = [g.cpu().numpy() for g in _run(G, o["dev"], slope, H, F)]
         for g, ref, tm, what in zip(got, (score, row[0], row[1], col[0]), (terms, row[2], row[3], col[2]),
                                     ("score", "grad_xl", "att_part", "grad_xr")):
@@ -235,7 +229,7 @@ def test_a_bad_word_poisons_what_the_restatement_says(pkg, graphs_, bad):
     o["xl"][row, 1, 5] = bad
     d = dict(o["dev"], xl=_dev(o["xl"]))
     for slope in SLOPES:
-        (score, _), rowp, colp = _reference(G, o, slope)
+        (score, _), rowp, colp = gatv2_float64(G, o, slope)
         got = _run(G, d, slope, H, F)
         for g, ref, what in zip(got, (score, rowp[0], rowp[1], colp[0]), ("score", "grad_xl", "att_part", "grad_xr")):
             g = g.cpu().numpy().reshape(ref.shape)
