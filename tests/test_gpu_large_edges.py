@@ -14,8 +14,10 @@ gathers in pieces below that size. With ``take_edges`` replaced by plain indexin
 and [8-bfloat16] fail from row 1024 = nnz - 2^26 on, and all cases of test_multi_head_spmm_function / test_multi_head_sddmm_function
 fail in grad_feat / grad_k at column 77, the column that holds CSC position 1024.
 
-On the MI355X the module takes about 6 s (the fixture 1 s, no test above 1.3 s) and peaks at 7.8 GB of device memory (the control-size test, which
-holds a second pattern; 7.2 GB otherwise)."""
+Section f runs the edge-sized ops again at H = 17 — arrays of 1.14e9 words, between 2^30 and 2^31 — and take_edges at 64-byte rows.
+
+On the MI355X the module takes about 8.4 s (the fixture 1 s, no test above 1.3 s) and peaks at 19.3 GiB of device memory (section f: four
+arrays of 4.5 GB; 7.8 GB without it)."""
 import numpy as np
 import pytest
 import torch
@@ -222,9 +224,12 @@ def test_multi_head_sddmm_function(big, dtype, order_dtype):
 
 @pytest.mark.parametrize("x16", (False, True), ids=("f32", "bf16"))
 def test_sddmm_heads_csr_and_coo(big, x16):
+    _sddmm_heads_case(big, 4, 8, x16, big.row_windows)
+
+
+def _sddmm_heads_case(g, H, F, x16, row_windows):
     from gespmm_amd import _lib, sddmm
 
-    g, H, F = big, 4, 8
     dtype = torch.bfloat16 if x16 else torch.float32
     assert _lib.describe_sddmm_heads(True, g.M, g.nnz, H, F, x16=x16)["route"] == "kernel"
     assert _lib.describe_sddmm_heads(False, g.M, g.nnz, H, F, x16=x16)["route"] == "kernel"
@@ -236,10 +241,10 @@ def test_sddmm_heads_csr_and_coo(big, x16):
         return band.ref_csr_scores(g.M, g.d, r0, r1, H, F, DEV)
 
     s = csr_fn(g.rowptr, g.colind, q, k, out=_nan((g.nnz, H)))
-    _check_windows("csr_sddmm_heads %s" % dtype, s, g.row_windows, ref, scale=g.d)
+    _check_windows("csr_sddmm_heads %s" % dtype, s, row_windows, ref, scale=g.d)
     rows = torch.div(torch.arange(g.nnz, device=DEV, dtype=torch.int32), g.d, rounding_mode="floor")
     s2 = coo_fn(rows, g.colind, q, k, out=_nan((g.nnz, H)))
-    _check_windows("coo_sddmm_heads %s" % dtype, s2, g.row_windows, ref, scale=g.d)
+    _check_windows("coo_sddmm_heads %s" % dtype, s2, row_windows, ref, scale=g.d)
     assert torch.equal(s, s2), "the two forms agree in every word"
     del s, s2
     # the COO form on the CSC order of the same edges: (rowind, column of the position) — the score array in CSC order
@@ -259,21 +264,24 @@ def test_sddmm_heads_csr_and_coo(big, x16):
 
 
 def test_edge_segment_sum_over_columns(big):
+    _edge_segment_sum_case(big, 4, big.row_windows, big.col_windows)
+
+
+def _edge_segment_sum_case(g, H, row_windows, col_windows):
     from gespmm_amd import softmax
 
-    g, H = big, 4
     x = g.weights(H)
     out = softmax.edge_segment_sum(g.colptr, x, order=g.order32, out=_nan((g.K, H)))
     one = lambda r, h, f: 1  # noqa: E731
-    _check_windows("edge_segment_sum(colptr, w, order)", out.view(g.K, H, 1), g.col_windows,
+    _check_windows("edge_segment_sum(colptr, w, order)", out.view(g.K, H, 1), col_windows,
                    lambda c0, c1: band.ref_csc_product(g.M, g.d, c0, c1, H, 1, DEV, dense_fn=one))
     x1 = x[:, 0].contiguous()
     out1 = softmax.edge_segment_sum(g.colptr, x1, order=g.order32, out=_nan((g.K,)))
-    _check_windows("edge_segment_sum(colptr, w[nnz], order)", out1.view(g.K, 1, 1), g.col_windows,
+    _check_windows("edge_segment_sum(colptr, w[nnz], order)", out1.view(g.K, 1, 1), col_windows,
                    lambda c0, c1: band.ref_csc_product(g.M, g.d, c0, c1, 1, 1, DEV, dense_fn=one))
     # rows: no order, segments are the CSR rows
     outr = softmax.edge_segment_sum(g.rowptr, x, out=_nan((g.M, H)))
-    _check_windows("edge_segment_sum(rowptr, w)", outr.view(g.M, H, 1), g.row_windows,
+    _check_windows("edge_segment_sum(rowptr, w)", outr.view(g.M, H, 1), row_windows,
                    lambda r0, r1: band.ref_csr_product(g.M, g.d, r0, r1, H, 1, DEV, dense_fn=one))
 
 
@@ -414,10 +422,14 @@ def _all_written(**results):
 
 @pytest.mark.parametrize("slope", (None, 0.2))
 def test_edge_softmax_forward_and_backward(big, subs, slope):
+    _edge_softmax_case(big, subs, 4, slope)
+
+
+def _edge_softmax_case(g, subs, H, slope):
     from gespmm_amd import softmax
     from test_edge_softmax_host import ref_backward, ref_forward, worst_ratio
 
-    g, H, gen = big, 4, _gen(11)
+    gen = _gen(11)
     score, grad = _rand(gen, (g.nnz, H), -16, 16), _rand(gen, (g.nnz, H), -2, 2)
     alpha = softmax.edge_softmax(g.rowptr, score, out=_nan((g.nnz, H)), negative_slope=slope)
     gs = softmax.edge_softmax_backward(g.rowptr, alpha, grad, score=score if slope is not None else None, negative_slope=slope,
@@ -431,27 +443,36 @@ def test_edge_softmax_forward_and_backward(big, subs, slope):
         rf, rb = worst_ratio(ah, a, tol), worst_ratio(s.edges(gs), gref, gtol)
         worst = [max(worst[0], rf), max(worst[1], rb)]
         assert rf <= 1.0 and rb <= 1.0, ("rows %d .. %d" % (s.r0, s.r1), slope, rf, rb)
-    print("edge_softmax slope=%s: worst error / tolerance forward %.3f backward %.3f" % (slope, *worst))
+    print("edge_softmax H=%d slope=%s: worst error / tolerance forward %.3f backward %.3f" % (H, slope, *worst))
 
 
 def test_gat_softmax_forward_and_backward(big, subs):
+    _gat_softmax_case(big, subs, 4)
+
+
+def _gat_softmax_case(g, subs, H):
     from gespmm_amd import _lib, softmax
     from test_edge_softmax_host import WANT_L, ref_backward, ref_forward, worst_ratio
     from test_gat_softmax_host import lane_sum, sum_bound, worst_sum_ratio
 
-    g, H, slope, gen = big, 4, 0.2, _gen(12)
+    slope, gen = 0.2, _gen(12)
     assert g.d <= WANT_L
     W_row, W_col = (_lib.describe_edge_softmax(n, g.nnz, H)["W"] for n in (g.M, g.K))
     el, er, grad = _rand(gen, (g.M, H), -16, 16), _rand(gen, (g.K, H), -16, 16), _rand(gen, (g.nnz, H), -2, 2)
     alpha = softmax.gat_edge_softmax(g.rowptr, g.colind, el, er, negative_slope=slope, out=_nan((g.nnz, H)))
+    stats = softmax.gat_softmax_stats(g.rowptr, g.colind, el, er, negative_slope=slope, out=_nan((g.M, H, 2)))
     _poison((g.nnz, H))
     gs, gel = softmax.gat_edge_softmax_backward(g.rowptr, g.colind, alpha, grad, el=el, er=er, negative_slope=slope)
     ger = softmax.edge_segment_sum(g.colptr, gs, order=g.order32, out=_nan((g.K, H)))
-    _all_written(alpha=alpha, grad_score=gs, grad_el=gel, grad_er=ger)
+    _all_written(alpha=alpha, grad_score=gs, grad_el=gel, grad_er=ger, stats=stats)
     worst = {}
     for s in subs:
         sh = s.row_nodes(el)[s.rows] + s.col_nodes(er)[s.colind]  # fl(el + er): one fp32 add, the contract's score
         assert sh.dtype == np.float32
+        # the statistics: m the row's largest leaky score on its bits, s = sum exp(x - m) >= 1 whose quotient IS alpha's
+        lk = np.where(sh >= 0, sh, sh * np.float32(slope)).astype(np.float32).reshape(s.M, g.d, H)
+        st = s.row_nodes(stats)
+        assert np.array_equal(st[..., 0].view(np.uint32), lk.max(1).view(np.uint32)) and bool((st[..., 1] >= 1.0).all()), "stats rows %d .." % s.r0
         ah, gsh = s.edges(alpha), s.edges(gs)
         a, tol = ref_forward(s.rowptr, sh, slope)
         gref, gtol = ref_backward(s.rowptr, ah, s.edges(grad), sh, slope)
@@ -464,14 +485,18 @@ def test_gat_softmax_forward_and_backward(big, subs):
             r[name] = worst_sum_ratio(got, ref, bound)
         assert max(r.values()) <= 1.0, ("rows %d .. %d" % (s.r0, s.r1), r)
         worst = {k: max(v, worst.get(k, 0.0)) for k, v in r.items()}
-    print("gat softmax: worst error / tolerance %s" % worst)
+    print("gat softmax H=%d: worst error / tolerance %s" % (H, worst))
 
 
 def test_gatv2_score_forward_and_both_backward_passes(big, subs):
+    _gatv2_case(big, subs, 4, 8)
+
+
+def _gatv2_case(g, subs, H, F):
     from gespmm_amd import sddmm
     from test_gatv2_host import restate_backward, restate_score, worst_ratio
 
-    g, H, F, slope, gen = big, 4, 8, 0.2, _gen(13)
+    slope, gen = 0.2, _gen(13)
     xl, xr = _rand(gen, (g.M, H, F), -1, 1), _rand(gen, (g.K, H, F), -1, 1)
     att, gsc = _rand(gen, (H, F), -2, 2), _rand(gen, (g.nnz, H), -2, 2)
     score = sddmm.gatv2_score(g.rowptr, g.colind, xl, xr, att, negative_slope=slope, out=_nan((g.nnz, H)))
@@ -490,7 +515,7 @@ def test_gatv2_score_forward_and_both_backward_passes(big, subs):
              "grad_xr": worst_ratio(s.full_cols(gxr), col[0][s.full], col[2][s.full], "grad_xr")}
         assert max(r.values()) <= 1.0, ("rows %d .. %d" % (s.r0, s.r1), r)
         worst = {k: max(v, worst.get(k, 0.0)) for k, v in r.items()}
-    print("gatv2: worst error / bound %s" % worst)
+    print("gatv2 H=%d F=%d: worst error / bound %s" % (H, F, worst))
 
 
 def test_dot_attention_three_launches(big, subs):
@@ -524,10 +549,14 @@ def test_dot_attention_three_launches(big, subs):
 
 
 def test_edge_dropout_mask(big, subs):
+    _edge_dropout_case(big, subs, 4)
+
+
+def _edge_dropout_case(g, subs, H):
     from gespmm_amd import _lib, softmax
     from test_edge_dropout_host import restate
 
-    g, H, p, gen = big, 4, 0.3, _gen(15)
+    p, gen = 0.3, _gen(15)
     x = _rand(gen, (g.nnz, H), -2, 2)
     seed = torch.from_numpy(np.array(DROPOUT_SEED, dtype=np.uint32).view(np.int32)).to(DEV)
     y = softmax.edge_dropout(g.rowptr, g.colind, x, p, seed, out=_nan((g.nnz, H)))
@@ -548,3 +577,66 @@ def test_edge_dropout_mask(big, subs):
         got = s.edges(y)
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "rows %d .. %d: %d words differ from the restated mask" % (
             s.r0, s.r1, int((got.view(np.uint32) != want.view(np.uint32)).sum()))
+
+
+# ---- f. the same edge-sized arrays past 2^30 WORDS: H = 17 on the same pattern is 1.14e9 words, 4.5 GB an array -------------------------
+# Every kernel above forms the word position e H + h of an [nnz, H] array in 32 bits; at H = 4 and 8 it stays below 2^30, so a position
+# that is turned into a 32-bit BYTE offset somewhere has never wrapped. The windows gain the one that holds edge floor(2^30 / H) — word
+# 2^30 lies inside its row of the array — in CSR order and, for the column-wise results, in CSC order. References, sub-patterns and
+# tolerances are those of the H = 4 cases.
+
+H_WIDE = 17
+
+
+class Wide:
+    """The windows and sub-patterns of ``big`` with the mark of an H-wide edge array added."""
+
+    def __init__(self, g, H):
+        self.H, self.edge = H, (1 << 30) // H
+        assert self.edge < g.nnz and (1 << 30) < g.nnz * H <= (1 << 31) - 1 - 4096
+        col = int(torch.searchsorted(g.colptr.long(), torch.tensor([self.edge], device=DEV), right=True)) - 1
+        self.row_windows = [(s, min(s + band.WINDOW, g.M)) for s in band.window_starts(g.M, (g.wrap // g.d, self.edge // g.d))]
+        self.col_windows = [(s, min(s + band.WINDOW, g.K)) for s in band.window_starts(g.K, (col, self.edge // g.d))]
+        assert any(s0 * g.d <= self.edge < s1 * g.d for s0, s1 in self.row_windows)
+        self.subs = []
+        for s0, s1 in self.row_windows:
+            r0 = g.M - FLOAT_ROWS if s1 == g.M else (self.edge // g.d - FLOAT_ROWS // 2 if s0 <= self.edge // g.d < s1 and s0 > 0 else s0)
+            self.subs.append(Sub(g, r0, r0 + FLOAT_ROWS))
+        assert self.subs[0].r0 == 0 and self.subs[-1].e1 == g.nnz and any(s.e0 <= self.edge < s.e1 for s in self.subs)
+
+
+@pytest.fixture(scope="module")
+def wide(big):
+    return Wide(big, H_WIDE)
+
+
+@pytest.mark.parametrize("slope", (None, 0.2))
+def test_edge_softmax_past_2_30_words(big, wide, slope):
+    _edge_softmax_case(big, wide.subs, H_WIDE, slope)
+
+
+def test_gat_softmax_with_stats_past_2_30_words(big, wide):
+    _gat_softmax_case(big, wide.subs, H_WIDE)
+
+
+def test_edge_dropout_mask_past_2_30_words(big, wide):
+    _edge_dropout_case(big, wide.subs, H_WIDE)
+
+
+def test_edge_segment_sum_past_2_30_words(big, wide):
+    _edge_segment_sum_case(big, H_WIDE, wide.row_windows, wide.col_windows)
+
+
+def test_gatv2_score_past_2_30_words(big, wide):
+    _gatv2_case(big, wide.subs, H_WIDE, 2)
+
+
+@pytest.mark.parametrize("x16", (False, True), ids=("f32", "bf16"))
+def test_sddmm_heads_past_2_30_words(big, wide, x16):
+    _sddmm_heads_case(big, H_WIDE, 2, x16, wide.row_windows)
+
+
+def test_take_edges_64_byte_rows_past_2_30_words(big):
+    """H = 16: 64-byte rows, the widest the HIP gather serves, 2^30 + 16384 words."""
+    assert big.nnz * 16 == (1 << 30) + 16384
+    _take_edges_case(big, 16, torch.float32)

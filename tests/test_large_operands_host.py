@@ -1,0 +1,343 @@
+"""Host checks behind test_gpu_large_operands.py and the H = 17 cases of test_gpu_large_edges.py (no device).
+
+* Sizes: every case's (M, K) from tests/large_operands.py; "below" and "at" lie on the two sides of each route switch, as the
+  host-only route functions and the entries themselves (called with null pointers) answer; regime B is the largest size the
+  entries accept and one row more is refused.
+* Windows: the compared windows — and, for the float ops, the 512-row sub-patterns inside them — hold the rows with byte 2^31, byte
+  2^32 and the last word of every operand of every case.
+* Each comparison can fail: for every marked window the reference is recomputed with the gathered operand read through a byte
+  offset displaced by 2^32 and by 2^31 (modulo 2^32; at 1200-byte rows the alias lies inside another row, at another head and
+  feature) and the case's comparator must reject it — exact equality for the integer ops, the op's own tolerance for the float ops
+  (there the alias holds another draw of the random values). This is a requirement on the INPUTS: a value and its aliases differ.
+* The band at d = 8 against a numpy transpose."""
+import numpy as np
+import pytest
+import torch
+
+import band
+import large_operands as lo
+from test_large_edges_host import _numpy_transpose
+
+EINVAL, ERANGE = -1, -3
+D = lo.D
+CASES_A = [(H, F, elem, side, walk) for H, F in lo.WIDTHS for elem in (4, 2) for side in ("below", "at") for walk in ("rows", "cols")]
+CASES_B = [(H, F, regime) for H, F in lo.WIDTHS for regime in ("A", "B")]
+
+
+@pytest.fixture(scope="module")
+def L(pkg):
+    from gespmm_amd import _lib
+
+    return _lib
+
+
+# ---- sizes and routes ---------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("H,F,elem,side,walk", CASES_A)
+def test_below_and_at_lie_on_the_two_sides_of_the_switch(L, H, F, elem, side, walk):
+    N = H * F
+    M, K = lo.sizes_a(N, side, walk, elem)
+    assert K == M + lo.LAST == band.sizes(M, D)[1]
+    nnz, below = M * D, side == "below"
+    gathered = K if walk == "rows" else M
+    assert (gathered * N * elem < (1 << 32)) == below and ((gathered + 1) * N * elem >= (1 << 32)) and (gathered - 1) * N * elem < (1 << 32)
+    S, T = (M, K) if walk == "rows" else (K, M)  # segments, rows of the gathered operand
+    if elem == 2:
+        assert L.heads_x16_route(S, T, H, F, nnz)[0] == (1 if below else 0)
+        assert L.heads_route(S, T, H, F, nnz)[0] == 0 or not below or N * T * 4 < (1 << 32)
+        return
+    assert L.heads_route(S, T, H, F, nnz)[0] == (1 if below else 0)
+    assert L.gat_aggregate_route(M, K, H, F, nnz, transposed=walk == "cols")[0] == (1 if below else 0)
+    if walk == "rows":  # the max reducer: no composition
+        f, b = L.lib.gespmm_csr_spmm_max_arg_f32, L.lib.gespmm_csr_spmm_max_backward_f32
+        assert f(*[None] * 5, M, K, N, nnz, -1e4, None) == (EINVAL if below else ERANGE)
+        assert b(*[None] * 6, M, K, N, nnz, None) == (EINVAL if below else ERANGE)
+        assert L.max_arg_route(M, nnz, N) is not None
+
+
+def _entries(L, H, F, slope=0.2):
+    """name -> f(M, K): the return code of the entry on null pointers"""
+    lib = L.lib
+    return {
+        "gatv2_score": lambda m, k: lib.gespmm_gatv2_score_f32(*[None] * 6, m, k, H, F, m * D, slope, None),
+        "gatv2_backward_rows": lambda m, k: lib.gespmm_gatv2_score_backward_f32(*[None] * 9, m, k, H, F, m * D, slope, None),
+        "gatv2_backward_cols": lambda m, k: lib.gespmm_gatv2_score_backward_f32(*[None] * 9, k, m, H, F, m * D, slope, None),
+        "dot_attention": lambda m, k: lib.gespmm_dot_attention_f32(*[None] * 7, m, k, H, F, m * D, 0.5, None),
+        "dot_attention_backward_q": lambda m, k: lib.gespmm_dot_attention_backward_q_f32(*[None] * 10, m, k, H, F, m * D, 0.5, None),
+        "dot_attention_backward_kv": lambda m, k: lib.gespmm_dot_attention_backward_kv_f32(*[None] * 10, m, k, H, F, m * D, 0.5, None),
+        "gat_backward_el": lambda m, k: lib.gespmm_gat_backward_el_f32(*[None] * 9, m, k, H, F, m * D, slope, None),
+        "gat_backward_er": lambda m, k: lib.gespmm_gat_backward_er_f32(*[None] * 9, m, k, H, F, m * D, slope, None),
+    }
+
+
+@pytest.mark.parametrize("H,F,regime", CASES_B)
+def test_regimes_of_the_word_position_kernels(L, H, F, regime):
+    N = H * F
+    M, K = lo.sizes_b(N, regime)
+    assert K == M + lo.LAST and K * N > (1 << 30), "word 2^30 (byte 2^32) lies inside every K-side operand"
+    assert M * N > (1 << 30) and K * N <= lo.MAX_WORDS
+    if regime == "A":
+        assert abs(M * N - lo.REGIME_A_ROWS_512 * 512) < N and 5.3e9 < M * N * 4 < 5.5e9
+    for name, f in _entries(L, H, F).items():
+        assert f(M, K) == EINVAL, (name, "sizes accepted: on to the pointers")
+        if regime == "B":
+            assert f(M, K + 1) == ERANGE, (name, "one row more of the K-side operands")
+            assert f(K + 1 - lo.LAST, K + 1) == ERANGE, (name, "the band of one row more")
+    # the routes of the GPU cases: one kernel each (H = 3 takes the ordinary routes too)
+    nnz = M * D
+    assert L.describe_dot_attention(M, K, H, F, nnz) == {"V": 4, "W": 8 if F == 64 else 16}
+    assert L.describe_gatv2_score(M, nnz, H, F)["V"] == 4
+    for csr in (True, False):
+        for x16 in (False, True):
+            assert L.describe_sddmm_heads(csr, M, nnz, H, F, x16=x16)["route"] == "kernel"
+    if N == 512:
+        assert L.describe_sddmm(True, M, nnz, N)["form"] == "csr-edge"
+
+
+# ---- windows ------------------------------------------------------------------------------------------------------------------------
+
+def _check_marks(M, K, N, elem, float_ops):
+    rw, cw = lo.case_windows(M, K, N, elem)
+    assert rw[0][0] == 0 and rw[-1][1] == M and cw[0][0] == 0 and cw[-1][1] == K and len(rw) >= 14 and len(cw) >= 14
+    rb = N * elem
+    few = lo.case_windows(M, K, N, elem, spread=2)[0]  # the float ops: the marked windows, the first and the last
+    assert set(few) <= set(rw) and few[0][0] == 0 and few[-1][1] == M
+    subs = [lo.sub_rows(w, M) for w in few]
+    assert subs[0] == (0, lo.FLOAT_ROWS) and subs[-1] == (M - lo.FLOAT_ROWS, M)
+    for rows, side in ((M, "M"), (K, "K")):
+        marks = lo.marked(rows, N, elem)
+        assert marks[-1] == rows - 1
+        for b in lo.BYTES:
+            if b < rows * rb:
+                r = b // rb
+                assert r in marks and r * rb <= b < (r + 1) * rb
+                if rb == 1200:
+                    assert r * rb < b, "the byte falls inside the row, not on its boundary"
+        for m in marks:
+            # an M-side row is compared in the row windows (its own result words) and gathered by the columns m .. m + 22;
+            # a K-side row is compared in the column windows and gathered by the rows m - 22 .. m
+            assert lo.holds(cw, m) and lo.holds(rw, min(m, M - 1)), (side, m)
+            if float_ops:  # ... and the sub-pattern's rows r0 .. r1 hold it or gather it, and its complete columns hold it
+                hit = [(r0, r1) for r0, r1 in subs if r0 <= min(m, M - 1) < r1]
+                assert hit, (side, m)
+                r0, r1 = hit[0]
+                if side == "K" and m < K - 1:
+                    f0, f1 = (0 if r0 == 0 else r0 + lo.LAST), (K if r1 == M else r1)
+                    assert f0 <= m < f1, "a complete column of the sub-pattern"
+    return rw, cw
+
+
+@pytest.mark.parametrize("H,F,elem,side,walk", CASES_A)
+def test_windows_hold_the_marked_rows_section_a(H, F, elem, side, walk):
+    N = H * F
+    M, K = lo.sizes_a(N, side, walk, elem)
+    _check_marks(M, K, N, elem, False)
+    if side == "below":  # the row straddling byte 2^31 of the gathered operand, and its last rows
+        gathered = K if walk == "rows" else M
+        assert (1 << 31) // (N * elem) in lo.marked(gathered, N, elem) and gathered - 1 in lo.marked(gathered, N, elem)
+
+
+@pytest.mark.parametrize("H,F,regime", CASES_B)
+def test_windows_hold_the_marked_rows_section_b(H, F, regime):
+    N = H * F
+    M, K = lo.sizes_b(N, regime)
+    _check_marks(M, K, N, 4, True)
+    assert {(1 << 29) // N, (1 << 30) // N} <= set(lo.marked(M, N)) and {(1 << 29) // N, (1 << 30) // N} <= set(lo.marked(K, N))
+    _check_marks(M, K, N, 2, False)  # the bf16 SDDMM: byte 2^32 is word 2^31 of a 16-bit array
+
+
+def test_windows_of_the_h17_edge_arrays():
+    """test_gpu_large_edges.py at H = 17: the [nnz, 17] arrays lie between 2^30 and 2^31 words and the window of the added mark holds
+    edge floor(2^30 / 17); take_edges at H = 16 has 2^30 + 16384 words in 64-byte rows."""
+    M, d = (1 << 20) + 16, 64
+    nnz = M * d
+    assert (1 << 30) < nnz * 17 <= lo.MAX_WORDS and nnz * 16 == (1 << 30) + 16384
+    e = (1 << 30) // 17
+    starts = band.window_starts(M, (1024 // d, e // d))
+    assert any(s <= e // d < s + band.WINDOW for s in starts)
+    assert e * 17 <= (1 << 30) < (e + 1) * 17, "word 2^30 lies inside this edge's row of the array"
+
+
+# ---- each comparison can fail: the reference through a displaced byte offset ---------------------------------------------------------
+
+def _slices(M, K, N, elem, rows_of_operand, shift):
+    """32-row slices of the marked windows at and after the rows whose aliases lie inside the operand"""
+    rb = N * elem
+    out = []
+    for m in lo.marked(rows_of_operand, N, elem):
+        if m * rb >= shift or (m + 1) * rb > shift:
+            out.append(m)
+    return out
+
+
+def _gathered_rows(H, F, elem, side, walk):
+    M, K = lo.sizes_a(H * F, side, walk, elem)
+    return K if walk == "rows" else M
+
+
+# (a displacement of 2^32 bytes has an alias inside the operand only past the switch: the "at" cases)
+CASES_A_SHIFTED = [c + (shift,) for c in CASES_A for shift in lo.BYTES if _gathered_rows(*c) * c[0] * c[1] * c[2] > shift]
+
+
+@pytest.mark.parametrize("H,F,elem,side,walk,shift", CASES_A_SHIFTED)
+def test_integer_references_reject_a_displaced_gather_section_a(H, F, elem, side, walk, shift):
+    """The heads product (fp32 and x16 element sizes), the fused aggregation (the same sum with unit weights) and the max reducer."""
+    N = H * F
+    M, K = lo.sizes_a(N, side, walk, elem)
+    gathered = K if walk == "rows" else M
+    assert gathered * N * elem > shift
+    fn = lo.b_at(H, F) if walk == "rows" else lo.k_at(H, F)
+    wrong = lo.displaced(fn, H, F, shift, gathered, elem)
+    one = lambda e, h: 1  # noqa: E731
+    for m in _slices(M, K, N, elem, gathered, shift):
+        for weight_fn in (lo.w_nz, one):
+            if walk == "rows":  # rows m - 22 .. m gather row m of the K-side operand
+                r1 = min(m + 1, M)
+                r0 = max(r1 - 32, 0)
+                good = band.ref_csr_product(M, D, r0, r1, H, F, dense_fn=fn, weight_fn=weight_fn)
+                bad = band.ref_csr_product(M, D, r0, r1, H, F, dense_fn=wrong, weight_fn=weight_fn)
+            else:  # columns m .. m + 22 gather row m of the M-side operand
+                c0 = m
+                good = band.ref_csc_product(M, D, c0, c0 + 32, H, F, dense_fn=fn, weight_fn=weight_fn)
+                bad = band.ref_csc_product(M, D, c0, c0 + 32, H, F, dense_fn=wrong, weight_fn=weight_fn)
+            assert band.first_difference(good.to(torch.float32), bad.to(torch.float32)) is not None, (m, weight_fn)
+        if walk == "rows" and elem == 4:  # the max: the values, or the first position that reaches them
+            r1 = min(m + 1, M)
+            r = torch.arange(max(r1 - 32, 0), r1).view(-1, 1, 1, 1)
+            j = torch.arange(D).view(1, D, 1, 1)
+            hh, ff = band._hf(H, F, "cpu")
+            tops = []
+            for f_ in (fn, wrong):
+                vals = f_(r + band.offset_of(j), hh, ff)
+                top = vals.max(1, keepdim=True).values
+                tops.append((top, torch.where(vals == top, j, D).min(1).values))
+            assert not (torch.equal(tops[0][0], tops[1][0]) and torch.equal(tops[0][1], tops[1][1])), m
+
+
+@pytest.mark.parametrize("shift", lo.BYTES)
+@pytest.mark.parametrize("x16", (False, True))
+@pytest.mark.parametrize("H,F,regime", CASES_B + [(1, 512, "A"), (1, 512, "B")])
+def test_integer_references_reject_a_displaced_gather_sddmm(H, F, regime, x16, shift):
+    """The multi-head SDDMM and (H = 1, F = 512) the plain one: either operand read through the displaced offset."""
+    N, elem = H * F, 2 if x16 else 4
+    M, K = lo.sizes_b(N, regime)
+    for side in ("q", "k"):
+        rows = M if side == "q" else K
+        if rows * N * elem <= shift:
+            continue
+        fns = {"q_fn": lo.b_at(H, F), "k_fn": lo.k_at(H, F)}
+        wrong = lo.displaced(fns[side + "_fn"], H, F, shift, rows, elem)
+        for m in _slices(M, K, N, elem, rows, shift):
+            r1 = min(m + 1, M)
+            r0 = max(r1 - 32, 0)
+            good = band.ref_csr_scores(M, D, r0, r1, H, F, **fns)
+            bad = band.ref_csr_scores(M, D, r0, r1, H, F, **dict(fns, **{side + "_fn": wrong}))
+            assert band.first_difference(good.to(torch.float32), bad.to(torch.float32)) is not None, (side, m)
+
+
+def test_the_closed_forms_differ_at_their_aliases():
+    """What the rejections above rest on: lo.b_at and lo.k_at are functions of the word position modulo 7 and 5, and no displacement
+    by 2^31 or 2^32 bytes — 2^29, 2^30 words, 2^30, 2^31 16-bit elements — is a multiple of either: EVERY word differs from its alias,
+    at 2048-byte and at 1200-byte rows. band.b_of / band.k_of would do at 2048-byte rows (2^21 = 1, 2^20 = 4 mod 7; 3 2^21 = 1,
+    3 2^20 = 3 mod 5); at 1200-byte rows a linear form of (r, h, f) can keep its value over whole bands of aliases."""
+    assert [(1 << e) % 7 for e in (29, 30, 31)] == [4, 1, 2] and [(1 << e) % 5 for e in (29, 30, 31)] == [2, 4, 3]
+    assert (1 << 21) % 7 == 1 and (1 << 20) % 7 == 4 and (3 << 21) % 5 == 1 and (3 << 20) % 5 == 3
+    for H, F in lo.WIDTHS:
+        N = H * F
+        h, f = torch.arange(H).view(1, H, 1), torch.arange(F).view(1, 1, F)
+        for elem in (4, 2):
+            rows = lo.regime_rows(N, "B") * 4 // elem
+            r = torch.arange(rows - 64, rows).view(-1, 1, 1)
+            for fn in (lo.b_at(H, F), lo.k_at(H, F)):
+                for shift in lo.BYTES:
+                    assert bool((fn(r, h, f) != lo.displaced(fn, H, F, shift, rows, elem)(r, h, f)).all())
+
+
+# ---- the float ops: a gathered row that holds another draw must fall outside the op's own tolerance ----------------------------------
+
+def _float_case(H, F):
+    """A 512-row sub-pattern's shape at small size: the band at d = 8 on 64 rows, random operands, and the same operands with ONE
+    gathered row (K side: row 40; M side: row 30) holding another draw — what a displaced offset reads in an array of random values."""
+    from test_dot_attention_host import transpose
+
+    M = 64
+    rowptr, colind = (t.numpy() for t in band.csr(M, D))
+    K = M + lo.LAST
+    colptr, rowind, order = transpose(rowptr, colind, K)
+    rows = np.repeat(np.arange(M, dtype=np.int32), D)
+    P = {"M": M, "K": K, "nnz": M * D, "rowptr": rowptr, "colind": colind, "colptr": colptr, "rowind": rowind, "order": order, "rows": rows,
+         "degs": np.full(M, D)}
+    rng = np.random.RandomState(100 * H + F)
+    u = lambda shape, a, b: rng.uniform(a, b, size=shape).astype(np.float32)  # noqa: E731
+    x = {"xm": u((M, H, F), -1, 1), "xk": u((K, H, F), -1, 1), "vk": u((K, H, F), -1, 1), "go": u((M, H, F), 0.5, 1), "att": u((H, F), -2, 2),
+         "gs": u((M * D, H), -2, 2), "el": u((M, H), -2, 2), "er": u((K, H), -2, 2)}
+    other = {k: v.copy() for k, v in x.items()}
+    for name, row in (("xk", 40), ("vk", 40), ("xm", 30), ("go", 30)):
+        other[name][row] = u(x[name][row].shape, *((0.5, 1) if name == "go" else (-1, 1)))
+    return P, x, other
+
+
+@pytest.mark.parametrize("H,F", lo.WIDTHS)
+def test_float_comparators_reject_a_displaced_gather(H, F):
+    from attention_refs import bound_ratio, gat_backward_float64
+    from test_dot_attention_host import ratio, ref_backward, ref_forward
+    from test_gatv2_host import restate_backward, restate_score, worst_ratio
+
+    P, x, o = _float_case(H, F)
+    f32 = lambda a: np.asarray(a).astype(np.float32)  # noqa: E731  (the result a correct kernel returns: the reference, rounded)
+    slope = 0.2
+    # GATv2: the score and the row pass gather xr (K side), the column pass gathers xl (M side)
+    got = restate_score(P["rowptr"], P["colind"], x["xm"], x["xk"], x["att"], slope)
+    bad = restate_score(P["rowptr"], P["colind"], x["xm"], o["xk"], x["att"], slope)
+    assert worst_ratio(f32(got[0]), got[0], got[1], "score") <= 1.0 < worst_ratio(f32(got[0]), bad[0], bad[1], "score")
+    got = restate_backward(P["rowptr"], P["colind"], x["gs"], x["xm"], x["xk"], x["att"], slope)
+    bad = restate_backward(P["rowptr"], P["colind"], x["gs"], x["xm"], o["xk"], x["att"], slope)
+    for i, name in ((0, "grad_xl"), (1, "att_part")):
+        assert worst_ratio(f32(got[i]), got[i], got[i + 2], name) <= 1.0 < worst_ratio(f32(got[i]), bad[i], bad[i + 2], name)
+    got = restate_backward(P["colptr"], P["rowind"], x["gs"], x["xk"], x["xm"], x["att"], slope, order=P["order"])
+    bad = restate_backward(P["colptr"], P["rowind"], x["gs"], x["xk"], o["xm"], x["att"], slope, order=P["order"])
+    assert worst_ratio(f32(got[0]), got[0], got[2], "grad_xr") <= 1.0 < worst_ratio(f32(got[0]), bad[0], bad[2], "grad_xr")
+    # dot attention: forward and row pass gather k and v, the column pass gathers q and grad_out
+    scale = float(np.float32(1.0 / np.sqrt(F)))
+    xs = {"q": x["xm"], "k": x["xk"], "v": x["vk"], "go": x["go"], "scale": scale}
+    f = ref_forward(P, xs)
+    stats, out = f32(np.stack([f["m"], f["l"]], -1)), f32(f["out"])
+    b = ref_backward(P, xs, stats, out)
+    delta = f32(b["delta"])
+    for name, other in (("k", o["xk"]), ("v", o["vk"]), ("q", o["xm"]), ("go", o["go"])):
+        xo = dict(xs, **{name: other})
+        fo = ref_forward(P, xo)
+        bo = ref_backward(P, xo, stats, out, delta)
+        r = {"out": ratio(out, fo["out"], fo["tol_out"]), "grad_q": ratio(f32(b["grad_q"]), bo["grad_q"], bo["tol_grad_q"]),
+             "grad_k": ratio(f32(b["grad_k"]), bo["grad_k"], bo["tol_grad_k"]), "grad_v": ratio(f32(b["grad_v"]), bo["grad_v"], bo["tol_grad_v"])}
+        seen = {"k": ("out", "grad_q"), "v": ("out", "grad_q"), "q": ("grad_k",), "go": ("grad_k", "grad_v")}[name]
+        assert all(r[s] > 1.0 for s in seen), (name, r)
+    r = {"out": ratio(out, f["out"], f["tol_out"]), "grad_q": ratio(f32(b["grad_q"]), b["grad_q"], b["tol_grad_q"]),
+         "grad_k": ratio(f32(b["grad_k"]), b["grad_k"], b["tol_grad_k"]), "grad_v": ratio(f32(b["grad_v"]), b["grad_v"], b["tol_grad_v"])}
+    assert max(r.values()) <= 1.0, r
+    # the fused GAT backward: grad_el gathers feat (K side); grad_er gathers grad_out (M side)
+    for p_keep in (None, 0.25):
+        keep = ks = None
+        if p_keep:
+            keep, ks = np.random.RandomState(5).uniform(size=(P["nnz"], H)) >= p_keep, np.float32(1.0) / (np.float32(1.0) - np.float32(p_keep))
+        args = (P["rows"], P["colind"], P["M"], P["K"], x["el"], x["er"])
+        gel, ger, sel, ser = gat_backward_float64(*args, x["go"], x["vk"], slope, keep, ks)
+        assert bound_ratio(f32(gel), gel, sel)[1] and bound_ratio(f32(ger), ger, ser)[1]
+        bel, _, bsel, _ = gat_backward_float64(*args, x["go"], o["vk"], slope, keep, ks)
+        _, ber, _, bser = gat_backward_float64(*args, o["go"], x["vk"], slope, keep, ks)
+        assert not bound_ratio(f32(gel), bel, bsel)[1] and not bound_ratio(f32(ger), ber, bser)[1]
+
+
+# ---- the band at d = 8 ----------------------------------------------------------------------------------------------------------------
+
+def test_band_at_d8_equals_a_numpy_transpose():
+    M = 1000
+    nnz, K = band.sizes(M, D)
+    assert K == M + 22 and [band.offset_of(j) for j in range(D)] == [0, 4, 7, 9, 13, 16, 18, 22]
+    rowptr, colind, rows, colptr_np, rowind_np, order_np = _numpy_transpose(M, D)
+    assert nnz == colind.size and K == colind.max() + 1
+    colptr, rowind, order = band.csc(M, D)
+    assert np.array_equal(colptr.numpy(), colptr_np) and np.array_equal(rowind.numpy(), rowind_np) and np.array_equal(order.numpy(), order_np)
+    band.verify_csc(M, D, colptr, order)
+    # the products of the GPU cases stay exact: |sum| <= 8 * 2 * 3 (heads with w_nz: 8 * 3 * 3, also in bf16 / fp16: integers below 2^8) and 512 * 3 * 2 (SDDMM)
+    assert D * 3 * 3 < (1 << 8) and 512 * 3 * 2 < (1 << 24)
