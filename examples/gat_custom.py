@@ -14,6 +14,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
     python examples/gat_custom.py --seed 0 --fused-aggregate       # seeded parameters and dropout: the losses of --seed 0 --fused-score
     python examples/gat_custom.py --v2                             # two ``GATv2Conv`` layers (Brody et al.): the non-linearity inside the
                                                                    # score's sum, one kernel, nothing of size nnz x H x F
+    python examples/gat_custom.py --v2 --fused-attention           # ``GATv2Conv(fused=True)``: score, softmax, dropout and aggregation in
+                                                                   # one kernel, the backward in two: no [nnz, H] array in a step
     python examples/gat_custom.py --dtype bf16                     # a .bfloat16() model on bf16 features (or fp16): the aggregation is the
                                                                    # 16-bit multi-head product, everything edge-sized stays fp32
 
@@ -50,13 +52,15 @@ def gat_graph(edge_index, n_v, device, int32_order=False):
 
 class Net(torch.nn.Module):
     def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused_score=False, fused_aggregate=False, fused_backward=False,
-                 attn_dropout=0.0, v2=False):
+                 attn_dropout=0.0, v2=False, fused_attention=False):
         super().__init__()
+        if fused_attention and not v2:
+            raise ValueError("fused_attention is GATv2Conv(fused=True): it needs v2=True")
         if v2:
             if fused_score or fused_aggregate or fused_backward:
-                raise ValueError("the fused paths are GATConv's: GATv2Conv has none")
-            self.conv1 = GATv2Conv(n_in, n_hidden, heads=heads, concat=True, dropout=attn_dropout)
-            self.conv2 = GATv2Conv(n_hidden * heads, n_out, heads=1, concat=False, dropout=attn_dropout)
+                raise ValueError("fused_score, fused_aggregate and fused_backward are GATConv's: GATv2Conv has fused_attention")
+            self.conv1 = GATv2Conv(n_in, n_hidden, heads=heads, concat=True, dropout=attn_dropout, fused=fused_attention)
+            self.conv2 = GATv2Conv(n_hidden * heads, n_out, heads=1, concat=False, dropout=attn_dropout, fused=fused_attention)
         else:
             fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward, dropout=attn_dropout)
             self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, **fused)
@@ -88,7 +92,10 @@ def main():
                     help="GATConv(fused_backward=True): the fused aggregation, and its backward for the attention terms in two "
                          "launches with no [nnz, H] array")
     ap.add_argument("--v2", action="store_true",
-                    help="GATv2Conv in both layers (the score's non-linearity inside its sum); not together with the --fused-* flags")
+                    help="GATv2Conv in both layers (the score's non-linearity inside its sum); not together with --fused-score, "
+                         "--fused-aggregate or --fused-backward")
+    ap.add_argument("--fused-attention", action="store_true",
+                    help="with --v2: GATv2Conv(fused=True), the whole attention in one kernel and its backward in two, no [nnz, H] array")
     ap.add_argument("--seed", type=int, default=None,
                     help="torch.manual_seed before the model is made (parameters and dropout masks): two runs, or two fused settings, "
                          "then print the same losses")
@@ -100,7 +107,9 @@ def main():
         ap.error("--dtype %s: --fused-aggregate, --fused-backward and --v2 run fp32-only kernels; use the default path or --fused-score"
                  % args.dtype)
     if args.v2 and (args.fused_score or args.fused_aggregate or args.fused_backward):
-        ap.error("--v2 has no fused path: --fused-score, --fused-aggregate and --fused-backward are GATConv's")
+        ap.error("--fused-score, --fused-aggregate and --fused-backward are GATConv's: --v2 has --fused-attention")
+    if args.fused_attention and not args.v2:
+        ap.error("--fused-attention is GATv2Conv(fused=True): it needs --v2")
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device (the ops have no CPU path)")
     device = torch.device("cuda")
@@ -122,7 +131,8 @@ def main():
     if args.seed is not None:
         torch.manual_seed(args.seed)
     model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused_score=args.fused_score,
-                fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward, attn_dropout=args.attn_dropout, v2=args.v2).to(device)
+                fused_aggregate=args.fused_aggregate, fused_backward=args.fused_backward, attn_dropout=args.attn_dropout, v2=args.v2,
+                fused_attention=args.fused_attention).to(device)
     if args.dtype != "fp32":
         dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
         model = model.to(dtype)
@@ -189,7 +199,7 @@ def main():
     wall = time.perf_counter() - t0
     print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused_score=%s fused_aggregate=%s fused_backward=%s%s" %
           (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused_score, args.fused_aggregate,
-           args.fused_backward, (" attn_dropout=%g" % args.attn_dropout if args.attn_dropout else "") + (" v2=True" if args.v2 else "") +
+           args.fused_backward, (" attn_dropout=%g" % args.attn_dropout if args.attn_dropout else "") + (" v2=True" if args.v2 else "") + (" fused_attention=True" if args.fused_attention else "") +
            (" dtype=%s" % args.dtype if args.dtype != "fp32" else "")))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))

@@ -139,6 +139,13 @@ EXPORTS = [
     "gespmm_dot_attention_backward_kv_f32",
     "gespmm_dot_attention_backward_kv_dropout_f32",
     "gespmm_describe_dot_attention",
+    "gespmm_gatv2_attention_f32",
+    "gespmm_gatv2_attention_dropout_f32",
+    "gespmm_gatv2_attention_backward_row_f32",
+    "gespmm_gatv2_attention_backward_row_dropout_f32",
+    "gespmm_gatv2_attention_backward_col_f32",
+    "gespmm_gatv2_attention_backward_col_dropout_f32",
+    "gespmm_describe_gatv2_attention",
     "gespmm_csr_spmm_max_arg_f32",
     "gespmm_csr_spmm_max_backward_f32",
     "gespmm_max_arg_route",
@@ -389,6 +396,20 @@ def _load():
         f.argtypes = [p] * 10 + [c_int64] * 5 + [c_float, c_float, p, p]
     lib.gespmm_describe_dot_attention.restype = c_int
     lib.gespmm_describe_dot_attention.argtypes = [c_int64] * 5 + [c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_gatv2_attention_f32.restype = c_int
+    lib.gespmm_gatv2_attention_f32.argtypes = [p] * 7 + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_attention_dropout_f32.restype = c_int
+    lib.gespmm_gatv2_attention_dropout_f32.argtypes = [p] * 7 + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_gatv2_attention_backward_row_f32.restype = c_int
+    lib.gespmm_gatv2_attention_backward_row_f32.argtypes = [p] * 11 + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_attention_backward_row_dropout_f32.restype = c_int
+    lib.gespmm_gatv2_attention_backward_row_dropout_f32.argtypes = [p] * 11 + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_gatv2_attention_backward_col_f32.restype = c_int
+    lib.gespmm_gatv2_attention_backward_col_f32.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_attention_backward_col_dropout_f32.restype = c_int
+    lib.gespmm_gatv2_attention_backward_col_dropout_f32.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_describe_gatv2_attention.restype = c_int
+    lib.gespmm_describe_gatv2_attention.argtypes = [c_int64] * 5 + [c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_csr_spmm_max_arg_f32.restype = c_int
     lib.gespmm_csr_spmm_max_arg_f32.argtypes = [p] * 5 + [c_int64] * 4 + [c_float, p]
     lib.gespmm_csr_spmm_max_backward_f32.restype = c_int
@@ -530,6 +551,23 @@ def describe_dot_attention(M, K, H, F, nnz, q_align=16, k_align=16, v_align=16):
         raise GespmmError(n, "gespmm_describe_dot_attention")
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
+
+
+GATV2_ATTENTION_MAX_F = 512
+
+
+def describe_gatv2_attention(M, K, H, F, nnz, xl_align=16, xr_align=16, att_align=16):
+    """The lane geometry of gespmm_gatv2_attention_f32 and its two backward passes for these sizes and operand alignments
+    (gespmm_describe_gatv2_attention: host only) — a dict ``{"V": floats per load, "W": lanes per (segment, head) pair, "supported":
+    True}``; ``{"route": "unsupported", "supported": False}`` when F > 512 (no kernel), ``{"route": "zeros", ...}`` when F == 0 and
+    ``{"form": "none", ...}`` when nnz == 0. V and W fix the score's summation order; the least aligned dense operand of a launch —
+    the dense results included: pass their alignment with ``xl_align`` — decides V."""
+    buf = ctypes.create_string_buffer(96)
+    n = lib.gespmm_describe_gatv2_attention(int(M), int(K), int(H), int(F), int(nnz), int(xl_align), int(xr_align), int(att_align), buf, 96)
+    if n < 0:
+        raise GespmmError(n, "gespmm_describe_gatv2_attention")
+    out = dict(kv.split("=") for kv in buf.value.decode().split())
+    return {k: (v if k in ("form", "route") else bool(int(v)) if k == "supported" else int(v)) for k, v in out.items()}
 
 
 def heads_route(M, K, H, F, nnz, b_align=16, c_align=16):

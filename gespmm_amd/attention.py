@@ -16,12 +16,28 @@ entry p of row r with column c and head h
 ``grad_v``; no ``csc_order``), both recomputing ``s_p`` and ``a_p`` with the same bits. ``dropout=(p, seed)`` puts ``softmax.edge_dropout``'s
 mask on ``a_p``: the decision of an entry is a function of ``(seed, row, column, head)``, recomputed wherever it is needed. Lane geometry
 and summation orders: include/gespmm.h and ``_lib.describe_dot_attention``. A head slice wider than 512 floats has no kernel: the calls
-raise a ``GespmmError`` that says so. fp32 only: other dtypes raise TypeError. All calls go through ctypes."""
+raise a ``GespmmError`` that says so. fp32 only: other dtypes raise TypeError. All calls go through ctypes.
+
+Fused GATv2 attention (Brody et al.) — score, softmax and aggregation in one sweep, the same contract otherwise:
+
+    gatv2_attention(rowptr, colind, xl, xr, att, negative_slope=None, dropout=None, out=None, stats=None)        -> (out f32[M, H, F], stats f32[M, H, 2])
+    gatv2_attention_backward_row(rowptr, colind, xl, xr, att, stats, out, grad_out, negative_slope=None, dropout=None,
+                                 want_att_part=True, results=None)                                               -> (delta, grad_xl[, att_part])
+    gatv2_attention_backward_col(colptr, rowind, xl, xr, att, stats, delta, grad_out, negative_slope=None, dropout=None,
+                                 result=None)                                                                    -> grad_xr f32[K, H, F]
+
+``xl`` f32[M, H, F] is the aggregating node's term, ``xr`` f32[K, H, F] the neighbour's — the score's operand AND the aggregated value, so
+one gathered row per entry serves the forward — ``att`` f32[H, F]:
+
+    s_p = sum_f att[h, f] leaky_relu(xl[r, h, f] + xr[c, h, f])      a_p = exp(s_p - m) / l      out[r, h, :] = sum_p a_p xr[c, h, :]
+
+``s_p`` has the bits of ``sddmm.gatv2_score`` on equally aligned operands (``_lib.describe_gatv2_attention``). ``negative_slope=None``: no
+leaky ReLU. F <= 512, fp32 only."""
 import math
 
 import torch
 
-from ._lib import DOT_ATTENTION_MAX_F, ERR_UNSUPPORTED, GespmmError, check, lib
+from ._lib import DOT_ATTENTION_MAX_F, ERR_UNSUPPORTED, GATV2_ATTENTION_MAX_F, GespmmError, check, lib
 from .softmax import _dropout, _dropout_typed
 from .spmm import _on_device, _ptr, _stream
 
@@ -226,3 +242,175 @@ def dot_attention_backward_kv(colptr, rowind, q, k, v, stats, delta, grad_out, s
             rc = lib.gespmm_dot_attention_backward_kv_f32(*args, _stream(dev))
     check(rc, "gespmm_dot_attention_backward_kv_dropout_f32" if dropout is not None else "gespmm_dot_attention_backward_kv_f32")
     return grad_k, grad_v
+
+
+# ---- fused GATv2 attention
+
+class Gatv2AttentionUnsupported(GespmmError):
+    """F > 512: no kernel serves the shape and nothing was launched."""
+
+    def __init__(self, F, where):
+        RuntimeError.__init__(self, "%s: a head slice of F = %d floats has no kernel; the fused GATv2 attention (gatv2_attention) "
+                                    "serves F <= %d (code %d)" % (where, F, GATV2_ATTENTION_MAX_F, ERR_UNSUPPORTED))
+        self.code = ERR_UNSUPPORTED
+
+
+def _slope(negative_slope):
+    if negative_slope is None:
+        return 1.0
+    if isinstance(negative_slope, torch.Tensor) or not isinstance(negative_slope, (int, float)):
+        raise TypeError("negative_slope must be a Python number or None")
+    s = float(negative_slope)
+    if s != s or s in (float("inf"), float("-inf")):
+        raise ValueError("negative_slope must be finite, got %r" % (negative_slope,))
+    return s
+
+
+def _gatv2_shapes(ptr, ptr_name, ind, ind_name, xl, xr, att, segments_are_rows):
+    """(M, K, H, F, nnz) of a call whose segments are the rows of xl (forward, row pass) or of xr (column pass)."""
+    if xl.dim() != 3 or xr.dim() != 3 or xl.shape[1] < 1:
+        raise ValueError("xl and xr must be [rows, H, F] with at least one head")
+    M, H, F = xl.shape
+    K = xr.shape[0]
+    if tuple(xr.shape[1:]) != (H, F) or tuple(att.shape) != (H, F):
+        raise ValueError("xl %s, xr %s and att %s must have the same heads and columns: att is [H, F]" %
+                         (tuple(xl.shape), tuple(xr.shape), tuple(att.shape)))
+    S = M if segments_are_rows else K
+    if ptr.dim() != 1 or ptr.numel() != S + 1:
+        raise ValueError("%s must be a vector of %d + 1 entries" % (ptr_name, S))
+    if ind.dim() != 1:
+        raise ValueError("%s must be a vector" % ind_name)
+    return M, K, H, F, ind.numel()
+
+
+def _gatv2_served(F, where):
+    if F > GATV2_ATTENTION_MAX_F:
+        raise Gatv2AttentionUnsupported(F, where)
+
+
+def gatv2_attention(rowptr, colind, xl, xr, att, negative_slope=None, dropout=None, out=None, stats=None):
+    """``out[r, h, :] = sum_p softmax_row(sum_f att[h, f] leaky_relu(xl[r, h, f] + xr[c_p, h, f]))_p xr[c_p, h, :]`` over the entries of CSR
+    row r, H heads in ONE launch (gespmm_gatv2_attention_f32): no score, no alpha, nothing of size nnz, one gathered row per entry.
+    Returns ``(out, stats)``; ``stats[r, h] = (m, l)`` is what the backward needs. Every word is written, an empty row +0.
+    ``dropout=(p, seed)``: dropout on the coefficients after the normalisation (gespmm_gatv2_attention_dropout_f32). ``out`` / ``stats``:
+    tensors to write into. ``colind`` within [0, K) and ``rowptr[M] == nnz`` are preconditions."""
+    _typed((("rowptr", rowptr), ("colind", colind)), (("xl", xl), ("xr", xr), ("att", att), ("out", out), ("stats", stats)))
+    _required((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _gatv2_shapes(rowptr, "rowptr", colind, "colind", xl, xr, att, True)
+    slope = _slope(negative_slope)
+    _shaped(out, "out", (M, H, F))
+    _shaped(stats, "stats", (M, H, 2))
+    dev = xl.device
+    _placed((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("out", out), ("stats", stats)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _gatv2_served(F, "gespmm_gatv2_attention_f32")
+    if out is None:
+        out = torch.empty((M, H, F), dtype=torch.float32, device=dev)
+    if stats is None:
+        stats = torch.empty((M, H, 2), dtype=torch.float32, device=dev)
+    if M == 0:  # (results of no words have no address to hand over)
+        return out, stats
+    args = (_ptr(rowptr), _ptr(colind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(out), _ptr(stats), M, K, H, F, nnz, slope)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_gatv2_attention_dropout_f32(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_gatv2_attention_f32(*args, _stream(dev))
+    check(rc, "gespmm_gatv2_attention_dropout_f32" if dropout is not None else "gespmm_gatv2_attention_f32")
+    return out, stats
+
+
+def gatv2_attention_backward_row(rowptr, colind, xl, xr, att, stats, out, grad_out, negative_slope=None, dropout=None, want_att_part=True,
+                                 results=None):
+    """The row pass of ``gatv2_attention``'s backward (gespmm_gatv2_attention_backward_row_f32): ``delta[r, h] = <grad_out[r, h], out[r, h]>``,
+    ``grad_xl[r, h, f] = sum_p ds_p (t_pf >= 0 ? att[h, f] : att[h, f] negative_slope)`` and, with ``want_att_part``, ``att_part[r, h, f] =
+    sum_p ds_p leaky_relu(t_pf)`` — ``att_part.sum(0)`` is the gradient of ``att`` — where ``ds_p = a_p (<grad_out[r, h], xr[c_p, h]> -
+    delta[r, h])``. ``stats`` and ``out`` are the forward's results; ``dropout`` the forward's pair. Returns ``(delta, grad_xl, att_part)``,
+    or ``(delta, grad_xl)`` with ``want_att_part=False`` (nothing of att_part's size is then written); every word is written.
+    ``results``: a tuple of tensors of that form to write into."""
+    want = bool(want_att_part)
+    n_res = 3 if want else 2
+    if results is None:
+        res = (None,) * n_res
+    elif not isinstance(results, (tuple, list)) or len(results) != n_res or any(t is None for t in results):
+        raise TypeError("results must be a tuple of %d tensors" % n_res)
+    else:
+        res = tuple(results)
+    delta, grad_xl = res[0], res[1]
+    att_part = res[2] if want else None
+    _typed((("rowptr", rowptr), ("colind", colind)),
+           (("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("out", out), ("grad_out", grad_out), ("results[0]", delta),
+            ("results[1]", grad_xl), ("results[2]", att_part)))
+    _required((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("out", out),
+               ("grad_out", grad_out)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _gatv2_shapes(rowptr, "rowptr", colind, "colind", xl, xr, att, True)
+    slope = _slope(negative_slope)
+    _shaped(stats, "stats", (M, H, 2))
+    _shaped(out, "out", (M, H, F))
+    _shaped(grad_out, "grad_out", (M, H, F))
+    _shaped(delta, "results[0]", (M, H))
+    _shaped(grad_xl, "results[1]", (M, H, F))
+    _shaped(att_part, "results[2]", (M, H, F))
+    dev = xl.device
+    _placed((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("out", out),
+             ("grad_out", grad_out), ("results[0]", delta), ("results[1]", grad_xl), ("results[2]", att_part)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _gatv2_served(F, "gespmm_gatv2_attention_backward_row_f32")
+    if delta is None:
+        delta = torch.empty((M, H), dtype=torch.float32, device=dev)
+        grad_xl = torch.empty((M, H, F), dtype=torch.float32, device=dev)
+        if want:
+            att_part = torch.empty((M, H, F), dtype=torch.float32, device=dev)
+    ret = (delta, grad_xl, att_part) if want else (delta, grad_xl)
+    if M == 0:
+        return ret
+    args = (_ptr(rowptr), _ptr(colind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(stats), _ptr(out), _ptr(grad_out), _ptr(delta), _ptr(grad_xl),
+            _ptr(att_part) if want else None, M, K, H, F, nnz, slope)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_gatv2_attention_backward_row_dropout_f32(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_gatv2_attention_backward_row_f32(*args, _stream(dev))
+    check(rc, "gespmm_gatv2_attention_backward_row_dropout_f32" if dropout is not None else "gespmm_gatv2_attention_backward_row_f32")
+    return ret
+
+
+def gatv2_attention_backward_col(colptr, rowind, xl, xr, att, stats, delta, grad_out, negative_slope=None, dropout=None, result=None):
+    """The column pass of ``gatv2_attention``'s backward (gespmm_gatv2_attention_backward_col_f32) on the CSC arrays of the pattern
+    (``graphs.transpose_csr``; no ``csc_order``): ``grad_xr[c, h, f] = sum over column c of ds_p (t_pf >= 0 ? att[h, f] : att[h, f]
+    negative_slope) + sum over column c of a_p grad_out[r_p, h, f]`` — the score's term and the aggregation's, two chains added once —
+    with ``ds_p`` and ``a_p`` the bits of the row pass. ``delta`` is the row pass's. Returns ``grad_xr``; every word is written, an
+    empty column +0. ``result``: a tensor to write into."""
+    _typed((("colptr", colptr), ("rowind", rowind)),
+           (("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("delta", delta), ("grad_out", grad_out), ("result", result)))
+    _required((("colptr", colptr), ("rowind", rowind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("delta", delta),
+               ("grad_out", grad_out)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _gatv2_shapes(colptr, "colptr", rowind, "rowind", xl, xr, att, False)
+    slope = _slope(negative_slope)
+    _shaped(stats, "stats", (M, H, 2))
+    _shaped(delta, "delta", (M, H))
+    _shaped(grad_out, "grad_out", (M, H, F))
+    _shaped(result, "result", (K, H, F))
+    dev = xl.device
+    _placed((("colptr", colptr), ("rowind", rowind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("delta", delta),
+             ("grad_out", grad_out), ("result", result)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _gatv2_served(F, "gespmm_gatv2_attention_backward_col_f32")
+    grad_xr = result if result is not None else torch.empty((K, H, F), dtype=torch.float32, device=dev)
+    if K == 0:
+        return grad_xr
+    args = (_ptr(colptr), _ptr(rowind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(stats), _ptr(delta), _ptr(grad_out), _ptr(grad_xr), M, K, H, F,
+            nnz, slope)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_gatv2_attention_backward_col_dropout_f32(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_gatv2_attention_backward_col_f32(*args, _stream(dev))
+    check(rc, "gespmm_gatv2_attention_backward_col_dropout_f32" if dropout is not None else "gespmm_gatv2_attention_backward_col_f32")
+    return grad_xr

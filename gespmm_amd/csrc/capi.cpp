@@ -27,6 +27,7 @@
 #include "gat_aggregate.h"
 #include "gat_backward.h"
 #include "dot_attention.h"
+#include "gatv2_attention.h"
 #include "gatv2_score.h"
 #include "plan.h"
 #include "sddmm_heads.h"
@@ -535,6 +536,16 @@ int check_dot_attention_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_
     if (rc != 0) return rc;
     if (const int rcs = check_dense_words(M * H, 2)) return rcs;  // (M H <= kSddmmMaxNnz: no overflow)
     return F > kDotAttentionMaxF ? GESPMM_ERR_UNSUPPORTED : 0;
+}
+
+// ---- the fused GATv2 attention (gespmm.h: gespmm_gatv2_attention_f32 and its backward; gatv2_attention.h): the same ladder with the
+// slope in the scale's place.
+int check_gatv2_attention_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, const float* p) {
+    int rc = check_gatv2_sizes(M, K, H, F, nnz, slope);
+    if (p) rc = check_dropout_p(rc, *p);
+    if (rc != 0) return rc;
+    if (const int rcs = check_dense_words(M * H, 2)) return rcs;  // (M H <= kSddmmMaxNnz: no overflow)
+    return F > kGatv2AttentionMaxF ? GESPMM_ERR_UNSUPPORTED : 0;
 }
 
 int least_alignment(std::initializer_list<const void*> ps) {
@@ -1665,6 +1676,136 @@ int gespmm_describe_dot_attention(int64_t M, int64_t K, int64_t H, int64_t F, in
         const gespmm::DotAttentionLaunch r =
             gespmm::resolve_dot_attention(F, q_align > 16 ? 16 : q_align, k_align > 16 ? 16 : k_align, v_align > 16 ? 16 : v_align);
         n = snprintf(out, (size_t)capacity, "V=%d W=%d", r.V, r.W);
+    }
+    return describe_result(n, capacity);
+}
+
+/* Fused GATv2 attention over a pattern and its backward (gespmm.h; gatv2_attention.h): one kernel each, nothing of size nnz but the
+   index arrays. The ladder is check_gatv2_attention_sizes, nnz == 0, F == 0, then the pointers — that of the dot-product attention. */
+static int gatv2_attention_entry(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att, float* out,
+                                 float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, const float* p,
+                                 const void* seed, void* stream) {
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, slope, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {  // every row is empty (F == 0: there is nothing to attend with): every word of the results is still written
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill({{out, (size_t)(M * H * F)}, {stats, (size_t)(M * H * 2)}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {xl, 4, true}, {xr, 4, true}, {att, 4, true}, {out, 4, true},
+                                        {stats, 8, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({xl, xr, att, out});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gatv2_attention(rowptr, colind, xl, xr, att, out, stats, M, K, H, F, nnz, slope,
+                                               gespmm::resolve_gatv2_attention(F, a, a, a), p ? &dropout : nullptr, st);
+}
+
+int gespmm_gatv2_attention_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att, float* out,
+                               float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    return gatv2_attention_entry(rowptr, colind, xl, xr, att, out, stats, M, K, H, F, nnz, slope, nullptr, nullptr, stream);
+}
+
+int gespmm_gatv2_attention_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att,
+                                       float* out, float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                       float p, const void* seed, void* stream) {
+    return gatv2_attention_entry(rowptr, colind, xl, xr, att, out, stats, M, K, H, F, nnz, slope, &p, seed, stream);
+}
+
+static int gatv2_attention_backward_row_entry(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr,
+                                              const float* att, const float* stats, const float* out, const float* grad_out, float* delta,
+                                              float* grad_xl, float* att_part, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                              float slope, const float* p, const void* seed, void* stream) {
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, slope, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill({{delta, (size_t)(M * H)}, {grad_xl, (size_t)(M * H * F)}, {att_part, att_part ? (size_t)(M * H * F) : 0}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {xl, 4, true}, {xr, 4, true}, {att, 4, true}, {stats, 8, true},
+                                        {out, 4, true}, {grad_out, 4, true}, {delta, 4, true}, {grad_xl, 4, true}, {att_part, 4, false},
+                                        {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({xl, xr, att, out, grad_out, grad_xl, att_part});  // (a null att_part counts as aligned)
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gatv2_attention_backward_row(rowptr, colind, xl, xr, att, stats, out, grad_out, delta, grad_xl, att_part, M, K,
+                                                            H, F, nnz, slope, gespmm::resolve_gatv2_attention(F, a, a, a),
+                                                            p ? &dropout : nullptr, st);
+}
+
+int gespmm_gatv2_attention_backward_row_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att,
+                                            const float* stats, const float* out, const float* grad_out, float* delta, float* grad_xl,
+                                            float* att_part, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                            void* stream) {
+    return gatv2_attention_backward_row_entry(rowptr, colind, xl, xr, att, stats, out, grad_out, delta, grad_xl, att_part, M, K, H, F, nnz,
+                                              slope, nullptr, nullptr, stream);
+}
+
+int gespmm_gatv2_attention_backward_row_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr,
+                                                    const float* att, const float* stats, const float* out, const float* grad_out,
+                                                    float* delta, float* grad_xl, float* att_part, int64_t M, int64_t K, int64_t H,
+                                                    int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream) {
+    return gatv2_attention_backward_row_entry(rowptr, colind, xl, xr, att, stats, out, grad_out, delta, grad_xl, att_part, M, K, H, F, nnz,
+                                              slope, &p, seed, stream);
+}
+
+static int gatv2_attention_backward_col_entry(const int32_t* colptr, const int32_t* rowind, const float* xl, const float* xr,
+                                              const float* att, const float* stats, const float* delta, const float* grad_out,
+                                              float* grad_xr, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                              const float* p, const void* seed, void* stream) {
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, slope, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill({{grad_xr, (size_t)(K * H * F)}}, st);
+    }
+    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {xl, 4, true}, {xr, 4, true}, {att, 4, true}, {stats, 8, true},
+                                        {delta, 4, true}, {grad_out, 4, true}, {grad_xr, 4, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({xl, xr, att, grad_out, grad_xr});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gatv2_attention_backward_col(colptr, rowind, xl, xr, att, stats, delta, grad_out, grad_xr, M, K, H, F, nnz,
+                                                            slope, gespmm::resolve_gatv2_attention(F, a, a, a), p ? &dropout : nullptr, st);
+}
+
+int gespmm_gatv2_attention_backward_col_f32(const int32_t* colptr, const int32_t* rowind, const float* xl, const float* xr, const float* att,
+                                            const float* stats, const float* delta, const float* grad_out, float* grad_xr, int64_t M,
+                                            int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    return gatv2_attention_backward_col_entry(colptr, rowind, xl, xr, att, stats, delta, grad_out, grad_xr, M, K, H, F, nnz, slope, nullptr,
+                                              nullptr, stream);
+}
+
+int gespmm_gatv2_attention_backward_col_dropout_f32(const int32_t* colptr, const int32_t* rowind, const float* xl, const float* xr,
+                                                    const float* att, const float* stats, const float* delta, const float* grad_out,
+                                                    float* grad_xr, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                                    float p, const void* seed, void* stream) {
+    return gatv2_attention_backward_col_entry(colptr, rowind, xl, xr, att, stats, delta, grad_out, grad_xr, M, K, H, F, nnz, slope, &p, seed,
+                                              stream);
+}
+
+int gespmm_describe_gatv2_attention(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int xl_align, int xr_align, int att_align,
+                                    char* out, int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    for (const int a : {xl_align, xr_align, att_align})
+        if (a < 4 || (a & (a - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, 1.0f, nullptr);
+    if (rc != 0 && rc != GESPMM_ERR_UNSUPPORTED) return rc;
+    int n;
+    if (rc == GESPMM_ERR_UNSUPPORTED) {
+        n = snprintf(out, (size_t)capacity, "route=unsupported supported=0");
+    } else if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none supported=1");
+    } else if (F == 0) {
+        n = snprintf(out, (size_t)capacity, "route=zeros supported=1");
+    } else {
+        const gespmm::Gatv2AttentionLaunch r = gespmm::resolve_gatv2_attention(F, xl_align > 16 ? 16 : xl_align,
+                                                                               xr_align > 16 ? 16 : xr_align, att_align > 16 ? 16 : att_align);
+        n = snprintf(out, (size_t)capacity, "V=%d W=%d supported=%d", r.V, r.W, r.supported ? 1 : 0);
     }
     return describe_result(n, capacity);
 }

@@ -343,4 +343,12 @@ DotAttentionLaunch resolve_dot_attention(int64_t F, int q_align, int k_align, in
     return DotAttentionLaunch{b.V, b.W, F <= kDotAttentionMaxF};
 }
 
+// The fused GATv2 attention: the same rule — the one resolve_gatv2_score applies to its three operands — so that on equally aligned
+// operands the fused score has the lane positions, hence the bits, of gespmm_gatv2_score_f32. Nothing here was measured for these
+// kernels.
+Gatv2AttentionLaunch resolve_gatv2_attention(int64_t F, int xl_align, int xr_align, int att_align) {
+    const SddmmLaunch b = resolve_sddmm(false, 1, 1, F, xl_align < xr_align ? xl_align : xr_align, att_align, false, 4);
+    return Gatv2AttentionLaunch{b.V, b.W, F <= kGatv2AttentionMaxF};
+}
+
 }  // namespace gespmm

@@ -89,4 +89,13 @@ struct DotAttentionLaunch {
 // F >= 1. *_align: largest power of two (bytes) that divides an operand's address — the least of a launch's dense operands decides.
 DotAttentionLaunch resolve_dot_attention(int64_t F, int q_align, int k_align, int v_align);
 
+// ---- fused GATv2 attention (gatv2_attention.h): the lane geometry of its three kernels (gespmm_describe_gatv2_attention prints it).
+constexpr int64_t kGatv2AttentionMaxF = 512;  // a lane holds 8 floats of a head slice, a lane group has at most 64 lanes
+struct Gatv2AttentionLaunch {
+    int V, W;        // what resolve_sddmm answers for WIDTH F and the least aligned dense operand: they fix the score's summation order
+    bool supported;  // F <= kGatv2AttentionMaxF; false: no kernel serves the shape, V and W mean nothing
+};
+// F >= 1. *_align: largest power of two (bytes) that divides an operand's address — the least of a launch's dense operands decides.
+Gatv2AttentionLaunch resolve_gatv2_attention(int64_t F, int xl_align, int xr_align, int att_align);
+
 }  // namespace gespmm

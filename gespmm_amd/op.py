@@ -57,6 +57,8 @@ and ``SAGEConv`` DGL's layer of that name with the ``mean``, ``gcn`` and ``pool`
 Graph transformers (extension): ``DotAttentionFunction`` is scaled dot-product attention over the edges in three fused launches
 (``attention.dot_attention`` and its two backward passes: no score, no alpha, nothing of size nnz saved), ``TransformerConv`` PyG's layer
 of that name on it (``fused=True``) or on the composition of the functions above (the default).
+``GATv2AttentionFunction`` is the same for GATv2 — score, softmax, dropout and aggregation in one launch on one gathered row per entry
+(``attention.gatv2_attention`` and its two backward passes), behind ``GATv2Conv(fused=True)``.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -758,6 +760,64 @@ class GATv2ScoreFunction(torch.autograd.Function):
         return None, None, None, None, None, grad_xl, grad_xr, grad_att, None
 
 
+class GATv2AttentionFunction(torch.autograd.Function):
+    """out[r, h, :] = sum_e softmax_row(sum_f att[h, f] leaky_relu(xl[r, h, f] + xr[col(e), h, f]))_e xr[col(e), h, :] — the whole attention
+    of GATv2 (score, softmax, dropout, aggregation) over the edges of a graph in ONE launch (``attention.gatv2_attention``), with
+    gradients for xl, xr and att in two more (``attention.gatv2_attention_backward_row`` over the rows,
+    ``attention.gatv2_attention_backward_col`` over the columns).
+
+        GATv2AttentionFunction.apply(rowptr, colind, colptr, rowind, xl, xr, att, negative_slope=None, dropout_p=0.0, seed=None) -> f32[M, H, F]
+
+    ``xl`` f32[M, H, F] (the aggregating node), ``xr`` f32[K, H, F] (the neighbour: scored AND aggregated), ``att`` f32[H, F]; ``colptr,
+    rowind = graphs.transpose_csr(rowptr, colind, K)`` — no ``csc_order``; ``negative_slope=None``: no leaky ReLU. No score and no
+    attention array exists in either direction: the function saves ``xl, xr, att, out`` and the [M, H, 2] softmax statistics (and the
+    two seed words), nothing of size nnz. ``dropout_p > 0`` with ``seed`` (int32[2] on the device): dropout on the coefficients with
+    ``EdgeDropoutFunction``'s mask, recomputed in all three launches; the seed is read when the backward runs. The row pass runs when
+    any of the three needs a gradient (``att``'s is the sum over nodes of a node-sized result asked for only then), the column pass
+    only when ``xr`` does. ``xl is xr`` (shared weights) works: autograd adds the two gradients. F <= 512. Index tensors get no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, xl, xr, att, negative_slope=None, dropout_p=0.0, seed=None):
+        dropout_p = float(dropout_p)
+        if dropout_p != 0.0 and seed is None:
+            raise ValueError("dropout_p needs a seed (an int32[2] device tensor)")
+        drop = (dropout_p, seed) if dropout_p != 0.0 else None
+        xl_c, xr_c, att_c = xl.contiguous(), xr.contiguous(), att.contiguous()
+        out, stats = _attention.gatv2_attention(rowptr, colind, xl_c, xr_c, att_c, negative_slope=negative_slope, dropout=drop)
+        ctx.graph = (rowptr, colind, colptr, rowind)
+        ctx.negative_slope, ctx.dropout_p = negative_slope, dropout_p
+        if drop is None:
+            ctx.save_for_backward(xl_c, xr_c, att_c, out, stats)
+        else:
+            ctx.save_for_backward(xl_c, xr_c, att_c, out, stats, seed)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        rowptr, colind, colptr, rowind = ctx.graph
+        xl, xr, att, out, stats = ctx.saved_tensors[:5]
+        drop = (ctx.dropout_p, ctx.saved_tensors[5]) if ctx.dropout_p != 0.0 else None
+        slope = ctx.negative_slope
+        grad_xl = grad_xr = grad_att = None
+        if any(ctx.needs_input_grad[4:7]):
+            grad_out = grad_out.contiguous()
+            want_att = bool(ctx.needs_input_grad[6])
+            res = _attention.gatv2_attention_backward_row(rowptr, colind, xl, xr, att, stats, out, grad_out, negative_slope=slope,
+                                                          dropout=drop, want_att_part=want_att)
+            delta, grad_xl = res[0], res[1]
+            if want_att:
+                grad_att = res[2].sum(0)
+            del res
+            if not ctx.needs_input_grad[4]:
+                grad_xl = None
+            if ctx.needs_input_grad[5]:
+                grad_xr = _attention.gatv2_attention_backward_col(colptr, rowind, xl, xr, att, stats, delta, grad_out, negative_slope=slope,
+                                                                  dropout=drop)
+        return None, None, None, None, grad_xl, grad_xr, grad_att, None, None, None
+
+
 class GATv2Conv(torch.nn.Module):
     """GATv2 layer (Brody et al., "How attentive are graph attention networks?") on the library's ops, H heads in every call:
 
@@ -768,20 +828,33 @@ class GATv2Conv(torch.nn.Module):
 
     then heads concatenated (``concat=True``: [n, H F]) or averaged ([n, F]), plus bias.
 
-        GATv2Conv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0)
+        GATv2Conv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0,
+                  fused=False)
         forward(x, rowptr, colind, colptr, rowind, csc_order, attn_seed=None)
 
     ``share_weights=True``: one matrix for both terms (W_dst is W_src). ``dropout=p`` (0 <= p < 1): ``EdgeDropoutFunction`` on alpha in
     training mode, the seed handled exactly as in ``GATConv`` (two words from torch's device generator unless ``attn_seed``, an int32[2]
     device tensor, is given); in ``eval()`` mode or with ``dropout == 0`` the layer makes exactly the launches it makes without it.
-    The ``[nnz, H]`` score and alpha arrays exist (folding the score into the softmax or the aggregation is out of scope).
+    With ``fused=False`` (the default) the ``[nnz, H]`` score and alpha arrays exist, with their gradients, and alpha is read through
+    ``csc_order`` in the backward.
+
+    ``fused=True`` runs ``GATv2AttentionFunction`` instead: score, softmax, dropout and aggregation are ONE launch on one gathered row
+    per entry, the backward two more, and a training step allocates nothing of size ``[nnz, H]`` in either direction. It serves
+    ``out_channels <= 512`` (ValueError at construction beyond), does not read ``csc_order``, and applies the mask of ``fused=False``
+    under one ``attn_seed``; outputs and gradients of the two settings agree to rounding. Off by default.
 
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
     ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only: the fused edge score and its
-    backward have no 16-bit form (the 16-bit multi-head ops serve ``GATConv`` and ``TransformerConv(fused=False)``)."""
+    backward have no 16-bit form (the 16-bit multi-head ops serve ``GATConv`` and ``TransformerConv(fused=False)``), nor has
+    ``fused=True``: 16-bit features raise TypeError."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0,
+                 fused=False):
         super().__init__()
+        if fused and out_channels > _attention.GATV2_ATTENTION_MAX_F:
+            raise ValueError("fused=True serves out_channels <= %d (a head slice is held in registers), got %d" %
+                             (_attention.GATV2_ATTENTION_MAX_F, out_channels))
+        self.fused = bool(fused)
         self.dropout = float(dropout)
         if not (0.0 <= self.dropout < 1.0):
             raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
@@ -820,6 +893,13 @@ class GATv2Conv(torch.nn.Module):
             raise ValueError("GATv2Conv needs a square graph: rowptr and colptr must have x.size(0) + 1 entries")
         xr = (x @ self.weight_src).view(n, H, F)
         xl = xr if self.share_weights else (x @ self.weight_dst).view(n, H, F)
+        if self.fused:
+            if _is_x16(xl) or _is_x16(xr):
+                raise TypeError("GATv2Conv(fused=True) needs torch.float32 features, got %s: attention.gatv2_attention "
+                                "(GATv2AttentionFunction) is fp32 only" % xr.dtype)
+            out = GATv2AttentionFunction.apply(rowptr, colind, colptr, rowind, xl, xr, self.att.view(H, F), self.negative_slope, p, seed)
+            out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
+            return out if self.bias is None else out + self.bias
         score = GATv2ScoreFunction.apply(rowptr, colind, colptr, rowind, csc_order, xl, xr, self.att.view(H, F), self.negative_slope)
         alpha = EdgeSoftmaxFunction.apply(rowptr, score, None)
         if seed is not None:

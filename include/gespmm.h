@@ -969,6 +969,71 @@ int gespmm_dot_attention_backward_kv_dropout_f32(const int32_t* colptr, const in
  * length written or a GESPMM_E* code. */
 int gespmm_describe_dot_attention(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int q_align, int k_align, int v_align, char* out,
                                   int64_t capacity);
+/*
+ * Fused GATv2 attention over the entries of a pattern — score, softmax and aggregation in ONE sweep — and its backward, with NOTHING of
+ * size nnz but the index arrays (new symbols of 0.5). xl [M x H x F] is the aggregating node's term (the row of an entry), xr
+ * [K x H x F] the neighbour's (the column), att [H x F]; out and grad_out [M x H x F], stats [M x H x 2], delta [M x H]. slope == 1:
+ * no multiply. For entry p of row r with column c and head h
+ *
+ *     t_pf = fl(xl[r, h, f] + xr[c, h, f])      s_p = sum_f att[h, f] leaky(t_pf)      leaky(t) = t >= 0 ? t : fl(slope t)
+ *     a_p = exp(s_p - m) / l,  (m, l) = stats[r, h] = (max_p s_p, sum_p exp(s_p - m))      out[r, h, :] = sum_p a_p xr[c, h, :]
+ *
+ * The neighbour's slice is the score's operand AND the aggregated value: one gathered row per entry serves the forward. Geometry of
+ * all three kernels: that of gespmm_dot_attention_f32 — a group of W lanes owns a (segment, head) pair (rows in the forward and in
+ * _backward_row, columns in _backward_col) with V floats per load and 8 floats per lane and operand; (V, W) from
+ * gespmm_describe_gatv2_attention: V the widest of 4 / 2 / 1 that divides F and whose bytes divide the address of every dense operand
+ * (xl, xr, att and the dense results), W the smallest power of two in 4 .. 64 with 8 W >= F — the rule of gespmm_describe_gatv2_score.
+ * F > 512 is not served: GESPMM_ERR_UNSUPPORTED, nothing launched. A hub segment is walked by its one lane group (a limit).
+ * Pinned orders: s_p is the lane chain acc = fmaf(att_j, leaky(fl(xl_j + xr_j)), acc) and xor butterfly of gespmm_gatv2_score_f32, so
+ * on equally aligned operands it has that call's bits; dot(x, y) is the pinned dot of gespmm_dot_attention_f32. The fp32 add and fmaf
+ * commute in their factors: both backward passes see the same bits of t, s_p and g_p. Every per-word accumulation is one chain per
+ * output word in segment (entry) order.
+ *
+ * Forward — one sweep with the online softmax of gespmm_dot_attention_f32 (the same per-entry expressions with v = xr, the same first
+ * entry, out = acc / l). Every word of out and stats is written; an empty row writes +0 everywhere.
+ * gespmm_gatv2_attention_backward_row_f32 (rowptr, colind) writes delta, grad_xl and — unless att_part is NULL — att_part [M x H x F]:
+ *     delta[r, h] = dot(grad_out[r, h, :], out[r, h, :])     g_p = dot(grad_out[r, h, :], xr[c, h, :])     ds_p = a_p (g_p - delta[r, h])
+ *     m_pf = t_pf >= 0 ? att[h, f] : fl(att[h, f] slope)                                        with a_p = __expf(s_p - m) / l
+ *     grad_xl[r, h, f] = chain over p of fmaf(ds_p, m_pf, acc)          att_part[r, h, f] = chain over p of fmaf(ds_p, leaky(t_pf), acc)
+ * (grad_att is att_part summed over r by the caller).
+ * gespmm_gatv2_attention_backward_col_f32 (colptr, rowind: the CSC arrays, no csc_order) reads delta and writes
+ *     grad_xr[c, h, f] = fl( chain over p of fmaf(ds_p, m_pf, acc1) + chain over p of fmaf(a_p, grad_out[r, h, f], acc2) )
+ * The *_dropout_f32 forms put dropout on a_p (the mask of gespmm_edge_dropout_f32: a function of (seed, r, c, h)) where
+ * gespmm_dot_attention_dropout_f32 puts it: the forward's l sums every entry and acc takes fl(t s) for a kept entry, +0 for a dropped
+ * one; the backward replaces g_p by fl(g_p s) or +0 directly after its chain, delta stays dot(grad_out, out), the second chain of
+ * grad_xr uses fl(a_p s) or +0.
+ * Checks, in this order: a negative size, H < 1, M < 1 or K < 1 with nnz > 0, a NaN or infinite slope, !(0 <= p < 1) -> GESPMM_EINVAL;
+ * M, K, nnz, nnz H, M H F, K H F or 2 M H > 2^31 - 4097 -> GESPMM_ERANGE; F > 512 -> GESPMM_ERR_UNSUPPORTED; nnz == 0 or F == 0 looks at
+ * the results (and the seed) alone and zero-fills them (hipMemsetAsync); NULL (att_part excepted) -> GESPMM_EINVAL; a pointer not
+ * 4-byte (stats: 8-byte) aligned -> GESPMM_EALIGN. No atomics, no workspace, no allocation, no host synchronisation: capturable.
+ * Results must not overlap an input (not checked); xl and xr may be the same array. colind within [0, K), rowind within [0, M) and
+ * ptr[last] == nnz are preconditions.
+ */
+int gespmm_gatv2_attention_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att, float* out,
+                               float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gatv2_attention_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att,
+                                       float* out, float* stats, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                       float p, const void* seed, void* stream);
+int gespmm_gatv2_attention_backward_row_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr, const float* att,
+                                            const float* stats, const float* out, const float* grad_out, float* delta, float* grad_xl,
+                                            float* att_part, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                            void* stream);
+int gespmm_gatv2_attention_backward_row_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* xl, const float* xr,
+                                                    const float* att, const float* stats, const float* out, const float* grad_out,
+                                                    float* delta, float* grad_xl, float* att_part, int64_t M, int64_t K, int64_t H,
+                                                    int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream);
+int gespmm_gatv2_attention_backward_col_f32(const int32_t* colptr, const int32_t* rowind, const float* xl, const float* xr, const float* att,
+                                            const float* stats, const float* delta, const float* grad_out, float* grad_xr, int64_t M,
+                                            int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gatv2_attention_backward_col_dropout_f32(const int32_t* colptr, const int32_t* rowind, const float* xl, const float* xr,
+                                                    const float* att, const float* stats, const float* delta, const float* grad_out,
+                                                    float* grad_xr, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                                    float p, const void* seed, void* stream);
+/* Host only: what the three entry points would launch, as text: "V=.. W=.. supported=1", "route=unsupported supported=0" (F > 512),
+ * "route=zeros supported=1" (F == 0) or "form=none supported=1" (nnz == 0). *_align: largest power of two (>= 4) dividing the operand's
+ * address (pass the least of the dense results' with xl's); the least of them decides V. Returns the length written or a GESPMM_E* code. */
+int gespmm_describe_gatv2_attention(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int xl_align, int xr_align, int att_align,
+                                    char* out, int64_t capacity);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
