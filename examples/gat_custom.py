@@ -18,6 +18,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
                                                                    # one kernel, the backward in two: no [nnz, H] array in a step
     python examples/gat_custom.py --dtype bf16                     # a .bfloat16() model on bf16 features (or fp16): the aggregation is the
                                                                    # 16-bit multi-head product, everything edge-sized stays fp32
+    python examples/gat_custom.py --v2 --dtype bf16                # ``GATv2Conv`` as a 16-bit model: the edge score and its two gradient
+                                                                   # passes read bf16 (or fp16) node terms, att and the score stay fp32
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
 chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
@@ -100,12 +102,13 @@ def main():
                     help="torch.manual_seed before the model is made (parameters and dropout masks): two runs, or two fused settings, "
                          "then print the same losses")
     ap.add_argument("--dtype", choices=("fp32", "bf16", "fp16"), default="fp32",
-                    help="cast the model and the features (bf16 / fp16: GATConv on the 16-bit multi-head product; not with "
-                         "--fused-aggregate, --fused-backward or --v2, which are fp32 only)")
+                    help="cast the model and the features (bf16 / fp16: GATConv on the 16-bit multi-head product, with --v2 GATv2Conv "
+                         "on the 16-bit edge score too; not with --fused-aggregate, --fused-backward or --fused-attention, which are "
+                         "fp32 only)")
     args = ap.parse_args()
-    if args.dtype != "fp32" and (args.fused_aggregate or args.fused_backward or args.v2):
-        ap.error("--dtype %s: --fused-aggregate, --fused-backward and --v2 run fp32-only kernels; use the default path or --fused-score"
-                 % args.dtype)
+    if args.dtype != "fp32" and (args.fused_aggregate or args.fused_backward or args.fused_attention):
+        ap.error("--dtype %s: --fused-aggregate, --fused-backward and --fused-attention run fp32-only kernels; use the default path, "
+                 "--fused-score or --v2" % args.dtype)
     if args.v2 and (args.fused_score or args.fused_aggregate or args.fused_backward):
         ap.error("--fused-score, --fused-aggregate and --fused-backward are GATConv's: --v2 has --fused-attention")
     if args.fused_attention and not args.v2:

@@ -132,6 +132,9 @@ EXPORTS = [
     "gespmm_gatv2_score_f32",
     "gespmm_gatv2_score_backward_f32",
     "gespmm_describe_gatv2_score",
+    "gespmm_gatv2_score_x16",
+    "gespmm_gatv2_score_backward_x16",
+    "gespmm_describe_gatv2_score_x16",
     "gespmm_dot_attention_f32",
     "gespmm_dot_attention_dropout_f32",
     "gespmm_dot_attention_backward_q_f32",
@@ -384,6 +387,12 @@ def _load():
     lib.gespmm_gatv2_score_backward_f32.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, p]
     lib.gespmm_describe_gatv2_score.restype = c_int
     lib.gespmm_describe_gatv2_score.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_gatv2_score_x16.restype = c_int
+    lib.gespmm_gatv2_score_x16.argtypes = [p] * 6 + [c_int] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_score_backward_x16.restype = c_int
+    lib.gespmm_gatv2_score_backward_x16.argtypes = [p] * 9 + [c_int] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_describe_gatv2_score_x16.restype = c_int
+    lib.gespmm_describe_gatv2_score_x16.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_dot_attention_f32.restype = c_int
     lib.gespmm_dot_attention_f32.argtypes = [p] * 7 + [c_int64] * 5 + [c_float, p]
     lib.gespmm_dot_attention_dropout_f32.restype = c_int
@@ -523,15 +532,18 @@ def describe_edge_softmax(M, nnz, H):
     return {"W": int(w.split("=")[1]), "L": int(long_rows.split(">")[1])}
 
 
-def describe_gatv2_score(M, nnz, H, F, xl_align=16, xr_align=16, att_align=16):
-    """What gespmm_gatv2_score_f32 would launch for these sizes and operand alignments (gespmm_describe_gatv2_score: host only) — a
-    dict ``{"V": floats per load, "W": lanes per (entry, head) pair, "epw": ENTRIES per wavefront}``; ``{"route": "zeros"}`` when
-    F == 0 and ``{"form": "none"}`` when nnz == 0. V and W fix the summation order; V divides F and 4 V bytes divide all three
-    operand addresses."""
+def describe_gatv2_score(M, nnz, H, F, xl_align=16, xr_align=16, att_align=16, x16=False):
+    """What gespmm_gatv2_score_f32 — x16=True: gespmm_gatv2_score_x16, fp16 / bf16 ``xl`` and ``xr`` with an fp32 ``att`` — would launch
+    for these sizes and operand alignments (gespmm_describe_gatv2_score / _x16: host only) — a dict ``{"V": elements per load, "W":
+    lanes per (entry, head) pair, "epw": ENTRIES per wavefront}``; ``{"route": "zeros"}`` when F == 0 and ``{"form": "none"}`` when
+    nnz == 0. V and W fix the summation order. fp32: V divides F and 4 V bytes divide all three operand addresses. x16: V is 8 / 4 / 2 /
+    1, divides F, 2 V bytes divide the addresses of ``xl`` and ``xr`` (alignments from 2) and min(4 V, 16) bytes that of ``att``."""
     buf = ctypes.create_string_buffer(96)
-    n = lib.gespmm_describe_gatv2_score(int(M), int(nnz), int(H), int(F), int(xl_align), int(xr_align), int(att_align), buf, 96)
+    f, name = (lib.gespmm_describe_gatv2_score_x16, "gespmm_describe_gatv2_score_x16") if x16 else \
+        (lib.gespmm_describe_gatv2_score, "gespmm_describe_gatv2_score")
+    n = f(int(M), int(nnz), int(H), int(F), int(xl_align), int(xr_align), int(att_align), buf, 96)
     if n < 0:
-        raise GespmmError(n, "gespmm_describe_gatv2_score")
+        raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
 

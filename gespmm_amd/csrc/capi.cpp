@@ -1541,6 +1541,72 @@ int gespmm_describe_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, in
     return describe_result(n, capacity);
 }
 
+/* ... on fp16 / bf16 node operands (gespmm.h; gatv2_score.h): the dtype code first, as in every _x16 entry, then the ladders above with
+   2-byte alignment for the 16-bit operands. */
+int gespmm_gatv2_score_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att, float* score,
+                           int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_sizes(M, K, H, F, nnz, slope);
+    if (rc != 0) return rc;
+    if (nnz == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (F == 0) {
+        if (const int rcp = check_pointers({{score, 4, true}})) return rcp;
+        return (int)hipMemsetAsync(score, 0, (size_t)nnz * (size_t)H * sizeof(float), st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {xl, 2, true}, {xr, 2, true}, {att, 4, true}, {score, 4, true}}))
+        return rcp;
+    const gespmm::Gatv2ScoreLaunch r =
+        gespmm::resolve_gatv2_score_x16(M, nnz, H, F, pointer_alignment(xl), pointer_alignment(xr), pointer_alignment(att));
+    return (int)gespmm::launch_gatv2_score_x16(rowptr, colind, xl, xr, att, score, dtype, M, nnz, H, F, slope, r, st);
+}
+
+int gespmm_gatv2_score_backward_x16(const int32_t* ptr, const int32_t* ind, const int32_t* order, const float* grad_score,
+                                    const void* x_seg, const void* x_ind, const float* att, void* grad_x, float* att_part, int dtype,
+                                    int64_t S, int64_t T, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_sizes(S, T, H, F, nnz, slope);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {  // every chain is empty: every word of the results is still written (+0 has no set bit in either type)
+        if (const int rcp = check_pointers({{grad_x, 2, true}, {att_part, 4, false}})) return rcp;
+        const size_t elems = (size_t)S * (size_t)H * (size_t)F;
+        if (elems == 0) return 0;
+        hipError_t e = hipMemsetAsync(grad_x, 0, elems * sizeof(uint16_t), st);
+        if (e == hipSuccess && att_part) e = hipMemsetAsync(att_part, 0, elems * sizeof(float), st);
+        return (int)e;
+    }
+    if (const int rcp = check_pointers({{ptr, 4, true}, {ind, 4, true}, {grad_score, 4, true}, {x_seg, 2, true}, {x_ind, 2, true},
+                                        {att, 4, true}, {grad_x, 2, true}, {order, 4, false}, {att_part, 4, false}}))
+        return rcp;
+    int f_align = pointer_alignment(att);
+    if (att_part) f_align = std::min(f_align, pointer_alignment(att_part));
+    const int x_align = gespmm::least_alignment({x_seg, x_ind, grad_x});
+    return (int)gespmm::launch_gatv2_score_backward_x16(ptr, ind, order, grad_score, x_seg, x_ind, att, grad_x, att_part, dtype, S, H, F, nnz,
+                                                        slope, gespmm::gatv2_score_x16_vec(F, x_align, std::min(f_align, 16)), st);
+}
+
+int gespmm_describe_gatv2_score_x16(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align, char* out,
+                                    int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    for (const int a : {xl_align, xr_align, att_align})
+        if (a < 2 || (a & (a - 1)) != 0) return GESPMM_EINVAL;
+    if (att_align < 4) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_sizes(M, nnz > 0 ? 1 : 0, H, F, nnz, 1.0f);  // (the forward's launch shape does not depend on K)
+    if (rc != 0) return rc;
+    int n;
+    if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else if (F == 0) {
+        n = snprintf(out, (size_t)capacity, "route=zeros");
+    } else {
+        const gespmm::Gatv2ScoreLaunch r = gespmm::resolve_gatv2_score_x16(M, nnz, H, F, xl_align > 16 ? 16 : xl_align,
+                                                                           xr_align > 16 ? 16 : xr_align, att_align > 16 ? 16 : att_align);
+        n = snprintf(out, (size_t)capacity, "V=%d W=%d epw=%d", r.V, r.W, r.epw);
+    }
+    return describe_result(n, capacity);
+}
+
 /* Fused scaled dot-product attention over a pattern and its backward (gespmm.h; dot_attention.h): one kernel each, nothing of size nnz
    but the index arrays. The ladder is check_dot_attention_sizes, nnz == 0, F == 0, then the pointers. */
 static int zero_fill(std::initializer_list<std::pair<float*, size_t>> outs, hipStream_t st) {

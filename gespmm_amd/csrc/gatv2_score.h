@@ -1,5 +1,6 @@
 // gatv2_score.h — the GATv2 edge score and its gradients (gespmm_gatv2_score_f32, gespmm_gatv2_score_backward_f32; kernels:
-// gatv2_score.hip). fp32, CSR form only; no plan, no composition route, no environment pin.
+// gatv2_score.hip). fp32, CSR form only; no plan, no composition route, no environment pin. The form on fp16 / bf16 node operands
+// (gespmm_gatv2_score_x16, gespmm_gatv2_score_backward_x16; kernels: gatv2_score_x16.hip) is described at the end of this header.
 //
 // xl is [M, H, F] (the aggregating node: the row of an entry), xr is [K, H, F] (the neighbour: the column), att is [H, F], score is
 // [nnz, H] in CSR entry order, head-minor — what the edge softmax reads:
@@ -55,5 +56,40 @@ hipError_t launch_gatv2_score(const int32_t* rowptr, const int32_t* colind, cons
 hipError_t launch_gatv2_score_backward(const int32_t* ptr, const int32_t* ind, const int32_t* order, const float* grad_score,
                                        const float* x_seg, const float* x_ind, const float* att, float* grad_x, float* att_part, int64_t S,
                                        int64_t H, int64_t F, int64_t nnz, float slope, bool vec4, hipStream_t st);
+
+// ---- the same two on 16-bit node operands (gespmm_gatv2_score_x16, gespmm_gatv2_score_backward_x16; kernels: gatv2_score_x16.hip).
+// xl, xr, x_seg, x_ind and grad_x are fp16 or bf16 (dtype kX16F16 / kX16Bf16, one type per call); att, grad_score, score and att_part
+// stay fp32 — att is a parameter of H F words whose gradient is a sum over nodes, and everything edge-sized is fp32 in this library.
+// The arithmetic is the fp32 contract above, unchanged: every 16-bit element is widened exactly at its use (widen_x16, spmm_device.h;
+// subnormals included), t = fl32(widen(xl_j) + widen(xr_j)) is ONE fp32 add, the branch is t >= 0, the forward is the pinned lane chain
+// and butterfly, the backward one fmaf chain per output word in segment order with m = t >= 0 ? att : fl(att slope). grad_x is rounded
+// ONCE, at the store (narrow_x16: to nearest even, overflow to +-inf, NaN stays NaN). No packed-fp16 arithmetic and no dot2.
+// Consequences: on equal (V, W) the forward has the bits of the fp32 kernel on the widened operands; the backward's att_part has the
+// bits of the fp32 kernel on the widened operands whatever the geometry, and grad_x is that kernel's grad_x rounded once.
+//
+// FORWARD geometry: the fp32 kernel's with a lane's vector counted in ELEMENTS, V in {8, 4, 2, 1} — a dwordx4 / dwordx2 / dword / ushort
+// load of xl and xr, and att's V floats at the same element positions (two dwordx4 loads at V = 8). V is the largest value that divides
+// F, whose 2 V bytes divide the addresses of xl and xr, and whose min(4 V, 16) bytes divide the address of att; W and epw are the
+// existing resolvers' at element size 2 for width F (resolve_gatv2_score_x16, select.cpp). The bits depend on (V, W) alone. Pairs in
+// flight per lane group: 4 up to V = 4, 2 at V = 8 (registers: gatv2_score_x16.hip).
+// BACKWARD geometry: the fp32 row walk at width N = H F with V elements per lane, four gathers in flight: V the largest of 8 / 4 / 2 / 1
+// that divides F (no vector spans two heads), whose 2 V bytes divide the addresses of x_seg, x_ind and grad_x and whose min(4 V, 16)
+// bytes divide those of att and att_part (gatv2_score_x16_vec) — 16-byte vectors when F % 8 == 0 and every dense operand is 16-byte
+// aligned; V = 1 serves any F and any 2-byte aligned address. Geometry leaves no trace in the bits.
+// The safety rules and the limits are those above (positions count 16-bit ELEMENTS); no long-segment pass.
+
+// nnz >= 1, M, K, H, F >= 1; nnz H, M H F and K H F <= kSddmmMaxNnz; colind within [0, K). r = resolve_gatv2_score_x16(...) for the
+// addresses of xl, xr and att.
+hipError_t launch_gatv2_score_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att,
+                                  float* score, int dtype, int64_t M, int64_t nnz, int64_t H, int64_t F, float slope,
+                                  const Gatv2ScoreLaunch& r, hipStream_t st);
+
+// The backward's vector: x_align the least alignment (bytes, a power of two <= 16) of the 16-bit operands, f_align that of the fp32 ones.
+int gatv2_score_x16_vec(int64_t F, int x_align, int f_align);
+
+// S, T, H, F, nnz >= 1; limits as above. att_part may be null. V = gatv2_score_x16_vec(F, ...) for x_seg, x_ind, grad_x | att, att_part.
+hipError_t launch_gatv2_score_backward_x16(const int32_t* ptr, const int32_t* ind, const int32_t* order, const float* grad_score,
+                                           const void* x_seg, const void* x_ind, const float* att, void* grad_x, float* att_part, int dtype,
+                                           int64_t S, int64_t H, int64_t F, int64_t nnz, float slope, int V, hipStream_t st);
 
 }  // namespace gespmm

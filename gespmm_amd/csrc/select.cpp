@@ -321,8 +321,7 @@ EdgeSoftmaxLaunch resolve_edge_softmax(int64_t M, int64_t nnz, int64_t H) {
 // less aligned of xl and xr as one operand and att as the other: V divides F and 4 V bytes divide all THREE bases. Entries per wavefront
 // and the multiply-shift for t / H are resolve_sddmm_heads' rule for its CSR kernel, on the pair count nnz H. None of these thresholds
 // was measured for this kernel, which loads three vectors per pair where the SDDMM loads two: all are carried over.
-Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align) {
-    const SddmmLaunch b = resolve_sddmm(false, M, nnz, F, xl_align < xr_align ? xl_align : xr_align, att_align, false, 4);
+static Gatv2ScoreLaunch gatv2_score_launch(const SddmmLaunch& b, int64_t nnz, int64_t H) {
     Gatv2ScoreLaunch r = {b.V, b.W, 0, 0};
     const int64_t pairs = nnz * H;
     const int G = 64 / r.W;
@@ -332,6 +331,19 @@ Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t 
     // t / H == (t * magic) >> 32 for t < 256 H needs 256 H (magic H - 2^32) < 2^32, and magic H - 2^32 < H: H <= 4096
     if (H <= 4096) r.magic = (uint32_t)(((1ull << 32) + (uint64_t)H - 1) / (uint64_t)H);
     return r;
+}
+
+Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align) {
+    return gatv2_score_launch(resolve_sddmm(false, M, nnz, F, xl_align < xr_align ? xl_align : xr_align, att_align, false, 4), nnz, H);
+}
+
+// ... on 16-bit xl and xr (att stays fp32): resolve_sddmm at element size 2 — V counts ELEMENTS, up to 8, and 2 V bytes divide the
+// bases of xl and xr. att's V floats are loaded in pieces of at most 16 bytes, so min(4 V, 16) bytes must divide its base: a 16-byte
+// aligned att allows every V, an 8-byte aligned one V = 2, a 4-byte aligned one V = 1 — which is the rule "2 V bytes divide" applied to
+// half its alignment. W, epw and the multiply-shift as above (carried over, not measured at 16 bits).
+Gatv2ScoreLaunch resolve_gatv2_score_x16(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align) {
+    const int att_as_x16 = att_align >= 16 ? 16 : att_align / 2;
+    return gatv2_score_launch(resolve_sddmm(false, M, nnz, F, xl_align < xr_align ? xl_align : xr_align, att_as_x16, false, 2), nnz, H);
 }
 
 // The fused dot-product attention. V and W are resolve_sddmm's at WIDTH F (its COO form: no row-walking or blocked answer) for the least

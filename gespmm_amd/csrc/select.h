@@ -79,6 +79,9 @@ struct Gatv2ScoreLaunch {
 };
 // nnz >= 1, H >= 1, F >= 1. *_align: largest power of two (bytes) that divides the operand's address, 16 is as good as more.
 Gatv2ScoreLaunch resolve_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align);
+// The same for fp16 / bf16 xl and xr with an fp32 att (gespmm_describe_gatv2_score_x16 prints it): V counts ELEMENTS, 8 / 4 / 2 / 1 — V
+// divides F, 2 V bytes divide the addresses of xl and xr, min(4 V, 16) bytes divide att's. xl_align, xr_align >= 2, att_align >= 4.
+Gatv2ScoreLaunch resolve_gatv2_score_x16(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align);
 
 // ---- fused dot-product attention (dot_attention.h): the lane geometry of its three kernels (gespmm_describe_dot_attention prints it).
 constexpr int64_t kDotAttentionMaxF = 512;  // a lane holds 8 floats of a head slice, a lane group has at most 64 lanes

@@ -45,7 +45,9 @@ instead of one ``sddmm.csr_sddmm`` per head on copies (the default, kept as it w
 16-bit attention (extension): both functions take fp16 / bf16 node tensors (``feat``; ``q`` and ``k``) and run forward and backward on
 ``spmm.csr_spmm_heads_x16`` / ``sddmm.csr_sddmm_heads_x16``; everything edge-sized — scores, weights, their gradients — stays fp32.
 ``GATConv`` (default and ``fused_score=True`` paths) and ``TransformerConv(fused=False)`` therefore work as ``.half()`` / ``.bfloat16()``
-models and under ``torch.autocast``; the fused aggregation / backward, ``GATv2Conv`` and ``TransformerConv(fused=True)`` are fp32 only.
+models and under ``torch.autocast``, and so does ``GATv2Conv(fused=False)``, whose score runs on 16-bit node terms too
+(``GATv2ScoreFunction`` on ``sddmm.gatv2_score_x16`` / ``gatv2_score_backward_x16``); the fused aggregation / backward,
+``GATv2Conv(fused=True)`` and ``TransformerConv(fused=True)`` are fp32 only.
 ``EdgeSoftmaxFunction`` is the step between the two — softmax over the entries of each row, per head, with the leaky ReLU of a GAT
 fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` the graph attention layer composed from the three.
 ``GATSoftmaxFunction`` is the first two in one: the softmax of el[row] + er[col] with no score array (``GATConv(fused_score=True)``).
@@ -93,8 +95,21 @@ def _csc_heads_product(ctx, colptr, rowind, csc_order, weight, dense):
     over as ``spmm.OrderedValues`` in the place of the weights) where the forward found the ordered kernel, gathered otherwise."""
     values = _spmm.OrderedValues(weight, ctx.order) if ctx.order is not None else _graphs.take_edges(weight, csc_order)
     if ctx.x16:
-        return _spmm.csr_spmm_heads_x16(colptr, rowind, values, dense)
+        return _heads_x16_product(colptr, rowind, values, dense)
     return _spmm.csr_spmm_heads(colptr, rowind, values, dense, plan=ctx.bwd_plan)
+
+
+def _heads_x16_product(rowptr, colind, values, dense):
+    """``spmm.csr_spmm_heads_x16`` for the autograd functions. Where that op has no kernel (``_lib.heads_x16_route`` answers 0: H = 1,
+    H > 8, odd F) it composes widen / fp32 product / narrow through a stream-ordered temporary, which it refuses on a capturing stream.
+    There — and only there — the same composition is made of torch's allocations, which a capture may hold:
+    ``csr_spmm_heads(rowptr, colind, values, dense.float()).to(dense.dtype)``, the bits the op documents."""
+    if isinstance(values, torch.Tensor) and dense.is_cuda and torch.cuda.is_current_stream_capturing():
+        M, K, (nnz, H) = rowptr.numel() - 1, dense.shape[0], values.shape
+        F = math.prod(dense.shape[1:]) // max(H, 1)
+        if _lib.heads_x16_route(M, K, H, F, nnz)[0] != 1:
+            return _spmm.csr_spmm_heads(rowptr, colind, values, dense.float()).to(dense.dtype)
+    return _spmm.csr_spmm_heads_x16(rowptr, colind, values, dense)
 
 
 def _is_x16(t):
@@ -209,7 +224,10 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
     rounding), grad_feat is ``csr_spmm_heads_x16`` on the CSC arrays with ``order=`` (``take_edges`` where ``_lib.heads_x16_route`` is 0: odd F
     too), grad_weight stays fp32 —
     ``sddmm.csr_sddmm_heads_x16(rowptr, colind, grad_out, feat)`` with ``heads_sddmm=True``, the 16-bit ``sddmm.csr_sddmm`` per head
-    otherwise. ``plans=`` with 16-bit tensors raises TypeError (the 16-bit multi-head ops have no plan form)."""
+    otherwise. ``plans=`` with 16-bit tensors raises TypeError (the 16-bit multi-head ops have no plan form). On a capturing stream,
+    where ``_lib.heads_x16_route`` is 0 (H = 1, H > 8, odd F: the op's own composition allocates and is refused there), forward and
+    grad_feat are ``csr_spmm_heads(..., feat.float()).to(feat.dtype)`` on torch's allocations — the same bits, so a 16-bit layer with one
+    head replays from a captured graph."""
 
     @staticmethod
     def forward(ctx, rowptr, colind, colptr, rowind, csc_order, feat, weight, plans=None, heads_sddmm=False):
@@ -221,7 +239,7 @@ class MultiHeadSPMMFunction(torch.autograd.Function):
             raise TypeError("plans= needs torch.float32 feat, got %s: spmm.csr_spmm_heads_x16 has no plan form" % feat.dtype)
         feat_c, weight_c = feat.contiguous(), weight.contiguous()
         if ctx.x16:
-            out = _spmm.csr_spmm_heads_x16(rowptr, colind, weight_c, feat_c)
+            out = _heads_x16_product(rowptr, colind, weight_c, feat_c)
         else:
             out = _spmm.csr_spmm_heads(rowptr, colind, weight_c, feat_c, plan=fwd_plan)
         ctx.graph = (rowptr, colind, colptr, rowind, csc_order)
@@ -727,12 +745,18 @@ class GATv2ScoreFunction(torch.autograd.Function):
     the row pass of ``sddmm.gatv2_score_backward`` when ``xl`` or ``att`` needs a gradient (grad_att is the sum over nodes of its second,
     node-sized result), the column pass on the CSC arrays when ``xr`` does. Saved: the three operands — no saved or allocated tensor
     has nnz * H * F words. An int64 ``csc_order`` is converted to int32 in every forward; pass an int32 one. Index tensors get no
-    gradient."""
+    gradient.
+
+    16-bit ``xl`` and ``xr`` (both ``torch.float16`` or both ``torch.bfloat16``; ``att`` must be fp32): the same three launches through
+    ``sddmm.gatv2_score_x16`` / ``sddmm.gatv2_score_backward_x16``. The score stays f32[nnz, H], the 16-bit operands are what is saved,
+    ``grad_xl`` / ``grad_xr`` come back in their dtype (fp32 chains, one rounding) and ``grad_att`` as fp32 (``att_part.sum(0)``)."""
 
     @staticmethod
     def forward(ctx, rowptr, colind, colptr, rowind, csc_order, xl, xr, att, negative_slope=None):
         xl_c, xr_c, att_c = xl.contiguous(), xr.contiguous(), att.contiguous()
-        score = _sddmm.gatv2_score(rowptr, colind, xl_c, xr_c, att_c, negative_slope=negative_slope)
+        ctx.x16 = _is_x16(xl) or _is_x16(xr)
+        score_op = _sddmm.gatv2_score_x16 if ctx.x16 else _sddmm.gatv2_score
+        score = score_op(rowptr, colind, xl_c, xr_c, att_c, negative_slope=negative_slope)
         order = (csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)).contiguous()
         ctx.graph = (rowptr, colind, colptr, rowind, order)
         ctx.negative_slope = negative_slope
@@ -745,10 +769,11 @@ class GATv2ScoreFunction(torch.autograd.Function):
         xl, xr, att = ctx.saved_tensors
         slope = ctx.negative_slope
         grad_score = grad_score.contiguous()
+        backward_op = _sddmm.gatv2_score_backward_x16 if ctx.x16 else _sddmm.gatv2_score_backward
         grad_xl = grad_xr = grad_att = None
         if ctx.needs_input_grad[5] or ctx.needs_input_grad[7]:
             want_att = bool(ctx.needs_input_grad[7])
-            res = _sddmm.gatv2_score_backward(rowptr, colind, grad_score, xl, xr, att, negative_slope=slope, want_att_part=want_att)
+            res = backward_op(rowptr, colind, grad_score, xl, xr, att, negative_slope=slope, want_att_part=want_att)
             grad_xl, att_part = res if want_att else (res, None)
             if want_att:
                 grad_att = att_part.sum(0)
@@ -756,7 +781,7 @@ class GATv2ScoreFunction(torch.autograd.Function):
             if not ctx.needs_input_grad[5]:
                 grad_xl = None
         if ctx.needs_input_grad[6]:
-            grad_xr = _sddmm.gatv2_score_backward(colptr, rowind, grad_score, xr, xl, att, negative_slope=slope, order=order)
+            grad_xr = backward_op(colptr, rowind, grad_score, xr, xl, att, negative_slope=slope, order=order)
         return None, None, None, None, None, grad_xl, grad_xr, grad_att, None
 
 
@@ -844,9 +869,14 @@ class GATv2Conv(torch.nn.Module):
     under one ``attn_seed``; outputs and gradients of the two settings agree to rounding. Off by default.
 
     The graph is square (row r and column r are the same node; add self-loops so that no row is empty);
-    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``. fp32 only: the fused edge score and its
-    backward have no 16-bit form (the 16-bit multi-head ops serve ``GATConv`` and ``TransformerConv(fused=False)``), nor has
-    ``fused=True``: 16-bit features raise TypeError."""
+    ``colptr, rowind, csc_order = graphs.transpose_csr(rowptr, colind, K, return_order=True)``.
+
+    16-bit features (a ``.half()`` / ``.bfloat16()`` layer, or ``torch.autocast``) with ``fused=False``: ``xl`` and ``xr`` stay 16-bit,
+    ``att`` is passed as ``self.att.view(H, F).float()`` (autograd rounds its gradient back into the parameter's dtype), the score is
+    ``GATv2ScoreFunction`` on ``sddmm.gatv2_score_x16`` (fp32 result; both gradient passes on ``sddmm.gatv2_score_backward_x16``),
+    softmax and dropout are the unchanged fp32 ops, the aggregation is the 16-bit product (``MultiHeadSPMMFunction`` on
+    ``spmm.csr_spmm_heads_x16``: fp32 sums, one rounding) and the bias add is torch's. ``share_weights=True`` works as in fp32.
+    ``fused=True`` — the fused attention kernels — is fp32 only: 16-bit features raise TypeError."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0,
                  fused=False):
@@ -900,7 +930,9 @@ class GATv2Conv(torch.nn.Module):
             out = GATv2AttentionFunction.apply(rowptr, colind, colptr, rowind, xl, xr, self.att.view(H, F), self.negative_slope, p, seed)
             out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
             return out if self.bias is None else out + self.bias
-        score = GATv2ScoreFunction.apply(rowptr, colind, colptr, rowind, csc_order, xl, xr, self.att.view(H, F), self.negative_slope)
+        # (att as fp32 — the same tensor in an fp32 layer; in a 16-bit one autograd rounds its gradient back into the parameter's dtype)
+        score = GATv2ScoreFunction.apply(rowptr, colind, colptr, rowind, csc_order, xl, xr, self.att.view(H, F).float(),
+                                         self.negative_slope)
         alpha = EdgeSoftmaxFunction.apply(rowptr, score, None)
         if seed is not None:
             alpha = EdgeDropoutFunction.apply(rowptr, colind, alpha, p, seed)

@@ -35,7 +35,15 @@ GATv2 edge score (extension; gespmm_gatv2_score_f32, gespmm_gatv2_score_backward
 
 score[p, h] = sum_f att[h, f] leaky_relu(xl[row(p), h, f] + xr[col(p), h, f]) — the non-linearity inside the sum, so the score is no
 dot product of a row term and a column term — in ONE kernel, and its gradients in one kernel that serves both node terms; nothing of
-size nnz * H * F exists in either direction. fp32 and CSR form only.
+size nnz * H * F exists in either direction. CSR form only. These two are fp32 only (16-bit operands raise TypeError); fp16 / bf16 node
+terms have names of their own (gespmm_gatv2_score_x16, gespmm_gatv2_score_backward_x16):
+
+    gatv2_score_x16(rowptr, colind, xl, xr, att, negative_slope=0.2, out=None)                     -> f32[nnz, H]
+    gatv2_score_backward_x16(ptr, ind, grad_score, x_seg, x_ind, att, negative_slope=0.2, order=None,
+                             want_att_part=False, out=None)                                        -> grad_x 16-bit [S, H, F] (, att_part f32)
+
+xl / xr (x_seg / x_ind) both ``torch.float16`` or both ``torch.bfloat16``; ``att``, ``grad_score``, the score and ``att_part`` stay fp32.
+The arithmetic is that of the fp32 pair on the exactly widened elements; ``grad_x`` is rounded once, to nearest even.
 """
 import torch
 
@@ -354,5 +362,118 @@ def gatv2_score_backward(ptr, ind, grad_score, x_seg, x_ind, att, negative_slope
                                                  _ptr(x_seg), _ptr(x_ind), _ptr(att), _ptr(out_x), _ptr(out_a) if want_att_part else None,
                                                  S, T, H, F, nnz, slope, _stream(dev))
     check(rc, "gespmm_gatv2_score_backward_f32")
+    return (out_x, out_a) if want_att_part else out_x
+
+
+# ---- ... on fp16 / bf16 node operands (gespmm_gatv2_score_x16 / gespmm_gatv2_score_backward_x16)
+
+def _gatv2_typed_x16(int_ops, node_ops, float_ops):
+    """``_gatv2_typed`` with a third class: the node operands, all ``torch.float16`` or all ``torch.bfloat16`` -> the GESPMM_X16_* code.
+    The first of them names the type (``None`` passes, but not there)."""
+    from .spmm import _X16
+
+    _gatv2_typed(int_ops, float_ops)
+    first_name, first = node_ops[0]
+    if not isinstance(first, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % first_name)
+    if first.dtype not in _X16:
+        raise TypeError("%s must have dtype torch.float16 or torch.bfloat16, got %s (fp32: the functions without _x16)" %
+                        (first_name, first.dtype))
+    for name, t in node_ops[1:]:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != first.dtype:  # (mixed 16-bit dtypes and fp32 node operands: TypeError)
+            raise TypeError("%s must have dtype %s, as %s, got %s" % (name, first.dtype, first_name, t.dtype))
+    return _X16[first.dtype]
+
+
+def gatv2_score_x16(rowptr, colind, xl, xr, att, negative_slope=0.2, out=None):
+    """``gatv2_score`` on 16-bit node terms (gespmm_gatv2_score_x16): ``xl`` [M, H, F] and ``xr`` [K, H, F] both ``torch.float16`` or both
+    ``torch.bfloat16``, ``att`` f32[H, F], result f32[nnz, H] — everything edge-sized stays fp32. Every element is widened exactly at its
+    use and the arithmetic is ``gatv2_score``'s: where ``_lib.describe_gatv2_score`` answers the same (V, W) with and without ``x16=True``
+    the result has the bits of ``gatv2_score`` on ``xl.float(), xr.float()``. A 16-bit ``att`` or ``out``, fp32 node terms and mixed 16-bit
+    dtypes raise TypeError."""
+    x16 = _gatv2_typed_x16((("rowptr", rowptr), ("colind", colind)), (("xl", xl), ("xr", xr)), (("att", att), ("out", out)))
+    for name, t in (("rowptr", rowptr), ("colind", colind), ("xr", xr), ("att", att)):
+        if t is None:
+            raise TypeError("%s must be a torch.Tensor" % name)
+    slope = _gatv2_slope(negative_slope)
+    if xl.dim() != 3 or xr.dim() != 3 or xl.shape[1] < 1:
+        raise ValueError("xl and xr must be [rows, H, F] with at least one head")
+    M, H, F = xl.shape
+    K = xr.shape[0]
+    if tuple(xr.shape[1:]) != (H, F):
+        raise ValueError("xl %s and xr %s must have the same heads and columns" % (tuple(xl.shape), tuple(xr.shape)))
+    if tuple(att.shape) != (H, F):
+        raise ValueError("att must be f32[%d, %d], got %s" % (H, F, tuple(att.shape)))
+    if rowptr.dim() != 1 or rowptr.numel() != M + 1:
+        raise ValueError("rowptr must be a vector of xl.size(0) + 1 entries")
+    if colind.dim() != 1:
+        raise ValueError("colind must be a vector")
+    nnz = colind.numel()
+    if out is not None and tuple(out.shape) != (nnz, H):
+        raise ValueError("out must be f32[%d, %d]" % (nnz, H))
+    dev = xl.device
+    _gatv2_shaped((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("out", out)), dev)
+    if out is None:
+        out = torch.empty((nnz, H), dtype=torch.float32, device=dev)
+    with _on_device(dev):
+        rc = lib.gespmm_gatv2_score_x16(_ptr(rowptr), _ptr(colind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(out), x16, M, K, H, F, nnz, slope,
+                                        _stream(dev))
+    check(rc, "gespmm_gatv2_score_x16")
+    return out
+
+
+def gatv2_score_backward_x16(ptr, ind, grad_score, x_seg, x_ind, att, negative_slope=0.2, order=None, want_att_part=False, out=None):
+    """``gatv2_score_backward`` on 16-bit node terms (gespmm_gatv2_score_backward_x16): ``x_seg`` [S, H, F] and ``x_ind`` [T, H, F] both
+    ``torch.float16`` or both ``torch.bfloat16``, ``grad_score`` f32[nnz, H] and ``att`` f32[H, F]. ``grad_x`` comes back in the operands'
+    dtype — the fp32 chain of ``gatv2_score_backward`` on the widened operands, rounded ONCE to nearest even — and ``att_part`` (with
+    ``want_att_part``) stays f32[S, H, F] with that call's bits. ``out``: the 16-bit [S, H, F] tensor for grad_x, or the pair ``(grad_x,
+    att_part)``. A 16-bit ``att`` or ``grad_score``, fp32 node terms and mixed 16-bit dtypes raise TypeError."""
+    out_x, out_a = out if isinstance(out, (tuple, list)) and len(out) == 2 else (out, None)
+    x16 = _gatv2_typed_x16((("ptr", ptr), ("ind", ind), ("order", order)), (("x_seg", x_seg), ("x_ind", x_ind), ("out", out_x)),
+                           (("grad_score", grad_score), ("att", att), ("out[1]", out_a)))
+    for name, t in (("ptr", ptr), ("ind", ind), ("grad_score", grad_score), ("x_ind", x_ind), ("att", att)):
+        if t is None:
+            raise TypeError("%s must be a torch.Tensor" % name)
+    slope = _gatv2_slope(negative_slope)
+    if x_seg.dim() != 3 or x_ind.dim() != 3 or x_seg.shape[1] < 1:
+        raise ValueError("x_seg and x_ind must be [rows, H, F] with at least one head")
+    S, H, F = x_seg.shape
+    T = x_ind.shape[0]
+    if tuple(x_ind.shape[1:]) != (H, F):
+        raise ValueError("x_seg %s and x_ind %s must have the same heads and columns" % (tuple(x_seg.shape), tuple(x_ind.shape)))
+    if tuple(att.shape) != (H, F):
+        raise ValueError("att must be f32[%d, %d], got %s" % (H, F, tuple(att.shape)))
+    if ptr.dim() != 1 or ptr.numel() != S + 1:
+        raise ValueError("ptr must be a vector of x_seg.size(0) + 1 entries")
+    if ind.dim() != 1:
+        raise ValueError("ind must be a vector")
+    nnz = ind.numel()
+    if tuple(grad_score.shape) != (nnz, H):
+        raise ValueError("grad_score must be f32[%d, %d], got %s" % (nnz, H, tuple(grad_score.shape)))
+    if order is not None and tuple(order.shape) != (nnz,):
+        raise ValueError("order must be a vector of %d entries" % nnz)
+    if out_a is not None and not want_att_part:
+        raise ValueError("out is a pair only with want_att_part")
+    for name, t in (("out", out_x), ("out[1]", out_a)):
+        if t is not None and tuple(t.shape) != (S, H, F):
+            raise ValueError("%s must be [%d, %d, %d]" % (name, S, H, F))
+    dev = x_seg.device
+    _gatv2_shaped((("ptr", ptr), ("ind", ind), ("order", order), ("grad_score", grad_score), ("x_seg", x_seg), ("x_ind", x_ind),
+                   ("att", att), ("out", out_x), ("out[1]", out_a)), dev)
+    if out_x is None:
+        out_x = torch.empty((S, H, F), dtype=x_seg.dtype, device=dev)
+    if want_att_part and out_a is None:
+        out_a = torch.empty((S, H, F), dtype=torch.float32, device=dev)
+    if out_x.numel() == 0:  # (results of no words have no address to hand over)
+        return (out_x, out_a) if want_att_part else out_x
+    with _on_device(dev):
+        rc = lib.gespmm_gatv2_score_backward_x16(_ptr(ptr), _ptr(ind), _ptr(order) if order is not None else None, _ptr(grad_score),
+                                                 _ptr(x_seg), _ptr(x_ind), _ptr(att), _ptr(out_x), _ptr(out_a) if want_att_part else None,
+                                                 x16, S, T, H, F, nnz, slope, _stream(dev))
+    check(rc, "gespmm_gatv2_score_backward_x16")
     return (out_x, out_a) if want_att_part else out_x
 

@@ -910,6 +910,42 @@ int gespmm_gatv2_score_backward_f32(const int32_t* ptr, const int32_t* ind, cons
 int gespmm_describe_gatv2_score(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align, char* out,
                                 int64_t capacity);
 /*
+ * The GATv2 edge score and its gradients on 16-bit node operands (new symbols of 0.5). xl, xr, x_seg, x_ind and grad_x are IEEE fp16 or
+ * bfloat16 (dtype: GESPMM_X16_F16 / GESPMM_X16_BF16, one type per call); att, grad_score, score and att_part stay fp32 — att is a
+ * parameter of H F words whose gradient is a sum over nodes, and everything edge-sized is fp32 in this library. The arithmetic is that
+ * of the fp32 pair above, unchanged: every 16-bit element is widened exactly at its use (subnormals included),
+ *
+ *     t = fl32(widen(xl[row(p), h, f]) + widen(xr[col(p), h, f]))                      ONE fp32 add; the leaky branch is t >= 0
+ *
+ * the forward is the pinned lane chain acc = fmaf(att_j, leaky(t_j), acc) over j = l V + i + t W V and the xor butterfly (a lane past
+ * the slice contributes fmaf(0, 0, 0)), the backward ONE fp32 fmaf chain per output word in segment order with m = t >= 0 ? att :
+ * fl(att slope). grad_x is rounded ONCE, at the store: to nearest even, overflow to +-inf, NaN stays NaN. No packed-fp16 arithmetic, no
+ * dot2. So att_part has the bits of gespmm_gatv2_score_backward_f32 on the widened operands, grad_x is that call's grad_x rounded once,
+ * and score has the bits of gespmm_gatv2_score_f32 on the widened operands wherever the two describe calls answer the same (V, W).
+ * Forward geometry (gespmm_describe_gatv2_score_x16): V counts ELEMENTS — 8 / 4 / 2 / 1, a 16 / 8 / 4 / 2-byte load of xl and xr, with
+ * att's V floats at the same positions in loads of at most 16 bytes — and is the largest value that divides F, whose 2 V bytes divide
+ * the addresses of xl and xr and whose min(4 V, 16) bytes divide the address of att; W and epw follow the rule of
+ * gespmm_describe_sddmm_heads_x16 at width F. The bits depend on (V, W) alone. Backward geometry: the row walk at width H F with V
+ * elements per lane under the same rule on x_seg, x_ind, grad_x (2 V bytes) and att, att_part (min(4 V, 16) bytes) — 16-byte vectors
+ * when F % 8 == 0 and every dense operand is 16-byte aligned, V = 1 for any F and any 2-byte aligned address; no vector spans two
+ * heads; geometry leaves no trace in the bits. There is no long-row pass.
+ * Checks, in this order: a dtype that is neither code -> GESPMM_EINVAL; then the ladder of the fp32 pair — sizes that make no sense
+ * (and a NaN or infinite slope) -> GESPMM_EINVAL; S, nnz, nnz H, S H F or T H F > 2^31 - 4097 -> GESPMM_ERANGE (32-bit ELEMENT
+ * positions); forward: nnz == 0 -> 0 without looking at pointers, F == 0 zero-fills score; backward: nnz == 0 or F == 0 looks at the
+ * results alone and zero-fills them; NULL (order and att_part may be NULL) -> GESPMM_EINVAL; a 16-bit operand not 2-byte aligned, or
+ * any other pointer not 4-byte aligned -> GESPMM_EALIGN. No atomics, no workspace, no allocation, no host synchronisation: capturable.
+ * Results must not overlap an input.
+ */
+int gespmm_gatv2_score_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att, float* score,
+                           int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gatv2_score_backward_x16(const int32_t* ptr, const int32_t* ind, const int32_t* order, const float* grad_score,
+                                    const void* x_seg, const void* x_ind, const float* att, void* grad_x, float* att_part, int dtype,
+                                    int64_t S, int64_t T, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+/* Host only: what gespmm_gatv2_score_x16 would launch, in the words of gespmm_describe_gatv2_score. xl_align, xr_align: largest power
+ * of two (>= 2) dividing the operand's address; att_align: >= 4. Returns the length written or a GESPMM_E* code. */
+int gespmm_describe_gatv2_score_x16(int64_t M, int64_t nnz, int64_t H, int64_t F, int xl_align, int xr_align, int att_align, char* out,
+                                    int64_t capacity);
+/*
  * Fused scaled dot-product attention over the entries of a pattern (the attention of a graph transformer: PyG's TransformerConv, UniMP)
  * and its backward, with NOTHING of size nnz but the index arrays (new symbols of 0.5). q [M x H x F] is the aggregating node's term
  * (the row of an entry), k and v [K x H x F] the neighbour's (the column); out and grad_out [M x H x F], stats [M x H x 2], delta
