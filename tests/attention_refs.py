@@ -5,7 +5,8 @@ Moved here from the GPU test files, arguments now host arrays instead of the fil
 ``gat_aggregate_float64`` (test_gpu_gat_aggregate.py), ``gat_backward_float64`` (test_gpu_gat_backward.py and, with the dropout mask,
 test_gpu_edge_dropout.py: the two were one function but for ``keep``), ``gatv2_float64`` (test_gpu_gatv2_score.py), and the rule those
 files wrote inline, ``bound_ratio``: |got - ref| <= 1e-4 max(|ref|, sum |terms|). Re-exported from the host test modules that own
-them: the derived tolerances of the edge softmax and of the dot-product attention, the GATv2 restatement, the max-arg chains."""
+them: the derived tolerances of the edge softmax, of the dot-product attention and of the fused GATv2 attention (its ``check_all``,
+restatement and geometry), the GATv2 restatement, the max-arg chains."""
 import numpy as np
 
 from max_arg_ref import max_arg_forward, max_backward, tied_words  # noqa: F401
@@ -18,6 +19,9 @@ from test_edge_dropout_host import restate as dropout_bits  # noqa: F401
 from test_edge_softmax_host import ref_backward as softmax_ref_backward  # noqa: F401
 from test_edge_softmax_host import ref_forward as softmax_ref_forward  # noqa: F401
 from test_edge_softmax_host import worst_ratio as softmax_worst_ratio  # noqa: F401
+from test_gatv2_attention_host import check_all as gatv2_attention_check_all  # noqa: F401
+from test_gatv2_attention_host import geometry as gatv2_attention_geometry  # noqa: F401
+from test_gatv2_attention_host import restate_all as gatv2_attention_restate_all  # noqa: F401
 from test_gatv2_host import restate_backward as gatv2_restate_backward
 from test_gatv2_host import restate_score as gatv2_restate_score
 from test_gatv2_host import worst_ratio as gatv2_worst_ratio  # noqa: F401

@@ -128,7 +128,39 @@ def reach(family, L, seed=None):
         for name, S in (("forward", "M"), ("backward", "K")):
             got = [L.max_arg_route(c["G"][S], c["G"]["nnz"], c["H"] * c["F"], x, x) for c, x in zip(cases, a)]
             geo(name, [g for g in got if g is not None])
+    elif family == "gatv2_attention":
+        pairs = set()
+        for c in live:
+            a = fz.align_of(c["offset"])
+            V, W = refs.gatv2_attention_geometry(c["F"], a)
+            assert L.describe_gatv2_attention(c["G"]["M"], c["G"]["K"], c["H"], c["F"], c["G"]["nnz"], a, a, a) == {"V": V, "W": W, "supported": True}
+            pairs.add((V, W))
+        r["V"], r["W"] = {p[0] for p in pairs}, {p[1] for p in pairs}
+        r["p"] = {c["p"] for c in cases}
+    elif family == "gatv2_x16":
+        # the first pass of the sweep: 16-bit and fp32 operands at the case's offset (the second, 2 bytes further, is V = 1 throughout)
+        got = [L.describe_gatv2_score(c["G"]["M"], c["G"]["nnz"], c["H"], c["F"], *(fz.align_of(c["offset"]),) * 3, x16=True) for c in live]
+        r["score V"], r["score W"] = {d["V"] for d in got}, {d["W"] for d in got}
+        bwd = {_bwd_shape_x16(c["H"], c["F"], *fz.x16_aligns(c["offset"])) for c in live}
+        r["backward V"], r["backward W"] = {b[0] for b in bwd}, {b[1] for b in bwd}
+        assert {_bwd_shape_x16(c["H"], c["F"], *fz.x16_aligns(c["offset"], 2))[0] for c in live} == {1}
     return r
+
+
+def _bwd_shape_x16(H, F, x_align, f_align):
+    """(V, W) of gespmm_gatv2_score_backward_x16's launch, restated (no describe call covers the backward):
+    * V — ``gatv2_score_x16_vec`` (gespmm_amd/csrc/gatv2_score_x16.hip:396-400): the largest of 8, 4, 2, 1 ELEMENTS that divides F, whose
+      2 V bytes divide the least aligned of x_seg, x_ind and grad_x and whose min(4 V, 16) bytes divide the less aligned of att and
+      att_part; the entry passes those two alignments, capped at 16 (gespmm_amd/csrc/capi.cpp:1582-1586);
+    * W — ``launch_gatv2_score_backward_x16`` (gatv2_score_x16.hip:422-424): the smallest power of two in 4 .. 64 that is no less than the
+      H F / V lanes a row of H F elements needs."""
+    V = 8
+    while V > 1 and (F % V or x_align % (2 * V) or min(f_align, 16) % min(4 * V, 16)):
+        V //= 2
+    need, W = H * F // V, 4
+    while W < 64 and W < need:
+        W *= 2
+    return V, W
 
 
 def wanted(family):
@@ -178,6 +210,14 @@ def wanted(family):
 
         for name in ("forward", "backward"):
             w[name + " V"], w[name + " S"], w[name + " W"] = ({t[i] for t in BUILT} for i in range(3))
+    elif family == "gatv2_attention":
+        # every V and every W on its own, as for the dot attention (the geometry is the same rule)
+        w.update({"V": {1, 2, 4}, "W": POW2, "p": set(fz.PS)})
+    elif family == "gatv2_x16":
+        # forward: at two bytes an element W = 64 would need a width above 512 (as the x16 SDDMM). V = 4 comes from F = 100 alone and V = 8
+        # from F in {8, 32, 64, 512}, both at offset 0: an fp32 att 8 bytes off allows V = 2, 4 bytes off V = 1. The backward's W covers
+        # H F / V lanes: every W in 4 .. 64 has widths behind it.
+        w.update({"score V": {1, 2, 4, 8}, "score W": POW2 - {64}, "backward V": {1, 2, 4, 8}, "backward W": POW2})
     return w
 
 
@@ -365,6 +405,68 @@ def test_dot_attention_comparison_rejects_a_lost_entry():
         assert ratios[name] > 1, (name, ratios)
 
 
+def test_gatv2_attention_restatement_of_every_case_stays_inside_the_tolerance(pkg):
+    """The reference alone, no GPU: the fp32 restatement of the three kernels' chains (test_gatv2_attention_host.restate_all) at each
+    case's own (V, W), slope and p — the dropout mask from the built library's ``keep_mask`` — against the float64 reference through
+    ``check_all``: <= 1.0 in every result. The derived tolerance was written for rows of at most 300 entries, four heads and aligned
+    operands; this holds it at hubs of 4097 entries, K = 1, 33 heads and V = 1, 2. No case is left out: all 24 hold at most
+    nnz H F = 2^22 words (CAP) and the list runs in well under a minute."""
+    worst = {}
+    for c in fz.family_cases("gatv2_attention"):
+        G, H, F = c["G"], c["H"], c["F"]
+        assert G["nnz"] * H * F <= fz.CAP
+        x = fz.gatv2_attention_inputs(c)
+        V, W = refs.gatv2_attention_geometry(F, fz.align_of(c["offset"]))
+        got, keep, ks = refs.gatv2_attention_restate_all(G, x, c["slope"], V, W, p=c["p"] or None)
+        assert (keep is None) == (not c["p"])
+        r = refs.gatv2_attention_check_all(G, x, c["slope"], got, keep, ks, what=fz.what("gatv2_attention", c))
+        assert max(r.values()) <= 1.0, (fz.what("gatv2_attention", c), r)
+        worst = {k: max(v, worst.get(k, 0.0)) for k, v in r.items()}
+    print("gatv2_attention restatement, worst error / tolerance over the 24 cases: %s" % worst)
+
+
+def test_gatv2_attention_comparison_rejects_a_lost_entry():
+    """The full float64 result against the reference of the pattern without the entry of the largest softmax share of head 0 in the
+    longest row, at slope 0.2 (without a slope grad_xl is rounding alone): out, l, grad_xl, att_part and grad_xr must land outside.
+    ``delta`` and ``m`` do not reject, by construction: delta's reference is <grad_out, out> of the RESULT's own out, whatever entries
+    made it, and m moves only if the lost entry held the row's maximum."""
+    import test_gatv2_attention_host as v2a
+
+    c = _short_case("gatv2_attention")
+    G, slope = c["G"], 0.2
+    x = fz.gatv2_attention_inputs(c)
+    f = v2a.ref_forward(G, x, slope)
+    stats = np.stack((f["m"], f["l"]), -1).astype(np.float32)
+    out = f["out"].astype(np.float32)
+    b = v2a.ref_backward(G, x, slope, stats, out)
+    got = {"out": out, "stats": stats, "delta": b["delta"].astype(np.float32), "grad_xl": b["grad_xl"].astype(np.float32),
+           "att_part": b["att_part"].astype(np.float32), "grad_xr": b["grad_xr"].astype(np.float32)}
+    assert max(refs.gatv2_attention_check_all(G, x, slope, got, what="float64 itself").values()) <= 1
+    r, e = _longest_row(G)
+    lost = int(e[np.argmax(f["a"][e, 0])])
+    ratios = refs.gatv2_attention_check_all(_without(G, lost), x, slope, got, what="one entry lost")
+    for name in ("out", "l", "grad_xl", "att_part", "grad_xr"):
+        assert ratios[name] > 1, (name, ratios)
+
+
+def test_gatv2_x16_comparison_rejects_the_other_type():
+    """Every backward comparison of the gatv2_x16 family is on bits, and the fp32 kernels it compares with are held to float64 by the
+    gatv2 family (rejection: test_gatv2_comparison_rejects_a_lost_entry_and_a_lost_term). What is left is the type: a kernel that
+    widened bf16 operands by fp16's rule must put the score outside 1e-4 max(|ref|, sum |terms|) (test_gatv2_x16_host's pattern)."""
+    from gatv2_x16_cases import narrow
+
+    c = _short_case("gatv2_x16", need=1)
+    G = c["G"]
+    o = fz.gatv2_inputs(c)
+    (xl16, xl_w), (xr16, xr_w) = narrow(o["xl"], torch.bfloat16), narrow(o["xr"], torch.bfloat16)
+    ref, terms = refs.gatv2_restate_score(G["rowptr"], G["colind"], xl_w, xr_w, o["att"], c["slope"])
+    assert refs.gatv2_worst_ratio(ref.astype(np.float32), ref, terms, "score") <= 1
+    as_fp16 = [t.view(torch.float16).float().numpy() for t in (xl16, xr16)]
+    assert all(np.isfinite(a).all() for a in as_fp16)
+    wrong, _ = refs.gatv2_restate_score(G["rowptr"], G["colind"], as_fp16[0], as_fp16[1], o["att"], c["slope"])
+    assert refs.gatv2_worst_ratio(wrong.astype(np.float32), ref, terms, "score") > 1
+
+
 def test_max_arg_comparison_rejects_a_lost_entry():
     c = _short_case("max_arg")
     G, N = c["G"], c["H"] * c["F"]
@@ -504,3 +606,7 @@ def test_the_moved_references_give_what_the_private_helpers_gave():
     assert refs.gatv2_worst_ratio is v2.worst_ratio and refs.dot_ref_forward is dot.ref_forward and refs.dot_ref_backward is dot.ref_backward
     assert refs.dot_check_all is dot.check_all and refs.max_arg_forward is max_arg_ref.max_arg_forward
     assert refs.max_backward is max_arg_ref.max_backward
+    import test_gatv2_attention_host as v2a
+
+    assert refs.gatv2_attention_check_all is v2a.check_all and refs.gatv2_attention_restate_all is v2a.restate_all
+    assert refs.gatv2_attention_geometry is v2a.geometry

@@ -29,10 +29,11 @@ SLOPES = (None, 0.2)
 PS = (0.0, 0.25, 0.6)
 CAP = 1 << 22
 N_CASES = 24
-FAMILIES = ("heads", "sddmm", "softmax", "aggregate", "gatv2", "dropout", "dot", "max_arg")
+FAMILIES = ("heads", "sddmm", "softmax", "aggregate", "gatv2", "dropout", "dot", "max_arg", "gatv2_attention", "gatv2_x16")
 # one seed per family, chosen on the CPU so that the reach conditions of tests/test_attention_fuzz_host.py hold
 FAMILY_SEEDS = {"heads": 20261227, "sddmm": 20262022, "softmax": 20263020, "aggregate": 20264032, "gatv2": 20265021,
-                "dropout": 20266023, "dot": 20267022, "max_arg": 20268022}
+                "dropout": 20266023, "dot": 20267022, "max_arg": 20268022,
+                "gatv2_attention": 20269000, "gatv2_x16": 20270024}
 GUARD = 64
 NAN = float("nan")
 WORST = {}
@@ -149,6 +150,18 @@ def gatv2_inputs(c):
     rng = np.random.RandomState(c["seed"])
     return {"xl": uniform(rng, (G["M"], H, F), 2), "xr": uniform(rng, (G["K"], H, F), 2), "att": uniform(rng, (H, F), 4),
             "gs": uniform(rng, (G["nnz"], H), 4)}
+
+
+def gatv2_attention_inputs(c):
+    """xl, xr, grad_out uniform in +-1, att uniform in +-2 narrowed by min(1, 8 / F) (a score of F terms stays of the order of one, as
+    test_gatv2_attention_host.draw_inputs keeps it); no fl(xl + xr) of an entry is exactly 0 (the branch t >= 0 has no tie)."""
+    G, H, F = c["G"], c["H"], c["F"]
+    rng = np.random.RandomState(c["seed"])
+    x = {"xl": uniform(rng, (G["M"], H, F), 2), "xr": uniform(rng, (G["K"], H, F), 2),
+         "att": (uniform(rng, (H, F), 4) * np.float32(min(1.0, 8.0 / F))).astype(np.float32), "go": uniform(rng, (G["M"], H, F), 2)}
+    t = (x["xl"][G["rows"]] + x["xr"][G["colind"]]).astype(np.float32)
+    assert not (t == 0).any() and np.isfinite(t).all(), "a sum fl(xl + xr) is exactly 0"
+    return x
 
 
 def keep_of(G, H, p):
@@ -689,3 +702,145 @@ def test_max_arg_and_backward(pkg):
             assert np.array_equal(gB.cpu().numpy().view(np.uint32), want_g.view(np.uint32)), "%s %s: grad_B" % (msg, kind)
             _same(backward(), gB, "%s %s: grad_B, second run" % (msg, kind))
     print("max_arg: %d cases, every comparison on bits" % N_CASES)
+
+
+# ------------------------------------------------------------------------------------------------------- 9. fused GATv2 attention
+
+RESULTS_V2 = ("out", "stats", "delta", "grad_xl", "att_part", "grad_xr")
+
+
+def _gatv2_attention_run(g, x, offset, slope, drop, want=True):
+    """The three launches, every dense operand and result ``offset`` bytes off a 16-byte boundary (stats: 8 or 0) -> (results, placed
+    operands). want=False: the row pass without att_part; its buffer stays as it was poisoned."""
+    from gespmm_amd import attention
+
+    xl, xr, att, go = (_place(_dev(x[n]), offset) for n in ("xl", "xr", "att", "go"))
+    M, H, F = x["xl"].shape
+    K = x["xr"].shape[0]
+    o = {"out": Out((M, H, F), offset), "stats": Out((M, H, 2), 8 if offset == 8 else 0), "delta": Out((M, H), offset),
+         "grad_xl": Out((M, H, F), offset), "att_part": Out((M, H, F), offset), "grad_xr": Out((K, H, F), offset)}
+    attention.gatv2_attention(g["rowptr"], g["colind"], xl, xr, att, negative_slope=slope, dropout=drop, out=o["out"].t, stats=o["stats"].t)
+    row = (o["delta"].t, o["grad_xl"].t, o["att_part"].t)
+    attention.gatv2_attention_backward_row(g["rowptr"], g["colind"], xl, xr, att, o["stats"].t, o["out"].t, go, negative_slope=slope,
+                                           dropout=drop, want_att_part=want, results=row if want else row[:2])
+    attention.gatv2_attention_backward_col(g["colptr"], g["rowind"], xl, xr, att, o["stats"].t, o["delta"].t, go, negative_slope=slope,
+                                           dropout=drop, result=o["grad_xr"].t)
+    return o, (xl, xr, att)
+
+
+def test_gatv2_attention(pkg):
+    """gatv2_attention and its two backward passes inside the derived tolerances of test_gatv2_attention_host.py, with and without
+    dropout; m of the stats the bits of the row maximum of sddmm.gatv2_score at the same alignment; a single-entry row its neighbour's
+    xr; a head the bits of the single-head call on its slices; the row pass without att_part the bits of the one with it."""
+    from gespmm_amd import sddmm
+
+    for c in family_cases("gatv2_attention"):
+        G, H, F, off, slope, p, msg = c["G"], c["H"], c["F"], c["offset"], c["slope"], c["p"], what("gatv2_attention", c)
+        g = _graph(G)
+        x = gatv2_attention_inputs(c)
+        keep = ks = drop = None
+        if p:
+            (keep, ks), drop = keep_of(G, H, p), (p, _seed())
+        o, (xl, xr, att) = _gatv2_attention_run(g, x, off, slope, drop)
+        got = {n: v.check("%s: %s" % (msg, n)) for n, v in o.items()}
+        h = {n: t.cpu().numpy() for n, t in got.items()}
+        r = refs.gatv2_attention_check_all(G, x, slope, h, keep, ks, what=msg)
+        _ratio("gatv2_attention", max(r.values()), "%s: %r" % (msg, r))
+        empty_r, empty_c = G["degs"] == 0, np.diff(G["colptr"]) == 0
+        for n in ("out", "stats", "delta", "grad_xl", "att_part"):
+            _plus_zero(got[n], empty_r, "%s: %s" % (msg, n))
+        _plus_zero(got["grad_xr"], empty_c, msg + ": grad_xr")
+        # ---- m: the row maximum of the score kernel's bits, on the very operands (one alignment: one (V, W), one lane order)
+        score = sddmm.gatv2_score(g["rowptr"], g["colind"], xl, xr, att, negative_slope=slope)
+        top = torch.full((G["M"], H), -float("inf"), device="cuda")
+        if G["nnz"]:
+            top = top.scatter_reduce(0, g["rows"].long()[:, None].expand(-1, H), score, "amax")
+        top[_dev(empty_r)] = 0.0
+        _same(got["stats"][:, :, 0].contiguous(), top, msg + ": m is the row maximum of gatv2_score")
+        if not p:
+            one = np.nonzero(G["degs"] == 1)[0]
+            assert h["out"][one].tobytes() == x["xr"][G["colind"][G["rowptr"][one]]].tobytes(), msg + ": a single-entry row is its neighbour's xr"
+            assert np.all(h["stats"][one, :, 1] == 1.0), msg + ": a single-entry row has l = 1"
+        again, _ = _gatv2_attention_run(g, x, off, slope, drop)
+        for n in got:
+            _same(again[n].check("%s: %s, second run" % (msg, n)), got[n], "%s: %s, second run" % (msg, n))
+        for hd in sorted({0, H - 1}) if H > 1 and not p else ():  # (with dropout the single-head call would draw head 0's mask)
+            xs = {n: np.ascontiguousarray(x[n][:, hd:hd + 1]) for n in ("xl", "xr", "go")}
+            xs["att"] = np.ascontiguousarray(x["att"][hd:hd + 1])
+            single, _ = _gatv2_attention_run(g, xs, off, slope, None)
+            for n in got:
+                _same(got[n][:, hd:hd + 1].contiguous(), single[n].t, "%s: head %d of %s is the single-head call" % (msg, hd, n))
+        if c["index"] % 2:
+            bare, _ = _gatv2_attention_run(g, x, off, slope, drop, want=False)
+            for n in ("delta", "grad_xl"):
+                _same(bare[n].check("%s: %s without att_part" % (msg, n)), got[n], "%s: %s without att_part" % (msg, n))
+            assert bare["att_part"]._untouched(bare["att_part"].buf), msg + ": want_att_part=False wrote into the poisoned buffer"
+    _report("gatv2_attention")
+
+
+# ----------------------------------------------------------------------------------------------- 10. GATv2 score on 16-bit operands
+
+def x16_aligns(offset, extra=0):
+    """(alignment of the 16-bit operands, alignment of the fp32 ones) in bytes: both ``offset`` bytes off a 16-byte boundary, the 16-bit
+    ones ``extra`` (0 or 2) bytes further."""
+    return (2 if extra else align_of(offset)), align_of(offset)
+
+
+def test_gatv2_x16(pkg):
+    """gatv2_score_x16 inside 1e-4 max(|ref|, sum |terms|) of the float64 restatement on the widened operands and on the bits of
+    sddmm.gatv2_score wherever both describe calls answer one (V, W); both passes of gatv2_score_backward_x16 on the bits of the fp32
+    backward on the widened operands (grad_x narrowed once), again with the 16-bit operands 2 bytes further off (V = 1)."""
+    from gatv2_x16_cases import narrow
+    from gespmm_amd import _lib, sddmm
+
+    shared = 0
+    for c in family_cases("gatv2_x16"):
+        G, H, F, off, slope = c["G"], c["H"], c["F"], c["offset"], c["slope"]
+        g = _graph(G)
+        o = gatv2_inputs(c)
+        att, gs = _place(_dev(o["att"]), off), _place(_dev(o["gs"]), off)
+        empty_r, empty_c = G["degs"] == 0, np.diff(G["colptr"]) == 0
+        for dtype in (torch.bfloat16, torch.float16):
+            msg = "%s %s" % (what("gatv2_x16", c), dtype)
+            (xl16, xl_w), (xr16, xr_w) = narrow(o["xl"], dtype), narrow(o["xr"], dtype)
+            ref, terms = refs.gatv2_restate_score(G["rowptr"], G["colind"], xl_w, xr_w, o["att"], slope)
+            # ---- the fp32 kernels on the exact widening, operands at the same offset
+            wl, wr = _place(_dev(xl_w), off), _place(_dev(xr_w), off)
+            score32 = sddmm.gatv2_score(g["rowptr"], g["colind"], wl, wr, att, negative_slope=slope)
+            gxl32, part32 = sddmm.gatv2_score_backward(g["rowptr"], g["colind"], gs, wl, wr, att, negative_slope=slope, want_att_part=True)
+            gxr32 = sddmm.gatv2_score_backward(g["colptr"], g["rowind"], gs, wr, wl, att, negative_slope=slope, order=g["order"])
+            want = (gxl32.to(dtype), part32, gxr32.to(dtype))
+            for extra in (0, 2):
+                m2 = "%s, 16-bit operands %d bytes off" % (msg, off + extra)
+                xl, xr = _place(xl16.cuda(), off + extra), _place(xr16.cuda(), off + extra)
+                assert xl.data_ptr() % 16 == off + extra and att.data_ptr() % 16 == off
+
+                def run():
+                    outs = [Out((G["nnz"], H), off), Out((G["M"], H, F), off + extra, dtype), Out((G["M"], H, F), off),
+                            Out((G["K"], H, F), off + extra, dtype)]
+                    sddmm.gatv2_score_x16(g["rowptr"], g["colind"], xl, xr, att, negative_slope=slope, out=outs[0].t)
+                    sddmm.gatv2_score_backward_x16(g["rowptr"], g["colind"], gs, xl, xr, att, negative_slope=slope, want_att_part=True,
+                                                   out=(outs[1].t, outs[2].t))
+                    sddmm.gatv2_score_backward_x16(g["colptr"], g["rowind"], gs, xr, xl, att, negative_slope=slope, order=g["order"],
+                                                   out=outs[3].t)
+                    return [t.check("%s: %s" % (m2, n)) for t, n in zip(outs, ("score", "grad_xl", "att_part", "grad_xr"))]
+
+                score, gxl, part, gxr = run()
+                _ratio("gatv2_x16", refs.gatv2_worst_ratio(score.cpu().numpy(), ref, terms, "score"), m2 + ": score")
+                if G["nnz"]:
+                    xa, fa = x16_aligns(off, extra)
+                    d16 = _lib.describe_gatv2_score(G["M"], G["nnz"], H, F, xa, xa, fa, x16=True)
+                    d32 = _lib.describe_gatv2_score(G["M"], G["nnz"], H, F, fa, fa, fa)
+                    if (d16["V"], d16["W"]) == (d32["V"], d32["W"]):
+                        _same(score, score32, m2 + ": score against the fp32 kernel at one (V, W)")
+                        shared += not extra
+                for t, w, n in zip((gxl, part, gxr), want, ("grad_xl", "att_part", "grad_xr")):
+                    _same(t, w, "%s: %s against the fp32 backward on the widened operands" % (m2, n))
+                _plus_zero(gxl, empty_r, m2 + ": grad_xl")
+                _plus_zero(part, empty_r, m2 + ": att_part")
+                _plus_zero(gxr, empty_c, m2 + ": grad_xr")
+                if not extra:
+                    for u, v, n in zip(run(), (score, gxl, part, gxr), ("score", "grad_xl", "att_part", "grad_xr")):
+                        _same(u, v, "%s: %s, second run" % (m2, n))
+    assert shared > 0, "no case compared the 16-bit score with the fp32 kernel's bits"
+    _report("gatv2_x16")

@@ -15,6 +15,11 @@ b. The kernels that form ``int`` word positions (sddmm_heads.h and sddmm_edge.h 
    dot_attention.hip, gat_backward.hip) run in regime A, 5.4 GB an array, and in regime B, the largest M and K the entry accepts —
    found here by calling the entry with null pointers: K is taken, K + 1 answers GESPMM_ERANGE. The last window of regime B ends
    with the last node: its words are the highest positions these kernels may ever form.
+c. The two files that landed after that audit and form the same ``int`` positions behind the same checks: the fused GATv2 attention
+   (gatv2_attention.hip; regimes A and B at p = 0 and 0.25, and once with every dense operand 4 bytes off a 16-byte boundary: the
+   V = 1 kernels) and the GATv2 score on fp16 / bf16 operands (gatv2_score_x16.hip), whose limit counts ELEMENTS — regime A has byte
+   2^31 inside every 16-bit operand, regime B ends them just below byte 2^32 — with the fp32 kernels on the exact widening as the
+   oracle over the WHOLE arrays, bit for bit.
 
 Sum-type ops get small integers of the word position (lo.b_at, lo.k_at: a value differs from every alias 2^31 or 2^32 bytes away)
 and must EQUAL an int64 closed form on every word of every window; float ops get seeded random values and the float64 references
@@ -22,9 +27,9 @@ and tolerances of their own tests, on 512-row sub-patterns of the marked, first 
 e). Every result goes into a NaN-prefilled tensor and must hold no NaN anywhere. Dense operands are filled in row chunks (integer
 temporaries of 256 MB) or in place. No tolerance is new.
 
-On the MI355X the module takes 55 s for 66 tests (the slowest 4.8 s, 54 below 2 s; single times move by seconds with the
-allocation and release of tens of GB, the kernels take milliseconds) and peaks at 65.6 GiB of device memory (dot attention in
-regime B: eight arrays of 8 GB)."""
+On the MI355X the module takes 84 s for 83 tests (the slowest 6.3 s; single times move by seconds with the allocation and release
+of tens of GB, the kernels take milliseconds) and peaks at 65.6 GiB of device memory (dot attention in regime B: eight arrays of
+8 GB)."""
 import numpy as np
 import pytest
 import torch
@@ -469,3 +474,152 @@ def test_gat_backward_el_and_er(pkg, H, F, regime, p):
         assert ok_el and ok_er, ("rows %d .. %d" % (s.r0, s.r1), re_, rr_)
         worst = [max(worst[0], re_), max(worst[1], rr_)]
     print("gat backward H=%d F=%d regime %s p=%g: worst error / bound grad_el %.3f grad_er %.3f" % (H, F, regime, p, *worst))
+
+
+# ---- c. the fused GATv2 attention (gatv2_attention.hip) and the 16-bit GATv2 score (gatv2_score_x16.hip): int positions, as section b ----
+
+def _off(shape, offset, gen=None, lo_=0.0, hi=1.0):
+    """A contiguous fp32 tensor carved from ONE allocation, its first byte ``offset`` bytes past a 16-byte boundary (0: the allocation
+    itself) — seeded uniform values drawn in place, or NaN (test_gpu_gatv2_attention._carved at node size)."""
+    n = int(np.prod(shape))
+    buf = torch.empty(n + 4, dtype=torch.float32, device=DEV)
+    assert buf.data_ptr() % 16 == 0
+    t = buf[offset // 4:offset // 4 + n].view(shape)
+    assert t.data_ptr() % 16 == offset and t.is_contiguous()
+    return t.uniform_(lo_, hi, generator=gen) if gen is not None else t.fill_(float("nan"))
+
+
+def _gatv2_attention_case(H, F, regime, p, offset):
+    from gespmm_amd import _lib, attention, sddmm
+    from test_dot_attention_host import ratio
+    from test_gatv2_attention_host import ref_backward, ref_forward
+
+    N, slope, gen = H * F, 0.2, _gen(26)
+    lib = _lib.lib
+    M, K = _sizes_b(N, regime, lambda m, k: lib.gespmm_gatv2_attention_f32(*[None] * 7, m, k, H, F, m * D, slope, None))
+    if regime == "B":
+        for f, n in ((lib.gespmm_gatv2_attention_backward_row_f32, 11), (lib.gespmm_gatv2_attention_backward_col_f32, 9)):
+            assert f(*[None] * n, M, K, H, F, M * D, slope, None) == EINVAL and f(*[None] * n, M, K + 1, H, F, M * D, slope, None) == ERANGE
+    _need(88)  # seven node arrays of 8 GB in regime B, the score array of the stats check, the band
+    g = _band(M)
+    rw, _ = _windows(g, N, spread=2)
+    subs = _subs(g, rw)
+    align, geo = (16, {"V": 4}) if offset == 0 else (4, {"V": 1})
+    assert _lib.describe_gatv2_attention(M, K, H, F, g.nnz, align, align, align) == dict(geo, W=8 if F == 64 else 16, supported=True)
+    xl, xr = _off((M, H, F), offset, gen, -1, 1), _off((K, H, F), offset, gen, -1, 1)
+    go = _off((M, H, F), offset, gen, 0.5, 1)
+    att = _off((H, F), offset, gen, -2, 2).mul_(min(1.0, 8.0 / F))
+    drop = (p, _seed()) if p else None
+    out, gxl, part, gxr = _off((M, H, F), offset), _off((M, H, F), offset), _off((M, H, F), offset), _off((K, H, F), offset)
+    stats, delta = _nan((M, H, 2)), _off((M, H), offset)
+    attention.gatv2_attention(g.rowptr, g.colind, xl, xr, att, negative_slope=slope, dropout=drop, out=out, stats=stats)
+    attention.gatv2_attention_backward_row(g.rowptr, g.colind, xl, xr, att, stats, out, go, negative_slope=slope, dropout=drop,
+                                           results=(delta, gxl, part))
+    attention.gatv2_attention_backward_col(g.colptr, g.rowind, xl, xr, att, stats, delta, go, negative_slope=slope, dropout=drop, result=gxr)
+    _written(out=out, stats=stats, delta=delta, grad_xl=gxl, att_part=part, grad_xr=gxr)
+    score = sddmm.gatv2_score(g.rowptr, g.colind, xl, xr, att, negative_slope=slope, out=_nan((g.nnz, H)))  # the same operands: one (V, W)
+    att_h, worst = att.cpu().numpy(), {}
+    for s in subs:
+        x = {"xl": s.row_nodes(xl), "xr": s.col_nodes(xr), "att": att_h, "go": s.row_nodes(go)}
+        keep, ks = _keep(s, H, p) if p else (None, None)
+        st, o, dl = s.row_nodes(stats), s.row_nodes(out), s.row_nodes(delta)
+        top = s.edges(score).reshape(s.M, D, H).max(1)
+        assert st[..., 0].tobytes() == top.tobytes(), "rows %d .. %d: m is not the row maximum of gatv2_score, bit for bit" % (s.r0, s.r1)
+        f = ref_forward(s.P, x, slope, keep, ks)
+        b = ref_backward(s.P, x, slope, st, o, None, keep, ks)
+        bc = ref_backward(s.P, x, slope, st, o, dl, keep, ks)
+        r = {"out": ratio(o, f["out"], f["tol_out"]), "m": ratio(st[..., 0], f["m"], f["tol_m"]), "l": ratio(st[..., 1], f["l"], f["tol_l"]),
+             "delta": ratio(dl, b["delta"], b["tol_delta"]), "grad_xl": ratio(s.row_nodes(gxl), b["grad_xl"], b["tol_grad_xl"]),
+             "att_part": ratio(s.row_nodes(part), b["att_part"], b["tol_att_part"]),
+             "grad_xr": ratio(s.full_cols(gxr), bc["grad_xr"][s.full], bc["tol_grad_xr"][s.full])}
+        assert max(r.values()) <= 1.0, ("rows %d .. %d" % (s.r0, s.r1), r)
+        worst = {k_: max(v_, worst.get(k_, 0.0)) for k_, v_ in r.items()}
+    print("gatv2 attention H=%d F=%d regime %s p=%g offset %d: worst error / tolerance %s" % (H, F, regime, p, offset, worst))
+
+
+@pytest.mark.parametrize("p", (0.0, 0.25))
+@pytest.mark.parametrize("regime", REGIMES)
+@pytest.mark.parametrize("H,F", lo.WIDTHS, ids=WIDTH_IDS)
+def test_gatv2_attention_three_launches(pkg, H, F, regime, p):
+    """gatv2_attention and its two backward passes: float64 with the tolerances of test_gatv2_attention_host.py on the sub-patterns,
+    m of the stats on the bits of the row maximum of sddmm.gatv2_score run on the whole operands."""
+    _gatv2_attention_case(H, F, regime, p, 0)
+
+
+def test_gatv2_attention_three_launches_four_bytes_off(pkg):
+    """(3, 100) at the largest sizes with every dense operand and result 4 bytes off a 16-byte boundary: the V = 1 kernels."""
+    _gatv2_attention_case(3, 100, "B", 0.0, 4)
+
+
+def _bits_equal(a, b, what):
+    """Two whole arrays on bits, 2^28 elements at a time (no temporary of the arrays' size)."""
+    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
+    view = {2: torch.int16, 4: torch.int32}[a.element_size()]
+    x, y = a.reshape(-1).view(view), b.reshape(-1).view(view)
+    for i in range(0, x.numel(), 1 << 28):
+        bad = int((x[i:i + (1 << 28)] != y[i:i + (1 << 28)]).sum())
+        assert bad == 0, "%s: %d elements differ among the elements %d .. %d" % (what, bad, i, min(i + (1 << 28), x.numel()))
+
+
+@pytest.mark.parametrize("dtype", (torch.bfloat16, torch.float16), ids=("bf16", "fp16"))
+@pytest.mark.parametrize("regime", REGIMES)
+@pytest.mark.parametrize("H,F", lo.WIDTHS, ids=WIDTH_IDS)
+def test_gatv2_score_x16_forward_and_both_backward_passes(pkg, H, F, regime, dtype):
+    """The limit counts ELEMENTS: regime A has more than 2^30 of them in every 16-bit operand (byte 2^31 inside), regime B ends just
+    below byte 2^32, and the fp32 att_part is 5.4 / 8 GB. The oracle is the fp32 backward on the exact widening over the WHOLE arrays:
+    att_part on its bits, grad_x on the bits of its result narrowed once; the score on the fp32 kernel's bits where both describe
+    calls answer one (V, W), and inside the float64 bound on the sub-patterns."""
+    from gespmm_amd import _lib, sddmm
+    from test_gatv2_host import restate_score, worst_ratio
+
+    N, slope, gen = H * F, 0.2, _gen(27)
+    lib, code = _lib.lib, (_lib.X16_BF16 if dtype == torch.bfloat16 else _lib.X16_F16)
+    M, K = _sizes_b(N, regime, lambda m, k: lib.gespmm_gatv2_score_x16(*[None] * 6, code, m, k, H, F, m * D, slope, None))
+    if regime == "B":  # the column pass: S = K segments, T = M rows
+        assert lib.gespmm_gatv2_score_backward_x16(*[None] * 9, code, K, M, H, F, M * D, slope, None) == EINVAL
+        assert lib.gespmm_gatv2_score_backward_x16(*[None] * 9, code, K + 1, M, H, F, M * D, slope, None) == ERANGE
+        assert (1 << 32) - 2 * N - 8192 <= K * N * 2 < (1 << 32), "the 16-bit K-side operands end just below byte 2^32"
+    assert M * N > (1 << 30), "byte 2^31 lies inside every 16-bit operand"
+    _need(72)
+    g = _band(M)
+    rw, _ = _windows(g, N, 2, spread=2)
+    subs = _subs(g, rw)
+    xl, xr = _uniform(gen, (M, H, F), -1, 1).to(dtype), _uniform(gen, (K, H, F), -1, 1).to(dtype)
+    att, gsc = _uniform(gen, (H, F), -2, 2), _uniform(gen, (g.nnz, H), -2, 2)
+    score = sddmm.gatv2_score_x16(g.rowptr, g.colind, xl, xr, att, negative_slope=slope, out=_nan((g.nnz, H)))
+    gxl, part = sddmm.gatv2_score_backward_x16(g.rowptr, g.colind, gsc, xl, xr, att, negative_slope=slope, want_att_part=True,
+                                               out=(_nan((M, H, F), dtype), _nan((M, H, F))))
+    gxr = sddmm.gatv2_score_backward_x16(g.colptr, g.rowind, gsc, xr, xl, att, negative_slope=slope, order=g.order32, out=_nan((K, H, F), dtype))
+    _written(score=score, grad_xl=gxl, att_part=part, grad_xr=gxr)
+    # ---- the score inside the float64 bound on the sub-patterns
+    att_h, worst = att.cpu().numpy(), 0.0
+    for s in subs:
+        xl_h, xr_h = xl[s.r0:s.r1].float().cpu().numpy(), xr[s.c0:s.c1].float().cpu().numpy()
+        ref, terms = restate_score(s.rowptr, s.colind, xl_h, xr_h, att_h, slope)
+        r = worst_ratio(s.edges(score), ref, terms, "score")
+        assert r <= 1.0, ("rows %d .. %d" % (s.r0, s.r1), r)
+        worst = max(worst, r)
+    print("gatv2 x16 H=%d F=%d regime %s %s: score worst error / bound %.4g" % (H, F, regime, dtype, worst))
+    # ---- the fp32 kernels on the exact widening, whole arrays
+    wl, wr = xl.float(), xr.float()
+    # On 16-byte aligned operands the two kernels do NOT share a lane order at these widths — (8, 64): (V, W) = (8, 4) on 16-bit operands,
+    # (4, 8) on fp32; (3, 100): (4, 8) and (4, 16) — so the score above has the float64 bound alone. With att 4 bytes off a 16-byte
+    # boundary (a tensor of H F floats: nothing node-sized is copied) both resolve to V = 1 at one W, asserted from the two describe
+    # calls, and the 16-bit score of the whole pattern must have the fp32 kernel's bits.
+    d16, d32 = _lib.describe_gatv2_score(M, g.nnz, H, F, x16=True), _lib.describe_gatv2_score(M, g.nnz, H, F)
+    assert (d16["V"], d16["W"]) == {(8, 64): (8, 4), (3, 100): (4, 8)}[(H, F)] and (d32["V"], d32["W"]) == (4, 8 if F == 64 else 16)
+    d16, d32 = _lib.describe_gatv2_score(M, g.nnz, H, F, 16, 16, 4, x16=True), _lib.describe_gatv2_score(M, g.nnz, H, F, 16, 16, 4)
+    assert (d16["V"], d16["W"]) == (d32["V"], d32["W"]) == (1, 8 if F == 64 else 16), (d16, d32)
+    att4 = _off((H, F), 4).copy_(att)
+    _bits_equal(sddmm.gatv2_score_x16(g.rowptr, g.colind, xl, xr, att4, negative_slope=slope, out=score.fill_(float("nan"))),
+                sddmm.gatv2_score(g.rowptr, g.colind, wl, wr, att4, negative_slope=slope, out=_nan((g.nnz, H))),
+                "score against the fp32 kernel at (V, W) = (1, %d)" % d16["W"])
+    _written(score=score)
+    del score
+    gxl32, part32 = sddmm.gatv2_score_backward(g.rowptr, g.colind, gsc, wl, wr, att, negative_slope=slope, want_att_part=True)
+    _bits_equal(part, part32, "att_part against the fp32 backward on the widened operands")
+    del part, part32
+    _bits_equal(gxl, gxl32.to(dtype), "grad_xl against the fp32 backward's result, narrowed once")
+    del gxl, gxl32
+    gxr32 = sddmm.gatv2_score_backward(g.colptr, g.rowind, gsc, wr, wl, att, negative_slope=slope, order=g.order32)
+    _bits_equal(gxr, gxr32.to(dtype), "grad_xr against the fp32 backward's result, narrowed once")

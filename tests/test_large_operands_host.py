@@ -9,6 +9,10 @@
   offset displaced by 2^32 and by 2^31 (modulo 2^32; at 1200-byte rows the alias lies inside another row, at another head and
   feature) and the case's comparator must reject it — exact equality for the integer ops, the op's own tolerance for the float ops
   (there the alias holds another draw of the random values). This is a requirement on the INPUTS: a value and its aliases differ.
+* Section c of the GPU module (the fused GATv2 attention; the GATv2 score on 16-bit operands, limits counted in elements): the sizes
+  on both sides of the limit through the same null-pointer calls, the windows marked at element size 2, byte 2^31 inside and byte
+  2^32 just outside every 16-bit operand, and the float comparators against a reference read through a displaced position, here
+  with node values that are a function of the GLOBAL word position (another value at every alias, as in an array of random values).
 * The band at d = 8 against a numpy transpose."""
 import numpy as np
 import pytest
@@ -67,6 +71,14 @@ def _entries(L, H, F, slope=0.2):
         "dot_attention_backward_kv": lambda m, k: lib.gespmm_dot_attention_backward_kv_f32(*[None] * 10, m, k, H, F, m * D, 0.5, None),
         "gat_backward_el": lambda m, k: lib.gespmm_gat_backward_el_f32(*[None] * 9, m, k, H, F, m * D, slope, None),
         "gat_backward_er": lambda m, k: lib.gespmm_gat_backward_er_f32(*[None] * 9, m, k, H, F, m * D, slope, None),
+        "gatv2_attention": lambda m, k: lib.gespmm_gatv2_attention_f32(*[None] * 7, m, k, H, F, m * D, slope, None),
+        "gatv2_attention_backward_row": lambda m, k: lib.gespmm_gatv2_attention_backward_row_f32(*[None] * 11, m, k, H, F, m * D, slope, None),
+        "gatv2_attention_backward_col": lambda m, k: lib.gespmm_gatv2_attention_backward_col_f32(*[None] * 9, m, k, H, F, m * D, slope, None),
+        # the 16-bit GATv2 score: the same limits, counted in ELEMENTS (the operands are half the bytes)
+        "gatv2_score_bf16": lambda m, k: lib.gespmm_gatv2_score_x16(*[None] * 6, L.X16_BF16, m, k, H, F, m * D, slope, None),
+        "gatv2_score_fp16": lambda m, k: lib.gespmm_gatv2_score_x16(*[None] * 6, L.X16_F16, m, k, H, F, m * D, slope, None),
+        "gatv2_backward_rows_bf16": lambda m, k: lib.gespmm_gatv2_score_backward_x16(*[None] * 9, L.X16_BF16, m, k, H, F, m * D, slope, None),
+        "gatv2_backward_cols_fp16": lambda m, k: lib.gespmm_gatv2_score_backward_x16(*[None] * 9, L.X16_F16, k, m, H, F, m * D, slope, None),
     }
 
 
@@ -87,6 +99,14 @@ def test_regimes_of_the_word_position_kernels(L, H, F, regime):
     nnz = M * D
     assert L.describe_dot_attention(M, K, H, F, nnz) == {"V": 4, "W": 8 if F == 64 else 16}
     assert L.describe_gatv2_score(M, nnz, H, F)["V"] == 4
+    W = 8 if F == 64 else 16
+    assert L.describe_gatv2_attention(M, K, H, F, nnz) == {"V": 4, "W": W, "supported": True}
+    assert L.describe_gatv2_attention(M, K, H, F, nnz, 4, 4, 4) == {"V": 1, "W": W, "supported": True}  # every operand 4 bytes off
+    # the 16-bit score: no lane order shared with fp32 on aligned operands at these widths; one (V, W) = (1, W) with att 4 bytes off
+    x16 = L.describe_gatv2_score(M, nnz, H, F, x16=True)
+    assert (x16["V"], x16["W"]) == ((8, 4) if F == 64 else (4, 8))
+    off = [L.describe_gatv2_score(M, nnz, H, F, 16, 16, 4, x16=x) for x in (True, False)]
+    assert [(d["V"], d["W"]) for d in off] == [(1, W), (1, W)]
     for csr in (True, False):
         for x16 in (False, True):
             assert L.describe_sddmm_heads(csr, M, nnz, H, F, x16=x16)["route"] == "kernel"
@@ -326,6 +346,147 @@ def test_float_comparators_reject_a_displaced_gather(H, F):
         bel, _, bsel, _ = gat_backward_float64(*args, x["go"], o["vk"], slope, keep, ks)
         _, ber, _, bser = gat_backward_float64(*args, o["go"], x["vk"], slope, keep, ks)
         assert not bound_ratio(f32(gel), bel, bsel)[1] and not bound_ratio(f32(ger), ber, bser)[1]
+
+
+# ---- the fused GATv2 attention and the 16-bit GATv2 score (section c of the GPU module) ------------------------------------------------
+
+@pytest.mark.parametrize("H,F,regime", CASES_B)
+def test_windows_and_bytes_of_the_16_bit_gatv2_score(H, F, regime):
+    """The limit counts elements: regime A's row counts put byte 2^31 (element 2^30) inside every 16-bit operand; regime B ends the
+    K-side operands within one row and the limit's margin (4096 elements) of byte 2^32, and nothing the entries accept reaches it. The
+    sub-patterns the score is compared on hold the rows with byte 2^31 and the last row of both sides (windows marked at elem = 2); the
+    fused attention's fp32 operands are the sizes test_windows_hold_the_marked_rows_section_b already checks at elem = 4."""
+    N = H * F
+    M, K = lo.sizes_b(N, regime)
+    _check_marks(M, K, N, 2, True)
+    for rows in (M, K):
+        assert rows * N > (1 << 30) and (1 << 31) // (2 * N) in lo.marked(rows, N, 2), "byte 2^31 lies inside the operand, its row is marked"
+        assert rows * N * 2 < (1 << 32) and lo.marked(rows, N, 2)[-1] == rows - 1
+    if regime == "B":
+        assert (1 << 32) - 2 * N - 8192 <= K * N * 2 < (1 << 32) <= (K + 1) * N * 2 + 8192
+    assert M * N * 4 > (1 << 32), "att_part (fp32, M rows) holds byte 2^32: compared whole on the device"
+
+
+def _hashed(lo_, hi, salt, H, F):
+    """A node-value function of the WORD position with values spread over [lo_, hi): what an array of seeded random values is to a
+    displaced offset — another value at every alias (float64 torch tensor)."""
+    def at(r, h, f):
+        w = torch.as_tensor(r * (H * F) + h * F + f, dtype=torch.int64)
+        return ((w * 1103515245 + salt) % (1 << 31)).to(torch.float64) / float(1 << 31) * (hi - lo_) + lo_
+
+    return at
+
+
+def _rows_of(fn, r0, r1, H, F):
+    r = torch.arange(r0, r1, dtype=torch.int64).view(-1, 1, 1)
+    return fn(r, torch.arange(H, dtype=torch.int64).view(1, H, 1), torch.arange(F, dtype=torch.int64).view(1, 1, F)).numpy().astype(np.float32)
+
+
+def _band_pattern(n):
+    """The band at d = 8 on n rows as a host pattern (the shape of a GPU sub-pattern)."""
+    from test_dot_attention_host import transpose
+
+    rowptr, colind = (t.numpy() for t in band.csr(n, D))
+    K = n + lo.LAST
+    colptr, rowind, order = transpose(rowptr, colind, K)
+    return {"M": n, "K": K, "nnz": n * D, "rowptr": rowptr, "colind": colind, "colptr": colptr, "rowind": rowind, "order": order,
+            "rows": np.repeat(np.arange(n, dtype=np.int32), D), "degs": np.full(n, D)}
+
+
+def _displaced_cases(elem):
+    """(H, F, regime, shift, side, first row): 64 rows of the pattern right behind the marked row of the operand of ``side`` — every word
+    there has its alias, ``shift`` bytes back, inside the operand."""
+    out = []
+    for H, F, regime in CASES_B:
+        N = H * F
+        M, K = lo.sizes_b(N, regime)
+        for shift in lo.BYTES:
+            for side, rows in (("M", M), ("K", K)):
+                if shift < rows * N * elem:
+                    r0 = shift // (N * elem) + 1
+                    assert r0 + 64 + lo.LAST <= rows
+                    out.append((H, F, regime, shift, side, r0))
+    return out
+
+
+def test_no_alias_2_32_bytes_away_inside_a_16_bit_operand():
+    """A displacement by 2^31 ELEMENTS (a position's sign, or a 32-bit byte offset formed from it) leaves every 16-bit operand the
+    entries accept: a fault, not a wrong value. What a value comparison has to reject at element size 2 is 2^30 elements."""
+    assert {c[3] for c in _displaced_cases(2)} == {1 << 31} and {c[3] for c in _displaced_cases(4)} == set(lo.BYTES)
+
+
+@pytest.mark.parametrize("H,F,regime,shift,side,r0", _displaced_cases(4))
+def test_gatv2_attention_comparators_reject_a_displaced_gather(H, F, regime, shift, side, r0):
+    """Displaced by 2^29 and 2^30 WORDS (2^31, 2^32 bytes of an fp32 operand; 2^31 words lie outside every accepted one): the float64
+    reference recomputed with the gathered operand read through the displaced position must put the correct result outside the
+    tolerances of test_gatv2_attention_host.py — xr (K side) for the forward and the row pass, xl and grad_out (M side) for the
+    column pass."""
+    from test_dot_attention_host import ratio
+    from test_gatv2_attention_host import ref_backward, ref_forward
+
+    N, slope = H * F, 0.2
+    M, K = lo.sizes_b(N, regime)
+    P = _band_pattern(64)
+    fns = {"xl": _hashed(-1, 1, 11, H, F), "xr": _hashed(-1, 1, 23, H, F), "go": _hashed(0.5, 1, 37, H, F)}
+    spans = {"xl": (r0, r0 + 64, M), "xr": (r0, r0 + 64 + lo.LAST, K), "go": (r0, r0 + 64, M)}
+    x = {k: _rows_of(fns[k], *spans[k][:2], H, F) for k in fns}
+    x["att"] = (np.random.RandomState(N).uniform(-2, 2, size=(H, F)) * min(1.0, 8.0 / F)).astype(np.float32)
+    f32 = lambda a: np.asarray(a).astype(np.float32)  # noqa: E731
+    f = ref_forward(P, x, slope)
+    stats, out = f32(np.stack([f["m"], f["l"]], -1)), f32(f["out"])
+    b = ref_backward(P, x, slope, stats, out)
+    delta = f32(b["delta"])
+    bc = ref_backward(P, x, slope, stats, out, delta)
+    good = {"out": ratio(out, f["out"], f["tol_out"]), "grad_xl": ratio(f32(b["grad_xl"]), b["grad_xl"], b["tol_grad_xl"]),
+            "att_part": ratio(f32(b["att_part"]), b["att_part"], b["tol_att_part"]),
+            "grad_xr": ratio(f32(bc["grad_xr"]), bc["grad_xr"], bc["tol_grad_xr"])}
+    assert max(good.values()) <= 1.0, good
+    for name in ("xr",) if side == "K" else ("xl", "go"):
+        wrong = lo.displaced(fns[name], H, F, shift, spans[name][2], 4)
+        xo = dict(x, **{name: _rows_of(wrong, *spans[name][:2], H, F)})
+        assert not np.array_equal(xo[name], x[name])
+        fo = ref_forward(P, xo, slope)
+        bo = ref_backward(P, xo, slope, stats, out, delta)
+        r = {"out": ratio(out, fo["out"], fo["tol_out"]), "grad_xl": ratio(f32(b["grad_xl"]), bo["grad_xl"], bo["tol_grad_xl"]),
+             "att_part": ratio(f32(b["att_part"]), bo["att_part"], bo["tol_att_part"]),
+             "grad_xr": ratio(f32(bc["grad_xr"]), bo["grad_xr"], bo["tol_grad_xr"])}
+        seen = {"xr": ("out", "grad_xl", "att_part"), "xl": ("grad_xr",), "go": ("grad_xr",)}[name]
+        assert all(r[s] > 1.0 for s in seen), (name, r)
+
+
+@pytest.mark.parametrize("dtype", (torch.bfloat16, torch.float16))
+@pytest.mark.parametrize("H,F,regime,shift,side,r0", _displaced_cases(2))
+def test_gatv2_x16_comparators_reject_a_displaced_gather(H, F, regime, shift, side, r0, dtype):
+    """Displaced by 2^30 ELEMENTS (2^31 bytes at element size 2): the score's float64 bound must reject the restatement on the displaced
+    operand, and the oracle of the backward — compared on bits on the device — must differ from it in att_part and in the narrowed
+    grad_x (xr, K side, for the score and the row pass; xl, M side, for the column pass)."""
+    from gatv2_x16_cases import narrow
+    from test_gatv2_host import restate_backward, restate_score, worst_ratio
+
+    N, slope = H * F, 0.2
+    M, K = lo.sizes_b(N, regime)
+    P = _band_pattern(64)
+    fns = {"xl": _hashed(-1, 1, 11, H, F), "xr": _hashed(-1, 1, 23, H, F)}
+    spans = {"xl": (r0, r0 + 64, M), "xr": (r0, r0 + 64 + lo.LAST, K)}
+    wide = lambda fn, k: narrow(_rows_of(fn, *spans[k][:2], H, F), dtype)[1]  # noqa: E731  (the 16-bit values, widened exactly)
+    rng = np.random.RandomState(N)
+    x = {"xl": wide(fns["xl"], "xl"), "xr": wide(fns["xr"], "xr"), "att": rng.uniform(-2, 2, size=(H, F)).astype(np.float32),
+         "gs": rng.uniform(-2, 2, size=(P["nnz"], H)).astype(np.float32)}
+    name = "xr" if side == "K" else "xl"
+    xo = dict(x, **{name: wide(lo.displaced(fns[name], H, F, shift, spans[name][2], 2), name)})
+    narrowed = lambda a: torch.from_numpy(np.asarray(a).astype(np.float32)).to(dtype).view(torch.int16).numpy()  # noqa: E731
+    if side == "K":
+        ref, terms = restate_score(P["rowptr"], P["colind"], x["xl"], x["xr"], x["att"], slope)
+        bad, bad_terms = restate_score(P["rowptr"], P["colind"], xo["xl"], xo["xr"], x["att"], slope)
+        got32 = ref.astype(np.float32)
+        assert worst_ratio(got32, ref, terms, "score") <= 1.0 < worst_ratio(got32, bad, bad_terms, "score")
+        got = restate_backward(P["rowptr"], P["colind"], x["gs"], x["xl"], x["xr"], x["att"], slope)
+        other = restate_backward(P["rowptr"], P["colind"], x["gs"], xo["xl"], xo["xr"], x["att"], slope)
+        assert not np.array_equal(got[1].astype(np.float32), other[1].astype(np.float32)), "att_part"
+    else:
+        got = restate_backward(P["colptr"], P["rowind"], x["gs"], x["xr"], x["xl"], x["att"], slope, order=P["order"])
+        other = restate_backward(P["colptr"], P["rowind"], x["gs"], xo["xr"], xo["xl"], x["att"], slope, order=P["order"])
+    assert not np.array_equal(narrowed(got[0]), narrowed(other[0])), "grad_x"
 
 
 # ---- the band at d = 8 ----------------------------------------------------------------------------------------------------------------
