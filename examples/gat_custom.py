@@ -20,6 +20,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
                                                                    # 16-bit multi-head product, everything edge-sized stays fp32
     python examples/gat_custom.py --v2 --dtype bf16                # ``GATv2Conv`` as a 16-bit model: the edge score and its two gradient
                                                                    # passes read bf16 (or fp16) node terms, att and the score stay fp32
+    python examples/gat_custom.py --v2 --fused-attention --dtype bf16   # ``GATv2Conv(fused=True, fused_x16=True)``: the fused attention on
+                                                                   # bf16 (or fp16) node terms: no [nnz, H] array AND half the node bytes
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
 chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
@@ -61,8 +63,10 @@ class Net(torch.nn.Module):
         if v2:
             if fused_score or fused_aggregate or fused_backward:
                 raise ValueError("fused_score, fused_aggregate and fused_backward are GATConv's: GATv2Conv has fused_attention")
-            self.conv1 = GATv2Conv(n_in, n_hidden, heads=heads, concat=True, dropout=attn_dropout, fused=fused_attention)
-            self.conv2 = GATv2Conv(n_hidden * heads, n_out, heads=1, concat=False, dropout=attn_dropout, fused=fused_attention)
+            # (fused_x16: a 16-bit model runs the fused attention on 16-bit node terms; an fp32 one runs what fused=True runs)
+            fused = dict(fused=fused_attention, fused_x16=fused_attention)
+            self.conv1 = GATv2Conv(n_in, n_hidden, heads=heads, concat=True, dropout=attn_dropout, **fused)
+            self.conv2 = GATv2Conv(n_hidden * heads, n_out, heads=1, concat=False, dropout=attn_dropout, **fused)
         else:
             fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward, dropout=attn_dropout)
             self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, **fused)
@@ -103,12 +107,12 @@ def main():
                          "then print the same losses")
     ap.add_argument("--dtype", choices=("fp32", "bf16", "fp16"), default="fp32",
                     help="cast the model and the features (bf16 / fp16: GATConv on the 16-bit multi-head product, with --v2 GATv2Conv "
-                         "on the 16-bit edge score too; not with --fused-aggregate, --fused-backward or --fused-attention, which are "
-                         "fp32 only)")
+                         "on the 16-bit edge score too, with --v2 --fused-attention the fused attention on 16-bit node terms; not "
+                         "with --fused-aggregate or --fused-backward, which are fp32 only)")
     args = ap.parse_args()
-    if args.dtype != "fp32" and (args.fused_aggregate or args.fused_backward or args.fused_attention):
-        ap.error("--dtype %s: --fused-aggregate, --fused-backward and --fused-attention run fp32-only kernels; use the default path, "
-                 "--fused-score or --v2" % args.dtype)
+    if args.dtype != "fp32" and (args.fused_aggregate or args.fused_backward or (args.fused_attention and not args.v2)):
+        ap.error("--dtype %s: --fused-aggregate and --fused-backward run fp32-only kernels; use the default path, --fused-score, --v2 "
+                 "or --v2 --fused-attention" % args.dtype)
     if args.v2 and (args.fused_score or args.fused_aggregate or args.fused_backward):
         ap.error("--fused-score, --fused-aggregate and --fused-backward are GATConv's: --v2 has --fused-attention")
     if args.fused_attention and not args.v2:

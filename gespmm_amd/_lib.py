@@ -149,6 +149,13 @@ EXPORTS = [
     "gespmm_gatv2_attention_backward_col_f32",
     "gespmm_gatv2_attention_backward_col_dropout_f32",
     "gespmm_describe_gatv2_attention",
+    "gespmm_gatv2_attention_x16",
+    "gespmm_gatv2_attention_dropout_x16",
+    "gespmm_gatv2_attention_backward_row_x16",
+    "gespmm_gatv2_attention_backward_row_dropout_x16",
+    "gespmm_gatv2_attention_backward_col_x16",
+    "gespmm_gatv2_attention_backward_col_dropout_x16",
+    "gespmm_describe_gatv2_attention_x16",
     "gespmm_csr_spmm_max_arg_f32",
     "gespmm_csr_spmm_max_backward_f32",
     "gespmm_max_arg_route",
@@ -419,6 +426,20 @@ def _load():
     lib.gespmm_gatv2_attention_backward_col_dropout_f32.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, c_float, p, p]
     lib.gespmm_describe_gatv2_attention.restype = c_int
     lib.gespmm_describe_gatv2_attention.argtypes = [c_int64] * 5 + [c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_gatv2_attention_x16.restype = c_int
+    lib.gespmm_gatv2_attention_x16.argtypes = [p] * 7 + [c_int] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_attention_dropout_x16.restype = c_int
+    lib.gespmm_gatv2_attention_dropout_x16.argtypes = [p] * 7 + [c_int] + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_gatv2_attention_backward_row_x16.restype = c_int
+    lib.gespmm_gatv2_attention_backward_row_x16.argtypes = [p] * 11 + [c_int] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_attention_backward_row_dropout_x16.restype = c_int
+    lib.gespmm_gatv2_attention_backward_row_dropout_x16.argtypes = [p] * 11 + [c_int] + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_gatv2_attention_backward_col_x16.restype = c_int
+    lib.gespmm_gatv2_attention_backward_col_x16.argtypes = [p] * 9 + [c_int] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gatv2_attention_backward_col_dropout_x16.restype = c_int
+    lib.gespmm_gatv2_attention_backward_col_dropout_x16.argtypes = [p] * 9 + [c_int] + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_describe_gatv2_attention_x16.restype = c_int
+    lib.gespmm_describe_gatv2_attention_x16.argtypes = [c_int64] * 5 + [c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_csr_spmm_max_arg_f32.restype = c_int
     lib.gespmm_csr_spmm_max_arg_f32.argtypes = [p] * 5 + [c_int64] * 4 + [c_float, p]
     lib.gespmm_csr_spmm_max_backward_f32.restype = c_int
@@ -568,16 +589,20 @@ def describe_dot_attention(M, K, H, F, nnz, q_align=16, k_align=16, v_align=16):
 GATV2_ATTENTION_MAX_F = 512
 
 
-def describe_gatv2_attention(M, K, H, F, nnz, xl_align=16, xr_align=16, att_align=16):
-    """The lane geometry of gespmm_gatv2_attention_f32 and its two backward passes for these sizes and operand alignments
-    (gespmm_describe_gatv2_attention: host only) — a dict ``{"V": floats per load, "W": lanes per (segment, head) pair, "supported":
+def describe_gatv2_attention(M, K, H, F, nnz, xl_align=16, xr_align=16, att_align=16, x16=False):
+    """The lane geometry of gespmm_gatv2_attention_f32 — x16=True: gespmm_gatv2_attention_x16, fp16 / bf16 node terms with an fp32
+    ``att`` — and its two backward passes for these sizes and operand alignments (gespmm_describe_gatv2_attention / _x16: host only) — a dict ``{"V": floats per load, "W": lanes per (segment, head) pair, "supported":
     True}``; ``{"route": "unsupported", "supported": False}`` when F > 512 (no kernel), ``{"route": "zeros", ...}`` when F == 0 and
     ``{"form": "none", ...}`` when nnz == 0. V and W fix the score's summation order; the least aligned dense operand of a launch —
-    the dense results included: pass their alignment with ``xl_align`` — decides V."""
+    the dense results included: pass their alignment with ``xl_align`` — decides V. x16: V counts elements and stays in 4 / 2 / 1; 2 V
+    bytes divide the 16-bit operands' addresses (``xl_align``, ``xr_align`` from 2), 4 V bytes those of ``att`` and ``att_part``
+    (``att_align`` from 4) — the fp32 answer at twice the 16-bit alignment."""
     buf = ctypes.create_string_buffer(96)
-    n = lib.gespmm_describe_gatv2_attention(int(M), int(K), int(H), int(F), int(nnz), int(xl_align), int(xr_align), int(att_align), buf, 96)
+    f, name = (lib.gespmm_describe_gatv2_attention_x16, "gespmm_describe_gatv2_attention_x16") if x16 else \
+        (lib.gespmm_describe_gatv2_attention, "gespmm_describe_gatv2_attention")
+    n = f(int(M), int(K), int(H), int(F), int(nnz), int(xl_align), int(xr_align), int(att_align), buf, 96)
     if n < 0:
-        raise GespmmError(n, "gespmm_describe_gatv2_attention")
+        raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k in ("form", "route") else bool(int(v)) if k == "supported" else int(v)) for k, v in out.items()}
 

@@ -32,7 +32,18 @@ one gathered row per entry serves the forward — ``att`` f32[H, F]:
     s_p = sum_f att[h, f] leaky_relu(xl[r, h, f] + xr[c, h, f])      a_p = exp(s_p - m) / l      out[r, h, :] = sum_p a_p xr[c, h, :]
 
 ``s_p`` has the bits of ``sddmm.gatv2_score`` on equally aligned operands (``_lib.describe_gatv2_attention``). ``negative_slope=None``: no
-leaky ReLU. F <= 512, fp32 only."""
+leaky ReLU. F <= 512. These three names are fp32 only; on fp16 / bf16 node terms (``att``, ``stats``, ``delta`` and ``att_part`` stay fp32):
+
+    gatv2_attention_x16(rowptr, colind, xl, xr, att, negative_slope=None, dropout=None, out=None, stats=None)    -> (out x16[M, H, F], stats f32[M, H, 2])
+    gatv2_attention_backward_row_x16(rowptr, colind, xl, xr, att, stats, out, grad_out, negative_slope=None, dropout=None,
+                                     want_att_part=True, results=None)                                           -> (delta f32, grad_xl x16[, att_part f32])
+    gatv2_attention_backward_col_x16(colptr, rowind, xl, xr, att, stats, delta, grad_out, negative_slope=None, dropout=None,
+                                     result=None)                                                                -> grad_xr x16[K, H, F]
+
+Every 16-bit element is widened exactly at its use, the arithmetic and the lane geometry are the fp32 kernels' and every 16-bit result is
+rounded once at its store: where ``_lib.describe_gatv2_attention`` answers the same (V, W) with and without ``x16=True``, ``stats``,
+``delta`` and ``att_part`` have the bits of the fp32 calls on the widened operands and ``out``, ``grad_xl``, ``grad_xr`` are theirs
+narrowed once."""
 import math
 
 import torch
@@ -413,4 +424,155 @@ def gatv2_attention_backward_col(colptr, rowind, xl, xr, att, stats, delta, grad
         else:
             rc = lib.gespmm_gatv2_attention_backward_col_f32(*args, _stream(dev))
     check(rc, "gespmm_gatv2_attention_backward_col_dropout_f32" if dropout is not None else "gespmm_gatv2_attention_backward_col_f32")
+    return grad_xr
+
+
+# ---- ... on fp16 / bf16 node terms (gespmm_gatv2_attention_x16 and its backward)
+
+def _typed_x16(int_ops, node_ops, float_ops):
+    """``_typed`` with a third class: the node operands and 16-bit results, all ``torch.float16`` or all ``torch.bfloat16`` -> the
+    GESPMM_X16_* code. The first of them names the type (``None`` passes, but not there)."""
+    from .spmm import _X16
+
+    _typed(int_ops, float_ops)
+    first_name, first = node_ops[0]
+    if not isinstance(first, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % first_name)
+    if first.dtype not in _X16:
+        raise TypeError("%s must have dtype torch.float16 or torch.bfloat16, got %s (fp32: the functions without _x16)" %
+                        (first_name, first.dtype))
+    for name, t in node_ops[1:]:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype != first.dtype:  # (mixed 16-bit dtypes and fp32 node terms: TypeError)
+            raise TypeError("%s must have dtype %s, as %s, got %s" % (name, first.dtype, first_name, t.dtype))
+    return _X16[first.dtype]
+
+
+def gatv2_attention_x16(rowptr, colind, xl, xr, att, negative_slope=None, dropout=None, out=None, stats=None):
+    """``gatv2_attention`` on 16-bit node terms (gespmm_gatv2_attention_x16 / _dropout_x16): ``xl`` [M, H, F] and ``xr`` [K, H, F] both
+    ``torch.float16`` or both ``torch.bfloat16``, ``att`` f32[H, F]. Returns ``(out, stats)``: ``out`` [M, H, F] in the node terms' dtype,
+    rounded once at the store; ``stats`` f32[M, H, 2]. Every element is widened exactly at its use and the arithmetic is
+    ``gatv2_attention``'s: where ``_lib.describe_gatv2_attention`` answers the same (V, W) with and without ``x16=True``, ``stats`` has the
+    bits of ``gatv2_attention`` on ``xl.float(), xr.float()`` and ``out`` is that call's ``out`` narrowed once. A 16-bit ``att`` or
+    ``stats``, fp32 node terms and mixed 16-bit dtypes raise TypeError."""
+    x16 = _typed_x16((("rowptr", rowptr), ("colind", colind)), (("xl", xl), ("xr", xr), ("out", out)), (("att", att), ("stats", stats)))
+    _required((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _gatv2_shapes(rowptr, "rowptr", colind, "colind", xl, xr, att, True)
+    slope = _slope(negative_slope)
+    _shaped(out, "out", (M, H, F))
+    _shaped(stats, "stats", (M, H, 2))
+    dev = xl.device
+    _placed((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("out", out), ("stats", stats)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _gatv2_served(F, "gespmm_gatv2_attention_x16")
+    if out is None:
+        out = torch.empty((M, H, F), dtype=xl.dtype, device=dev)
+    if stats is None:
+        stats = torch.empty((M, H, 2), dtype=torch.float32, device=dev)
+    if M == 0:  # (results of no words have no address to hand over)
+        return out, stats
+    args = (_ptr(rowptr), _ptr(colind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(out), _ptr(stats), x16, M, K, H, F, nnz, slope)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_gatv2_attention_dropout_x16(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_gatv2_attention_x16(*args, _stream(dev))
+    check(rc, "gespmm_gatv2_attention_dropout_x16" if dropout is not None else "gespmm_gatv2_attention_x16")
+    return out, stats
+
+
+def gatv2_attention_backward_row_x16(rowptr, colind, xl, xr, att, stats, out, grad_out, negative_slope=None, dropout=None,
+                                     want_att_part=True, results=None):
+    """``gatv2_attention_backward_row`` on 16-bit node terms (gespmm_gatv2_attention_backward_row_x16 / _dropout_x16): ``xl``, ``xr``,
+    ``out``, ``grad_out`` and the result ``grad_xl`` in one 16-bit dtype; ``att``, ``stats`` and the results ``delta`` f32[M, H] and
+    ``att_part`` f32[M, H, F] stay fp32. ``delta`` is taken of the STORED 16-bit ``out``; ``grad_xl`` is rounded once at the store.
+    Returns ``(delta, grad_xl, att_part)``, or ``(delta, grad_xl)`` with ``want_att_part=False``. On equal (V, W) ``delta`` and
+    ``att_part`` have the bits of ``gatv2_attention_backward_row`` on the widened operands, ``grad_xl`` is its ``grad_xl`` narrowed once."""
+    want = bool(want_att_part)
+    n_res = 3 if want else 2
+    if results is None:
+        res = (None,) * n_res
+    elif not isinstance(results, (tuple, list)) or len(results) != n_res or any(t is None for t in results):
+        raise TypeError("results must be a tuple of %d tensors" % n_res)
+    else:
+        res = tuple(results)
+    delta, grad_xl = res[0], res[1]
+    att_part = res[2] if want else None
+    x16 = _typed_x16((("rowptr", rowptr), ("colind", colind)),
+                     (("xl", xl), ("xr", xr), ("out", out), ("grad_out", grad_out), ("results[1]", grad_xl)),
+                     (("att", att), ("stats", stats), ("results[0]", delta), ("results[2]", att_part)))
+    _required((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("out", out),
+               ("grad_out", grad_out)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _gatv2_shapes(rowptr, "rowptr", colind, "colind", xl, xr, att, True)
+    slope = _slope(negative_slope)
+    _shaped(stats, "stats", (M, H, 2))
+    _shaped(out, "out", (M, H, F))
+    _shaped(grad_out, "grad_out", (M, H, F))
+    _shaped(delta, "results[0]", (M, H))
+    _shaped(grad_xl, "results[1]", (M, H, F))
+    _shaped(att_part, "results[2]", (M, H, F))
+    dev = xl.device
+    _placed((("rowptr", rowptr), ("colind", colind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("out", out),
+             ("grad_out", grad_out), ("results[0]", delta), ("results[1]", grad_xl), ("results[2]", att_part)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _gatv2_served(F, "gespmm_gatv2_attention_backward_row_x16")
+    if delta is None:
+        delta = torch.empty((M, H), dtype=torch.float32, device=dev)
+        grad_xl = torch.empty((M, H, F), dtype=xl.dtype, device=dev)
+        if want:
+            att_part = torch.empty((M, H, F), dtype=torch.float32, device=dev)
+    ret = (delta, grad_xl, att_part) if want else (delta, grad_xl)
+    if M == 0:
+        return ret
+    args = (_ptr(rowptr), _ptr(colind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(stats), _ptr(out), _ptr(grad_out), _ptr(delta), _ptr(grad_xl),
+            _ptr(att_part) if want else None, x16, M, K, H, F, nnz, slope)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_gatv2_attention_backward_row_dropout_x16(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_gatv2_attention_backward_row_x16(*args, _stream(dev))
+    check(rc, "gespmm_gatv2_attention_backward_row_dropout_x16" if dropout is not None else "gespmm_gatv2_attention_backward_row_x16")
+    return ret
+
+
+def gatv2_attention_backward_col_x16(colptr, rowind, xl, xr, att, stats, delta, grad_out, negative_slope=None, dropout=None, result=None):
+    """``gatv2_attention_backward_col`` on 16-bit node terms (gespmm_gatv2_attention_backward_col_x16 / _dropout_x16): ``xl``, ``xr``,
+    ``grad_out`` and the result ``grad_xr`` [K, H, F] in one 16-bit dtype; ``att``, ``stats`` and ``delta`` (the row pass's) stay fp32.
+    The two fp32 chains of a word are added once and that sum is rounded once, at the store: on equal (V, W) ``grad_xr`` is
+    ``gatv2_attention_backward_col`` on the widened operands, narrowed once. ``result``: a tensor to write into."""
+    x16 = _typed_x16((("colptr", colptr), ("rowind", rowind)), (("xl", xl), ("xr", xr), ("grad_out", grad_out), ("result", result)),
+                     (("att", att), ("stats", stats), ("delta", delta)))
+    _required((("colptr", colptr), ("rowind", rowind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("delta", delta),
+               ("grad_out", grad_out)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _gatv2_shapes(colptr, "colptr", rowind, "rowind", xl, xr, att, False)
+    slope = _slope(negative_slope)
+    _shaped(stats, "stats", (M, H, 2))
+    _shaped(delta, "delta", (M, H))
+    _shaped(grad_out, "grad_out", (M, H, F))
+    _shaped(result, "result", (K, H, F))
+    dev = xl.device
+    _placed((("colptr", colptr), ("rowind", rowind), ("xl", xl), ("xr", xr), ("att", att), ("stats", stats), ("delta", delta),
+             ("grad_out", grad_out), ("result", result)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _gatv2_served(F, "gespmm_gatv2_attention_backward_col_x16")
+    grad_xr = result if result is not None else torch.empty((K, H, F), dtype=xl.dtype, device=dev)
+    if K == 0:
+        return grad_xr
+    args = (_ptr(colptr), _ptr(rowind), _ptr(xl), _ptr(xr), _ptr(att), _ptr(stats), _ptr(delta), _ptr(grad_out), _ptr(grad_xr), x16, M, K, H,
+            F, nnz, slope)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_gatv2_attention_backward_col_dropout_x16(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_gatv2_attention_backward_col_x16(*args, _stream(dev))
+    check(rc, "gespmm_gatv2_attention_backward_col_dropout_x16" if dropout is not None else "gespmm_gatv2_attention_backward_col_x16")
     return grad_xr

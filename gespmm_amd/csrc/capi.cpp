@@ -28,6 +28,7 @@
 #include "gat_backward.h"
 #include "dot_attention.h"
 #include "gatv2_attention.h"
+#include "gatv2_attention_x16.h"
 #include "gatv2_score.h"
 #include "plan.h"
 #include "sddmm_heads.h"
@@ -1871,6 +1872,163 @@ int gespmm_describe_gatv2_attention(int64_t M, int64_t K, int64_t H, int64_t F, 
     } else {
         const gespmm::Gatv2AttentionLaunch r = gespmm::resolve_gatv2_attention(F, xl_align > 16 ? 16 : xl_align,
                                                                                xr_align > 16 ? 16 : xr_align, att_align > 16 ? 16 : att_align);
+        n = snprintf(out, (size_t)capacity, "V=%d W=%d supported=%d", r.V, r.W, r.supported ? 1 : 0);
+    }
+    return describe_result(n, capacity);
+}
+
+/* ... on fp16 / bf16 node terms (gespmm.h; gatv2_attention_x16.h): the dtype code first, as in every _x16 entry, then the ladder above
+   with 2-byte alignment for the 16-bit operands and results. att, stats, delta and att_part stay fp32. */
+struct ZeroFillArg {
+    void* p;
+    int elem;      // bytes
+    size_t count;  // elements; 0: the array is absent or empty
+};
+static int zero_fill_x16(std::initializer_list<ZeroFillArg> outs, hipStream_t st) {
+    for (const auto& o : outs)
+        if (!o.p && o.count) return GESPMM_EINVAL;
+    for (const auto& o : outs)
+        if (reinterpret_cast<uintptr_t>(o.p) % (uintptr_t)o.elem != 0) return GESPMM_EALIGN;
+    for (const auto& o : outs) {
+        if (o.count == 0) continue;
+        const hipError_t e = hipMemsetAsync(o.p, 0, o.count * (size_t)o.elem, st);  // (+0 has no set bit in either type)
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+static int gatv2_attention_x16_entry(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att, void* out,
+                                     float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                     const float* p, const void* seed, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, slope, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {  // every row is empty: every word of the results is still written
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill_x16({{out, 2, (size_t)(M * H * F)}, {stats, 4, (size_t)(M * H * 2)}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {xl, 2, true}, {xr, 2, true}, {att, 4, true}, {out, 2, true},
+                                        {stats, 8, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({xl, xr, out});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gatv2_attention_x16(rowptr, colind, xl, xr, att, out, stats, dtype, M, K, H, F, nnz, slope,
+                                                   gespmm::resolve_gatv2_attention_x16(F, a, a, pointer_alignment(att)),
+                                                   p ? &dropout : nullptr, st);
+}
+
+int gespmm_gatv2_attention_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att, void* out,
+                               float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    return gatv2_attention_x16_entry(rowptr, colind, xl, xr, att, out, stats, dtype, M, K, H, F, nnz, slope, nullptr, nullptr, stream);
+}
+
+int gespmm_gatv2_attention_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att,
+                                       void* out, float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                       float slope, float p, const void* seed, void* stream) {
+    return gatv2_attention_x16_entry(rowptr, colind, xl, xr, att, out, stats, dtype, M, K, H, F, nnz, slope, &p, seed, stream);
+}
+
+static int gatv2_attention_backward_row_x16_entry(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr,
+                                                  const float* att, const float* stats, const void* out, const void* grad_out, float* delta,
+                                                  void* grad_xl, float* att_part, int dtype, int64_t M, int64_t K, int64_t H, int64_t F,
+                                                  int64_t nnz, float slope, const float* p, const void* seed, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, slope, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill_x16({{delta, 4, (size_t)(M * H)}, {grad_xl, 2, (size_t)(M * H * F)},
+                              {att_part, 4, att_part ? (size_t)(M * H * F) : 0}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {xl, 2, true}, {xr, 2, true}, {att, 4, true}, {stats, 8, true},
+                                        {out, 2, true}, {grad_out, 2, true}, {delta, 4, true}, {grad_xl, 2, true}, {att_part, 4, false},
+                                        {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({xl, xr, out, grad_out, grad_xl});
+    const int fa = gespmm::least_alignment({att, att_part});  // (a null att_part counts as aligned)
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gatv2_attention_backward_row_x16(rowptr, colind, xl, xr, att, stats, out, grad_out, delta, grad_xl, att_part,
+                                                                dtype, M, K, H, F, nnz, slope,
+                                                                gespmm::resolve_gatv2_attention_x16(F, a, a, fa), p ? &dropout : nullptr, st);
+}
+
+int gespmm_gatv2_attention_backward_row_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att,
+                                            const float* stats, const void* out, const void* grad_out, float* delta, void* grad_xl,
+                                            float* att_part, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                            void* stream) {
+    return gatv2_attention_backward_row_x16_entry(rowptr, colind, xl, xr, att, stats, out, grad_out, delta, grad_xl, att_part, dtype, M, K, H,
+                                                  F, nnz, slope, nullptr, nullptr, stream);
+}
+
+int gespmm_gatv2_attention_backward_row_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr,
+                                                    const float* att, const float* stats, const void* out, const void* grad_out,
+                                                    float* delta, void* grad_xl, float* att_part, int dtype, int64_t M, int64_t K, int64_t H,
+                                                    int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream) {
+    return gatv2_attention_backward_row_x16_entry(rowptr, colind, xl, xr, att, stats, out, grad_out, delta, grad_xl, att_part, dtype, M, K, H,
+                                                  F, nnz, slope, &p, seed, stream);
+}
+
+static int gatv2_attention_backward_col_x16_entry(const int32_t* colptr, const int32_t* rowind, const void* xl, const void* xr,
+                                                  const float* att, const float* stats, const float* delta, const void* grad_out,
+                                                  void* grad_xr, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                                  float slope, const float* p, const void* seed, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, slope, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill_x16({{grad_xr, 2, (size_t)(K * H * F)}}, st);
+    }
+    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {xl, 2, true}, {xr, 2, true}, {att, 4, true}, {stats, 8, true},
+                                        {delta, 4, true}, {grad_out, 2, true}, {grad_xr, 2, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({xl, xr, grad_out, grad_xr});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_gatv2_attention_backward_col_x16(colptr, rowind, xl, xr, att, stats, delta, grad_out, grad_xr, dtype, M, K, H, F,
+                                                                nnz, slope,
+                                                                gespmm::resolve_gatv2_attention_x16(F, a, a, pointer_alignment(att)),
+                                                                p ? &dropout : nullptr, st);
+}
+
+int gespmm_gatv2_attention_backward_col_x16(const int32_t* colptr, const int32_t* rowind, const void* xl, const void* xr, const float* att,
+                                            const float* stats, const float* delta, const void* grad_out, void* grad_xr, int dtype, int64_t M,
+                                            int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    return gatv2_attention_backward_col_x16_entry(colptr, rowind, xl, xr, att, stats, delta, grad_out, grad_xr, dtype, M, K, H, F, nnz, slope,
+                                                  nullptr, nullptr, stream);
+}
+
+int gespmm_gatv2_attention_backward_col_dropout_x16(const int32_t* colptr, const int32_t* rowind, const void* xl, const void* xr,
+                                                    const float* att, const float* stats, const float* delta, const void* grad_out,
+                                                    void* grad_xr, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                                    float slope, float p, const void* seed, void* stream) {
+    return gatv2_attention_backward_col_x16_entry(colptr, rowind, xl, xr, att, stats, delta, grad_out, grad_xr, dtype, M, K, H, F, nnz, slope,
+                                                  &p, seed, stream);
+}
+
+int gespmm_describe_gatv2_attention_x16(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int xl_align, int xr_align, int att_align,
+                                        char* out, int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    for (const int a : {xl_align, xr_align, att_align})
+        if (a < 2 || (a & (a - 1)) != 0) return GESPMM_EINVAL;
+    if (att_align < 4) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gatv2_attention_sizes(M, K, H, F, nnz, 1.0f, nullptr);
+    if (rc != 0 && rc != GESPMM_ERR_UNSUPPORTED) return rc;
+    int n;
+    if (rc == GESPMM_ERR_UNSUPPORTED) {
+        n = snprintf(out, (size_t)capacity, "route=unsupported supported=0");
+    } else if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none supported=1");
+    } else if (F == 0) {
+        n = snprintf(out, (size_t)capacity, "route=zeros supported=1");
+    } else {
+        const gespmm::Gatv2AttentionLaunch r = gespmm::resolve_gatv2_attention_x16(
+            F, xl_align > 16 ? 16 : xl_align, xr_align > 16 ? 16 : xr_align, att_align > 16 ? 16 : att_align);
         n = snprintf(out, (size_t)capacity, "V=%d W=%d supported=%d", r.V, r.W, r.supported ? 1 : 0);
     }
     return describe_result(n, capacity);

@@ -363,4 +363,11 @@ Gatv2AttentionLaunch resolve_gatv2_attention(int64_t F, int xl_align, int xr_ali
     return Gatv2AttentionLaunch{b.V, b.W, F <= kGatv2AttentionMaxF};
 }
 
+// ... on 16-bit node terms: the fp32 rule on the widened operands' alignments, so that both resolvers answer the same (V, W) for an
+// operand and its widened copy placed to match. No V = 8 (a 16-byte load of 16-bit elements): it would move the lane positions.
+Gatv2AttentionLaunch resolve_gatv2_attention_x16(int64_t F, int xl_align, int xr_align, int att_align) {
+    const int l = 2 * xl_align > 16 ? 16 : 2 * xl_align, r = 2 * xr_align > 16 ? 16 : 2 * xr_align;
+    return resolve_gatv2_attention(F, l, r, att_align);
+}
+
 }  // namespace gespmm

@@ -100,5 +100,9 @@ struct Gatv2AttentionLaunch {
 };
 // F >= 1. *_align: largest power of two (bytes) that divides an operand's address — the least of a launch's dense operands decides.
 Gatv2AttentionLaunch resolve_gatv2_attention(int64_t F, int xl_align, int xr_align, int att_align);
+// ... on 16-bit node terms (gatv2_attention_x16.h): V counts ELEMENTS and stays in {4, 2, 1} — 2 V bytes divide xl_align and xr_align
+// (the least of the 16-bit operands and results, >= 2), 4 V bytes divide att_align (the least of att and att_part, >= 4). The answer is
+// resolve_gatv2_attention's for the widened operands: a 16-bit operand b bytes off a 16-byte boundary is an fp32 operand 2 b bytes off.
+Gatv2AttentionLaunch resolve_gatv2_attention_x16(int64_t F, int xl_align, int xr_align, int att_align);
 
 }  // namespace gespmm

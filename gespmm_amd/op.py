@@ -60,7 +60,8 @@ Graph transformers (extension): ``DotAttentionFunction`` is scaled dot-product a
 (``attention.dot_attention`` and its two backward passes: no score, no alpha, nothing of size nnz saved), ``TransformerConv`` PyG's layer
 of that name on it (``fused=True``) or on the composition of the functions above (the default).
 ``GATv2AttentionFunction`` is the same for GATv2 — score, softmax, dropout and aggregation in one launch on one gathered row per entry
-(``attention.gatv2_attention`` and its two backward passes), behind ``GATv2Conv(fused=True)``.
+(``attention.gatv2_attention`` and its two backward passes), behind ``GATv2Conv(fused=True)`` — and on fp16 / bf16 node terms
+(``attention.gatv2_attention_x16`` and its two backward passes), behind ``GATv2Conv(fused=True, fused_x16=True)``.
 The reference's ``normalize=False`` branch raises TypeError (``rowptr.shape(0)``,
 op.py:133-134); here it does what the branch evidently intends: no scaling.
 """
@@ -800,7 +801,12 @@ class GATv2AttentionFunction(torch.autograd.Function):
     ``EdgeDropoutFunction``'s mask, recomputed in all three launches; the seed is read when the backward runs. The row pass runs when
     any of the three needs a gradient (``att``'s is the sum over nodes of a node-sized result asked for only then), the column pass
     only when ``xr`` does. ``xl is xr`` (shared weights) works: autograd adds the two gradients. F <= 512. Index tensors get no
-    gradient."""
+    gradient.
+
+    16-bit ``xl`` and ``xr`` (both ``torch.float16`` or both ``torch.bfloat16``; ``att`` must be fp32): the same three launches through
+    ``attention.gatv2_attention_x16`` / ``gatv2_attention_backward_row_x16`` / ``gatv2_attention_backward_col_x16``. Saved: the 16-bit
+    ``xl, xr, out`` and the fp32 ``att, stats``. ``out``, ``grad_xl`` and ``grad_xr`` come in the features' dtype (fp32 sums, one
+    rounding each), ``grad_att`` as fp32 (``att_part.sum(0)``)."""
 
     @staticmethod
     def forward(ctx, rowptr, colind, colptr, rowind, xl, xr, att, negative_slope=None, dropout_p=0.0, seed=None):
@@ -809,7 +815,9 @@ class GATv2AttentionFunction(torch.autograd.Function):
             raise ValueError("dropout_p needs a seed (an int32[2] device tensor)")
         drop = (dropout_p, seed) if dropout_p != 0.0 else None
         xl_c, xr_c, att_c = xl.contiguous(), xr.contiguous(), att.contiguous()
-        out, stats = _attention.gatv2_attention(rowptr, colind, xl_c, xr_c, att_c, negative_slope=negative_slope, dropout=drop)
+        ctx.x16 = _is_x16(xl) or _is_x16(xr)
+        forward_op = _attention.gatv2_attention_x16 if ctx.x16 else _attention.gatv2_attention
+        out, stats = forward_op(rowptr, colind, xl_c, xr_c, att_c, negative_slope=negative_slope, dropout=drop)
         ctx.graph = (rowptr, colind, colptr, rowind)
         ctx.negative_slope, ctx.dropout_p = negative_slope, dropout_p
         if drop is None:
@@ -825,12 +833,13 @@ class GATv2AttentionFunction(torch.autograd.Function):
         xl, xr, att, out, stats = ctx.saved_tensors[:5]
         drop = (ctx.dropout_p, ctx.saved_tensors[5]) if ctx.dropout_p != 0.0 else None
         slope = ctx.negative_slope
+        row_op = _attention.gatv2_attention_backward_row_x16 if ctx.x16 else _attention.gatv2_attention_backward_row
+        col_op = _attention.gatv2_attention_backward_col_x16 if ctx.x16 else _attention.gatv2_attention_backward_col
         grad_xl = grad_xr = grad_att = None
         if any(ctx.needs_input_grad[4:7]):
             grad_out = grad_out.contiguous()
             want_att = bool(ctx.needs_input_grad[6])
-            res = _attention.gatv2_attention_backward_row(rowptr, colind, xl, xr, att, stats, out, grad_out, negative_slope=slope,
-                                                          dropout=drop, want_att_part=want_att)
+            res = row_op(rowptr, colind, xl, xr, att, stats, out, grad_out, negative_slope=slope, dropout=drop, want_att_part=want_att)
             delta, grad_xl = res[0], res[1]
             if want_att:
                 grad_att = res[2].sum(0)
@@ -838,8 +847,7 @@ class GATv2AttentionFunction(torch.autograd.Function):
             if not ctx.needs_input_grad[4]:
                 grad_xl = None
             if ctx.needs_input_grad[5]:
-                grad_xr = _attention.gatv2_attention_backward_col(colptr, rowind, xl, xr, att, stats, delta, grad_out, negative_slope=slope,
-                                                                  dropout=drop)
+                grad_xr = col_op(colptr, rowind, xl, xr, att, stats, delta, grad_out, negative_slope=slope, dropout=drop)
         return None, None, None, None, grad_xl, grad_xr, grad_att, None, None, None
 
 
@@ -854,7 +862,7 @@ class GATv2Conv(torch.nn.Module):
     then heads concatenated (``concat=True``: [n, H F]) or averaged ([n, F]), plus bias.
 
         GATv2Conv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0,
-                  fused=False)
+                  fused=False, fused_x16=False)
         forward(x, rowptr, colind, colptr, rowind, csc_order, attn_seed=None)
 
     ``share_weights=True``: one matrix for both terms (W_dst is W_src). ``dropout=p`` (0 <= p < 1): ``EdgeDropoutFunction`` on alpha in
@@ -876,11 +884,20 @@ class GATv2Conv(torch.nn.Module):
     ``GATv2ScoreFunction`` on ``sddmm.gatv2_score_x16`` (fp32 result; both gradient passes on ``sddmm.gatv2_score_backward_x16``),
     softmax and dropout are the unchanged fp32 ops, the aggregation is the 16-bit product (``MultiHeadSPMMFunction`` on
     ``spmm.csr_spmm_heads_x16``: fp32 sums, one rounding) and the bias add is torch's. ``share_weights=True`` works as in fp32.
-    ``fused=True`` — the fused attention kernels — is fp32 only: 16-bit features raise TypeError."""
+    ``fused=True`` alone refuses 16-bit features with a TypeError.
+
+    ``fused=True, fused_x16=True``: 16-bit features run ``GATv2AttentionFunction`` on the 16-bit terms (``attention.gatv2_attention_x16``
+    and its two backward passes: fp32 sums, one rounding per 16-bit result, nothing of size ``[nnz, H]``), with ``att`` passed as
+    ``self.att.view(H, F).float()`` as in the unfused 16-bit path; fp32 features run exactly what ``fused=True`` runs. The keyword exists
+    because the refusal of ``fused=True`` on 16-bit features is pinned by committed tests; it is to be folded into ``fused=True`` when
+    those tests may change. ``fused_x16=True`` without ``fused=True`` is a ValueError."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, share_weights=False, dropout=0.0,
-                 fused=False):
+                 fused=False, fused_x16=False):
         super().__init__()
+        if fused_x16 and not fused:
+            raise ValueError("fused_x16=True selects the 16-bit form of the fused attention: it needs fused=True")
+        self.fused_x16 = bool(fused_x16)
         if fused and out_channels > _attention.GATV2_ATTENTION_MAX_F:
             raise ValueError("fused=True serves out_channels <= %d (a head slice is held in registers), got %d" %
                              (_attention.GATV2_ATTENTION_MAX_F, out_channels))
@@ -924,10 +941,13 @@ class GATv2Conv(torch.nn.Module):
         xr = (x @ self.weight_src).view(n, H, F)
         xl = xr if self.share_weights else (x @ self.weight_dst).view(n, H, F)
         if self.fused:
+            att = self.att.view(H, F)
             if _is_x16(xl) or _is_x16(xr):
-                raise TypeError("GATv2Conv(fused=True) needs torch.float32 features, got %s: attention.gatv2_attention "
-                                "(GATv2AttentionFunction) is fp32 only" % xr.dtype)
-            out = GATv2AttentionFunction.apply(rowptr, colind, colptr, rowind, xl, xr, self.att.view(H, F), self.negative_slope, p, seed)
+                if not self.fused_x16:
+                    raise TypeError("GATv2Conv(fused=True) needs torch.float32 features, got %s: attention.gatv2_attention "
+                                    "(GATv2AttentionFunction) is fp32 only here; fused_x16=True selects the 16-bit form" % xr.dtype)
+                att = att.float()  # (autograd rounds its gradient back into the parameter's dtype)
+            out = GATv2AttentionFunction.apply(rowptr, colind, colptr, rowind, xl, xr, att, self.negative_slope, p, seed)
             out = out.reshape(n, H * F) if self.concat else out.mean(dim=1)
             return out if self.bias is None else out + self.bias
         # (att as fp32 — the same tensor in an fp32 layer; in a 16-bit one autograd rounds its gradient back into the parameter's dtype)

@@ -1070,6 +1070,54 @@ int gespmm_gatv2_attention_backward_col_dropout_f32(const int32_t* colptr, const
  * address (pass the least of the dense results' with xl's); the least of them decides V. Returns the length written or a GESPMM_E* code. */
 int gespmm_describe_gatv2_attention(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int xl_align, int xr_align, int att_align,
                                     char* out, int64_t capacity);
+/*
+ * ... on 16-bit node terms (new symbols of 0.5): xl, xr, out, grad_out, grad_xl and grad_xr are IEEE fp16 or bfloat16 (dtype:
+ * GESPMM_X16_F16 / GESPMM_X16_BF16, one type per call); att, stats, delta and att_part stay fp32 — parameters, row statistics and
+ * everything a sum over nodes is taken of, the split of gespmm_gatv2_score_x16.
+ * The arithmetic is the fp32 contract above, expression for expression: every 16-bit element is widened exactly at its use (subnormals
+ * included), t = fl32(widen(xl_j) + widen(xr_j)) is ONE fp32 add, the leaky branch is t >= 0; the score chain, the pinned dot, the xor
+ * butterfly and the online softmax are the fp32 kernel's; every accumulation is fp32, in entry order. _backward_row reads the STORED,
+ * 16-bit out for delta = dot(grad_out, out). Every 16-bit result is rounded ONCE, at its store (to nearest even, overflow to +-inf, NaN
+ * stays NaN); for grad_xr that is the one add of its two chains, then one rounding. No packed-fp16 arithmetic and no dot2.
+ * Geometry (gespmm_describe_gatv2_attention_x16): the fp32 kernel's with V counted in ELEMENTS — V in {4, 2, 1}, an 8 / 4 / 2-byte load
+ * of the 16-bit operands with att's V floats at the same positions; 8 elements per lane and operand; W the smallest power of two in
+ * 4 .. 64 with 8 W >= F; V the widest of 4 / 2 / 1 that divides F, whose 2 V bytes divide the address of every 16-bit dense operand and
+ * result and whose 4 V bytes divide the addresses of att and att_part. A 16-byte load form (V = 8) is deliberately not built.
+ * Lane positions, chains and orders are those of the fp32 kernels at the same (V, W): wherever gespmm_describe_gatv2_attention answers
+ * the same (V, W) for the widened operands (a 16-bit operand b bytes off a 16-byte boundary corresponds to an fp32 operand 2 b bytes
+ * off), stats, delta and att_part have the BITS of the fp32 entry points on the widened operands — _backward_row fed widen(out),
+ * _backward_col fed that delta — and out, grad_xl and grad_xr are those calls' results narrowed once.
+ * Checks, in this order: a dtype that is neither code -> GESPMM_EINVAL; then the fp32 ladder with limits in ELEMENT positions (M H F,
+ * K H F, nnz, nnz H, 2 M H <= 2^31 - 4097 -> else GESPMM_ERANGE; F > 512 -> GESPMM_ERR_UNSUPPORTED; nnz == 0 or F == 0 zero-fills the
+ * results); NULL (att_part excepted) -> GESPMM_EINVAL; a 16-bit pointer not 2-byte aligned, att, delta or att_part not 4-byte aligned,
+ * stats not 8-byte aligned -> GESPMM_EALIGN. xl and xr may be the same array. No atomics, no workspace, no allocation, no host
+ * synchronisation: capturable.
+ */
+int gespmm_gatv2_attention_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att, void* out,
+                               float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gatv2_attention_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att,
+                                       void* out, float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                       float slope, float p, const void* seed, void* stream);
+int gespmm_gatv2_attention_backward_row_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr, const float* att,
+                                            const float* stats, const void* out, const void* grad_out, float* delta, void* grad_xl,
+                                            float* att_part, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope,
+                                            void* stream);
+int gespmm_gatv2_attention_backward_row_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* xl, const void* xr,
+                                                    const float* att, const float* stats, const void* out, const void* grad_out,
+                                                    float* delta, void* grad_xl, float* att_part, int dtype, int64_t M, int64_t K, int64_t H,
+                                                    int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream);
+int gespmm_gatv2_attention_backward_col_x16(const int32_t* colptr, const int32_t* rowind, const void* xl, const void* xr, const float* att,
+                                            const float* stats, const float* delta, const void* grad_out, void* grad_xr, int dtype, int64_t M,
+                                            int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gatv2_attention_backward_col_dropout_x16(const int32_t* colptr, const int32_t* rowind, const void* xl, const void* xr,
+                                                    const float* att, const float* stats, const float* delta, const void* grad_out,
+                                                    void* grad_xr, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                                    float slope, float p, const void* seed, void* stream);
+/* Host only: what the three 16-bit entry points would launch, in the words of gespmm_describe_gatv2_attention. xl_align, xr_align:
+ * largest power of two (>= 2) dividing the 16-bit operands' addresses (pass the least of the 16-bit results' with them); att_align
+ * (>= 4): the least of att and att_part. Returns the length written or a GESPMM_E* code. */
+int gespmm_describe_gatv2_attention_x16(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int xl_align, int xr_align, int att_align,
+                                        char* out, int64_t capacity);
 /* New values on the unchanged pattern (val in the caller's CSR order, device memory; NULL = A == 1). */
 int gespmm_plan_set_values(gespmm_plan* plan, const float* val, void* stream);
 /* perm_host[i] = row processed at position i (HOST memory, M entries). Returns 1 if clustered, 0 if storage order. */
