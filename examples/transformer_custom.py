@@ -11,6 +11,10 @@ this library.
     python examples/transformer_custom.py --fused --graph-capture  # replay each step from a HIP graph (one stream)
     python examples/transformer_custom.py --beta                   # the gated skip connection
     python examples/transformer_custom.py --seed 0 --fused         # seeded parameters and dropout: the losses of --seed 0 to rounding
+    python examples/transformer_custom.py --dtype bf16             # a .bfloat16() model on bf16 features (or fp16): 16-bit SDDMM and
+                                                                   # aggregation, everything edge-sized stays fp32
+    python examples/transformer_custom.py --fused --dtype bf16     # ``TransformerConv(fused=True, fused_x16=True)``: the fused attention on
+                                                                   # bf16 (or fp16) q, k, v: no [nnz, H] array AND half the node bytes
 
 Data handling is that of examples/gcn_custom.py (same bundled adjacency, same synthetic features / labels / masks, so accuracy is
 chance level by construction); the point of the script is that the loss goes down and what an epoch costs.
@@ -36,7 +40,8 @@ from gespmm_amd import TransformerConv  # noqa: E402
 class Net(torch.nn.Module):
     def __init__(self, n_in, n_out, n_hidden=8, heads=8, dropout=0.6, fused=False, attn_dropout=0.0, beta=False):
         super().__init__()
-        kw = dict(fused=fused, dropout=attn_dropout, beta=beta)
+        # (fused_x16: a 16-bit model runs the fused attention on 16-bit q, k and v; an fp32 one runs what fused=True runs)
+        kw = dict(fused=fused, fused_x16=fused, dropout=attn_dropout, beta=beta)
         self.conv1 = TransformerConv(n_in, n_hidden, heads=heads, concat=True, **kw)
         self.conv2 = TransformerConv(n_hidden * heads, n_out, heads=1, concat=False, **kw)
         self.dropout = dropout
@@ -64,6 +69,9 @@ def main():
     ap.add_argument("--beta", action="store_true", help="TransformerConv(beta=True): the gated skip connection")
     ap.add_argument("--seed", type=int, default=None,
                     help="torch.manual_seed before the model is made (parameters and dropout masks)")
+    ap.add_argument("--dtype", choices=("fp32", "bf16", "fp16"), default="fp32",
+                    help="cast the model and the features (bf16 / fp16: TransformerConv on the 16-bit SDDMM and multi-head product, with "
+                         "--fused the fused attention on 16-bit q, k and v)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs a HIP device (the ops have no CPU path)")
@@ -87,7 +95,13 @@ def main():
         torch.manual_seed(args.seed)
     model = Net(n_feat, n_cls, args.n_hidden, args.heads, args.dropout, fused=args.fused, attn_dropout=args.attn_dropout,
                 beta=args.beta).to(device)
-    optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture)
+    if args.dtype != "fp32":
+        dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
+        model = model.to(dtype)
+        x = x.to(dtype)
+    # (fp16 parameters: Adam's default eps, 1e-8, is zero in fp16 and a parameter whose gradient is zero would be updated by 0 / 0)
+    adam = {"eps": 1e-4} if args.dtype == "fp16" else {}
+    optimizer = torch.optim.Adam(model.parameters(), lr=0.005, weight_decay=5e-4, capturable=args.graph_capture, **adam)
     train_idx = masks["train"].nonzero().squeeze(1)
     y_train = y[train_idx]
 
@@ -147,7 +161,7 @@ def main():
     wall = time.perf_counter() - t0
     print("dataset=%s n=%d nnz(+I)=%d heads=%d hidden=%d graph_capture=%s fused=%s beta=%s%s" %
           (args.dataset, n_v, g["colind"].numel(), args.heads, args.n_hidden, args.graph_capture, args.fused, args.beta,
-           " attn_dropout=%g" % args.attn_dropout if args.attn_dropout else ""))
+           (" attn_dropout=%g" % args.attn_dropout if args.attn_dropout else "") + (" dtype=%s" % args.dtype if args.dtype != "fp32" else "")))
     print("epochs=%d  gpu %.3f ms/epoch  wall %.3f ms/epoch" %
           (args.epochs, e0.elapsed_time(e1) / args.epochs, wall * 1e3 / args.epochs))
 

@@ -142,6 +142,13 @@ EXPORTS = [
     "gespmm_dot_attention_backward_kv_f32",
     "gespmm_dot_attention_backward_kv_dropout_f32",
     "gespmm_describe_dot_attention",
+    "gespmm_dot_attention_x16",
+    "gespmm_dot_attention_dropout_x16",
+    "gespmm_dot_attention_backward_q_x16",
+    "gespmm_dot_attention_backward_q_dropout_x16",
+    "gespmm_dot_attention_backward_kv_x16",
+    "gespmm_dot_attention_backward_kv_dropout_x16",
+    "gespmm_describe_dot_attention_x16",
     "gespmm_gatv2_attention_f32",
     "gespmm_gatv2_attention_dropout_f32",
     "gespmm_gatv2_attention_backward_row_f32",
@@ -412,6 +419,18 @@ def _load():
         f.argtypes = [p] * 10 + [c_int64] * 5 + [c_float, c_float, p, p]
     lib.gespmm_describe_dot_attention.restype = c_int
     lib.gespmm_describe_dot_attention.argtypes = [c_int64] * 5 + [c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_dot_attention_x16.restype = c_int
+    lib.gespmm_dot_attention_x16.argtypes = [p] * 7 + [c_int] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_dot_attention_dropout_x16.restype = c_int
+    lib.gespmm_dot_attention_dropout_x16.argtypes = [p] * 7 + [c_int] + [c_int64] * 5 + [c_float, c_float, p, p]
+    for f in (lib.gespmm_dot_attention_backward_q_x16, lib.gespmm_dot_attention_backward_kv_x16):
+        f.restype = c_int
+        f.argtypes = [p] * 10 + [c_int] + [c_int64] * 5 + [c_float, p]
+    for f in (lib.gespmm_dot_attention_backward_q_dropout_x16, lib.gespmm_dot_attention_backward_kv_dropout_x16):
+        f.restype = c_int
+        f.argtypes = [p] * 10 + [c_int] + [c_int64] * 5 + [c_float, c_float, p, p]
+    lib.gespmm_describe_dot_attention_x16.restype = c_int
+    lib.gespmm_describe_dot_attention_x16.argtypes = [c_int64] * 5 + [c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_gatv2_attention_f32.restype = c_int
     lib.gespmm_gatv2_attention_f32.argtypes = [p] * 7 + [c_int64] * 5 + [c_float, p]
     lib.gespmm_gatv2_attention_dropout_f32.restype = c_int
@@ -573,15 +592,19 @@ ERR_UNSUPPORTED = -7
 DOT_ATTENTION_MAX_F = 512
 
 
-def describe_dot_attention(M, K, H, F, nnz, q_align=16, k_align=16, v_align=16):
-    """The lane geometry of gespmm_dot_attention_f32 and its two backward passes for these sizes and operand alignments
-    (gespmm_describe_dot_attention: host only) — a dict ``{"V": floats per load, "W": lanes per (segment, head) pair}``;
-    ``{"route": "unsupported"}`` when F > 512 (no kernel), ``{"route": "zeros"}`` when F == 0 and ``{"form": "none"}`` when nnz == 0.
-    V and W fix the dot's summation order; the least aligned dense operand of a launch decides V."""
+def describe_dot_attention(M, K, H, F, nnz, q_align=16, k_align=16, v_align=16, x16=False):
+    """The lane geometry of gespmm_dot_attention_f32 — x16=True: gespmm_dot_attention_x16, fp16 / bf16 q, k and v — and its two backward
+    passes for these sizes and operand alignments (gespmm_describe_dot_attention / _x16: host only) — a dict ``{"V": floats per load,
+    "W": lanes per (segment, head) pair}``; ``{"route": "unsupported"}`` when F > 512 (no kernel), ``{"route": "zeros"}`` when F == 0
+    and ``{"form": "none"}`` when nnz == 0. V and W fix the dot's summation order; the least aligned dense operand of a launch — the
+    dense results included — decides V. x16: V counts elements and stays in 4 / 2 / 1; 2 V bytes divide the operands' addresses
+    (alignments from 2) — the fp32 answer at twice each alignment."""
     buf = ctypes.create_string_buffer(96)
-    n = lib.gespmm_describe_dot_attention(int(M), int(K), int(H), int(F), int(nnz), int(q_align), int(k_align), int(v_align), buf, 96)
+    f, name = (lib.gespmm_describe_dot_attention_x16, "gespmm_describe_dot_attention_x16") if x16 else \
+        (lib.gespmm_describe_dot_attention, "gespmm_describe_dot_attention")
+    n = f(int(M), int(K), int(H), int(F), int(nnz), int(q_align), int(k_align), int(v_align), buf, 96)
     if n < 0:
-        raise GespmmError(n, "gespmm_describe_dot_attention")
+        raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k in ("form", "route") else int(v)) for k, v in out.items()}
 

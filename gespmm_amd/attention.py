@@ -16,7 +16,15 @@ entry p of row r with column c and head h
 ``grad_v``; no ``csc_order``), both recomputing ``s_p`` and ``a_p`` with the same bits. ``dropout=(p, seed)`` puts ``softmax.edge_dropout``'s
 mask on ``a_p``: the decision of an entry is a function of ``(seed, row, column, head)``, recomputed wherever it is needed. Lane geometry
 and summation orders: include/gespmm.h and ``_lib.describe_dot_attention``. A head slice wider than 512 floats has no kernel: the calls
-raise a ``GespmmError`` that says so. fp32 only: other dtypes raise TypeError. All calls go through ctypes.
+raise a ``GespmmError`` that says so. These three names are fp32 only: other dtypes raise TypeError. All calls go through ctypes. On
+fp16 / bf16 q, k and v (``stats`` and ``delta`` stay fp32; fp32 sums, every 16-bit result rounded once at its store):
+
+    dot_attention_x16(rowptr, colind, q, k, v, scale=None, dropout=None, out=None, stats=None)               -> (out x16[M, H, F], stats f32[M, H, 2])
+    dot_attention_backward_q_x16(rowptr, colind, q, k, v, stats, out, grad_out, scale=None, dropout=None, results=None)    -> (delta f32[M, H], grad_q x16[M, H, F])
+    dot_attention_backward_kv_x16(colptr, rowind, q, k, v, stats, delta, grad_out, scale=None, dropout=None, results=None) -> (grad_k, grad_v) x16[K, H, F]
+
+Where ``_lib.describe_dot_attention`` answers the same (V, W) with and without ``x16=True``, ``stats`` and ``delta`` have the bits of the
+fp32 calls on the widened operands and ``out``, ``grad_q``, ``grad_k``, ``grad_v`` are theirs narrowed once.
 
 Fused GATv2 attention (Brody et al.) — score, softmax and aggregation in one sweep, the same contract otherwise:
 
@@ -576,3 +584,122 @@ def gatv2_attention_backward_col_x16(colptr, rowind, xl, xr, att, stats, delta, 
             rc = lib.gespmm_gatv2_attention_backward_col_x16(*args, _stream(dev))
     check(rc, "gespmm_gatv2_attention_backward_col_dropout_x16" if dropout is not None else "gespmm_gatv2_attention_backward_col_x16")
     return grad_xr
+
+
+# ---- the fused dot-product attention on fp16 / bf16 q, k and v (gespmm_dot_attention_x16 and its backward)
+
+def dot_attention_x16(rowptr, colind, q, k, v, scale=None, dropout=None, out=None, stats=None):
+    """``dot_attention`` on 16-bit node terms (gespmm_dot_attention_x16 / _dropout_x16): ``q`` [M, H, F], ``k`` and ``v`` [K, H, F] all
+    ``torch.float16`` or all ``torch.bfloat16``. Returns ``(out, stats)``: ``out`` [M, H, F] in the terms' dtype, fp32 sums rounded once
+    at the store; ``stats`` f32[M, H, 2]. Every element is widened exactly at its use and the arithmetic is ``dot_attention``'s: where
+    ``_lib.describe_dot_attention`` answers the same (V, W) with and without ``x16=True``, ``stats`` has the bits of ``dot_attention`` on
+    ``q.float(), k.float(), v.float()`` and ``out`` is that call's ``out`` narrowed once. A 16-bit ``stats``, fp32 node terms and mixed
+    16-bit dtypes raise TypeError."""
+    x16 = _typed_x16((("rowptr", rowptr), ("colind", colind)), (("q", q), ("k", k), ("v", v), ("out", out)), (("stats", stats),))
+    _required((("rowptr", rowptr), ("colind", colind), ("q", q), ("k", k), ("v", v)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _shapes(rowptr, "rowptr", colind, "colind", q, k, v, True)
+    sc = _scale(scale, F)
+    _shaped(out, "out", (M, H, F))
+    _shaped(stats, "stats", (M, H, 2))
+    dev = q.device
+    _placed((("rowptr", rowptr), ("colind", colind), ("q", q), ("k", k), ("v", v), ("out", out), ("stats", stats)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _served(F, "gespmm_dot_attention_x16")
+    if out is None:
+        out = torch.empty((M, H, F), dtype=q.dtype, device=dev)
+    if stats is None:
+        stats = torch.empty((M, H, 2), dtype=torch.float32, device=dev)
+    if M == 0:  # (results of no words have no address to hand over)
+        return out, stats
+    args = (_ptr(rowptr), _ptr(colind), _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(stats), x16, M, K, H, F, nnz, sc)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_dot_attention_dropout_x16(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_dot_attention_x16(*args, _stream(dev))
+    check(rc, "gespmm_dot_attention_dropout_x16" if dropout is not None else "gespmm_dot_attention_x16")
+    return out, stats
+
+
+def dot_attention_backward_q_x16(rowptr, colind, q, k, v, stats, out, grad_out, scale=None, dropout=None, results=None):
+    """``dot_attention_backward_q`` on 16-bit node terms (gespmm_dot_attention_backward_q_x16 / _dropout_x16): ``q``, ``k``, ``v``,
+    ``out``, ``grad_out`` and the result ``grad_q`` in one 16-bit dtype; ``stats`` and the result ``delta`` f32[M, H] stay fp32.
+    ``delta`` is taken of the STORED 16-bit ``out``; ``grad_q`` is ``fl32(scale * chain)`` rounded once at the store. Returns
+    ``(delta, grad_q)``. On equal (V, W) ``delta`` has the bits of ``dot_attention_backward_q`` on the widened operands and ``grad_q`` is
+    its ``grad_q`` narrowed once. ``results``: a pair ``(delta, grad_q)`` to write into."""
+    delta, grad_q = _pair(results)
+    x16 = _typed_x16((("rowptr", rowptr), ("colind", colind)),
+                     (("q", q), ("k", k), ("v", v), ("out", out), ("grad_out", grad_out), ("results[1]", grad_q)),
+                     (("stats", stats), ("results[0]", delta)))
+    _required((("rowptr", rowptr), ("colind", colind), ("q", q), ("k", k), ("v", v), ("stats", stats), ("out", out), ("grad_out", grad_out)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _shapes(rowptr, "rowptr", colind, "colind", q, k, v, True)
+    sc = _scale(scale, F)
+    _shaped(stats, "stats", (M, H, 2))
+    _shaped(out, "out", (M, H, F))
+    _shaped(grad_out, "grad_out", (M, H, F))
+    _shaped(delta, "results[0]", (M, H))
+    _shaped(grad_q, "results[1]", (M, H, F))
+    dev = q.device
+    _placed((("rowptr", rowptr), ("colind", colind), ("q", q), ("k", k), ("v", v), ("stats", stats), ("out", out), ("grad_out", grad_out),
+             ("results[0]", delta), ("results[1]", grad_q)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _served(F, "gespmm_dot_attention_backward_q_x16")
+    if delta is None:
+        delta = torch.empty((M, H), dtype=torch.float32, device=dev)
+        grad_q = torch.empty((M, H, F), dtype=q.dtype, device=dev)
+    if M == 0:
+        return delta, grad_q
+    args = (_ptr(rowptr), _ptr(colind), _ptr(q), _ptr(k), _ptr(v), _ptr(stats), _ptr(out), _ptr(grad_out), _ptr(delta), _ptr(grad_q), x16, M,
+            K, H, F, nnz, sc)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_dot_attention_backward_q_dropout_x16(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_dot_attention_backward_q_x16(*args, _stream(dev))
+    check(rc, "gespmm_dot_attention_backward_q_dropout_x16" if dropout is not None else "gespmm_dot_attention_backward_q_x16")
+    return delta, grad_q
+
+
+def dot_attention_backward_kv_x16(colptr, rowind, q, k, v, stats, delta, grad_out, scale=None, dropout=None, results=None):
+    """``dot_attention_backward_kv`` on 16-bit node terms (gespmm_dot_attention_backward_kv_x16 / _dropout_x16): ``q``, ``k``, ``v``,
+    ``grad_out`` and the results ``grad_k``, ``grad_v`` [K, H, F] in one 16-bit dtype; ``stats`` and ``delta`` (the row pass's) stay
+    fp32. ``grad_k`` is ``fl32(scale * chain)`` and ``grad_v`` its chain, each rounded once at the store: on equal (V, W) they are
+    ``dot_attention_backward_kv``'s on the widened operands, narrowed once. ``results``: a pair ``(grad_k, grad_v)`` to write into."""
+    grad_k, grad_v = _pair(results)
+    x16 = _typed_x16((("colptr", colptr), ("rowind", rowind)),
+                     (("q", q), ("k", k), ("v", v), ("grad_out", grad_out), ("results[0]", grad_k), ("results[1]", grad_v)),
+                     (("stats", stats), ("delta", delta)))
+    _required((("colptr", colptr), ("rowind", rowind), ("q", q), ("k", k), ("v", v), ("stats", stats), ("delta", delta),
+               ("grad_out", grad_out)))
+    _dropout_typed(dropout)
+    M, K, H, F, nnz = _shapes(colptr, "colptr", rowind, "rowind", q, k, v, False)
+    sc = _scale(scale, F)
+    _shaped(stats, "stats", (M, H, 2))
+    _shaped(delta, "delta", (M, H))
+    _shaped(grad_out, "grad_out", (M, H, F))
+    _shaped(grad_k, "results[0]", (K, H, F))
+    _shaped(grad_v, "results[1]", (K, H, F))
+    dev = q.device
+    _placed((("colptr", colptr), ("rowind", rowind), ("q", q), ("k", k), ("v", v), ("stats", stats), ("delta", delta),
+             ("grad_out", grad_out), ("results[0]", grad_k), ("results[1]", grad_v)), dev)
+    if dropout is not None:
+        p, seed = _dropout(dropout, dev)
+    _served(F, "gespmm_dot_attention_backward_kv_x16")
+    if grad_k is None:
+        grad_k = torch.empty((K, H, F), dtype=q.dtype, device=dev)
+        grad_v = torch.empty((K, H, F), dtype=q.dtype, device=dev)
+    if K == 0:
+        return grad_k, grad_v
+    args = (_ptr(colptr), _ptr(rowind), _ptr(q), _ptr(k), _ptr(v), _ptr(stats), _ptr(delta), _ptr(grad_out), _ptr(grad_k), _ptr(grad_v), x16,
+            M, K, H, F, nnz, sc)
+    with _on_device(dev):
+        if dropout is not None:
+            rc = lib.gespmm_dot_attention_backward_kv_dropout_x16(*args, p, _ptr(seed), _stream(dev))
+        else:
+            rc = lib.gespmm_dot_attention_backward_kv_x16(*args, _stream(dev))
+    check(rc, "gespmm_dot_attention_backward_kv_dropout_x16" if dropout is not None else "gespmm_dot_attention_backward_kv_x16")
+    return grad_k, grad_v

@@ -27,6 +27,7 @@
 #include "gat_aggregate.h"
 #include "gat_backward.h"
 #include "dot_attention.h"
+#include "dot_attention_x16.h"
 #include "gatv2_attention.h"
 #include "gatv2_attention_x16.h"
 #include "gatv2_score.h"
@@ -2030,6 +2031,138 @@ int gespmm_describe_gatv2_attention_x16(int64_t M, int64_t K, int64_t H, int64_t
         const gespmm::Gatv2AttentionLaunch r = gespmm::resolve_gatv2_attention_x16(
             F, xl_align > 16 ? 16 : xl_align, xr_align > 16 ? 16 : xr_align, att_align > 16 ? 16 : att_align);
         n = snprintf(out, (size_t)capacity, "V=%d W=%d supported=%d", r.V, r.W, r.supported ? 1 : 0);
+    }
+    return describe_result(n, capacity);
+}
+
+/* The fused dot-product attention on fp16 / bf16 q, k and v (gespmm.h; dot_attention_x16.h): the dtype code first, as in every _x16
+   entry, then the ladder of the _f32 entries with 2-byte alignment for the 16-bit operands and results. stats and delta stay fp32. */
+static int dot_attention_x16_entry(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v, void* out,
+                                   float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale,
+                                   const float* p, const void* seed, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, scale, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {  // every row is empty: every word of the results is still written
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill_x16({{out, 2, (size_t)(M * H * F)}, {stats, 4, (size_t)(M * H * 2)}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {q, 2, true}, {k, 2, true}, {v, 2, true}, {out, 2, true},
+                                        {stats, 8, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({q, k, v, out});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_dot_attention_x16(rowptr, colind, q, k, v, out, stats, dtype, M, K, H, F, nnz, scale,
+                                                 gespmm::resolve_dot_attention_x16(F, a, a, a), p ? &dropout : nullptr, st);
+}
+
+int gespmm_dot_attention_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v, void* out,
+                             float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream) {
+    return dot_attention_x16_entry(rowptr, colind, q, k, v, out, stats, dtype, M, K, H, F, nnz, scale, nullptr, nullptr, stream);
+}
+
+int gespmm_dot_attention_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v, void* out,
+                                     float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                     const void* seed, void* stream) {
+    return dot_attention_x16_entry(rowptr, colind, q, k, v, out, stats, dtype, M, K, H, F, nnz, scale, &p, seed, stream);
+}
+
+static int dot_attention_backward_q_x16_entry(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v,
+                                              const float* stats, const void* out, const void* grad_out, float* delta, void* grad_q,
+                                              int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale,
+                                              const float* p, const void* seed, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, scale, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill_x16({{delta, 4, (size_t)(M * H)}, {grad_q, 2, (size_t)(M * H * F)}}, st);
+    }
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {q, 2, true}, {k, 2, true}, {v, 2, true}, {stats, 8, true},
+                                        {out, 2, true}, {grad_out, 2, true}, {delta, 4, true}, {grad_q, 2, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({q, k, v, out, grad_out, grad_q});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_dot_attention_backward_q_x16(rowptr, colind, q, k, v, stats, out, grad_out, delta, grad_q, dtype, M, K, H, F,
+                                                            nnz, scale, gespmm::resolve_dot_attention_x16(F, a, a, a),
+                                                            p ? &dropout : nullptr, st);
+}
+
+int gespmm_dot_attention_backward_q_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v,
+                                        const float* stats, const void* out, const void* grad_out, float* delta, void* grad_q, int dtype,
+                                        int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream) {
+    return dot_attention_backward_q_x16_entry(rowptr, colind, q, k, v, stats, out, grad_out, delta, grad_q, dtype, M, K, H, F, nnz, scale,
+                                              nullptr, nullptr, stream);
+}
+
+int gespmm_dot_attention_backward_q_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v,
+                                                const float* stats, const void* out, const void* grad_out, float* delta, void* grad_q,
+                                                int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                                const void* seed, void* stream) {
+    return dot_attention_backward_q_x16_entry(rowptr, colind, q, k, v, stats, out, grad_out, delta, grad_q, dtype, M, K, H, F, nnz, scale, &p,
+                                              seed, stream);
+}
+
+static int dot_attention_backward_kv_x16_entry(const int32_t* colptr, const int32_t* rowind, const void* q, const void* k, const void* v,
+                                               const float* stats, const float* delta, const void* grad_out, void* grad_k, void* grad_v,
+                                               int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale,
+                                               const float* p, const void* seed, void* stream) {
+    if (!gespmm::valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, scale, p);
+    if (rc != 0) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0 || F == 0) {
+        if (const int rcp = check_pointers({{seed, 4, p != nullptr}})) return rcp;
+        return zero_fill_x16({{grad_k, 2, (size_t)(K * H * F)}, {grad_v, 2, (size_t)(K * H * F)}}, st);
+    }
+    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {q, 2, true}, {k, 2, true}, {v, 2, true}, {stats, 8, true},
+                                        {delta, 4, true}, {grad_out, 2, true}, {grad_k, 2, true}, {grad_v, 2, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    const int a = gespmm::least_alignment({q, k, v, grad_out, grad_k, grad_v});
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    return (int)gespmm::launch_dot_attention_backward_kv_x16(colptr, rowind, q, k, v, stats, delta, grad_out, grad_k, grad_v, dtype, M, K, H,
+                                                             F, nnz, scale, gespmm::resolve_dot_attention_x16(F, a, a, a),
+                                                             p ? &dropout : nullptr, st);
+}
+
+int gespmm_dot_attention_backward_kv_x16(const int32_t* colptr, const int32_t* rowind, const void* q, const void* k, const void* v,
+                                         const float* stats, const float* delta, const void* grad_out, void* grad_k, void* grad_v, int dtype,
+                                         int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream) {
+    return dot_attention_backward_kv_x16_entry(colptr, rowind, q, k, v, stats, delta, grad_out, grad_k, grad_v, dtype, M, K, H, F, nnz, scale,
+                                               nullptr, nullptr, stream);
+}
+
+int gespmm_dot_attention_backward_kv_dropout_x16(const int32_t* colptr, const int32_t* rowind, const void* q, const void* k, const void* v,
+                                                 const float* stats, const float* delta, const void* grad_out, void* grad_k, void* grad_v,
+                                                 int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                                 const void* seed, void* stream) {
+    return dot_attention_backward_kv_x16_entry(colptr, rowind, q, k, v, stats, delta, grad_out, grad_k, grad_v, dtype, M, K, H, F, nnz, scale,
+                                               &p, seed, stream);
+}
+
+int gespmm_describe_dot_attention_x16(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int q_align, int k_align, int v_align,
+                                      char* out, int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    for (const int a : {q_align, k_align, v_align})
+        if (a < 2 || (a & (a - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_dot_attention_sizes(M, K, H, F, nnz, 1.0f, nullptr);
+    if (rc != 0 && rc != GESPMM_ERR_UNSUPPORTED) return rc;
+    int n;
+    if (rc == GESPMM_ERR_UNSUPPORTED) {
+        n = snprintf(out, (size_t)capacity, "route=unsupported");
+    } else if (nnz == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else if (F == 0) {
+        n = snprintf(out, (size_t)capacity, "route=zeros");
+    } else {
+        const gespmm::DotAttentionLaunch r =
+            gespmm::resolve_dot_attention_x16(F, q_align > 16 ? 16 : q_align, k_align > 16 ? 16 : k_align, v_align > 16 ? 16 : v_align);
+        n = snprintf(out, (size_t)capacity, "V=%d W=%d", r.V, r.W);
     }
     return describe_result(n, capacity);
 }

@@ -355,6 +355,13 @@ DotAttentionLaunch resolve_dot_attention(int64_t F, int q_align, int k_align, in
     return DotAttentionLaunch{b.V, b.W, F <= kDotAttentionMaxF};
 }
 
+// ... on 16-bit q, k and v: the fp32 rule at twice each alignment, capped at 16, so that both resolvers answer the same (V, W) for an
+// operand and its widened copy placed to match. No V = 8 (a 16-byte load of 16-bit elements): it would move the dot's lane positions.
+DotAttentionLaunch resolve_dot_attention_x16(int64_t F, int q_align, int k_align, int v_align) {
+    const auto twice = [](int a) { return 2 * a > 16 ? 16 : 2 * a; };
+    return resolve_dot_attention(F, twice(q_align), twice(k_align), twice(v_align));
+}
+
 // The fused GATv2 attention: the same rule — the one resolve_gatv2_score applies to its three operands — so that on equally aligned
 // operands the fused score has the lane positions, hence the bits, of gespmm_gatv2_score_f32. Nothing here was measured for these
 // kernels.

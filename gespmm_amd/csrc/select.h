@@ -91,6 +91,10 @@ struct DotAttentionLaunch {
 };
 // F >= 1. *_align: largest power of two (bytes) that divides an operand's address — the least of a launch's dense operands decides.
 DotAttentionLaunch resolve_dot_attention(int64_t F, int q_align, int k_align, int v_align);
+// ... on 16-bit node terms (dot_attention_x16.h): V counts ELEMENTS and stays in {4, 2, 1} — 2 V bytes divide every alignment (the least
+// of the 16-bit operands and results, >= 2). The answer is resolve_dot_attention's at twice each alignment, capped at 16: a 16-bit
+// operand b bytes off a 16-byte boundary is an fp32 operand 2 b bytes off.
+DotAttentionLaunch resolve_dot_attention_x16(int64_t F, int q_align, int k_align, int v_align);
 
 // ---- fused GATv2 attention (gatv2_attention.h): the lane geometry of its three kernels (gespmm_describe_gatv2_attention prints it).
 constexpr int64_t kGatv2AttentionMaxF = 512;  // a lane holds 8 floats of a head slice, a lane group has at most 64 lanes

@@ -58,7 +58,8 @@ every output word (``spmm.csr_spmm_max_arg``), the backward adds ``grad_out`` wh
 and ``SAGEConv`` DGL's layer of that name with the ``mean``, ``gcn`` and ``pool`` aggregators.
 Graph transformers (extension): ``DotAttentionFunction`` is scaled dot-product attention over the edges in three fused launches
 (``attention.dot_attention`` and its two backward passes: no score, no alpha, nothing of size nnz saved), ``TransformerConv`` PyG's layer
-of that name on it (``fused=True``) or on the composition of the functions above (the default).
+of that name on it (``fused=True``) or on the composition of the functions above (the default) — and on fp16 / bf16 q, k and v
+(``attention.dot_attention_x16`` and its two backward passes), behind ``TransformerConv(fused=True, fused_x16=True)``.
 ``GATv2AttentionFunction`` is the same for GATv2 — score, softmax, dropout and aggregation in one launch on one gathered row per entry
 (``attention.gatv2_attention`` and its two backward passes), behind ``GATv2Conv(fused=True)`` — and on fp16 / bf16 node terms
 (``attention.gatv2_attention_x16`` and its two backward passes), behind ``GATv2Conv(fused=True, fused_x16=True)``.
@@ -975,7 +976,12 @@ class DotAttentionFunction(torch.autograd.Function):
     ``scale=None``: 1 / sqrt(F). No score and no attention array exists in either direction: the function saves ``q, k, v, out`` and the
     [M, H, 2] softmax statistics (and the two seed words), nothing of size nnz. ``dropout_p > 0`` with ``seed`` (int32[2] on the device):
     dropout on the coefficients with ``EdgeDropoutFunction``'s mask, recomputed in all three launches; the seed is read when the backward
-    runs. F <= 512. Index tensors get no gradient. Both backward launches run whenever any of q, k, v requires grad."""
+    runs. F <= 512. Index tensors get no gradient. Both backward launches run whenever any of q, k, v requires grad.
+
+    16-bit ``q``, ``k`` and ``v`` (all ``torch.float16`` or all ``torch.bfloat16``; anything mixed is a TypeError): the same three
+    launches through ``attention.dot_attention_x16`` / ``dot_attention_backward_q_x16`` / ``dot_attention_backward_kv_x16``. Saved: the
+    16-bit ``q, k, v, out`` and the fp32 ``stats``. ``out``, ``grad_q``, ``grad_k`` and ``grad_v`` come in the inputs' dtype (fp32 sums,
+    one rounding each)."""
 
     @staticmethod
     def forward(ctx, q, k, v, rowptr, colind, colptr, rowind, scale=None, dropout_p=0.0, seed=None):
@@ -984,7 +990,9 @@ class DotAttentionFunction(torch.autograd.Function):
             raise ValueError("dropout_p needs a seed (an int32[2] device tensor)")
         drop = (dropout_p, seed) if dropout_p != 0.0 else None
         q_c, k_c, v_c = q.contiguous(), k.contiguous(), v.contiguous()
-        out, stats = _attention.dot_attention(rowptr, colind, q_c, k_c, v_c, scale=scale, dropout=drop)
+        ctx.x16 = _is_x16(q) or _is_x16(k) or _is_x16(v)
+        forward_op = _attention.dot_attention_x16 if ctx.x16 else _attention.dot_attention
+        out, stats = forward_op(rowptr, colind, q_c, k_c, v_c, scale=scale, dropout=drop)
         ctx.graph = (rowptr, colind, colptr, rowind)
         ctx.scale, ctx.dropout_p = scale, dropout_p
         if drop is None:
@@ -999,13 +1007,14 @@ class DotAttentionFunction(torch.autograd.Function):
         rowptr, colind, colptr, rowind = ctx.graph
         q, k, v, out, stats = ctx.saved_tensors[:5]
         drop = (ctx.dropout_p, ctx.saved_tensors[5]) if ctx.dropout_p != 0.0 else None
+        q_op = _attention.dot_attention_backward_q_x16 if ctx.x16 else _attention.dot_attention_backward_q
+        kv_op = _attention.dot_attention_backward_kv_x16 if ctx.x16 else _attention.dot_attention_backward_kv
         grad_q = grad_k = grad_v = None
         if any(ctx.needs_input_grad[:3]):
             grad_out = grad_out.contiguous()
-            delta, grad_q = _attention.dot_attention_backward_q(rowptr, colind, q, k, v, stats, out, grad_out, scale=ctx.scale, dropout=drop)
+            delta, grad_q = q_op(rowptr, colind, q, k, v, stats, out, grad_out, scale=ctx.scale, dropout=drop)
             if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-                grad_k, grad_v = _attention.dot_attention_backward_kv(colptr, rowind, q, k, v, stats, delta, grad_out, scale=ctx.scale,
-                                                                      dropout=drop)
+                grad_k, grad_v = kv_op(colptr, rowind, q, k, v, stats, delta, grad_out, scale=ctx.scale, dropout=drop)
         return grad_q, grad_k, grad_v, None, None, None, None, None, None, None
 
 
@@ -1021,7 +1030,7 @@ class TransformerConv(torch.nn.Module):
     added — or, with ``beta``, gated: ``b = sigmoid(lin_beta([out, x_r, out - x_r]))``, ``out = b x_r + (1 - b) out``.
 
         TransformerConv(in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, bias=True, root_weight=True, fused=False,
-                        attn_seed=None)
+                        attn_seed=None, fused_x16=False)
         forward(x, rowptr, colind, colptr, rowind, csc_order)
 
     ``fused=False`` (the default) composes the attention from ``MultiHeadSDDMMFunction``, the scaling, ``EdgeSoftmaxFunction`` (no slope),
@@ -1037,11 +1046,19 @@ class TransformerConv(torch.nn.Module):
 
     16-bit ``x`` (a ``.half()`` / ``.bfloat16()`` layer, or ``torch.autocast``) with ``fused=False``: q, k and v stay 16-bit, the score
     (``MultiHeadSDDMMFunction`` on ``sddmm.csr_sddmm_heads_x16``), the scaling, softmax and dropout are fp32, the aggregation is the 16-bit
-    product. ``fused=True`` — the fused dot-product attention kernels — is fp32 only: 16-bit features raise TypeError."""
+    product. ``fused=True`` alone refuses 16-bit features with a TypeError.
+
+    ``fused=True, fused_x16=True``: 16-bit features run ``DotAttentionFunction`` on the 16-bit q, k and v (``attention.dot_attention_x16``
+    and its two backward passes: fp32 sums, one rounding per 16-bit result, nothing of size ``[nnz, H]``); fp32 features run exactly what
+    ``fused=True`` runs. The keyword exists because the refusal of ``fused=True`` on 16-bit features is pinned by a committed test; it
+    is to be folded into ``fused=True`` when that test may change. ``fused_x16=True`` without ``fused=True`` is a ValueError."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, bias=True, root_weight=True, fused=False,
-                 attn_seed=None):
+                 attn_seed=None, fused_x16=False):
         super().__init__()
+        if fused_x16 and not fused:
+            raise ValueError("fused_x16=True selects the 16-bit form of the fused attention: it needs fused=True")
+        self.fused_x16 = bool(fused_x16)
         self.dropout = float(dropout)
         if not (0.0 <= self.dropout < 1.0):
             raise ValueError("dropout must be in [0, 1), got %r" % (dropout,))
@@ -1087,7 +1104,7 @@ class TransformerConv(torch.nn.Module):
         k = self.lin_key(x).view(n, H, F)
         v = self.lin_value(x).view(n, H, F)
         scale = 1.0 / math.sqrt(F)
-        if self.fused and (_is_x16(q) or _is_x16(k) or _is_x16(v)):
+        if self.fused and not self.fused_x16 and (_is_x16(q) or _is_x16(k) or _is_x16(v)):
             raise TypeError("TransformerConv(fused=True) needs torch.float32 features, got %s: attention.dot_attention "
                             "(DotAttentionFunction) is fp32 only; fused=False serves fp16 / bf16" % q.dtype)
         if self.fused:

@@ -1006,6 +1006,51 @@ int gespmm_dot_attention_backward_kv_dropout_f32(const int32_t* colptr, const in
 int gespmm_describe_dot_attention(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int q_align, int k_align, int v_align, char* out,
                                   int64_t capacity);
 /*
+ * ... on 16-bit node terms (new symbols of 0.5): q, out, grad_out, grad_q [M x H x F] and k, v, grad_k, grad_v [K x H x F] are IEEE
+ * fp16 or bfloat16 (dtype: GESPMM_X16_F16 / GESPMM_X16_BF16, one type per call); stats, delta and scale stay fp32.
+ * The arithmetic is the fp32 contract above, expression for expression: every 16-bit element is widened exactly at its use (subnormals
+ * included); the pinned lane dot, the xor butterfly, s_p = fl(scale dot), the online softmax, out = acc / l, a_p, g_p, ds_p, the
+ * per-word chains in entry order and the dropout placement are the fp32 kernels'; every accumulation is fp32. _backward_q reads the
+ * STORED, 16-bit out for delta = dot(grad_out, out). Every 16-bit result is rounded ONCE, at its store (to nearest even, overflow to
+ * +-inf, NaN stays NaN); for grad_q and grad_k that is fl32(scale chain), then one rounding. No packed-fp16 arithmetic and no dot2.
+ * Geometry (gespmm_describe_dot_attention_x16): the fp32 kernel's with V counted in ELEMENTS — V in {4, 2, 1}, an 8 / 4 / 2-byte load;
+ * 8 elements per lane and operand; W the smallest power of two in 4 .. 64 with 8 W >= F; V the widest of 4 / 2 / 1 that divides F and
+ * whose 2 V bytes divide the address of every 16-bit operand and result of the launch. A 16-byte load form (V = 8) is deliberately not
+ * built. Lane positions, chains and orders are those of the fp32 kernels at the same (V, W): wherever gespmm_describe_dot_attention
+ * answers the same (V, W) for the widened operands (a 16-bit operand b bytes off a 16-byte boundary corresponds to an fp32 operand 2 b
+ * bytes off), stats and delta have the BITS of the fp32 entry points on the widened operands — _backward_q fed widen(out),
+ * _backward_kv fed that delta — and out, grad_q, grad_k and grad_v are those calls' results narrowed once.
+ * Checks, in this order: a dtype that is neither code -> GESPMM_EINVAL; then the fp32 ladder with limits in ELEMENT positions (sizes
+ * that make no sense -> GESPMM_EINVAL; M, K, nnz, nnz H, M H F, K H F or 2 M H > 2^31 - 4097 -> GESPMM_ERANGE; F > 512 ->
+ * GESPMM_ERR_UNSUPPORTED; nnz == 0 or F == 0 zero-fills the results); NULL -> GESPMM_EINVAL; a 16-bit pointer not 2-byte aligned, delta
+ * or the seed not 4-byte aligned, stats not 8-byte aligned -> GESPMM_EALIGN. No atomics, no workspace, no allocation, no host
+ * synchronisation: capturable.
+ */
+int gespmm_dot_attention_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v, void* out,
+                             float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream);
+int gespmm_dot_attention_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v, void* out,
+                                     float* stats, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                     const void* seed, void* stream);
+int gespmm_dot_attention_backward_q_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v,
+                                        const float* stats, const void* out, const void* grad_out, float* delta, void* grad_q, int dtype,
+                                        int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream);
+int gespmm_dot_attention_backward_q_dropout_x16(const int32_t* rowptr, const int32_t* colind, const void* q, const void* k, const void* v,
+                                                const float* stats, const void* out, const void* grad_out, float* delta, void* grad_q,
+                                                int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                                const void* seed, void* stream);
+int gespmm_dot_attention_backward_kv_x16(const int32_t* colptr, const int32_t* rowind, const void* q, const void* k, const void* v,
+                                         const float* stats, const float* delta, const void* grad_out, void* grad_k, void* grad_v, int dtype,
+                                         int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, void* stream);
+int gespmm_dot_attention_backward_kv_dropout_x16(const int32_t* colptr, const int32_t* rowind, const void* q, const void* k, const void* v,
+                                                 const float* stats, const float* delta, const void* grad_out, void* grad_k, void* grad_v,
+                                                 int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float scale, float p,
+                                                 const void* seed, void* stream);
+/* Host only: what the three 16-bit entry points would launch, in the words of gespmm_describe_dot_attention. *_align: largest power of
+ * two (>= 2) dividing the 16-bit operand's address (pass the least of the 16-bit results' with them); the answer is
+ * gespmm_describe_dot_attention's at twice each alignment, capped at 16. Returns the length written or a GESPMM_E* code. */
+int gespmm_describe_dot_attention_x16(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int q_align, int k_align, int v_align,
+                                      char* out, int64_t capacity);
+/*
  * Fused GATv2 attention over the entries of a pattern — score, softmax and aggregation in ONE sweep — and its backward, with NOTHING of
  * size nnz but the index arrays (new symbols of 0.5). xl [M x H x F] is the aggregating node's term (the row of an entry), xr
  * [K x H x F] the neighbour's (the column), att [H x F]; out and grad_out [M x H x F], stats [M x H x 2], delta [M x H]. slope == 1:
