@@ -6,25 +6,75 @@ Moved here from the GPU test files, arguments now host arrays instead of the fil
 test_gpu_edge_dropout.py: the two were one function but for ``keep``), ``gatv2_float64`` (test_gpu_gatv2_score.py), and the rule those
 files wrote inline, ``bound_ratio``: |got - ref| <= 1e-4 max(|ref|, sum |terms|). Re-exported from the host test modules that own
 them: the derived tolerances of the edge softmax, of the dot-product attention and of the fused GATv2 attention (its ``check_all``,
-restatement and geometry), the GATv2 restatement, the max-arg chains."""
+restatement and geometry), the GATv2 restatement, the max-arg chains, and the rounding, the restated geometry and the restatement of the
+two 16-bit attention families. The one rounding of a 16-bit store (``U16``, ``TINY16``, ``tol16``) moved here from
+test_gpu_dot_attention_x16.py; ``dot_x16_check_all`` and ``gatv2_attention_x16_check_all`` are the fp32 ``check_all`` with ``tol16``
+around the tolerance of each 16-bit result, as that file's float64 test wrote it inline."""
 import numpy as np
+import torch
 
 from max_arg_ref import max_arg_forward, max_backward, tied_words  # noqa: F401
 from max_arg_ref import transpose as max_arg_transpose  # noqa: F401
 from test_dot_attention_host import check_all as dot_check_all  # noqa: F401
-from test_dot_attention_host import ratio as dot_ratio  # noqa: F401
-from test_dot_attention_host import ref_backward as dot_ref_backward  # noqa: F401
-from test_dot_attention_host import ref_forward as dot_ref_forward  # noqa: F401
+from test_dot_attention_host import ratio as dot_ratio
+from test_dot_attention_host import ref_backward as dot_ref_backward
+from test_dot_attention_host import ref_forward as dot_ref_forward
+from test_dot_attention_x16_host import geometry_x16 as dot_x16_geometry  # noqa: F401
+from test_dot_attention_x16_host import restate_x16 as dot_x16_restate  # noqa: F401
+from test_dot_attention_x16_host import rounded  # noqa: F401
 from test_edge_dropout_host import restate as dropout_bits  # noqa: F401
 from test_edge_softmax_host import ref_backward as softmax_ref_backward  # noqa: F401
 from test_edge_softmax_host import ref_forward as softmax_ref_forward  # noqa: F401
 from test_edge_softmax_host import worst_ratio as softmax_worst_ratio  # noqa: F401
 from test_gatv2_attention_host import check_all as gatv2_attention_check_all  # noqa: F401
 from test_gatv2_attention_host import geometry as gatv2_attention_geometry  # noqa: F401
+from test_gatv2_attention_host import ref_backward as gatv2_attention_ref_backward
+from test_gatv2_attention_host import ref_forward as gatv2_attention_ref_forward
 from test_gatv2_attention_host import restate_all as gatv2_attention_restate_all  # noqa: F401
+from test_gatv2_attention_x16_host import geometry_x16 as gatv2_attention_x16_geometry  # noqa: F401
+from test_gatv2_attention_x16_host import restate_x16 as gatv2_attention_x16_restate  # noqa: F401
 from test_gatv2_host import restate_backward as gatv2_restate_backward
 from test_gatv2_host import restate_score as gatv2_restate_score
 from test_gatv2_host import worst_ratio as gatv2_worst_ratio  # noqa: F401
+
+
+U16 = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}  # the one rounding at a 16-bit store
+TINY16 = {torch.float16: 2.0 ** -25, torch.bfloat16: 0.0}     # half the smallest fp16 subnormal; bf16 has fp32's exponents
+
+
+def tol16(ref, tol, dtype):
+    """The tolerance of a result stored in a 16-bit type: the fp32 result's own ``tol`` plus the one rounding at the store."""
+    return tol + U16[dtype] * np.abs(ref) + TINY16[dtype]
+
+
+def dot_x16_check_all(P, x, got, dtype, keep=None, ks=None, what=""):
+    """test_dot_attention_host.check_all for the results of the 16-bit launches (fp32 host arrays; x: the widened operands): stats and
+    delta inside the derived tolerances, out, grad_q, grad_k and grad_v inside ``tol16`` of theirs -> the worst ratio per result."""
+    f = dot_ref_forward(P, x, keep, ks)
+    b = dot_ref_backward(P, x, got["stats"], got["out"], None, keep, ks)
+    bc = dot_ref_backward(P, x, got["stats"], got["out"], got["delta"], keep, ks)
+    r = {"out": dot_ratio(got["out"], f["out"], tol16(f["out"], f["tol_out"], dtype)), "m": dot_ratio(got["stats"][..., 0], f["m"], f["tol_m"]),
+         "l": dot_ratio(got["stats"][..., 1], f["l"], f["tol_l"]), "delta": dot_ratio(got["delta"], b["delta"], b["tol_delta"]),
+         "grad_q": dot_ratio(got["grad_q"], b["grad_q"], tol16(b["grad_q"], b["tol_grad_q"], dtype)),
+         "grad_k": dot_ratio(got["grad_k"], bc["grad_k"], tol16(bc["grad_k"], bc["tol_grad_k"], dtype)),
+         "grad_v": dot_ratio(got["grad_v"], bc["grad_v"], tol16(bc["grad_v"], bc["tol_grad_v"], dtype))}
+    print("%s worst error / tolerance: %s" % (what, "  ".join("%s %.3g" % kv for kv in r.items())))
+    return r
+
+
+def gatv2_attention_x16_check_all(P, x, slope, got, dtype, keep=None, ks=None, what=""):
+    """test_gatv2_attention_host.check_all for the results of the 16-bit launches (fp32 host arrays; x: the widened operands): stats,
+    delta and att_part inside the derived tolerances, out, grad_xl and grad_xr inside ``tol16`` of theirs -> the worst ratio per result."""
+    f = gatv2_attention_ref_forward(P, x, slope, keep, ks)
+    b = gatv2_attention_ref_backward(P, x, slope, got["stats"], got["out"], None, keep, ks)
+    bc = gatv2_attention_ref_backward(P, x, slope, got["stats"], got["out"], got["delta"], keep, ks)
+    r = {"out": dot_ratio(got["out"], f["out"], tol16(f["out"], f["tol_out"], dtype)), "m": dot_ratio(got["stats"][..., 0], f["m"], f["tol_m"]),
+         "l": dot_ratio(got["stats"][..., 1], f["l"], f["tol_l"]), "delta": dot_ratio(got["delta"], b["delta"], b["tol_delta"]),
+         "grad_xl": dot_ratio(got["grad_xl"], b["grad_xl"], tol16(b["grad_xl"], b["tol_grad_xl"], dtype)),
+         "att_part": dot_ratio(got["att_part"], b["att_part"], b["tol_att_part"]),
+         "grad_xr": dot_ratio(got["grad_xr"], bc["grad_xr"], tol16(bc["grad_xr"], bc["tol_grad_xr"], dtype))}
+    print("%s worst error / tolerance: %s" % (what, "  ".join("%s %.3g" % kv for kv in r.items())))
+    return r
 
 
 def rows_of(rowptr):

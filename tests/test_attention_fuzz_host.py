@@ -1,7 +1,9 @@
 """The seeded sweep of tests/test_gpu_attention_fuzz.py, as far as it can be judged without a GPU: the generator is deterministic, the
 case lists reach the launch parameters of every family's tables (a condition on the inputs: the seeds of FAMILY_SEEDS were chosen until
 it held), every family's comparison rejects a result that lost one entry, and the float64 references moved into
-tests/attention_refs.py give what the private helpers of the GPU test files gave before the move."""
+tests/attention_refs.py give what the private helpers of the GPU test files gave before the move. For the two 16-bit attention
+families (gatv2_attention_x16, dot_x16) also: the fp32 restatement of every case, both dtypes and both passes, stays inside the
+sweep's float64 rule with the 16-bit results rounded once, bf16 bits read as fp16 leave it, and the inputs witness the rounding."""
 import numpy as np
 import pytest
 import torch
@@ -144,6 +146,33 @@ def reach(family, L, seed=None):
         bwd = {_bwd_shape_x16(c["H"], c["F"], *fz.x16_aligns(c["offset"])) for c in live}
         r["backward V"], r["backward W"] = {b[0] for b in bwd}, {b[1] for b in bwd}
         assert {_bwd_shape_x16(c["H"], c["F"], *fz.x16_aligns(c["offset"], 2))[0] for c in live} == {1}
+    elif family in ("gatv2_attention_x16", "dot_x16"):
+        # both passes of the sweep: the 16-bit operands at the case's offset and 2 bytes further; att / att_part and the fp32 oracle's
+        # tensors at twice that. Each describe call against the restated rule, the 16-bit and the fp32 call on one {V, W}.
+        passes = {0: set(), 2: set()}
+        for c in live:
+            size = (c["G"]["M"], c["G"]["K"], c["H"], c["F"], c["G"]["nnz"])
+            for extra in passes:
+                xa, fa = (fz.align_at(o) for o in fz.x16_offsets(c["offset"], extra))
+                if family == "dot_x16":
+                    V, W = refs.dot_x16_geometry(c["F"], xa)
+                    assert L.describe_dot_attention(*size, xa, xa, xa, x16=True) == {"V": V, "W": W} == L.describe_dot_attention(*size, fa, fa, fa)
+                    assert (V, W) == geometry(c["F"], fa)
+                else:
+                    V, W = refs.gatv2_attention_x16_geometry(c["F"], xa, fa)
+                    want = {"V": V, "W": W, "supported": True}
+                    assert L.describe_gatv2_attention(*size, xa, xa, fa, x16=True) == want == L.describe_gatv2_attention(*size, fa, fa, fa)
+                    assert (V, W) == refs.gatv2_attention_geometry(c["F"], fa)
+                passes[extra].add((V, W))
+        assert {v for v, _ in passes[2]} == {1}
+        r["V"], r["W"] = ({p[i] for q in passes.values() for p in q} for i in (0, 1))
+        r["first pass V"] = {v for v, _ in passes[0]}
+        r["p"] = {c["p"] for c in cases}
+        r["dropout off a 16-byte boundary"] = {c["p"] != 0 and c["offset"] != 0 for c in live}
+        r["longest row"] = {int(c["G"]["degs"].max()) for c in cases}
+        # what the exact corners and the single-head comparison of the sweep need: both run without dropout only
+        r["a single-entry row without dropout"] = {bool((c["G"]["degs"] == 1).any()) for c in live if not c["p"]}
+        r["several heads without dropout"] = {c["H"] > 1 for c in live if not c["p"]}
     return r
 
 
@@ -218,6 +247,11 @@ def wanted(family):
         # from F in {8, 32, 64, 512}, both at offset 0: an fp32 att 8 bytes off allows V = 2, 4 bytes off V = 1. The backward's W covers
         # H F / V lanes: every W in 4 .. 64 has widths behind it.
         w.update({"score V": {1, 2, 4, 8}, "score W": POW2 - {64}, "backward V": {1, 2, 4, 8}, "backward W": POW2})
+    elif family in ("gatv2_attention_x16", "dot_x16"):
+        # every V and every W on its own (V = 4 and 2 on the first pass: the second is V = 1 throughout), a dropout case whose 16-bit
+        # operands lie off a 16-byte boundary, and hubs of 2049 and 4097 entries
+        w.update({"V": {1, 2, 4}, "first pass V": {2, 4}, "W": POW2, "p": set(fz.PS), "dropout off a 16-byte boundary": {True},
+                  "longest row": {2049, 4097}, "a single-entry row without dropout": {True}, "several heads without dropout": {True}})
     return w
 
 
@@ -467,6 +501,132 @@ def test_gatv2_x16_comparison_rejects_the_other_type():
     assert refs.gatv2_worst_ratio(wrong.astype(np.float32), ref, terms, "score") > 1
 
 
+# ------------------------------------------------------------------------- the two 16-bit attention families (3.27, 3.28)
+
+X16 = ("gatv2_attention_x16", "dot_x16")
+X16_NARROW = {"gatv2_attention_x16": fz.NARROW_V2, "dot_x16": fz.NARROW_DOT}
+
+
+def _x16_inputs(family, c, dtype):
+    return fz.gatv2_attention_x16_inputs(c, dtype) if family == "gatv2_attention_x16" else fz.dot_x16_inputs(c, dtype)
+
+
+def _x16_geometry(family, c, extra):
+    """(V, W) of a pass of the sweep: the 16-bit operands ``extra`` bytes past the case's offset, att and att_part at twice that."""
+    xa, fa = (fz.align_at(o) for o in fz.x16_offsets(c["offset"], extra))
+    return refs.dot_x16_geometry(c["F"], xa) if family == "dot_x16" else refs.gatv2_attention_x16_geometry(c["F"], xa, fa)
+
+
+def _x16_check(family, G, x, slope, got, dtype, keep=None, ks=None, what=""):
+    """Rule 3 of the sweep: the derived tolerances, ``tol16`` around those of the 16-bit results."""
+    if family == "dot_x16":
+        return refs.dot_x16_check_all(G, x, got, dtype, keep, ks, what=what)
+    return refs.gatv2_attention_x16_check_all(G, x, slope, got, dtype, keep, ks, what=what)
+
+
+def _x16_float64_itself(family, G, x, slope, dtype):
+    """The six results in float64, rounded once to the type each is stored in; the row pass reads the rounded out."""
+    f32 = lambda a: a.astype(np.float32)  # noqa: E731
+    r16 = lambda a: refs.rounded(f32(a), dtype)  # noqa: E731
+    if family == "dot_x16":
+        f = refs.dot_ref_forward(G, x)
+        stats, out = f32(np.stack((f["m"], f["l"]), -1)), r16(f["out"])
+        b = refs.dot_ref_backward(G, x, stats, out)
+        got = {"out": out, "stats": stats, "delta": f32(b["delta"]), "grad_q": r16(b["grad_q"]), "grad_k": r16(b["grad_k"]),
+               "grad_v": r16(b["grad_v"])}
+    else:
+        f = refs.gatv2_attention_ref_forward(G, x, slope)
+        stats, out = f32(np.stack((f["m"], f["l"]), -1)), r16(f["out"])
+        b = refs.gatv2_attention_ref_backward(G, x, slope, stats, out)
+        got = {"out": out, "stats": stats, "delta": f32(b["delta"]), "grad_xl": r16(b["grad_xl"]), "att_part": f32(b["att_part"]),
+               "grad_xr": r16(b["grad_xr"])}
+    return got, f["a"]
+
+
+@pytest.mark.parametrize("dtype", fz.X16_DTYPES, ids=fz.X16_IDS)
+@pytest.mark.parametrize("family", X16)
+def test_x16_restatement_of_every_case_stays_inside_the_tolerance(pkg, family, dtype):
+    """The reference alone, no GPU: the fp32 restatement on the widened operands with the 16-bit results rounded once (``restate_x16``
+    of the two ``*_x16_host`` modules) at each case's own (V, W) of BOTH passes, slope and p, against float64 by the sweep's rule 3:
+    <= 1.0 in every result, every word finite (no fp16 overflow). No case is left out; where the second pass (V = 1) has the first
+    one's (V, W) its chains are the first one's word for word and it is not computed twice. The 16-bit results sit near 1 by
+    construction — a half-ulp store just above a power of two is u16 |ref| — the fp32 ones far below."""
+    worst = {}
+    for c in fz.family_cases(family):
+        G, H, p = c["G"], c["H"], c["p"]
+        assert G["nnz"] * H * c["F"] <= fz.CAP
+        x = _x16_inputs(family, c, dtype)
+        keep, ks = fz.keep_of(G, H, p) if p else (None, None)
+        for V, W in sorted({_x16_geometry(family, c, 0), _x16_geometry(family, c, 2)}):
+            msg = "%s %s V=%d W=%d" % (fz.what(family, c), dtype, V, W)
+            if family == "dot_x16":
+                _, got = refs.dot_x16_restate(G, x, V, W, dtype, p=p or None)
+            else:
+                _, got = refs.gatv2_attention_x16_restate(G, x, c["slope"], V, W, dtype, p=p or None)
+            assert all(np.isfinite(a).all() for a in got.values()), msg
+            r = _x16_check(family, G, x, c["slope"], got, dtype, keep, ks, what=msg)
+            assert max(r.values()) <= 1.0, (msg, r)
+            worst = {k: max(v, worst.get(k, 0.0)) for k, v in r.items()}
+    print("%s %s restatement, worst error / tolerance over the 24 cases: %s" % (family, dtype, worst))
+
+
+@pytest.mark.parametrize("dtype", fz.X16_DTYPES, ids=fz.X16_IDS)
+@pytest.mark.parametrize("family", X16)
+def test_x16_comparison_rejects_a_lost_entry(family, dtype):
+    """The lost-entry rejection of the fp32 counterparts through rule 3, the u16 |ref| of the 16-bit results INCLUDED: the float64
+    results rounded once against the reference of the pattern without the entry of the largest softmax share of head 0 in the longest
+    row, at slope 0.2 (GATv2). out, l, the row gradient and the column gradients must land outside (delta and m cannot, by
+    construction: test_gatv2_attention_comparison_rejects_a_lost_entry)."""
+    c = _short_case(family)
+    G, slope = c["G"], 0.2
+    x = _x16_inputs(family, c, dtype)
+    got, a = _x16_float64_itself(family, G, x, slope, dtype)
+    assert max(_x16_check(family, G, x, slope, got, dtype, what="float64 itself, rounded once").values()) <= 1
+    r, e = _longest_row(G)
+    lost = int(e[np.argmax(a[e, 0])])
+    ratios = _x16_check(family, _without(G, lost), x, slope, got, dtype, what="one entry lost")
+    for name in ("out", "l") + (("grad_q", "grad_k", "grad_v") if family == "dot_x16" else ("grad_xl", "att_part", "grad_xr")):
+        assert ratios[name] > 1, (name, ratios)
+
+
+@pytest.mark.parametrize("family", X16)
+def test_x16_comparison_rejects_the_other_type(family):
+    """Every 16-bit result of the two families is also compared on bits with the fp32 entry points, which their own families hold to
+    float64. What is left is the type: results of operands whose bf16 bits were widened by fp16's rule must leave rule 3's bound."""
+    bf = torch.bfloat16
+    c = _short_case(family, need=1)
+    G, slope = c["G"], c["slope"]
+    x = _x16_inputs(family, c, bf)
+    got, _ = _x16_float64_itself(family, G, x, slope, bf)
+    assert max(_x16_check(family, G, x, slope, got, bf, what="float64 itself, rounded once").values()) <= 1
+    halves = ("q", "k", "v", "go") if family == "dot_x16" else ("xl", "xr", "go")
+    wrong = dict(x, **{n: torch.from_numpy(x[n]).to(bf).view(torch.float16).float().numpy() for n in halves})
+    assert all(np.isfinite(wrong[n]).all() for n in halves)
+    misread, _ = _x16_float64_itself(family, G, wrong, slope, bf)
+    ratios = _x16_check(family, G, x, slope, misread, bf, what="bf16 bits read as fp16")
+    for name in X16_NARROW[family]:
+        assert ratios[name] > 1, (name, ratios)
+
+
+@pytest.mark.parametrize("dtype", fz.X16_DTYPES, ids=fz.X16_IDS)
+@pytest.mark.parametrize("family", X16)
+def test_x16_inputs_witness_the_rounding(pkg, family, dtype):
+    """The bit comparison with the narrowed fp32 results needs no proof beyond this: on the first short case of each family, at its own
+    slope and p and the first pass's (V, W), more than half of the words of each 16-bit result change under the rounding
+    (test_inputs_witness_the_rounding of the two ``*_x16_host`` modules, on the sweep's inputs)."""
+    c = _short_case(family)
+    x = _x16_inputs(family, c, dtype)
+    V, W = _x16_geometry(family, c, 0)
+    if family == "dot_x16":
+        raw, narrowed = refs.dot_x16_restate(c["G"], x, V, W, dtype, p=c["p"] or None)
+    else:
+        raw, narrowed = refs.gatv2_attention_x16_restate(c["G"], x, c["slope"], V, W, dtype, p=c["p"] or None)
+    for key in X16_NARROW[family]:
+        frac = float((raw[key] != narrowed[key]).mean())
+        print("%s %s %s: %.3f of the words change under the rounding" % (fz.what(family, c), dtype, key, frac))
+        assert frac > 0.5, (key, frac)
+
+
 def test_max_arg_comparison_rejects_a_lost_entry():
     c = _short_case("max_arg")
     G, N = c["G"], c["H"] * c["F"]
@@ -610,3 +770,15 @@ def test_the_moved_references_give_what_the_private_helpers_gave():
 
     assert refs.gatv2_attention_check_all is v2a.check_all and refs.gatv2_attention_restate_all is v2a.restate_all
     assert refs.gatv2_attention_geometry is v2a.geometry
+    assert refs.gatv2_attention_ref_forward is v2a.ref_forward and refs.gatv2_attention_ref_backward is v2a.ref_backward
+    assert refs.dot_ratio is dot.ratio
+    import test_dot_attention_x16_host as dot16
+    import test_gatv2_attention_x16_host as v2a16
+
+    assert refs.rounded is dot16.rounded and refs.dot_x16_geometry is dot16.geometry_x16 and refs.dot_x16_restate is dot16.restate_x16
+    assert refs.gatv2_attention_x16_geometry is v2a16.geometry_x16 and refs.gatv2_attention_x16_restate is v2a16.restate_x16
+    # the 16-bit rule is the one test_gpu_dot_attention_x16.py wrote inline before the move
+    ref, tol = np.array([-3.0, 0.0, 2.0 ** -20]), np.array([1e-7, 2.0 ** -120, 0.0])
+    for dt, u, tiny in ((torch.float16, 2.0 ** -11, 2.0 ** -25), (torch.bfloat16, 2.0 ** -8, 0.0)):
+        assert refs.U16[dt] == u and refs.TINY16[dt] == tiny
+        assert np.array_equal(refs.tol16(ref, tol, dt), tol + u * np.abs(ref) + tiny)

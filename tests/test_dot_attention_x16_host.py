@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_dot_attention_host import BIG, OK, UNSUPPORTED, geometry, inputs, pattern, restate_backward_kv, restate_backward_q, restate_forward
+from test_dot_attention_host import (BIG, OK, UNSUPPORTED, geometry, inputs, keep_mask, pattern, restate_backward_kv, restate_backward_q,
+                                     restate_forward)
 from test_heads_host import EALIGN, EINVAL, ERANGE
 
 F32 = np.float32
@@ -324,13 +325,18 @@ def test_function_and_layer_on_host_tensors(pkg, dt):
 
 # ------------------------------------------------------------------------------- the condition on the GPU test's inputs
 
-def restate_x16(P, x, V, W, dtype):
+def restate_x16(P, x, V, W, dtype, p=None):
     """The six results as the 16-bit kernels define them, by the fp32 restatement on the widened operands: -> (unrounded fp32 results,
-    the same with out, grad_q, grad_k and grad_v rounded once). The row pass is fed the ROUNDED out, the column pass that delta."""
-    out, stats = restate_forward(P, x, V, W)
+    the same with out, grad_q, grad_k and grad_v rounded once). The row pass is fed the ROUNDED out, the column pass that delta. p: the
+    dropout rate, the mask ``keep_mask``'s as in ``restate_all``."""
+    keep = keep_t = ks = None
+    if p is not None:
+        keep, ks = keep_mask(P, x["q"].shape[1], p)
+        keep_t, _ = keep_mask(P, x["q"].shape[1], p, transposed=True)
+    out, stats = restate_forward(P, x, V, W, keep=keep, ks=ks)
     out16 = rounded(out, dtype)
-    delta, grad_q = restate_backward_q(P, x, stats, out16, V, W)
-    grad_k, grad_v = restate_backward_kv(P, x, stats, delta, V, W)
+    delta, grad_q = restate_backward_q(P, x, stats, out16, V, W, keep=keep, ks=ks)
+    grad_k, grad_v = restate_backward_kv(P, x, stats, delta, V, W, keep_t=keep_t, ks=ks)
     raw = {"out": out, "stats": stats, "delta": delta, "grad_q": grad_q, "grad_k": grad_k, "grad_v": grad_v}
     return raw, dict(raw, out=out16, grad_q=rounded(grad_q, dtype), grad_k=rounded(grad_k, dtype), grad_v=rounded(grad_v, dtype))
 

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_dot_attention_host import pattern
+from test_dot_attention_host import keep_mask, pattern
 from test_gatv2_attention_host import BIG, OK, UNSUPPORTED, geometry, inputs, restate_backward_col, restate_backward_row, restate_forward
 from test_heads_host import EALIGN, EINVAL, ERANGE
 
@@ -305,13 +305,18 @@ def test_function_and_layer_on_host_tensors(pkg, dt):
 
 # ------------------------------------------------------------------------------- the condition on the GPU test's inputs
 
-def restate_x16(P, x, slope, V, W, dtype):
+def restate_x16(P, x, slope, V, W, dtype, p=None):
     """The six results as the 16-bit kernels define them, by the fp32 restatement on the widened operands: -> (unrounded fp32 results,
-    the same with out, grad_xl and grad_xr rounded once). The row pass is fed the ROUNDED out, the column pass that delta."""
-    out, stats = restate_forward(P, x, slope, V, W)
+    the same with out, grad_xl and grad_xr rounded once). The row pass is fed the ROUNDED out, the column pass that delta. p: the
+    dropout rate, the mask ``keep_mask``'s as in ``restate_all``."""
+    keep = keep_t = ks = None
+    if p is not None:
+        keep, ks = keep_mask(P, x["xl"].shape[1], p)
+        keep_t, _ = keep_mask(P, x["xl"].shape[1], p, transposed=True)
+    out, stats = restate_forward(P, x, slope, V, W, keep=keep, ks=ks)
     out16 = rounded(out, dtype)
-    delta, grad_xl, att_part = restate_backward_row(P, x, stats, out16, slope, V, W)
-    grad_xr = restate_backward_col(P, x, stats, delta, slope, V, W)
+    delta, grad_xl, att_part = restate_backward_row(P, x, stats, out16, slope, V, W, keep=keep, ks=ks)
+    grad_xr = restate_backward_col(P, x, stats, delta, slope, V, W, keep_t=keep_t, ks=ks)
     raw = {"out": out, "stats": stats, "delta": delta, "grad_xl": grad_xl, "att_part": att_part, "grad_xr": grad_xr}
     return raw, dict(raw, out=out16, grad_xl=rounded(grad_xl, dtype), grad_xr=rounded(grad_xr, dtype))
 

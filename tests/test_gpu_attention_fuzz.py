@@ -29,11 +29,13 @@ SLOPES = (None, 0.2)
 PS = (0.0, 0.25, 0.6)
 CAP = 1 << 22
 N_CASES = 24
-FAMILIES = ("heads", "sddmm", "softmax", "aggregate", "gatv2", "dropout", "dot", "max_arg", "gatv2_attention", "gatv2_x16")
+FAMILIES = ("heads", "sddmm", "softmax", "aggregate", "gatv2", "dropout", "dot", "max_arg", "gatv2_attention", "gatv2_x16",
+            "gatv2_attention_x16", "dot_x16")
 # one seed per family, chosen on the CPU so that the reach conditions of tests/test_attention_fuzz_host.py hold
 FAMILY_SEEDS = {"heads": 20261227, "sddmm": 20262022, "softmax": 20263020, "aggregate": 20264032, "gatv2": 20265021,
                 "dropout": 20266023, "dot": 20267022, "max_arg": 20268022,
-                "gatv2_attention": 20269000, "gatv2_x16": 20270024}
+                "gatv2_attention": 20269000, "gatv2_x16": 20270024,
+                "gatv2_attention_x16": 20271023, "dot_x16": 20272031}
 GUARD = 64
 NAN = float("nan")
 WORST = {}
@@ -601,16 +603,20 @@ def test_edge_dropout(pkg, monkeypatch):
 
 # --------------------------------------------------------------------------------------------------------------- 7. dot attention
 
-def _dot_run(g, x, offset, drop):
+def _dot_run(g, x, offset, drop, small=None, stored=None):
+    """The three launches, every dense operand and result ``offset`` bytes off a 16-byte boundary; small: the offsets of (stats, delta)
+    where they are not the family's own (8 or 0, ``offset``); stored: a 16-bit type — the row pass is fed out rounded once to it."""
     from gespmm_amd import attention
 
     q, k, v, go = (_place(_dev(x[n]), offset) for n in ("q", "k", "v", "go"))
     M, H, F = x["q"].shape
     K = x["k"].shape[0]
-    o = {"out": Out((M, H, F), offset), "stats": Out((M, H, 2), 8 if offset == 8 else 0), "delta": Out((M, H), offset),
+    at_stats, at_delta = small or (8 if offset == 8 else 0, offset)
+    o = {"out": Out((M, H, F), offset), "stats": Out((M, H, 2), at_stats), "delta": Out((M, H), at_delta),
          "grad_q": Out((M, H, F), offset), "grad_k": Out((K, H, F), offset), "grad_v": Out((K, H, F), offset)}
     attention.dot_attention(g["rowptr"], g["colind"], q, k, v, scale=x["scale"], dropout=drop, out=o["out"].t, stats=o["stats"].t)
-    attention.dot_attention_backward_q(g["rowptr"], g["colind"], q, k, v, o["stats"].t, o["out"].t, go, scale=x["scale"], dropout=drop,
+    fed = o["out"].t if stored is None else _place(o["out"].t.to(stored).float(), offset)
+    attention.dot_attention_backward_q(g["rowptr"], g["colind"], q, k, v, o["stats"].t, fed, go, scale=x["scale"], dropout=drop,
                                        results=(o["delta"].t, o["grad_q"].t))
     attention.dot_attention_backward_kv(g["colptr"], g["rowind"], q, k, v, o["stats"].t, o["delta"].t, go, scale=x["scale"], dropout=drop,
                                         results=(o["grad_k"].t, o["grad_v"].t))
@@ -709,19 +715,22 @@ def test_max_arg_and_backward(pkg):
 RESULTS_V2 = ("out", "stats", "delta", "grad_xl", "att_part", "grad_xr")
 
 
-def _gatv2_attention_run(g, x, offset, slope, drop, want=True):
+def _gatv2_attention_run(g, x, offset, slope, drop, want=True, small=None, stored=None):
     """The three launches, every dense operand and result ``offset`` bytes off a 16-byte boundary (stats: 8 or 0) -> (results, placed
-    operands). want=False: the row pass without att_part; its buffer stays as it was poisoned."""
+    operands). want=False: the row pass without att_part; its buffer stays as it was poisoned. small: the offsets of (stats, delta)
+    where they are not the family's own; stored: a 16-bit type — the row pass is fed out rounded once to it."""
     from gespmm_amd import attention
 
     xl, xr, att, go = (_place(_dev(x[n]), offset) for n in ("xl", "xr", "att", "go"))
     M, H, F = x["xl"].shape
     K = x["xr"].shape[0]
-    o = {"out": Out((M, H, F), offset), "stats": Out((M, H, 2), 8 if offset == 8 else 0), "delta": Out((M, H), offset),
+    at_stats, at_delta = small or (8 if offset == 8 else 0, offset)
+    o = {"out": Out((M, H, F), offset), "stats": Out((M, H, 2), at_stats), "delta": Out((M, H), at_delta),
          "grad_xl": Out((M, H, F), offset), "att_part": Out((M, H, F), offset), "grad_xr": Out((K, H, F), offset)}
     attention.gatv2_attention(g["rowptr"], g["colind"], xl, xr, att, negative_slope=slope, dropout=drop, out=o["out"].t, stats=o["stats"].t)
     row = (o["delta"].t, o["grad_xl"].t, o["att_part"].t)
-    attention.gatv2_attention_backward_row(g["rowptr"], g["colind"], xl, xr, att, o["stats"].t, o["out"].t, go, negative_slope=slope,
+    fed = o["out"].t if stored is None else _place(o["out"].t.to(stored).float(), offset)
+    attention.gatv2_attention_backward_row(g["rowptr"], g["colind"], xl, xr, att, o["stats"].t, fed, go, negative_slope=slope,
                                            dropout=drop, want_att_part=want, results=row if want else row[:2])
     attention.gatv2_attention_backward_col(g["colptr"], g["rowind"], xl, xr, att, o["stats"].t, o["delta"].t, go, negative_slope=slope,
                                            dropout=drop, result=o["grad_xr"].t)
@@ -844,3 +853,214 @@ def test_gatv2_x16(pkg):
                         _same(u, v, "%s: %s, second run" % (m2, n))
     assert shared > 0, "no case compared the 16-bit score with the fp32 kernel's bits"
     _report("gatv2_x16")
+
+
+# ------------------------------------------------------------------- 11, 12. the fused GATv2 and dot-product attention on 16-bit operands
+
+X16_DTYPES = (torch.bfloat16, torch.float16)
+X16_IDS = ("bf16", "fp16")
+RESULTS_DOT = ("out", "stats", "delta", "grad_q", "grad_k", "grad_v")
+NARROW_V2, NARROW_DOT = ("out", "grad_xl", "grad_xr"), ("out", "grad_q", "grad_k", "grad_v")  # the 16-bit results; the others are fp32
+
+
+def x16_offsets(offset, extra=0):
+    """(offset of the 16-bit operands and results, offset of the fp32 oracle's tensors — and of the 16-bit run's fp32 att and att_part)
+    in bytes past a 16-byte boundary: a 16-bit operand b bytes off is an fp32 operand 2 b bytes off."""
+    return offset + extra, (2 * (offset + extra)) % 16
+
+
+def align_at(offset):
+    """The alignment in bytes, capped at 16, of an address ``offset`` bytes past a 16-byte boundary."""
+    return 16 if offset % 16 == 0 else offset & -offset
+
+
+def gatv2_attention_x16_inputs(c, dtype):
+    """``gatv2_attention_inputs`` with xl, xr and grad_out rounded to ``dtype`` AFTER the call (widened fp32 arrays; att stays fp32): the
+    fp32 family's assertion that no fl(xl + xr) is exactly 0 stays where it is, on the unrounded draw, and cannot be asked of the rounded
+    operands — sums of 16-bit values cancel exactly in hundreds of words a case. A sum of two 16-bit values is zero in fp32 exactly when
+    it is zero exactly, and the kernels (``!(t >= 0.0f)``) and the float64 reference (``t >= 0``) both take the non-negative branch
+    there: a tie is a legitimate input, and only finiteness is asserted."""
+    x = gatv2_attention_inputs(c)
+    x = dict(x, **{n: refs.rounded(x[n], dtype) for n in ("xl", "xr", "go")})
+    assert all(np.isfinite(x[n]).all() for n in ("xl", "xr", "go", "att"))
+    return x
+
+
+def dot_x16_inputs(c, dtype):
+    """``dot_inputs`` with q, k, v and grad_out rounded to ``dtype`` (widened fp32 arrays); the fp32 scale is untouched."""
+    x = dot_inputs(c)
+    x = dict(x, **{n: refs.rounded(x[n], dtype) for n in ("q", "k", "v", "go")})
+    assert all(np.isfinite(x[n]).all() for n in ("q", "k", "v", "go"))
+    return x
+
+
+def _gatv2_attention_x16_run(g, x, dtype, at16, at32, small, slope, drop, want=True):
+    """The three 16-bit launches: xl, xr, grad_out, out, grad_xl and grad_xr ``at16`` bytes off a 16-byte boundary, att and att_part
+    ``at32``, (stats, delta) at ``small`` -> results. want=False: the row pass without att_part; its buffer stays as it was poisoned."""
+    from gespmm_amd import attention
+
+    xl, xr, go = (_place(_dev(x[n]).to(dtype), at16) for n in ("xl", "xr", "go"))
+    att = _place(_dev(x["att"]), at32)
+    M, H, F = x["xl"].shape
+    K = x["xr"].shape[0]
+    o = {"out": Out((M, H, F), at16, dtype), "stats": Out((M, H, 2), small[0]), "delta": Out((M, H), small[1]),
+         "grad_xl": Out((M, H, F), at16, dtype), "att_part": Out((M, H, F), at32), "grad_xr": Out((K, H, F), at16, dtype)}
+    for t in (xl, xr, go, o["out"].t, o["grad_xl"].t, o["grad_xr"].t):
+        assert t.data_ptr() % 16 == at16
+    assert att.data_ptr() % 16 == at32 == o["att_part"].t.data_ptr() % 16
+    assert o["stats"].t.data_ptr() % 16 == small[0] and o["delta"].t.data_ptr() % 16 == small[1]
+    attention.gatv2_attention_x16(g["rowptr"], g["colind"], xl, xr, att, negative_slope=slope, dropout=drop, out=o["out"].t, stats=o["stats"].t)
+    row = (o["delta"].t, o["grad_xl"].t, o["att_part"].t)
+    attention.gatv2_attention_backward_row_x16(g["rowptr"], g["colind"], xl, xr, att, o["stats"].t, o["out"].t, go, negative_slope=slope,
+                                               dropout=drop, want_att_part=want, results=row if want else row[:2])
+    attention.gatv2_attention_backward_col_x16(g["colptr"], g["rowind"], xl, xr, att, o["stats"].t, o["delta"].t, go, negative_slope=slope,
+                                               dropout=drop, result=o["grad_xr"].t)
+    return o
+
+
+def _dot_x16_run(g, x, dtype, at16, small, drop):
+    """The three 16-bit launches: q, k, v, grad_out, out, grad_q, grad_k and grad_v ``at16`` bytes off a 16-byte boundary, (stats, delta)
+    at ``small`` -> results."""
+    from gespmm_amd import attention
+
+    q, k, v, go = (_place(_dev(x[n]).to(dtype), at16) for n in ("q", "k", "v", "go"))
+    M, H, F = x["q"].shape
+    K = x["k"].shape[0]
+    o = {"out": Out((M, H, F), at16, dtype), "stats": Out((M, H, 2), small[0]), "delta": Out((M, H), small[1]),
+         "grad_q": Out((M, H, F), at16, dtype), "grad_k": Out((K, H, F), at16, dtype), "grad_v": Out((K, H, F), at16, dtype)}
+    for t in (q, k, v, go, o["out"].t, o["grad_q"].t, o["grad_k"].t, o["grad_v"].t):
+        assert t.data_ptr() % 16 == at16
+    assert o["stats"].t.data_ptr() % 16 == small[0] and o["delta"].t.data_ptr() % 16 == small[1]
+    attention.dot_attention_x16(g["rowptr"], g["colind"], q, k, v, scale=x["scale"], dropout=drop, out=o["out"].t, stats=o["stats"].t)
+    attention.dot_attention_backward_q_x16(g["rowptr"], g["colind"], q, k, v, o["stats"].t, o["out"].t, go, scale=x["scale"], dropout=drop,
+                                           results=(o["delta"].t, o["grad_q"].t))
+    attention.dot_attention_backward_kv_x16(g["colptr"], g["rowind"], q, k, v, o["stats"].t, o["delta"].t, go, scale=x["scale"], dropout=drop,
+                                            results=(o["grad_k"].t, o["grad_v"].t))
+    return o
+
+
+def _x16_common(family, c, dtype, names, narrow, column, run, oracle, describe, single, check64, neighbour, extra_checks=None):
+    """What the two 16-bit attention families share, per case: two passes — the 16-bit operands and results ``c["offset"]`` bytes off a
+    16-byte boundary, then 2 bytes further (V = 1) — each written and guarded, +0 on empty rows (``column``: on empty columns), on the
+    bits of the fp32 entry points on the widened operands carved at twice the offset (the 16-bit results narrowed once), at one (V, W)
+    by both describe calls (a mismatch fails: nothing is skipped); stats at 8 bytes off where the case's offset is 8, delta at the
+    case's offset, in both runs; on the first pass inside the derived tolerances of float64 plus the one rounding of a 16-bit store,
+    the same bits in a second run, and, without dropout, a single-entry row its neighbour's value and heads 0 and H - 1 the bits of
+    the single-head call."""
+    G, H, off, p = c["G"], c["H"], c["offset"], c["p"]
+    g = _graph(G)
+    keep = ks = drop = None
+    if p:
+        (keep, ks), drop = keep_of(G, H, p), (p, _seed())
+    small = (8 if off == 8 else 0, off)
+    empty_r, empty_c = G["degs"] == 0, np.diff(G["colptr"]) == 0
+    for extra in (0, 2):
+        at16, at32 = x16_offsets(off, extra)
+        msg = "%s %s, 16-bit operands %d bytes off" % (what(family, c), dtype, at16)
+        o = run(g, at16, at32, small, drop)
+        got = {n: o[n].check("%s: %s" % (msg, n)) for n in names}
+        for n in names:
+            _plus_zero(got[n], empty_c if n in column else empty_r, "%s: %s" % (msg, n))
+        # ---- the bits of the fp32 entry points on the widened operands
+        want, placed = oracle(g, at32, small, drop)
+        if G["nnz"]:
+            d16, d32 = describe(align_at(at16), align_at(at32), True), describe(align_at(at32), align_at(at32), False)
+            assert {k: d16[k] for k in ("V", "W")} == {k: d32[k] for k in ("V", "W")}, "%s: %r on 16-bit, %r on fp32" % (msg, d16, d32)
+            assert extra == 0 or d16["V"] == 1, (msg, d16)
+        for n in names:
+            w = want[n].check("%s: fp32 %s" % (msg, n))
+            _same(got[n], w.to(dtype) if n in narrow else w, "%s: %s against the fp32 entry point%s" % (msg, n, " narrowed once" if n in narrow else ""))
+        if extra_checks is not None:
+            extra_checks(g, at16, at32, small, drop, got, placed, msg)
+        if extra:
+            continue
+        # ---- float64, the derived tolerances plus the one rounding of a 16-bit store
+        h = {n: t.float().cpu().numpy() for n, t in got.items()}
+        r = check64(h, keep, ks, msg)
+        _ratio("%s %s" % (family, X16_IDS[X16_DTYPES.index(dtype)]), max(r.values()), "%s: %r" % (msg, r))
+        if not p:
+            one = np.nonzero(G["degs"] == 1)[0]
+            assert _bits16(got["out"][_dev(one).long()]) == _bits16(_dev(neighbour[G["colind"][G["rowptr"][one]]]).to(dtype)), \
+                msg + ": a single-entry row is its neighbour's value"
+            assert np.all(h["stats"][one, :, 1] == 1.0), msg + ": a single-entry row has l = 1"
+        again = run(g, at16, at32, small, drop)
+        for n in names:
+            _same(again[n].check("%s: %s, second run" % (msg, n)), got[n], "%s: %s, second run" % (msg, n))
+        for hd in sorted({0, H - 1}) if H > 1 and not p else ():  # (with dropout the single-head call would draw head 0's mask)
+            alone = single(hd)(g, at16, at32, small, None)
+            for n in names:
+                _same(got[n][:, hd:hd + 1].contiguous(), alone[n].check("%s: head %d of %s alone" % (msg, hd, n)),
+                      "%s: head %d of %s is the single-head call" % (msg, hd, n))
+
+
+def _bits16(t):
+    return t.contiguous().view(torch.int16).cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("dtype", X16_DTYPES, ids=X16_IDS)
+def test_gatv2_attention_x16(pkg, dtype):
+    """gatv2_attention_x16 and its two backward passes on bf16 / fp16 node terms (``_x16_common``): att and att_part (fp32) at the fp32
+    oracle's offset, so that both describe calls answer one V; m of the stats the bits of the row maximum of sddmm.gatv2_score on the
+    widened operands at the oracle's offset; on every odd case the row pass without att_part the bits of the one with it, the poisoned
+    buffer untouched. Exact zeros of fl(xl + xr) are in the inputs (``gatv2_attention_x16_inputs``)."""
+    from gespmm_amd import _lib, sddmm
+
+    family = "gatv2_attention_x16"
+    for c in family_cases(family):
+        G, H, F, slope = c["G"], c["H"], c["F"], c["slope"]
+        x = gatv2_attention_x16_inputs(c, dtype)
+
+        def head(hd):
+            xs = {n: np.ascontiguousarray(x[n][:, hd:hd + 1]) for n in ("xl", "xr", "go")}
+            xs["att"] = np.ascontiguousarray(x["att"][hd:hd + 1])
+            return lambda g, at16, at32, small, drop: _gatv2_attention_x16_run(g, xs, dtype, at16, at32, small, slope, drop)
+
+        def extras(g, at16, at32, small, drop, got, placed, msg):
+            xl, xr, att = placed
+            score = sddmm.gatv2_score(g["rowptr"], g["colind"], xl, xr, att, negative_slope=slope)
+            top = torch.full((G["M"], H), -float("inf"), device="cuda")
+            if G["nnz"]:
+                top = top.scatter_reduce(0, g["rows"].long()[:, None].expand(-1, H), score, "amax")
+            top[_dev(G["degs"] == 0)] = 0.0
+            _same(got["stats"][:, :, 0].contiguous(), top, msg + ": m is the row maximum of gatv2_score on the widened operands")
+            if c["index"] % 2:
+                bare = _gatv2_attention_x16_run(g, x, dtype, at16, at32, small, slope, drop, want=False)
+                for n in ("delta", "grad_xl"):
+                    _same(bare[n].check("%s: %s without att_part" % (msg, n)), got[n], "%s: %s without att_part" % (msg, n))
+                assert bare["att_part"]._untouched(bare["att_part"].buf), msg + ": want_att_part=False wrote into the poisoned buffer"
+
+        _x16_common(
+            family, c, dtype, RESULTS_V2, NARROW_V2, ("grad_xr",),
+            run=lambda g, at16, at32, small, drop: _gatv2_attention_x16_run(g, x, dtype, at16, at32, small, slope, drop),
+            oracle=lambda g, at32, small, drop: _gatv2_attention_run(g, x, at32, slope, drop, small=small, stored=dtype),
+            describe=lambda xa, fa, x16: _lib.describe_gatv2_attention(G["M"], G["K"], H, F, G["nnz"], xa, xa, fa, x16=x16),
+            single=head,
+            check64=lambda h, keep, ks, msg: refs.gatv2_attention_x16_check_all(G, x, slope, h, dtype, keep, ks, what=msg),
+            neighbour=x["xr"], extra_checks=extras)
+    _report("%s %s" % (family, X16_IDS[X16_DTYPES.index(dtype)]))
+
+
+@pytest.mark.parametrize("dtype", X16_DTYPES, ids=X16_IDS)
+def test_dot_attention_x16(pkg, dtype):
+    """dot_attention_x16 and its two backward passes on bf16 / fp16 q, k and v (``_x16_common``)."""
+    from gespmm_amd import _lib
+
+    family = "dot_x16"
+    for c in family_cases(family):
+        G, H, F = c["G"], c["H"], c["F"]
+        x = dot_x16_inputs(c, dtype)
+
+        def head(hd):
+            xs = {n: np.ascontiguousarray(x[n][:, hd:hd + 1]) for n in ("q", "k", "v", "go")}
+            xs["scale"] = x["scale"]
+            return lambda g, at16, at32, small, drop: _dot_x16_run(g, xs, dtype, at16, small, drop)
+
+        _x16_common(
+            family, c, dtype, RESULTS_DOT, NARROW_DOT, ("grad_k", "grad_v"),
+            run=lambda g, at16, at32, small, drop: _dot_x16_run(g, x, dtype, at16, small, drop),
+            oracle=lambda g, at32, small, drop: (_dot_run(g, x, at32, drop, small=small, stored=dtype), None),
+            describe=lambda xa, fa, x16: _lib.describe_dot_attention(G["M"], G["K"], H, F, G["nnz"], xa, xa, xa, x16=x16),
+            single=head,
+            check64=lambda h, keep, ks, msg: refs.dot_x16_check_all(G, x, h, dtype, keep, ks, what=msg),
+            neighbour=x["v"])
+    _report("%s %s" % (family, X16_IDS[X16_DTYPES.index(dtype)]))

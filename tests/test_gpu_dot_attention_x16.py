@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from attention_refs import tol16
 from test_dot_attention_host import FS, HS, SEED, _chain_case, geometry, pattern, ratio, ref_backward, ref_forward, transpose
 from test_dot_attention_x16_host import DTYPES, FS16, HS16, IDS, PATTERNS, geometry_x16, inputs_x16, rounded
 from test_gpu_dot_attention import CHAINS
@@ -19,8 +20,6 @@ pytestmark = pytest.mark.gpu
 KEYS = ("out", "stats", "delta", "grad_q", "grad_k", "grad_v")
 NARROW = ("out", "grad_q", "grad_k", "grad_v")  # the 16-bit results; stats and delta are fp32 in both
 NAN = float("nan")
-U16 = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}  # the one rounding at a 16-bit store
-TINY16 = {torch.float16: 2.0 ** -25, torch.bfloat16: 0.0}     # half the smallest fp16 subnormal; bf16 has fp32's exponents
 
 
 def _dev(a):
@@ -206,14 +205,11 @@ def test_three_launches_against_float64(pkg, name, F, H, di):
     b = ref_backward(P, x, h["stats"], h["out"], None)
     bc = ref_backward(P, x, h["stats"], h["out"], h["delta"])
 
-    def tol16(ref, tol):
-        return tol + U16[dtype] * np.abs(ref) + TINY16[dtype]
-
-    r = {"out": ratio(h["out"], f["out"], tol16(f["out"], f["tol_out"])), "m": ratio(h["stats"][..., 0], f["m"], f["tol_m"]),
+    r = {"out": ratio(h["out"], f["out"], tol16(f["out"], f["tol_out"], dtype)), "m": ratio(h["stats"][..., 0], f["m"], f["tol_m"]),
          "l": ratio(h["stats"][..., 1], f["l"], f["tol_l"]), "delta": ratio(h["delta"], b["delta"], b["tol_delta"]),
-         "grad_q": ratio(h["grad_q"], b["grad_q"], tol16(b["grad_q"], b["tol_grad_q"])),
-         "grad_k": ratio(h["grad_k"], bc["grad_k"], tol16(bc["grad_k"], bc["tol_grad_k"])),
-         "grad_v": ratio(h["grad_v"], bc["grad_v"], tol16(bc["grad_v"], bc["tol_grad_v"]))}
+         "grad_q": ratio(h["grad_q"], b["grad_q"], tol16(b["grad_q"], b["tol_grad_q"], dtype)),
+         "grad_k": ratio(h["grad_k"], bc["grad_k"], tol16(bc["grad_k"], bc["tol_grad_k"], dtype)),
+         "grad_v": ratio(h["grad_v"], bc["grad_v"], tol16(bc["grad_v"], bc["tol_grad_v"], dtype))}
     print("gpu %s F=%d H=%d %s worst error / tolerance: %s" % (name, F, H, IDS[di], "  ".join("%s %.3g" % kv for kv in r.items())))
     assert max(r.values()) <= 1.0, r
 
