@@ -5,9 +5,10 @@
     python examples/sage_custom.py --dataset cora --aggregator-type pool
     python examples/sage_custom.py --dataset pubmed --aggregator-type mean --n-hidden 64
     python examples/sage_custom.py --aggregator-type pool --graph-capture      # replay each step from a HIP graph
+    python examples/sage_custom.py --aggregator-type pool --dtype bf16         # a .bfloat16() model on 16-bit features
 
 The command-line options are the reference script's (sage_dgl.py:182-201; ``--dataset`` is what ``register_data_args`` adds), plus
-``--graph-capture`` and ``--seed``. Differences forced by the environment are those of examples/gcn_custom.py, whose data path this
+``--graph-capture``, ``--seed`` and ``--dtype`` (fp16 / bf16: model and features in that type, the loss in fp32). Differences forced by the environment are those of examples/gcn_custom.py, whose data path this
 script uses: the bundled adjacency matrices or the synthetic stand-ins, random features, labels and masks — accuracy is chance level by
 construction, the point is the step time and that the loss falls. As in the reference, self loops are removed (sage_dgl.py:101) and the
 profiler table is replaced by HIP-event timing of the epoch loop.
@@ -69,6 +70,7 @@ def main():
     ap.add_argument("--aggregator-type", type=str, default="gcn", help="Aggregator type: mean/gcn/pool")
     ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dtype", choices=("fp32", "fp16", "bf16"), default="fp32", help="type of the model and the features (the loss stays fp32)")
     args = ap.parse_args()
     print(args)
     if args.gpu < 0 or not torch.cuda.is_available():
@@ -91,6 +93,9 @@ def main():
           % (n_edges, n_cls, idx["train"].numel(), idx["val"].numel(), idx["test"].numel()))
 
     model = GraphSAGE(g, n_feat, args.n_hidden, n_cls, args.n_layers, F.relu, args.dropout, args.aggregator_type).to(device)
+    if args.dtype != "fp32":
+        dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype]
+        model, features = model.to(dtype), features.to(dtype)
     loss_fcn = torch.nn.CrossEntropyLoss()
     optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay, capturable=args.graph_capture)
     y_train = labels[idx["train"]]
@@ -98,7 +103,7 @@ def main():
     def train_step():
         optimizer.zero_grad(set_to_none=False)
         logits = model(features)
-        loss = loss_fcn(logits.index_select(0, idx["train"]), y_train)
+        loss = loss_fcn(logits.index_select(0, idx["train"]).float(), y_train)
         loss.backward()
         optimizer.step()
         return loss

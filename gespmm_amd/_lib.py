@@ -166,6 +166,9 @@ EXPORTS = [
     "gespmm_csr_spmm_max_arg_f32",
     "gespmm_csr_spmm_max_backward_f32",
     "gespmm_max_arg_route",
+    "gespmm_csr_spmm_max_arg_x16",
+    "gespmm_csr_spmm_max_backward_x16",
+    "gespmm_max_arg_route_x16",
     "gespmm_csr_spmm_heads_order_f32",
     "gespmm_csr_spmm_heads_order_x16",
     "gespmm_plan_spmm_heads_order_f32",
@@ -465,6 +468,12 @@ def _load():
     lib.gespmm_csr_spmm_max_backward_f32.argtypes = [p] * 6 + [c_int64] * 4 + [p]
     lib.gespmm_max_arg_route.restype = c_int
     lib.gespmm_max_arg_route.argtypes = [c_int64, c_int64, c_int64, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_csr_spmm_max_arg_x16.restype = c_int
+    lib.gespmm_csr_spmm_max_arg_x16.argtypes = [p] * 5 + [c_int64] * 4 + [c_float, c_int, p]
+    lib.gespmm_csr_spmm_max_backward_x16.restype = c_int
+    lib.gespmm_csr_spmm_max_backward_x16.argtypes = [p] * 6 + [c_int64] * 4 + [c_int, p]
+    lib.gespmm_max_arg_route_x16.restype = c_int
+    lib.gespmm_max_arg_route_x16.argtypes = [c_int64, c_int64, c_int64, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_gat_aggregate_route.restype = c_int
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
@@ -659,6 +668,21 @@ def max_arg_route(M, nnz, N, b_align=16, c_align=16):
     n = lib.gespmm_max_arg_route(int(M), int(nnz), int(N), int(b_align), int(c_align), buf, 64)
     if n < 0:
         raise GespmmError(n, "gespmm_max_arg_route")
+    text = buf.value.decode()
+    if text == "form=none":
+        return None
+    out = dict(kv.split("=") for kv in text.split())
+    return int(out["V"]), int(out["S"]), int(out["W"])
+
+
+def max_arg_route_x16(M, nnz, N, x16_align=16, arg_align=16):
+    """The lane geometry of gespmm_csr_spmm_max_arg_x16 / gespmm_csr_spmm_max_backward_x16, V in ELEMENTS, with the 16-bit arrays on
+    ``x16_align``-byte and arg on ``arg_align``-byte boundaries (gespmm_max_arg_route_x16: host only): ``(V, S, W)``, or ``None`` when
+    there is nothing to launch."""
+    buf = ctypes.create_string_buffer(64)
+    n = lib.gespmm_max_arg_route_x16(int(M), int(nnz), int(N), int(x16_align), int(arg_align), buf, 64)
+    if n < 0:
+        raise GespmmError(n, "gespmm_max_arg_route_x16")
     text = buf.value.decode()
     if text == "form=none":
         return None

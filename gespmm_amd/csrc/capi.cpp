@@ -946,6 +946,81 @@ int gespmm_max_arg_route(int64_t M, int64_t nnz, int64_t N, int b_align, int c_a
     return describe_result(n, capacity);
 }
 
+/* ... on 16-bit dense operands (gespmm.h; spmm_max_arg_x16.hip). The geometry counts ELEMENTS and is the fp32 one at the EFFECTIVE
+   alignment: a V-element vector is 2 V bytes of the 16-bit arrays and 4 V bytes of arg, so a 16-bit array aligned to x counts as 2 x.
+   The size limits are max_arg_sizes' as they stand: arg is the 4-byte array that sets them. */
+static int max_arg_x16_align(int x16_align, int arg_align) { return std::min(std::min(2 * std::min(x16_align, 8), arg_align), 16); }
+
+int gespmm_csr_spmm_max_arg_x16(const int32_t* rowptr, const int32_t* colind, const void* B, void* C, int32_t* arg, int64_t M, int64_t K,
+                                int64_t N, int64_t nnz, float empty_value, int dtype, void* stream) {
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    int rc = max_arg_sizes(M, K, N, nnz);
+    if (rc == GESPMM_EINVAL || std::isnan(empty_value)) return GESPMM_EINVAL;
+    if (rc != 0) return rc;
+    if (M == 0 || N == 0) return 0;
+    if ((rc = check_pointers({{rowptr, 4, true}, {C, 2, true}, {arg, 4, true}, {colind, 4, nnz != 0}, {B, 2, nnz != 0}})) != 0) return rc;
+    const uint64_t b_bytes = (uint64_t)K * (uint64_t)N * 2, c_bytes = (uint64_t)M * (uint64_t)N * 2, a_bytes = (uint64_t)M * (uint64_t)N * 4;
+    if (ranges_overlap(C, c_bytes, B, b_bytes) || ranges_overlap(arg, a_bytes, B, b_bytes) || ranges_overlap(C, c_bytes, arg, a_bytes))
+        return GESPMM_EINVAL;
+    Geometry geo = {};
+    const int x16_align = std::min(nnz != 0 ? pointer_alignment(B) : 16, pointer_alignment(C));
+    if ((rc = max_arg_geometry(M, K, N, nnz, max_arg_x16_align(x16_align, pointer_alignment(arg)), &geo)) != 0) return rc;
+    gespmm::MaxArgArgs a = {};
+    a.ptr = rowptr;
+    a.ind = colind;
+    a.src = static_cast<const float*>(B);  // (the 16-bit arrays: spmm_max_arg.h)
+    a.dst = static_cast<float*>(C);
+    a.arg_out = arg;
+    a.S = (int32_t)M;
+    a.N = (int32_t)N;
+    a.empty = empty_value;
+    return (int)gespmm::launch_spmm_max_arg_x16(a, dtype, geo, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_csr_spmm_max_backward_x16(const int32_t* colptr, const int32_t* rowind, const int32_t* order, const int32_t* arg,
+                                     const void* grad_out, void* grad_B, int64_t M, int64_t K, int64_t N, int64_t nnz, int dtype,
+                                     void* stream) {
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    int rc = max_arg_sizes(M, K, N, nnz);
+    if (rc != 0) return rc;
+    if (K == 0 || N == 0) return 0;
+    if ((rc = check_pointers({{colptr, 4, true}, {grad_B, 2, true}, {rowind, 4, nnz != 0}, {order, 4, nnz != 0}, {arg, 4, nnz != 0},
+                              {grad_out, 2, nnz != 0}})) != 0)
+        return rc;
+    const uint64_t g_bytes = (uint64_t)K * (uint64_t)N * 2, o_bytes = (uint64_t)M * (uint64_t)N * 2, a_bytes = (uint64_t)M * (uint64_t)N * 4;
+    if (ranges_overlap(grad_B, g_bytes, grad_out, o_bytes) || ranges_overlap(grad_B, g_bytes, arg, a_bytes)) return GESPMM_EINVAL;
+    Geometry geo = {};
+    const int x16_align = std::min(nnz != 0 ? pointer_alignment(grad_out) : 16, pointer_alignment(grad_B));
+    if ((rc = max_arg_geometry(K, M, N, nnz, max_arg_x16_align(x16_align, nnz != 0 ? pointer_alignment(arg) : 16), &geo)) != 0) return rc;
+    gespmm::MaxArgArgs a = {};
+    a.ptr = colptr;
+    a.ind = rowind;
+    a.order = order;
+    a.src = static_cast<const float*>(grad_out);
+    a.arg_in = arg;
+    a.dst = static_cast<float*>(grad_B);
+    a.S = (int32_t)K;
+    a.N = (int32_t)N;
+    return (int)gespmm::launch_spmm_max_backward_x16(a, dtype, geo, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_max_arg_route_x16(int64_t M, int64_t nnz, int64_t N, int x16_align, int arg_align, char* out, int64_t capacity) {
+    if (!out || capacity <= 0) return GESPMM_EINVAL;
+    if (x16_align < 2 || (x16_align & (x16_align - 1)) != 0 || arg_align < 4 || (arg_align & (arg_align - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::check_csr_sizes(M, 1, N, nnz, 0);
+    if (rc != 0) return rc;
+    int n;
+    if (M == 0 || N == 0) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else {
+        Geometry geo = {};
+        const int rcg = max_arg_geometry(M, 1, N, nnz, max_arg_x16_align(x16_align, arg_align), &geo);
+        if (rcg != 0) return rcg;
+        n = snprintf(out, (size_t)capacity, "V=%d S=%d W=%d", geo.vec, geo.strips, geo.group);
+    }
+    return describe_result(n, capacity);
+}
+
 int64_t gespmm_csr_spmm_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant,
                                         const gespmm_launch_cfg* cfg) {
     if (M < 0 || K < 0 || N < 0 || nnz < -1) return GESPMM_EINVAL;

@@ -52,4 +52,10 @@ inline bool max_arg_geometry_served(const Geometry& g) {
 hipError_t launch_spmm_max_arg(const MaxArgArgs& a, const Geometry& geo, hipStream_t st);
 hipError_t launch_spmm_max_backward(const MaxArgArgs& a, const Geometry& geo, hipStream_t st);
 
+// The same on 16-bit dense operands (spmm_max_arg_x16.hip; dtype kX16F16 / kX16Bf16): src and dst are the 16-bit arrays, arg stays int32,
+// N and the geometry count ELEMENTS. The chains above run in fp32 on the exactly widened elements, from `empty` as given; C and grad_B
+// are narrowed once at the store, to nearest even.
+hipError_t launch_spmm_max_arg_x16(const MaxArgArgs& a, int dtype, const Geometry& geo, hipStream_t st);
+hipError_t launch_spmm_max_backward_x16(const MaxArgArgs& a, int dtype, const Geometry& geo, hipStream_t st);
+
 }  // namespace gespmm

@@ -55,7 +55,8 @@ fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` 
 ``GATAggregateFunction`` is all three in one: no score and no attention array, nothing of size nnz x H saved (``GATConv(fused_aggregate=True)``).
 GraphSAGE (extension): ``SpmmMaxFunction`` is the max over neighbours with a gradient — the forward saves the winning CSR position of
 every output word (``spmm.csr_spmm_max_arg``), the backward adds ``grad_out`` where that position sits (``spmm.csr_spmm_max_backward``) —
-and ``SAGEConv`` DGL's layer of that name with the ``mean``, ``gcn`` and ``pool`` aggregators.
+and ``SAGEConv`` DGL's layer of that name with the ``mean``, ``gcn`` and ``pool`` aggregators. Both take fp16 / bf16 features
+(``spmm.csr_spmm_max_arg_x16`` / ``csr_spmm_max_backward_x16``; ``mean`` as the valued 16-bit product with fp32 weights 1 / deg).
 Graph transformers (extension): ``DotAttentionFunction`` is scaled dot-product attention over the edges in three fused launches
 (``attention.dot_attention`` and its two backward passes: no score, no alpha, nothing of size nnz saved), ``TransformerConv`` PyG's layer
 of that name on it (``fused=True``) or on the composition of the functions above (the default) — and on fp16 / bf16 q, k and v
@@ -1140,11 +1141,20 @@ class SpmmMaxFunction(torch.autograd.Function):
     ``feat``. The backward gives each word of ``grad_out`` to the ONE entry ``arg`` names: grad_feat[k, c] is the sum, in CSC order,
     of grad_out[r, c] over the rows that chose an entry of node k; words nobody chose (and rows that kept ``empty_value``) pass
     nothing on. Among equal values the first entry of the row gets the gradient. ``csc_order`` (int32) maps a CSC position to its CSR
-    position, as in the GAT functions. Index tensors get no gradient; once differentiable; fp32 only."""
+    position, as in the GAT functions. Index tensors get no gradient; once differentiable.
+
+    ``feat`` of ``torch.float16`` / ``torch.bfloat16`` runs on the 16-bit kernels (``spmm.csr_spmm_max_arg_x16`` /
+    ``csr_spmm_max_backward_x16``): ``out`` has the dtype of ``feat`` and is the exact maximum (a max rounds nothing), the saved ``arg``
+    is still the only saved array, ``grad_out`` arrives in the forward's dtype and each word of ``grad_feat`` is one fp32 add chain
+    rounded once."""
 
     @staticmethod
     def forward(ctx, rowptr, colind, colptr, rowind, csc_order, feat, empty_value=-10000.0):
-        out, arg = _spmm.csr_spmm_max_arg(rowptr, colind, feat.contiguous(), empty_value=empty_value)
+        ctx.x16 = feat.dtype in (torch.float16, torch.bfloat16)
+        if ctx.x16:
+            out, arg = _spmm.csr_spmm_max_arg_x16(rowptr, colind, feat.contiguous(), empty_value=empty_value)
+        else:
+            out, arg = _spmm.csr_spmm_max_arg(rowptr, colind, feat.contiguous(), empty_value=empty_value)
         ctx.save_for_backward(colptr, rowind, csc_order, arg)
         ctx.K = feat.shape[0]
         return out
@@ -1155,7 +1165,8 @@ class SpmmMaxFunction(torch.autograd.Function):
         colptr, rowind, csc_order, arg = ctx.saved_tensors
         grad_feat = None
         if ctx.needs_input_grad[5]:
-            grad_feat = _spmm.csr_spmm_max_backward(colptr, rowind, csc_order, arg, grad_out.contiguous(), ctx.K)
+            backward = _spmm.csr_spmm_max_backward_x16 if ctx.x16 else _spmm.csr_spmm_max_backward
+            grad_feat = backward(colptr, rowind, csc_order, arg, grad_out.contiguous(), ctx.K)
         return None, None, None, None, None, grad_feat, None
 
 
@@ -1170,7 +1181,16 @@ class SAGEConv(torch.nn.Module):
     with h = feat_drop(x), deg the row's entry count (rows without entries aggregate 0), then ``activation``, then ``norm``.
     ``forward(x, rowptr, colind, colptr, rowind, csc_order)`` takes the square pattern in both orders; ``csc_order`` (int32: CSC
     position -> CSR position, ``graphs.transpose_csr(..., return_order=True)``) is read by ``pool`` alone and may be None otherwise.
-    ``lstm`` is not served (ValueError). fp32 only."""
+    ``lstm`` is not served (ValueError).
+
+    16-bit features: the layer runs as ``.half()`` / ``.bfloat16()`` and under ``torch.autocast``; the dtype of the tensor that reaches
+    the aggregation decides the path, and fp32 tensors take exactly the steps above. On fp16 / bf16:
+
+        pool   ``SpmmMaxFunction`` on the 16-bit relu(fc_pool(h)): the exact maximum, int32 ``arg`` the only saved array
+        gcn    the 16-bit ``SPMMFunction`` sum (fp32 chain, one rounding), ``+ h``, times 1 / (deg + 1) cast to the dtype
+        mean   the VALUED 16-bit product with fp32 edge weights 1 / deg(row): one fp32 fma chain per word and ONE rounding (a 16-bit
+               sum scaled afterwards would round twice and can overflow fp16 on hub rows). The weights are two fp32 [nnz] arrays,
+               in CSR and in CSC order, made per forward by torch without a host synchronisation."""
 
     def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0.0, bias=True, norm=None, activation=None):
         super().__init__()
@@ -1200,13 +1220,22 @@ class SAGEConv(torch.nn.Module):
             raise ValueError("SAGEConv needs a square pattern and x of [%d, in_feats]" % n)
         h = self.feat_drop(x)
         degree = torch.diff(rowptr).to(torch.float32)
+        x16 = h.dtype in (torch.float16, torch.bfloat16)
         if self.aggregator_type == "mean":
             inv_deg = torch.where(degree > 0, 1 / degree, torch.zeros_like(degree))
-            h_neigh = FusedGCNFunction.apply(rowptr, colind, colptr, rowind, h, None, inv_deg, None)
+            if x16:
+                w_csr = torch.repeat_interleave(inv_deg, torch.diff(rowptr), output_size=colind.numel())
+                w_csc = inv_deg.index_select(0, rowind)
+                h_neigh = SPMMFunction.apply(rowptr, colind, colptr, rowind, h.contiguous(), w_csr, w_csc)
+            else:
+                h_neigh = FusedGCNFunction.apply(rowptr, colind, colptr, rowind, h, None, inv_deg, None)
             out = self.fc_self(h) + self.fc_neigh(h_neigh)
         elif self.aggregator_type == "gcn":
             h_sum = SPMMFunction.apply(rowptr, colind, colptr, rowind, h.contiguous())
-            out = self.fc_neigh((h_sum + h) / (degree + 1).unsqueeze(1))
+            if x16:
+                out = self.fc_neigh((h_sum + h) * (1 / (degree + 1)).to(h.dtype).unsqueeze(1))
+            else:
+                out = self.fc_neigh((h_sum + h) / (degree + 1).unsqueeze(1))
         else:
             if csc_order is None:
                 raise ValueError("the pool aggregator needs csc_order (graphs.transpose_csr(..., return_order=True), int32)")

@@ -715,7 +715,7 @@ def csr_spmm_max_arg(rowptr, colind, dense, empty_value=-10000.0, out=None, arg=
     int32[M, N]. Per output word ONE chain over the row's entries in CSR order, ``if dense[colind[p], c] > acc: acc, a = that, p`` from
     ``(empty_value, -1)``: ``arg`` is a CSR POSITION (not a column id), the first of equal values wins (+0 == -0), NaN and values
     ``<= empty_value`` never win. ``out`` has the bits of ``csr_spmm_max`` wherever no zeros of both signs compete for a maximum.
-    fp32 only; ``out=`` / ``arg=`` reuse the caller's tensors."""
+    fp32 tensors only (fp16 / bf16: ``csr_spmm_max_arg_x16``); ``out=`` / ``arg=`` reuse the caller's tensors."""
     _need(rowptr, "rowptr", torch.int32, 1)
     _need(colind, "colind", torch.int32, 1)
     _need(dense, "dense", torch.float32, 2)
@@ -760,6 +760,67 @@ def csr_spmm_max_backward(colptr, rowind, order, arg, grad_out, K, out=None):
         rc = lib.gespmm_csr_spmm_max_backward_f32(_ptr(colptr), _ptr(rowind), _ptr(order), _ptr(arg), _ptr(grad_out), _ptr(out), M, K, N,
                                                   rowind.numel(), _stream(dev))
     check(rc, "gespmm_csr_spmm_max_backward_f32")
+    return out
+
+
+def _need_x16(t, name, sibling):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if t.dtype not in _X16:
+        raise TypeError("%s must have dtype torch.float16 or torch.bfloat16, got %s (fp32: %s)" % (name, t.dtype, sibling))
+    _need(t, name, t.dtype, 2)
+
+
+def csr_spmm_max_arg_x16(rowptr, colind, dense, empty_value=-10000.0, out=None, arg=None):
+    """``csr_spmm_max_arg`` on 16-bit features (gespmm_csr_spmm_max_arg_x16): ``dense`` fp16 or bf16 [K, N]; returns ``(out, arg)``, ``out``
+    in the dtype of ``dense`` and ``arg`` int32. A max rounds nothing: the chain runs in fp32 on the exactly widened elements, from
+    ``empty_value`` as given, and ``out`` is narrowed once at the store — ``arg`` is that of ``csr_spmm_max_arg(.., dense.float(), ..)``
+    and ``out`` has the bits of its result cast to the dtype (an ``empty_value`` the dtype cannot hold, -10000 in bf16, is rounded only
+    where a row without a winner stores it). Any N and any 2-byte aligned tensor is served by one kernel; no allocation when ``out=`` and
+    ``arg=`` are given."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    _need_x16(dense, "dense", "csr_spmm_max_arg")
+    dev = _same_device(dense, rowptr, colind)
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have M+1 >= 1 entries")
+    empty_value = float(empty_value)
+    if empty_value != empty_value:
+        raise ValueError("empty_value must not be NaN")
+    M = rowptr.numel() - 1
+    K, N = dense.shape
+    out = torch.empty((M, N), dtype=dense.dtype, device=dev) if out is None else _result(out, "out", dense.dtype, (M, N), dev, (dense,))
+    arg = torch.empty((M, N), dtype=torch.int32, device=dev) if arg is None else _result(arg, "arg", torch.int32, (M, N), dev, (dense, out))
+    with _on_device(dev):
+        rc = lib.gespmm_csr_spmm_max_arg_x16(_ptr(rowptr), _ptr(colind), _ptr(dense), _ptr(out), _ptr(arg), M, K, N, colind.numel(),
+                                             empty_value, _X16[dense.dtype], _stream(dev))
+    check(rc, "gespmm_csr_spmm_max_arg_x16")
+    return out, arg
+
+
+def csr_spmm_max_backward_x16(colptr, rowind, order, arg, grad_out, K, out=None):
+    """``csr_spmm_max_backward`` on a 16-bit ``grad_out`` (gespmm_csr_spmm_max_backward_x16): fp16 or bf16 [K, N] in its dtype. Per word
+    one fp32 add chain from +0 in CSC order over the widened elements, rounded once at the store: the bits of
+    ``csr_spmm_max_backward(.., grad_out.float(), K).to(grad_out.dtype)``. ``arg`` stays int32."""
+    _need(colptr, "colptr", torch.int32, 1)
+    _need(rowind, "rowind", torch.int32, 1)
+    _need(order, "order", torch.int32, 1)
+    _need_x16(grad_out, "grad_out", "csr_spmm_max_backward")
+    _need(arg, "arg", torch.int32, 2)
+    dev = _same_device(grad_out, colptr, rowind, order, arg)
+    K = int(K)
+    if colptr.numel() != K + 1:
+        raise ValueError("colptr must have K + 1 = %d entries" % (K + 1))
+    if order.numel() != rowind.numel():
+        raise ValueError("order and rowind must have the same length")
+    if tuple(arg.shape) != tuple(grad_out.shape):
+        raise ValueError("arg must have the shape of grad_out, %s" % (list(grad_out.shape),))
+    M, N = grad_out.shape
+    out = torch.empty((K, N), dtype=grad_out.dtype, device=dev) if out is None else _result(out, "out", grad_out.dtype, (K, N), dev, (grad_out, arg))
+    with _on_device(dev):
+        rc = lib.gespmm_csr_spmm_max_backward_x16(_ptr(colptr), _ptr(rowind), _ptr(order), _ptr(arg), _ptr(grad_out), _ptr(out), M, K, N,
+                                                  rowind.numel(), _X16[grad_out.dtype], _stream(dev))
+    check(rc, "gespmm_csr_spmm_max_backward_x16")
     return out
 
 

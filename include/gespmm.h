@@ -181,6 +181,35 @@ int gespmm_csr_spmm_max_backward_f32(const int32_t* colptr, const int32_t* rowin
  * arg and grad_out), c_align: of the results (C and arg; grad_B). Returns the length written or a GESPMM_E* code. */
 int gespmm_max_arg_route(int64_t M, int64_t nnz, int64_t N, int b_align, int c_align, char* out, int64_t capacity);
 
+/*
+ * The same two on 16-bit dense operands: B [K, N], C [M, N], grad_out [M, N] and grad_B [K, N] are IEEE fp16 or bfloat16 (dtype
+ * GESPMM_X16_F16 / GESPMM_X16_BF16, one type per call; anything else -> GESPMM_EINVAL, before every other check); arg stays int32
+ * [M, N], empty_value stays a float. A max rounds nothing, so the contract is the fp32 one on the exactly widened operand:
+ *
+ *     forward    acc = empty_value (fp32, as given); a = -1
+ *                for p ascending:  b = widen(B[colind[p] N + c]);  if (b > acc) { acc = b; a = p; }
+ *                C[r, c] = narrow(acc);  arg[r, c] = a
+ *     backward   g = +0 (fp32);  for q ascending:  if (arg[r N + c] == order[q]) g = g + widen(grad_out[r N + c]);  grad_B[k, c] = narrow(g)
+ *
+ * widen is exact; narrow rounds ONCE, to nearest even, at the store. C therefore has the bits of narrow(gespmm_csr_spmm_max_arg_f32 on
+ * widen(B)) and arg is identical; an empty_value the type cannot hold (-10000 in bf16) is compared exactly and rounded only where a row
+ * without a winner stores it. Ties, zeros of both signs and NaN: as above.
+ *
+ * One kernel each, the fp32 walk with V ELEMENTS per lane: V = 4 needs 8-byte aligned 16-bit arrays and a 16-byte aligned arg, V = 2
+ * 4- and 8-byte, V = 1 serves any N and any 2-byte aligned address (2-byte loads and stores; no composition route, no scratch). 16-byte
+ * loads (V = 8) are not built. Checks and their order are those of the fp32 entries; the 16-bit arrays must be 2-byte aligned (index
+ * arrays and arg: 4), overlaps count 2 bytes per 16-bit element, and the size limits are unchanged — K N 4 < 2^32 and M N 4 < 2^32 —
+ * because arg is the 4-byte array that sets them. No allocation, no host synchronisation: capturable.
+ */
+int gespmm_csr_spmm_max_arg_x16(const int32_t* rowptr, const int32_t* colind, const void* B, void* C, int32_t* arg, int64_t M, int64_t K,
+                                int64_t N, int64_t nnz, float empty_value, int dtype, void* stream);
+int gespmm_csr_spmm_max_backward_x16(const int32_t* colptr, const int32_t* rowind, const int32_t* order, const int32_t* arg,
+                                     const void* grad_out, void* grad_B, int64_t M, int64_t K, int64_t N, int64_t nnz, int dtype,
+                                     void* stream);
+/* Host only: gespmm_max_arg_route for the two calls above, V in ELEMENTS. x16_align: largest power of two (>= 2) dividing the addresses
+ * of the 16-bit arrays, arg_align: (>= 4) of arg. The answer is gespmm_max_arg_route's at the alignment min(2 x16_align, arg_align). */
+int gespmm_max_arg_route_x16(int64_t M, int64_t nnz, int64_t N, int x16_align, int arg_align, char* out, int64_t capacity);
+
 /* The variant `GESPMM_VARIANT_AUTO` resolves to for this shape (pure host logic). */
 int gespmm_select_variant(int64_t M, int64_t nnz, int64_t N);
 
