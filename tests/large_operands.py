@@ -92,6 +92,44 @@ def case_windows(M, K, N, elem=4, spread=14):
     return windows(M, marks, spread), windows(K, marks, spread)
 
 
+# ---- the max reducer on the band: closed forms of both directions, by window (the 16-bit tests and their host checks) -----------------
+
+def max_arg_at(r, n):
+    """arg[r, n] = r d + ((r + n) mod d): word n of row r was won by the row's entry j = (r + n) mod d (test_gpu_large_edges.py)."""
+    return r * D + (r + n) % D
+
+
+def max_grad_at(r, n):
+    """grad_out[r, n] = ((r + 3 n) mod 7) - 3, an integer in -3 .. 3: exact in fp32, bf16 and fp16."""
+    return (r + 3 * n) % 7 - 3
+
+
+def ref_max_forward(r0, r1, H, F, device="cpu", dense_fn=None):
+    """(int64[r1 - r0, H F] max, int64[r1 - r0, H F] arg) of rows r0 .. r1: the largest of dense(r + o_j, h, f) over the d band entries
+    and the CSR position r d + j of the FIRST entry that reaches it."""
+    dense_fn = b_at(H, F) if dense_fn is None else dense_fn
+    r = torch.arange(r0, r1, device=device, dtype=torch.int64).view(-1, 1, 1, 1)
+    j = torch.arange(D, device=device, dtype=torch.int64).view(1, D, 1, 1)
+    hh, ff = band._hf(H, F, device)
+    vals = dense_fn(r + band.offset_of(j), hh, ff)
+    top = vals.max(1, keepdim=True).values
+    first = torch.where(vals == top, j, D).min(1).values
+    return top.reshape(r1 - r0, H * F), (r.view(-1, 1, 1) * D + first).reshape(r1 - r0, H * F)
+
+
+def ref_max_backward(M, c0, c1, N, device="cpu", grad_fn=max_grad_at, arg_fn=max_arg_at):
+    """int64[c1 - c0, N]: columns c0 .. c1 of grad_B — column c receives grad(r, n) from every row r = c - o_j of the band whose
+    arg(r, n) names that entry's CSR position r d + j."""
+    c = torch.arange(c0, c1, device=device, dtype=torch.int64).view(-1, 1, 1)
+    j = torch.arange(D, device=device, dtype=torch.int64).view(1, -1, 1)
+    n = torch.arange(N, device=device, dtype=torch.int64).view(1, 1, -1)
+    r = c - band.offset_of(j)
+    inside = (r >= 0) & (r < M)
+    r = r.clamp(0, M - 1)  # (rows outside the band contribute nothing; clamped so that the closed forms see a row that exists)
+    hit = inside & (arg_fn(r, n) == r * D + j)
+    return (hit.to(torch.int64) * grad_fn(r, n)).sum(1)
+
+
 FLOAT_ROWS = 512  # rows of a float op's sub-pattern (test_gpu_large_edges.py)
 
 

@@ -3,7 +3,9 @@ case lists reach the launch parameters of every family's tables (a condition on 
 it held), every family's comparison rejects a result that lost one entry, and the float64 references moved into
 tests/attention_refs.py give what the private helpers of the GPU test files gave before the move. For the two 16-bit attention
 families (gatv2_attention_x16, dot_x16) also: the fp32 restatement of every case, both dtypes and both passes, stays inside the
-sweep's float64 rule with the 16-bit results rounded once, bf16 bits read as fp16 leave it, and the inputs witness the rounding."""
+sweep's float64 rule with the 16-bit results rounded once, bf16 bits read as fp16 leave it, and the inputs witness the rounding. For
+the 16-bit max reducer (max_arg_x16), whose every comparison is on bits: the expected bits of every case, type and kind, and five
+conditions on the inputs under which a wrong kernel would leave the comparison."""
 import numpy as np
 import pytest
 import torch
@@ -130,6 +132,22 @@ def reach(family, L, seed=None):
         for name, S in (("forward", "M"), ("backward", "K")):
             got = [L.max_arg_route(c["G"][S], c["G"]["nnz"], c["H"] * c["F"], x, x) for c, x in zip(cases, a)]
             geo(name, [g for g in got if g is not None])
+    elif family == "max_arg_x16":
+        # both passes of the sweep: the 16-bit arrays at the case's offset and 2 bytes further, arg at twice that modulo 16
+        got = {(name, extra): [] for name in ("forward", "backward") for extra in (0, 2)}
+        for c in cases:
+            for extra in (0, 2):
+                xa, aa = (fz.align_at(o) for o in fz.x16_offsets(c["offset"], extra))
+                for name, S in (("forward", "M"), ("backward", "K")):
+                    g = L.max_arg_route_x16(c["G"][S], c["G"]["nnz"], c["H"] * c["F"], xa, aa)
+                    assert g is not None and g == L.max_arg_route(c["G"][S], c["G"]["nnz"], c["H"] * c["F"], min(2 * xa, aa, 16), min(2 * xa, aa, 16))
+                    got[(name, extra)].append(g)
+        for name in ("forward", "backward"):
+            geo(name, got[(name, 0)] + got[(name, 2)])
+        assert {g[0] for name in ("forward", "backward") for g in got[(name, 2)]} == {1}, "the second pass is V = 1 throughout"
+        r["first pass V"] = {g[0] for name in ("forward", "backward") for g in got[(name, 0)]}
+        r["longest row"] = {int(c["G"]["degs"].max()) for c in cases}
+        r["empty_value"] = {fz.MAX_ARG_EMPTIES[c["seed"] % 3] for c in cases}
     elif family == "gatv2_attention":
         pairs = set()
         for c in live:
@@ -239,6 +257,14 @@ def wanted(family):
 
         for name in ("forward", "backward"):
             w[name + " V"], w[name + " S"], w[name + " W"] = ({t[i] for t in BUILT} for i in range(3))
+    elif family == "max_arg_x16":
+        # as the fp32 family, over both passes together; V = 4 and 2 on the first pass (the second is V = 1 throughout), hubs of 2049
+        # and 4097 entries (the tile stream refills dozens of times inside one segment) and each of the three empty_values
+        from test_gpu_max_arg import BUILT
+
+        for name in ("forward", "backward"):
+            w[name + " V"], w[name + " S"], w[name + " W"] = ({t[i] for t in BUILT} for i in range(3))
+        w.update({"first pass V": {2, 4}, "longest row": {2049, 4097}, "empty_value": set(fz.MAX_ARG_EMPTIES)})
     elif family == "gatv2_attention":
         # every V and every W on its own, as for the dot attention (the geometry is the same rule)
         w.update({"V": {1, 2, 4}, "W": POW2, "p": set(fz.PS)})
@@ -643,6 +669,170 @@ def test_max_arg_comparison_rejects_a_lost_entry():
     g1 = refs.max_backward(G["colptr"], G["rowind"], G["order"], arg, grad, G["K"])
     g2 = refs.max_backward(G2["colptr"], G2["rowind"], G2["order"], arg2, grad, G["K"])
     assert not np.array_equal(g1, g2)
+
+
+# ------------------------------------------------------------------------------------- the max reducer on 16-bit operands (3.29)
+# Every comparison of the family is on bits: there is no rule to stay inside. What can be judged without a device is that the expected
+# bits of all 24 x 2 x 3 combinations come out of the test's own plumbing, and that each comparison would see a kernel that is wrong in
+# one of the ways such a kernel can be: an entry lost, the other type, the last of equal values, a rounding per add, empty_value rounded
+# before it is compared. Each is a condition on the INPUTS, checked with the references alone.
+
+def max_arg_forward_last(rowptr, colind, B, empty_value):
+    """``max_arg_ref.max_arg_forward`` with its compare turned into ``>=``: of equal values the LAST wins. A local copy, wrong on purpose."""
+    B = np.asarray(B, dtype=np.float32)
+    M, N = len(rowptr) - 1, B.shape[1]
+    C = np.full((M, N), np.float32(empty_value), dtype=np.float32)
+    arg = np.full((M, N), -1, dtype=np.int32)
+    with np.errstate(invalid="ignore"):
+        for r in range(M):
+            acc, a = C[r], arg[r]
+            for p in range(int(rowptr[r]), int(rowptr[r + 1])):
+                b = B[colind[p]]
+                win = b >= acc
+                acc[win] = b[win]
+                a[win] = p
+    return C, arg
+
+
+def round16(x, dtype):
+    """fp32 -> fp32, rounded to ``dtype`` to nearest even, in numpy (finite values; ``refs.rounded`` without the trip through torch:
+    it runs once per entry below)."""
+    if dtype == torch.float16:
+        return x.astype(np.float16).astype(np.float32)
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    return ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def max_backward_rounding_every_add(colptr, rowind, order, arg, grad_out, K, dtype):
+    """``max_arg_ref.max_backward`` with g rounded to the 16-bit type after EVERY add. A local copy, wrong on purpose."""
+    grad_B = np.zeros((K, grad_out.shape[1]), dtype=np.float32)
+    for k in range(K):
+        g = grad_B[k]
+        for q in range(int(colptr[k]), int(colptr[k + 1])):
+            r = rowind[q]
+            hit = arg[r] == order[q]
+            if hit.any():
+                g[hit] = round16(g[hit] + grad_out[r][hit], dtype)
+    return grad_B
+
+
+@pytest.mark.parametrize("dtype", fz.X16_DTYPES, ids=fz.X16_IDS)
+def test_max_arg_x16_restatement_of_every_case(pkg, dtype):
+    """The reference path of ``test_max_arg_x16`` for all 24 cases and three kinds of this type, no device: the expected bits are those
+    both passes compare with (a pass moves the arrays, not the values). out is NaN nowhere — B holds NaN in the floats, and a NaN never
+    wins —, -inf exactly where empty_value is -inf and no entry won, finite elsewhere (-20000 and 65504 > |normals| fit fp16); arg is -1
+    on every empty row and a position of its own row elsewhere; grad_B is finite. -10000 stores as -9984 in bf16."""
+    bits = lambda v: int(fz.narrow_bits(np.full(1, v, dtype=np.float32), dtype)[0]) & 0xFFFF  # noqa: E731
+    assert bits(-10000.0) == (0xF0E2 if dtype == torch.float16 else 0xC61C) and bits(0.0) == 0 and bits(-np.inf) == (0xFC00 if dtype == torch.float16 else 0xFF80)
+    widen = lambda b: torch.from_numpy(b.copy()).view(dtype).float().numpy()  # noqa: E731
+    for c in fz.max_arg_x16_cases():
+        G, msg = c["G"], "%s %s" % (fz.what("max_arg_x16", c), dtype)
+        want = fz.max_arg_x16_expected(c["index"], dtype)
+        assert want["empty"] == fz.MAX_ARG_EMPTIES[c["seed"] % 3] and np.isfinite(want["grad"]).all()
+        assert np.array_equal(round16(want["grad"], dtype), want["grad"]), "grad_out holds 16-bit values"
+        lo_, hi = G["rowptr"][:-1][:, None], G["rowptr"][1:][:, None]
+        for kind in fz.MAX_ARG_KINDS:
+            w = want[kind]
+            assert kind == "floats" or np.isfinite(w["B"]).all(), (msg, kind)
+            out, arg = widen(w["out_bits"]), w["arg"]
+            assert out.shape == arg.shape == (G["M"], c["H"] * c["F"]) and w["grad_B_bits"].shape == (G["K"], c["H"] * c["F"])
+            assert not np.isnan(out).any(), (msg, kind)
+            assert np.array_equal(np.isinf(out), (arg == -1) & np.isinf(want["empty"])), (msg, kind)
+            assert bool(((arg == -1) | ((arg >= lo_) & (arg < hi))).all()) and bool((arg[G["degs"] == 0] == -1).all()), (msg, kind)
+            assert bool((w["out_bits"][arg == -1].astype(np.int64) & 0xFFFF == bits(want["empty"])).all()), (msg, kind)
+            assert np.isfinite(widen(w["grad_B_bits"])).all(), (msg, kind)
+
+
+@pytest.mark.parametrize("dtype", fz.X16_DTYPES, ids=fz.X16_IDS)
+def test_max_arg_x16_comparison_rejects_a_lost_entry(dtype):
+    """(a) ``test_max_arg_comparison_rejects_a_lost_entry`` on the narrowed operand, through the narrowed bits the sweep compares."""
+    c = _short_case("max_arg_x16")
+    G, N = c["G"], c["H"] * c["F"]
+    B = refs.rounded(np.abs(np.random.RandomState(c["seed"]).standard_normal((G["K"], N))).astype(np.float32), dtype)
+    C, arg = refs.max_arg_forward(G["rowptr"], G["colind"], B, -10000.0)
+    r, e = _longest_row(G)
+    lost = int(arg[r, 0])  # the winner of the longest row's first word
+    assert lost in e
+    G2 = _without(G, lost)
+    C2, arg2 = refs.max_arg_forward(G2["rowptr"], G2["colind"], B, -10000.0)
+    assert not np.array_equal(fz.narrow_bits(C, dtype), fz.narrow_bits(C2, dtype)) or len(np.unique(G["colind"][e])) < len(e)
+    assert not np.array_equal(arg, arg2)
+    grad = np.ones((G["M"], N), dtype=np.float32)
+    g1 = refs.max_backward(G["colptr"], G["rowind"], G["order"], arg, grad, G["K"])
+    g2 = refs.max_backward(G2["colptr"], G2["rowind"], G2["order"], arg2, grad, G["K"])
+    assert not np.array_equal(fz.narrow_bits(g1, dtype), fz.narrow_bits(g2, dtype))
+
+
+def test_max_arg_x16_comparison_rejects_the_other_type():
+    """(b) The expected out and grad_B bits of a bf16 case differ from the fp16 expectation of the same case in every kind: a kernel
+    that narrowed (or a comparison that read) by the other type's rule leaves the comparison."""
+    c = _short_case("max_arg_x16", need=1)
+    bf, fp = (fz.max_arg_x16_expected(c["index"], dt) for dt in (torch.bfloat16, torch.float16))
+    for kind in ("floats", "positive"):  # (integers in -2 .. 2 pick the same winners in both types; their BITS differ all the same)
+        assert not np.array_equal(bf[kind]["out_bits"], fp[kind]["out_bits"]), kind
+        assert not np.array_equal(bf[kind]["grad_B_bits"], fp[kind]["grad_B_bits"]), kind
+    live = bf["ints"]["arg"] >= 0
+    assert live.any() and np.array_equal(bf["ints"]["arg"], fp["ints"]["arg"]) and np.array_equal(bf["ints"]["C"], fp["ints"]["C"])
+    assert bool((bf["ints"]["out_bits"][live] != fp["ints"]["out_bits"][live]).any())
+
+
+def test_max_arg_x16_comparison_rejects_the_last_position_rule():
+    """(c) On the integers (-2 .. 2: exact in both types, ties everywhere) ``>=`` in place of ``>`` changes arg in EVERY case that has
+    a row of two or more entries — 22 of the 24 at this seed."""
+    tied = 0
+    for c in fz.max_arg_x16_cases():
+        G = c["G"]
+        if G["degs"].size == 0 or G["degs"].max() < 2:
+            continue
+        tied += 1
+        for dtype in fz.X16_DTYPES:
+            want = fz.max_arg_x16_expected(c["index"], dtype)
+            assert np.array_equal(want["ints"]["B"], np.round(want["ints"]["B"])) and np.abs(want["ints"]["B"]).max() <= 2
+            _, last = max_arg_forward_last(G["rowptr"], G["colind"], want["ints"]["B"], want["empty"])
+            assert not np.array_equal(last, want["ints"]["arg"]), fz.what("max_arg_x16", c)
+    print("max_arg_x16: %d of %d cases have a row of two or more entries" % (tied, fz.N_CASES))
+    assert tied >= 12
+
+
+@pytest.mark.parametrize("dtype", fz.X16_DTYPES, ids=fz.X16_IDS)
+def test_max_arg_x16_comparison_rejects_a_rounding_per_add(dtype):
+    """(d) "Narrowed once" is observable: a chain that rounds g to the 16-bit type after every add changes a word of grad_B in a case
+    of the family (three or more rows must have chosen one node for one word: the first add and the second are exact or rounded once
+    either way). Cases in ascending nnz; the first witness ends the search."""
+    g = np.random.RandomState(3).standard_normal(4096).astype(np.float32)
+    assert np.array_equal(round16(g, dtype), refs.rounded(g, dtype)), "the numpy rounding is torch's"
+    for c in sorted(fz.max_arg_x16_cases(), key=lambda c: c["G"]["nnz"]):
+        G = c["G"]
+        if G["nnz"] < 3:
+            continue
+        want = fz.max_arg_x16_expected(c["index"], dtype)
+        for kind in fz.MAX_ARG_KINDS:
+            every = max_backward_rounding_every_add(G["colptr"], G["rowind"], G["order"], want[kind]["arg"], want["grad"], G["K"], dtype)
+            changed = int((fz.narrow_bits(every, dtype) != want[kind]["grad_B_bits"]).sum())
+            if changed:
+                print("%s %s %s: %d of %d words of grad_B change under a rounding per add" % (fz.what("max_arg_x16", c), dtype, kind, changed, every.size))
+                return
+    raise AssertionError("no case witnesses the one narrowing of grad_B")
+
+
+def test_max_arg_x16_comparison_rejects_a_narrowed_empty_value():
+    """(e) -10000 is no bf16 value. Compared after narrowing (-9984) it changes arg in a bf16 case of the family: a word whose best
+    entry is the planted -9984 has a winner against -10000 as given and none against -9984 (``max_arg_x16_inputs`` plants -9984 and
+    -10048 in the bf16 floats; no other draw holds a value in [-10000, -9984])."""
+    bf = torch.bfloat16
+    assert float(refs.rounded(np.float32([-10000.0]), bf)[0]) == -9984.0
+    for c in fz.max_arg_x16_cases():
+        want = fz.max_arg_x16_expected(c["index"], bf)
+        if want["empty"] != -10000.0 or c["G"]["nnz"] == 0:
+            continue
+        B = want["floats"]["B"]
+        _, arg = refs.max_arg_forward(c["G"]["rowptr"], c["G"]["colind"], B, -9984.0)
+        changed = int((arg != want["floats"]["arg"]).sum())
+        if changed:
+            print("%s: %d words of arg change when empty_value is narrowed before the compare" % (fz.what("max_arg_x16", c), changed))
+            assert bool((arg[arg != want["floats"]["arg"]] == -1).all())
+            return
+    raise AssertionError("no bf16 case tells -10000 from its rounding")
 
 
 @pytest.mark.parametrize("H,F", ((8, 3), (8, 32), (33, 3), (33, 32)))

@@ -9,6 +9,8 @@ long-row threshold of 2048, and two wavefront sweeps) — plus two laws of this 
 "mean" (a mean degree that lands the softmax's W on 4, 8 or 16, with rows of IT W and IT W + 1 entries: both sides of the register /
 sweep boundary). A case holds at most 2^22 words nnz H F; an (H, F) over the cap is redrawn. tests/test_attention_fuzz_host.py asserts,
 without a GPU, that the case lists below reach the launch parameters of every family's tables and that every comparison can fail."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -30,12 +32,12 @@ PS = (0.0, 0.25, 0.6)
 CAP = 1 << 22
 N_CASES = 24
 FAMILIES = ("heads", "sddmm", "softmax", "aggregate", "gatv2", "dropout", "dot", "max_arg", "gatv2_attention", "gatv2_x16",
-            "gatv2_attention_x16", "dot_x16")
+            "gatv2_attention_x16", "dot_x16", "max_arg_x16")
 # one seed per family, chosen on the CPU so that the reach conditions of tests/test_attention_fuzz_host.py hold
 FAMILY_SEEDS = {"heads": 20261227, "sddmm": 20262022, "softmax": 20263020, "aggregate": 20264032, "gatv2": 20265021,
                 "dropout": 20266023, "dot": 20267022, "max_arg": 20268022,
                 "gatv2_attention": 20269000, "gatv2_x16": 20270024,
-                "gatv2_attention_x16": 20271023, "dot_x16": 20272031}
+                "gatv2_attention_x16": 20271023, "dot_x16": 20272031, "max_arg_x16": 20273002}
 GUARD = 64
 NAN = float("nan")
 WORST = {}
@@ -1064,3 +1066,128 @@ def test_dot_attention_x16(pkg, dtype):
             check64=lambda h, keep, ks, msg: refs.dot_x16_check_all(G, x, h, dtype, keep, ks, what=msg),
             neighbour=x["v"])
     _report("%s %s" % (family, X16_IDS[X16_DTYPES.index(dtype)]))
+
+
+# ------------------------------------------------------------------------------------------ 13. the max reducer on 16-bit operands
+
+MAX_ARG_KINDS = ("ints", "floats", "positive")
+MAX_ARG_EMPTIES = (-10000.0, 0.0, float("-inf"))
+
+
+def narrow_bits(a, dtype):
+    """fp32 host array -> the bits (int16) of its ONE rounding to ``dtype``, to nearest even."""
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dtype).view(torch.int16).numpy()
+
+
+def max_arg_x16_inputs(c, dtype):
+    """-> (grad_out, {kind: B}, empty_value): the draws of ``test_max_arg_and_backward`` in its order — grad_out seeded normals, B
+    integers in -2 .. 2, normals with planted +0, -0, NaN and -20000, and |normals| — rounded once to ``dtype`` and widened again
+    (``refs.rounded``): the fp32 values of what the device holds, so the reference sees bf16's -19968 where -20000 was planted.
+    ``empty_value`` is one of -10000, 0 and -inf by the case's seed. bf16 alone: after every other draw, -9984 and -10048 are planted
+    in the floats (4 % of the words each) — the two bf16 neighbours of -10000, which is no bf16 value; no draw holds either by itself,
+    and without them nothing in the family tells a compare against -10000 as given from one against its rounding, -9984."""
+    G, N = c["G"], c["H"] * c["F"]
+    rng = np.random.RandomState(c["seed"])
+    grad = rng.standard_normal((G["M"], N)).astype(np.float32)
+    B = {"ints": rng.randint(-2, 3, size=(G["K"], N)).astype(np.float32)}
+    B["floats"] = rng.standard_normal((G["K"], N)).astype(np.float32)
+    for value in (0.0, -0.0, np.nan, -20000.0):
+        B["floats"][rng.rand(G["K"], N) < 0.04] = np.float32(value)
+    B["positive"] = np.abs(rng.standard_normal((G["K"], N))).astype(np.float32)
+    if dtype == torch.bfloat16:
+        for value in (-9984.0, -10048.0):
+            B["floats"][rng.rand(G["K"], N) < 0.04] = np.float32(value)
+    return refs.rounded(grad, dtype), {k: refs.rounded(v, dtype) for k, v in B.items()}, MAX_ARG_EMPTIES[c["seed"] % 3]
+
+
+@functools.lru_cache(maxsize=None)
+def max_arg_x16_cases():
+    return tuple(family_cases("max_arg_x16"))
+
+
+@functools.lru_cache(maxsize=None)
+def max_arg_x16_expected(index, dtype):
+    """The expected results of case ``index`` in ``dtype``, computed once and shared by the device test and the host tests (nobody
+    writes into them): {"empty", "grad" (widened fp32), kind: {"B" (widened fp32), "arg", "C" (fp32, of the widened operand), "out_bits"
+    (C narrowed once), "grad_B" (fp32 chain on the widened grad_out), "grad_B_bits" (narrowed once)}}."""
+    c = max_arg_x16_cases()[index]
+    G = c["G"]
+    grad, B, empty = max_arg_x16_inputs(c, dtype)
+    want = {"empty": empty, "grad": grad}
+    for kind in MAX_ARG_KINDS:
+        C, arg = refs.max_arg_forward(G["rowptr"], G["colind"], B[kind], empty)
+        gB = refs.max_backward(G["colptr"], G["rowind"], G["order"], arg, grad, G["K"])
+        want[kind] = {"B": B[kind], "arg": arg, "C": C, "out_bits": narrow_bits(C, dtype), "grad_B": gB, "grad_B_bits": narrow_bits(gB, dtype)}
+    return want
+
+
+def _host_bits16(t):
+    return t.contiguous().view(torch.int16).cpu().numpy()
+
+
+@pytest.mark.parametrize("dtype", X16_DTYPES, ids=X16_IDS)
+def test_max_arg_x16(pkg, dtype):
+    """csr_spmm_max_arg_x16 and csr_spmm_max_backward_x16 (width N = H F), every comparison on bits: arg the restatement's on the
+    exact widening of the 16-bit operand, out its C narrowed once, grad_B the fp32 add chain on the widened grad_out narrowed once
+    (``max_arg_x16_expected``). Two passes: B, out, grad_out and grad_B at the case's offset in bytes, then 2 bytes further, where the
+    route function must answer V = 1 (neighbouring lanes store the two halves of a dword); arg at the fp32 oracle's offset, twice the
+    16-bit one modulo 16. Operands of ``test_max_arg_and_backward`` narrowed once; empty_value -10000 (no bf16 value: compared as given,
+    narrowed only where a row keeps it), 0 or -inf by the case's seed. On |normals| the fp32 entry on the widened operand, on the GPU,
+    gives the same arg and, narrowed, the same out. First pass: a second run repeats the bits. On the MI355X: 0.43 s (bf16) and
+    0.38 s (fp16) in the module's own run, where the other 16-bit families take 0.66 - 0.72 s; no mismatch."""
+    from gespmm_amd import _lib, spmm
+
+    for c in max_arg_x16_cases():
+        G, N, off = c["G"], c["H"] * c["F"], c["offset"]
+        g = _graph(G)
+        want = max_arg_x16_expected(c["index"], dtype)
+        empty = want["empty"]
+        empty_bits = narrow_bits(np.full(1, empty, dtype=np.float32), dtype)[0]
+        empty_r = G["degs"] == 0
+        for extra in (0, 2):
+            at16, at32 = x16_offsets(off, extra)
+            msg = "%s %s empty_value=%s, 16-bit arrays %d bytes off, arg %d" % (what("max_arg_x16", c), dtype, empty, at16, at32)
+            for S in (G["M"], G["K"]):
+                route = _lib.max_arg_route_x16(S, G["nnz"], N, align_at(at16), align_at(at32))
+                assert route is not None and (extra == 0 or route[0] == 1), (msg, route)
+            grad = _place(_dev(want["grad"]).to(dtype), at16)
+            for kind in MAX_ARG_KINDS:
+                w, m2 = want[kind], "%s %s" % (msg, kind)
+                B = _place(_dev(w["B"]).to(dtype), at16)
+                assert B.data_ptr() % 16 == at16 == grad.data_ptr() % 16
+
+                def forward():
+                    oc, oa = Out((G["M"], N), at16, dtype), Out((G["M"], N), at32, torch.int32)
+                    assert oc.t.data_ptr() % 16 == at16 and oa.t.data_ptr() % 16 == at32
+                    r = spmm.csr_spmm_max_arg_x16(g["rowptr"], g["colind"], B, empty_value=empty, out=oc.t, arg=oa.t)
+                    assert r[0] is oc.t and r[1] is oa.t
+                    return oc.check(m2 + ": out"), oa.check(m2 + ": arg")
+
+                out, arg = forward()
+                assert out.dtype == dtype and np.array_equal(arg.cpu().numpy(), w["arg"]), m2 + ": arg"
+                assert np.array_equal(_host_bits16(out), w["out_bits"]), m2 + ": out"
+                if empty_r.any():
+                    assert bool((arg.cpu().numpy()[empty_r] == -1).all()) and bool((_host_bits16(out)[empty_r] == empty_bits).all()), \
+                        m2 + ": an empty row is not (narrow(empty_value), -1)"
+                if kind == "positive":
+                    C32, arg32 = spmm.csr_spmm_max_arg(g["rowptr"], g["colind"], _place(_dev(w["B"]), at32), empty_value=empty)
+                    _same(arg32, arg, m2 + ": arg against the fp32 entry on the widened operand")
+                    _same(C32.to(dtype), out, m2 + ": out against the fp32 entry's C narrowed once")
+
+                def backward():
+                    ob = Out((G["K"], N), at16, dtype)
+                    assert ob.t.data_ptr() % 16 == at16
+                    assert spmm.csr_spmm_max_backward_x16(g["colptr"], g["rowind"], g["order"], arg, grad, G["K"], out=ob.t) is ob.t
+                    return ob.check(m2 + ": grad_B")
+
+                gB = backward()
+                assert gB.dtype == dtype and np.array_equal(_host_bits16(gB), w["grad_B_bits"]), m2 + ": grad_B"
+                chosen = np.zeros(G["K"], dtype=bool)
+                chosen[G["colind"][w["arg"][w["arg"] >= 0]]] = True
+                _plus_zero(gB, ~chosen, m2 + ": grad_B of a node no row chose")
+                if not extra:
+                    out2, arg2 = forward()
+                    _same(out2, out, m2 + ": out, second run")
+                    _same(arg2, arg, m2 + ": arg, second run")
+                    _same(backward(), gB, m2 + ": grad_B, second run")
+    print("max_arg_x16 %s: %d cases, two passes, every comparison on bits" % (X16_IDS[X16_DTYPES.index(dtype)], N_CASES))

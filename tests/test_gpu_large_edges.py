@@ -16,8 +16,11 @@ fail in grad_feat / grad_k at column 77, the column that holds CSC position 1024
 
 Section f runs the edge-sized ops again at H = 17 — arrays of 1.14e9 words, between 2^30 and 2^31 — and take_edges at 64-byte rows.
 
-On the MI355X the module takes about 8.4 s (the fixture 1 s, no test above 1.3 s) and peaks at 19.3 GiB of device memory (section f: four
-arrays of 4.5 GB; 7.8 GB without it)."""
+The max reducer runs in both directions and both widths of element (section d): the forward, the op that PRODUCES positions past 2^26,
+in fp32 and bf16, and the backward on a closed-form argmax in fp32 and bf16.
+
+On the MI355X the module takes about 9.3 s for 54 tests (8.4 s for 51 before the three max-reducer cases were added; the fixture 1 s, no
+test above 1.3 s) and peaks at 19.3 GiB of device memory (section f: four arrays of 4.5 GB; 7.8 GB without it)."""
 import numpy as np
 import pytest
 import torch
@@ -309,9 +312,14 @@ def test_gat_aggregate_with_dyadic_alpha(big):
                    lambda r0, r1: band.ref_csr_product(g.M, g.d, r0, r1, H, F, DEV, weight_fn=one))
 
 
-def test_max_backward_on_a_closed_form_argmax(big):
+MAX_DTYPES, MAX_IDS = (torch.float32, torch.bfloat16), ("float32", "bfloat16")
+
+
+@pytest.mark.parametrize("dtype", MAX_DTYPES, ids=MAX_IDS)
+def test_max_backward_on_a_closed_form_argmax(big, dtype):
     """arg[r, n] = r d + ((r + n) mod d): row r's word n was won by its entry j = (r + n) mod d. Column k then receives grad_out[r, n]
-    from every row r = k - o_j with (r + n) mod d == j."""
+    from every row r = k - o_j with (r + n) mod d == j. bfloat16: grad_out narrowed (integers in -3 .. 3) through
+    csr_spmm_max_backward_x16; a sum is an integer of at most 64 x 3 in magnitude, exact in bf16; the reference is the same int64 form."""
     from gespmm_amd import spmm
 
     g, N = big, 4
@@ -320,7 +328,11 @@ def test_max_backward_on_a_closed_form_argmax(big):
     arg = (r * g.d + (r + n) % g.d).to(torch.int32)
     grad_fn = lambda r, n: (r + 3 * n) % 7 - 3  # noqa: E731
     grad_out = grad_fn(r, n).to(torch.float32)
-    out = spmm.csr_spmm_max_backward(g.colptr, g.rowind, g.order32, arg, grad_out, g.K, out=_nan((g.K, N)))
+    if dtype == torch.float32:
+        out = spmm.csr_spmm_max_backward(g.colptr, g.rowind, g.order32, arg, grad_out, g.K, out=_nan((g.K, N)))
+    else:
+        out = spmm.csr_spmm_max_backward_x16(g.colptr, g.rowind, g.order32, arg, grad_out.to(dtype), g.K, out=_nan((g.K, N), dtype))
+    assert out.dtype == dtype and g.d * 3 <= 256
 
     def ref(c0, c1):
         c = torch.arange(c0, c1, device=DEV, dtype=torch.int64).view(-1, 1, 1)
@@ -330,7 +342,34 @@ def test_max_backward_on_a_closed_form_argmax(big):
         hit = (rr >= 0) & (rr < g.M) & ((rr + nn) % g.d == j)
         return (hit.to(torch.int64) * grad_fn(rr, nn)).sum(1)
 
-    _check_windows("csr_spmm_max_backward", out, g.col_windows, ref)
+    _check_windows("csr_spmm_max_backward %s" % dtype, out, g.col_windows, ref)
+
+
+@pytest.mark.parametrize("dtype", MAX_DTYPES, ids=MAX_IDS)
+def test_max_arg_forward_past_2_26(big, dtype):
+    """The forward is the op that PRODUCES positions past 2^26: N = 4, B = band.node_values (integers in -3 .. 3, exact in bf16:
+    tests/test_large_edges_host.py), every row window against the closed form — the largest of the row's d = 64 band entries and
+    arg = r d + the first j that reaches it (seven values over 64 entries: ties in every word, the first-position rule decides)."""
+    from gespmm_amd import spmm
+
+    g, N = big, 4
+    B = band.node_values(g.K, 1, N, DEV, dtype).view(g.K, N)
+    out, arg = _nan((g.M, N), dtype), torch.full((g.M, N), -7, dtype=torch.int32, device=DEV)
+    fn = spmm.csr_spmm_max_arg if dtype == torch.float32 else spmm.csr_spmm_max_arg_x16
+    got = fn(g.rowptr, g.colind, B, out=out, arg=arg)
+    assert got[0] is out and got[1] is arg and out.dtype == dtype
+    _all_written(out=out)
+    assert int(arg.min()) >= 0 and int(arg.max()) > (1 << 26)
+    assert any(s0 * g.d <= g.wrap < s1 * g.d for s0, s1 in g.row_windows), "the window holding position nnz - 2^26 is compared"
+    j = torch.arange(g.d, device=DEV, dtype=torch.int64).view(1, -1, 1)
+    f = torch.arange(N, device=DEV, dtype=torch.int64).view(1, 1, -1)
+    for r0, r1 in g.row_windows:
+        r = torch.arange(r0, r1, device=DEV, dtype=torch.int64).view(-1, 1, 1)
+        vals = band.b_of(r + band.offset_of(j), 0, f)
+        top = vals.max(1, keepdim=True).values
+        first = torch.where(vals == top, j, g.d).min(1).values
+        assert torch.equal(out[r0:r1].float(), top.view(-1, N).to(torch.float32)), "max, rows %d .. %d" % (r0, r1)
+        assert torch.equal(arg[r0:r1].long(), r.view(-1, 1) * g.d + first), "arg, rows %d .. %d" % (r0, r1)
 
 
 def test_transpose_csr_with_values(big):

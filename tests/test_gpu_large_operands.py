@@ -27,9 +27,14 @@ and tolerances of their own tests, on 512-row sub-patterns of the marked, first 
 e). Every result goes into a NaN-prefilled tensor and must hold no NaN anywhere. Dense operands are filled in row chunks (integer
 temporaries of 256 MB) or in place. No tolerance is new.
 
-On the MI355X the module takes 84 s for 83 tests (the slowest 6.3 s; single times move by seconds with the allocation and release
-of tens of GB, the kernels take milliseconds) and peaks at 65.6 GiB of device memory (dot attention in regime B: eight arrays of
-8 GB)."""
+Section a also runs the max reducer's 16-bit entries (spmm_max_arg_kernel.h) at the same limit, which counts the 4-byte words of
+``arg``: the backward reads grad_out at ``(off + 4 c) >> 1`` with the top bit of the ``uint32_t`` sum set in the upper half of the rows.
+
+On the MI355X the module takes 86 s for 89 tests (84 s for 83 before the six 16-bit max-reducer cases; the slowest 6.2 s; single
+times move by seconds with the allocation and release of tens of GB, the kernels take milliseconds) and peaks at 65.6 GiB of device
+memory (dot attention in regime B: eight arrays of 8 GB). The slowest new case, test_max_arg_x16_below_the_4gb_limit, took 0.05 s
+in the module's run and 1.24 s ([8x64-fp16]) in a run of the max-reducer cases alone; its peak is below the fp32 case's (the two
+largest arrays halve)."""
 import numpy as np
 import pytest
 import torch
@@ -281,6 +286,71 @@ def test_max_arg_refuses_the_first_size_past_the_limit(pkg, H, F):
     with pytest.raises(_lib.GespmmError) as e:
         spmm.csr_spmm_max_backward(g.colptr, g.rowind, g.order32, arg, out, K, out=grad)
     assert e.value.code == ERANGE and "gespmm_csr_spmm_max_backward_f32" in str(e.value)
+    assert bool(torch.isnan(grad[-4096:]).all())
+
+
+X16_DTYPES, X16_IDS = (torch.bfloat16, torch.float16), ("bf16", "fp16")
+
+
+@pytest.mark.parametrize("dtype", X16_DTYPES, ids=X16_IDS)
+@pytest.mark.parametrize("H,F", lo.WIDTHS, ids=WIDTH_IDS)
+def test_max_arg_x16_below_the_4gb_limit(pkg, H, F, dtype):
+    """The 16-bit entries at the largest size ``max_arg_sizes`` accepts. The limit counts the 4-byte ``arg`` words: arg ends just below
+    byte 2^32 and the 16-bit B, out, grad_out and grad_B just below byte 2^31. The backward stages the arg row's byte offset r N 4 as
+    ``uint32_t`` and reads grad_out at ``(off + 4 c) >> 1``: above row 2^31 / (4 N) the sum has its top bit set, and a signed shift, a
+    31-bit mask or an ``int`` temporary in that expression is wrong only there — those rows, and the last, lie inside the windows
+    (tests/test_large_operands_host.py). The closed forms are test_max_arg_below_the_4gb_limit's (lo.ref_max_forward,
+    lo.ref_max_backward); every value is an integer of at most 8 x 3 in magnitude, exact in both types."""
+    from gespmm_amd import _lib, spmm
+
+    N = H * F
+    M, K = lo.sizes_a(N, "below", "rows")
+    assert K * N * 4 < (1 << 32) <= (K + 1) * N * 4 and K * N * 2 < (1 << 31)
+    _need(24)
+    g = _band(M)
+    rw, cw = _windows(g, N)
+    assert _lib.max_arg_route_x16(M, g.nnz, N) is not None and _lib.max_arg_route_x16(K, g.nnz, N) is not None
+    dense = _nodes(K, H, F, dtype).view(K, N)
+    out, arg = spmm.csr_spmm_max_arg_x16(g.rowptr, g.colind, dense, out=_nan((M, N), dtype),
+                                         arg=torch.full((M, N), -7, dtype=torch.int32, device=DEV))
+    assert out.dtype == dtype
+    _written(out=out)
+    assert int(arg.min()) >= 0
+    for r0, r1 in rw:
+        top, first = lo.ref_max_forward(r0, r1, H, F, DEV)
+        assert torch.equal(out[r0:r1].float(), top.to(torch.float32)), "max, rows %d .. %d" % (r0, r1)
+        assert torch.equal(arg[r0:r1].long(), first), "arg, rows %d .. %d" % (r0, r1)
+    del dense, out, arg, top, first
+    arg, grad_out = _arg_and_grad(M, N)
+    tail, nn = torch.arange(M - 64, M, device=DEV).view(-1, 1), torch.arange(N, device=DEV).view(1, -1)
+    assert torch.equal(arg[-64:].long(), lo.max_arg_at(tail, nn)) and torch.equal(grad_out[-64:].long(), lo.max_grad_at(tail, nn))
+    grad_out = grad_out.to(dtype)
+    grad = spmm.csr_spmm_max_backward_x16(g.colptr, g.rowind, g.order32, arg, grad_out, K, out=_nan((K, N), dtype))
+    assert grad.dtype == dtype
+    _written(grad=grad)
+    _check_windows("csr_spmm_max_backward_x16", grad, cw, lambda c0, c1: lo.ref_max_backward(M, c0, c1, N, DEV))
+
+
+@pytest.mark.parametrize("H,F", lo.WIDTHS, ids=WIDTH_IDS)
+def test_max_arg_x16_refuses_the_first_size_past_the_limit(pkg, H, F):
+    """One row more: both 16-bit entries raise GespmmError with GESPMM_ERANGE, with real arrays, and write nothing (bf16)."""
+    from gespmm_amd import _lib, spmm
+
+    N, dtype = H * F, torch.bfloat16
+    M, K = lo.sizes_a(N, "at", "rows")
+    assert K * N * 4 >= (1 << 32) > (K - 1) * N * 4
+    _need(24)
+    g = _band(M)
+    dense, out = torch.empty((K, N), dtype=dtype, device=DEV), _nan((M, N), dtype)
+    arg = torch.full((M, N), -7, dtype=torch.int32, device=DEV)
+    with pytest.raises(_lib.GespmmError) as e:
+        spmm.csr_spmm_max_arg_x16(g.rowptr, g.colind, dense, out=out, arg=arg)
+    assert e.value.code == ERANGE and "gespmm_csr_spmm_max_arg_x16" in str(e.value)
+    assert bool(torch.isnan(out[-4096:]).all()) and bool((arg[-4096:] == -7).all())
+    grad = _nan((K, N), dtype)
+    with pytest.raises(_lib.GespmmError) as e:
+        spmm.csr_spmm_max_backward_x16(g.colptr, g.rowind, g.order32, arg, out, K, out=grad)
+    assert e.value.code == ERANGE and "gespmm_csr_spmm_max_backward_x16" in str(e.value)
     assert bool(torch.isnan(grad[-4096:]).all())
 
 

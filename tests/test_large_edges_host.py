@@ -110,6 +110,31 @@ def test_first_difference_names_the_element():
     assert band.first_difference(c, c)[0] == (0, 0, 0)
 
 
+def test_the_max_reducer_operands_past_2_26_are_exact_in_bf16_and_tied():
+    """test_gpu_large_edges.test_max_arg_forward_past_2_26 / test_max_backward_on_a_closed_form_argmax[bfloat16]: band.node_values at
+    H = 1, N = 4 and the closed-form grad_out narrow to bf16 without a change (integers in -3 .. 3), a backward sum is an integer of at
+    most 64 x 3 <= 2^8 in magnitude (exact in bf16's 8 significant bits), and the closed-form forward agrees with the reducer's
+    restatement on a small band with ties in every word — the first-position rule decides them."""
+    from max_arg_ref import max_arg_forward, tied_words
+
+    d, M, N = 64, 300, 4
+    K = band.sizes(M, d)[1]
+    wide = band.node_values(K, 1, N)
+    assert torch.equal(band.node_values(K, 1, N, dtype=torch.bfloat16).float(), wide) and int(wide.abs().max()) == 3
+    r, n = torch.arange(M).view(-1, 1), torch.arange(N).view(1, -1)
+    grad = ((r + 3 * n) % 7 - 3).to(torch.float32)
+    assert torch.equal(grad.to(torch.bfloat16).float(), grad) and d * 3 <= (1 << 8)
+    rowptr, colind = (t.numpy() for t in band.csr(M, d))
+    B = wide.view(K, N).numpy()
+    C, arg = max_arg_forward(rowptr, colind, B, -10000.0)
+    j, f = torch.arange(d).view(1, -1, 1), torch.arange(N).view(1, 1, -1)
+    vals = band.b_of(r.view(-1, 1, 1) + band.offset_of(j), 0, f)
+    top = vals.max(1, keepdim=True).values
+    first = torch.where(vals == top, j, d).min(1).values
+    assert np.array_equal(C, top.view(-1, N).numpy().astype(np.float32)) and np.array_equal(arg, (r * d + first).numpy().astype(np.int32))
+    assert tied_words(rowptr, colind, B, C, arg).all()
+
+
 # ---- graphs.take_edges ----------------------------------------------------------------------------------------------------------------
 
 def _bits(t):

@@ -57,6 +57,11 @@ def test_below_and_at_lie_on_the_two_sides_of_the_switch(L, H, F, elem, side, wa
         assert f(*[None] * 5, M, K, N, nnz, -1e4, None) == (EINVAL if below else ERANGE)
         assert b(*[None] * 6, M, K, N, nnz, None) == (EINVAL if below else ERANGE)
         assert L.max_arg_route(M, nnz, N) is not None
+        # ... and its 16-bit entries: the limit is the same one, counted in the 4-byte words of arg
+        for code in (L.X16_BF16, L.X16_F16):
+            assert L.lib.gespmm_csr_spmm_max_arg_x16(*[None] * 5, M, K, N, nnz, -1e4, code, None) == (EINVAL if below else ERANGE)
+            assert L.lib.gespmm_csr_spmm_max_backward_x16(*[None] * 6, M, K, N, nnz, code, None) == (EINVAL if below else ERANGE)
+        assert L.max_arg_route_x16(M, nnz, N) is not None and L.max_arg_route_x16(K, nnz, N) is not None
 
 
 def _entries(L, H, F, slope=0.2):
@@ -487,6 +492,91 @@ def test_gatv2_x16_comparators_reject_a_displaced_gather(H, F, regime, shift, si
         got = restate_backward(P["colptr"], P["rowind"], x["gs"], x["xr"], x["xl"], x["att"], slope, order=P["order"])
         other = restate_backward(P["colptr"], P["rowind"], x["gs"], xo["xr"], xo["xl"], x["att"], slope, order=P["order"])
     assert not np.array_equal(narrowed(got[0]), narrowed(other[0])), "grad_x"
+
+
+# ---- the 16-bit max reducer at the 4 GB limit (section a of the GPU module) -------------------------------------------------------------
+
+def _x16_max_sizes(H, F):
+    N = H * F
+    M, K = lo.sizes_a(N, "below", "rows")
+    assert K * N * 4 < (1 << 32) <= (K + 1) * N * 4 and (1 << 30) < M * N * 2 < K * N * 2 < (1 << 31)
+    return N, M, K
+
+
+@pytest.mark.parametrize("H,F", lo.WIDTHS)
+def test_windows_of_the_16_bit_max_reducer(H, F):
+    """The windows of test_max_arg_x16_below_the_4gb_limit are marked at elem = 4, the size of an ``arg`` word: the row with byte 2^31
+    of arg is the row with byte 2^30 of every 16-bit array — from it on ``off + 4 c`` has its top bit set — and it, and the last row of
+    every operand, lie inside a row window and a column window."""
+    N, M, K = _x16_max_sizes(H, F)
+    rw, cw = _check_marks(M, K, N, 4, False)
+    r = (1 << 31) // (N * 4)
+    assert r == (1 << 30) // (N * 2) and r * N * 2 <= (1 << 30) < (r + 1) * N * 2 and r * N * 4 <= (1 << 31) < (r + 1) * N * 4
+    for rows in (M, K):
+        assert r in lo.marked(rows, N, 4) and rows - 1 in lo.marked(rows, N, 4) and r < rows - 1
+    assert lo.holds(rw, r) and lo.holds(cw, r) and lo.holds(rw, M - 1) and lo.holds(cw, M - 1) and lo.holds(cw, K - 1)
+    assert ((M - 1) * N * 4 + 4 * (N - 1)) >> 31 == 1 and (M - 1) * N * 4 + 4 * (N - 1) <= (1 << 32) - 16, "the largest staged sum: top bit set"
+    assert ((r - 1) * N * 4) >> 31 == 0
+
+
+def _marks_with_an_alias(rows, N, shift_words):
+    """The marked rows (elem = 4: the windows' marks) of a [rows, N] array that hold a word whose alias ``shift_words`` back lies inside"""
+    return [m for m in lo.marked(rows, N, 4) if (m + 1) * N > shift_words]
+
+
+@pytest.mark.parametrize("H,F", lo.WIDTHS)
+def test_16_bit_max_references_reject_a_displaced_gather(H, F):
+    """What a lost top bit of ``(off + 4 c)`` reads: grad_out 2^30 bytes back (elem = 2), arg 2^31 bytes back (elem = 4) — 2^29 words
+    either way; and for the forward a B row 2^30 bytes back. Around every marked row whose alias lies inside the array, the closed-form
+    reference through the displaced offset must differ from the true one: the comparisons of the GPU test are exact equalities."""
+    N, M, K = _x16_max_sizes(H, F)
+    shift = 1 << 29  # words of arg, elements of a 16-bit array
+    assert shift % 7 != 0 and (1 << 30) % 7 != 0, "b_at and max_grad_at are residues modulo 7"
+    # ---- forward: B (K rows, 16-bit) gathered 2^30 bytes back
+    fn = lo.b_at(H, F)
+    wrong = lo.displaced(fn, H, F, 1 << 30, K, 2)
+    marks = _marks_with_an_alias(K, N, shift)
+    assert (1 << 30) // (N * 2) in marks and K - 1 in marks
+    for m in marks:
+        r1 = min(m + 1, M)
+        good, bad = (lo.ref_max_forward(max(r1 - 32, 0), r1, H, F, dense_fn=f_) for f_ in (fn, wrong))
+        assert not (torch.equal(good[0], bad[0]) and torch.equal(good[1], bad[1])), ("forward", m)
+        assert not torch.equal(good[0], bad[0]), ("forward: the values alone", m)
+    # ---- backward: grad_out (M rows, 16-bit) 2^30 bytes back, arg (M rows, 4-byte) 2^31 bytes back
+    grad_back = lo.displaced(lambda r, h, f: lo.max_grad_at(r, f), 1, N, 1 << 30, M, 2)
+    arg_back = lo.displaced(lambda r, h, f: lo.max_arg_at(r, f), 1, N, 1 << 31, M, 4)
+    marks = _marks_with_an_alias(M, N, shift)
+    assert (1 << 31) // (N * 4) in marks and M - 1 in marks
+    for m in marks:
+        c0, c1 = m, min(m + 32, K)
+        good = lo.ref_max_backward(M, c0, c1, N)
+        assert int(good.abs().sum()) > 0 and int(good.abs().max()) <= D * 3
+        bad_grad = lo.ref_max_backward(M, c0, c1, N, grad_fn=lambda r, n: grad_back(r, 0, n))
+        bad_arg = lo.ref_max_backward(M, c0, c1, N, arg_fn=lambda r, n: arg_back(r, 0, n))
+        for dtype in (torch.bfloat16, torch.float16):
+            narrow = lambda t: t.to(torch.float32).to(dtype)  # noqa: E731  (what _check_windows compares with)
+            assert band.first_difference(narrow(good), narrow(bad_grad)) is not None, ("grad_out", m, dtype)
+            assert band.first_difference(narrow(good), narrow(bad_arg)) is not None, ("arg", m, dtype)
+
+
+def test_the_closed_forms_of_the_max_reducer_are_the_fp32_tests():
+    """lo.ref_max_forward / lo.ref_max_backward against the reducer's restatement (max_arg_ref.py) on a small band with the same
+    operands: the closed forms the 16-bit GPU test compares with are the chains' results."""
+    from max_arg_ref import max_arg_forward, max_backward, transpose
+
+    M, H, F = 200, 3, 5
+    N, K = H * F, M + lo.LAST
+    rowptr, colind = (t.numpy() for t in band.csr(M, D))
+    r, h, f = torch.arange(K).view(-1, 1, 1), torch.arange(H).view(1, H, 1), torch.arange(F).view(1, 1, F)
+    B = lo.b_at(H, F)(r, h, f).reshape(K, N).numpy().astype(np.float32)
+    C, arg = max_arg_forward(rowptr, colind, B, -10000.0)
+    top, first = lo.ref_max_forward(0, M, H, F)
+    assert np.array_equal(C, top.numpy().astype(np.float32)) and np.array_equal(arg, first.numpy().astype(np.int32))
+    rr, nn = torch.arange(M).view(-1, 1), torch.arange(N).view(1, -1)
+    arg2, grad = lo.max_arg_at(rr, nn).numpy().astype(np.int32), lo.max_grad_at(rr, nn).numpy().astype(np.float32)
+    colptr, rowind, order = transpose(rowptr, colind, K)
+    want = max_backward(colptr, rowind, order, arg2, grad, K)
+    assert np.array_equal(want, lo.ref_max_backward(M, 0, K, N).numpy().astype(np.float32))
 
 
 # ---- the band at d = 8 ----------------------------------------------------------------------------------------------------------------
