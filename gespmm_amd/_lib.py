@@ -173,6 +173,7 @@ EXPORTS = [
     "gespmm_csr_spmm_heads_order_x16",
     "gespmm_plan_spmm_heads_order_f32",
     "gespmm_edge_gather",
+    "gespmm_describe_gat_backward",
 ]
 
 X16_F16 = 1
@@ -478,6 +479,8 @@ def _load():
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
     lib.gespmm_describe_edge_softmax.argtypes = [c_int64, c_int64, c_int64, c_char_p, c_int64]
+    lib.gespmm_describe_gat_backward.restype = c_int
+    lib.gespmm_describe_gat_backward.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
     lib.gespmm_plan_set_values.restype = c_int
     lib.gespmm_plan_set_values.argtypes = [p, p, p]
     lib.gespmm_plan_get_order.restype = c_int
@@ -579,6 +582,22 @@ def describe_edge_softmax(M, nnz, H):
         return {"form": "none"}
     w, long_rows = text.split()
     return {"W": int(w.split("=")[1]), "L": int(long_rows.split(">")[1])}
+
+
+def describe_gat_backward(M, K, H, F, nnz, transposed=False, aligns=(16, 16)):
+    """What gespmm_gat_backward_el_f32 (transposed=True: gespmm_gat_backward_er_f32) and their dropout siblings would launch for these
+    sizes and the alignments of (``grad_out``, ``feat``) — the function the entry points route through, the pin
+    GESPMM_GAT_BACKWARD_FORM=lane|group included (gespmm_describe_gat_backward: host only). A dict ``{"form": "lane" | "group", "V":
+    floats per load, "Wd": lanes that share a dot (lane form: 1), "W": lanes per (segment, head) pair, "L": longer segments take a whole
+    wavefront}``; ``{"form": "none"}`` where nothing is launched. In the group form (V, Wd) fix the bits of the dot: those of the
+    multi-head SDDMM at that (V, W)."""
+    buf = ctypes.create_string_buffer(96)
+    n = lib.gespmm_describe_gat_backward(int(M), int(K), int(H), int(F), int(nnz), 1 if transposed else 0, int(aligns[0]), int(aligns[1]),
+                                         buf, 96)
+    if n < 0:
+        raise GespmmError(n, "gespmm_describe_gat_backward")
+    out = dict(kv.split("=") for kv in buf.value.decode().split())
+    return {k: (v if k == "form" else int(v)) for k, v in out.items()}
 
 
 def describe_gatv2_score(M, nnz, H, F, xl_align=16, xr_align=16, att_align=16, x16=False):

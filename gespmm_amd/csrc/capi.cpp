@@ -1451,7 +1451,17 @@ uint32_t gespmm_edge_dropout_bits(uint32_t s0, uint32_t s1, uint32_t r, uint32_t
 uint32_t gespmm_edge_dropout_threshold(float p) { return (p >= 0.0f && p < 1.0f) ? gespmm::edge_dropout_threshold(p) : 0xffffffffu; }
 
 /* The fused backward of a GAT layer for el / er (gespmm.h; gat_backward.h): two launches on node-sized words, no [nnz x H] array. The
-   ladder is check_gat_backward_sizes, then the pointers. */
+   ladder is check_gat_backward_sizes, then the pointers; then the form resolve_gat_backward answers (lane or group), nothing else.
+   GESPMM_GAT_BACKWARD_FORM=lane|group pins the form (read per call: scripts/gat_backward_group_timing.py measures both in one process);
+   resolve_gat_backward says where the pin is ignored (an ineligible call runs the lane form). */
+static int gat_backward_pin() {
+    if (const char* env = getenv("GESPMM_GAT_BACKWARD_FORM")) {
+        if (!strcmp(env, "lane")) return gespmm::kGatBackwardPinLane;
+        if (!strcmp(env, "group")) return gespmm::kGatBackwardPinGroup;
+    }
+    return gespmm::kGatBackwardPinNone;
+}
+
 static int gat_backward_el_entry(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
                                  const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K, int64_t H,
                                  int64_t F, int64_t nnz, float slope, const float* p, const void* seed, void* stream) {
@@ -1471,6 +1481,11 @@ static int gat_backward_el_entry(const int32_t* rowptr, const int32_t* colind, c
         return rcp;
     gespmm::EdgeDropout dropout = {};
     if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    const gespmm::GatBackwardLaunch b =
+        gespmm::resolve_gat_backward(M, nnz, H, F, pointer_alignment(grad_out), pointer_alignment(feat), gat_backward_pin());
+    if (b.form == gespmm::kGatBackwardGroup)
+        return (int)gespmm::launch_gat_backward_group_el(rowptr, colind, el, er, stats, grad_out, feat, delta, grad_el, M, K, H, F, nnz, slope,
+                                                         b, p ? &dropout : nullptr, st);
     return (int)gespmm::launch_gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, delta, grad_el, M, K, H, F, nnz, slope, r,
                                                p ? &dropout : nullptr, st);
 }
@@ -1505,6 +1520,11 @@ static int gat_backward_er_entry(const int32_t* colptr, const int32_t* rowind, c
         return rcp;
     gespmm::EdgeDropout dropout = {};
     if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    const gespmm::GatBackwardLaunch b =
+        gespmm::resolve_gat_backward(K, nnz, H, F, pointer_alignment(grad_out), pointer_alignment(feat), gat_backward_pin());
+    if (b.form == gespmm::kGatBackwardGroup)
+        return (int)gespmm::launch_gat_backward_group_er(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope,
+                                                         b, p ? &dropout : nullptr, st);
     return (int)gespmm::launch_gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope, r,
                                                p ? &dropout : nullptr, st);
 }
@@ -1519,6 +1539,25 @@ int gespmm_gat_backward_er_dropout_f32(const int32_t* colptr, const int32_t* row
                                        const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
                                        int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream) {
     return gat_backward_er_entry(colptr, rowind, el, er, stats, delta, grad_out, feat, grad_er, M, K, H, F, nnz, slope, &p, seed, stream);
+}
+
+/* Host only: what the two entry points above would launch — the function they route through, the pin included. */
+int gespmm_describe_gat_backward(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int grad_out_align, int feat_align,
+                                 char* out, int64_t capacity) {
+    if (!out || capacity <= 0 || grad_out_align < 4 || feat_align < 4 || (transposed != 0 && transposed != 1)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, 1.0f);
+    if (rc != 0) return rc;
+    int n;
+    if (nnz == 0 || F == 0 || (!transposed && M == 0)) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else {
+        const gespmm::GatBackwardLaunch b =
+            gespmm::resolve_gat_backward(transposed ? K : M, nnz, H, F, grad_out_align > 16 ? 16 : grad_out_align,
+                                         feat_align > 16 ? 16 : feat_align, gat_backward_pin());
+        n = snprintf(out, (size_t)capacity, "form=%s V=%d Wd=%d W=%d L=%d", b.form == gespmm::kGatBackwardGroup ? "group" : "lane", b.V, b.Wd,
+                     b.W, b.L);
+    }
+    return describe_result(n, capacity);
 }
 
 int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,

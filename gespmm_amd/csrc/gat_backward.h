@@ -57,4 +57,30 @@ hipError_t launch_gat_backward_er(const int32_t* colptr, const int32_t* rowind, 
                                   int64_t H, int64_t F, int64_t nnz, float slope, const EdgeSoftmaxLaunch& r, const EdgeDropout* drop,
                                   hipStream_t st);
 
+// ---- The GROUP form (kernels in gat_backward_group.hip): the same two passes, the same segment geometry, regimes and pinned orders of
+// delta, gs_p, grad_el and grad_er — only g_p is computed differently. The 64 lanes of a wavefront also form 64 / W_d dot sub-groups of
+// W_d contiguous lanes, (4, W_d) = resolve_sddmm's answer at WIDTH F for 16-byte aligned operands (W_d the smallest power of two in
+// 4 .. 64 with 8 W_d >= F, independent of the segment width W); per batch of entries a sub-group serves, in W_d steps, the entry each
+// of its lanes owns, and
+//   g_p      lane q of the W_d runs ONE chain acc = fmaf(a_j, b_j, acc) from +0 over j = 4 q + i + 4 W_d t (i ascending in a vector,
+//            t < 2 ascending; a lane past the slice keeps +0), then the xor butterfly W_d / 2 .. 1
+// which is launch_sddmm_heads' order at (4, W_d), in every form of that kernel, H = 1 included. Hence on ANY operands:
+//   grad_el and grad_er have the bits of launch_gat_softmax, launch_sddmm_heads, launch_gat_softmax_backward and
+//   launch_edge_segment_sum(colptr, .., order); delta has them in the pairs whose products alpha * grad_alpha are exact (the fmaf chain
+//   rounds once where the composition rounds twice: the lane form's caveat, unchanged); with drop != nullptr they are the bits of that
+//   composition with launch_edge_dropout between the SDDMM and the softmax's backward.
+// Form rule (resolve_gat_backward, select.cpp — the one place): the group form is ELIGIBLE when F % 4 == 0, 16 <= F <= 512 and grad_out
+// and feat are both 16-byte aligned (V is then always 4: the bits depend on F alone); an eligible launch takes it where F >=
+// kGatBackwardGroupMinF (measured; 0: nowhere) or the pin GESPMM_GAT_BACKWARD_FORM=group says so; =lane pins the lane form. Every other
+// launch takes the lane form, whose contract above stands. r.form == kGatBackwardGroup; a launch outside the rule is refused
+// (hipErrorInvalidValue). nnz >= 1 (the lane form's entry serves nnz == 0). No atomics, no LDS, no workspace: capturable.
+hipError_t launch_gat_backward_group_el(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                        const float* grad_out, const float* feat, float* delta, float* grad_el, int64_t M, int64_t K,
+                                        int64_t H, int64_t F, int64_t nnz, float slope, const GatBackwardLaunch& r, const EdgeDropout* drop,
+                                        hipStream_t st);
+hipError_t launch_gat_backward_group_er(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                        const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
+                                        int64_t H, int64_t F, int64_t nnz, float slope, const GatBackwardLaunch& r, const EdgeDropout* drop,
+                                        hipStream_t st);
+
 }  // namespace gespmm

@@ -317,6 +317,24 @@ EdgeSoftmaxLaunch resolve_edge_softmax(int64_t M, int64_t nnz, int64_t H) {
     return r;
 }
 
+// The fused GAT backward. Segment geometry: the edge softmax's, for both forms. The group form's dot geometry is resolve_sddmm's at
+// WIDTH F (its COO form: no row-walking or blocked answer) — the (V, W) of launch_sddmm_heads in every form, H = 1 included — and it
+// is eligible only where that V is 4 whatever else holds, so its bits depend on F alone. Which eligible widths take it by default is
+// kGatBackwardGroupMinF (select.h: measured); the pin overrides that threshold, never eligibility.
+GatBackwardLaunch resolve_gat_backward(int64_t S, int64_t nnz, int64_t H, int64_t F, int grad_out_align, int feat_align, int pin) {
+    const EdgeSoftmaxLaunch e = resolve_edge_softmax(S, nnz, H);
+    const bool aligned = grad_out_align >= 16 && feat_align >= 16;
+    GatBackwardLaunch r = {kGatBackwardLane, (F % 4 == 0 && aligned) ? 4 : 1, 1, e.W, e.L, e.rpw};
+    const bool eligible = F % 4 == 0 && F >= 16 && F <= kGatBackwardGroupMaxF && aligned;
+    const bool by_default = kGatBackwardGroupMinF >= 16 && F >= kGatBackwardGroupMinF;
+    if (!eligible || pin == kGatBackwardPinLane || (pin != kGatBackwardPinGroup && !by_default)) return r;
+    const SddmmLaunch b = resolve_sddmm(false, 1, 1, F, 16, 16, false, 4);
+    r.form = kGatBackwardGroup;
+    r.V = b.V;
+    r.Wd = b.W;
+    return r;
+}
+
 // The GATv2 score. V and W are resolve_sddmm's at WIDTH F — asked in its COO form, which has no row-walking or blocked answer — with the
 // less aligned of xl and xr as one operand and att as the other: V divides F and 4 V bytes divide all THREE bases. Entries per wavefront
 // and the multiply-shift for t / H are resolve_sddmm_heads' rule for its CSR kernel, on the pair count nnz H. None of these thresholds

@@ -71,6 +71,30 @@ struct EdgeSoftmaxLaunch {
 // M >= 1, nnz >= 1, H >= 1. W and L depend on (M, nnz) alone.
 EdgeSoftmaxLaunch resolve_edge_softmax(int64_t M, int64_t nnz, int64_t H);
 
+// ---- fused GAT backward for el / er (gat_backward.h): which of its two forms a launch takes, and the shape of both
+// (gespmm_describe_gat_backward prints it; the two entry points run exactly this).
+enum GatBackwardForm {
+    kGatBackwardLane = 0,   // gat_backward.hip: one lane walks the whole dot of the entry it owns
+    kGatBackwardGroup = 1,  // gat_backward_group.hip: W_d lanes walk it, in the multi-head SDDMM's order at (4, W_d)
+};
+enum GatBackwardPin { kGatBackwardPinNone = 0, kGatBackwardPinLane = 1, kGatBackwardPinGroup = 2 };
+constexpr int64_t kGatBackwardGroupMaxF = 512;  // a lane of the group form holds 8 floats of a head slice, a dot sub-group has <= 64 lanes
+// The smallest width from which the group form is the default; 0: nowhere (the pin alone reaches it). MEASURED, never below 16: the
+// smallest of {16, 32, 64} from which the group form's two launches beat the lane form's on com-amazon-sbm AND pubmed beyond the
+// spread of the runs (profiles/r25/gat_backward_group/timing.log).
+constexpr int64_t kGatBackwardGroupMinF = 16;
+struct GatBackwardLaunch {
+    int form;       // GatBackwardForm
+    int V, Wd;      // group form: (4, W_d) = resolve_sddmm's answer at WIDTH F, which fixes the bits of g; lane form: V = 4 or 1 (the
+                    // width of its loads, no bit depends on it), Wd = 1
+    int W, L, rpw;  // resolve_edge_softmax(S, nnz, H), for both forms
+};
+// S: the segments of the pass (M rows, or K columns). F >= 1. *_align: largest power of two (bytes) that divides the address of
+// grad_out / feat. The group form is ELIGIBLE when F % 4 == 0, 16 <= F <= kGatBackwardGroupMaxF and both alignments are 16 (so V is
+// always 4 and the bits depend on F alone); an eligible call takes it from kGatBackwardGroupMinF on, or wherever the pin says group.
+GatBackwardLaunch resolve_gat_backward(int64_t S, int64_t nnz, int64_t H, int64_t F, int grad_out_align, int feat_align,
+                                       int pin = kGatBackwardPinNone);
+
 // ---- GATv2 edge score (gatv2_score.h): the launch shape of the forward (gespmm_describe_gatv2_score prints it).
 struct Gatv2ScoreLaunch {
     int V, W;        // what resolve_sddmm answers for WIDTH F, with att's address as a third operand: they fix the summation order

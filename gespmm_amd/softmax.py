@@ -398,7 +398,11 @@ def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slop
     the pinned order of ``gat_edge_softmax_backward``. ``grad_out`` f32[M, H, F], ``feat`` f32[K, H, F]. ``delta`` is what
     ``gat_backward_er`` needs. ``out``: a pair of tensors ``(delta, grad_el)`` to write into; every word is written, empty rows +0.
     ``dropout=(p, seed)``: the backward of ``spmm.gat_aggregate(.., dropout=(p, seed))`` (gespmm_gat_backward_el_dropout_f32): ``g``
-    becomes ``edge_dropout``'s value of it, recomputed from the seed; ``w`` stays the undropped weight."""
+    becomes ``edge_dropout``'s value of it, recomputed from the seed; ``w`` stays the undropped weight.
+    Two forms, here and in ``gat_backward_er`` (``_lib.describe_gat_backward`` says which a call takes): where ``F % 4 == 0``,
+    ``16 <= F <= 512`` and ``grad_out`` and ``feat`` are 16-byte aligned, a lane GROUP computes ``g`` in ``csr_sddmm_heads``' order, and
+    ``grad_el`` / ``grad_er`` have the bits of the four-step composition on any operands; elsewhere one lane runs the ascending chain
+    above. ``GESPMM_GAT_BACKWARD_FORM=lane|group`` in the environment pins the form of an eligible call."""
     slope = _slope(negative_slope)
     _typed(torch.int32, rowptr=rowptr, colind=colind)
     _typed(torch.float32, el=el, er=er, stats=stats, grad_out=grad_out, feat=feat)

@@ -848,6 +848,24 @@ int gespmm_gat_backward_er_f32(const int32_t* colptr, const int32_t* rowind, con
                                const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K, int64_t H,
                                int64_t F, int64_t nnz, float slope, void* stream);
 /*
+ * The two forms of the fused backward (new symbol of 0.5). Both entry points above, and their dropout siblings below, run one of two
+ * kernels that differ in g_p alone. LANE form: the order stated above. GROUP form: W_d lanes share the dot, lane q running ONE chain
+ * acc = fmaf(a_j, b_j, acc) from +0 over j = 4 q + i + 4 W_d t (i ascending, t < 2), then the xor butterfly W_d / 2 .. 1, W_d the
+ * smallest power of two in 4 .. 64 with 8 W_d >= F — the order of gespmm_sddmm_csr_heads_f32 at (V, W) = (4, W_d). In the group form,
+ * on ANY operands, grad_el and grad_er have the bits of the composition named above (with gespmm_edge_dropout_f32 in it for the
+ * dropout siblings), and delta has them in the (row, head) pairs whose products alpha * grad_alpha are exact.
+ * A call is ELIGIBLE for the group form when F % 4 == 0, 16 <= F <= 512 and grad_out and feat are both 16-byte aligned. An eligible call
+ * takes it from a measured width F_min on ("nowhere" is a legal outcome), or where the environment variable
+ * GESPMM_GAT_BACKWARD_FORM=group, read per call, says so; =lane pins the lane form. Every other call runs the lane form.
+ * gespmm_describe_gat_backward (host only) prints what a call would launch, the pin included: "form=lane|group V=.. Wd=.. W=.. L=.."
+ * (lane form: V is the width of its loads, Wd = 1; W and L are gespmm_describe_edge_softmax's for the M rows, transposed == 1: for the
+ * K columns), or "form=none" where nothing is launched. *_align: the largest power of two (bytes, >= 4) that divides the operand's
+ * address. Checks: out == NULL, capacity <= 0, an alignment < 4, transposed not 0 / 1 -> GESPMM_EINVAL; then the size ladder above.
+ * Returns the length of the text (truncated to capacity - 1, as the other describe calls).
+ */
+int gespmm_describe_gat_backward(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int grad_out_align, int feat_align,
+                                 char* out, int64_t capacity);
+/*
  * Dropout on the attention coefficients with a mask that is never stored (new symbols of 0.5). Whether entry (r, c) of the pattern
  * keeps head h is a pure function of (seed, r, c, h), in uint32 arithmetic:
  *
