@@ -18,6 +18,8 @@ each node's edges (edge softmax, leaky ReLU fused in), the aggregation (multi-he
                                                                    # one kernel, the backward in two: no [nnz, H] array in a step
     python examples/gat_custom.py --dtype bf16                     # a .bfloat16() model on bf16 features (or fp16): the aggregation is the
                                                                    # 16-bit multi-head product, everything edge-sized stays fp32
+    python examples/gat_custom.py --fused-backward --dtype bf16 --attn-dropout 0.6 --graph-capture   # ``GATConv(fused_backward=True,
+                                                                   # fused_x16=True)``: the fused aggregation on 16-bit features
     python examples/gat_custom.py --v2 --dtype bf16                # ``GATv2Conv`` as a 16-bit model: the edge score and its two gradient
                                                                    # passes read bf16 (or fp16) node terms, att and the score stay fp32
     python examples/gat_custom.py --v2 --fused-attention --dtype bf16   # ``GATv2Conv(fused=True, fused_x16=True)``: the fused attention on
@@ -68,7 +70,9 @@ class Net(torch.nn.Module):
             self.conv1 = GATv2Conv(n_in, n_hidden, heads=heads, concat=True, dropout=attn_dropout, **fused)
             self.conv2 = GATv2Conv(n_hidden * heads, n_out, heads=1, concat=False, dropout=attn_dropout, **fused)
         else:
-            fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward, dropout=attn_dropout)
+            # (fused_x16: a 16-bit model runs the fused aggregation on 16-bit features; an fp32 one ignores the flag)
+            fused = dict(fused_score=fused_score, fused_aggregate=fused_aggregate, fused_backward=fused_backward, dropout=attn_dropout,
+                         fused_x16=fused_aggregate or fused_backward)
             self.conv1 = GATConv(n_in, n_hidden, heads=heads, concat=True, **fused)
             self.conv2 = GATConv(n_hidden * heads, n_out, heads=1, concat=False, **fused)
         self.dropout = dropout
@@ -107,12 +111,9 @@ def main():
                          "then print the same losses")
     ap.add_argument("--dtype", choices=("fp32", "bf16", "fp16"), default="fp32",
                     help="cast the model and the features (bf16 / fp16: GATConv on the 16-bit multi-head product, with --v2 GATv2Conv "
-                         "on the 16-bit edge score too, with --v2 --fused-attention the fused attention on 16-bit node terms; not "
-                         "with --fused-aggregate or --fused-backward, which are fp32 only)")
+                         "on the 16-bit edge score too, with --v2 --fused-attention the fused attention on 16-bit node terms, with "
+                         "--fused-aggregate / --fused-backward GATConv(.., fused_x16=True): the fused aggregation on 16-bit features)")
     args = ap.parse_args()
-    if args.dtype != "fp32" and (args.fused_aggregate or args.fused_backward or (args.fused_attention and not args.v2)):
-        ap.error("--dtype %s: --fused-aggregate and --fused-backward run fp32-only kernels; use the default path, --fused-score, --v2 "
-                 "or --v2 --fused-attention" % args.dtype)
     if args.v2 and (args.fused_score or args.fused_aggregate or args.fused_backward):
         ap.error("--fused-score, --fused-aggregate and --fused-backward are GATConv's: --v2 has --fused-attention")
     if args.fused_attention and not args.v2:

@@ -125,6 +125,9 @@ EXPORTS = [
     "gespmm_gat_backward_er_f32",
     "gespmm_edge_dropout_f32",
     "gespmm_gat_aggregate_dropout_f32",
+    "gespmm_gat_aggregate_x16",
+    "gespmm_gat_aggregate_dropout_x16",
+    "gespmm_gat_aggregate_x16_route",
     "gespmm_gat_backward_el_dropout_f32",
     "gespmm_gat_backward_er_dropout_f32",
     "gespmm_edge_dropout_bits",
@@ -392,6 +395,12 @@ def _load():
     lib.gespmm_edge_dropout_f32.argtypes = [p, p, p, p, c_int64, c_int64, c_int64, c_int64, c_float, p, p]
     lib.gespmm_gat_aggregate_dropout_f32.restype = c_int
     lib.gespmm_gat_aggregate_dropout_f32.argtypes = lib.gespmm_gat_aggregate_f32.argtypes[:-1] + [c_float, p, p]
+    lib.gespmm_gat_aggregate_x16.restype = c_int
+    lib.gespmm_gat_aggregate_x16.argtypes = [p, p, p, p, p, p, p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_int, p]
+    lib.gespmm_gat_aggregate_dropout_x16.restype = c_int
+    lib.gespmm_gat_aggregate_dropout_x16.argtypes = lib.gespmm_gat_aggregate_x16.argtypes[:-1] + [c_float, p, p]
+    lib.gespmm_gat_aggregate_x16_route.restype = c_int
+    lib.gespmm_gat_aggregate_x16_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     for f in (lib.gespmm_gat_backward_el_dropout_f32, lib.gespmm_gat_backward_er_dropout_f32):
         f.restype = c_int
         f.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, c_float, p, p]
@@ -728,6 +737,17 @@ def gat_aggregate_route(M, K, H, F, nnz, transposed=False, b_align=16, c_align=1
     rc = lib.gespmm_gat_aggregate_route(int(M), int(K), int(H), int(F), int(nnz), 1 if transposed else 0, int(b_align), int(c_align), geo)
     if rc < 0:
         raise GespmmError(rc, "gespmm_gat_aggregate_route")
+    return rc, tuple(int(x) for x in geo)
+
+
+def gat_aggregate_x16_route(M, K, H, F, nnz, transposed=False, b_align=16, c_align=16):
+    """What gespmm_gat_aggregate_x16 would do for these sizes and operand alignments (gespmm_gat_aggregate_x16_route: host only):
+    ``(route, (V, S, W, rpw))`` — route 1 the one 16-bit kernel with that lane geometry in 32-bit words (V words per lane and strip,
+    V | F / 2), route 0 the composition widen / fp32 / narrow (zeros)."""
+    geo = (ctypes.c_int32 * 4)()
+    rc = lib.gespmm_gat_aggregate_x16_route(int(M), int(K), int(H), int(F), int(nnz), 1 if transposed else 0, int(b_align), int(c_align), geo)
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_gat_aggregate_x16_route")
     return rc, tuple(int(x) for x in geo)
 
 

@@ -395,6 +395,37 @@ int run_gat_aggregate(const CsrView& A, const GatTerms& t, const float* B, float
     return (int)launch_gat_aggregate(a, r.sel.geo, transposed, drop, reinterpret_cast<hipStream_t>(stream));
 }
 
+// ... and on 16-bit B and C (gespmm_gat_aggregate_x16): ONE 16-bit kernel or nothing (kHeadsUnavailable: the caller composes widen, the
+// fp32 entry, narrow). The kernel works in 32-bit words, so the geometry is run_gat_aggregate's for H heads of F / 2 WORDS: the width
+// H F / 2, V limited to what divides F / 2 and to what B and C can be addressed with. The same pin; the stream is never asked.
+int run_gat_aggregate_x16(const CsrView& A, const GatTerms& t, const void* B, void* C, int dtype, int64_t H, int64_t F, bool transposed,
+                          void* stream, int b_align, int c_align, bool dry_run, int* kind, Geometry* geo_out, const EdgeDropout* drop = nullptr) {
+    *kind = 0;
+    if (H < 1 || H > kHeadsMax || A.M <= 0 || F <= 0 || F % 2 != 0 || A.nnz < 0 || b_align < 4 || c_align < 4) return kHeadsUnavailable;
+    if (const char* env = getenv("GESPMM_GAT_AGGREGATE_ROUTE"))
+        if (!strcmp(env, "composition")) return kHeadsUnavailable;
+    const int64_t Fw = F / 2, Nw = H * Fw;  // words per head, words per row
+    if ((uint64_t)A.K * (uint64_t)Nw * 4ull >= (1ull << 32) || A.nnz * H >= (1ll << 31)) return kHeadsUnavailable;  // 32-bit offsets only
+    const int flags = kFlagBatchStream | kFlagStrictOrder | kFlagNoSlabBlocked;
+    const StreamQuery q = {A.M, A.K, Nw, A.nnz, vec_limit(Fw, std::min(b_align, c_align)), A.variant, flags, kReduceSum, nullptr, nullptr, false, nullptr};
+    StreamLaunch r;
+    const int rc = resolve_stream_launch(q, &r);
+    if (rc != 0) return rc == kNotStreaming ? kHeadsUnavailable : GESPMM_EINVAL;
+    if (!heads_geometry_served(r.sel.geo, false)) return kHeadsUnavailable;
+    *kind = 1;
+    if (geo_out) *geo_out = r.sel.geo;
+    if (dry_run) return 0;
+    // (arrays of words: gat_aggregate.h)
+    GatAggregateArgs a = stream_args<GatAggregateArgs>(A, static_cast<const float*>(B), static_cast<float*>(C), Nw, r);
+    a.H = (int32_t)H;
+    a.F = (int32_t)Fw;
+    a.el = t.el;
+    a.er = t.er;
+    a.stats = t.stats;
+    a.slope = t.slope;
+    return (int)launch_gat_aggregate_x16(a, dtype, r.sel.geo, transposed, drop, reinterpret_cast<hipStream_t>(stream));
+}
+
 // gespmm_gat_aggregate_f32 / gespmm_gat_aggregate_route: the ladder of gespmm_gat_softmax_f32 on (M, K, H, nnz), then the multi-head
 // product's on the width (segments x rows of B: M x K, transposed K x M)
 int check_gat_aggregate_sizes(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, bool transposed) {
@@ -1430,6 +1461,57 @@ int gespmm_gat_aggregate_dropout_f32(const int32_t* ptr, const int32_t* ind, con
     return gat_aggregate_entry(ptr, ind, el, er, stats, B, C, M, K, H, F, nnz, slope, transposed, &p, seed, stream);
 }
 
+/* ... on 16-bit features (gespmm.h): the 16-bit kernel where it exists, else the composition — widen B into a stream-ordered temporary,
+   the fp32 entry above unchanged into a second one, narrow into C. Same bits: widening is exact and either way each fp32 chain is
+   rounded once. */
+static int gat_aggregate_x16_entry(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const void* B,
+                                   void* C, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed,
+                                   const float* p, const void* seed, void* stream) {
+    if (!valid_x16_dtype(dtype) || (transposed != 0 && transposed != 1)) return GESPMM_EINVAL;
+    int rc = gespmm::check_gat_aggregate_sizes(M, K, H, F, nnz, slope, transposed != 0);
+    if (p) rc = gespmm::check_dropout_p(rc, *p);
+    if (rc != 0) return rc;
+    const int64_t S = transposed ? K : M, Kb = transposed ? M : K;  // segments, rows of B
+    if (S == 0 || F == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (nnz == 0) {  // C = 0: all-zero bits are +0 in both types
+        if (const int rcp = check_pointers({{C, 2, true}, {seed, 4, p != nullptr}})) return rcp;
+        return (int)hipMemsetAsync(C, 0, (size_t)S * (size_t)H * (size_t)F * 2, st);
+    }
+    rc = check_pointers({{ptr, 4, true}, {ind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true}, {B, 2, true}, {C, 2, true},
+                         {seed, 4, p != nullptr}});
+    if (rc != 0) return rc;
+    const gespmm::GatTerms terms = {el, er, stats, slope};
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    int kind = 0;
+    rc = gespmm::run_gat_aggregate_x16(csr_view(ptr, ind, nullptr, S, Kb, nnz, GESPMM_VARIANT_AUTO), terms, B, C, dtype, H, F, transposed != 0,
+                                       stream, pointer_alignment(B), pointer_alignment(C), false, &kind, nullptr, p ? &dropout : nullptr);
+    if (rc != kHeadsUnavailable) return rc;
+    const int64_t N = H * F;
+    const size_t b_bytes = (size_t)Kb * (size_t)N * 4, c_bytes = (size_t)S * (size_t)N * 4;
+    PooledScratch scratch;
+    if ((rc = scratch.open(PooledScratch::slice(b_bytes) + c_bytes, st)) != 0) return rc;  // (nothing launched)
+    float* Bf = scratch.take(b_bytes);
+    float* Cf = scratch.take(c_bytes);
+    rc = (int)launch_widen_x16(B, Bf, dtype, Kb * N, st);
+    if (rc == 0) rc = gat_aggregate_entry(ptr, ind, el, er, stats, Bf, Cf, M, K, H, F, nnz, slope, transposed, p, seed, stream);
+    if (rc == 0) rc = (int)launch_narrow_x16(Cf, C, dtype, S * N, st);
+    return scratch.close(rc);
+}
+
+int gespmm_gat_aggregate_x16(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const void* B,
+                             void* C, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed,
+                             void* stream) {
+    return gat_aggregate_x16_entry(ptr, ind, el, er, stats, B, C, dtype, M, K, H, F, nnz, slope, transposed, nullptr, nullptr, stream);
+}
+
+int gespmm_gat_aggregate_dropout_x16(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats,
+                                     const void* B, void* C, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                     float slope, int transposed, float p, const void* seed, void* stream) {
+    return gat_aggregate_x16_entry(ptr, ind, el, er, stats, B, C, dtype, M, K, H, F, nnz, slope, transposed, &p, seed, stream);
+}
+
 /* Dropout on an [nnz, H] array of the pattern (gespmm.h; edge_dropout.h): the softmax's ladder on (M, K, H, nnz) with p in the slope's
    place, then the pointers. */
 int gespmm_edge_dropout_f32(const int32_t* rowptr, const int32_t* colind, const float* x, float* y, int64_t M, int64_t K, int64_t H,
@@ -1571,6 +1653,27 @@ int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64
     const gespmm::GatTerms none = {nullptr, nullptr, nullptr, 1.0f};
     const int rc = gespmm::run_gat_aggregate(csr_view(nullptr, nullptr, nullptr, S, Kb, nnz, GESPMM_VARIANT_AUTO), none, nullptr, nullptr, H, F,
                                              transposed != 0, nullptr, b_align, c_align, true, &kind, &geo);
+    const int route = route_result(rc == kHeadsUnavailable ? 0 : rc, kind);
+    if (route >= 0 && geometry_out) {
+        geometry_out[0] = kind ? geo.vec : 0;
+        geometry_out[1] = kind ? geo.strips : 0;
+        geometry_out[2] = kind ? geo.group : 0;
+        geometry_out[3] = kind ? geo.rows_per_wave : 0;
+    }
+    return route;
+}
+
+int gespmm_gat_aggregate_x16_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,
+                                   int32_t* geometry_out) {
+    if (b_align < 1 || c_align < 1 || (transposed != 0 && transposed != 1)) return GESPMM_EINVAL;
+    const int rc0 = gespmm::check_gat_aggregate_sizes(M, K, H, F, nnz, 1.0f, transposed != 0);
+    if (rc0 != 0) return rc0;
+    const int64_t S = transposed ? K : M, Kb = transposed ? M : K;
+    int kind = 0;
+    Geometry geo = {};
+    const gespmm::GatTerms none = {nullptr, nullptr, nullptr, 1.0f};
+    const int rc = gespmm::run_gat_aggregate_x16(csr_view(nullptr, nullptr, nullptr, S, Kb, nnz, GESPMM_VARIANT_AUTO), none, nullptr, nullptr,
+                                                 GESPMM_X16_BF16, H, F, transposed != 0, nullptr, b_align, c_align, true, &kind, &geo);
     const int route = route_result(rc == kHeadsUnavailable ? 0 : rc, kind);
     if (route >= 0 && geometry_out) {
         geometry_out[0] = kind ? geo.vec : 0;

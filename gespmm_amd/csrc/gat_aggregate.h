@@ -45,6 +45,10 @@ struct EdgeDropout;  // edge_dropout.h
 // One kernel: the geometries heads_geometry_served serves without a plan, 32-bit offsets. hipErrorInvalidValue otherwise.
 // drop != nullptr: the staged weight is dropout(weight(r, c, h)) with edge_dropout.h's mask — the same (r, c) in both modes.
 hipError_t launch_gat_aggregate(const GatAggregateArgs& a, const Geometry& geo, bool transposed, const EdgeDropout* drop, hipStream_t st);
+// gat_aggregate_x16.hip: B and C fp16 / bf16 (dtype kX16F16 / kX16Bf16), `a` in 32-bit WORDS as launch_spmm_heads_x16 takes it: a.B / a.C
+// the 16-bit arrays, a.N = H F / 2, a.F = F / 2, the geometry resolved for that width; el, er, stats as above.
+hipError_t launch_gat_aggregate_x16(const GatAggregateArgs& a, int dtype, const Geometry& geo, bool transposed, const EdgeDropout* drop,
+                                    hipStream_t st);
 // The composition's first step: w[p H + h] = weight(..) of entry p in the order of (ptr, ind), S segments. nnz H < 2^31.
 hipError_t launch_gat_weights(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, float* w,
                               int64_t S, int64_t H, int64_t nnz, float slope, bool transposed, hipStream_t st);

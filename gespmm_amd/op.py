@@ -52,7 +52,9 @@ models and under ``torch.autocast``, and so does ``GATv2Conv(fused=False)``, who
 fused in (``softmax.edge_softmax`` and its backward kernel) — and ``GATConv`` the graph attention layer composed from the three.
 ``GATSoftmaxFunction`` is the first two in one: the softmax of el[row] + er[col] with no score array (``GATConv(fused_score=True)``).
 ``EdgeDropoutFunction`` is dropout on alpha with a mask recomputed from (seed, row, column, head), never stored (``GATConv(dropout=p)``).
-``GATAggregateFunction`` is all three in one: no score and no attention array, nothing of size nnz x H saved (``GATConv(fused_aggregate=True)``).
+``GATAggregateFunction`` is all three in one: no score and no attention array, nothing of size nnz x H saved (``GATConv(fused_aggregate=True)``)
+— and on fp16 / bf16 features (``spmm.gat_aggregate_x16`` forward and for the feature gradient; with ``fused_backward`` the two attention
+gradients compose the fp32 kernels on widened node tensors), behind ``GATConv(fused_aggregate=True, fused_x16=True)``.
 GraphSAGE (extension): ``SpmmMaxFunction`` is the max over neighbours with a gradient — the forward saves the winning CSR position of
 every output word (``spmm.csr_spmm_max_arg``), the backward adds ``grad_out`` where that position sits (``spmm.csr_spmm_max_backward``) —
 and ``SAGEConv`` DGL's layer of that name with the ``mean``, ``gcn`` and ``pool`` aggregators. Both take fp16 / bf16 features
@@ -113,6 +115,20 @@ def _heads_x16_product(rowptr, colind, values, dense):
         if _lib.heads_x16_route(M, K, H, F, nnz)[0] != 1:
             return _spmm.csr_spmm_heads(rowptr, colind, values, dense.float()).to(dense.dtype)
     return _spmm.csr_spmm_heads_x16(rowptr, colind, values, dense)
+
+
+def _gat_aggregate_x16(ptr, ind, el, er, stats, dense, negative_slope, transposed, dropout):
+    """``spmm.gat_aggregate_x16`` for ``GATAggregateFunction``. Where that op has no kernel (``_lib.gat_aggregate_x16_route`` answers 0:
+    odd F — the last layer of a model with an odd number of classes — or H > 8) it composes widen / fp32 entry / narrow through a
+    stream-ordered temporary, which it refuses on a capturing stream. There — and only there — the same composition is made of torch's
+    allocations, which a capture may hold: ``gat_aggregate(.., dense.float()).to(dense.dtype)``, the bits the op documents."""
+    if dense.is_cuda and torch.cuda.is_current_stream_capturing():
+        M, K, H = el.shape[0], er.shape[0], el.shape[1]
+        F = math.prod(dense.shape[1:]) // max(H, 1)
+        if _lib.gat_aggregate_x16_route(M, K, H, F, ind.numel(), transposed)[0] != 1:
+            return _spmm.gat_aggregate(ptr, ind, el, er, stats, dense.float(), negative_slope=negative_slope, transposed=transposed,
+                                       dropout=dropout).to(dense.dtype)
+    return _spmm.gat_aggregate_x16(ptr, ind, el, er, stats, dense, negative_slope=negative_slope, transposed=transposed, dropout=dropout)
 
 
 def _is_x16(t):
@@ -458,7 +474,16 @@ class GATAggregateFunction(torch.autograd.Function):
     above would apply it, with the mask recomputed wherever an entry is seen — in the aggregation, in its transposed form for
     grad_feat and in both backward passes (``dropout=(p, seed)`` of those calls; the default backward applies ``softmax.edge_dropout``
     to its transient grad_alpha). The two seed words are the only thing saved on top; with ``dropout_p == 0`` the launches are exactly
-    those above."""
+    those above.
+
+    16-bit ``feat`` (fp16 or bf16; ``el``, ``er``, the statistics and every gradient of theirs stay fp32): the forward is
+    ``gat_softmax_stats`` unchanged, then ``spmm.gat_aggregate_x16``; grad_feat is ``spmm.gat_aggregate_x16(colptr, rowind, ..,
+    grad_out, transposed=True)``, 16-bit; the default backward takes grad_alpha from ``sddmm.csr_sddmm_heads_x16``. With
+    ``fused_backward=True`` grad_el / grad_er are a COMPOSITION: ``grad_out`` and ``feat`` are widened (``.float()``: exact, two
+    node-sized transients) and go through the unchanged fp32 ``softmax.gat_backward_el`` / ``gat_backward_er`` — there are no 16-bit
+    forms of those two kernels yet; still nothing of size nnz H is allocated. Inside a stream capture, where ``spmm.gat_aggregate_x16``
+    has no kernel (odd F, H > 8), its composition is made of torch's allocations (``_gat_aggregate_x16``): the same bits. Saved: ``el``, ``er``, the 16-bit ``feat``, the
+    statistics and the seed. ``grad_out`` must have ``feat``'s dtype (TypeError otherwise)."""
 
     @staticmethod
     def forward(ctx, rowptr, colind, colptr, rowind, csc_order, el, er, feat, negative_slope=None, fused_backward=False, dropout_p=0.0,
@@ -469,8 +494,12 @@ class GATAggregateFunction(torch.autograd.Function):
             raise ValueError("dropout_p needs a seed (an int32[2] device tensor)")
         ctx.dropout_p = dropout_p
         drop = (dropout_p, seed) if dropout_p != 0.0 else None
+        x16 = feat_c.dtype in (torch.float16, torch.bfloat16)  # (el, er stay fp32: spmm.gat_aggregate_x16 says so otherwise)
         stats = _softmax.gat_softmax_stats(rowptr, colind, el_c, er_c, negative_slope=negative_slope)
-        out = _spmm.gat_aggregate(rowptr, colind, el_c, er_c, stats, feat_c, negative_slope=negative_slope, dropout=drop)
+        if x16:
+            out = _gat_aggregate_x16(rowptr, colind, el_c, er_c, stats, feat_c, negative_slope, False, drop)
+        else:
+            out = _spmm.gat_aggregate(rowptr, colind, el_c, er_c, stats, feat_c, negative_slope=negative_slope, dropout=drop)
         order = None
         if not fused_backward:
             order = (csc_order if csc_order.dtype == torch.int32 else csc_order.to(torch.int32)).contiguous()
@@ -489,17 +518,23 @@ class GATAggregateFunction(torch.autograd.Function):
         drop = (ctx.dropout_p, ctx.saved_tensors[4]) if ctx.dropout_p != 0.0 else None
         slope = ctx.negative_slope
         grad_out = grad_out.contiguous()
+        x16 = feat.dtype in (torch.float16, torch.bfloat16)
+        if grad_out.dtype != feat.dtype:
+            raise TypeError("grad_out is %s and feat %s: one dtype per call" % (grad_out.dtype, feat.dtype))
         grad_el = grad_er = grad_feat = None
         if ctx.fused_backward and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):  # node-sized tensors only
-            delta, grad_el = _softmax.gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=slope, dropout=drop)
+            # (16-bit: a composition — the two operands widened, exactly, into node-sized transients for the fp32 kernels)
+            go32, feat32 = (grad_out.float(), feat.float()) if x16 else (grad_out, feat)
+            delta, grad_el = _softmax.gat_backward_el(rowptr, colind, el, er, stats, go32, feat32, negative_slope=slope, dropout=drop)
             if ctx.needs_input_grad[6]:
-                grad_er = _softmax.gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=slope,
+                grad_er = _softmax.gat_backward_er(colptr, rowind, el, er, stats, delta, go32, feat32, negative_slope=slope,
                                                    dropout=drop)
+            del go32, feat32
             if not ctx.needs_input_grad[5]:
                 grad_el = None
         elif ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:  # (first: its three edge-sized temporaries are gone before grad_feat exists)
             alpha = _softmax.gat_edge_softmax(rowptr, colind, el, er, negative_slope=slope)
-            grad_alpha = _sddmm.csr_sddmm_heads(rowptr, colind, grad_out, feat)
+            grad_alpha = (_sddmm.csr_sddmm_heads_x16 if x16 else _sddmm.csr_sddmm_heads)(rowptr, colind, grad_out, feat)
             if drop is not None:  # the gradient of the undropped alpha, in place
                 _softmax.edge_dropout(rowptr, colind, grad_alpha, drop[0], drop[1], out=grad_alpha)
             grad_score, grad_el = _softmax.gat_edge_softmax_backward(rowptr, colind, alpha, grad_alpha, el=el if slope is not None else None,
@@ -511,7 +546,10 @@ class GATAggregateFunction(torch.autograd.Function):
             if not ctx.needs_input_grad[5]:
                 grad_el = None
         if ctx.needs_input_grad[7]:
-            grad_feat = _spmm.gat_aggregate(colptr, rowind, el, er, stats, grad_out, negative_slope=slope, transposed=True, dropout=drop)
+            if x16:
+                grad_feat = _gat_aggregate_x16(colptr, rowind, el, er, stats, grad_out, slope, True, drop)
+            else:
+                grad_feat = _spmm.gat_aggregate(colptr, rowind, el, er, stats, grad_out, negative_slope=slope, transposed=True, dropout=drop)
         return None, None, None, None, None, grad_el, grad_er, grad_feat, None, None, None, None
 
 
@@ -636,7 +674,7 @@ class GATConv(torch.nn.Module):
     and its backward hands grad_el and grad_er back as component 0 of grad_q and component 1 of grad_k.
 
         GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
-                fused_aggregate=False, fused_backward=False, dropout=0.0)
+                fused_aggregate=False, fused_backward=False, dropout=0.0, fused_x16=False)
         forward(x, rowptr, colind, colptr, rowind, csc_order, attn_seed=None)
 
     ``fused_score=True``: the score and the softmax are ONE ``GATSoftmaxFunction`` — el + er is added inside the softmax kernel, no
@@ -666,10 +704,16 @@ class GATConv(torch.nn.Module):
     16-bit features (a ``.half()`` / ``.bfloat16()`` layer, or ``torch.autocast``), default and ``fused_score=True`` paths: ``xw`` stays
     16-bit, ``el`` and ``er`` — node-sized — are computed by torch from it and widened (``.float()``), score, softmax and dropout are the
     unchanged fp32 ops, the aggregation is the 16-bit product (``MultiHeadSPMMFunction`` on ``spmm.csr_spmm_heads_x16``: fp32 sums, one
-    rounding) and the bias add is torch's. ``fused_aggregate`` / ``fused_backward`` are fp32 only: 16-bit features raise TypeError."""
+    rounding) and the bias add is torch's. ``fused_aggregate`` / ``fused_backward`` take 16-bit features only with ``fused_x16=True``
+    (a ValueError without one of the two): ``GATAggregateFunction`` on the 16-bit ``xw`` — ``spmm.gat_aggregate_x16`` forward and,
+    transposed, for the feature gradient, ``dropout=`` included; output and all gradients of ``fused_aggregate`` have the bits of the
+    16-bit ``fused_score=True`` layer. With ``fused_backward`` the two attention gradients are a composition: ``grad_out`` and ``xw`` are
+    widened into two node-sized fp32 transients for the fp32 ``softmax.gat_backward_el`` / ``gat_backward_er`` (no 16-bit forms of
+    those kernels exist yet); nothing of size ``[nnz, H]`` is allocated. Without the flag 16-bit features raise TypeError there; fp32
+    features ignore it."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,
-                 fused_aggregate=False, fused_backward=False, dropout=0.0):
+                 fused_aggregate=False, fused_backward=False, dropout=0.0, fused_x16=False):
         super().__init__()
         self.dropout = float(dropout)
         if not (0.0 <= self.dropout < 1.0):
@@ -677,6 +721,9 @@ class GATConv(torch.nn.Module):
         self.fused_backward = bool(fused_backward)
         self.fused_aggregate = bool(fused_aggregate) or self.fused_backward
         self.fused_score = bool(fused_score) or self.fused_aggregate
+        self.fused_x16 = bool(fused_x16)
+        if self.fused_x16 and not self.fused_aggregate:
+            raise ValueError("fused_x16=True needs fused_aggregate=True or fused_backward=True")
         if heads < 1:
             raise ValueError("heads must be at least 1")
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, int(heads)
@@ -706,7 +753,7 @@ class GATConv(torch.nn.Module):
         if rowptr.numel() != n + 1 or colptr.numel() != n + 1:
             raise ValueError("GATConv needs a square graph: rowptr and colptr must have x.size(0) + 1 entries")
         xw = (x @ self.weight).view(n, H, F)
-        if self.fused_aggregate and _is_x16(xw):
+        if self.fused_aggregate and _is_x16(xw) and not self.fused_x16:
             raise TypeError("GATConv(fused_aggregate=True / fused_backward=True) needs torch.float32 features, got %s: "
                             "spmm.gat_aggregate (GATAggregateFunction) is fp32 only" % xw.dtype)
         el = (xw * self.att_dst).sum(-1).float()  # (node-sized; fp32 features: the same tensor)

@@ -563,6 +563,20 @@ def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transpose
     scaled by 1 / (1 - p), or +0 — recomputed inside the kernel from ``seed`` (int32[2] on the device) and the entry's (row, column,
     head), which are the same in both modes: the bits of ``csr_spmm_heads`` on ``edge_dropout(gat_edge_softmax(..))``. ``stats`` stay
     those of the softmax without dropout."""
+    return _gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope, transposed, out, dropout, False)
+
+
+def gat_aggregate_x16(ptr, ind, el, er, stats, dense, negative_slope=None, transposed=False, out=None, dropout=None):
+    """``gat_aggregate`` on 16-bit features (gespmm_gat_aggregate_x16 / _dropout_x16): ``dense`` fp16 or bf16, [rows, H, F] or
+    [rows, H * F]; ``el``, ``er``, ``stats`` — and the weights computed from them — stay fp32; the result has the dtype and rank of
+    ``dense``. Each output element is one fp32 fma chain in strict entry order, rounded once at the store: the bits of
+    ``gat_aggregate(.., dense.float()).to(dense.dtype)``, forward, transposed and with ``dropout=(p, seed)``. One kernel, capturable
+    and allocation-free, for H <= 8, even F and 4-byte aligned operands (``_lib.gat_aggregate_x16_route``); the composition widen /
+    fp32 / narrow through pooled temporaries otherwise (not on a capturing stream). Argument checks are ``gat_aggregate``'s."""
+    return _gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope, transposed, out, dropout, True)
+
+
+def _gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope, transposed, out, dropout, x16):
     from . import softmax as _sm  # (softmax imports this module)
 
     slope = _sm._slope(negative_slope)
@@ -578,8 +592,12 @@ def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transpose
     _sm._stats_array(stats, "stats", M, H, dev)
     if not isinstance(dense, torch.Tensor):
         raise TypeError("dense must be a torch.Tensor")
-    if dense.dtype != torch.float32:
+    if x16 and dense.dtype not in _X16:
+        raise TypeError("dense must have dtype torch.float16 or torch.bfloat16, got %s (fp32: gat_aggregate)" % dense.dtype)
+    if not x16 and dense.dtype != torch.float32:
         raise TypeError("dense must have dtype torch.float32, got %s" % dense.dtype)
+    dt = dense.dtype
+    tag = str(dt).replace("torch.", "") if x16 else "f32"
     if dense.dim() not in (2, 3) or dense.shape[0] != Kb:
         raise ValueError("dense must be [%d, H, F] or [%d, H * F]" % (Kb, Kb))
     N = dense.shape[1] * dense.shape[2] if dense.dim() == 3 else dense.shape[1]
@@ -590,16 +608,29 @@ def gat_aggregate(ptr, ind, el, er, stats, dense, negative_slope=None, transpose
     F = N // H
     shape = (S, H, F) if dense.dim() == 3 else (S, N)
     if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        out = torch.empty(shape, dtype=dt, device=dev)
     else:
         if not isinstance(out, torch.Tensor):
             raise TypeError("out must be a torch.Tensor")
-        if out.dtype != torch.float32:
-            raise TypeError("out must have dtype torch.float32, got %s" % out.dtype)
+        if out.dtype != dt:
+            raise TypeError("out must have dtype %s, got %s" % (dt, out.dtype))
         if tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
-            raise ValueError("out must be contiguous f32%s on %s" % (list(shape), dev))
+            raise ValueError("out must be contiguous %s%s on %s" % (tag, list(shape), dev))
         if any(_overlaps(out, t) for t in (el, er, stats, dense)):
             raise ValueError("out must not overlap an input")
+    if x16:
+        if dropout is not None:
+            p, seed = _sm._dropout(dropout, dev)
+            with _on_device(dev):
+                rc = lib.gespmm_gat_aggregate_dropout_x16(_ptr(ptr), _ptr(ind), _ptr(el), _ptr(er), _ptr(stats), _ptr(dense), _ptr(out), _X16[dt],
+                                                          M, K, H, F, ind.numel(), slope, 1 if transposed else 0, p, _ptr(seed), _stream(dev))
+            check(rc, "gespmm_gat_aggregate_dropout_x16")
+            return out
+        with _on_device(dev):
+            rc = lib.gespmm_gat_aggregate_x16(_ptr(ptr), _ptr(ind), _ptr(el), _ptr(er), _ptr(stats), _ptr(dense), _ptr(out), _X16[dt], M, K, H, F,
+                                              ind.numel(), slope, 1 if transposed else 0, _stream(dev))
+        check(rc, "gespmm_gat_aggregate_x16")
+        return out
     if dropout is not None:
         p, seed = _sm._dropout(dropout, dev)
         with _on_device(dev):

@@ -40,6 +40,8 @@
  *                               node-sized words, no [nnz x H] array either
  *   gespmm_edge_dropout_f32 / gespmm_gat_aggregate_dropout_f32 / gespmm_gat_backward_{el,er}_dropout_f32 / gespmm_edge_dropout_bits /
  *                               _threshold <- (new) dropout on the attention coefficients with a mask that is never stored
+ *   gespmm_gat_aggregate_x16 / gespmm_gat_aggregate_dropout_x16 / gespmm_gat_aggregate_x16_route <- (new) that aggregation on fp16 /
+ *                               bf16 features: fp32 weights and sums, one rounding at the store
  *   gespmm_baseline_copy_f32 <- (new) streaming-copy yardstick for the roofline record; no reference counterpart
  *
  * Conventions (all device entry points):
@@ -911,6 +913,33 @@ int gespmm_gat_backward_el_dropout_f32(const int32_t* rowptr, const int32_t* col
 int gespmm_gat_backward_er_dropout_f32(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
                                        const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
                                        int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream);
+/*
+ * The fused GAT aggregation on 16-bit features (new symbols of 0.5). B [rows x H F] and C [segments x H F] are IEEE fp16
+ * (GESPMM_X16_F16) or bfloat16 (GESPMM_X16_BF16), one type per call; el, er, stats and the weights stay fp32:
+ *
+ *     C[i, h F + f] = narrow( fmaf(w(r, c, h), widen(B[j, h F + f]), acc) over the segment's entries, ascending, from +0 )
+ *
+ * with w of gespmm_gat_aggregate_f32 (the dropout form: of gespmm_gat_aggregate_dropout_f32). widen is exact, narrow rounds each fp32
+ * sum once to nearest even (overflow gives +-inf, NaN stays NaN): the bits of narrow(gespmm_gat_aggregate_f32(.., widen(B))).
+ * nnz == 0 gives all-zero bits in C (hipMemsetAsync).
+ * Routes (gespmm_gat_aggregate_x16_route): 1 = ONE kernel that works in 32-bit words of two elements — 1 <= H <= 8, F even, B and C
+ * 4-byte aligned (8 / 16 bytes allow wider vectors), rows of B x H F x 2 < 2^32, nnz H < 2^31, a lane geometry of
+ * gespmm_heads_x16_route at the width H F / 2 words with V | F / 2; no workspace, no allocation: capturable. 0 = the composition:
+ * widen B into a stream-ordered temporary from the library's pool, gespmm_gat_aggregate_f32 / _dropout_f32 into a second one, narrow
+ * into C — the same bits; on a capturing stream it returns hipErrorStreamCaptureUnsupported (900) and launches nothing.
+ * GESPMM_GAT_AGGREGATE_ROUTE=composition pins route 0 here too.
+ * Checks: dtype not GESPMM_X16_F16 / _BF16 -> GESPMM_EINVAL; then the ladder of gespmm_gat_aggregate_f32 (_dropout_f32), with B and C
+ * 2-byte aligned (GESPMM_EALIGN otherwise). C must not overlap an input (not checked).
+ */
+int gespmm_gat_aggregate_x16(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats, const void* B,
+                             void* C, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, int transposed,
+                             void* stream);
+int gespmm_gat_aggregate_dropout_x16(const int32_t* ptr, const int32_t* ind, const float* el, const float* er, const float* stats,
+                                     const void* B, void* C, int dtype, int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz,
+                                     float slope, int transposed, float p, const void* seed, void* stream);
+/* Host only: the route of the two calls above, as gespmm_gat_aggregate_route; geometry_out is in words (V words per lane and strip). */
+int gespmm_gat_aggregate_x16_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,
+                                   int32_t* geometry_out);
 /* Host only: the mask's bits and the threshold T as the kernels compute them. gespmm_edge_dropout_threshold answers 0xffffffff for a p
  * outside [0, 1), which no legal p gives. */
 uint32_t gespmm_edge_dropout_bits(uint32_t s0, uint32_t s1, uint32_t r, uint32_t c, uint32_t h);
