@@ -130,6 +130,11 @@ EXPORTS = [
     "gespmm_gat_aggregate_x16_route",
     "gespmm_gat_backward_el_dropout_f32",
     "gespmm_gat_backward_er_dropout_f32",
+    "gespmm_gat_backward_el_x16",
+    "gespmm_gat_backward_er_x16",
+    "gespmm_gat_backward_el_dropout_x16",
+    "gespmm_gat_backward_er_dropout_x16",
+    "gespmm_describe_gat_backward_x16",
     "gespmm_edge_dropout_bits",
     "gespmm_edge_dropout_threshold",
     "gespmm_gatv2_score_f32",
@@ -404,6 +409,13 @@ def _load():
     for f in (lib.gespmm_gat_backward_el_dropout_f32, lib.gespmm_gat_backward_er_dropout_f32):
         f.restype = c_int
         f.argtypes = [p] * 9 + [c_int64] * 5 + [c_float, c_float, p, p]
+    for f in (lib.gespmm_gat_backward_el_x16, lib.gespmm_gat_backward_er_x16):
+        f.restype = c_int
+        f.argtypes = [p] * 7 + [c_int, p, p] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gat_backward_er_x16.argtypes = [p] * 8 + [c_int, p] + [c_int64] * 5 + [c_float, p]
+    lib.gespmm_gat_backward_el_dropout_x16.restype = lib.gespmm_gat_backward_er_dropout_x16.restype = c_int
+    lib.gespmm_gat_backward_el_dropout_x16.argtypes = lib.gespmm_gat_backward_el_x16.argtypes[:-1] + [c_float, p, p]
+    lib.gespmm_gat_backward_er_dropout_x16.argtypes = lib.gespmm_gat_backward_er_x16.argtypes[:-1] + [c_float, p, p]
     lib.gespmm_edge_dropout_bits.restype = ctypes.c_uint32
     lib.gespmm_edge_dropout_bits.argtypes = [ctypes.c_uint32] * 5
     lib.gespmm_edge_dropout_threshold.restype = ctypes.c_uint32
@@ -490,6 +502,8 @@ def _load():
     lib.gespmm_describe_edge_softmax.argtypes = [c_int64, c_int64, c_int64, c_char_p, c_int64]
     lib.gespmm_describe_gat_backward.restype = c_int
     lib.gespmm_describe_gat_backward.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_char_p, c_int64]
+    lib.gespmm_describe_gat_backward_x16.restype = c_int
+    lib.gespmm_describe_gat_backward_x16.argtypes = lib.gespmm_describe_gat_backward.argtypes
     lib.gespmm_plan_set_values.restype = c_int
     lib.gespmm_plan_set_values.argtypes = [p, p, p]
     lib.gespmm_plan_get_order.restype = c_int
@@ -593,18 +607,21 @@ def describe_edge_softmax(M, nnz, H):
     return {"W": int(w.split("=")[1]), "L": int(long_rows.split(">")[1])}
 
 
-def describe_gat_backward(M, K, H, F, nnz, transposed=False, aligns=(16, 16)):
+def describe_gat_backward(M, K, H, F, nnz, transposed=False, aligns=(16, 16), x16=False):
     """What gespmm_gat_backward_el_f32 (transposed=True: gespmm_gat_backward_er_f32) and their dropout siblings would launch for these
     sizes and the alignments of (``grad_out``, ``feat``) — the function the entry points route through, the pin
     GESPMM_GAT_BACKWARD_FORM=lane|group included (gespmm_describe_gat_backward: host only). A dict ``{"form": "lane" | "group", "V":
     floats per load, "Wd": lanes that share a dot (lane form: 1), "W": lanes per (segment, head) pair, "L": longer segments take a whole
     wavefront}``; ``{"form": "none"}`` where nothing is launched. In the group form (V, Wd) fix the bits of the dot: those of the
-    multi-head SDDMM at that (V, W)."""
+    multi-head SDDMM at that (V, W). ``x16=True``: the fp16 / bf16 entries (gespmm_describe_gat_backward_x16) — V counts ELEMENTS (lane
+    form: 8 / 4 / 2 / 1, no bit depends on it), alignments from 2, the group form eligible from 8-byte alignment, and "rpw" (segments per
+    wavefront) is part of the answer."""
     buf = ctypes.create_string_buffer(96)
-    n = lib.gespmm_describe_gat_backward(int(M), int(K), int(H), int(F), int(nnz), 1 if transposed else 0, int(aligns[0]), int(aligns[1]),
-                                         buf, 96)
+    f, name = (lib.gespmm_describe_gat_backward_x16, "gespmm_describe_gat_backward_x16") if x16 else \
+        (lib.gespmm_describe_gat_backward, "gespmm_describe_gat_backward")
+    n = f(int(M), int(K), int(H), int(F), int(nnz), 1 if transposed else 0, int(aligns[0]), int(aligns[1]), buf, 96)
     if n < 0:
-        raise GespmmError(n, "gespmm_describe_gat_backward")
+        raise GespmmError(n, name)
     out = dict(kv.split("=") for kv in buf.value.decode().split())
     return {k: (v if k == "form" else int(v)) for k, v in out.items()}
 

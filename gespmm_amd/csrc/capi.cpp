@@ -1642,6 +1642,103 @@ int gespmm_describe_gat_backward(int64_t M, int64_t K, int64_t H, int64_t F, int
     return describe_result(n, capacity);
 }
 
+/* ... on 16-bit grad_out and feat (gespmm.h; gat_backward.h): the dtype, then the fp32 ladder with 2-byte alignment for the two 16-bit
+   operands, then the form resolve_gat_backward_x16 answers under the same pin. nnz == 0 is the fp32 entry's zero fill. */
+static int gat_backward_el_x16_entry(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                     const void* grad_out, const void* feat, int dtype, float* delta, float* grad_el, int64_t M, int64_t K,
+                                     int64_t H, int64_t F, int64_t nnz, float slope, const float* p, const void* seed, void* stream) {
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    if (nnz == 0 || F == 0 || M == 0)  // (no 16-bit word is looked at)
+        return gat_backward_el_entry(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, delta, grad_el, M, K, H, F, nnz, slope, p, seed,
+                                     stream);
+    int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
+    if (p) rc = gespmm::check_dropout_p(rc, *p);
+    if (rc != 0) return rc;
+    if (const int rcp = check_pointers({{rowptr, 4, true}, {colind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true},
+                                        {grad_out, 2, true}, {feat, 2, true}, {delta, 4, true}, {grad_el, 4, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const gespmm::GatBackwardLaunch b =
+        gespmm::resolve_gat_backward_x16(M, nnz, H, F, pointer_alignment(grad_out), pointer_alignment(feat), gat_backward_pin());
+    if (b.form == gespmm::kGatBackwardGroup)
+        return (int)gespmm::launch_gat_backward_group_el_x16(rowptr, colind, el, er, stats, grad_out, feat, dtype, delta, grad_el, M, K, H, F, nnz,
+                                                             slope, b, p ? &dropout : nullptr, st);
+    return (int)gespmm::launch_gat_backward_el_x16(rowptr, colind, el, er, stats, grad_out, feat, dtype, delta, grad_el, M, K, H, F, nnz, slope, b,
+                                                   p ? &dropout : nullptr, st);
+}
+
+static int gat_backward_er_x16_entry(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                     const float* delta, const void* grad_out, const void* feat, int dtype, float* grad_er, int64_t M, int64_t K,
+                                     int64_t H, int64_t F, int64_t nnz, float slope, const float* p, const void* seed, void* stream) {
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    if (nnz == 0 || F == 0)
+        return gat_backward_er_entry(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, grad_er, M, K, H, F, nnz, slope, p, seed,
+                                     stream);
+    int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, slope);
+    if (p) rc = gespmm::check_dropout_p(rc, *p);
+    if (rc != 0) return rc;
+    if (const int rcp = check_pointers({{colptr, 4, true}, {rowind, 4, true}, {el, 4, true}, {er, 4, true}, {stats, 8, true},
+                                        {delta, 4, true}, {grad_out, 2, true}, {feat, 2, true}, {grad_er, 4, true}, {seed, 4, p != nullptr}}))
+        return rcp;
+    gespmm::EdgeDropout dropout = {};
+    if (p) dropout = gespmm::make_edge_dropout(*p, seed);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const gespmm::GatBackwardLaunch b =
+        gespmm::resolve_gat_backward_x16(K, nnz, H, F, pointer_alignment(grad_out), pointer_alignment(feat), gat_backward_pin());
+    if (b.form == gespmm::kGatBackwardGroup)
+        return (int)gespmm::launch_gat_backward_group_er_x16(colptr, rowind, el, er, stats, delta, grad_out, feat, dtype, grad_er, M, K, H, F, nnz,
+                                                             slope, b, p ? &dropout : nullptr, st);
+    return (int)gespmm::launch_gat_backward_er_x16(colptr, rowind, el, er, stats, delta, grad_out, feat, dtype, grad_er, M, K, H, F, nnz, slope, b,
+                                                   p ? &dropout : nullptr, st);
+}
+
+int gespmm_gat_backward_el_x16(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                               const void* grad_out, const void* feat, int dtype, float* delta, float* grad_el, int64_t M, int64_t K,
+                               int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    return gat_backward_el_x16_entry(rowptr, colind, el, er, stats, grad_out, feat, dtype, delta, grad_el, M, K, H, F, nnz, slope, nullptr, nullptr,
+                                     stream);
+}
+
+int gespmm_gat_backward_er_x16(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                               const float* delta, const void* grad_out, const void* feat, int dtype, float* grad_er, int64_t M, int64_t K,
+                               int64_t H, int64_t F, int64_t nnz, float slope, void* stream) {
+    return gat_backward_er_x16_entry(colptr, rowind, el, er, stats, delta, grad_out, feat, dtype, grad_er, M, K, H, F, nnz, slope, nullptr, nullptr,
+                                     stream);
+}
+
+int gespmm_gat_backward_el_dropout_x16(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                       const void* grad_out, const void* feat, int dtype, float* delta, float* grad_el, int64_t M,
+                                       int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream) {
+    return gat_backward_el_x16_entry(rowptr, colind, el, er, stats, grad_out, feat, dtype, delta, grad_el, M, K, H, F, nnz, slope, &p, seed, stream);
+}
+
+int gespmm_gat_backward_er_dropout_x16(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                       const float* delta, const void* grad_out, const void* feat, int dtype, float* grad_er, int64_t M,
+                                       int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream) {
+    return gat_backward_er_x16_entry(colptr, rowind, el, er, stats, delta, grad_out, feat, dtype, grad_er, M, K, H, F, nnz, slope, &p, seed, stream);
+}
+
+/* Host only: what the four entry points above would launch — the function they route through, the pin included. */
+int gespmm_describe_gat_backward_x16(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int grad_out_align,
+                                     int feat_align, char* out, int64_t capacity) {
+    if (!out || capacity <= 0 || grad_out_align < 2 || feat_align < 2 || (transposed != 0 && transposed != 1)) return GESPMM_EINVAL;
+    const int rc = gespmm::check_gat_backward_sizes(M, K, H, F, nnz, 1.0f);
+    if (rc != 0) return rc;
+    int n;
+    if (nnz == 0 || F == 0 || (!transposed && M == 0)) {
+        n = snprintf(out, (size_t)capacity, "form=none");
+    } else {
+        const gespmm::GatBackwardLaunch b =
+            gespmm::resolve_gat_backward_x16(transposed ? K : M, nnz, H, F, grad_out_align > 16 ? 16 : grad_out_align,
+                                             feat_align > 16 ? 16 : feat_align, gat_backward_pin());
+        n = snprintf(out, (size_t)capacity, "form=%s V=%d Wd=%d W=%d L=%d rpw=%d", b.form == gespmm::kGatBackwardGroup ? "group" : "lane", b.V,
+                     b.Wd, b.W, b.L, b.rpw);
+    }
+    return describe_result(n, capacity);
+}
+
 int gespmm_gat_aggregate_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,
                                int32_t* geometry_out) {
     if (b_align < 1 || c_align < 1 || (transposed != 0 && transposed != 1)) return GESPMM_EINVAL;

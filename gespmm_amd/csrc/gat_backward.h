@@ -43,6 +43,18 @@ namespace gespmm {
 
 struct EdgeDropout;  // edge_dropout.h
 
+// An element of grad_out / feat as the kernels address it: a float, or the 16 bits of an fp16 / bf16 value.
+template <int DT>
+struct GatBackwardElem {
+    using type = uint16_t;
+};
+template <>
+struct GatBackwardElem<0> {
+    using type = float;
+};
+template <int DT>
+using gb_elem_t = typename GatBackwardElem<DT>::type;
+
 // drop != nullptr (gespmm_gat_backward_{el,er}_dropout_f32): g_p is replaced by g'_p = dropout(g_p) — edge_dropout.h's mask of (r, c, h),
 // one rounding fl(g_p s) or +0 — directly after its chain; delta, gs_p and the sums are the statements above on g'_p, w_p the undropped
 // weight. The bits are then those of the composition with launch_edge_dropout between the SDDMM and the softmax's backward.
@@ -82,5 +94,33 @@ hipError_t launch_gat_backward_group_er(const int32_t* colptr, const int32_t* ro
                                         const float* delta, const float* grad_out, const float* feat, float* grad_er, int64_t M, int64_t K,
                                         int64_t H, int64_t F, int64_t nnz, float slope, const GatBackwardLaunch& r, const EdgeDropout* drop,
                                         hipStream_t st);
+
+// ---- fp16 / bf16 grad_out and feat (gespmm_gat_backward_{el,er}_x16; kernels in gat_backward_x16.hip and gat_backward_group_x16.hip: the
+// two bodies above as templates on the element type). dtype kX16F16 / kX16Bf16, one type per call; el, er, stats, delta, grad_el and
+// grad_er stay fp32, as do the weights, the dropout arithmetic and every chain. Each 16-bit element is widened, exactly, at its fmaf and
+// no 16-bit word is written: nothing is rounded that the fp32 kernels do not round. r = resolve_gat_backward_x16 (select.h).
+//   lane form   the contract at the top of this file; a load brings r.V ELEMENTS, 8 / 4 / 2 / 1 (F % V == 0, 2 V bytes divide both
+//               addresses — refused otherwise). The chain does not see V: delta, grad_el and grad_er have the bits of
+//               launch_gat_backward_el / _er on the widened operands, whatever either side's load width.
+//   group form  the contract above at V = 4 ELEMENTS per lane and step (one 8-byte load): W_d, lane positions and butterfly are those of
+//               the fp32 group form at width F, so the results have the bits of launch_gat_backward_group_el / _er on the widened
+//               operands. Eligible when F % 4 == 0, 16 <= F <= 512 and both operands are 8-byte aligned.
+// Sizes, nnz == 0, safety rules, capture: as the fp32 entries. No LDS, no atomics, no workspace.
+hipError_t launch_gat_backward_el_x16(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                      const void* grad_out, const void* feat, int dtype, float* delta, float* grad_el, int64_t M, int64_t K,
+                                      int64_t H, int64_t F, int64_t nnz, float slope, const GatBackwardLaunch& r, const EdgeDropout* drop,
+                                      hipStream_t st);
+hipError_t launch_gat_backward_er_x16(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                      const float* delta, const void* grad_out, const void* feat, int dtype, float* grad_er, int64_t M,
+                                      int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, const GatBackwardLaunch& r,
+                                      const EdgeDropout* drop, hipStream_t st);
+hipError_t launch_gat_backward_group_el_x16(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                            const void* grad_out, const void* feat, int dtype, float* delta, float* grad_el, int64_t M,
+                                            int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, const GatBackwardLaunch& r,
+                                            const EdgeDropout* drop, hipStream_t st);
+hipError_t launch_gat_backward_group_er_x16(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                            const float* delta, const void* grad_out, const void* feat, int dtype, float* grad_er, int64_t M,
+                                            int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, const GatBackwardLaunch& r,
+                                            const EdgeDropout* drop, hipStream_t st);
 
 }  // namespace gespmm

@@ -335,6 +335,24 @@ GatBackwardLaunch resolve_gat_backward(int64_t S, int64_t nnz, int64_t H, int64_
     return r;
 }
 
+// ... on 16-bit operands. The group form's eligibility and geometry are the fp32 rule at twice each alignment (an 8-byte aligned row of
+// 16-bit elements is the 16-byte aligned widened row), with a default threshold of its own; the lane form takes the widest load.
+GatBackwardLaunch resolve_gat_backward_x16(int64_t S, int64_t nnz, int64_t H, int64_t F, int grad_out_align, int feat_align, int pin) {
+    const EdgeSoftmaxLaunch e = resolve_edge_softmax(S, nnz, H);
+    const int least = grad_out_align < feat_align ? grad_out_align : feat_align;
+    int V = 8;
+    while (V > 1 && (F % V != 0 || least < 2 * V)) V /= 2;
+    GatBackwardLaunch r = {kGatBackwardLane, V, 1, e.W, e.L, e.rpw};
+    const bool eligible = F % 4 == 0 && F >= 16 && F <= kGatBackwardGroupMaxF && least >= 8;
+    const bool by_default = kGatBackwardX16GroupMinF >= 16 && F >= kGatBackwardX16GroupMinF;
+    if (!eligible || pin == kGatBackwardPinLane || (pin != kGatBackwardPinGroup && !by_default)) return r;
+    const SddmmLaunch b = resolve_sddmm(false, 1, 1, F, 16, 16, false, 4);  // (the widened operands)
+    r.form = kGatBackwardGroup;
+    r.V = b.V;
+    r.Wd = b.W;
+    return r;
+}
+
 // The GATv2 score. V and W are resolve_sddmm's at WIDTH F — asked in its COO form, which has no row-walking or blocked answer — with the
 // less aligned of xl and xr as one operand and att as the other: V divides F and 4 V bytes divide all THREE bases. Entries per wavefront
 // and the multiply-shift for t / H are resolve_sddmm_heads' rule for its CSR kernel, on the pair count nnz H. None of these thresholds

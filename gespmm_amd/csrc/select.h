@@ -95,6 +95,17 @@ struct GatBackwardLaunch {
 GatBackwardLaunch resolve_gat_backward(int64_t S, int64_t nnz, int64_t H, int64_t F, int grad_out_align, int feat_align,
                                        int pin = kGatBackwardPinNone);
 
+// ... on fp16 / bf16 grad_out and feat (gespmm_describe_gat_backward_x16 prints it; the x16 entry points run exactly this). The group form
+// walks ELEMENTS in the fp32 order at V = 4 — one 8-byte load — so it is ELIGIBLE when F % 4 == 0, 16 <= F <= kGatBackwardGroupMaxF and
+// both alignments are at least 8: the answer (form, group V, W_d) is resolve_gat_backward's for the widened operands, a 16-bit operand b
+// bytes off a 16-byte boundary being an fp32 one 2 b bytes off. The lane form reports the V of its loads, 8 / 4 / 2 / 1 ELEMENTS: the
+// widest that divides F and whose 2 V bytes divide both alignments (>= 2); no bit depends on it. Same pin.
+// The smallest width from which an eligible 16-bit launch takes the group form by default: CARRIED OVER from kGatBackwardGroupMinF,
+// not measured at 16 bits.
+constexpr int64_t kGatBackwardX16GroupMinF = 16;
+GatBackwardLaunch resolve_gat_backward_x16(int64_t S, int64_t nnz, int64_t H, int64_t F, int grad_out_align, int feat_align,
+                                           int pin = kGatBackwardPinNone);
+
 // ---- GATv2 edge score (gatv2_score.h): the launch shape of the forward (gespmm_describe_gatv2_score prints it).
 struct Gatv2ScoreLaunch {
     int V, W;        // what resolve_sddmm answers for WIDTH F, with att's address as a third operand: they fix the summation order

@@ -479,9 +479,8 @@ class GATAggregateFunction(torch.autograd.Function):
     16-bit ``feat`` (fp16 or bf16; ``el``, ``er``, the statistics and every gradient of theirs stay fp32): the forward is
     ``gat_softmax_stats`` unchanged, then ``spmm.gat_aggregate_x16``; grad_feat is ``spmm.gat_aggregate_x16(colptr, rowind, ..,
     grad_out, transposed=True)``, 16-bit; the default backward takes grad_alpha from ``sddmm.csr_sddmm_heads_x16``. With
-    ``fused_backward=True`` grad_el / grad_er are a COMPOSITION: ``grad_out`` and ``feat`` are widened (``.float()``: exact, two
-    node-sized transients) and go through the unchanged fp32 ``softmax.gat_backward_el`` / ``gat_backward_er`` — there are no 16-bit
-    forms of those two kernels yet; still nothing of size nnz H is allocated. Inside a stream capture, where ``spmm.gat_aggregate_x16``
+    ``fused_backward=True`` grad_el / grad_er are ``softmax.gat_backward_el_x16`` / ``gat_backward_er_x16`` on ``grad_out`` and ``feat``
+    as they are: the bits of the fp32 kernels on the widened tensors, with no fp32 copy of either and nothing of size nnz H. Inside a stream capture, where ``spmm.gat_aggregate_x16``
     has no kernel (odd F, H > 8), its composition is made of torch's allocations (``_gat_aggregate_x16``): the same bits. Saved: ``el``, ``er``, the 16-bit ``feat``, the
     statistics and the seed. ``grad_out`` must have ``feat``'s dtype (TypeError otherwise)."""
 
@@ -523,13 +522,12 @@ class GATAggregateFunction(torch.autograd.Function):
             raise TypeError("grad_out is %s and feat %s: one dtype per call" % (grad_out.dtype, feat.dtype))
         grad_el = grad_er = grad_feat = None
         if ctx.fused_backward and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):  # node-sized tensors only
-            # (16-bit: a composition — the two operands widened, exactly, into node-sized transients for the fp32 kernels)
-            go32, feat32 = (grad_out.float(), feat.float()) if x16 else (grad_out, feat)
-            delta, grad_el = _softmax.gat_backward_el(rowptr, colind, el, er, stats, go32, feat32, negative_slope=slope, dropout=drop)
+            # (16-bit: the x16 forms of the two kernels read grad_out and feat as they are — no fp32 copy of either)
+            bel, ber = (_softmax.gat_backward_el_x16, _softmax.gat_backward_er_x16) if x16 else \
+                (_softmax.gat_backward_el, _softmax.gat_backward_er)
+            delta, grad_el = bel(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=slope, dropout=drop)
             if ctx.needs_input_grad[6]:
-                grad_er = _softmax.gat_backward_er(colptr, rowind, el, er, stats, delta, go32, feat32, negative_slope=slope,
-                                                   dropout=drop)
-            del go32, feat32
+                grad_er = ber(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=slope, dropout=drop)
             if not ctx.needs_input_grad[5]:
                 grad_el = None
         elif ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:  # (first: its three edge-sized temporaries are gone before grad_feat exists)
@@ -707,9 +705,9 @@ class GATConv(torch.nn.Module):
     rounding) and the bias add is torch's. ``fused_aggregate`` / ``fused_backward`` take 16-bit features only with ``fused_x16=True``
     (a ValueError without one of the two): ``GATAggregateFunction`` on the 16-bit ``xw`` — ``spmm.gat_aggregate_x16`` forward and,
     transposed, for the feature gradient, ``dropout=`` included; output and all gradients of ``fused_aggregate`` have the bits of the
-    16-bit ``fused_score=True`` layer. With ``fused_backward`` the two attention gradients are a composition: ``grad_out`` and ``xw`` are
-    widened into two node-sized fp32 transients for the fp32 ``softmax.gat_backward_el`` / ``gat_backward_er`` (no 16-bit forms of
-    those kernels exist yet); nothing of size ``[nnz, H]`` is allocated. Without the flag 16-bit features raise TypeError there; fp32
+    16-bit ``fused_score=True`` layer. With ``fused_backward`` the two attention gradients come from
+    ``softmax.gat_backward_el_x16`` / ``gat_backward_er_x16`` on the 16-bit ``grad_out`` and ``xw`` themselves — the bits of the fp32
+    kernels on the widened tensors, no fp32 copy of either; nothing of size ``[nnz, H]`` is allocated. Without the flag 16-bit features raise TypeError there; fp32
     features ignore it."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, bias=True, fused_score=False,

@@ -9,6 +9,7 @@ gespmm_edge_softmax_backward_f32 — the reference has no counterpart).
     gat_softmax_stats(rowptr, colind, el, er, negative_slope=None, out=None)                      -> f32[M, H, 2]
     gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None, dropout=None) -> (delta f32[M, H], grad_el f32[M, H])
     gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None, dropout=None) -> grad_er f32[K, H]
+    gat_backward_el_x16 / gat_backward_er_x16(... the same arguments, grad_out and feat fp16 or bf16 ...)     -> the same fp32 results
     edge_dropout(rowptr, colind, x, p, seed, out=None)                                            -> f32[nnz, H] (or f32[nnz])
 
 ``score`` is f32[nnz] or f32[nnz, H] in CSR edge order — what ``sddmm.csr_sddmm`` / ``sddmm.csr_sddmm_heads`` return and what
@@ -40,7 +41,7 @@ changes the mask. Two entries with the same (row, column) — a multigraph — s
 All calls go through ctypes."""
 import torch
 
-from ._lib import check, lib
+from ._lib import X16_BF16, X16_F16, check, lib
 from .spmm import _on_device, _ptr, _stream
 
 
@@ -358,14 +359,14 @@ def edge_segment_sum(ptr, x, order=None, out=None):
     return out
 
 
-def _head_rows(t, name, rows, H, dev, F=None):
-    """fp32, contiguous, [rows, H, F] on ``dev`` (F >= 1; the given F when there is one) -> F"""
+def _head_rows(t, name, rows, H, dev, F=None, dtype=torch.float32):
+    """``dtype`` (fp32), contiguous, [rows, H, F] on ``dev`` (F >= 1; the given F when there is one) -> F"""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
-    if t.dtype != torch.float32:
-        raise TypeError("%s must have dtype torch.float32, got %s" % (name, t.dtype))
+    if t.dtype != dtype:
+        raise TypeError("%s must have dtype %s, got %s" % (name, dtype, t.dtype))
     if t.dim() != 3 or t.shape[0] != rows or t.shape[1] != H or t.shape[2] < 1 or (F is not None and t.shape[2] != F):
-        raise ValueError("%s must be f32[%d, %d, %s], got %s" % (name, rows, H, "F" if F is None else F, list(t.shape)))
+        raise ValueError("%s must be [%d, %d, %s], got %s" % (name, rows, H, "F" if F is None else F, list(t.shape)))
     if not t.is_contiguous():
         raise ValueError("%s must be contiguous" % name)
     if t.device != dev:
@@ -403,14 +404,49 @@ def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slop
     ``16 <= F <= 512`` and ``grad_out`` and ``feat`` are 16-byte aligned, a lane GROUP computes ``g`` in ``csr_sddmm_heads``' order, and
     ``grad_el`` / ``grad_er`` have the bits of the four-step composition on any operands; elsewhere one lane runs the ascending chain
     above. ``GESPMM_GAT_BACKWARD_FORM=lane|group`` in the environment pins the form of an eligible call."""
+    return _gat_backward_el(torch.float32, rowptr, colind, el, er, stats, grad_out, feat, negative_slope, out, dropout)
+
+
+_X16 = {torch.float16: X16_F16, torch.bfloat16: X16_BF16}
+
+
+def _x16_dtype(grad_out, feat):
+    """The one 16-bit dtype of ``grad_out`` and ``feat``; TypeError for fp32, mixed or any other operands."""
+    for name, t in (("grad_out", grad_out), ("feat", feat)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        if t.dtype not in _X16:
+            raise TypeError("%s must have dtype torch.float16 or torch.bfloat16, got %s" % (name, t.dtype))
+    if grad_out.dtype != feat.dtype:
+        raise TypeError("grad_out is %s and feat %s: one dtype per call" % (grad_out.dtype, feat.dtype))
+    return feat.dtype
+
+
+def gat_backward_el_x16(rowptr, colind, el, er, stats, grad_out, feat, negative_slope=None, out=None, dropout=None):
+    """``gat_backward_el`` on fp16 / bf16 ``grad_out`` [M, H, F] and ``feat`` [K, H, F], one dtype for both (gespmm_gat_backward_el_x16 /
+    _dropout_x16) -> ``(delta, grad_el)``, both f32[M, H]. ``el``, ``er``, ``stats`` and the results stay fp32; each 16-bit element is
+    widened exactly at its fmaf and nothing 16-bit is written, so the results have the bits of ``gat_backward_el`` on
+    ``grad_out.float()`` and ``feat.float()`` wherever ``_lib.describe_gat_backward`` answers the same form (and, in the group form,
+    ``Wd``) for those — without the two fp32 copies. Both forms exist (``_lib.describe_gat_backward(.., x16=True)``): the lane form
+    loads 8 / 4 / 2 / 1 elements at a time (any F, any 2-byte aligned operand; no bit depends on the width), the group form is
+    eligible where ``F % 4 == 0``, ``16 <= F <= 512`` and both operands are 8-byte aligned. Mixed or fp32 operands: TypeError."""
+    return _gat_backward_el(_x16_dtype(grad_out, feat), rowptr, colind, el, er, stats, grad_out, feat, negative_slope, out, dropout)
+
+
+def _gat_backward_el(dtype, rowptr, colind, el, er, stats, grad_out, feat, negative_slope, out, dropout):
+    x16 = _X16.get(dtype)
+    names = ("gespmm_gat_backward_el_dropout_x16", "gespmm_gat_backward_el_x16") if x16 else \
+        ("gespmm_gat_backward_el_dropout_f32", "gespmm_gat_backward_el_f32")
+    code = (x16,) if x16 else ()
     slope = _slope(negative_slope)
     _typed(torch.int32, rowptr=rowptr, colind=colind)
-    _typed(torch.float32, el=el, er=er, stats=stats, grad_out=grad_out, feat=feat)
+    _typed(torch.float32, el=el, er=er, stats=stats)
+    _typed(dtype, grad_out=grad_out, feat=feat)
     _dropout_typed(dropout)
     dev, M, K, H, nnz = _gat_terms(rowptr, colind, el, er)
     _stats_array(stats, "stats", M, H, dev)
-    F = _head_rows(grad_out, "grad_out", M, H, dev)
-    _head_rows(feat, "feat", K, H, dev, F)
+    F = _head_rows(grad_out, "grad_out", M, H, dev, dtype=dtype)
+    _head_rows(feat, "feat", K, H, dev, F, dtype=dtype)
     if out is None:
         delta = torch.empty(M, H, dtype=torch.float32, device=dev)
         grad_el = torch.empty(M, H, dtype=torch.float32, device=dev)
@@ -420,18 +456,17 @@ def gat_backward_el(rowptr, colind, el, er, stats, grad_out, feat, negative_slop
         delta, grad_el = out
         _node_result(delta, "out[0]", M, H, dev)
         _node_result(grad_el, "out[1]", M, H, dev)
+    args = (_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(stats), _ptr(grad_out), _ptr(feat)) + code + \
+        (_ptr(delta), _ptr(grad_el), M, K, H, F, nnz, slope)
     if dropout is not None:
         p, seed = _dropout(dropout, dev)
         with _on_device(dev):
-            rc = lib.gespmm_gat_backward_el_dropout_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(stats), _ptr(grad_out),
-                                                        _ptr(feat), _ptr(delta), _ptr(grad_el), M, K, H, F, nnz, slope, p, _ptr(seed),
-                                                        _stream(dev))
-        check(rc, "gespmm_gat_backward_el_dropout_f32")
+            rc = getattr(lib, names[0])(*args, p, _ptr(seed), _stream(dev))
+        check(rc, names[0])
         return delta, grad_el
     with _on_device(dev):
-        rc = lib.gespmm_gat_backward_el_f32(_ptr(rowptr), _ptr(colind), _ptr(el), _ptr(er), _ptr(stats), _ptr(grad_out), _ptr(feat),
-                                            _ptr(delta), _ptr(grad_el), M, K, H, F, nnz, slope, _stream(dev))
-    check(rc, "gespmm_gat_backward_el_f32")
+        rc = getattr(lib, names[1])(*args, _stream(dev))
+    check(rc, names[1])
     return delta, grad_el
 
 
@@ -441,9 +476,24 @@ def gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negati
     entries of each column in the pinned order of ``edge_segment_sum(colptr, .., order=csc_order)``. ``colptr, rowind`` are the CSC
     arrays (``graphs.transpose_csr``); no ``csc_order`` is needed. Every word is written, empty columns +0. ``dropout=(p, seed)``: as in
     ``gat_backward_el`` (gespmm_gat_backward_er_dropout_f32) — the walk over the columns recomputes the decisions of the walk over rows."""
+    return _gat_backward_er(torch.float32, colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope, out, dropout)
+
+
+def gat_backward_er_x16(colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope=None, out=None, dropout=None):
+    """``gat_backward_er`` on fp16 / bf16 ``grad_out`` and ``feat`` (gespmm_gat_backward_er_x16 / _dropout_x16) -> ``grad_er`` f32[K, H],
+    from the fp32 ``delta`` of ``gat_backward_el_x16``: forms, operands and bits as stated there."""
+    return _gat_backward_er(_x16_dtype(grad_out, feat), colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope, out, dropout)
+
+
+def _gat_backward_er(dtype, colptr, rowind, el, er, stats, delta, grad_out, feat, negative_slope, out, dropout):
+    x16 = _X16.get(dtype)
+    names = ("gespmm_gat_backward_er_dropout_x16", "gespmm_gat_backward_er_x16") if x16 else \
+        ("gespmm_gat_backward_er_dropout_f32", "gespmm_gat_backward_er_f32")
+    code = (x16,) if x16 else ()
     slope = _slope(negative_slope)
     _typed(torch.int32, colptr=colptr, rowind=rowind)
-    _typed(torch.float32, el=el, er=er, stats=stats, delta=delta, grad_out=grad_out, feat=feat)
+    _typed(torch.float32, el=el, er=er, stats=stats, delta=delta)
+    _typed(dtype, grad_out=grad_out, feat=feat)
     _dropout_typed(dropout)
     K = _checked_rowptr(colptr)
     _node_array(er, "er", rows=K)
@@ -454,22 +504,21 @@ def gat_backward_er(colptr, rowind, el, er, stats, delta, grad_out, feat, negati
     M, H, nnz = el.shape[0], er.shape[1], rowind.numel()
     _stats_array(stats, "stats", M, H, dev)
     _node_result(delta, "delta", M, H, dev)
-    F = _head_rows(grad_out, "grad_out", M, H, dev)
-    _head_rows(feat, "feat", K, H, dev, F)
+    F = _head_rows(grad_out, "grad_out", M, H, dev, dtype=dtype)
+    _head_rows(feat, "feat", K, H, dev, F, dtype=dtype)
     if out is None:
         out = torch.empty(K, H, dtype=torch.float32, device=dev)
     else:
         _node_result(out, "out", K, H, dev)
+    args = (_ptr(colptr), _ptr(rowind), _ptr(el), _ptr(er), _ptr(stats), _ptr(delta), _ptr(grad_out), _ptr(feat)) + code + \
+        (_ptr(out), M, K, H, F, nnz, slope)
     if dropout is not None:
         p, seed = _dropout(dropout, dev)
         with _on_device(dev):
-            rc = lib.gespmm_gat_backward_er_dropout_f32(_ptr(colptr), _ptr(rowind), _ptr(el), _ptr(er), _ptr(stats), _ptr(delta),
-                                                        _ptr(grad_out), _ptr(feat), _ptr(out), M, K, H, F, nnz, slope, p, _ptr(seed),
-                                                        _stream(dev))
-        check(rc, "gespmm_gat_backward_er_dropout_f32")
+            rc = getattr(lib, names[0])(*args, p, _ptr(seed), _stream(dev))
+        check(rc, names[0])
         return out
     with _on_device(dev):
-        rc = lib.gespmm_gat_backward_er_f32(_ptr(colptr), _ptr(rowind), _ptr(el), _ptr(er), _ptr(stats), _ptr(delta), _ptr(grad_out),
-                                            _ptr(feat), _ptr(out), M, K, H, F, nnz, slope, _stream(dev))
-    check(rc, "gespmm_gat_backward_er_f32")
+        rc = getattr(lib, names[1])(*args, _stream(dev))
+    check(rc, names[1])
     return out

@@ -42,6 +42,8 @@
  *                               _threshold <- (new) dropout on the attention coefficients with a mask that is never stored
  *   gespmm_gat_aggregate_x16 / gespmm_gat_aggregate_dropout_x16 / gespmm_gat_aggregate_x16_route <- (new) that aggregation on fp16 /
  *                               bf16 features: fp32 weights and sums, one rounding at the store
+ *   gespmm_gat_backward_{el,er}_x16 / _dropout_x16 / gespmm_describe_gat_backward_x16 <- (new) that backward on fp16 / bf16 grad_out and
+ *                               feat: fp32 results with the bits of the fp32 entry points on the widened operands
  *   gespmm_baseline_copy_f32 <- (new) streaming-copy yardstick for the roofline record; no reference counterpart
  *
  * Conventions (all device entry points):
@@ -940,6 +942,40 @@ int gespmm_gat_aggregate_dropout_x16(const int32_t* ptr, const int32_t* ind, con
 /* Host only: the route of the two calls above, as gespmm_gat_aggregate_route; geometry_out is in words (V words per lane and strip). */
 int gespmm_gat_aggregate_x16_route(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int b_align, int c_align,
                                    int32_t* geometry_out);
+/*
+ * The fused backward for el and er on 16-bit grad_out and feat (new symbols of 0.5). grad_out [M x H x F] and feat [K x H x F] are IEEE
+ * fp16 (GESPMM_X16_F16) or bfloat16 (GESPMM_X16_BF16), one type per call; el, er, stats, delta, grad_el and grad_er stay fp32, as do the
+ * weights, the dropout arithmetic and every chain of gespmm_gat_backward_el_f32 / _er_f32. Each 16-bit element is widened (exactly) at
+ * its fmaf and no 16-bit word is written, so nothing is rounded that the fp32 kernels do not round. Both forms exist:
+ *   LANE   the ascending chain of one lane. A load brings V ELEMENTS, V = 8 / 4 / 2 / 1 (16 / 8 / 4 / 2 bytes): the widest V that divides
+ *          F and whose 2 V bytes divide both addresses. Every F >= 1 and every 2-byte aligned address is served; no bit depends on V.
+ *   GROUP  V = 4 elements per lane and step (one 8-byte load), lane q walking j = 4 q + i + 4 W_d t, t < 2, then the butterfly, W_d the
+ *          smallest power of two in 4 .. 64 with 8 W_d >= F: the fp32 group form's lane positions. ELIGIBLE when F % 4 == 0,
+ *          16 <= F <= 512 and grad_out and feat are both 8-byte aligned; taken from F = 16 on (a threshold carried over from fp32, not
+ *          measured at 16 bits: DESIGN 3.31) or where GESPMM_GAT_BACKWARD_FORM=group says so; =lane pins the lane form.
+ * Hence: wherever gespmm_describe_gat_backward answers the same form (and, in the group form, W_d) for the widened operands — a 16-bit
+ * operand b bytes off a 16-byte boundary corresponds to an fp32 one 2 b bytes off — delta, grad_el and grad_er have the BITS of
+ * gespmm_gat_backward_el_f32 / _er_f32 (the dropout forms: _dropout_f32) on widen(grad_out) and widen(feat). Every word of the results is
+ * written (an empty row or column: +0). One kernel each, no LDS, no atomics, no workspace, no allocation: capturable.
+ * Checks: dtype not GESPMM_X16_F16 / _BF16 -> GESPMM_EINVAL; then the ladder of the fp32 entry, with grad_out and feat 2-byte aligned
+ * (GESPMM_EALIGN otherwise); nnz == 0 or F == 0 zero-fills the results and launches nothing.
+ * gespmm_describe_gat_backward_x16 (host only): gespmm_describe_gat_backward's text for these entries, "form=lane|group V=.. Wd=.. W=..
+ * L=.. rpw=.." (V in ELEMENTS) or "form=none"; *_align >= 2.
+ */
+int gespmm_gat_backward_el_x16(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                               const void* grad_out, const void* feat, int dtype, float* delta, float* grad_el, int64_t M, int64_t K,
+                               int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gat_backward_er_x16(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                               const float* delta, const void* grad_out, const void* feat, int dtype, float* grad_er, int64_t M, int64_t K,
+                               int64_t H, int64_t F, int64_t nnz, float slope, void* stream);
+int gespmm_gat_backward_el_dropout_x16(const int32_t* rowptr, const int32_t* colind, const float* el, const float* er, const float* stats,
+                                       const void* grad_out, const void* feat, int dtype, float* delta, float* grad_el, int64_t M,
+                                       int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream);
+int gespmm_gat_backward_er_dropout_x16(const int32_t* colptr, const int32_t* rowind, const float* el, const float* er, const float* stats,
+                                       const float* delta, const void* grad_out, const void* feat, int dtype, float* grad_er, int64_t M,
+                                       int64_t K, int64_t H, int64_t F, int64_t nnz, float slope, float p, const void* seed, void* stream);
+int gespmm_describe_gat_backward_x16(int64_t M, int64_t K, int64_t H, int64_t F, int64_t nnz, int transposed, int grad_out_align,
+                                     int feat_align, char* out, int64_t capacity);
 /* Host only: the mask's bits and the threshold T as the kernels compute them. gespmm_edge_dropout_threshold answers 0xffffffff for a p
  * outside [0, 1), which no legal p gives. */
 uint32_t gespmm_edge_dropout_bits(uint32_t s0, uint32_t s1, uint32_t r, uint32_t c, uint32_t h);
