@@ -6,9 +6,12 @@
     python examples/sage_custom.py --dataset pubmed --aggregator-type mean --n-hidden 64
     python examples/sage_custom.py --aggregator-type pool --graph-capture      # replay each step from a HIP graph
     python examples/sage_custom.py --aggregator-type pool --dtype bf16         # a .bfloat16() model on 16-bit features
+    python examples/sage_custom.py --aggregator-type mean --dtype bf16 --fused-linear   # each layer ONE aggregate-and-linear kernel
 
 The command-line options are the reference script's (sage_dgl.py:182-201; ``--dataset`` is what ``register_data_args`` adds), plus
-``--graph-capture``, ``--seed`` and ``--dtype`` (fp16 / bf16: model and features in that type, the loss in fp32). Differences forced by the environment are those of examples/gcn_custom.py, whose data path this
+``--graph-capture``, ``--seed``, ``--dtype`` (fp16 / bf16: model and features in that type, the loss in fp32) and ``--fused-linear``
+(``SAGEConv(fused_linear=True)``: with ``--aggregator-type mean --dtype bf16|fp16`` only; layers whose width the kernel does not serve
+compose the same arithmetic). Differences forced by the environment are those of examples/gcn_custom.py, whose data path this
 script uses: the bundled adjacency matrices or the synthetic stand-ins, random features, labels and masks — accuracy is chance level by
 construction, the point is the step time and that the loss falls. As in the reference, self loops are removed (sage_dgl.py:101) and the
 profiler table is replaced by HIP-event timing of the epoch loop.
@@ -32,12 +35,13 @@ from gespmm_amd import SAGEConv, graphs  # noqa: E402
 class GraphSAGE(torch.nn.Module):
     """sage_dgl.py:21-48: an input layer, n_layers - 1 hidden layers, an output layer without activation."""
 
-    def __init__(self, g, in_feats, n_hidden, n_classes, n_layers, activation, dropout, aggregator_type):
+    def __init__(self, g, in_feats, n_hidden, n_classes, n_layers, activation, dropout, aggregator_type, fused_linear=False):
         super().__init__()
         self.g = g
         dims = [in_feats] + [n_hidden] * n_layers + [n_classes]
         self.layers = torch.nn.ModuleList(
-            [SAGEConv(dims[i], dims[i + 1], aggregator_type, feat_drop=dropout, activation=activation if i + 2 < len(dims) else None)
+            [SAGEConv(dims[i], dims[i + 1], aggregator_type, feat_drop=dropout, activation=activation if i + 2 < len(dims) else None,
+                      fused_linear=fused_linear)
              for i in range(len(dims) - 1)])
 
     def forward(self, features):
@@ -71,8 +75,11 @@ def main():
     ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dtype", choices=("fp32", "fp16", "bf16"), default="fp32", help="type of the model and the features (the loss stays fp32)")
+    ap.add_argument("--fused-linear", action="store_true", help="one aggregate-and-linear kernel per layer (mean, fp16 / bf16 only)")
     args = ap.parse_args()
     print(args)
+    if args.fused_linear and (args.aggregator_type != "mean" or args.dtype == "fp32"):
+        raise SystemExit("--fused-linear needs --aggregator-type mean and --dtype bf16 or fp16")
     if args.gpu < 0 or not torch.cuda.is_available():
         raise SystemExit("needs a HIP device (the op has no CPU path)")
     torch.cuda.set_device(args.gpu)
@@ -92,7 +99,7 @@ def main():
     print("----Data statistics------\n  #Edges %d\n  #Classes %d\n  #Train samples %d\n  #Val samples %d\n  #Test samples %d"
           % (n_edges, n_cls, idx["train"].numel(), idx["val"].numel(), idx["test"].numel()))
 
-    model = GraphSAGE(g, n_feat, args.n_hidden, n_cls, args.n_layers, F.relu, args.dropout, args.aggregator_type).to(device)
+    model = GraphSAGE(g, n_feat, args.n_hidden, n_cls, args.n_layers, F.relu, args.dropout, args.aggregator_type, args.fused_linear).to(device)
     if args.dtype != "fp32":
         dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype]
         model, features = model.to(dtype), features.to(dtype)

@@ -1215,6 +1215,63 @@ class SpmmMaxFunction(torch.autograd.Function):
         return None, None, None, None, None, grad_feat, None
 
 
+class SpmmLinearFunction(torch.autograd.Function):
+    """out = narrow(narrow(row_scale * (A @ x)) @ weight.T + root @ root_weight.T + bias) as ONE kernel on fp16 / bf16 features
+    (``spmm.csr_spmm_linear``: the CSR sum of a block of rows stays in LDS and feeds the matrix unit; the [M, K] aggregate never
+    reaches memory).
+
+        SpmmLinearFunction.apply(rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias,
+                                 values_csr=None, values_csc=None)
+
+    ``row_scale`` (fp32 [M]), ``root`` / ``root_weight`` (together) and ``bias`` may be None; edge weights are fp32 in CSR and CSC
+    order and get no gradient. The backward composes existing ops and saves nothing of size [M, K] beyond its inputs:
+    g' = row_scale * grad_out, G = A^T g' through the 16-bit product on the CSC arrays ([Kn, N_out]), grad_x = G @ weight,
+    grad_weight = G^T @ x, grad_root = grad_out @ root_weight, grad_root_weight = grad_out^T @ root, grad_bias = grad_out.sum(0) (fp32
+    sum). No [nnz] array is made. Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias, values_csr=None, values_csc=None):
+        # grad_x AND grad_weight go through G = A^T g', which needs the weights in CSC order
+        if values_csr is not None and values_csc is None and (x.requires_grad or weight.requires_grad):
+            raise RuntimeError("the backward of SpmmLinearFunction (grad_x, grad_weight) needs the edge weights in CSC order too: values_csc")
+        x, weight = x.contiguous(), weight.contiguous()
+        if root is not None:
+            root, root_weight = root.contiguous(), root_weight.contiguous()
+        out = _spmm.csr_spmm_linear(rowptr, colind, values_csr, x, weight, row_scale=row_scale, root=root, root_weight=root_weight,
+                                    bias=None if bias is None else bias.detach())
+        ctx.save_for_backward(colptr, rowind, x, weight, row_scale, root, root_weight, values_csc)
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        colptr, rowind, x, weight, row_scale, root, root_weight, values_csc = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        need = ctx.needs_input_grad
+        grad_x = grad_w = grad_root = grad_rw = grad_bias = None
+        if need[4] or need[5]:
+            g = grad_out if row_scale is None else (grad_out.float() * row_scale.unsqueeze(1)).to(grad_out.dtype)
+            # (a width the 16-bit kernels do not serve, an odd N_out say, goes through the fp32 product on the widened g, narrowed
+            #  once: the bits of the 16-bit entry's own composition, without its scratch allocation — the step stays capturable)
+            kernel = _lib.lib.gespmm_x16_route(colptr.numel() - 1, g.shape[0], g.shape[1], rowind.numel(), _lib.VARIANT_AUTO,
+                                               _spmm.x16_align(g), 16) in (1, 2)
+            gin = g if kernel else g.float()
+            G = (_spmm.csr_spmm_no_edge_value(colptr, rowind, gin) if values_csc is None
+                 else _spmm.csr_spmm(colptr, rowind, values_csc, gin)).to(g.dtype)
+            if need[4]:
+                grad_x = G @ weight
+            if need[5]:
+                grad_w = G.t() @ x
+        if root is not None and need[7]:
+            grad_root = grad_out @ root_weight
+        if root is not None and need[8]:
+            grad_rw = grad_out.t() @ root
+        if ctx.bias_dtype is not None and need[9]:
+            grad_bias = grad_out.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+        return None, None, None, None, grad_x, grad_w, None, grad_root, grad_rw, grad_bias, None, None
+
+
 class SAGEConv(torch.nn.Module):
     """GraphSAGE layer (Hamilton et al., 2017) with the constructor and semantics of DGL's ``SAGEConv``, on the library's ops:
 
@@ -1235,13 +1292,21 @@ class SAGEConv(torch.nn.Module):
         gcn    the 16-bit ``SPMMFunction`` sum (fp32 chain, one rounding), ``+ h``, times 1 / (deg + 1) cast to the dtype
         mean   the VALUED 16-bit product with fp32 edge weights 1 / deg(row): one fp32 fma chain per word and ONE rounding (a 16-bit
                sum scaled afterwards would round twice and can overflow fp16 on hub rows). The weights are two fp32 [nnz] arrays,
-               in CSR and in CSC order, made per forward by torch without a host synchronisation."""
+               in CSR and in CSC order, made per forward by torch without a host synchronisation.
 
-    def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0.0, bias=True, norm=None, activation=None):
+    ``fused_linear=True`` (``mean`` on fp16 / bf16 features only): the forward is ONE ``SpmmLinearFunction`` call — the aggregation
+    with row_scale = 1 / deg (0 for rows without entries), both linears and the sum of both biases in one kernel; neither the
+    aggregate nor an [nnz] weight array exists. ``gcn`` / ``pool`` raise ValueError at construction, fp32 features TypeError at the
+    call: their fusions are not built."""
+
+    def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0.0, bias=True, norm=None, activation=None, fused_linear=False):
         super().__init__()
         if aggregator_type not in ("mean", "gcn", "pool"):
             raise ValueError("aggregator_type must be 'mean', 'gcn' or 'pool', got %r%s"
                              % (aggregator_type, " (the lstm aggregator is not served)" if aggregator_type == "lstm" else ""))
+        if fused_linear and aggregator_type != "mean":
+            raise ValueError("fused_linear=True serves aggregator_type='mean' on fp16 / bf16 features, got %r" % (aggregator_type,))
+        self.fused_linear = bool(fused_linear)
         self.in_feats, self.out_feats, self.aggregator_type = in_feats, out_feats, aggregator_type
         self.norm, self.activation = norm, activation
         self.feat_drop = torch.nn.Dropout(feat_drop)
@@ -1266,7 +1331,14 @@ class SAGEConv(torch.nn.Module):
         h = self.feat_drop(x)
         degree = torch.diff(rowptr).to(torch.float32)
         x16 = h.dtype in (torch.float16, torch.bfloat16)
-        if self.aggregator_type == "mean":
+        if self.fused_linear:
+            if not x16:
+                raise TypeError("fused_linear=True serves fp16 / bf16 features (aggregator_type='mean'), got %s" % h.dtype)
+            inv_deg = torch.where(degree > 0, 1 / degree, torch.zeros_like(degree))
+            b = None if self.fc_neigh.bias is None else self.fc_self.bias.float() + self.fc_neigh.bias.float()
+            out = SpmmLinearFunction.apply(rowptr, colind, colptr, rowind, h, self.fc_neigh.weight.to(h.dtype), inv_deg, h,
+                                           self.fc_self.weight.to(h.dtype), b)
+        elif self.aggregator_type == "mean":
             inv_deg = torch.where(degree > 0, 1 / degree, torch.zeros_like(degree))
             if x16:
                 w_csr = torch.repeat_interleave(inv_deg, torch.diff(rowptr), output_size=colind.numel())

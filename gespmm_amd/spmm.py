@@ -855,6 +855,88 @@ def csr_spmm_max_backward_x16(colptr, rowind, order, arg, grad_out, K, out=None)
     return out
 
 
+def x16_align(*ts):
+    """The largest power of two (<= 16) that divides the address of every given tensor."""
+    al = 16
+    for t in ts:
+        if t is not None and t.numel() > 0:
+            while al > 1 and t.data_ptr() % al != 0:
+                al >>= 1
+    return al
+
+
+def csr_spmm_linear(rowptr, colind, values, dense, weight, row_scale=None, root=None, root_weight=None, bias=None, out=None):
+    """Aggregate, then transform, in ONE kernel on 16-bit features (gespmm_csr_spmm_linear_x16):
+
+        H   = narrow(row_scale[:, None] * (A @ dense))                      the 16-bit product as it stands, bit for bit
+        out = narrow(H @ weight.T + root @ root_weight.T + bias)            fp32 sums on the matrix unit, one rounding
+
+    ``dense`` [Kn, K], ``weight`` [N_out, K] (``torch.nn.Linear``'s layout), ``root`` [M, K] and ``root_weight`` [N_out, K] are all
+    fp16 or all bf16; ``values`` [nnz] (None: A == 1), ``row_scale`` [M] and ``bias`` [N_out] are fp32 (a 16-bit ``bias`` is widened
+    here: N_out elements). ``root`` and ``root_weight`` come together or not at all. H never reaches memory. fp32 ``dense`` raises
+    TypeError: the fp32 matrix instructions are not built.
+
+    The kernel serves K % 8 == 0, 8 <= K <= 256, N_out <= 256 and 16-byte aligned tensors (``_lib.spmm_linear_route_x16``). Anything
+    else is composed here from the existing 16-bit product and ``torch.nn.functional.linear`` in fp32, rounded once — the call never
+    fails on an odd K or a wide layer."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    _need_x16(dense, "dense", "csr_spmm / csr_spmm_fused, then torch.nn.functional.linear")
+    dt = dense.dtype
+    _need(weight, "weight", dt, 2)
+    if (root is None) != (root_weight is None):
+        raise ValueError("root and root_weight come together or not at all")
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have M+1 >= 1 entries")
+    M = rowptr.numel() - 1
+    Kn, K = dense.shape
+    N_out = weight.shape[0]
+    if weight.shape[1] != K:
+        raise ValueError("weight must be [N_out, %d]" % K)
+    others = [weight]
+    if root is not None:
+        _need(root, "root", dt, 2)
+        _need(root_weight, "root_weight", dt, 2)
+        if tuple(root.shape) != (M, K) or tuple(root_weight.shape) != (N_out, K):
+            raise ValueError("root must be [%d, %d] and root_weight [%d, %d]" % (M, K, N_out, K))
+        others += [root, root_weight]
+    if values is not None:
+        _need(values, "values", torch.float32, 1)
+        if values.numel() != colind.numel():
+            raise ValueError("values and colind must have the same length")
+        others.append(values)
+    if isinstance(bias, torch.Tensor) and bias.dtype in _X16:
+        bias = bias.float()
+    for t, name, n in ((row_scale, "row_scale", M), (bias, "bias", N_out)):
+        if t is not None:
+            _need(t, name, torch.float32, 1)
+            if t.numel() != n:
+                raise ValueError("%s must have %d entries, got %d" % (name, n, t.numel()))
+            others.append(t)
+    dev = _same_device(dense, rowptr, colind, *others)
+    inputs = (dense, weight) + ((root, root_weight) if root is not None else ())
+    result = torch.empty((M, N_out), dtype=dt, device=dev) if out is None else _result(out, "out", dt, (M, N_out), dev, inputs)
+    nnz = colind.numel()
+    if _lib.spmm_linear_route_x16(M, Kn, K, N_out, nnz, x16_align(dense if nnz else None, weight, root, root_weight, result)) == 1:
+        with _on_device(dev):
+            rc = lib.gespmm_csr_spmm_linear_x16(_ptr(rowptr), _ptr(colind), _optr(values), _optr(row_scale), _ptr(dense), _ptr(weight),
+                                                _optr(root), _optr(root_weight), _optr(bias), _ptr(result), _X16[dt], M, Kn, K, N_out, nnz,
+                                                _stream(dev))
+        check(rc, "gespmm_csr_spmm_linear_x16")
+        return result
+    # the composition: the 16-bit product as it stands, then the two linears and the bias in fp32, one rounding
+    if row_scale is not None:
+        h = csr_spmm_fused(rowptr, colind, values, dense.float(), row_scale=row_scale).to(dt)
+    elif values is None:
+        h = csr_spmm_no_edge_value(rowptr, colind, dense)
+    else:
+        h = csr_spmm(rowptr, colind, values, dense)
+    acc = torch.nn.functional.linear(h.float(), weight.float(), bias)
+    if root is not None:
+        acc = acc + torch.nn.functional.linear(root.float(), root_weight.float())
+    return result.copy_(acc)
+
+
 def csr2csc(rowptr, colind, colptr, rowind, csr_data):
     """Fill ``colptr`` / ``rowind`` in place with the CSC form of CSR(rowptr, colind)
     and return the values in CSC order. Mirrors spmm.cpp:70-93 (whose CUDA

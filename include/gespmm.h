@@ -214,6 +214,38 @@ int gespmm_csr_spmm_max_backward_x16(const int32_t* colptr, const int32_t* rowin
  * of the 16-bit arrays, arg_align: (>= 4) of arg. The answer is gespmm_max_arg_route's at the alignment min(2 x16_align, arg_align). */
 int gespmm_max_arg_route_x16(int64_t M, int64_t nnz, int64_t N, int x16_align, int arg_align, char* out, int64_t capacity);
 
+/*
+ * Fused aggregate-and-linear on 16-bit features: the CSR sum of a block of rows goes to LDS and is multiplied by the layer's weight on
+ * the matrix unit (v_mfma_f32_32x32x16_f16 / _bf16); the [M, K] aggregate never reaches memory. X [Kn, K], W_n [N_out, K], X_root
+ * [M, K], W_r [N_out, K] and out [M, N_out] are row-major IEEE fp16 or bfloat16 (dtype GESPMM_X16_F16 / GESPMM_X16_BF16, one type per
+ * call); val [nnz], row_scale [M] and bias [N_out] are fp32. W_n and W_r are [out, in] as a linear layer stores them: no transposed copy.
+ *
+ *     H[r, c]   = narrow( row_scale[r] * (sum over p = rowptr[r] .. rowptr[r + 1] - 1, ascending, of val[p] * X[colind[p], c]) )
+ *     out[r, n] = narrow( sum_c H[r, c] W_n[n, c]  +  sum_c X_root[r, c] W_r[n, c]  +  bias[n] )
+ *
+ * H: one fp32 chain per element from +0 — fmaf(val[p], x, acc), or acc + x when val is NULL — exactly that of gespmm_csr_spmm_x16,
+ * then ONE fp32 multiply by row_scale (NULL: none) and ONE rounding to nearest even: H has the bits the 16-bit product returns. The
+ * two sums over c accumulate in fp32 on the matrix unit, in the hardware's order (not pinned; products of 16-bit numbers are exact in
+ * fp32); bias is one fp32 add (NULL: none) and the store rounds once. val, row_scale, bias may be NULL; X_root and W_r are NULL together
+ * or given together.
+ *
+ * Served by the kernel: K a multiple of 8 in 8 .. 256, N_out in 1 .. 256, every 16-bit array 16-byte aligned. One 256-thread workgroup
+ * per 64 rows; a hub row is walked by one lane group. No allocation, no host synchronisation: capturable.
+ * Checks, in this order: dtype -> GESPMM_EINVAL; a negative size -> GESPMM_EINVAL; M, Kn, nnz, M K, Kn K or M N_out > 2^31 - 4097 ->
+ * GESPMM_ERANGE; M == 0 or N_out == 0 -> 0; exactly one of X_root / W_r -> GESPMM_EINVAL; NULL rowptr, W_n or out (colind, X: when
+ * nnz != 0) -> GESPMM_EINVAL; an index or fp32 array not 4-byte, a 16-bit array not 2-byte aligned -> GESPMM_EALIGN; a 16-bit array
+ * not 16-byte aligned -> GESPMM_EINVAL; out overlapping an operand -> GESPMM_EINVAL; a K or N_out the kernel does not serve ->
+ * GESPMM_ERR_UNSUPPORTED with nothing launched (the composition — gespmm_csr_spmm_x16, then a dense linear — is the caller's).
+ * nnz == 0 still computes root + bias.
+ */
+int gespmm_csr_spmm_linear_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const void* X,
+                               const void* W_n, const void* X_root, const void* W_r, const float* bias, void* out, int dtype, int64_t M,
+                               int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream);
+/* Host only: 1 when the call above runs its kernel for these sizes, 0 when it answers GESPMM_ERR_UNSUPPORTED (or has nothing to do:
+ * M == 0, N_out == 0). align: the largest power of two (>= 2) dividing the address of every 16-bit array. The function the launch
+ * itself consults. Negative sizes, an align that is no power of two -> GESPMM_EINVAL; sizes past the limits -> GESPMM_ERANGE. */
+int gespmm_spmm_linear_route_x16(int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align);
+
 /* The variant `GESPMM_VARIANT_AUTO` resolves to for this shape (pure host logic). */
 int gespmm_select_variant(int64_t M, int64_t nnz, int64_t N);
 
