@@ -179,6 +179,8 @@ EXPORTS = [
     "gespmm_max_arg_route_x16",
     "gespmm_csr_spmm_linear_x16",
     "gespmm_spmm_linear_route_x16",
+    "gespmm_csr_spmm_relational_x16",
+    "gespmm_spmm_relational_route_x16",
     "gespmm_csr_spmm_heads_order_f32",
     "gespmm_csr_spmm_heads_order_x16",
     "gespmm_plan_spmm_heads_order_f32",
@@ -502,6 +504,10 @@ def _load():
     lib.gespmm_csr_spmm_linear_x16.argtypes = [p] * 10 + [c_int] + [c_int64] * 5 + [p]
     lib.gespmm_spmm_linear_route_x16.restype = c_int
     lib.gespmm_spmm_linear_route_x16.argtypes = [c_int64] * 5 + [c_int]
+    lib.gespmm_csr_spmm_relational_x16.restype = c_int
+    lib.gespmm_csr_spmm_relational_x16.argtypes = [p] * 10 + [c_int] + [c_int64] * 6 + [p]
+    lib.gespmm_spmm_relational_route_x16.restype = c_int
+    lib.gespmm_spmm_relational_route_x16.argtypes = [c_int64] * 6 + [c_int]
     lib.gespmm_gat_aggregate_route.restype = c_int
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
@@ -756,6 +762,22 @@ def csr_spmm_linear_x16(rowptr, colind, val, row_scale, X, W_n, X_root, W_r, bia
     ptrs = [ctypes.c_void_p(a) if a is not None else None for a in (rowptr, colind, val, row_scale, X, W_n, X_root, W_r, bias, out)]
     return lib.gespmm_csr_spmm_linear_x16(*ptrs, int(dtype), int(M), int(Kn), int(K), int(N_out), int(nnz),
                                           ctypes.c_void_p(stream) if stream is not None else None)
+
+
+def spmm_relational_route_x16(R, M, Kn, K, N_out, nnz, align=16):
+    """``spmm_linear_route_x16`` for gespmm_csr_spmm_relational_x16 on a stacked CSR of R relations x M rows: 1 the kernel, 0 the
+    composition is the caller's (``spmm.csr_spmm_relational_linear`` composes it), or there is nothing to do."""
+    rc = lib.gespmm_spmm_relational_route_x16(int(R), int(M), int(Kn), int(K), int(N_out), int(nnz), int(align))
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_spmm_relational_route_x16")
+    return rc
+
+
+def csr_spmm_relational_x16(rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out, dtype, R, M, Kn, K, N_out, nnz, stream=None):
+    """gespmm_csr_spmm_relational_x16 on raw addresses (ints or None), argument for argument; returns the C return code unchecked."""
+    ptrs = [ctypes.c_void_p(a) if a is not None else None for a in (rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out)]
+    return lib.gespmm_csr_spmm_relational_x16(*ptrs, int(dtype), int(R), int(M), int(Kn), int(K), int(N_out), int(nnz),
+                                              ctypes.c_void_p(stream) if stream is not None else None)
 
 
 def edge_dropout_bits(s0, s1, r, c, h):

@@ -35,6 +35,7 @@
 #include "sddmm_heads.h"
 #include "spmm_heads.h"
 #include "spmm_linear.h"
+#include "spmm_relational.h"
 #include "spmm_max_arg.h"
 #include "spmm_kernels.h"
 #include "workspace.h"
@@ -1103,6 +1104,52 @@ int gespmm_spmm_linear_route_x16(int64_t M, int64_t Kn, int64_t K, int64_t N_out
     const int rc = gespmm::spmm_linear_sizes(M, Kn, K, N_out, nnz);
     if (rc != 0) return rc;
     return gespmm::spmm_linear_served(M, Kn, K, N_out, nnz, align) ? 1 : 0;
+}
+
+/* The relational aggregate-and-linear on 16-bit features (gespmm.h; spmm_relational.hip): the argument ladder of the call above on a
+   stacked CSR of R M rows, ONE kernel or GESPMM_ERR_UNSUPPORTED. gespmm_spmm_relational_route_x16 answers from the function the launch
+   asks: spmm_relational_served. */
+int gespmm_csr_spmm_relational_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const void* X,
+                                   const void* W, const void* X_root, const void* W_root, const float* bias, void* out, int dtype,
+                                   int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream) {
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    if (rc != 0) return rc;
+    if (M == 0 || N_out == 0) return 0;
+    if ((X_root == nullptr) != (W_root == nullptr)) return GESPMM_EINVAL;
+    if ((rc = check_pointers({{rowptr, 4, true}, {W, 2, true}, {out, 2, true}, {colind, 4, nnz != 0}, {X, 2, nnz != 0}, {val, 4, false},
+                              {row_scale, 4, false}, {bias, 4, false}, {X_root, 2, false}, {W_root, 2, false}})) != 0)
+        return rc;
+    const int align = linear_x16_align({nnz != 0 ? X : nullptr, W, X_root, W_root, out});
+    if (align < 16) return GESPMM_EINVAL;  // (every 16-bit array is read or written 16 bytes at a time)
+    const uint64_t o_bytes = (uint64_t)M * (uint64_t)N_out * 2, w_bytes = (uint64_t)N_out * (uint64_t)K * 2;
+    if ((nnz != 0 && ranges_overlap(out, o_bytes, X, (uint64_t)Kn * (uint64_t)K * 2)) || ranges_overlap(out, o_bytes, W, (uint64_t)R * w_bytes) ||
+        (X_root && (ranges_overlap(out, o_bytes, X_root, (uint64_t)M * (uint64_t)K * 2) || ranges_overlap(out, o_bytes, W_root, w_bytes))))
+        return GESPMM_EINVAL;
+    if (!gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align)) return GESPMM_ERR_UNSUPPORTED;  // (nothing launched)
+    gespmm::SpmmRelationalArgs a = {};
+    a.rowptr = rowptr;
+    a.colind = colind;
+    a.val = nnz != 0 ? val : nullptr;
+    a.row_scale = row_scale;
+    a.X = static_cast<const float*>(X);  // (the 16-bit array seen as words: spmm_relational.h)
+    a.W = W;
+    a.Xroot = X_root;
+    a.Wroot = W_root;
+    a.bias = bias;
+    a.out = out;
+    a.R = (int32_t)R;
+    a.M = (int32_t)M;
+    a.K = (int32_t)K;
+    a.N_out = (int32_t)N_out;
+    return (int)gespmm::launch_spmm_relational_x16(a, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_spmm_relational_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align) {
+    if (align < 2 || (align & (align - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    if (rc != 0) return rc;
+    return gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align) ? 1 : 0;
 }
 
 int64_t gespmm_csr_spmm_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant,

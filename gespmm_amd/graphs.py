@@ -508,6 +508,16 @@ def transpose_csr(rowptr, colind, K=None, val=None, return_order=False):
     return out + (order,) if return_order else out
 
 
+def transpose_stacked_csr(rowptr, colind, R, Kn, val=None, return_order=False):
+    """Stacked CSC of a stacked CSR (R * M rows over Kn columns, row r * M + i: relation r, row i): R * Kn rows over M columns, row
+    r * Kn + j holding the rows i of relation r's entries (i, j) — ``transpose_csr`` of the block-diagonal form, relation by relation."""
+    M = (rowptr.numel() - 1) // R
+    rows = torch.repeat_interleave(torch.arange(R * M, device=rowptr.device), (rowptr[1:] - rowptr[:-1]).to(torch.int64))
+    out = transpose_csr(rowptr, (torch.div(rows, M, rounding_mode="floor") * Kn + colind).to(torch.int32), K=R * Kn, val=val, return_order=True)
+    out = (out[0], (out[1] % M).to(torch.int32)) + out[2:]
+    return out if return_order else out[:-1]
+
+
 def reference_B(K, N, seed=1, device="cpu"):
     """Dense operand with the reference driver's value set, float(r % 100 - 50) / 100
     (spmm_test.cu:586-594), from a seeded torch generator instead of libc rand()."""

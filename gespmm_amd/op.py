@@ -1367,3 +1367,123 @@ class SAGEConv(torch.nn.Module):
 
     def __repr__(self):
         return "%s(%d, %d, %s)" % (type(self).__name__, self.in_feats, self.out_feats, self.aggregator_type)
+
+
+class RelationalLinearFunction(torch.autograd.Function):
+    """out = narrow(sum_r narrow(row_scale_r * (A_r @ x)) @ weight[r].T + root @ root_weight.T + bias) on a stacked CSR
+    (``spmm.csr_spmm_relational_linear``: on fp16 / bf16 features ONE kernel, every relation's aggregate of a 64-row block through one
+    LDS tile into the same matrix-unit accumulators; neither the [R, M, K] aggregates nor the [R, Kn, N_out] transforms exist).
+
+        RelationalLinearFunction.apply(rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias,
+                                       values_csr=None, values_csc=None, fused=True)
+
+    ``rowptr`` / ``colind``: the stacked CSR, R * M rows over Kn columns (row r * M + i: relation r, row i). ``colptr`` / ``rowind``: the
+    stacked CSC, R * Kn rows over M columns (row r * Kn + j holds the rows i of relation r's entries (i, j)); ``weight`` [R, N_out, K];
+    ``row_scale`` fp32 [R * M] or None; edge weights fp32 in both orders, no gradient. It saves only its inputs. The backward:
+    grad_x = sum_r (A_r^T g'_r) @ weight[r] with g'_r = row_scale_r * grad_out is the SAME op on the stacked CSC arrays, with
+    dense = grad_out, weight = weight.transpose(1, 2) (R K N_out elements, copied) and the per-entry fp32 weights
+    row_scale[r * M + rowind[e]] (times values_csc) — ONE fp32 [nnz] array made by ``index_select`` in the backward, only when
+    ``row_scale`` is given. grad_weight[r] = grad_out^T @ H_r recomputes the [R * M, K] stack of aggregates with the existing product:
+    that transient exists in the backward only. Root and bias gradients as in ``SpmmLinearFunction``. ``fused=False``: both products take the
+    composition. Once differentiable."""
+
+    @staticmethod
+    def forward(ctx, rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias, values_csr=None, values_csc=None, fused=True):
+        if values_csr is not None and values_csc is None and (x.requires_grad or weight.requires_grad):
+            raise RuntimeError("the backward of RelationalLinearFunction (grad_x, grad_weight) needs the edge weights in CSC order too: values_csc")
+        x, weight = x.contiguous(), weight.contiguous()
+        if root is not None:
+            root, root_weight = root.contiguous(), root_weight.contiguous()
+        out = _spmm.csr_spmm_relational_linear(rowptr, colind, values_csr, x, weight, row_scale=row_scale, root=root,
+                                               root_weight=root_weight, bias=None if bias is None else bias.detach(), fused=fused)
+        ctx.save_for_backward(rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, values_csr, values_csc)
+        ctx.fused = fused
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, values_csr, values_csc = ctx.saved_tensors
+        grad_out = grad_out.contiguous()
+        need = ctx.needs_input_grad
+        R, N_out, K = weight.shape
+        M, Kn = grad_out.shape[0], x.shape[0]
+        grad_x = grad_w = grad_root = grad_rw = grad_bias = None
+        if need[4]:
+            w_csc = values_csc
+            if row_scale is not None:  # the scale of (relation, row) as a weight of the entry: CSC row r Kn + j is of relation r
+                rel = torch.repeat_interleave(torch.arange(R * Kn, device=colptr.device) // Kn, torch.diff(colptr), output_size=rowind.numel())
+                w_csc = row_scale.index_select(0, rel * M + rowind)
+                if values_csc is not None:
+                    w_csc = w_csc * values_csc
+            grad_x = _spmm.csr_spmm_relational_linear(colptr, rowind, w_csc, grad_out, weight.transpose(1, 2).contiguous(), fused=ctx.fused)
+        if need[5]:
+            H = _spmm.stacked_aggregate(rowptr, colind, values_csr, x, row_scale)
+            grad_w = torch.matmul(grad_out.t().unsqueeze(0), H.view(R, M, K))
+        if root is not None and need[7]:
+            grad_root = grad_out @ root_weight
+        if root is not None and need[8]:
+            grad_rw = grad_out.t() @ root
+        if ctx.bias_dtype is not None and need[9]:
+            grad_bias = grad_out.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+        return None, None, None, None, grad_x, grad_w, None, grad_root, grad_rw, grad_bias, None, None, None
+
+
+class RGCNConv(torch.nn.Module):
+    """Relational graph convolution (Schlichtkrull et al., 2018) with the constructor of DGL's ``RelGraphConv``:
+
+        out[i] = sum_r c_{i,r} (sum over the r-edges (i, j) of x[j]) @ W_r^T + x[i] @ W_0^T + b
+
+    ``forward(x, rowptr, colind, colptr, rowind)`` takes the stacked CSR (``num_rels * M`` rows over the nodes: relation r's row i is
+    row r * M + i, ``graphs.coo_to_csr(R * M, Kn, etype * M + row, col)``) and the stacked CSC (``graphs.transpose_stacked_csr``).
+    ``norm="right"``: c_{i,r} = 1 / (entries of row r * M + i), 0 for rows without entries; ``norm=None``: the plain sum.
+    ``num_bases=B``: W_r = sum_b coeff[r, b] V_b, formed per forward by one small matmul and differentiated by torch.
+    ``self_loop`` is the root term W_0 (it needs a square graph). One ``RelationalLinearFunction`` call: fp32 tensors take its
+    composition, fp16 / bf16 tensors (a ``.half()`` / ``.bfloat16()`` layer, or autocast) the kernel where the route serves the shape."""
+
+    def __init__(self, in_feats, out_feats, num_rels, num_bases=None, bias=True, self_loop=True, norm="right", activation=None, fused=True):
+        super().__init__()
+        self.fused = bool(fused)
+        if norm not in ("right", None):
+            raise ValueError("norm must be 'right' or None, got %r" % (norm,))
+        if num_rels < 1 or (num_bases is not None and num_bases < 1):
+            raise ValueError("num_rels and num_bases must be >= 1")
+        self.in_feats, self.out_feats, self.num_rels, self.num_bases = in_feats, out_feats, num_rels, num_bases
+        self.norm, self.activation = norm, activation
+        self.weight = torch.nn.Parameter(torch.empty(num_bases or num_rels, out_feats, in_feats))
+        self.coeff = torch.nn.Parameter(torch.empty(num_rels, num_bases)) if num_bases else None
+        self.loop_weight = torch.nn.Parameter(torch.empty(out_feats, in_feats)) if self_loop else None
+        self.bias = torch.nn.Parameter(torch.zeros(out_feats)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        for w in self.weight:
+            torch.nn.init.xavier_uniform_(w, gain=gain)
+        if self.coeff is not None:
+            torch.nn.init.xavier_uniform_(self.coeff, gain=gain)
+        if self.loop_weight is not None:
+            torch.nn.init.xavier_uniform_(self.loop_weight, gain=gain)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x, rowptr, colind, colptr, rowind):
+        R = self.num_rels
+        if x.dim() != 2 or (rowptr.numel() - 1) % R != 0 or colptr.numel() - 1 != R * x.shape[0]:
+            raise ValueError("RGCNConv needs a stacked CSR of num_rels * M rows and a stacked CSC of num_rels * %d rows" % x.shape[0])
+        M = (rowptr.numel() - 1) // R
+        if self.loop_weight is not None and M != x.shape[0]:
+            raise ValueError("self_loop=True needs a square graph: M = %d rows, x has %d" % (M, x.shape[0]))
+        weight = self.weight if self.coeff is None else (self.coeff @ self.weight.view(self.num_bases, -1)).view(R, self.out_feats, self.in_feats)
+        scale = None
+        if self.norm == "right":
+            degree = torch.diff(rowptr).to(torch.float32)
+            scale = torch.where(degree > 0, 1 / degree, torch.zeros_like(degree))
+        loop = None if self.loop_weight is None else self.loop_weight.to(x.dtype)
+        out = RelationalLinearFunction.apply(rowptr, colind, colptr, rowind, x, weight.to(x.dtype), scale, None if loop is None else x, loop,
+                                             None if self.bias is None else self.bias.float(), None, None, self.fused)
+        return out if self.activation is None else self.activation(out)
+
+    def __repr__(self):
+        return "%s(%d, %d, num_rels=%d)" % (type(self).__name__, self.in_feats, self.out_feats, self.num_rels)

@@ -937,6 +937,97 @@ def csr_spmm_linear(rowptr, colind, values, dense, weight, row_scale=None, root=
     return result.copy_(acc)
 
 
+def stacked_aggregate(rowptr, colind, values, dense, row_scale=None):
+    """narrow(row_scale * (A @ dense)) for every row of a (stacked) CSR with the existing products, in the dtype of ``dense``: the
+    [R * M, K] stack of per-relation aggregates that ``csr_spmm_relational_linear`` never forms. A 16-bit width the 16-bit kernels do
+    not serve (an odd K, say) goes through the fp32 product on the widened ``dense``, narrowed once: the bits of the 16-bit entry's own
+    composition, without its scratch allocation, so a captured step stays capturable."""
+    dt = dense.dtype
+    if row_scale is not None:
+        return csr_spmm_fused(rowptr, colind, values, dense.float(), row_scale=row_scale).to(dt)
+    if dt in _X16 and lib.gespmm_x16_route(rowptr.numel() - 1, dense.shape[0], dense.shape[1], colind.numel(), _lib.VARIANT_AUTO,
+                                           x16_align(dense), 16) not in (1, 2):
+        dense = dense.float()
+    return (csr_spmm_no_edge_value(rowptr, colind, dense) if values is None else csr_spmm(rowptr, colind, values, dense)).to(dt)
+
+
+def csr_spmm_relational_linear(rowptr, colind, values, dense, weight, row_scale=None, root=None, root_weight=None, bias=None, out=None,
+                               fused=True):
+    """A relational graph convolution (RGCN) in ONE kernel on 16-bit features (gespmm_csr_spmm_relational_x16):
+
+        H_r = narrow(row_scale[r M : (r + 1) M, None] * (A_r @ dense))             per relation, the 16-bit product's bits
+        out = narrow(sum_r H_r @ weight[r].T + root @ root_weight.T + bias)        fp32 sums on the matrix unit, one rounding
+
+    The graph is a STACKED CSR: relation r's row i is row ``r * M + i`` of one ordinary CSR with R * M rows over Kn columns —
+    ``graphs.coo_to_csr(R * M, Kn, etype * M + row, col)`` builds it, ``rowptr`` is int32 [R * M + 1], ``values`` fp32 [nnz] or None
+    and ``row_scale`` fp32 [R * M] or None. Being a plain CSR, the existing product on it (``csr_spmm`` / ``csr_spmm_no_edge_value`` /
+    ``csr_spmm_fused``) returns the [R * M, K] stack of every H_r: that is the composition route here and what the kernel's bits are checked against,
+    in which no H_r and no per-relation transform ever reaches memory. ``weight`` is [R, N_out, K] (R is read from it), ``dense``
+    [Kn, K], ``root`` [M, K] with ``root_weight`` [N_out, K] (together or not at all), ``bias`` fp32 [N_out].
+
+    16-bit ``dense`` takes the kernel where ``_lib.spmm_relational_route_x16`` answers 1 (K % 8 == 0, 8 <= K <= 256, N_out <= 256,
+    16-byte aligned tensors). Everything else — fp32 ``dense`` (all tensors fp32), an odd K, a wide layer, a 2-byte offset — is
+    composed: the product on the stacked arrays, one fp32 matmul of the [M, R K] regrouped aggregate, root and bias in fp32, rounded
+    once for a 16-bit result. The call never fails on shape. ``fused=False`` takes the composition whatever the shape (measurements)."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    dt = dense.dtype
+    if dt not in _X16 and dt != torch.float32:
+        raise TypeError("dense must be torch.float16, torch.bfloat16 or torch.float32, got %s" % dt)
+    _need(dense, "dense", dt, 2)
+    _need(weight, "weight", dt, 3)
+    if (root is None) != (root_weight is None):
+        raise ValueError("root and root_weight come together or not at all")
+    R, N_out = weight.shape[0], weight.shape[1]
+    Kn, K = dense.shape
+    if weight.shape[2] != K:
+        raise ValueError("weight must be [R, N_out, %d]" % K)
+    rows = rowptr.numel() - 1
+    if rows < 0 or (R == 0 and rows != 0) or (R != 0 and rows % R != 0):
+        raise ValueError("rowptr must have R * M + 1 entries for the R = %d relations of weight" % R)
+    M = rows // R if R else (root.shape[0] if root is not None else 0)
+    others = [weight]
+    if root is not None:
+        _need(root, "root", dt, 2)
+        _need(root_weight, "root_weight", dt, 2)
+        if tuple(root.shape) != (M, K) or tuple(root_weight.shape) != (N_out, K):
+            raise ValueError("root must be [%d, %d] and root_weight [%d, %d]" % (M, K, N_out, K))
+        others += [root, root_weight]
+    if values is not None:
+        _need(values, "values", torch.float32, 1)
+        if values.numel() != colind.numel():
+            raise ValueError("values and colind must have the same length")
+        others.append(values)
+    if isinstance(bias, torch.Tensor) and bias.dtype in _X16:
+        bias = bias.float()
+    for t, name, n in ((row_scale, "row_scale", R * M), (bias, "bias", N_out)):
+        if t is not None:
+            _need(t, name, torch.float32, 1)
+            if t.numel() != n:
+                raise ValueError("%s must have %d entries, got %d" % (name, n, t.numel()))
+            others.append(t)
+    dev = _same_device(dense, rowptr, colind, *others)
+    inputs = (dense, weight) + ((root, root_weight) if root is not None else ())
+    result = torch.empty((M, N_out), dtype=dt, device=dev) if out is None else _result(out, "out", dt, (M, N_out), dev, inputs)
+    nnz = colind.numel()
+    if fused and dt in _X16 and _lib.spmm_relational_route_x16(R, M, Kn, K, N_out, nnz,
+                                                               x16_align(dense if nnz else None, weight, root, root_weight, result)) == 1:
+        with _on_device(dev):
+            rc = lib.gespmm_csr_spmm_relational_x16(_ptr(rowptr), _ptr(colind), _optr(values), _optr(row_scale), _ptr(dense), _ptr(weight),
+                                                    _optr(root), _optr(root_weight), _optr(bias), _ptr(result), _X16[dt], R, M, Kn, K,
+                                                    N_out, nnz, _stream(dev))
+        check(rc, "gespmm_csr_spmm_relational_x16")
+        return result
+    # the composition: the product on the stacked CSR as it stands ([R M, K]), its relations side by side ([M, R K]) against
+    # weight as [N_out, R K] in fp32, root and bias in fp32, one rounding
+    h = stacked_aggregate(rowptr, colind, values, dense, row_scale)
+    acc = torch.nn.functional.linear(h.view(R, M, K).transpose(0, 1).reshape(M, R * K).float(),
+                                     weight.transpose(0, 1).reshape(N_out, R * K).float(), bias)
+    if root is not None:
+        acc = acc + torch.nn.functional.linear(root.float(), root_weight.float())
+    return result.copy_(acc)
+
+
 def csr2csc(rowptr, colind, colptr, rowind, csr_data):
     """Fill ``colptr`` / ``rowind`` in place with the CSC form of CSR(rowptr, colind)
     and return the values in CSC order. Mirrors spmm.cpp:70-93 (whose CUDA

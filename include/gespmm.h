@@ -246,6 +246,28 @@ int gespmm_csr_spmm_linear_x16(const int32_t* rowptr, const int32_t* colind, con
  * itself consults. Negative sizes, an align that is no power of two -> GESPMM_EINVAL; sizes past the limits -> GESPMM_ERANGE. */
 int gespmm_spmm_linear_route_x16(int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align);
 
+/*
+ * Relational aggregate-and-linear on 16-bit features: an RGCN layer in one kernel. The graph is a STACKED CSR — relation r's row i is
+ * row r M + i of one ordinary CSR with R M rows over Kn columns (rowptr [R M + 1], colind / val [nnz], row_scale [R M]) — so
+ * gespmm_csr_spmm_x16 on the same arrays returns every per-relation aggregate H_r; that is the composition route and the bit oracle.
+ * W is [R, N_out, K], W_root [N_out, K], X [Kn, K], X_root [M, K], out [M, N_out], row-major fp16 or bfloat16, one type per call.
+ *
+ *     H_r[i, c] = narrow( row_scale[r M + i] * (sum over p = rowptr[r M + i] .. rowptr[r M + i + 1] - 1, ascending, of val[p] * X[colind[p], c]) )
+ *     out[i, n] = narrow( sum_r sum_c H_r[i, c] W[r, n, c]  +  sum_c X_root[i, c] W_root[n, c]  +  bias[n] )
+ *
+ * H_r has the arithmetic of gespmm_csr_spmm_linear_x16's H (one fp32 chain from +0, one fp32 multiply, ONE rounding) and exists only
+ * as one 64-row LDS tile at a time; all relations accumulate into the same matrix-unit accumulators in fp32, in the hardware's order;
+ * bias is one fp32 add and the store rounds once. A 64-row block without an entry of relation r skips that relation entirely.
+ * Served by the kernel: R >= 1, K a multiple of 8 in 8 .. 256, N_out in 1 .. 256, every 16-bit array 16-byte aligned. No allocation, no
+ * host synchronisation: capturable. Checks, in this order, are those of gespmm_csr_spmm_linear_x16 with the size limits on R M, Kn,
+ * nnz, R M K, Kn K, M N_out and R N_out K (each <= 2^31 - 4097, else GESPMM_ERANGE); R == 0 is a shape that is not served.
+ */
+int gespmm_csr_spmm_relational_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const void* X,
+                                   const void* W, const void* X_root, const void* W_root, const float* bias, void* out, int dtype,
+                                   int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream);
+/* Host only: gespmm_spmm_linear_route_x16 for the call above. */
+int gespmm_spmm_relational_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align);
+
 /* The variant `GESPMM_VARIANT_AUTO` resolves to for this shape (pure host logic). */
 int gespmm_select_variant(int64_t M, int64_t nnz, int64_t N);
 
