@@ -4,6 +4,7 @@
     python examples/rgcn_custom.py --dataset pubmed --num-rels 4
     python examples/rgcn_custom.py --dataset cora --num-rels 16 --num-bases 4 --dtype bf16    # each layer ONE relational kernel
     python examples/rgcn_custom.py --dtype bf16 --graph-capture                               # replay each step from a HIP graph
+    python examples/rgcn_custom.py --dtype bf16 --fused-weight-grad                           # the weights' gradient without the [R M, K] aggregates
 
 The data path is examples/gcn_custom.py's (the bundled adjacency matrices or the synthetic stand-ins, random features). Every edge
 gets one of ``--num-rels`` types by a seeded rule (``--skew``: half of the relations share 5 % of the edges). The labels are those of
@@ -47,11 +48,11 @@ def stacked_graph(row, col, etype, num_rels, n_v):
 
 
 class RGCN(torch.nn.Module):
-    def __init__(self, g, in_feats, n_hidden, n_classes, num_rels, num_bases, fused=True):
+    def __init__(self, g, in_feats, n_hidden, n_classes, num_rels, num_bases, fused=True, fused_weight_grad=False):
         super().__init__()
         self.g = g
-        self.conv1 = RGCNConv(in_feats, n_hidden, num_rels, num_bases=num_bases, activation=F.relu, fused=fused)
-        self.conv2 = RGCNConv(n_hidden, n_classes, num_rels, num_bases=num_bases, fused=fused)
+        self.conv1 = RGCNConv(in_feats, n_hidden, num_rels, num_bases=num_bases, activation=F.relu, fused=fused, fused_weight_grad=fused_weight_grad)
+        self.conv2 = RGCNConv(n_hidden, n_classes, num_rels, num_bases=num_bases, fused=fused, fused_weight_grad=fused_weight_grad)
 
     def forward(self, features):
         return self.conv2(self.conv1(features, *self.g), *self.g)
@@ -70,6 +71,7 @@ def main():
     ap.add_argument("--skew", action="store_true", help="half of the relations hold 5 %% of the edges")
     ap.add_argument("--dtype", choices=("fp32", "fp16", "bf16"), default="fp32")
     ap.add_argument("--composition", action="store_true", help="16-bit layers compose the product and the matmul instead of the kernel")
+    ap.add_argument("--fused-weight-grad", action="store_true", help="16-bit layers take the weights' gradient from the fused kernel")
     ap.add_argument("--graph-capture", action="store_true", help="capture one training step in a HIP graph")
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
@@ -99,7 +101,8 @@ def main():
     print("nodes %d  edges %d  relations %d (entries per stacked row %.2f)  classes %d  train %d  test %d"
           % (n_v, g[1].numel(), args.num_rels, g[1].numel() / (args.num_rels * n_v), n_cls, n_train, idx["test"].numel()))
 
-    model = RGCN(g, n_feat, args.n_hidden, n_cls, args.num_rels, args.num_bases, fused=not args.composition).to(device)
+    model = RGCN(g, n_feat, args.n_hidden, n_cls, args.num_rels, args.num_bases, fused=not args.composition,
+                 fused_weight_grad=args.fused_weight_grad).to(device)
     if args.dtype != "fp32":
         dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype]
         model, features = model.to(dtype), features.to(dtype)
@@ -139,8 +142,8 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     if args.n_epochs > 3:
-        print("gpu %.3f ms/epoch over %d epochs (dtype=%s, composition=%s, graph_capture=%s)"
-              % (e0.elapsed_time(e1) / (args.n_epochs - 3), args.n_epochs - 3, args.dtype, args.composition, args.graph_capture))
+        print("gpu %.3f ms/epoch over %d epochs (dtype=%s, composition=%s, fused_weight_grad=%s, graph_capture=%s)"
+              % (e0.elapsed_time(e1) / (args.n_epochs - 3), args.n_epochs - 3, args.dtype, args.composition, args.fused_weight_grad, args.graph_capture))
     with torch.no_grad():
         pred = model(features).index_select(0, idx["test"]).max(1)[1]
     print("Test Accuracy {:.4f} (seed {}, {})".format(pred.eq(labels[idx["test"]]).float().mean().item(), args.seed, args.dtype))

@@ -181,6 +181,9 @@ EXPORTS = [
     "gespmm_spmm_linear_route_x16",
     "gespmm_csr_spmm_relational_x16",
     "gespmm_spmm_relational_route_x16",
+    "gespmm_csr_spmm_relational_wgrad_x16",
+    "gespmm_spmm_relational_wgrad_route_x16",
+    "gespmm_spmm_relational_wgrad_chunks",
     "gespmm_csr_spmm_heads_order_f32",
     "gespmm_csr_spmm_heads_order_x16",
     "gespmm_plan_spmm_heads_order_f32",
@@ -508,6 +511,12 @@ def _load():
     lib.gespmm_csr_spmm_relational_x16.argtypes = [p] * 10 + [c_int] + [c_int64] * 6 + [p]
     lib.gespmm_spmm_relational_route_x16.restype = c_int
     lib.gespmm_spmm_relational_route_x16.argtypes = [c_int64] * 6 + [c_int]
+    lib.gespmm_csr_spmm_relational_wgrad_x16.restype = c_int
+    lib.gespmm_csr_spmm_relational_wgrad_x16.argtypes = [p] * 8 + [c_int] + [c_int64] * 7 + [p]
+    lib.gespmm_spmm_relational_wgrad_route_x16.restype = c_int
+    lib.gespmm_spmm_relational_wgrad_route_x16.argtypes = [c_int64] * 7 + [c_int]
+    lib.gespmm_spmm_relational_wgrad_chunks.restype = c_int64
+    lib.gespmm_spmm_relational_wgrad_chunks.argtypes = [c_int64] * 4
     lib.gespmm_gat_aggregate_route.restype = c_int
     lib.gespmm_gat_aggregate_route.argtypes = [c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, p]
     lib.gespmm_describe_edge_softmax.restype = c_int
@@ -778,6 +787,31 @@ def csr_spmm_relational_x16(rowptr, colind, val, row_scale, X, W, X_root, W_root
     ptrs = [ctypes.c_void_p(a) if a is not None else None for a in (rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out)]
     return lib.gespmm_csr_spmm_relational_x16(*ptrs, int(dtype), int(R), int(M), int(Kn), int(K), int(N_out), int(nnz),
                                               ctypes.c_void_p(stream) if stream is not None else None)
+
+
+def spmm_relational_wgrad_chunks(R, M, K, N_out):
+    """The chunk count gespmm_spmm_relational_wgrad_chunks suggests for the fused relational weight gradient (0: a size is 0)."""
+    rc = int(lib.gespmm_spmm_relational_wgrad_chunks(int(R), int(M), int(K), int(N_out)))
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_spmm_relational_wgrad_chunks")
+    return rc
+
+
+def spmm_relational_wgrad_route_x16(R, M, Kn, K, N_out, nnz, chunks, align=16):
+    """``spmm_relational_route_x16`` for gespmm_csr_spmm_relational_wgrad_x16 with ``chunks`` row chunks: 1 the kernels, 0 the
+    composition is the caller's (``spmm.csr_spmm_relational_weight_grad`` composes it)."""
+    rc = lib.gespmm_spmm_relational_wgrad_route_x16(int(R), int(M), int(Kn), int(K), int(N_out), int(nnz), int(chunks), int(align))
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_spmm_relational_wgrad_route_x16")
+    return rc
+
+
+def csr_spmm_relational_wgrad_x16(rowptr, colind, val, row_scale, X, grad_out, partials, grad_W, dtype, R, M, Kn, K, N_out, nnz, chunks,
+                                  stream=None):
+    """gespmm_csr_spmm_relational_wgrad_x16 on raw addresses (ints or None), argument for argument; returns the C return code unchecked."""
+    ptrs = [ctypes.c_void_p(a) if a is not None else None for a in (rowptr, colind, val, row_scale, X, grad_out, partials, grad_W)]
+    return lib.gespmm_csr_spmm_relational_wgrad_x16(*ptrs, int(dtype), int(R), int(M), int(Kn), int(K), int(N_out), int(nnz), int(chunks),
+                                                    ctypes.c_void_p(stream) if stream is not None else None)
 
 
 def edge_dropout_bits(s0, s1, r, c, h):

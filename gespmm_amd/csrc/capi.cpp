@@ -36,6 +36,7 @@
 #include "spmm_heads.h"
 #include "spmm_linear.h"
 #include "spmm_relational.h"
+#include "spmm_relational_wgrad.h"
 #include "spmm_max_arg.h"
 #include "spmm_kernels.h"
 #include "workspace.h"
@@ -1150,6 +1151,59 @@ int gespmm_spmm_relational_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K
     const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
     if (rc != 0) return rc;
     return gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align) ? 1 : 0;
+}
+
+/* The fused relational weight gradient on 16-bit features (gespmm.h; spmm_relational_wgrad.hip): grad_W[r] = grad_out^T @ H_r over the
+   same stacked CSR, two launches (the chunks' partials, then their sum) or GESPMM_ERR_UNSUPPORTED. The workspace is the caller's.
+   gespmm_spmm_relational_wgrad_route_x16 answers from the function the launch asks: spmm_relational_wgrad_served. */
+int gespmm_csr_spmm_relational_wgrad_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const void* X,
+                                         const void* grad_out, float* partials, void* grad_W, int dtype, int64_t R, int64_t M, int64_t Kn,
+                                         int64_t K, int64_t N_out, int64_t nnz, int64_t chunks, void* stream) {
+    if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
+    int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    if (rc != 0) return rc;
+    if (R == 0 || N_out == 0 || K == 0) return 0;  // (an empty result)
+    if ((rc = check_pointers({{rowptr, 4, true}, {grad_out, 2, M != 0}, {partials, 4, true}, {grad_W, 2, true}, {colind, 4, nnz != 0},
+                              {X, 2, nnz != 0}, {val, 4, false}, {row_scale, 4, false}})) != 0)
+        return rc;
+    const int align = linear_x16_align({nnz != 0 ? X : nullptr, grad_out, grad_W, partials});
+    if (align < 16) return GESPMM_EINVAL;  // (every 16-bit array and the workspace are read or written 16 or 8 bytes at a time)
+    const uint64_t w_bytes = (uint64_t)R * (uint64_t)N_out * (uint64_t)K * 2, g_bytes = (uint64_t)M * (uint64_t)N_out * 2;
+    const uint64_t x_bytes = nnz != 0 ? (uint64_t)Kn * (uint64_t)K * 2 : 0;
+    if (!gespmm::spmm_relational_wgrad_served(R, M, Kn, K, N_out, nnz, chunks, align)) return GESPMM_ERR_UNSUPPORTED;  // (nothing launched)
+    const uint64_t p_bytes = (uint64_t)chunks * w_bytes * 2;
+    if ((x_bytes != 0 && (ranges_overlap(grad_W, w_bytes, X, x_bytes) || ranges_overlap(partials, p_bytes, X, x_bytes))) ||
+        ranges_overlap(grad_W, w_bytes, grad_out, g_bytes) || ranges_overlap(partials, p_bytes, grad_out, g_bytes) ||
+        ranges_overlap(partials, p_bytes, grad_W, w_bytes))
+        return GESPMM_EINVAL;
+    gespmm::SpmmRelationalWgradArgs a = {};
+    a.rowptr = rowptr;
+    a.colind = colind;
+    a.val = nnz != 0 ? val : nullptr;
+    a.row_scale = row_scale;
+    a.X = static_cast<const float*>(X);  // (the 16-bit array seen as words: spmm_relational.h)
+    a.grad_out = grad_out;
+    a.partials = partials;
+    a.grad_w = grad_W;
+    a.R = (int32_t)R;
+    a.M = (int32_t)M;
+    a.K = (int32_t)K;
+    a.N_out = (int32_t)N_out;
+    a.C = (int32_t)chunks;
+    return (int)gespmm::launch_spmm_relational_wgrad_x16(a, dtype, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_spmm_relational_wgrad_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int64_t chunks, int align) {
+    if (align < 2 || (align & (align - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    if (rc != 0) return rc;
+    return gespmm::spmm_relational_wgrad_served(R, M, Kn, K, N_out, nnz, chunks, align) ? 1 : 0;
+}
+
+int64_t gespmm_spmm_relational_wgrad_chunks(int64_t R, int64_t M, int64_t K, int64_t N_out) {
+    const int rc = gespmm::spmm_relational_sizes(R, M, 0, K, N_out, 0);
+    if (rc != 0) return rc;
+    return gespmm::spmm_relational_wgrad_chunks(R, M, K, N_out);
 }
 
 int64_t gespmm_csr_spmm_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t nnz, int variant,

@@ -1375,7 +1375,7 @@ class RelationalLinearFunction(torch.autograd.Function):
     LDS tile into the same matrix-unit accumulators; neither the [R, M, K] aggregates nor the [R, Kn, N_out] transforms exist).
 
         RelationalLinearFunction.apply(rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias,
-                                       values_csr=None, values_csc=None, fused=True)
+                                       values_csr=None, values_csc=None, fused=True, fused_weight_grad=False)
 
     ``rowptr`` / ``colind``: the stacked CSR, R * M rows over Kn columns (row r * M + i: relation r, row i). ``colptr`` / ``rowind``: the
     stacked CSC, R * Kn rows over M columns (row r * Kn + j holds the rows i of relation r's entries (i, j)); ``weight`` [R, N_out, K];
@@ -1384,11 +1384,14 @@ class RelationalLinearFunction(torch.autograd.Function):
     dense = grad_out, weight = weight.transpose(1, 2) (R K N_out elements, copied) and the per-entry fp32 weights
     row_scale[r * M + rowind[e]] (times values_csc) — ONE fp32 [nnz] array made by ``index_select`` in the backward, only when
     ``row_scale`` is given. grad_weight[r] = grad_out^T @ H_r recomputes the [R * M, K] stack of aggregates with the existing product:
-    that transient exists in the backward only. Root and bias gradients as in ``SpmmLinearFunction``. ``fused=False``: both products take the
-    composition. Once differentiable."""
+    that transient exists in the backward only — unless ``fused_weight_grad=True``: then grad_weight is
+    ``spmm.csr_spmm_relational_weight_grad``, on fp16 / bf16 features two kernels that reduce grad_out^T @ H_r over the rows on the
+    matrix unit with H_r in LDS alone, and the transient is an fp32 workspace of chunks * R * N_out * K elements. Root and bias
+    gradients as in ``SpmmLinearFunction``. ``fused=False``: both products take the composition. Once differentiable."""
 
     @staticmethod
-    def forward(ctx, rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias, values_csr=None, values_csc=None, fused=True):
+    def forward(ctx, rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias, values_csr=None, values_csc=None, fused=True,
+                fused_weight_grad=False):
         if values_csr is not None and values_csc is None and (x.requires_grad or weight.requires_grad):
             raise RuntimeError("the backward of RelationalLinearFunction (grad_x, grad_weight) needs the edge weights in CSC order too: values_csc")
         x, weight = x.contiguous(), weight.contiguous()
@@ -1398,6 +1401,7 @@ class RelationalLinearFunction(torch.autograd.Function):
                                                root_weight=root_weight, bias=None if bias is None else bias.detach(), fused=fused)
         ctx.save_for_backward(rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, values_csr, values_csc)
         ctx.fused = fused
+        ctx.fused_weight_grad = fused_weight_grad
         ctx.bias_dtype = None if bias is None else bias.dtype
         return out
 
@@ -1418,7 +1422,9 @@ class RelationalLinearFunction(torch.autograd.Function):
                 if values_csc is not None:
                     w_csc = w_csc * values_csc
             grad_x = _spmm.csr_spmm_relational_linear(colptr, rowind, w_csc, grad_out, weight.transpose(1, 2).contiguous(), fused=ctx.fused)
-        if need[5]:
+        if need[5] and ctx.fused_weight_grad:
+            grad_w = _spmm.csr_spmm_relational_weight_grad(rowptr, colind, values_csr, x, grad_out, R, row_scale=row_scale, fused=ctx.fused)
+        elif need[5]:
             H = _spmm.stacked_aggregate(rowptr, colind, values_csr, x, row_scale)
             grad_w = torch.matmul(grad_out.t().unsqueeze(0), H.view(R, M, K))
         if root is not None and need[7]:
@@ -1427,7 +1433,7 @@ class RelationalLinearFunction(torch.autograd.Function):
             grad_rw = grad_out.t() @ root
         if ctx.bias_dtype is not None and need[9]:
             grad_bias = grad_out.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        return None, None, None, None, grad_x, grad_w, None, grad_root, grad_rw, grad_bias, None, None, None
+        return None, None, None, None, grad_x, grad_w, None, grad_root, grad_rw, grad_bias, None, None, None, None
 
 
 class RGCNConv(torch.nn.Module):
@@ -1440,11 +1446,15 @@ class RGCNConv(torch.nn.Module):
     ``norm="right"``: c_{i,r} = 1 / (entries of row r * M + i), 0 for rows without entries; ``norm=None``: the plain sum.
     ``num_bases=B``: W_r = sum_b coeff[r, b] V_b, formed per forward by one small matmul and differentiated by torch.
     ``self_loop`` is the root term W_0 (it needs a square graph). One ``RelationalLinearFunction`` call: fp32 tensors take its
-    composition, fp16 / bf16 tensors (a ``.half()`` / ``.bfloat16()`` layer, or autocast) the kernel where the route serves the shape."""
+    composition, fp16 / bf16 tensors (a ``.half()`` / ``.bfloat16()`` layer, or autocast) the kernel where the route serves the shape.
+    ``fused_weight_grad=True`` (opt-in): the backward takes the gradient of W_r from ``spmm.csr_spmm_relational_weight_grad`` and never
+    forms the [num_rels * M, in_feats] stack of aggregates; with bases the gradient still reaches ``coeff`` / ``weight`` through torch."""
 
-    def __init__(self, in_feats, out_feats, num_rels, num_bases=None, bias=True, self_loop=True, norm="right", activation=None, fused=True):
+    def __init__(self, in_feats, out_feats, num_rels, num_bases=None, bias=True, self_loop=True, norm="right", activation=None, fused=True,
+                 fused_weight_grad=False):
         super().__init__()
         self.fused = bool(fused)
+        self.fused_weight_grad = bool(fused_weight_grad)
         if norm not in ("right", None):
             raise ValueError("norm must be 'right' or None, got %r" % (norm,))
         if num_rels < 1 or (num_bases is not None and num_bases < 1):
@@ -1482,7 +1492,7 @@ class RGCNConv(torch.nn.Module):
             scale = torch.where(degree > 0, 1 / degree, torch.zeros_like(degree))
         loop = None if self.loop_weight is None else self.loop_weight.to(x.dtype)
         out = RelationalLinearFunction.apply(rowptr, colind, colptr, rowind, x, weight.to(x.dtype), scale, None if loop is None else x, loop,
-                                             None if self.bias is None else self.bias.float(), None, None, self.fused)
+                                             None if self.bias is None else self.bias.float(), None, None, self.fused, self.fused_weight_grad)
         return out if self.activation is None else self.activation(out)
 
     def __repr__(self):

@@ -1028,6 +1028,83 @@ def csr_spmm_relational_linear(rowptr, colind, values, dense, weight, row_scale=
     return result.copy_(acc)
 
 
+def csr_spmm_relational_weight_grad(rowptr, colind, values, dense, grad_out, R, row_scale=None, chunks=None, workspace=None, out=None,
+                                    fused=True):
+    """The weight gradient of ``csr_spmm_relational_linear`` without the [R * M, K] stack of aggregates
+    (gespmm_csr_spmm_relational_wgrad_x16):
+
+        H_r       = narrow(row_scale[r M : (r + 1) M, None] * (A_r @ dense))       per relation, the 16-bit product's bits, never stored
+        grad_W[r] = narrow(grad_out.T @ H_r)                                       [R, N_out, K], fp32 sums on the matrix unit, one rounding
+
+    ``rowptr`` / ``colind`` / ``values`` / ``row_scale``: the stacked CSR of ``csr_spmm_relational_linear`` (R * M rows); ``dense``
+    [Kn, K] and ``grad_out`` [M, N_out], both fp16, both bf16 or both fp32. The rows are reduced in ``chunks`` contiguous runs of 64-row
+    blocks whose fp32 partial sums are added in a fixed order: the same ``chunks`` gives the same bits. ``chunks=None`` takes
+    ``_lib.spmm_relational_wgrad_chunks``; any 1 <= chunks <= ceil(M / 64) may be forced. ``workspace``: an fp32 tensor of at least
+    chunks * R * N_out * K elements (None: allocated here with torch, which a graph capture records like any other allocation).
+
+    16-bit tensors take the kernels where ``_lib.spmm_relational_wgrad_route_x16`` answers 1 (the shapes of the forward's kernel).
+    Everything else — fp32, an odd K, a wide layer, a 2-byte offset — is composed: ``stacked_aggregate``, then one batched matmul. The
+    call never fails on shape. ``fused=False`` takes the composition whatever the shape (measurements)."""
+    _need(rowptr, "rowptr", torch.int32, 1)
+    _need(colind, "colind", torch.int32, 1)
+    dt = dense.dtype
+    if dt not in _X16 and dt != torch.float32:
+        raise TypeError("dense must be torch.float16, torch.bfloat16 or torch.float32, got %s" % dt)
+    _need(dense, "dense", dt, 2)
+    _need(grad_out, "grad_out", dt, 2)
+    R = int(R)
+    rows = rowptr.numel() - 1
+    if R < 0 or rows < 0 or (R == 0 and rows != 0) or (R != 0 and rows % R != 0):
+        raise ValueError("rowptr must have R * M + 1 entries for R = %d relations" % R)
+    M, N_out = grad_out.shape
+    Kn, K = dense.shape
+    if R != 0 and rows // R != M:
+        raise ValueError("grad_out must have M = %d rows" % (rows // R))
+    others = [grad_out]
+    if values is not None:
+        _need(values, "values", torch.float32, 1)
+        if values.numel() != colind.numel():
+            raise ValueError("values and colind must have the same length")
+        others.append(values)
+    if row_scale is not None:
+        _need(row_scale, "row_scale", torch.float32, 1)
+        if row_scale.numel() != R * M:
+            raise ValueError("row_scale must have %d entries, got %d" % (R * M, row_scale.numel()))
+        others.append(row_scale)
+    dev = _same_device(dense, rowptr, colind, *others)
+    if out is not None:
+        _result(out, "out", dt, (R, N_out, K), dev, (dense, grad_out))
+    nnz = colind.numel()
+    blocks = (M + 63) // 64
+    if chunks is None:
+        C = _lib.spmm_relational_wgrad_chunks(R, M, K, N_out)
+    else:
+        C = int(chunks)
+        if not 1 <= C <= max(blocks, 1):
+            raise ValueError("chunks must be in 1 .. ceil(M / 64) = %d, got %d" % (max(blocks, 1), C))
+    if workspace is not None:
+        _need(workspace, "workspace", torch.float32, workspace.dim())
+        if workspace.device != dev or workspace.numel() < C * R * N_out * K:
+            raise ValueError("workspace must hold chunks * R * N_out * K = %d fp32 elements on %s" % (C * R * N_out * K, dev))
+        if any(_overlaps(workspace, t) for t in (dense, grad_out, out) if t is not None):
+            raise ValueError("workspace must not overlap an operand or the result")
+    if fused and dt in _X16 and C >= 1 and _lib.spmm_relational_wgrad_route_x16(
+            R, M, Kn, K, N_out, nnz, C, x16_align(dense if nnz else None, grad_out, out, workspace)) == 1:
+        ws = torch.empty((C, R, N_out, K), dtype=torch.float32, device=dev) if workspace is None else workspace
+        result = torch.empty((R, N_out, K), dtype=dt, device=dev) if out is None else out
+        if x16_align(ws, result) == 16:
+            with _on_device(dev):
+                rc = lib.gespmm_csr_spmm_relational_wgrad_x16(_ptr(rowptr), _ptr(colind), _optr(values), _optr(row_scale), _ptr(dense),
+                                                              _ptr(grad_out), _ptr(ws), _ptr(result), _X16[dt], R, M, Kn, K, N_out, nnz, C,
+                                                              _stream(dev))
+            check(rc, "gespmm_csr_spmm_relational_wgrad_x16")
+            return result
+    # the composition: the product on the stacked CSR as it stands ([R M, K]), then grad_out^T against each relation's rows
+    h = stacked_aggregate(rowptr, colind, values, dense, row_scale)
+    g = torch.matmul(grad_out.t().unsqueeze(0), h.view(R, M, K))
+    return g if out is None else out.copy_(g)
+
+
 def csr2csc(rowptr, colind, colptr, rowind, csr_data):
     """Fill ``colptr`` / ``rowind`` in place with the CSC form of CSR(rowptr, colind)
     and return the values in CSC order. Mirrors spmm.cpp:70-93 (whose CUDA

@@ -268,6 +268,37 @@ int gespmm_csr_spmm_relational_x16(const int32_t* rowptr, const int32_t* colind,
 /* Host only: gespmm_spmm_linear_route_x16 for the call above. */
 int gespmm_spmm_relational_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align);
 
+/*
+ * Fused relational weight gradient on 16-bit features: the gradient of the layer above with respect to W, with no per-relation
+ * aggregate in memory. The stacked CSR, X, val and row_scale are those of gespmm_csr_spmm_relational_x16; grad_out is [M, N_out] and
+ * grad_W [R, N_out, K], row-major, in the type of X.
+ *
+ *     H_r[i, c]       = as above (one fp32 chain from +0, one fp32 multiply by row_scale, ONE rounding: the 16-bit product's bits)
+ *     grad_W[r, n, c] = narrow( sum_i grad_out[i, n] H_r[i, c] )
+ *
+ * The sum over the rows i accumulates in fp32 on the matrix unit inside each of `chunks` contiguous runs of 64-row blocks, in the
+ * hardware's order; the chunks' fp32 partial sums are added in the order 0 .. chunks - 1 and the store rounds once. No atomics: the
+ * same operands and the same `chunks` give the same bits. partials is the CALLER's workspace, chunks * R * N_out * K floats, 16-byte
+ * aligned, overwritten; the call allocates nothing and does not synchronise the host: capturable. Two launches.
+ * Served by the kernels: the shapes of gespmm_csr_spmm_relational_x16 (M >= 1), 1 <= chunks <= ceil(M / 64) and
+ * chunks * R * N_out * K <= 2^31 - 4097. Checks, in this order: dtype -> GESPMM_EINVAL; a negative size -> GESPMM_EINVAL; the size limits
+ * of gespmm_csr_spmm_relational_x16 -> GESPMM_ERANGE; R == 0, N_out == 0 or K == 0 -> 0; NULL rowptr, partials or grad_W (grad_out: when
+ * M != 0; colind, X: when nnz != 0) -> GESPMM_EINVAL; an index or fp32 array not 4-byte, a 16-bit array not 2-byte aligned ->
+ * GESPMM_EALIGN; X, grad_out, grad_W or partials not 16-byte aligned -> GESPMM_EINVAL; a shape or chunk count that is not served ->
+ * GESPMM_ERR_UNSUPPORTED with nothing launched (the composition — the 16-bit product, then a batched matmul — is the caller's); grad_W
+ * or partials overlapping an operand or each other -> GESPMM_EINVAL. nnz == 0 stores zeros.
+ */
+int gespmm_csr_spmm_relational_wgrad_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const void* X,
+                                         const void* grad_out, float* partials, void* grad_W, int dtype, int64_t R, int64_t M, int64_t Kn,
+                                         int64_t K, int64_t N_out, int64_t nnz, int64_t chunks, void* stream);
+/* Host only: gespmm_spmm_linear_route_x16 for the call above with this chunk count. */
+int gespmm_spmm_relational_wgrad_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int64_t chunks, int align);
+/* Host only: the chunk count the library suggests — the smallest that puts about four workgroups on each compute unit,
+ * ceil(1024 / (R * ceil(K / 64))), at most ceil(M / 64), at most M / (4 N_out) (the workspace stays below half of the [R M, K] 16-bit
+ * aggregates the call avoids) and within the workspace's size limit; at least 1, and 0 when a size is 0. Negative sizes ->
+ * GESPMM_EINVAL; sizes past the limits -> GESPMM_ERANGE. */
+int64_t gespmm_spmm_relational_wgrad_chunks(int64_t R, int64_t M, int64_t K, int64_t N_out);
+
 /* The variant `GESPMM_VARIANT_AUTO` resolves to for this shape (pure host logic). */
 int gespmm_select_variant(int64_t M, int64_t nnz, int64_t N);
 
