@@ -181,6 +181,8 @@ EXPORTS = [
     "gespmm_spmm_linear_route_x16",
     "gespmm_csr_spmm_relational_x16",
     "gespmm_spmm_relational_route_x16",
+    "gespmm_csr_spmm_relational_f32",
+    "gespmm_spmm_relational_route_f32",
     "gespmm_csr_spmm_relational_wgrad_x16",
     "gespmm_spmm_relational_wgrad_route_x16",
     "gespmm_spmm_relational_wgrad_chunks",
@@ -511,6 +513,10 @@ def _load():
     lib.gespmm_csr_spmm_relational_x16.argtypes = [p] * 10 + [c_int] + [c_int64] * 6 + [p]
     lib.gespmm_spmm_relational_route_x16.restype = c_int
     lib.gespmm_spmm_relational_route_x16.argtypes = [c_int64] * 6 + [c_int]
+    lib.gespmm_csr_spmm_relational_f32.restype = c_int
+    lib.gespmm_csr_spmm_relational_f32.argtypes = [p] * 10 + [c_int64] * 6 + [p]
+    lib.gespmm_spmm_relational_route_f32.restype = c_int
+    lib.gespmm_spmm_relational_route_f32.argtypes = [c_int64] * 6 + [c_int]
     lib.gespmm_csr_spmm_relational_wgrad_x16.restype = c_int
     lib.gespmm_csr_spmm_relational_wgrad_x16.argtypes = [p] * 8 + [c_int] + [c_int64] * 7 + [p]
     lib.gespmm_spmm_relational_wgrad_route_x16.restype = c_int
@@ -786,6 +792,22 @@ def csr_spmm_relational_x16(rowptr, colind, val, row_scale, X, W, X_root, W_root
     """gespmm_csr_spmm_relational_x16 on raw addresses (ints or None), argument for argument; returns the C return code unchecked."""
     ptrs = [ctypes.c_void_p(a) if a is not None else None for a in (rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out)]
     return lib.gespmm_csr_spmm_relational_x16(*ptrs, int(dtype), int(R), int(M), int(Kn), int(K), int(N_out), int(nnz),
+                                              ctypes.c_void_p(stream) if stream is not None else None)
+
+
+def spmm_relational_route_f32(R, M, Kn, K, N_out, nnz, align=16):
+    """``spmm_relational_route_x16`` for gespmm_csr_spmm_relational_f32 (fp32 features; ``align``: of X, W, X_root, W_root and out, a
+    power of two >= 4): 1 the kernel, 0 the composition is the caller's (``spmm.csr_spmm_relational_linear`` composes it)."""
+    rc = lib.gespmm_spmm_relational_route_f32(int(R), int(M), int(Kn), int(K), int(N_out), int(nnz), int(align))
+    if rc < 0:
+        raise GespmmError(rc, "gespmm_spmm_relational_route_f32")
+    return rc
+
+
+def csr_spmm_relational_f32(rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out, R, M, Kn, K, N_out, nnz, stream=None):
+    """gespmm_csr_spmm_relational_f32 on raw addresses (ints or None), argument for argument; returns the C return code unchecked."""
+    ptrs = [ctypes.c_void_p(a) if a is not None else None for a in (rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out)]
+    return lib.gespmm_csr_spmm_relational_f32(*ptrs, int(R), int(M), int(Kn), int(K), int(N_out), int(nnz),
                                               ctypes.c_void_p(stream) if stream is not None else None)
 
 

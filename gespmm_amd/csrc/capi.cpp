@@ -36,6 +36,7 @@
 #include "spmm_heads.h"
 #include "spmm_linear.h"
 #include "spmm_relational.h"
+#include "spmm_relational_f32.h"
 #include "spmm_relational_wgrad.h"
 #include "spmm_max_arg.h"
 #include "spmm_kernels.h"
@@ -1151,6 +1152,51 @@ int gespmm_spmm_relational_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K
     const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
     if (rc != 0) return rc;
     return gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align) ? 1 : 0;
+}
+
+/* The relational aggregate-and-linear on fp32 features (gespmm.h; spmm_relational_f32.hip): the ladder of the 16-bit call above without
+   a dtype, every array fp32; an array the kernel moves 16 bytes at a time that is not 16-byte aligned is GESPMM_EALIGN. ONE kernel or
+   GESPMM_ERR_UNSUPPORTED. gespmm_spmm_relational_route_f32 answers from the function the launch asks: spmm_relational_f32_served. */
+int gespmm_csr_spmm_relational_f32(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const float* X,
+                                   const float* W, const float* X_root, const float* W_root, const float* bias, float* out, int64_t R,
+                                   int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream) {
+    int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    if (rc != 0) return rc;
+    if (M == 0 || N_out == 0) return 0;
+    if ((X_root == nullptr) != (W_root == nullptr)) return GESPMM_EINVAL;
+    if ((rc = check_pointers({{rowptr, 4, true}, {W, 4, true}, {out, 4, true}, {colind, 4, nnz != 0}, {X, 4, nnz != 0}, {val, 4, false},
+                              {row_scale, 4, false}, {bias, 4, false}, {X_root, 4, false}, {W_root, 4, false}})) != 0)
+        return rc;
+    const int align = linear_x16_align({nnz != 0 ? X : nullptr, W, X_root, W_root, out});
+    if (align < 16) return GESPMM_EALIGN;  // (X, W, X_root, W_root and out are read or written 16 bytes at a time)
+    const uint64_t o_bytes = (uint64_t)M * (uint64_t)N_out * 4, w_bytes = (uint64_t)N_out * (uint64_t)K * 4;
+    if ((nnz != 0 && ranges_overlap(out, o_bytes, X, (uint64_t)Kn * (uint64_t)K * 4)) || ranges_overlap(out, o_bytes, W, (uint64_t)R * w_bytes) ||
+        (X_root && (ranges_overlap(out, o_bytes, X_root, (uint64_t)M * (uint64_t)K * 4) || ranges_overlap(out, o_bytes, W_root, w_bytes))))
+        return GESPMM_EINVAL;
+    if (!gespmm::spmm_relational_f32_served(R, M, Kn, K, N_out, nnz, align)) return GESPMM_ERR_UNSUPPORTED;  // (nothing launched)
+    gespmm::SpmmRelationalF32Args a = {};
+    a.rowptr = rowptr;
+    a.colind = colind;
+    a.val = nnz != 0 ? val : nullptr;
+    a.row_scale = row_scale;
+    a.X = X;
+    a.W = W;
+    a.Xroot = X_root;
+    a.Wroot = W_root;
+    a.bias = bias;
+    a.out = out;
+    a.R = (int32_t)R;
+    a.M = (int32_t)M;
+    a.K = (int32_t)K;
+    a.N_out = (int32_t)N_out;
+    return (int)gespmm::launch_spmm_relational_f32(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+int gespmm_spmm_relational_route_f32(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align) {
+    if (align < 4 || (align & (align - 1)) != 0) return GESPMM_EINVAL;
+    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    if (rc != 0) return rc;
+    return gespmm::spmm_relational_f32_served(R, M, Kn, K, N_out, nnz, align) ? 1 : 0;
 }
 
 /* The fused relational weight gradient on 16-bit features (gespmm.h; spmm_relational_wgrad.hip): grad_W[r] = grad_out^T @ H_r over the

@@ -1371,8 +1371,9 @@ class SAGEConv(torch.nn.Module):
 
 class RelationalLinearFunction(torch.autograd.Function):
     """out = narrow(sum_r narrow(row_scale_r * (A_r @ x)) @ weight[r].T + root @ root_weight.T + bias) on a stacked CSR
-    (``spmm.csr_spmm_relational_linear``: on fp16 / bf16 features ONE kernel, every relation's aggregate of a 64-row block through one
-    LDS tile into the same matrix-unit accumulators; neither the [R, M, K] aggregates nor the [R, Kn, N_out] transforms exist).
+    (``spmm.csr_spmm_relational_linear``: on fp16 / bf16 and on fp32 features ONE kernel, every relation's aggregate of a 64-row block
+    through one LDS tile into the same matrix-unit accumulators; neither the [R, M, K] aggregates nor the [R, Kn, N_out] transforms
+    exist. On fp32 that holds for the forward and for grad_x where K resp. N_out is a multiple of 4; grad_weight is composed).
 
         RelationalLinearFunction.apply(rowptr, colind, colptr, rowind, x, weight, row_scale, root, root_weight, bias,
                                        values_csr=None, values_csc=None, fused=True, fused_weight_grad=False)

@@ -953,9 +953,10 @@ def stacked_aggregate(rowptr, colind, values, dense, row_scale=None):
 
 def csr_spmm_relational_linear(rowptr, colind, values, dense, weight, row_scale=None, root=None, root_weight=None, bias=None, out=None,
                                fused=True):
-    """A relational graph convolution (RGCN) in ONE kernel on 16-bit features (gespmm_csr_spmm_relational_x16):
+    """A relational graph convolution (RGCN) in ONE kernel, on 16-bit features (gespmm_csr_spmm_relational_x16) and on fp32 features
+    (gespmm_csr_spmm_relational_f32; ``narrow`` is then the identity):
 
-        H_r = narrow(row_scale[r M : (r + 1) M, None] * (A_r @ dense))             per relation, the 16-bit product's bits
+        H_r = narrow(row_scale[r M : (r + 1) M, None] * (A_r @ dense))             per relation, the product's bits in dense's type
         out = narrow(sum_r H_r @ weight[r].T + root @ root_weight.T + bias)        fp32 sums on the matrix unit, one rounding
 
     The graph is a STACKED CSR: relation r's row i is row ``r * M + i`` of one ordinary CSR with R * M rows over Kn columns —
@@ -966,8 +967,9 @@ def csr_spmm_relational_linear(rowptr, colind, values, dense, weight, row_scale=
     [Kn, K], ``root`` [M, K] with ``root_weight`` [N_out, K] (together or not at all), ``bias`` fp32 [N_out].
 
     16-bit ``dense`` takes the kernel where ``_lib.spmm_relational_route_x16`` answers 1 (K % 8 == 0, 8 <= K <= 256, N_out <= 256,
-    16-byte aligned tensors). Everything else — fp32 ``dense`` (all tensors fp32), an odd K, a wide layer, a 2-byte offset — is
-    composed: the product on the stacked arrays, one fp32 matmul of the [M, R K] regrouped aggregate, root and bias in fp32, rounded
+    16-byte aligned tensors). fp32 ``dense`` (all tensors fp32) takes the fp32 kernel where ``_lib.spmm_relational_route_f32`` answers
+    1 (K % 4 == 0, 4 <= K <= 256, N_out <= 256, 16-byte aligned tensors); with R = 1 that is the plain aggregate-and-linear on fp32.
+    Everything else — a K the type's kernel does not take, a wide layer, a view off the 16-byte boundary — is composed: the product on the stacked arrays, one fp32 matmul of the [M, R K] regrouped aggregate, root and bias in fp32, rounded
     once for a 16-bit result. The call never fails on shape. ``fused=False`` takes the composition whatever the shape (measurements)."""
     _need(rowptr, "rowptr", torch.int32, 1)
     _need(colind, "colind", torch.int32, 1)
@@ -1017,6 +1019,14 @@ def csr_spmm_relational_linear(rowptr, colind, values, dense, weight, row_scale=
                                                     _optr(root), _optr(root_weight), _optr(bias), _ptr(result), _X16[dt], R, M, Kn, K,
                                                     N_out, nnz, _stream(dev))
         check(rc, "gespmm_csr_spmm_relational_x16")
+        return result
+    if fused and dt == torch.float32 and _lib.spmm_relational_route_f32(
+            R, M, Kn, K, N_out, nnz, max(4, x16_align(dense if nnz else None, weight, root, root_weight, result))) == 1:
+        with _on_device(dev):
+            rc = lib.gespmm_csr_spmm_relational_f32(_ptr(rowptr), _ptr(colind), _optr(values), _optr(row_scale), _ptr(dense), _ptr(weight),
+                                                    _optr(root), _optr(root_weight), _optr(bias), _ptr(result), R, M, Kn, K, N_out, nnz,
+                                                    _stream(dev))
+        check(rc, "gespmm_csr_spmm_relational_f32")
         return result
     # the composition: the product on the stacked CSR as it stands ([R M, K]), its relations side by side ([M, R K]) against
     # weight as [N_out, R K] in fp32, root and bias in fp32, one rounding

@@ -269,6 +269,32 @@ int gespmm_csr_spmm_relational_x16(const int32_t* rowptr, const int32_t* colind,
 int gespmm_spmm_relational_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align);
 
 /*
+ * Relational aggregate-and-linear on fp32 features: the layer above with every array fp32, in one kernel on v_mfma_f32_32x32x2_f32.
+ * The stacked CSR, the shapes and the NULL rules are those of gespmm_csr_spmm_relational_x16; R == 1 is the plain aggregate-and-linear.
+ *
+ *     H_r[i, c] = row_scale[r M + i] * (sum over p = rowptr[r M + i] .. rowptr[r M + i + 1] - 1, ascending, of val[p] * X[colind[p], c])
+ *     out[i, n] = sum_r sum_c H_r[i, c] W[r, n, c]  +  sum_c X_root[i, c] W_root[n, c]  +  bias[n]
+ *
+ * H_r: one fp32 chain per element from +0 — fmaf(val[p], x, acc), or acc + x when val is NULL — then ONE fp32 multiply by row_scale
+ * (NULL: none): the bits gespmm_csr_spmm_f32 (gespmm_csr_spmm_fused_f32 with row_scale) returns on the same arrays, which is the
+ * composition route and the bit oracle. H_r exists only as one 64-row fp32 LDS tile at a time. The sums over c and r accumulate in fp32
+ * on the matrix unit, k in steps of 8 as the pairs {k0 + j, k0 + 4 + j}, j = 0 .. 3: the hardware's and the kernel's order, fixed for
+ * a shape but not pinned by this contract. bias is one fp32 add (NULL: none). A 64-row block without an entry of relation r skips it.
+ * Served by the kernel: R >= 1, M >= 1, K a multiple of 4 in 4 .. 256, N_out in 1 .. 256, X, W, X_root, W_root and out 16-byte aligned.
+ * No allocation, no host synchronisation: capturable. Checks, in this order: a negative size -> GESPMM_EINVAL; the size limits of
+ * gespmm_csr_spmm_relational_x16 -> GESPMM_ERANGE; M == 0 or N_out == 0 -> 0; exactly one of X_root / W_root -> GESPMM_EINVAL; NULL
+ * rowptr, W or out (colind, X: when nnz != 0) -> GESPMM_EINVAL; an array not 4-byte aligned, or X, W, X_root, W_root or out not
+ * 16-byte aligned -> GESPMM_EALIGN; out overlapping an operand -> GESPMM_EINVAL; a shape the kernel does not serve ->
+ * GESPMM_ERR_UNSUPPORTED with nothing launched (the composition — gespmm_csr_spmm_f32, then a dense linear — is the caller's).
+ */
+int gespmm_csr_spmm_relational_f32(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const float* X,
+                                   const float* W, const float* X_root, const float* W_root, const float* bias, float* out, int64_t R,
+                                   int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream);
+/* Host only: gespmm_spmm_linear_route_x16 for the call above; align: the largest power of two (>= 4) dividing the address of X, W,
+ * X_root, W_root and out. */
+int gespmm_spmm_relational_route_f32(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align);
+
+/*
  * Fused relational weight gradient on 16-bit features: the gradient of the layer above with respect to W, with no per-relation
  * aggregate in memory. The stacked CSR, X, val and row_scale are those of gespmm_csr_spmm_relational_x16; grad_out is [M, N_out] and
  * grad_W [R, N_out, K], row-major, in the type of X.
