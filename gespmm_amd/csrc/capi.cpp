@@ -1056,9 +1056,10 @@ int gespmm_max_arg_route_x16(int64_t M, int64_t nnz, int64_t N, int x16_align, i
     return describe_result(n, capacity);
 }
 
-/* The fused aggregate-and-linear on 16-bit features (gespmm.h; spmm_linear.hip): ONE kernel or GESPMM_ERR_UNSUPPORTED — the composition
-   (the 16-bit product, then a dense linear) needs a GEMM this library does not have, so it is the caller's (spmm.csr_spmm_linear).
-   gespmm_spmm_linear_route_x16 answers from the function the launch asks: spmm_linear_served. */
+/* The fused aggregate-and-linear (gespmm.h; spmm_linear.hip, spmm_relational.hip, spmm_relational_f32.hip): ONE kernel or
+   GESPMM_ERR_UNSUPPORTED — the composition (the product, then a dense linear) needs a GEMM this library does not have, so it is the
+   caller's (spmm.csr_spmm_linear). The three forward entries share one argument ladder on a stacked CSR of R M rows (R = 1: the plain
+   layer); each route function answers from the function its launch asks (spmm_linear_served and its kin). */
 static int linear_x16_align(std::initializer_list<const void*> ptrs) {
     int al = 16;
     for (const void* p : ptrs)
@@ -1066,137 +1067,112 @@ static int linear_x16_align(std::initializer_list<const void*> ptrs) {
     return al;
 }
 
+struct LinearForward {
+    const int32_t *rowptr, *colind;
+    const float *val, *row_scale;
+    const void *X, *W, *X_root, *W_root;
+    const float* bias;
+    void* out;
+    int64_t R, M, Kn, K, N_out, nnz;
+};
+
+/* After the entry's own size check: every array of `es`-byte elements, W of R weight matrices. An array the kernel moves 16 bytes at a
+   time that is not 16-byte aligned is `ealign`. served(align) false: GESPMM_ERR_UNSUPPORTED, nothing launched. launch(a) gets the
+   entry's args struct with every field but R filled. */
+extern "C++" template <typename Args, typename Served, typename Launch>
+static int linear_forward(const LinearForward& c, int es, int ealign, Served served, Launch launch) {
+    if (c.M == 0 || c.N_out == 0) return 0;
+    if ((c.X_root == nullptr) != (c.W_root == nullptr)) return GESPMM_EINVAL;
+    const bool edges = c.nnz != 0;
+    const int rc = check_pointers({{c.rowptr, 4, true}, {c.W, es, true}, {c.out, es, true}, {c.colind, 4, edges}, {c.X, es, edges},
+                                   {c.val, 4, false}, {c.row_scale, 4, false}, {c.bias, 4, false}, {c.X_root, es, false}, {c.W_root, es, false}});
+    if (rc != 0) return rc;
+    const int align = linear_x16_align({edges ? c.X : nullptr, c.W, c.X_root, c.W_root, c.out});
+    if (align < 16) return ealign;
+    const uint64_t e = (uint64_t)es, o_bytes = (uint64_t)c.M * (uint64_t)c.N_out * e, w_bytes = (uint64_t)c.N_out * (uint64_t)c.K * e;
+    if ((edges && ranges_overlap(c.out, o_bytes, c.X, (uint64_t)c.Kn * (uint64_t)c.K * e)) ||
+        ranges_overlap(c.out, o_bytes, c.W, (uint64_t)c.R * w_bytes) ||
+        (c.X_root && (ranges_overlap(c.out, o_bytes, c.X_root, (uint64_t)c.M * (uint64_t)c.K * e) || ranges_overlap(c.out, o_bytes, c.W_root, w_bytes))))
+        return GESPMM_EINVAL;
+    if (!served(align)) return GESPMM_ERR_UNSUPPORTED;
+    Args a = {};
+    a.rowptr = c.rowptr;
+    a.colind = c.colind;
+    a.val = edges ? c.val : nullptr;
+    a.row_scale = c.row_scale;
+    a.X = static_cast<decltype(a.X)>(c.X);  // (a 16-bit array seen as words: spmm_linear.h)
+    a.W = static_cast<decltype(a.W)>(c.W);
+    a.Xroot = static_cast<decltype(a.Xroot)>(c.X_root);
+    a.Wroot = static_cast<decltype(a.Wroot)>(c.W_root);
+    a.bias = c.bias;
+    a.out = static_cast<decltype(a.out)>(c.out);
+    a.M = (int32_t)c.M;
+    a.K = (int32_t)c.K;
+    a.N_out = (int32_t)c.N_out;
+    return (int)launch(a);
+}
+
+/* A route answer: `align` a power of two, at least one element. */
+static int served_route(int align, int min_align, int sizes_rc, bool served) {
+    if (align < min_align || (align & (align - 1)) != 0) return GESPMM_EINVAL;
+    if (sizes_rc != 0) return sizes_rc;
+    return served ? 1 : 0;
+}
+
 int gespmm_csr_spmm_linear_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const void* X,
                                const void* W_n, const void* X_root, const void* W_r, const float* bias, void* out, int dtype, int64_t M,
                                int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream) {
     if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
-    int rc = gespmm::spmm_linear_sizes(M, Kn, K, N_out, nnz);
+    const int rc = gespmm::spmm_linear_sizes(M, Kn, K, N_out, nnz);
     if (rc != 0) return rc;
-    if (M == 0 || N_out == 0) return 0;
-    if ((X_root == nullptr) != (W_r == nullptr)) return GESPMM_EINVAL;
-    if ((rc = check_pointers({{rowptr, 4, true}, {W_n, 2, true}, {out, 2, true}, {colind, 4, nnz != 0}, {X, 2, nnz != 0}, {val, 4, false},
-                              {row_scale, 4, false}, {bias, 4, false}, {X_root, 2, false}, {W_r, 2, false}})) != 0)
-        return rc;
-    const int align = linear_x16_align({nnz != 0 ? X : nullptr, W_n, X_root, W_r, out});
-    if (align < 16) return GESPMM_EINVAL;  // (every 16-bit array is read or written 16 bytes at a time)
-    const uint64_t o_bytes = (uint64_t)M * (uint64_t)N_out * 2, w_bytes = (uint64_t)N_out * (uint64_t)K * 2;
-    if ((nnz != 0 && ranges_overlap(out, o_bytes, X, (uint64_t)Kn * (uint64_t)K * 2)) || ranges_overlap(out, o_bytes, W_n, w_bytes) ||
-        (X_root && (ranges_overlap(out, o_bytes, X_root, (uint64_t)M * (uint64_t)K * 2) || ranges_overlap(out, o_bytes, W_r, w_bytes))))
-        return GESPMM_EINVAL;
-    if (!gespmm::spmm_linear_served(M, Kn, K, N_out, nnz, align)) return GESPMM_ERR_UNSUPPORTED;  // (nothing launched)
-    gespmm::SpmmLinearArgs a = {};
-    a.rowptr = rowptr;
-    a.colind = colind;
-    a.val = nnz != 0 ? val : nullptr;
-    a.row_scale = row_scale;
-    a.X = static_cast<const float*>(X);  // (the 16-bit array seen as words: spmm_linear.h)
-    a.Wn = W_n;
-    a.Xroot = X_root;
-    a.Wr = W_r;
-    a.bias = bias;
-    a.out = out;
-    a.M = (int32_t)M;
-    a.K = (int32_t)K;
-    a.N_out = (int32_t)N_out;
-    return (int)gespmm::launch_spmm_linear_x16(a, dtype, reinterpret_cast<hipStream_t>(stream));
+    return linear_forward<gespmm::SpmmLinearArgs>(
+        {rowptr, colind, val, row_scale, X, W_n, X_root, W_r, bias, out, 1, M, Kn, K, N_out, nnz}, 2, GESPMM_EINVAL,
+        [&](int align) { return gespmm::spmm_linear_served(M, Kn, K, N_out, nnz, align); },
+        [&](gespmm::SpmmLinearArgs& a) { return gespmm::launch_spmm_linear_x16(a, dtype, reinterpret_cast<hipStream_t>(stream)); });
 }
 
 int gespmm_spmm_linear_route_x16(int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align) {
-    if (align < 2 || (align & (align - 1)) != 0) return GESPMM_EINVAL;
-    const int rc = gespmm::spmm_linear_sizes(M, Kn, K, N_out, nnz);
-    if (rc != 0) return rc;
-    return gespmm::spmm_linear_served(M, Kn, K, N_out, nnz, align) ? 1 : 0;
+    return served_route(align, 2, gespmm::spmm_linear_sizes(M, Kn, K, N_out, nnz), gespmm::spmm_linear_served(M, Kn, K, N_out, nnz, align));
 }
 
-/* The relational aggregate-and-linear on 16-bit features (gespmm.h; spmm_relational.hip): the argument ladder of the call above on a
-   stacked CSR of R M rows, ONE kernel or GESPMM_ERR_UNSUPPORTED. gespmm_spmm_relational_route_x16 answers from the function the launch
-   asks: spmm_relational_served. */
 int gespmm_csr_spmm_relational_x16(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const void* X,
                                    const void* W, const void* X_root, const void* W_root, const float* bias, void* out, int dtype,
                                    int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream) {
     if (!valid_x16_dtype(dtype)) return GESPMM_EINVAL;
-    int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
     if (rc != 0) return rc;
-    if (M == 0 || N_out == 0) return 0;
-    if ((X_root == nullptr) != (W_root == nullptr)) return GESPMM_EINVAL;
-    if ((rc = check_pointers({{rowptr, 4, true}, {W, 2, true}, {out, 2, true}, {colind, 4, nnz != 0}, {X, 2, nnz != 0}, {val, 4, false},
-                              {row_scale, 4, false}, {bias, 4, false}, {X_root, 2, false}, {W_root, 2, false}})) != 0)
-        return rc;
-    const int align = linear_x16_align({nnz != 0 ? X : nullptr, W, X_root, W_root, out});
-    if (align < 16) return GESPMM_EINVAL;  // (every 16-bit array is read or written 16 bytes at a time)
-    const uint64_t o_bytes = (uint64_t)M * (uint64_t)N_out * 2, w_bytes = (uint64_t)N_out * (uint64_t)K * 2;
-    if ((nnz != 0 && ranges_overlap(out, o_bytes, X, (uint64_t)Kn * (uint64_t)K * 2)) || ranges_overlap(out, o_bytes, W, (uint64_t)R * w_bytes) ||
-        (X_root && (ranges_overlap(out, o_bytes, X_root, (uint64_t)M * (uint64_t)K * 2) || ranges_overlap(out, o_bytes, W_root, w_bytes))))
-        return GESPMM_EINVAL;
-    if (!gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align)) return GESPMM_ERR_UNSUPPORTED;  // (nothing launched)
-    gespmm::SpmmRelationalArgs a = {};
-    a.rowptr = rowptr;
-    a.colind = colind;
-    a.val = nnz != 0 ? val : nullptr;
-    a.row_scale = row_scale;
-    a.X = static_cast<const float*>(X);  // (the 16-bit array seen as words: spmm_relational.h)
-    a.W = W;
-    a.Xroot = X_root;
-    a.Wroot = W_root;
-    a.bias = bias;
-    a.out = out;
-    a.R = (int32_t)R;
-    a.M = (int32_t)M;
-    a.K = (int32_t)K;
-    a.N_out = (int32_t)N_out;
-    return (int)gespmm::launch_spmm_relational_x16(a, dtype, reinterpret_cast<hipStream_t>(stream));
+    return linear_forward<gespmm::SpmmRelationalArgs>(
+        {rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out, R, M, Kn, K, N_out, nnz}, 2, GESPMM_EINVAL,
+        [&](int align) { return gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align); },
+        [&](gespmm::SpmmRelationalArgs& a) {
+            a.R = (int32_t)R;
+            return gespmm::launch_spmm_relational_x16(a, dtype, reinterpret_cast<hipStream_t>(stream));
+        });
 }
 
 int gespmm_spmm_relational_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align) {
-    if (align < 2 || (align & (align - 1)) != 0) return GESPMM_EINVAL;
-    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
-    if (rc != 0) return rc;
-    return gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align) ? 1 : 0;
+    return served_route(align, 2, gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz),
+                        gespmm::spmm_relational_served(R, M, Kn, K, N_out, nnz, align));
 }
 
-/* The relational aggregate-and-linear on fp32 features (gespmm.h; spmm_relational_f32.hip): the ladder of the 16-bit call above without
-   a dtype, every array fp32; an array the kernel moves 16 bytes at a time that is not 16-byte aligned is GESPMM_EALIGN. ONE kernel or
-   GESPMM_ERR_UNSUPPORTED. gespmm_spmm_relational_route_f32 answers from the function the launch asks: spmm_relational_f32_served. */
+/* ... on fp32 features: no dtype, every array fp32, a misaligned one GESPMM_EALIGN. */
 int gespmm_csr_spmm_relational_f32(const int32_t* rowptr, const int32_t* colind, const float* val, const float* row_scale, const float* X,
                                    const float* W, const float* X_root, const float* W_root, const float* bias, float* out, int64_t R,
                                    int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, void* stream) {
-    int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
+    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
     if (rc != 0) return rc;
-    if (M == 0 || N_out == 0) return 0;
-    if ((X_root == nullptr) != (W_root == nullptr)) return GESPMM_EINVAL;
-    if ((rc = check_pointers({{rowptr, 4, true}, {W, 4, true}, {out, 4, true}, {colind, 4, nnz != 0}, {X, 4, nnz != 0}, {val, 4, false},
-                              {row_scale, 4, false}, {bias, 4, false}, {X_root, 4, false}, {W_root, 4, false}})) != 0)
-        return rc;
-    const int align = linear_x16_align({nnz != 0 ? X : nullptr, W, X_root, W_root, out});
-    if (align < 16) return GESPMM_EALIGN;  // (X, W, X_root, W_root and out are read or written 16 bytes at a time)
-    const uint64_t o_bytes = (uint64_t)M * (uint64_t)N_out * 4, w_bytes = (uint64_t)N_out * (uint64_t)K * 4;
-    if ((nnz != 0 && ranges_overlap(out, o_bytes, X, (uint64_t)Kn * (uint64_t)K * 4)) || ranges_overlap(out, o_bytes, W, (uint64_t)R * w_bytes) ||
-        (X_root && (ranges_overlap(out, o_bytes, X_root, (uint64_t)M * (uint64_t)K * 4) || ranges_overlap(out, o_bytes, W_root, w_bytes))))
-        return GESPMM_EINVAL;
-    if (!gespmm::spmm_relational_f32_served(R, M, Kn, K, N_out, nnz, align)) return GESPMM_ERR_UNSUPPORTED;  // (nothing launched)
-    gespmm::SpmmRelationalF32Args a = {};
-    a.rowptr = rowptr;
-    a.colind = colind;
-    a.val = nnz != 0 ? val : nullptr;
-    a.row_scale = row_scale;
-    a.X = X;
-    a.W = W;
-    a.Xroot = X_root;
-    a.Wroot = W_root;
-    a.bias = bias;
-    a.out = out;
-    a.R = (int32_t)R;
-    a.M = (int32_t)M;
-    a.K = (int32_t)K;
-    a.N_out = (int32_t)N_out;
-    return (int)gespmm::launch_spmm_relational_f32(a, reinterpret_cast<hipStream_t>(stream));
+    return linear_forward<gespmm::SpmmRelationalF32Args>(
+        {rowptr, colind, val, row_scale, X, W, X_root, W_root, bias, out, R, M, Kn, K, N_out, nnz}, 4, GESPMM_EALIGN,
+        [&](int align) { return gespmm::spmm_relational_f32_served(R, M, Kn, K, N_out, nnz, align); },
+        [&](gespmm::SpmmRelationalF32Args& a) {
+            a.R = (int32_t)R;
+            return gespmm::launch_spmm_relational_f32(a, reinterpret_cast<hipStream_t>(stream));
+        });
 }
 
 int gespmm_spmm_relational_route_f32(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int align) {
-    if (align < 4 || (align & (align - 1)) != 0) return GESPMM_EINVAL;
-    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
-    if (rc != 0) return rc;
-    return gespmm::spmm_relational_f32_served(R, M, Kn, K, N_out, nnz, align) ? 1 : 0;
+    return served_route(align, 4, gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz),
+                        gespmm::spmm_relational_f32_served(R, M, Kn, K, N_out, nnz, align));
 }
 
 /* The fused relational weight gradient on 16-bit features (gespmm.h; spmm_relational_wgrad.hip): grad_W[r] = grad_out^T @ H_r over the
@@ -1240,10 +1216,8 @@ int gespmm_csr_spmm_relational_wgrad_x16(const int32_t* rowptr, const int32_t* c
 }
 
 int gespmm_spmm_relational_wgrad_route_x16(int64_t R, int64_t M, int64_t Kn, int64_t K, int64_t N_out, int64_t nnz, int64_t chunks, int align) {
-    if (align < 2 || (align & (align - 1)) != 0) return GESPMM_EINVAL;
-    const int rc = gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz);
-    if (rc != 0) return rc;
-    return gespmm::spmm_relational_wgrad_served(R, M, Kn, K, N_out, nnz, chunks, align) ? 1 : 0;
+    return served_route(align, 2, gespmm::spmm_relational_sizes(R, M, Kn, K, N_out, nnz),
+                        gespmm::spmm_relational_wgrad_served(R, M, Kn, K, N_out, nnz, chunks, align));
 }
 
 int64_t gespmm_spmm_relational_wgrad_chunks(int64_t R, int64_t M, int64_t K, int64_t N_out) {

@@ -24,9 +24,9 @@ struct SpmmLinearArgs {
     const float* val;        // [nnz] or NULL: A == 1 on its pattern
     const float* row_scale;  // [M] or NULL
     const float* X;          // [Kn, K] 16-bit elements, seen as words
-    const void* Wn;          // [N_out, K]
+    const void* W;           // [N_out, K]: W_n
     const void* Xroot;       // [M, K] or NULL
-    const void* Wr;          // [N_out, K] or NULL (with Xroot)
+    const void* Wroot;       // [N_out, K] or NULL (with Xroot): W_r
     const float* bias;       // [N_out] or NULL
     void* out;               // [M, N_out]
     int32_t M, K, N_out;

@@ -21,31 +21,10 @@
 // No scratch, no atomics, no allocation: {fp16, bf16} x {valued, unweighted} x six lane geometries = 24 kernels. Compiled without
 // packed fp32 arithmetic.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "spmm_device.h"
 #include "spmm_linear.h"
+#include "spmm_tile_mfma.h"
 
 namespace gespmm {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ floatx16 mfma_32x32x16(uint4 a, uint4 b, floatx16 c) {
-    if constexpr (DT == kX16F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(halfx8, a), __builtin_bit_cast(halfx8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// x as a finished fp32 value in a register. Without it the compiler merges an fp32 multiply (or add) with the fp16 rounding behind it
-// into ONE operation that rounds the exact result straight to fp16 (v_fma_mixlo_f16): the fp32 rounding skipped, and an element that
-// differs from the 16-bit product's wherever fl32 lands on an fp16 tie.
-__device__ __forceinline__ float fl32(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
 
 template <int DT, bool VALUED, int W, int WPL>
 __global__ __launch_bounds__(kThreads) void spmm_linear_kernel(const SpmmLinearArgs a) {
@@ -137,8 +116,8 @@ __global__ __launch_bounds__(kThreads) void spmm_linear_kernel(const SpmmLinearA
     const int Kp = Kpw * 2;
     const int stride_b = stride_w * 4;
     const int nslab = (a.N_out + 31) >> 5;
-    const uint16_t* Wn = static_cast<const uint16_t*>(a.Wn);
-    const uint16_t* Wr = static_cast<const uint16_t*>(a.Wr);
+    const uint16_t* Wn = static_cast<const uint16_t*>(a.W);
+    const uint16_t* Wr = static_cast<const uint16_t*>(a.Wroot);
     const uint16_t* Xr = static_cast<const uint16_t*>(a.Xroot);
     uint16_t* out = static_cast<uint16_t*>(a.out);
     const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
@@ -199,24 +178,13 @@ static hipError_t launch_linear(const SpmmLinearArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int DT, bool VALUED>
-static hipError_t launch_linear_geometry(const SpmmLinearArgs& a, hipStream_t st) {
-    const int Kw = a.K / 2;  // words per row: the smallest lane group that covers them, two words per lane beyond 64
-    if (Kw > 64) return launch_linear<DT, VALUED, 64, 2>(a, st);
-    if (Kw > 32) return launch_linear<DT, VALUED, 64, 1>(a, st);
-    if (Kw > 16) return launch_linear<DT, VALUED, 32, 1>(a, st);
-    if (Kw > 8) return launch_linear<DT, VALUED, 16, 1>(a, st);
-    if (Kw > 4) return launch_linear<DT, VALUED, 8, 1>(a, st);
-    return launch_linear<DT, VALUED, 4, 1>(a, st);
-}
-
 hipError_t launch_spmm_linear_x16(const SpmmLinearArgs& a, int dtype, hipStream_t st) {
     if (!spmm_linear_served(a.M, 0, a.K, a.N_out, 0, 16)) return hipErrorInvalidValue;
-    if (dtype == kX16F16)
-        return a.val != nullptr ? launch_linear_geometry<kX16F16, true>(a, st) : launch_linear_geometry<kX16F16, false>(a, st);
-    if (dtype == kX16Bf16)
-        return a.val != nullptr ? launch_linear_geometry<kX16Bf16, true>(a, st) : launch_linear_geometry<kX16Bf16, false>(a, st);
-    return hipErrorInvalidValue;
+    return dispatch_x16_valued(dtype, a.val != nullptr, [&](auto dt, auto valued) {
+        return dispatch_lane_group<kLinearMaxK / 2>(a.K / 2, [&](auto w, auto wpl) {  // words per row
+            return launch_linear<decltype(dt)::value, decltype(valued)::value, decltype(w)::value, decltype(wpl)::value>(a, st);
+        });
+    });
 }
 
 }  // namespace gespmm

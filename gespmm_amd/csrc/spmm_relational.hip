@@ -22,30 +22,10 @@
 // packed fp32 arithmetic. GESPMM_RELATIONAL_DEAD_GATHERS (measurement only, never in the shipped library) issues every gather
 // unconditionally, as spmm_linear.hip does.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "spmm_device.h"
 #include "spmm_relational.h"
+#include "spmm_tile_mfma.h"
 
 namespace gespmm {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ floatx16 rel_mfma_32x32x16(uint4 a, uint4 b, floatx16 c) {
-    if constexpr (DT == kX16F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(halfx8, a), __builtin_bit_cast(halfx8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-// x as a finished fp32 value in a register: keeps the compiler from merging an fp32 multiply (or add) with the fp16 rounding behind it
-// into one operation that skips the fp32 rounding (spmm_linear.hip).
-__device__ __forceinline__ float rel_fl32(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
 
 template <int DT, bool VALUED, int W, int WPL, int NS>
 __global__ __launch_bounds__(kThreads) void spmm_relational_kernel(const SpmmRelationalArgs a) {
@@ -167,7 +147,7 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_kernel(const SpmmRel
 #pragma unroll
             for (int i = 0; i < WPL; ++i)
                 if (wok[i])
-                    trow[wi[i]] = narrow_x16<DT>(rel_fl32(__fmul_rn(sum[2 * i], rs))) | (narrow_x16<DT>(rel_fl32(__fmul_rn(sum[2 * i + 1], rs))) << 16);
+                    trow[wi[i]] = narrow_x16<DT>(fl32(__fmul_rn(sum[2 * i], rs))) | (narrow_x16<DT>(fl32(__fmul_rn(sum[2 * i + 1], rs))) << 16);
         }
         __syncthreads();
 
@@ -183,8 +163,8 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_kernel(const SpmmRel
                     if (!sok[s]) continue;
                     uint4 bf = zero;
                     if (nok[s] && k < a.K) bf = *reinterpret_cast<const uint4*>(Wn + n[s] * a.K + k);
-                    acc[s][0] = rel_mfma_32x32x16<DT>(a0, bf, acc[s][0]);
-                    acc[s][1] = rel_mfma_32x32x16<DT>(a1, bf, acc[s][1]);
+                    acc[s][0] = mfma_32x32x16<DT>(a0, bf, acc[s][0]);
+                    acc[s][1] = mfma_32x32x16<DT>(a1, bf, acc[s][1]);
                 }
             }
         }
@@ -209,8 +189,8 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_kernel(const SpmmRel
                 if (!sok[s]) continue;
                 uint4 bf = zero;
                 if (nok[s] && k < a.K) bf = *reinterpret_cast<const uint4*>(Wr + n[s] * a.K + k);
-                acc[s][0] = rel_mfma_32x32x16<DT>(a0, bf, acc[s][0]);
-                acc[s][1] = rel_mfma_32x32x16<DT>(a1, bf, acc[s][1]);
+                acc[s][0] = mfma_32x32x16<DT>(a0, bf, acc[s][0]);
+                acc[s][1] = mfma_32x32x16<DT>(a1, bf, acc[s][1]);
             }
         }
     }
@@ -224,8 +204,8 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_kernel(const SpmmRel
             const int r = row0 + 8 * (v / 4) + 4 * kh + (v % 4);
             float x0 = acc[s][0][v], x1 = acc[s][1][v];
             if (has_bias) {  // (NULL skips the add: x + 0.0f would turn -0.0 into +0.0)
-                x0 = rel_fl32(__fadd_rn(x0, bv));
-                x1 = rel_fl32(__fadd_rn(x1, bv));
+                x0 = fl32(__fadd_rn(x0, bv));
+                x1 = fl32(__fadd_rn(x1, bv));
             }
             if (nok[s] && r < a.M) out[(uint32_t)r * (uint32_t)a.N_out + n[s]] = (uint16_t)narrow_x16<DT>(x0);
             if (nok[s] && r + 32 < a.M) out[(uint32_t)(r + 32) * (uint32_t)a.N_out + n[s]] = (uint16_t)narrow_x16<DT>(x1);
@@ -243,24 +223,13 @@ static hipError_t launch_relational(const SpmmRelationalArgs& a, hipStream_t st)
     return hipGetLastError();
 }
 
-template <int DT, bool VALUED>
-static hipError_t launch_relational_geometry(const SpmmRelationalArgs& a, hipStream_t st) {
-    const int Kw = a.K / 2;  // words per row: the smallest lane group that covers them, two words per lane beyond 64
-    if (Kw > 64) return launch_relational<DT, VALUED, 64, 2>(a, st);
-    if (Kw > 32) return launch_relational<DT, VALUED, 64, 1>(a, st);
-    if (Kw > 16) return launch_relational<DT, VALUED, 32, 1>(a, st);
-    if (Kw > 8) return launch_relational<DT, VALUED, 16, 1>(a, st);
-    if (Kw > 4) return launch_relational<DT, VALUED, 8, 1>(a, st);
-    return launch_relational<DT, VALUED, 4, 1>(a, st);
-}
-
 hipError_t launch_spmm_relational_x16(const SpmmRelationalArgs& a, int dtype, hipStream_t st) {
     if (!spmm_relational_served(a.R, a.M, 0, a.K, a.N_out, 0, 16)) return hipErrorInvalidValue;
-    if (dtype == kX16F16)
-        return a.val != nullptr ? launch_relational_geometry<kX16F16, true>(a, st) : launch_relational_geometry<kX16F16, false>(a, st);
-    if (dtype == kX16Bf16)
-        return a.val != nullptr ? launch_relational_geometry<kX16Bf16, true>(a, st) : launch_relational_geometry<kX16Bf16, false>(a, st);
-    return hipErrorInvalidValue;
+    return dispatch_x16_valued(dtype, a.val != nullptr, [&](auto dt, auto valued) {
+        return dispatch_lane_group<kLinearMaxK / 2>(a.K / 2, [&](auto w, auto wpl) {  // words per row
+            return launch_relational<decltype(dt)::value, decltype(valued)::value, decltype(w)::value, decltype(wpl)::value>(a, st);
+        });
+    });
 }
 
 }  // namespace gespmm

@@ -1,6 +1,6 @@
 // spmm_relational_f32.hip — relational aggregate-and-linear on fp32 features (spmm_relational_f32.h): one 256-thread workgroup per 64
 // consecutive output rows, a loop over the R relations of a stacked CSR, one fp32 LDS tile and one set of matrix-unit accumulators.
-// Self-contained: the 16-bit kernels (spmm_relational.hip) pack two elements per word and feed v_mfma_f32_32x32x16; here a lane holds a
+// Its own body: the 16-bit kernels (spmm_relational.hip) pack two elements per word and feed v_mfma_f32_32x32x16; here a lane holds a
 // float4 of a row, the tile is fp32 and the matrix instruction is v_mfma_f32_32x32x2_f32, whose fragment is ONE k per lane.
 //
 // Per relation r, two phases between two barriers — unless the block has no entry of r: rowptr[r M + row0] == rowptr[r M + rend] is
@@ -24,21 +24,15 @@
 // No scratch, no atomics, no allocation: {valued, unweighted} x five lane geometries x NS = 20 kernels. The tile is static LDS, sized
 // by the geometry's K_pad class (<= 64, <= 128, <= 256). Compiled without packed fp32 arithmetic.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "spmm_device.h"
 #include "spmm_relational_f32.h"
+#include "spmm_tile_mfma.h"
 
 namespace gespmm {
-
-typedef float relf_x16 __attribute__((ext_vector_type(16)));
-typedef float relf_x4 __attribute__((ext_vector_type(4)));
 
 constexpr int rel_f32_kpad_class(int W) { return W <= 16 ? 64 : (W == 32 ? 128 : 256); }
 
 // four MFMAs of one k step: component j of a and b is the lane's ONE k of the j-th instruction
-__device__ __forceinline__ relf_x16 rel_f32_mfma4(relf_x4 a, relf_x4 b, relf_x16 c) {
+__device__ __forceinline__ floatx16 rel_f32_mfma4(floatx4 a, floatx4 b, floatx16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], b[1], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], b[2], c, 0, 0, 0);
@@ -62,17 +56,17 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_f32_kernel(const Spm
     const int rend = row0 + kLinearBlockRows < a.M ? row0 + kLinearBlockRows : a.M;
     const bool wok = 4 * l < a.K;        // the lane holds a float4 of the row
     const int xoff = wok ? 4 * l : 0;    // (a masked lane reads the row's first vector and drops it)
-    const relf_x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
+    const floatx4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
 
     // columns K .. K_pad - 1 of the tile (one float4, when K % 8 == 4) are zero for every relation: written once, by the first masked lane
     if (4 * l == a.K && a.K < Kp)
-        for (int b = 0; b < 16; b += G) *reinterpret_cast<relf_x4*>(tile + (wave * 16 + b + g) * stride + a.K) = zero4;
+        for (int b = 0; b < 16; b += G) *reinterpret_cast<floatx4*>(tile + (wave * 16 + b + g) * stride + a.K) = zero4;
 
     const int li = lane & 31, kh = lane >> 5;
     const int nslab = (a.N_out + 31) >> 5;
     int n[NS];
     bool nok[NS], sok[NS];  // sok: the wavefront has this slab at all (wave-uniform)
-    relf_x16 acc[NS][2];
+    floatx16 acc[NS][2];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         n[s] = (wave + kWaves * s) * 32 + li;
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_f32_kernel(const Spm
                 for (int s = 0; s < T; s += U) {
                     if (__builtin_amdgcn_ballot_w64(s < cnt) == 0) break;  // past the wavefront's largest remaining count
                     float v[U];
-                    relf_x4 xv[U];
+                    floatx4 xv[U];
 #pragma unroll
                     for (int j = 0; j < U; ++j) {
                         const int e = (E == 1) ? 0 : j / W;  // (W = 4: one step of eight, entry j in slot j / 4 of lane j % 4)
@@ -130,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_f32_kernel(const Spm
                         if constexpr (VALUED) v[j] = __shfl(pv[e], src, W);
                         else v[j] = 1.0f;
                         xv[j] = zero4;
-                        if (s + j < cnt) xv[j] = *reinterpret_cast<const relf_x4*>(a.X + (uint32_t)c * (uint32_t)a.K + xoff);  // (Kn K <= 2^31 - 4097)
+                        if (s + j < cnt) xv[j] = *reinterpret_cast<const floatx4*>(a.X + (uint32_t)c * (uint32_t)a.K + xoff);  // (Kn K <= 2^31 - 4097)
                     }
 #pragma unroll
                     for (int j = 0; j < U; ++j)
@@ -143,10 +137,10 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_f32_kernel(const Spm
             }
 
             if (wok) {
-                relf_x4 h;
+                floatx4 h;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) h[i] = __fmul_rn(sum[i], rs);
-                *reinterpret_cast<relf_x4*>(tile + tr * stride + 4 * l) = h;  // (rows >= M: zeros)
+                *reinterpret_cast<floatx4*>(tile + tr * stride + 4 * l) = h;  // (rows >= M: zeros)
             }
         }
         __syncthreads();
@@ -156,13 +150,13 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_f32_kernel(const Spm
         if (sok[0]) {
             for (int k0 = 0; k0 < Kp; k0 += 8) {
                 const int k = k0 + 4 * kh;
-                const relf_x4 a0 = *reinterpret_cast<const relf_x4*>(tile + li * stride + k);
-                const relf_x4 a1 = *reinterpret_cast<const relf_x4*>(tile + (32 + li) * stride + k);
+                const floatx4 a0 = *reinterpret_cast<const floatx4*>(tile + li * stride + k);
+                const floatx4 a1 = *reinterpret_cast<const floatx4*>(tile + (32 + li) * stride + k);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
                     if (!sok[s]) continue;
-                    relf_x4 bf = zero4;
-                    if (nok[s] && k < a.K) bf = *reinterpret_cast<const relf_x4*>(Wn + n[s] * a.K + k);
+                    floatx4 bf = zero4;
+                    if (nok[s] && k < a.K) bf = *reinterpret_cast<const floatx4*>(Wn + n[s] * a.K + k);
                     acc[s][0] = rel_f32_mfma4(a0, bf, acc[s][0]);
                     acc[s][1] = rel_f32_mfma4(a1, bf, acc[s][1]);
                 }
@@ -176,16 +170,16 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_f32_kernel(const Spm
         const int r0 = row0 + li, r1 = r0 + 32;
         for (int k0 = 0; k0 < Kp; k0 += 8) {
             const int k = k0 + 4 * kh;
-            relf_x4 a0 = zero4, a1 = zero4;
+            floatx4 a0 = zero4, a1 = zero4;
             if (k < a.K) {
-                if (r0 < a.M) a0 = *reinterpret_cast<const relf_x4*>(a.Xroot + (uint32_t)r0 * (uint32_t)a.K + k);
-                if (r1 < a.M) a1 = *reinterpret_cast<const relf_x4*>(a.Xroot + (uint32_t)r1 * (uint32_t)a.K + k);
+                if (r0 < a.M) a0 = *reinterpret_cast<const floatx4*>(a.Xroot + (uint32_t)r0 * (uint32_t)a.K + k);
+                if (r1 < a.M) a1 = *reinterpret_cast<const floatx4*>(a.Xroot + (uint32_t)r1 * (uint32_t)a.K + k);
             }
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 if (!sok[s]) continue;
-                relf_x4 bf = zero4;
-                if (nok[s] && k < a.K) bf = *reinterpret_cast<const relf_x4*>(a.Wroot + n[s] * a.K + k);
+                floatx4 bf = zero4;
+                if (nok[s] && k < a.K) bf = *reinterpret_cast<const floatx4*>(a.Wroot + n[s] * a.K + k);
                 acc[s][0] = rel_f32_mfma4(a0, bf, acc[s][0]);
                 acc[s][1] = rel_f32_mfma4(a1, bf, acc[s][1]);
             }
@@ -218,19 +212,11 @@ static hipError_t launch_relational_f32(const SpmmRelationalF32Args& a, hipStrea
     return hipGetLastError();
 }
 
-template <bool VALUED>
-static hipError_t launch_relational_f32_geometry(const SpmmRelationalF32Args& a, hipStream_t st) {
-    const int Kv = a.K / 4;  // float4 vectors per row: the smallest lane group that covers them
-    if (Kv > 32) return launch_relational_f32<VALUED, 64>(a, st);
-    if (Kv > 16) return launch_relational_f32<VALUED, 32>(a, st);
-    if (Kv > 8) return launch_relational_f32<VALUED, 16>(a, st);
-    if (Kv > 4) return launch_relational_f32<VALUED, 8>(a, st);
-    return launch_relational_f32<VALUED, 4>(a, st);
-}
-
 hipError_t launch_spmm_relational_f32(const SpmmRelationalF32Args& a, hipStream_t st) {
     if (!spmm_relational_f32_served(a.R, a.M, 0, a.K, a.N_out, 0, 16)) return hipErrorInvalidValue;
-    return a.val != nullptr ? launch_relational_f32_geometry<true>(a, st) : launch_relational_f32_geometry<false>(a, st);
+    return dispatch_lane_group<kRelF32MaxK / 4>(a.K / 4, [&](auto w, auto) {  // float4 vectors per row
+        return a.val != nullptr ? launch_relational_f32<true, decltype(w)::value>(a, st) : launch_relational_f32<false, decltype(w)::value>(a, st);
+    });
 }
 
 }  // namespace gespmm

@@ -23,30 +23,10 @@
 // partials in the order c = 0 .. C - 1 in fp32 and rounds once. No scratch, no atomics, no allocation: {fp16, bf16} x {valued,
 // unweighted} x four lane geometries x NS = 32 kernels and two reductions. Compiled without packed fp32 arithmetic.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "spmm_device.h"
 #include "spmm_relational_wgrad.h"
+#include "spmm_tile_mfma.h"
 
 namespace gespmm {
-
-typedef float wg_floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 wg_halfx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-
-template <int DT>
-__device__ __forceinline__ wg_floatx16 wg_mfma_32x32x16(uint4 a, uint4 b, wg_floatx16 c) {
-    if constexpr (DT == kX16F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(wg_halfx8, a), __builtin_bit_cast(wg_halfx8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, a), __builtin_bit_cast(wg_bf16x8, b), c, 0, 0, 0);
-}
-
-// x as a finished fp32 value in a register: keeps the compiler from merging an fp32 multiply (or add) with the fp16 rounding behind it
-// into one operation that skips the fp32 rounding (spmm_linear.hip).
-__device__ __forceinline__ float wg_fl32(float x) {
-    asm volatile("" : "+v"(x));
-    return x;
-}
 
 // The block's grad_out tile, rows row0 .. row0 + 63 of [M, N_out] (contiguous in memory: 64 N_out elements), into GT[n][i]: V elements
 // per load (V divides N_out, so a load stays inside a row and is V * 2 bytes aligned), consecutive threads consecutive addresses.
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_wgrad_kernel(const S
     const int nslab = (a.N_out + 31) >> 5;
     const bool two = SW > 32;  // the slab has a second 32-column half (workgroup-uniform)
     bool sok[NS];              // the wavefront has this slab of grad_W[r] at all (wave-uniform)
-    wg_floatx16 acc[NS][2];
+    floatx16 acc[NS][2];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         sok[s] = wave + kWaves * s < nslab;
@@ -182,8 +162,8 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_wgrad_kernel(const S
             }
 
             if (wok) {  // rows >= M of the block are written too, as zeros: the reduction runs over all 64
-                HT[(2 * l) * kWgradStride + tr] = (uint16_t)narrow_x16<DT>(wg_fl32(__fmul_rn(sum[0], rs)));
-                HT[(2 * l + 1) * kWgradStride + tr] = (uint16_t)narrow_x16<DT>(wg_fl32(__fmul_rn(sum[1], rs)));
+                HT[(2 * l) * kWgradStride + tr] = (uint16_t)narrow_x16<DT>(fl32(__fmul_rn(sum[0], rs)));
+                HT[(2 * l + 1) * kWgradStride + tr] = (uint16_t)narrow_x16<DT>(fl32(__fmul_rn(sum[1], rs)));
             }
         }
         if (gvec == 8) wg_stage_grad_out<8>(go, GT, row0, a.M, a.N_out);
@@ -204,8 +184,8 @@ __global__ __launch_bounds__(kThreads) void spmm_relational_wgrad_kernel(const S
                 for (int s = 0; s < NS; ++s) {
                     if (!sok[s]) continue;
                     const uint4 af = *reinterpret_cast<const uint4*>(GT + ((wave + kWaves * s) * 32 + li) * kWgradStride + i0);
-                    acc[s][0] = wg_mfma_32x32x16<DT>(af, b0, acc[s][0]);
-                    if (two) acc[s][1] = wg_mfma_32x32x16<DT>(af, b1, acc[s][1]);
+                    acc[s][0] = mfma_32x32x16<DT>(af, b0, acc[s][0]);
+                    if (two) acc[s][1] = mfma_32x32x16<DT>(af, b1, acc[s][1]);
                 }
             }
         }
@@ -241,8 +221,8 @@ __global__ __launch_bounds__(kThreads) void wgrad_reduce_kernel(const float4* __
         s.z = __fadd_rn(s.z, p.z);
         s.w = __fadd_rn(s.w, p.w);
     }
-    out[idx] = make_uint2(narrow_x16<DT>(wg_fl32(s.x)) | (narrow_x16<DT>(wg_fl32(s.y)) << 16),
-                          narrow_x16<DT>(wg_fl32(s.z)) | (narrow_x16<DT>(wg_fl32(s.w)) << 16));
+    out[idx] = make_uint2(narrow_x16<DT>(fl32(s.x)) | (narrow_x16<DT>(fl32(s.y)) << 16),
+                          narrow_x16<DT>(fl32(s.z)) | (narrow_x16<DT>(fl32(s.w)) << 16));
 }
 
 template <int DT, bool VALUED, int W>
@@ -261,22 +241,14 @@ static hipError_t launch_wgrad(const SpmmRelationalWgradArgs& a, hipStream_t st)
     return hipGetLastError();
 }
 
-template <int DT, bool VALUED>
-static hipError_t launch_wgrad_geometry(const SpmmRelationalWgradArgs& a, hipStream_t st) {
-    const int Sw = (a.K < kWgradSlab ? a.K : kWgradSlab) / 2;  // words of the widest slab: the smallest lane group that covers them
-    if (Sw > 16) return launch_wgrad<DT, VALUED, 32>(a, st);
-    if (Sw > 8) return launch_wgrad<DT, VALUED, 16>(a, st);
-    if (Sw > 4) return launch_wgrad<DT, VALUED, 8>(a, st);
-    return launch_wgrad<DT, VALUED, 4>(a, st);
-}
-
 hipError_t launch_spmm_relational_wgrad_x16(const SpmmRelationalWgradArgs& a, int dtype, hipStream_t st) {
     if (!spmm_relational_wgrad_served(a.R, a.M, 0, a.K, a.N_out, 0, a.C, 16)) return hipErrorInvalidValue;
-    if (dtype == kX16F16)
-        return a.val != nullptr ? launch_wgrad_geometry<kX16F16, true>(a, st) : launch_wgrad_geometry<kX16F16, false>(a, st);
-    if (dtype == kX16Bf16)
-        return a.val != nullptr ? launch_wgrad_geometry<kX16Bf16, true>(a, st) : launch_wgrad_geometry<kX16Bf16, false>(a, st);
-    return hipErrorInvalidValue;
+    const int Sw = (a.K < kWgradSlab ? a.K : kWgradSlab) / 2;  // words of the widest slab
+    return dispatch_x16_valued(dtype, a.val != nullptr, [&](auto dt, auto valued) {
+        return dispatch_lane_group<kWgradSlab / 2>(Sw, [&](auto w, auto) {
+            return launch_wgrad<decltype(dt)::value, decltype(valued)::value, decltype(w)::value>(a, st);
+        });
+    });
 }
 
 }  // namespace gespmm
